@@ -3,7 +3,7 @@
 bench.py -- headline benchmark: Mcell.steps/s of the classic dimension-split step on the
 2-D Euler shock-bubble problem (BASELINE.json configs[2]: 4096 x 4096 cells on one MI355X).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--nx 4096 --ny 4096]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--nx 4096 --ny 4096] [--dump-outputs DIR]
 
 One "step" = one accepted pass of the hot path on the block resident in HBM: ghost-cell
 fill (+ halo exchange when N > 1), x sweep, y sweep, device CFL reduction, the 8-byte CFL
@@ -386,6 +386,35 @@ def state_object(tag, claw, steps, warmup, cells_total, bytes_launch, describe):
             "avg_ms": lab, "result_finite": fin}
 
 
+DUMP_BYTES = 64 * 10 ** 6      # --dump-outputs: at most this much in all
+DUMP_SEED = 20240601           # the fixed sample of cells written when q is larger than that
+
+
+def dump_outputs(directory, claw, rank, size):
+    """Write what the timed path returned to its caller after its last step: solution.state.q (meqn x cells,
+    float64) and the step status (t, dtmin, dtmax, cflmax of the last evolve_to_time call).  q is written whole as
+    q.npy when it fits the budget; otherwise a fixed, seeded sample of cells: q_sample.npy (meqn x n, cells in
+    increasing flat C-order index) and q_sample_cells.npy (those flat indices, as float64).  With several ranks every
+    rank writes its own block under a rank<r>_ prefix and the budget is shared."""
+    os.makedirs(directory, exist_ok=True)
+    pre = "rank%d_" % rank if size > 1 else ""
+    sol, st = claw.solution, claw.solver.status
+    np.save(os.path.join(directory, pre + "status.npy"),
+            np.array([sol.t, st["dtmin"], st["dtmax"], st["cflmax"]], dtype=np.float64))
+    q = sol.state.q
+    budget = DUMP_BYTES // size - 4096
+    if q.nbytes <= budget:
+        np.save(os.path.join(directory, pre + "q.npy"), np.ascontiguousarray(q, dtype=np.float64))
+        return
+    cells = q.shape[1:]
+    ncell = int(np.prod(cells))
+    n = min(ncell, budget // (8 * (q.shape[0] + 1)))
+    flat = np.sort(np.random.default_rng(DUMP_SEED).choice(ncell, n, replace=False))
+    sample = q[(slice(None),) + np.unravel_index(flat, cells)]
+    np.save(os.path.join(directory, pre + "q_sample.npy"), np.ascontiguousarray(sample, dtype=np.float64))
+    np.save(os.path.join(directory, pre + "q_sample_cells.npy"), flat.astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -418,7 +447,12 @@ def main():
                     help="--solver sharpclaw: with the app's radial source (dq_src) evaluated inside the last pass")
     ap.add_argument("--ndim", type=int, default=2, choices=[2, 3],
                     help="3: 3-D dim-split acoustics on an nx^3 grid (single GPU; not the headline)")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step (the state q, "
+                         "whole or a fixed seeded sample, and the step status) to DIR/<name>.npy, at most 64 MB")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     from pyclaw_amd import parallel, _lib
     # a multi-GPU run whose RCCL set-up fails on this node still produces a (slow, clearly labelled) line over the
@@ -477,6 +511,8 @@ def main():
         args.no_states = True
     elapsed, ms, nl, finite = timed_run(claw, args.steps, args.warmup)
     attempted = timed_run.attempted
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, claw, rank, size)
 
     cells_total = float(nxg) * float(nyg) * (float(args.nx * dims[2]) if args.ndim == 3 else 1.0)
     value = cells_total * args.steps / elapsed / 1e6

@@ -1,15 +1,15 @@
 """
 CPU: the oracle's C restatement against the REFERENCE'S OWN FORTRAN (oracle/_ref, flang build of
 step2ds.f/step2.f/flux2.f/limiter.f/philim.f + the vendored Euler 5-wave solvers) on seeded
-random inputs -- bit for bit.  Skipped where oracle/_ref has not been built (it needs the
-reference tree; the GPU box only has the prebuilt file).
+random inputs -- bit for bit.  What the reference build returns for every case is pinned in
+tests/golden/ref_pins.json (tests/ref_pins.py), so the comparison runs where oracle/_ref has not
+been built (it needs the reference tree); where it has, the live build is compared as well.
 """
 import numpy as np
 import pytest
 
+import ref_pins as P
 from oracle import oracle as O
-
-pytestmark = pytest.mark.skipif(not O.RefEuler2D.available(), reason="oracle/_ref not built")
 
 
 def euler_state(rng, shape, strong=False):
@@ -34,7 +34,7 @@ def euler_state(rng, shape, strong=False):
 
 @pytest.fixture(scope="module")
 def ref():
-    return O.RefEuler2D()
+    return O.RefEuler2D() if O.RefEuler2D.available() else None
 
 
 @pytest.mark.parametrize("mx,my", [(5, 3), (40, 23), (97, 64)])
@@ -48,13 +48,18 @@ def test_step2ds_matches_reference(coracle, ref, mx, my, strong, order, mth):
     method = np.array([1, order, -1, 0, 0, 0, 0], dtype=np.int32)
     dx, dy, dt = 1.0 / mx, 1.0 / my, 0.1 / max(mx, my)
     for ids in (1, 2):
+        key = "step2ds/%dx%d/strong%d/order%d/mth%s/ids%d" % (mx, my, strong, order, "".join(map(str, mth)), ids)
         a = q0.copy("F")
         b = q0.copy("F")
         _, ca = coracle.step2ds(O.RP_EULER5_2D, par, max(mx, my), mbc, mx, my, q0.copy("F"), a, None, dx,
                                 dy, dt, method, mth, ids)
-        _, cb = ref.step2ds(O.RP_EULER5_2D, par, max(mx, my), mbc, mx, my, q0.copy("F"), b, None, dx, dy,
-                            dt, method, mth, ids)
-        assert np.array_equal(a, b) and ca == cb
+        assert not np.isnan(a).any()
+        P.check(key, a, ca)
+        if ref is not None:
+            _, cb = ref.step2ds(O.RP_EULER5_2D, par, max(mx, my), mbc, mx, my, q0.copy("F"), b, None, dx, dy,
+                                dt, method, mth, ids)
+            P.record(key, b, cb)
+            assert np.array_equal(a, b) and ca == cb
 
 
 @pytest.mark.parametrize("mx,my", [(6, 4), (33, 50)])
@@ -68,13 +73,18 @@ def test_step2_unsplit_matches_reference(coracle, ref, mx, my, trans, strong):
     mth = [4, 4, 4, 4, 2]
     method = np.array([1, 2, trans, 0, 0, 0, 0], dtype=np.int32)
     dx, dy, dt = 1.0 / mx, 1.0 / my, 0.05 / max(mx, my)
+    key = "step2/%dx%d/trans%d/strong%d" % (mx, my, trans, strong)
     a = q0.copy("F")
     b = q0.copy("F")
     _, ca = coracle.step2(O.RP_EULER5_2D, par, max(mx, my), mbc, mx, my, q0.copy("F"), a, None, dx, dy, dt,
                           method, mth)
-    _, cb = ref.step2(O.RP_EULER5_2D, par, max(mx, my), mbc, mx, my, q0.copy("F"), b, None, dx, dy, dt,
-                      method, mth)
-    assert np.array_equal(a, b) and ca == cb
+    assert not np.isnan(a).any()
+    P.check(key, a, ca)
+    if ref is not None:
+        _, cb = ref.step2(O.RP_EULER5_2D, par, max(mx, my), mbc, mx, my, q0.copy("F"), b, None, dx, dy, dt,
+                          method, mth)
+        P.record(key, b, cb)
+        assert np.array_equal(a, b) and ca == cb
 
 
 @pytest.mark.parametrize("unsplit", [False, True])
@@ -92,43 +102,55 @@ def test_capa_matches_reference(coracle, ref, unsplit):
     b = q0.copy("F")
     if unsplit:
         _, ca = coracle.step2(O.RP_EULER5_2D, par, mx, mbc, mx, my, q0.copy("F"), a, aux, dx, dy, dt, method, mth)
-        _, cb = ref.step2(O.RP_EULER5_2D, par, mx, mbc, mx, my, q0.copy("F"), b, aux, dx, dy, dt, method, mth)
-        assert np.array_equal(a, b) and ca == cb
+        assert not np.isnan(a).any()
+        P.check("capa/unsplit", a, ca)
+        if ref is not None:
+            _, cb = ref.step2(O.RP_EULER5_2D, par, mx, mbc, mx, my, q0.copy("F"), b, aux, dx, dy, dt, method, mth)
+            P.record("capa/unsplit", b, cb)
+            assert np.array_equal(a, b) and ca == cb
     else:
         for ids in (1, 2):
             _, ca = coracle.step2ds(O.RP_EULER5_2D, par, mx, mbc, mx, my, q0.copy("F"), a, aux, dx, dy, dt,
                                     method, mth, ids)
-            _, cb = ref.step2ds(O.RP_EULER5_2D, par, mx, mbc, mx, my, q0.copy("F"), b, aux, dx, dy, dt,
-                                method, mth, ids)
-            assert np.array_equal(a, b) and ca == cb
+            assert not np.isnan(a).any()
+            P.check("capa/dimsplit/ids%d" % ids, a, ca)
+            if ref is not None:
+                _, cb = ref.step2ds(O.RP_EULER5_2D, par, mx, mbc, mx, my, q0.copy("F"), b, aux, dx, dy, dt,
+                                    method, mth, ids)
+                P.record("capa/dimsplit/ids%d" % ids, b, cb)
+                assert np.array_equal(a, b) and ca == cb
 
 
-@pytest.mark.skipif(not O.RefSharp2DEuler.available(), reason="oracle/_ref sharpclaw not built")
 @pytest.mark.parametrize("mx,my", [(7, 5), (37, 29), (64, 90)])
 @pytest.mark.parametrize("lim", [2, 3])
 def test_sharpclaw_flux2_matches_reference(coracle, mx, my, lim):
     """C restatement of flux2/flux1/weno5 == the reference's SharpClaw modules (flang), bit for bit"""
-    ref = O.RefSharp2DEuler()
+    ref = O.RefSharp2DEuler() if O.RefSharp2DEuler.available() else None
     rng = np.random.default_rng(mx + my)
     mbc = 3
     q = euler_state(rng, (mx + 2 * mbc, my + 2 * mbc), strong=(mx == 37))
     par = [1.4, 0.4]
     dx, dy, dt = 1.0 / mx, 1.0 / my, 0.01
+    key = "sharp_flux2/%dx%d/lim%d" % (mx, my, lim)
     a, ca = coracle.sharp_flux2(O.RP_EULER5_2D, par, lim, 5, 0, mbc, mx, my, q, None, dx, dy, dt)
-    b, cb = ref.sharp_flux2(O.RP_EULER5_2D, par, lim, 5, 0, mbc, mx, my, q, None, dx, dy, dt)
     inner = (slice(None), slice(mbc, -mbc), slice(mbc, -mbc))
     # a strong random state makes WENO overshoot into negative pressure at some edges: NaNs, in the same places
-    assert np.array_equal(a[inner], b[inner], equal_nan=True) and ca == cb
+    # (the pin's digest reads every NaN as one NaN, like equal_nan=True)
+    P.check(key, a[inner], ca)
+    if ref is not None:
+        b, cb = ref.sharp_flux2(O.RP_EULER5_2D, par, lim, 5, 0, mbc, mx, my, q, None, dx, dy, dt)
+        P.record(key, b[inner], cb)
+        assert np.array_equal(a[inner], b[inner], equal_nan=True) and ca == cb
 
 
-@pytest.mark.skipif(not O.RefEuler2D.available(fwave=True), reason="oracle/_ref/libref_euler2d_fw.so not built")
 @pytest.mark.parametrize("mx,my", [(7, 5), (41, 30)])
 @pytest.mark.parametrize("strong", [False, True])
 @pytest.mark.parametrize("mth", [[4, 4, 4, 4, 2], [1, 2, 3, 5, 0]])
 def test_fwave_form_matches_reference_flux2fw(coracle, mx, my, strong, mth):
     """the oracle's fwave=1 path against the reference's classic2fw link (flux2fw.f), dim-split and unsplit, on random
     Euler states: flux2fw.f:145-152 bit for bit"""
-    reffw = O.RefEuler2D(fwave=True)
+    reffw = O.RefEuler2D(fwave=True) if O.RefEuler2D.available(fwave=True) else None
+    case = "fwave/%dx%d/strong%d/mth%s" % (mx, my, strong, "".join(map(str, mth)))
     rng = np.random.default_rng(3 * mx + my)
     mbc = 2
     q0 = euler_state(rng, (mx + 2 * mbc, my + 2 * mbc), strong)
@@ -139,14 +161,22 @@ def test_fwave_form_matches_reference_flux2fw(coracle, mx, my, strong, mth):
         a, b = q0.copy("F"), q0.copy("F")
         _, ca = coracle.step2ds(O.RP_EULER5_2D, par, max(mx, my), mbc, mx, my, q0.copy("F"), a, None, dx, dy, dt, method,
                                 mth, ids, fwave=True)
-        _, cb = reffw.step2ds(O.RP_EULER5_2D, par, max(mx, my), mbc, mx, my, q0.copy("F"), b, None, dx, dy, dt, method,
-                              mth, ids, fwave=True)
-        assert np.array_equal(a, b) and ca == cb
+        assert not np.isnan(a).any()
+        P.check(case + "/ids%d" % ids, a, ca)
+        if reffw is not None:
+            _, cb = reffw.step2ds(O.RP_EULER5_2D, par, max(mx, my), mbc, mx, my, q0.copy("F"), b, None, dx, dy, dt,
+                                  method, mth, ids, fwave=True)
+            P.record(case + "/ids%d" % ids, b, cb)
+            assert np.array_equal(a, b) and ca == cb
     for trans in (0, 1, 2):
         method = np.array([1, 2, trans, 0, 0, 0, 0], dtype=np.int32)
         a, b = q0.copy("F"), q0.copy("F")
         _, ca = coracle.step2(O.RP_EULER5_2D, par, max(mx, my), mbc, mx, my, q0.copy("F"), a, None, dx, dy, dt, method, mth,
                               fwave=True)
-        _, cb = reffw.step2(O.RP_EULER5_2D, par, max(mx, my), mbc, mx, my, q0.copy("F"), b, None, dx, dy, dt, method, mth,
-                            fwave=True)
-        assert np.array_equal(a, b) and ca == cb
+        assert not np.isnan(a).any()
+        P.check(case + "/trans%d" % trans, a, ca)
+        if reffw is not None:
+            _, cb = reffw.step2(O.RP_EULER5_2D, par, max(mx, my), mbc, mx, my, q0.copy("F"), b, None, dx, dy, dt, method,
+                                mth, fwave=True)
+            P.record(case + "/trans%d" % trans, b, cb)
+            assert np.array_equal(a, b) and ca == cb
