@@ -25,43 +25,20 @@
 // and the arrays (671 MB per 4096^2 Euler state) are far larger than L2 + the 256 MB Infinity Cache, so nothing a pass
 // touches is still cached when the next pass wants it: nontemporal loads / stores stop the lines from displacing each
 // other on their way through.  Measured (tools/ubench/copy_rates.hip, 5 planes in / 5 out, this tile shape):
-// 6193 GB/s plain, 6853 GB/s nontemporal.  PCL_NT=0 builds the plain form for A/B.
-#ifndef PCL_NT
-#define PCL_NT 1
-#endif
+// 6193 GB/s plain, 6853 GB/s nontemporal.
 namespace pcl {
 namespace PCL_NS {
 typedef double pcl_d2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ double ld_stream(const double *p) {
-#if PCL_NT
-    return __builtin_nontemporal_load(p);
-#else
-    return *p;
-#endif
-}
+__device__ __forceinline__ double ld_stream(const double *p) { return __builtin_nontemporal_load(p); }
 __device__ __forceinline__ double2 ld_stream2(const double *p) {
-#if PCL_NT
     const pcl_d2 v = __builtin_nontemporal_load(reinterpret_cast<const pcl_d2 *>(p));
     double2 r; r.x = v.x; r.y = v.y;
     return r;
-#else
-    return *reinterpret_cast<const double2 *>(p);
-#endif
 }
-__device__ __forceinline__ void st_stream(double *p, double v) {
-#if PCL_NT
-    __builtin_nontemporal_store(v, p);
-#else
-    *p = v;
-#endif
-}
+__device__ __forceinline__ void st_stream(double *p, double v) { __builtin_nontemporal_store(v, p); }
 __device__ __forceinline__ void st_stream2(double *p, double2 v) {
-#if PCL_NT
     pcl_d2 w; w.x = v.x; w.y = v.y;
     __builtin_nontemporal_store(w, reinterpret_cast<pcl_d2 *>(p));
-#else
-    *reinterpret_cast<double2 *>(p) = v;
-#endif
 }
 }  // namespace PCL_NS
 }  // namespace pcl
@@ -246,7 +223,7 @@ __device__ __forceinline__ bool lane_core(const double (&q)[RP::MEQN], double dt
         // (every shift runs with all lanes active, outside the short-circuit expressions: a DPP read of a lane that is
         // masked off returns nothing useful)
         const double ql0 = from_left(q[0]);
-        bool same = !(a.ablate & 16) && __all(lane0 || ql0 == q[0]);
+        bool same = __all(lane0 || ql0 == q[0]);
         if (same) {      // wave-uniform
             double ql[MEQN];
 #pragma unroll
@@ -263,7 +240,7 @@ __device__ __forceinline__ bool lane_core(const double (&q)[RP::MEQN], double dt
 #pragma unroll
                     for (int m = 0; m < MEQN; m++) hit = hit & (q[m] == memo->key[m]);
                     if (__all(hit)) {
-                        if (!(a.ablate & 8) && cfl_ok) cflmax = dmax(cflmax, memo->m);
+                        if (cfl_ok) cflmax = dmax(cflmax, memo->m);
 #pragma unroll
                         for (int m = 0; m < MEQN; m++) qn[m] = q[m];
                         return true;
@@ -276,7 +253,7 @@ __device__ __forceinline__ bool lane_core(const double (&q)[RP::MEQN], double dt
 #pragma unroll
             for (int mw = 0; mw < MWAVES; mw++) finite = finite && (s[mw] - s[mw] == 0.0);
             if (__all(finite || lane0)) {
-                if (!(a.ablate & 8)) cfl_accumulate<CAPA, MWAVES>(s, dtdx_c, dtdx_l, cfl_ok, cflmax);
+                cfl_accumulate<CAPA, MWAVES>(s, dtdx_c, dtdx_l, cfl_ok, cflmax);
                 if constexpr (!CAPA && !TRANS) {
                     if (memo) {                  // every lane holds this cell: lane 1's copy is the wavefront's
                         double mx = fabs(s[0]);
@@ -307,11 +284,11 @@ __device__ __forceinline__ bool lane_core(const double (&q)[RP::MEQN], double dt
     // fluxes are zero and the update is the identity, whatever the limiter -- the reference computes exactly
     // that (q + 0).  Only the wave speeds are needed, for the Courant number (flux2.f:109-117); they come
     // from the same Roe average the full solve uses.  Wave-uniform branch; a non-finite speed (unphysical
-    // state) takes the full path.  PCL_TUNE_ABLATE bit 4 switches the shortcut off (tools/kbench.py).
+    // state) takes the full path.
     if constexpr (!FWAVE && RP::NAUX > 0) {   // f-waves over varying aux are non-zero even for equal q: no shortcut there
         const bool lane0 = (threadIdx.x & (WAVE - 1)) == 0;   // lane 0 has no left cell
         // first component first: where the state varies at all, one compare per lane settles it
-        bool same = !(a.ablate & 16) && __all(lane0 || cL.q[0] == cR.q[0]);
+        bool same = __all(lane0 || cL.q[0] == cR.q[0]);
         if (same) {
             bool rest = true;
 #pragma unroll
@@ -324,7 +301,7 @@ __device__ __forceinline__ bool lane_core(const double (&q)[RP::MEQN], double dt
 #pragma unroll
             for (int mw = 0; mw < MWAVES; mw++) finite = finite && (s[mw] - s[mw] == 0.0);
             if (__all(finite || (threadIdx.x & (WAVE - 1)) == 0)) {
-                if (!(a.ablate & 8)) cfl_accumulate<CAPA, MWAVES>(s, dtdx_c, dtdx_l, cfl_ok, cflmax);
+                cfl_accumulate<CAPA, MWAVES>(s, dtdx_c, dtdx_l, cfl_ok, cflmax);
 #pragma unroll
                 for (int m = 0; m < MEQN; m++) {
                     if constexpr (TRANS) { qn[m] = 0.0; df[m] = 0.0; g1[m] = 0.0; g2[m] = 0.0; }  // the slice's pieces
@@ -337,13 +314,13 @@ __device__ __forceinline__ bool lane_core(const double (&q)[RP::MEQN], double dt
     RP::template solve<IXY>(cL, cR, a.par, wave, s, amdq, apdq);
 
     // Courant number, flux2.f:109-117
-    if (!(a.ablate & 8)) cfl_accumulate<CAPA, MWAVES>(s, dtdx_c, dtdx_l, cfl_ok, cflmax);
+    cfl_accumulate<CAPA, MWAVES>(s, dtdx_c, dtdx_l, cfl_ok, cflmax);
 
     double fadd[MEQN], cq[MEQN];
 #pragma unroll
     for (int m = 0; m < MEQN; m++) { fadd[m] = 0.0; cq[m] = 0.0; }
 
-    if (a.order != 1 && !(a.ablate & 4)) {
+    if (a.order != 1) {
         // limiter.f:33-57 -- dotl(i) = w(i-1).w(i) here, dotr(i) = dotl(i+1) from the right lane.
         // The reference skips an interface whose wave has zero norm (limiter.f:45); when NO lane of the
         // wavefront has a wave in this family (a tracer-free or shear-free stretch, undisturbed gas) the
@@ -351,7 +328,7 @@ __device__ __forceinline__ bool lane_core(const double (&q)[RP::MEQN], double dt
 #pragma unroll
         for (int mw = 0; mw < MWAVES; mw++) {
             const int lim = a.mthlim[mw];
-            if (lim == 0 || (a.ablate & 2)) continue;
+            if (lim == 0) continue;
             double wn = 0.0;
             bool first = true;
 #pragma unroll
@@ -504,20 +481,13 @@ template <int IXY> struct TileShape {
     static constexpr int NSTRIP = IXY == 1 ? 4 : 1;                 // strips along the sweep per tile
     static constexpr int ALONG = NSTRIP * STRIP + 2 * HALO;         // cells loaded along the sweep
     static constexpr int ACROSS = IXY == 1 ? 4 : 16;                // cells across
-#ifndef PCL_YTILE_PAD       /* 1: the round-1 layout (17th padding double per row) -- A/B builds for the bank-conflict counters */
-#define PCL_YTILE_PAD 0
-#endif
-    static constexpr int PLANE = (IXY == 2 && PCL_YTILE_PAD) ? (ACROSS + 1) * ALONG : ACROSS * ALONG;
+    static constexpr int PLANE = ACROSS * ALONG;
     static constexpr int UNITS = NSTRIP * ACROSS / 4;               // strips per wavefront
     __device__ static __forceinline__ int at(int m, int al, int ac) {
         // y pass: rows of 16 doubles, the column XOR-swizzled with bits 1..4 of the row instead of a 17th padding
         // double: a wavefront reading one column of 64 rows still hits 32 different 8-byte banks per half, and the five
         // Euler planes take 40960 B instead of 43520 -- FOUR workgroups per CU (160 KB) instead of three
-#if PCL_YTILE_PAD
-        return IXY == 1 ? (m * ACROSS + ac) * ALONG + al : m * PLANE + al * (ACROSS + 1) + ac;
-#else
         return IXY == 1 ? (m * ACROSS + ac) * ALONG + al : (m * ALONG + al) * ACROSS + (ac ^ ((al >> 1) & (ACROSS - 1)));
-#endif
     }
 };
 constexpr int LINE = 16;  // doubles per 128-byte line
@@ -548,9 +518,8 @@ __device__ __forceinline__ VbcMap vbc_map(int k, int n, int mbc, int lo, int hi)
 // cache lines (the unsplit kernels' 60-cell / 14-column pieces are not line-aligned) should therefore run on
 // the SAME XCD, close in time, so that the shared lines are fetched once and the two partial-line stores merge
 // in that L2 before they go to HBM.  This maps blockIdx to a logical index such that each XCD walks a
-// contiguous range of logical indices (a bijection for any grid size).  PCL_TUNE_XCD=0 switches it off.
-__device__ __forceinline__ int xcd_logical_block(int on) {
-    if (!on) return blockIdx.x;
+// contiguous range of logical indices (a bijection for any grid size).
+__device__ __forceinline__ int xcd_logical_block() {
     const int nb = gridDim.x, x = blockIdx.x & 7, k = blockIdx.x >> 3;
     const int base = nb >> 3, rem = nb & 7;
     return x * base + (x < rem ? x : rem) + k;
@@ -558,11 +527,9 @@ __device__ __forceinline__ int xcd_logical_block(int on) {
 
 // SRC: the instantiation that applies the fused source term while storing (y pass of the Euler solver only; the
 // plain instantiation keeps its store loops untouched: a run-time switch there cost the memory-bound pass 4-5 %)
-#ifndef PCL_SWEEP_OCC      /* workgroups per CU the aux-free instantiations are register-allocated for (A/B: 1 = no target) */
-#define PCL_SWEEP_OCC 4
-#endif
+// (the aux-free instantiations are register-allocated for 4 workgroups per CU)
 template <class RP, int IXY, bool CAPA, bool FWAVE, bool DIM1, bool SRC = false>
-__global__ __launch_bounds__(256, (RP::NAUX == 0 && !CAPA) ? PCL_SWEEP_OCC : 1) void sweep_kernel(SweepArgs a, int ntiles_across, int ntiles_along) {
+__global__ __launch_bounds__(256, (RP::NAUX == 0 && !CAPA) ? 4 : 1) void sweep_kernel(SweepArgs a, int ntiles_across, int ntiles_along) {
     using T = TileShape<IXY>;
     constexpr int MEQN = RP::MEQN;
     // tile planes: q(0..MEQN-1), the capacity function (CAPA), then the first RP::NAUX aux components for
@@ -782,11 +749,7 @@ __global__ __launch_bounds__(256, (RP::NAUX == 0 && !CAPA) ? PCL_SWEEP_OCC : 1) 
         double auxv[NAUX > 0 ? NAUX : 1];
 #pragma unroll
         for (int m = 0; m < NAUX; m++) auxv[m] = tile[T::at(PAUX + m, al, ac)];   // aux planes are never overwritten
-        if (a.ablate & 1) {
-#pragma unroll
-            for (int m = 0; m < MEQN; m++) qn[m] = q[m];
-        } else
-            lane_core<RP, IXY, CAPA, FWAVE, DIM1>(q, dtdx_c, capa, cfl_ok, a, qn, cflmax, nullptr, nullptr, nullptr, auxv);
+        lane_core<RP, IXY, CAPA, FWAVE, DIM1>(q, dtdx_c, capa, cfl_ok, a, qn, cflmax, nullptr, nullptr, nullptr, auxv);
         if (owned) {
 #pragma unroll
             for (int m = 0; m < MEQN; m++) tile[T::at(m, al, ac)] = qn[m];
@@ -913,7 +876,7 @@ __global__ __launch_bounds__(U_WAVES *WAVE) void unsplit_x_kernel(SweepArgs a, i
     __shared__ double gm[U_WAVES][MEQN][WAVE], gp[U_WAVES][MEQN][WAVE];
     const int lane = threadIdx.x & (WAVE - 1);
     const int w = threadIdx.x / WAVE;
-    const int bid = xcd_logical_block(a.xcd);
+    const int bid = xcd_logical_block();
     const int ta = bid % nstrips, tr = bid / nstrips;
     if (a.sub != 0) {   // decomposed run: the tiles that read no ghost cell (box) in one launch, the rim in another
         const bool inside = tr >= a.box[0] && tr < a.box[1] && ta >= a.box[2] && ta < a.box[3];
@@ -1009,7 +972,7 @@ __global__ __launch_bounds__(U_WAVES *WAVE) void unsplit_y_kernel(SweepArgs a, i
     constexpr long LDS_REST = (long)sizeof(double) * (MEQN * WAVE * TP + 2 * U_WAVES * MEQN * WAVE);
     constexpr int NPL = LDS_REST + (long)sizeof(double) * aux_planes_y<RP>() * WAVE * AP <= 160 * 1024 ? aux_planes_y<RP>() : 0;
     __shared__ double atile[NPL > 0 ? NPL : 1][NPL > 0 ? WAVE : 1][NPL > 0 ? AP : 1];
-    const int bid = xcd_logical_block(a.xcd);
+    const int bid = xcd_logical_block();
     const int ti = bid % ntiles_i, tj = bid / ntiles_i;
     const int i0 = a.mbc - 1 + ti * U_OUT;               // slices i = 0 .. mx+1  <->  columns mbc-1 .. mbc+mx
     const int j0 = a.mbc - HALO + tj * STRIP;

@@ -5,13 +5,13 @@
 //   flux3.f:260-593   rpt3 x4 (+4 for the correction waves), rptt3 x8, gadd / hadd accumulation
 //   step3.f:114-592   x, y, z sweeps over slices 0..m+1; every slice updates the 3 x 3 cells around it
 //
-// Two kernels per direction.  slices3_kernel: one lane = one cell of a 64-cell strip (like sweep3_kernel); it leaves
-// the slice's pieces for each cell -- qadd, fadd(i+1)-fadd(i), gadd(2,-1:1), hadd(2,-1:1): 14 values per component --
-// in scratch planes.  combine3_kernel: every interior cell gathers the nine slices around it IN THE ORDER the
-// Fortran's loop nest visits them (x and z sweeps: z-like index outer, y-like inner; y sweep: y-like outer) and
-// applies their updates with the reference's association.  All three directions read the same qold, and the
-// x, y, z contributions are added in that order, exactly like step3.f.  (Throughput was not the aim of this first
-// device version: 14 scratch values per component and direction move ~20x the algorithmic bytes.)
+// One kernel per direction (march3p_kernel, below).  Each lane computes the pieces one slice leaves for the 3 x 3 cells
+// around it -- qadd, fadd(i+1)-fadd(i), gadd(2,-1:1), hadd(2,-1:1) -- in registers, and every interior cell receives the
+// nine slices around it IN THE ORDER the Fortran's loop nest visits them (x and z sweeps: z-like index outer, y-like
+// inner; y sweep: y-like outer), with the reference's association.  All three directions read the same qold, and the
+// x, y, z contributions are added in that order, exactly like step3.f.  The kernel exists for the solvers whose
+// transverse splits are driven by one component (RP::T3_PRESSURE, the variable-coefficient acoustics); the launcher
+// refuses every other solver.
 //
 // Direction roles (step3.f:176,303,470): sweep DIR, y-like = DIR+1, z-like = DIR+2 (cyclic).  aux block of a cell:
 // blk[oe+1][of+1][k] = aux component k of the neighbour at y-like offset oe, z-like offset of.
@@ -22,7 +22,6 @@ namespace pcl {
 namespace PCL_NS {
 
 struct Slices3Args {
-    double *scr[14];     // [0] qadd, [1] fadd(i+1)-fadd(i), [2+3*(side-1)+(slice+1)] gadd, [8+...] hadd; MEQN planes each
     long s_e, s_f;       // strides (doubles) of the y-like and z-like directions
     int n_e, n_f;        // extents with ghost cells
     int lo_e, hi_e, lo_f, hi_f;   // swept slices: 0..m+1 in both transverse directions (ghost-offset indices)
@@ -47,319 +46,17 @@ __device__ __forceinline__ void load_blk(const SweepArgs &a, const Slices3Args &
         }
 }
 
-// The pieces one slice leaves for its cells (flux3.f:168-593), in registers: qadd, fadd(i+1)-fadd(i), gadd(side, z-like
-// offset), hadd(side, y-like offset).  q / auxv: this lane's cell; blkR: its aux block (load_blk); the left lane's block
-// and state arrive by DPP shifts.  Shared by the scratch-plane kernel and the marching kernel below.
-template <class RP, int DIR>
-__device__ __forceinline__ void slice3_pieces(const double (&q)[RP::MEQN], const double (&auxv)[RP::NAUX],
-                                              const double (&blkR)[3][3][RP::NAUX], const SweepArgs &a, const Slices3Args &t,
-                                              bool cfl_ok, double &cflmax, double (&qadd)[RP::MEQN], double (&df)[RP::MEQN],
-                                              double (&gadd)[2][3][RP::MEQN], double (&hadd)[2][3][RP::MEQN]) {
-    constexpr int MEQN = RP::MEQN, MWAVES = RP::MWAVES, NAUX = RP::NAUX;
-    using Cell = typename RP::Cell;
-    double blkL[3][3][NAUX];
-    // cell l-1 (A^- dq): the left lane's block (lane 0 has no interface of its own)
-#pragma unroll
-    for (int oe = 0; oe < 3; oe++)
-#pragma unroll
-        for (int of = 0; of < 3; of++)
-#pragma unroll
-            for (int k = 0; k < NAUX; k++) blkL[oe][of][k] = from_left(blkR[oe][of][k]);
-    // reciprocals of the impedance sums the transverse solves divide by (rp.hpp: BlkRcp); the left cell's arrive by shift
-    const typename RP::BlkRcp rcR = RP::blk_rcp(blkR);
-    typename RP::BlkRcp rcL;
-#pragma unroll
-    for (int r = 0; r < 3; r++)
-#pragma unroll
-        for (int k = 0; k < 2; k++) {
-            rcL.y[r][k].r = from_left(rcR.y[r][k].r);
-            rcL.z[r][k].r = from_left(rcR.z[r][k].r);
-        }
-#pragma unroll
-    for (int r = 0; r < 3; r++) {      // the denominators themselves: one add each instead of a shift
-        rcL.y[r][0].d = blkL[0][r][0] + blkL[1][r][0]; rcL.y[r][1].d = blkL[1][r][0] + blkL[2][r][0];
-        rcL.z[r][0].d = blkL[r][0][0] + blkL[r][1][0]; rcL.z[r][1].d = blkL[r][1][0] + blkL[r][2][0];
-    }
-
-    const double d = a.dtd;
-
-    const Cell cR = RP::template precell<DIR>(q, a.par, auxv);
-    const Cell cL = struct_from_left(cR);
-    double wave[MWAVES][MEQN], s[MWAVES], amdq[MEQN], apdq[MEQN];
-    RP::template solve<DIR>(cL, cR, a.par, wave, s, amdq, apdq);
-    cfl_accumulate<false, MWAVES>(s, d, d, cfl_ok, cflmax);
-
-    double cq[MEQN];
-#pragma unroll
-    for (int m = 0; m < MEQN; m++) cq[m] = 0.0;
-    if (a.order != 1) {
-        // limiter.f:33-57 (same code as lane_core, without its wave-uniform skips)
-#pragma unroll
-        for (int mw = 0; mw < MWAVES; mw++) {
-            const int lim = a.mthlim[mw];
-            if (lim == 0) continue;
-            double wn = 0.0, dl = 0.0;
-            bool first = true;
-#pragma unroll
-            for (int m = 0; m < MEQN; m++) {
-                if (!RP::template nz<DIR>(mw, m)) continue;
-                const double w = wave[mw][m], wl = from_left(w);
-                wn = first ? w * w : wn + w * w;
-                dl = first ? wl * w : dl + wl * w;
-                first = false;
-            }
-            const double dr = from_right(dl);
-            if (wn != 0.0) {
-                const double phi = philim(wn, s[mw] > 0.0 ? dl : dr, lim);
-#pragma unroll
-                for (int m = 0; m < MEQN; m++)
-                    if (RP::template nz<DIR>(mw, m)) wave[mw][m] = phi * wave[mw][m];
-            }
-        }
-        const double dtdxave = 0.5 * (d + d);
-#pragma unroll
-        for (int m = 0; m < MEQN; m++) {       // flux3.f:244-247
-            double c = 0.0;
-            bool first = true;
-#pragma unroll
-            for (int mw = 0; mw < MWAVES; mw++)
-                if (RP::template nz<DIR>(mw, m)) {
-                    const double sa = fabs(s[mw]);
-                    const double term = 0.5 * sa * (1.0 - sa * dtdxave) * wave[mw][m];
-                    c = first ? term : c + term;
-                    first = false;
-                }
-            cq[m] = c;
-        }
-    }
-#pragma unroll
-    for (int m = 0; m < MEQN; m++) {
-        const double amdq_r = from_right(amdq[m]), fadd_r = from_right(cq[m]);
-        qadd[m] = -(d * apdq[m]) - d * amdq_r;
-        df[m] = fadd_r - cq[m];
-    }
-
-#pragma unroll
-    for (int k = 0; k < 2; k++)
-#pragma unroll
-        for (int j = 0; j < 3; j++)
-#pragma unroll
-            for (int m = 0; m < MEQN; m++) { gadd[k][j][m] = 0.0; hadd[k][j][m] = 0.0; }
-
-    if (t.m3 > 0) {
-        // ---- transverse splits of the fluctuations (flux3.f:269-291) and of the correction waves (:299-321)
-        double bmamdq[MEQN], bpamdq[MEQN], bmapdq[MEQN], bpapdq[MEQN];
-        double cmamdq[MEQN], cpamdq[MEQN], cmapdq[MEQN], cpapdq[MEQN];
-        RP::template transverse3<DIR>(2, blkL, rcL, amdq, bmamdq, bpamdq);
-        RP::template transverse3<DIR>(2, blkR, rcR, apdq, bmapdq, bpapdq);
-        RP::template transverse3<DIR>(3, blkL, rcL, amdq, cmamdq, cpamdq);
-        RP::template transverse3<DIR>(3, blkR, rcR, apdq, cmapdq, cpapdq);
-        double bmcqxxm[MEQN], bpcqxxm[MEQN], bmcqxxp[MEQN], bpcqxxp[MEQN];
-        double cmcqxxm[MEQN], cpcqxxm[MEQN], cmcqxxp[MEQN], cpcqxxp[MEQN];
-#pragma unroll
-        for (int m = 0; m < MEQN; m++)
-            bmcqxxm[m] = bpcqxxm[m] = bmcqxxp[m] = bpcqxxp[m] = cmcqxxm[m] = cpcqxxm[m] = cmcqxxp[m] = cpcqxxp[m] = 0.0;
-        if (t.m3 == 2) {
-            RP::template transverse3<DIR>(2, blkL, rcL, cq, bmcqxxm, bpcqxxm);
-            RP::template transverse3<DIR>(2, blkR, rcR, cq, bmcqxxp, bpcqxxp);
-            RP::template transverse3<DIR>(3, blkL, rcL, cq, cmcqxxm, cpcqxxm);
-            RP::template transverse3<DIR>(3, blkR, rcR, cq, cmcqxxp, cpcqxxp);
-        }
-        const double k6z = (1.0 / 6.0) * d * t.dtz, k6y = (1.0 / 6.0) * d * t.dty;
-        double bmcpapdq[MEQN], bpcpapdq[MEQN], bmcpamdq[MEQN], bpcpamdq[MEQN];
-        double bmcmapdq[MEQN], bpcmapdq[MEQN], bmcmamdq[MEQN], bpcmamdq[MEQN];
-#pragma unroll
-        for (int m = 0; m < MEQN; m++)
-            bmcpapdq[m] = bpcpapdq[m] = bmcpamdq[m] = bpcpamdq[m] = bmcmapdq[m] = bpcmapdq[m] = bmcmamdq[m] = bpcmamdq[m] = 0.0;
-
-        // ---- G fluxes (y-like), flux3.f:347-452
-        if (t.m4 > 0) {
-            double cpapdq2[MEQN], cpamdq2[MEQN], cmapdq2[MEQN], cmamdq2[MEQN];
-#pragma unroll
-            for (int m = 0; m < MEQN; m++) {
-                if (t.m4 == 2) {
-                    cpapdq2[m] = cpapdq[m] - 3.0 * cpcqxxp[m];
-                    cpamdq2[m] = cpamdq[m] + 3.0 * cpcqxxm[m];
-                    cmapdq2[m] = cmapdq[m] - 3.0 * cmcqxxp[m];
-                    cmamdq2[m] = cmamdq[m] + 3.0 * cmcqxxm[m];
-                } else {
-                    cpapdq2[m] = cpapdq[m]; cpamdq2[m] = cpamdq[m]; cmapdq2[m] = cmapdq[m]; cmamdq2[m] = cmamdq[m];
-                }
-            }
-            RP::template transverse3t<DIR>(2, 2, blkR, rcR, cpapdq2, bmcpapdq, bpcpapdq);
-            RP::template transverse3t<DIR>(2, 2, blkL, rcL, cpamdq2, bmcpamdq, bpcpamdq);
-            RP::template transverse3t<DIR>(2, 1, blkR, rcR, cmapdq2, bmcmapdq, bpcmapdq);
-            RP::template transverse3t<DIR>(2, 1, blkL, rcL, cmamdq2, bmcmamdq, bpcmamdq);
-        }
-#pragma unroll
-        for (int m = 0; m < MEQN; m++) {
-            // the A^- parts of interface l+1 belong to this cell: they arrive from the right-hand lane
-            const double r_bmamdq = from_right(bmamdq[m]), r_bpamdq = from_right(bpamdq[m]);
-            const double r_bmcpamdq = from_right(bmcpamdq[m]), r_bpcpamdq = from_right(bpcpamdq[m]);
-            const double r_bmcmamdq = from_right(bmcmamdq[m]), r_bpcmamdq = from_right(bpcmamdq[m]);
-            const double r_bmcqxxm = from_right(bmcqxxm[m]), r_bpcqxxm = from_right(bpcqxxm[m]);
-            double g10 = 0.0, g20 = 0.0, g21 = 0.0, g11 = 0.0, g2m = 0.0, g1m = 0.0;
-            // iteration i = l of flux3.f's loop 180 (index i)
-            g10 = g10 - 0.5 * d * bmapdq[m];
-            g20 = g20 - 0.5 * d * bpapdq[m];
-            if (t.m4 > 0) {
-                g20 = g20 + k6z * (bpcpapdq[m] - bpcmapdq[m]);
-                g10 = g10 + k6z * (bmcpapdq[m] - bmcmapdq[m]);
-                g21 = g21 - k6z * bpcpapdq[m];
-                g11 = g11 - k6z * bmcpapdq[m];
-                g2m = g2m + k6z * bpcmapdq[m];
-                g1m = g1m + k6z * bmcmapdq[m];
-            }
-            if (t.m3 >= 2) {
-                g20 = g20 + d * bpcqxxp[m];
-                g10 = g10 + d * bmcqxxp[m];
-            }
-            // iteration i = l+1 (index i-1)
-            g10 = g10 - 0.5 * d * r_bmamdq;
-            g20 = g20 - 0.5 * d * r_bpamdq;
-            if (t.m4 > 0) {
-                g20 = g20 + k6z * (r_bpcpamdq - r_bpcmamdq);
-                g10 = g10 + k6z * (r_bmcpamdq - r_bmcmamdq);
-                g21 = g21 - k6z * r_bpcpamdq;
-                g11 = g11 - k6z * r_bmcpamdq;
-                g2m = g2m + k6z * r_bpcmamdq;
-                g1m = g1m + k6z * r_bmcmamdq;
-            }
-            if (t.m3 >= 2) {
-                g20 = g20 - d * r_bpcqxxm;
-                g10 = g10 - d * r_bmcqxxm;
-            }
-            gadd[0][1][m] = g10; gadd[1][1][m] = g20; gadd[1][2][m] = g21; gadd[0][2][m] = g11;
-            gadd[1][0][m] = g2m; gadd[0][0][m] = g1m;
-        }
-        // ---- H fluxes (z-like), flux3.f:462-590
-        if (t.m4 == 2) {
-#pragma unroll
-            for (int m = 0; m < MEQN; m++) {
-                bpapdq[m] = bpapdq[m] - 3.0 * bpcqxxp[m];
-                bpamdq[m] = bpamdq[m] + 3.0 * bpcqxxm[m];
-                bmapdq[m] = bmapdq[m] - 3.0 * bmcqxxp[m];
-                bmamdq[m] = bmamdq[m] + 3.0 * bmcqxxm[m];
-            }
-        }
-        if (t.m4 > 0) {
-            RP::template transverse3t<DIR>(3, 2, blkR, rcR, bpapdq, bmcpapdq, bpcpapdq);
-            RP::template transverse3t<DIR>(3, 2, blkL, rcL, bpamdq, bmcpamdq, bpcpamdq);
-            RP::template transverse3t<DIR>(3, 1, blkR, rcR, bmapdq, bmcmapdq, bpcmapdq);
-            RP::template transverse3t<DIR>(3, 1, blkL, rcL, bmamdq, bmcmamdq, bpcmamdq);
-        }
-#pragma unroll
-        for (int m = 0; m < MEQN; m++) {
-            const double r_cmamdq = from_right(cmamdq[m]), r_cpamdq = from_right(cpamdq[m]);
-            const double r_bmcpamdq = from_right(bmcpamdq[m]), r_bpcpamdq = from_right(bpcpamdq[m]);
-            const double r_bmcmamdq = from_right(bmcmamdq[m]), r_bpcmamdq = from_right(bpcmamdq[m]);
-            const double r_cmcqxxm = from_right(cmcqxxm[m]), r_cpcqxxm = from_right(cpcqxxm[m]);
-            double h10 = 0.0, h20 = 0.0, h21 = 0.0, h11 = 0.0, h2m = 0.0, h1m = 0.0;
-            h10 = h10 - 0.5 * d * cmapdq[m];
-            h20 = h20 - 0.5 * d * cpapdq[m];
-            if (t.m4 > 0) {
-                h20 = h20 + k6y * (bpcpapdq[m] - bpcmapdq[m]);
-                h10 = h10 + k6y * (bmcpapdq[m] - bmcmapdq[m]);
-                h21 = h21 - k6y * bpcpapdq[m];
-                h11 = h11 - k6y * bmcpapdq[m];
-                h2m = h2m + k6y * bpcmapdq[m];
-                h1m = h1m + k6y * bmcmapdq[m];
-            }
-            if (t.m3 >= 2) {
-                h20 = h20 + d * cpcqxxp[m];
-                h10 = h10 + d * cmcqxxp[m];
-            }
-            h10 = h10 - 0.5 * d * r_cmamdq;
-            h20 = h20 - 0.5 * d * r_cpamdq;
-            if (t.m4 > 0) {
-                h20 = h20 + k6y * (r_bpcpamdq - r_bpcmamdq);
-                h10 = h10 + k6y * (r_bmcpamdq - r_bmcmamdq);
-                h21 = h21 - k6y * r_bpcpamdq;
-                h11 = h11 - k6y * r_bmcpamdq;
-                h2m = h2m + k6y * r_bpcmamdq;
-                h1m = h1m + k6y * r_bmcmamdq;
-            }
-            if (t.m3 >= 2) {
-                h20 = h20 - d * r_cpcqxxm;
-                h10 = h10 - d * r_cmcqxxm;
-            }
-            hadd[0][1][m] = h10; hadd[1][1][m] = h20; hadd[1][2][m] = h21; hadd[0][2][m] = h11;
-            hadd[1][0][m] = h2m; hadd[0][0][m] = h1m;
-        }
-    }
-}
-
-template <class RP, int DIR>
-__global__ __launch_bounds__(256) void slices3_kernel(SweepArgs a, Slices3Args t, int ntiles_al) {
-    constexpr int MEQN = RP::MEQN, MWAVES = RP::MWAVES, NAUX = RP::NAUX;
-    using Cell = typename RP::Cell;
-    // One wavefront = one 64-cell strip along the sweep; a workgroup = 4 strips.  x direction: 4 consecutive y-like
-    // rows.  y and z directions: the lanes' accesses are `pitch` apart, so the 4 wavefronts of a workgroup -- and
-    // consecutive workgroups, kept on one XCD by xcd_logical_block -- take CONSECUTIVE i: together they use whole
-    // 128-byte lines while those are still in that XCD's L2 (with i spread over blockIdx.y every line was fetched
-    // from / written to HBM up to 16 times: 54 ms instead of 6 ms per direction at 256^3).
-    const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x / WAVE;
-    int ta, ce, cf;
-    if (DIR == 1) {
-        ta = blockIdx.x % ntiles_al;
-        ce = (blockIdx.x / ntiles_al) * 4 + wv + t.lo_e;
-        cf = blockIdx.y + t.lo_f;
-    } else {
-        const int bx = xcd_logical_block(a.xcd);
-        const int ngrp = gridDim.x / ntiles_al;                // groups of 4 consecutive i
-        const int ci = (bx % ngrp) * 4 + wv;
-        ta = bx / ngrp;
-        if (DIR == 2) { cf = ci + t.lo_f; ce = blockIdx.y + t.lo_e; }   // y sweep: z-like index = i
-        else { ce = ci + t.lo_e; cf = blockIdx.y + t.lo_f; }           // z sweep: y-like index = i
-    }
-    if (ce > t.hi_e || cf > t.hi_f) return;                    // wave-uniform
-    const int a0 = a.mbc - HALO + ta * STRIP;
-    const int ca = a0 + lane;
-    const int cc = ca < a.n_al ? ca : a.n_al - 1;
-    const long g = (long)cc * a.s_al + (long)ce * t.s_e + (long)cf * t.s_f;
-    double q[MEQN], auxv[NAUX];
-#pragma unroll
-    for (int m = 0; m < MEQN; m++) q[m] = a.qin[m * a.plane + g];
-#pragma unroll
-    for (int k = 0; k < NAUX; k++) auxv[k] = a.aux[aux_idx<RP, DIR>(k) * a.plane + g];
-    double blkR[3][3][NAUX];
-    load_blk<RP, DIR>(a, t, g, ce, cf, blkR);     // cell l: A^+ dq of interface l sits here
-    const bool cfl_ok = (ca >= a.mbc) && (ca <= a.mbc + a.m_al) && lane >= 1;
-    const bool owned = (ca >= a.mbc) && (ca < a.mbc + a.m_al) && lane >= HALO && lane < WAVE - HALO;
-    double cflmax = 0.0;
-    double qadd[MEQN], df[MEQN], gadd[2][3][MEQN], hadd[2][3][MEQN];
-    slice3_pieces<RP, DIR>(q, auxv, blkR, a, t, cfl_ok, cflmax, qadd, df, gadd, hadd);
-    if (owned) {
-#pragma unroll
-        for (int m = 0; m < MEQN; m++) {
-            const long at = m * a.plane + g;
-            t.scr[0][at] = qadd[m];
-            t.scr[1][at] = df[m];
-#pragma unroll
-            for (int k = 0; k < 2; k++)
-#pragma unroll
-                for (int j = 0; j < 3; j++) {
-                    t.scr[2 + 3 * k + j][at] = gadd[k][j][m];
-                    t.scr[8 + 3 * k + j][at] = hadd[k][j][m];
-                }
-        }
-    }
-    cfl_publish(a.cfl, cfl_value<false>(cflmax, a.dtd));
-}
-
-// ---- the same pieces for solvers whose transverse splits are driven by ONE component ---------------------------------
+// ---- the pieces of one slice (flux3.f:168-593) for solvers whose transverse splits are driven by ONE component -------
 // (RP::T3_PRESSURE: acoustics.)  rpt3 / rptt3_vc_acoustics read asdq(1) and asdq(iuvw+1) (oracle/classic_oracle.c), and
 // what they are handed never has the second one: the normal fluctuations carry (p, sweep velocity), a y-like split
 // returns (p, y-like velocity), a z-like split (p, z-like velocity).  So all 16 solves per interface reduce to
 //     a1 = -t0 / (Zm + Z),  a2 = t0 / (Z + Zp)      outputs  (cm a1 Zm, -cm a1)  and  (cp a2 Zp, cp a2),
 // the G terms live in components (p, y-like velocity), the H terms in (p, z-like velocity), qadd / fadd in
 // (p, sweep velocity).  This form keeps only those: 24 doubles of gadd / hadd instead of 48, half the work after the
-// normal solve, half the exchange.  Every operation that remains is the dense code's, in its order; the ones dropped
+// normal solve, half the exchange.  Every operation that remains is the general form's (every component of every
+// split, as flux3.f and oracle/classic_oracle.c compute them), in its order; the ones dropped
 // have a structural zero as operand, so the values agree except, possibly, in the SIGN of a zero (v + 0.0 for
 // v = -0.0; -t0 + 0.0*Z for t0 = 0) -- the difference DESIGN section 4.1 already accepts for dmax1/dmin1.
-#ifndef PCL_T3_SHARED_RCP
-#define PCL_T3_SHARED_RCP 0      /* 1: spills at the 256-VGPR budget of 8 wavefronts (140 B of scratch per lane) */
-#endif
 struct P2 { double p, v; };
 // M34: method(3) = 10*m3 + m4 as a compile-time constant (22: the solver default, every term present, no run-time
 // selects), or -1 = read at run time
@@ -431,7 +128,7 @@ __device__ __forceinline__ void slice3_pieces_p(const double (&q)[RP::MEQN], con
     if (m3 <= 0) return;
 
     // Every split below uses THIS cell's block: A^+ dq and the correction flux of interface l belong to cell l, and
-    // A^- dq / the correction flux of interface l+1 -- which the dense code splits in lane l+1 with the left
+    // A^- dq / the correction flux of interface l+1 -- which the general form splits in lane l+1 with the left
     // neighbour's block and then shifts back -- are fetched from the right-hand lane first and split here.  Same
     // operands, same operations, one lane to the left: the left neighbour's block, its reciprocals and 32 shifts of
     // results disappear, and the twelve impedance sums of the block are inverted once.
@@ -462,7 +159,7 @@ __device__ __forceinline__ void slice3_pieces_p(const double (&q)[RP::MEQN], con
         op.p = cp * a2 * zp; op.v = cp * a2;
     };
     const P2 zero{0.0, 0.0};
-    // names as in flux3.f; the ...amdq / ...cqxxm ones are those of interface l+1 (the dense code's r_ values)
+    // names as in flux3.f; the ...amdq / ...cqxxm ones are those of interface l+1 (the general form's r_ values)
     P2 bmamdq, bpamdq, bmapdq, bpapdq, cmamdq, cpamdq, cmapdq, cpapdq;
     split(true, 1, aM, bmamdq, bpamdq);
     split(true, 1, aP, bmapdq, bpapdq);
@@ -476,7 +173,7 @@ __device__ __forceinline__ void slice3_pieces_p(const double (&q)[RP::MEQN], con
         split(false, 1, kP, cmcqxxp, cpcqxxp);
     }
     const double k6z = (1.0 / 6.0) * d * t.dtz, k6y = (1.0 / 6.0) * d * t.dty;
-    // one component of the six G (or H) values of this cell: the dense code's statements in their order.
+    // one component of the six G (or H) values of this cell: the general form's statements in their order.
     // b?a?dq: first-level split in the flux's own direction; x???: second-level results; q???: correction-wave splits
     auto six = [&](double k6, double bmap, double bpap, double bmam, double bpam, double xmcpap, double xpcpap, double xmcmap,
                    double xpcmap, double xmcpam, double xpcpam, double xmcmam, double xpcmam, double qmp, double qpp, double qmm,
@@ -553,26 +250,25 @@ __device__ __forceinline__ void slice3_pieces_p(const double (&q)[RP::MEQN], con
     }
 }
 
-// ---- the marching form: no scratch planes ---------------------------------------------------------------------------
+// ---- the marching kernel ------------------------------------------------------------------------------------------
 // step3.f visits the slices of a direction in a loop nest -- x and z sweeps: z-like index outside, y-like inside; y sweep:
 // y-like outside (step3.f:176,303,470) -- and every slice adds to the 3 x 3 cells around it, so a cell receives its nine
-// contributions ordered by the OUTER index of the source slice first, the inner one second.  march3_kernel walks the
+// contributions ordered by the OUTER index of the source slice first, the inner one second.  march3p_kernel walks the
 // outer index ("march axis" M): a workgroup of NW wavefronts holds NW consecutive slices of the inner index ("wave
-// axis" W) of one 64-cell strip, and at march step m every wavefront computes the pieces of its slice (w, m) with the
-// code of the scratch-plane kernel (slice3_pieces).  A target cell (w, tm) then gets, in the reference's order,
+// axis" W) of one 64-cell strip, and at march step m every wavefront computes the pieces of its slice (w, m)
+// (slice3_pieces_p).  A target cell (w, tm) then gets, in the reference's order,
 //     from plane m = tm-1:  slices w-1, w, w+1      (first: the accumulator starts from the cell's old value)
 //     from plane m = tm  :  slices w-1, w, w+1
 //     from plane m = tm+1:  slices w-1, w, w+1      (last: the cell is complete and is stored)
 // i.e. three accumulators per wavefront live in registers across march steps (planes m+1, m, m-1) and only the
-// contributions to the neighbouring slices w-1 / w+1 cross wavefronts, through LDS: per component 6 targets x 2
-// addends (every update is q = (q + A) + B with A the y-like and B the z-like flux term, products and signs applied by
-// the SOURCE lane -- the same operations the combine kernel did, so the bits are the same), two components per
-// exchange phase: NW * 2 * 12 * 64 doubles = 96 KB for NW = 8.  Tiles overlap by two slices along W (NW/(NW-2)
+// contributions to the neighbouring slices w-1 / w+1 cross wavefronts, through LDS (every update is q = (q + A) + B
+// with A the y-like and B the z-like flux term, products and signs applied by the SOURCE lane -- the operations of
+// step3.f's update, so the bits are the same).  Tiles overlap by two slices along W (NW/(NW-2)
 // recompute) and the march range is cut into segments (one extra source plane at each end) so that a 256^3 grid
 // still gives every CU a workgroup.
 //     DIR 1: M = z-like (k), W = y-like (j)     DIR 2: M = y-like (k), W = z-like (i)     DIR 3: M = z-like (j), W = y-like (i)
 // For the y and z sweeps the wave axis is i: the 8 wavefronts of a workgroup touch 8 neighbouring doubles of every
-// line and workgroups that are neighbours along i run on the same XCD (xcd_logical_block), like slices3_kernel.
+// line and workgroups that are neighbours along i run on the same XCD (xcd_logical_block).
 struct March3Args {
     const double *qsrc;   // what a cell's accumulator starts from: qold (x direction), the state accumulated so far (y, z)
     double *qacc;
@@ -583,134 +279,9 @@ struct March3Args {
 };
 
 // the ordered pair of addends slice S gives the cell at (y-like offset oe, z-like offset of) from itself (step3.f's
-// update formulas as the combine kernel evaluates them; G_(k,j) = gadd[k-1][j+1], H_(k,j) = hadd[k-1][j+1]):
-// q := (q + A) + B.  The centre cell (0,0) has two more addends in front (qadd, -dtd*df), applied by the caller.
-template <int MEQN>
-__device__ __forceinline__ void pair3(int oe, int of, int m, double dty, double dtz, const double (&gadd)[2][3][MEQN],
-                                      const double (&hadd)[2][3][MEQN], double &A, double &B) {
-#define G_(k, j) gadd[(k)-1][(j) + 1][m]
-#define H_(k, j) hadd[(k)-1][(j) + 1][m]
-    if (oe == 0 && of == 0) { A = -(dty * (G_(2, 0) - G_(1, 0))); B = -(dtz * (H_(2, 0) - H_(1, 0))); }
-    else if (oe == -1 && of == 0) { A = -(dty * G_(1, 0)); B = -(dtz * (H_(2, -1) - H_(1, -1))); }
-    else if (oe == -1 && of == -1) { A = -(dty * G_(1, -1)); B = -(dtz * H_(1, -1)); }
-    else if (oe == 0 && of == -1) { A = -(dty * (G_(2, -1) - G_(1, -1))); B = -(dtz * H_(1, 0)); }
-    else if (oe == 1 && of == -1) { A = dty * G_(2, -1); B = -(dtz * H_(1, 1)); }
-    else if (oe == 1 && of == 0) { A = dty * G_(2, 0); B = -(dtz * (H_(2, 1) - H_(1, 1))); }
-    else if (oe == 1 && of == 1) { A = dty * G_(2, 1); B = dtz * H_(2, 1); }
-    else if (oe == 0 && of == 1) { A = -(dty * (G_(2, 1) - G_(1, 1))); B = dtz * H_(2, 0); }
-    else { A = -(dty * G_(1, 1)); B = dtz * H_(2, -1); }       // (-1, 1)
-#undef G_
-#undef H_
-}
-
-template <class RP, int DIR, int NW>
-__global__ __launch_bounds__(NW *WAVE) void march3_kernel(SweepArgs a, Slices3Args t, March3Args g) {
-    constexpr int MEQN = RP::MEQN, NAUX = RP::NAUX;
-    constexpr bool E_OUTER = DIR == 2;          // the march axis is the y-like index (y sweep), else the z-like one
-    constexpr int CP = 2;                        // components per exchange phase
-    static_assert(MEQN % CP == 0, "exchange phases take two components");
-    // xbuf[w][c][side][o][A|B][lane]: side 0 = for the slice w+1 (W offset +1), 1 = for the slice w-1; o = M offset + 1
-    __shared__ double xbuf[NW][CP][2][3][2][WAVE];
-    const int lane = threadIdx.x & (WAVE - 1), w = threadIdx.x / WAVE;
-    const int bid = DIR == 1 ? (int)blockIdx.x : xcd_logical_block(a.xcd);
-    // W tiles fastest (neighbours along the wave axis close together), then the strips, then the march segments
-    const int tw = bid % g.ntiles_w, ta = (bid / g.ntiles_w) % g.ntiles_al, ts = bid / (g.ntiles_w * g.ntiles_al);
-    const int a0 = a.mbc - HALO + ta * STRIP;
-    const int ca = a0 + lane;
-    const int cc = ca < a.n_al ? ca : a.n_al - 1;
-    const int cw = a.mbc - 1 + tw * (NW - 2) + w;                       // this wavefront's slice along the wave axis
-    const bool w_live = cw <= a.mbc + g.m_w;                           // slices 0 .. m+1 exist (wave-uniform)
-    const int cwc = cw < g.n_w ? cw : g.n_w - 1;
-    const bool target_w = w >= 1 && w <= NW - 2 && cw >= a.mbc && cw < a.mbc + g.m_w;
-    const bool owned = (ca >= a.mbc) && (ca < a.mbc + a.m_al) && lane >= HALO && lane < WAVE - HALO && target_w;
-    const bool cfl_ok = (ca >= a.mbc) && (ca <= a.mbc + a.m_al) && lane >= 1;
-    const int tm0 = a.mbc + ts * g.seg;
-    const int tm1 = tm0 + g.seg < a.mbc + g.m_m ? tm0 + g.seg : a.mbc + g.m_m;      // target planes [tm0, tm1)
-    const long base = (long)cc * a.s_al + (long)cwc * g.s_w;
-    const int wl = w > 0 ? w - 1 : w, wr = w < NW - 1 ? w + 1 : w;       // (the end wavefronts are never targets)
-    double cflmax = 0.0;
-    double accP[MEQN], acc0[MEQN], accM[MEQN];
-#pragma unroll
-    for (int m = 0; m < MEQN; m++) { accP[m] = 0.0; acc0[m] = 0.0; accM[m] = 0.0; }
-
-    for (int pm = tm0 - 1; pm <= tm1; pm++) {                            // source planes (all within 0 .. m+1)
-        const long gc = base + (long)pm * g.s_m;
-        double qadd[MEQN], df[MEQN], gadd[2][3][MEQN], hadd[2][3][MEQN];
-        if (w_live) {
-            double q[MEQN], auxv[NAUX], blkR[3][3][NAUX];
-#pragma unroll
-            for (int m = 0; m < MEQN; m++) q[m] = a.qin[m * a.plane + gc];
-#pragma unroll
-            for (int k = 0; k < NAUX; k++) auxv[k] = a.aux[aux_idx<RP, DIR>(k) * a.plane + gc];
-            load_blk<RP, DIR>(a, t, gc, E_OUTER ? pm : cwc, E_OUTER ? cwc : pm, blkR);
-            slice3_pieces<RP, DIR>(q, auxv, blkR, a, t, cfl_ok, cflmax, qadd, df, gadd, hadd);
-        } else {
-#pragma unroll
-            for (int m = 0; m < MEQN; m++) {
-                qadd[m] = 0.0; df[m] = 0.0;
-#pragma unroll
-                for (int k = 0; k < 2; k++)
-#pragma unroll
-                    for (int j = 0; j < 3; j++) { gadd[k][j][m] = 0.0; hadd[k][j][m] = 0.0; }
-            }
-        }
-        // the plane ahead starts its accumulator from the cell's value (the march never leaves the array: pm+1 <= m+3)
-        if (target_w) {      // wave-uniform
-#pragma unroll
-            for (int m = 0; m < MEQN; m++) accP[m] = g.qsrc[m * a.plane + gc + g.s_m];
-        }
-
-#pragma unroll
-        for (int ph = 0; ph < MEQN / CP; ph++) {
-            // publish what this slice gives the slices w+1 (side 0) and w-1 (side 1) of the planes pm+1, pm, pm-1
-#pragma unroll
-            for (int c = 0; c < CP; c++) {
-                const int m = ph * CP + c;
-#pragma unroll
-                for (int side = 0; side < 2; side++)
-#pragma unroll
-                    for (int o = -1; o <= 1; o++) {
-                        const int in = side == 0 ? 1 : -1;
-                        double A, B;
-                        pair3<MEQN>(E_OUTER ? o : in, E_OUTER ? in : o, m, t.dty, t.dtz, gadd, hadd, A, B);
-                        xbuf[w][c][side][o + 1][0][lane] = A;
-                        xbuf[w][c][side][o + 1][1][lane] = B;
-                    }
-            }
-            __syncthreads();
-#pragma unroll
-            for (int c = 0; c < CP; c++) {
-                const int m = ph * CP + c;
-#pragma unroll
-                for (int o = 1; o >= -1; o--) {
-                    double v = o == 1 ? accP[m] : (o == 0 ? acc0[m] : accM[m]);
-                    v = v + xbuf[wl][c][0][o + 1][0][lane];               // from the slice w-1 (its W offset +1)
-                    v = v + xbuf[wl][c][0][o + 1][1][lane];
-                    double A, B;
-                    pair3<MEQN>(E_OUTER ? o : 0, E_OUTER ? 0 : o, m, t.dty, t.dtz, gadd, hadd, A, B);
-                    if (o == 0) { v = v + qadd[m]; v = v - a.dtd * df[m]; }
-                    v = v + A;                                             // this slice's own contribution
-                    v = v + B;
-                    v = v + xbuf[wr][c][1][o + 1][0][lane];               // from the slice w+1 (its W offset -1)
-                    v = v + xbuf[wr][c][1][o + 1][1][lane];
-                    if (o == 1) accP[m] = v; else if (o == 0) acc0[m] = v; else accM[m] = v;
-                }
-            }
-            __syncthreads();
-        }
-        // the plane behind is complete
-        if (owned && pm - 1 >= tm0 && pm - 1 < tm1) {
-#pragma unroll
-            for (int m = 0; m < MEQN; m++) g.qacc[m * a.plane + gc - g.s_m] = accM[m];
-        }
-#pragma unroll
-        for (int m = 0; m < MEQN; m++) { accM[m] = acc0[m]; acc0[m] = accP[m]; }
-    }
-    cfl_publish(a.cfl, cfl_value<false>(cflmax, a.dtd));
-}
-
-// the pair of addends of pair3 for the pressure-driven form: A from G (components p, y-like velocity), B from H
-// (components p, z-like velocity)
+// update formulas; G_(k,j) = G[k-1][j+1], H_(k,j) = H[k-1][j+1]): q := (q + A) + B, A from G (components p, y-like
+// velocity), B from H (components p, z-like velocity).  The centre cell (0,0) has two more addends in front (qadd,
+// -dtd*df), applied by the caller.
 __device__ __forceinline__ void pair3p(int oe, int of, double dty, double dtz, const P2 (&G)[2][3], const P2 (&H)[2][3],
                                        P2 &A, P2 &B) {
 #define G_(k, j, c) G[(k)-1][(j) + 1].c
@@ -766,7 +337,7 @@ __device__ __forceinline__ void pair3p(int oe, int of, double dty, double dtz, c
 #undef BMP
 }
 
-// march3_kernel for the pressure-driven form (slice3_pieces_p): component 0 receives both addends of every contribution,
+// The marching kernel (above) for the pressure-driven pieces: component 0 receives both addends of every contribution,
 // the y-like velocity only A, the z-like velocity only B, the sweep velocity only the slice's own qadd / fadd -- 24
 // doubles per lane cross wavefronts instead of 48, in ONE exchange phase (two barriers per march step).
 template <class RP, int DIR, int NW, int M34 = -1>
@@ -793,7 +364,7 @@ __global__ __launch_bounds__(NW *WAVE) void march3p_kernel(SweepArgs a, Slices3A
     double(*tout)[WAVE][TP] = reinterpret_cast<double(*)[WAVE][TP]>(&xbuf[0][0][0][0][0]);
     constexpr int NT = NW * WAVE;
     const int lane = threadIdx.x & (WAVE - 1), w = threadIdx.x / WAVE;
-    const int bid = DIR == 1 ? (int)blockIdx.x : xcd_logical_block(a.xcd);
+    const int bid = DIR == 1 ? (int)blockIdx.x : xcd_logical_block();
     const int tw = bid % g.ntiles_w, ta = (bid / g.ntiles_w) % g.ntiles_al, ts = bid / (g.ntiles_w * g.ntiles_al);
     const int a0 = a.mbc - HALO + ta * STRIP;
     const int ca = a0 + lane;
@@ -998,56 +569,6 @@ __global__ __launch_bounds__(256) void ghost3_copy_kernel(const double *src, dou
     if (i >= mbc && i < I - mbc && j >= mbc && j < J - mbc && k >= mbc && k < K - mbc) return;
     const long c = ((long)k * J + j) * pitch + i;
     for (int m = 0; m < meqn; m++) dst[m * plane + c] = src[m * plane + c];
-}
-
-// One thread per cell: qacc(T) += the nine slices of direction DIR around T, in the loop order of step3.f
-struct Combine3Args {
-    const double *scr[14];
-    const double *qsrc;   // qold for the x direction (qacc starts as a copy), qacc itself afterwards
-    double *qacc;
-    long plane, s_al, s_e, s_f;
-    int n_al, n_e, n_f, mbc, m_al, m_e, m_f, meqn;
-    double dtd, dty, dtz;
-    int e_outer;          // 1: the Fortran's outer loop runs over the y-like index (y sweep), 0: over the z-like one
-    int first;            // 1: x direction (start from qsrc and write every cell, ghost cells copied through)
-    int dir;              // sweep direction 1..3 (thread -> cell mapping)
-};
-__global__ __launch_bounds__(256) void combine3_kernel(Combine3Args c) {
-    // threads run along i (memory-contiguous) whatever the sweep direction: every load and the store are coalesced
-    const int pi = blockIdx.x * blockDim.x + threadIdx.x, pj = blockIdx.y, pk = blockIdx.z;
-    const int ia = c.dir == 1 ? pi : (c.dir == 2 ? pj : pk);       // index along the sweep
-    const int ie = c.dir == 1 ? pj : (c.dir == 2 ? pk : pi);       // y-like
-    const int jf = c.dir == 1 ? pk : (c.dir == 2 ? pi : pj);       // z-like
-    if (ia >= c.n_al || ie >= c.n_e || jf >= c.n_f) return;
-    const long g = (long)ia * c.s_al + (long)ie * c.s_e + (long)jf * c.s_f;
-    const bool interior = ia >= c.mbc && ia < c.mbc + c.m_al && ie >= c.mbc && ie < c.mbc + c.m_e && jf >= c.mbc &&
-                          jf < c.mbc + c.m_f;
-    for (int m = 0; m < c.meqn; m++) {
-        const long at = m * c.plane + g;
-        double q = c.first ? c.qsrc[at] : c.qacc[at];
-        if (interior) {
-            for (int o = 1; o >= -1; o--)
-                for (int in = 1; in >= -1; in--) {
-                    const int oe = c.e_outer ? o : in, of = c.e_outer ? in : o;
-                    const long S = at - oe * c.s_e - of * c.s_f;      // the slice that adds to (oe, of) from itself
-#define G_(k, j) c.scr[2 + 3 * ((k)-1) + ((j) + 1)][S]
-#define H_(k, j) c.scr[8 + 3 * ((k)-1) + ((j) + 1)][S]
-                    if (oe == 0 && of == 0)
-                        q = q + c.scr[0][S] - c.dtd * c.scr[1][S] - c.dty * (G_(2, 0) - G_(1, 0)) - c.dtz * (H_(2, 0) - H_(1, 0));
-                    else if (oe == -1 && of == 0) q = q - c.dty * G_(1, 0) - c.dtz * (H_(2, -1) - H_(1, -1));
-                    else if (oe == -1 && of == -1) q = q - c.dty * G_(1, -1) - c.dtz * H_(1, -1);
-                    else if (oe == 0 && of == -1) q = q - c.dty * (G_(2, -1) - G_(1, -1)) - c.dtz * H_(1, 0);
-                    else if (oe == 1 && of == -1) q = q + c.dty * G_(2, -1) - c.dtz * H_(1, 1);
-                    else if (oe == 1 && of == 0) q = q + c.dty * G_(2, 0) - c.dtz * (H_(2, 1) - H_(1, 1));
-                    else if (oe == 1 && of == 1) q = q + c.dty * G_(2, 1) + c.dtz * H_(2, 1);
-                    else if (oe == 0 && of == 1) q = q - c.dty * (G_(2, 1) - G_(1, 1)) + c.dtz * H_(2, 0);
-                    else q = q - c.dty * G_(1, 1) + c.dtz * H_(2, -1);
-#undef G_
-#undef H_
-                }
-        }
-        if (interior || c.first) c.qacc[at] = q;
-    }
 }
 
 }  // namespace PCL_NS

@@ -8,8 +8,8 @@
 // Riemann solvers and mbc != 2.
 //
 // Tile: 16 rows x 64 columns of q with a 2-cell halo on every side, all MEQN planes in LDS (Euler: 40 KB, four
-// workgroups of 256 threads per CU; the round's first form was 32 x 64 with 512 threads, two per CU -- still a build
-// option, see PCL_FUSED_ROWS below).  Four phases, a barrier in front of the y sweeps and one behind them:
+// workgroups of 256 threads per CU; the round's first form was 32 x 64 with 512 threads, two per CU -- measured
+// slower, see the tile shape below).  Four phases, a barrier in front of the y sweeps and one behind them:
 //   load   the tile, ghost cells remapped to their boundary-condition source cells (tiles on the frame only);
 //   x      wavefront w sweeps the four rows it loaded (2w, 2w+1, 8+2w, 9+2w): one lane = one cell, the row is a 64-lane
 //          strip exactly as in the x pass; the 60 inner lanes put the updated cell back IN PLACE (interior columns only:
@@ -31,23 +31,14 @@
 namespace pcl {
 namespace PCL_NS {
 
-// Tile shape (build-time A/B: -DPCL_FUSED_ROWS / _COLS / _THREADS; tools/fused_ab.sh).  32 x 64 with 512 threads is two
-// 80 KB workgroups per CU for Euler; 16 x 64 and 32 x 32 with 256 threads are four of 40 KB (shorter phases, more of them
+// Tile shape: 16 x 64 with 256 threads, four 40 KB workgroups per CU for Euler.  32 x 64 with 512 threads is two
+// 80 KB workgroups per CU; 16 x 64 and 32 x 32 with 256 threads are four of 40 KB (shorter phases, more of them
 // in flight, for 17 % / 7 % more halo work).  Same box, 4096^2 shock-bubble state, ms per step: 32 x 64 0.350, 16 x 64
 // 0.331, 32 x 32 0.370 (its 256-byte row pieces stream badly: 0.376 even without arithmetic); dense state 0.835 / 0.94 /
 // 0.86 -- there the solver runs the two passes anyway (pclaw.hip, form trials).
-#ifndef PCL_FUSED_ROWS
-#define PCL_FUSED_ROWS 16
-#endif
-#ifndef PCL_FUSED_COLS
-#define PCL_FUSED_COLS 64
-#endif
-#ifndef PCL_FUSED_THREADS
-#define PCL_FUSED_THREADS 256
-#endif
-constexpr int F_ROWS = PCL_FUSED_ROWS, F_COLS = PCL_FUSED_COLS;
+constexpr int F_ROWS = 16, F_COLS = 64;
 constexpr int F_OWN_R = F_ROWS - 2 * HALO, F_OWN_C = F_COLS - 2 * HALO;
-constexpr int F_THREADS = PCL_FUSED_THREADS, F_WAVES = F_THREADS / WAVE;
+constexpr int F_THREADS = 256, F_WAVES = F_THREADS / WAVE;
 constexpr int F_RX = WAVE / F_COLS;          // rows of the tile one wavefront sweeps at a time (x sweeps)
 constexpr int F_CY = WAVE / F_ROWS;          // columns one wavefront sweeps at a time (y sweeps)
 constexpr int F_PPR = F_COLS / 2;            // 16-byte pairs per tile row
@@ -58,9 +49,6 @@ static_assert(F_COLS * F_RX == WAVE && F_ROWS * F_CY == WAVE && F_OWN_C % 2 == 0
 static_assert(F_ROWS * F_PPR % F_THREADS == 0 && (WAVE / F_PPR) % F_RX == 0, "tile shape");
 static_assert(F_NS * F_RX * F_WAVES == F_ROWS && (F_COLS / F_CY) % F_WAVES == 0, "tile shape");
 
-#ifndef PCL_FUSED_NT      /* 1: the tile loads bypass the caches like the two-pass kernels' (A/B) */
-#define PCL_FUSED_NT 0
-#endif
 // first row of the tile wavefront w loads and sweeps in its x sweep k = 0..F_NS-1 (16 x 64, 256 threads: 2w, 2w+1,
 // 8+2w, 9+2w -- what the threads taking the tile's 16-byte pairs in order give it); lanes >= F_COLS take the next row
 __device__ __forceinline__ int wave_row(int w, int k) {
@@ -71,39 +59,22 @@ __device__ __forceinline__ int fswz(int r) { return F_ROWS >= 32 ? r : r * (32 /
 __device__ __forceinline__ int ftile_at(int m, int r, int c) { return (m * F_ROWS + r) * F_COLS + (c ^ fswz(r)); }
 
 template <class RP, bool FWAVE, bool SRC>
-__global__ __launch_bounds__(F_THREADS, F_THREADS == 512 ? (RP::MEQN > 3 ? 2 : 3) : 1024 / F_THREADS) void step2ds_kernel(SweepArgs a, int ntx, int nty) {
+__global__ __launch_bounds__(F_THREADS, 1024 / F_THREADS) void step2ds_kernel(SweepArgs a, int ntx, int nty) {
     constexpr int MEQN = RP::MEQN;
     static_assert(RP::NAUX == 0, "solvers without aux arrays");
     static_assert(!SRC || MEQN == 5, "fused source: the Euler solver");
     __shared__ __attribute__((aligned(16))) double tile[MEQN * F_ROWS * F_COLS];
 
-    // (the XCD-contiguous order of xcd_logical_block costs this kernel 2-3 % although it saves HBM reads -- PCL_TUNE_XCD
-    // bit 1 switches it on for A/B)
-    int bid = (a.xcd & 2) ? xcd_logical_block(1) : (int)blockIdx.x;
-    if (a.xcd & 4) {
-        // chunked order (the default; PCL_TUNE_XCD bit 2): the hardware deals consecutive workgroups to the 8 XCDs in
-        // turn; in every window of 64 tiles each XCD takes 8 CONSECUTIVE tiles of a tile row (they share partial lines
-        // and halo columns in that XCD's L2) while the windows still walk the grid in row order: without arithmetic
-        // 0.288 -> 0.274 ms, the shock-bubble step 0.331 -> 0.330 (16 x 64, before the memo)
-        const int nb = gridDim.x, win = bid >> 6;
-        if ((win + 1) << 6 <= nb) bid = (win << 6) + ((bid & 7) << 3) + ((bid >> 3) & 7);
-    }
+    // Chunked order: the hardware deals consecutive workgroups to the 8 XCDs in turn; in every window of 64 tiles each
+    // XCD takes 8 CONSECUTIVE tiles of a tile row (they share partial lines and halo columns in that XCD's L2) while the
+    // windows still walk the grid in row order: without arithmetic 0.288 -> 0.274 ms, the shock-bubble step 0.331 ->
+    // 0.330 (16 x 64, before the memo).  The XCD-contiguous order of xcd_logical_block costs this kernel 2-3 % although
+    // it saves HBM reads; column bands per XCD (a tile's four neighbours on the same XCD) measured 25 % slower on the
+    // shock-bubble state, equal without arithmetic.
+    int bid = blockIdx.x;
+    const int nb = gridDim.x, win = bid >> 6;
+    if ((win + 1) << 6 <= nb) bid = (win << 6) + ((bid & 7) << 3) + ((bid >> 3) & 7);
     int tx = bid % ntx, ty = bid / ntx;
-    if ((a.xcd & 8) && a.sub == 0 && ntx >= 8) {
-        // column bands (A/B only, PCL_TUNE_XCD bit 3; measured 25 % SLOWER on the shock-bubble state, equal without
-        // arithmetic): XCD x walks the tiles of column band x row by row, so a tile's
-        // neighbours to the left, right, above and below run on the same XCD (halo rows / columns and shared partial
-        // lines hit its L2) while all eight XCDs advance through the tile rows together.  The contiguous ranges of
-        // xcd_logical_block over the band-major order of the tiles: a bijection for any grid (bands differ by one column)
-        int l = xcd_logical_block(1);
-        const int wlo = ntx >> 3, nwide = ntx & 7;       // bands 0..nwide-1 have wlo + 1 columns
-        const int wide = nwide * (wlo + 1) * nty;
-        int b, w, r;
-        if (l < wide) { w = wlo + 1; b = l / (w * nty); r = l - b * w * nty; tx = b * w; }
-        else { l -= wide; w = wlo; b = l / (w * nty); r = l - b * w * nty; tx = nwide * (wlo + 1) + b * w; }
-        ty = r / w;
-        tx += r - ty * w;
-    }
     if (a.sub != 0) {
         // decomposed block (pclaw.hip): the tiles inside box = [ty_lo, ty_hi) x [tx_lo, tx_hi) read no ghost cell a
         // neighbour block has to send -- sub 1 = those (they run beside the halo exchange), 2 = the others
@@ -144,11 +115,7 @@ __global__ __launch_bounds__(F_THREADS, F_THREADS == 512 ? (RP::MEQN > 3 ? 2 : 3
             const long g = (long)(y0 + r) * a.pitch + (x0 + c);
 #pragma unroll
             for (int m = 0; m < MEQN; m++) {
-#if PCL_FUSED_NT
-                double2 v = ld_stream2(&a.qin[m * a.plane + g]);
-#else
                 double2 v = *reinterpret_cast<const double2 *>(&a.qin[m * a.plane + g]);
-#endif
                 if (fswz(r) & 1) { const double t = v.x; v.x = v.y; v.y = t; }       // the swizzle swaps the pair in odd rows
                 *reinterpret_cast<double2 *>(&tile[(m * F_ROWS + r) * F_COLS + ((c ^ fswz(r)) & ~1)]) = v;
             }
@@ -206,13 +173,10 @@ __global__ __launch_bounds__(F_THREADS, F_THREADS == 512 ? (RP::MEQN > 3 ? 2 : 3
             double q[MEQN], qn[MEQN];
 #pragma unroll
             for (int m = 0; m < MEQN; m++) q[m] = tile[ftile_at(m, r, cl)];
-            bool nojump = false;     // wave-uniform: the cells go back as they came, nothing to put back
-            if (a.ablate & 1) {      // diagnostic (tools/kbench.py): the kernel's memory traffic without its arithmetic
-#pragma unroll
-                for (int m = 0; m < MEQN; m++) qn[m] = q[m];
-            } else
-                nojump = lane_core<RP, 1, false, FWAVE, false>(q, a.dtd, 1.0, cfl_ok && (F_RX == 1 || y0 + r < a.J), a, qn, cflx,
-                                                               nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &memo);
+            // nojump (wave-uniform): the cells go back as they came, nothing to put back
+            const bool nojump = lane_core<RP, 1, false, FWAVE, false>(q, a.dtd, 1.0, cfl_ok && (F_RX == 1 || y0 + r < a.J), a, qn,
+                                                                      cflx, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                                                      nullptr, &memo);
             if (owned && !nojump) {
 #pragma unroll
                 for (int m = 0; m < MEQN; m++) tile[ftile_at(m, r, cl)] = qn[m];
@@ -248,13 +212,9 @@ __global__ __launch_bounds__(F_THREADS, F_THREADS == 512 ? (RP::MEQN > 3 ? 2 : 3
             double q[MEQN], qn[MEQN];
 #pragma unroll
             for (int m = 0; m < MEQN; m++) q[m] = tile[ftile_at(m, rl, c)];
-            bool nojump = false;
-            if (a.ablate & 1) {
-#pragma unroll
-                for (int m = 0; m < MEQN; m++) qn[m] = q[m];
-            } else
-                nojump = lane_core<RP, 2, false, FWAVE, false>(q, ay.dtd, 1.0, row_cfl && col_ok, ay, qn, cfly,
-                                                               nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &memo);
+            const bool nojump = lane_core<RP, 2, false, FWAVE, false>(q, ay.dtd, 1.0, row_cfl && col_ok, ay, qn, cfly,
+                                                                      nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                                                      nullptr, &memo);
             if (row_owned && col_int && !nojump) {
 #pragma unroll
                 for (int m = 0; m < MEQN; m++) tile[ftile_at(m, rl, c)] = qn[m];

@@ -174,78 +174,49 @@ int launch_sweep3(const SweepLaunch &l, std::string &err) {
     return e == hipSuccess ? PCL_OK : hip_fail(err, "sweep3 launch", e);
 }
 
-// unsplit 3-D step, one direction: slices3_kernel into the scratch planes, then combine3_kernel (classic3.hpp)
+// unsplit 3-D step, one direction: march3p_kernel (classic3.hpp), one launch per direction
 namespace {
 template <class RP, int DIR> int launch_unsplit3_t(const Unsplit3Launch &l, std::string &err) {
+    static_assert(RP::T3_PRESSURE, "the marching kernel takes the pressure-driven pieces");
     const SweepArgs &a = l.a;
     Slices3Args t;
-    for (int k = 0; k < 14; k++) t.scr[k] = l.scr[k];
     t.s_e = l.s_e; t.s_f = l.s_f; t.n_e = l.n_e; t.n_f = l.n_f;
     t.lo_e = a.mbc - 1; t.hi_e = a.mbc + l.m_e; t.lo_f = a.mbc - 1; t.hi_f = a.mbc + l.m_f;
     t.m3 = l.m3; t.m4 = l.m4; t.dty = l.dty; t.dtz = l.dtz;
-    const int ntiles_al = (a.m_al + STRIP - 1) / STRIP;
-    static const int marching = [] { const char *e = getenv("PCL_TUNE_UNSPLIT3"); return e ? atoi(e) : 1; }();
-    if (marching) {
-        // the marching form (classic3.hpp: march3_kernel): no scratch planes, one launch per direction
-        constexpr int NW = 8;
-        March3Args g;
-        g.qsrc = DIR == 1 ? a.qin : l.qacc;
-        g.qacc = l.qacc;
-        const bool e_outer = DIR == 2;
-        g.s_w = e_outer ? l.s_f : l.s_e; g.s_m = e_outer ? l.s_e : l.s_f;
-        g.n_w = e_outer ? l.n_f : l.n_e; g.n_m = e_outer ? l.n_e : l.n_f;
-        g.m_w = e_outer ? l.m_f : l.m_e; g.m_m = e_outer ? l.m_e : l.m_f;
-        g.ntiles_al = ntiles_al;
-        g.ntiles_w = (g.m_w + (NW - 2) - 1) / (NW - 2);
-        // march segments: enough workgroups to fill the 256 CUs in whole rounds, not so many that the two extra source
-        // planes per segment cost more than the idle CUs would
-        const long per = (long)g.ntiles_al * g.ntiles_w;
-        int best = 1;
-        double best_eff = 0.0;
-        for (int ns = 1; ns <= (g.m_m + 7) / 8; ns++) {
-            const int seg = (g.m_m + ns - 1) / ns;
-            const long wgs = per * ((g.m_m + seg - 1) / seg);
-            const double eff = (double)wgs / (256.0 * ((wgs + 255) / 256)) * seg / (seg + 2.0);
-            if (eff > best_eff + 1e-9) { best_eff = eff; best = ns; }
-        }
-        g.seg = (g.m_m + best - 1) / best;
-        const int nseg = (g.m_m + g.seg - 1) / g.seg;
-        if (DIR == 1) {     // the first direction writes interior cells only: the ghost frame of the result := qold's
-            const int I = a.n_al, J = l.n_e, K = l.n_f;
-            hipLaunchKernelGGL(ghost3_copy_kernel, dim3((unsigned)((I + 255) / 256), (unsigned)J, (unsigned)K), dim3(256), 0,
-                               l.stream, a.qin, l.qacc, (int)RP::MEQN, a.plane, I, J, K, l.s_e, a.mbc);
-        }
-        static const int dense = [] { const char *e = getenv("PCL_TUNE_UNSPLIT3_DENSE"); return e ? atoi(e) : 0; }();
-        if (RP::T3_PRESSURE && !dense && l.m3 == 2 && l.m4 == 2)      // the solver default, method(3) = 22, as constants
-            hipLaunchKernelGGL((march3p_kernel<RP, DIR, NW, 22>), dim3((unsigned)(per * nseg)), dim3(NW * WAVE), 0, l.stream, a, t, g);
-        else if (RP::T3_PRESSURE && !dense)
-            hipLaunchKernelGGL((march3p_kernel<RP, DIR, NW>), dim3((unsigned)(per * nseg)), dim3(NW * WAVE), 0, l.stream, a, t, g);
-        else
-            hipLaunchKernelGGL((march3_kernel<RP, DIR, NW>), dim3((unsigned)(per * nseg)), dim3(NW * WAVE), 0, l.stream, a, t, g);
-        hipError_t e = hipGetLastError();
-        return e == hipSuccess ? PCL_OK : hip_fail(err, "march3 launch", e);
+    constexpr int NW = 8;
+    March3Args g;
+    g.qsrc = DIR == 1 ? a.qin : l.qacc;
+    g.qacc = l.qacc;
+    const bool e_outer = DIR == 2;
+    g.s_w = e_outer ? l.s_f : l.s_e; g.s_m = e_outer ? l.s_e : l.s_f;
+    g.n_w = e_outer ? l.n_f : l.n_e; g.n_m = e_outer ? l.n_e : l.n_f;
+    g.m_w = e_outer ? l.m_f : l.m_e; g.m_m = e_outer ? l.m_e : l.m_f;
+    g.ntiles_al = (a.m_al + STRIP - 1) / STRIP;
+    g.ntiles_w = (g.m_w + (NW - 2) - 1) / (NW - 2);
+    // march segments: enough workgroups to fill the 256 CUs in whole rounds, not so many that the two extra source
+    // planes per segment cost more than the idle CUs would
+    const long per = (long)g.ntiles_al * g.ntiles_w;
+    int best = 1;
+    double best_eff = 0.0;
+    for (int ns = 1; ns <= (g.m_m + 7) / 8; ns++) {
+        const int seg = (g.m_m + ns - 1) / ns;
+        const long wgs = per * ((g.m_m + seg - 1) / seg);
+        const double eff = (double)wgs / (256.0 * ((wgs + 255) / 256)) * seg / (seg + 2.0);
+        if (eff > best_eff + 1e-9) { best_eff = eff; best = ns; }
     }
-    // workgroups of 4 strips: 4 consecutive y-like rows (x direction) / 4 consecutive i (y, z directions; classic3.hpp)
-    const int n4 = DIR == 2 ? l.m_f + 2 : l.m_e + 2, nother = DIR == 2 ? l.m_e + 2 : l.m_f + 2;
-    hipLaunchKernelGGL((slices3_kernel<RP, DIR>), dim3((unsigned)ntiles_al * ((n4 + 3) / 4), (unsigned)nother), dim3(256), 0,
-                       l.stream, a, t, ntiles_al);
+    g.seg = (g.m_m + best - 1) / best;
+    const int nseg = (g.m_m + g.seg - 1) / g.seg;
+    if (DIR == 1) {     // the first direction writes interior cells only: the ghost frame of the result := qold's
+        const int I = a.n_al, J = l.n_e, K = l.n_f;
+        hipLaunchKernelGGL(ghost3_copy_kernel, dim3((unsigned)((I + 255) / 256), (unsigned)J, (unsigned)K), dim3(256), 0,
+                           l.stream, a.qin, l.qacc, (int)RP::MEQN, a.plane, I, J, K, l.s_e, a.mbc);
+    }
+    if (l.m3 == 2 && l.m4 == 2)      // the solver default, method(3) = 22, as constants
+        hipLaunchKernelGGL((march3p_kernel<RP, DIR, NW, 22>), dim3((unsigned)(per * nseg)), dim3(NW * WAVE), 0, l.stream, a, t, g);
+    else
+        hipLaunchKernelGGL((march3p_kernel<RP, DIR, NW>), dim3((unsigned)(per * nseg)), dim3(NW * WAVE), 0, l.stream, a, t, g);
     hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(err, "slices3 launch", e);
-    Combine3Args c;
-    for (int k = 0; k < 14; k++) c.scr[k] = l.scr[k];
-    c.qsrc = a.qin; c.qacc = l.qacc; c.plane = a.plane; c.s_al = a.s_al; c.s_e = l.s_e; c.s_f = l.s_f;
-    c.n_al = a.n_al; c.n_e = l.n_e; c.n_f = l.n_f; c.mbc = a.mbc; c.m_al = a.m_al; c.m_e = l.m_e; c.m_f = l.m_f;
-    c.meqn = RP::MEQN; c.dtd = a.dtd; c.dty = l.dty; c.dtz = l.dtz;
-    c.e_outer = DIR == 2 ? 1 : 0;       // step3.f: y sweeps loop k (their y-like index) outside, x and z sweeps inside
-    c.first = DIR == 1 ? 1 : 0;
-    c.dir = DIR;
-    const int ni = DIR == 1 ? a.n_al : (DIR == 2 ? l.n_f : l.n_e);     // physical extents (i, j, k) of the block
-    const int nj = DIR == 1 ? l.n_e : (DIR == 2 ? a.n_al : l.n_f);
-    const int nk = DIR == 1 ? l.n_f : (DIR == 2 ? l.n_e : a.n_al);
-    hipLaunchKernelGGL(combine3_kernel, dim3((unsigned)((ni + 255) / 256), (unsigned)nj, (unsigned)nk), dim3(256), 0,
-                       l.stream, c);
-    e = hipGetLastError();
-    return e == hipSuccess ? PCL_OK : hip_fail(err, "combine3 launch", e);
+    return e == hipSuccess ? PCL_OK : hip_fail(err, "march3 launch", e);
 }
 }  // namespace
 
@@ -312,7 +283,6 @@ template <class RP, int UX, int UY> int launch_unsplit_u(const SweepLaunch &l, c
     } else {
         const int nti = (a.mx + (UY - 2) - 1) / (UY - 2);
         const int ntj = (a.my + STRIP - 1) / STRIP;
-        static const int ymarch = [] { const char *e = getenv("PCL_TUNE_YMARCH"); return e ? atoi(e) : 1; }();
         if constexpr (RP::NAUX == 0 && UY == 16) {
             // marching y phase (classic.hpp: unsplit_ym_kernel): segments of `seg` lines of 16 columns; enough
             // workgroups for ~4 rounds over the 256 CUs, warm-up step of a segment <= 1/8 of its work
@@ -324,23 +294,18 @@ template <class RP, int UX, int UY> int launch_unsplit_u(const SweepLaunch &l, c
             nseg = (nlines + seg - 1) / seg;
             // a small grid cannot give every CU two marching workgroups (1024^2: 18 bands x 8 segments = 144; 2048^2: 560): the tile
             // kernel's many independent workgroups are the better shape there (C2, acoustics 1024^2: 103 vs 131 us per step; 2048^2: 240 vs 249; 4096^2: 731 vs 702, same box)
-            const bool big = (long)ntj * nseg >= 1024 || ymarch == 8 || ymarch == 16;
-            if (ymarch && big && a.mcapa <= 0 && (a.src_id == 0 || std::is_same<RP, Euler5>::value)) {
+            const bool big = (long)ntj * nseg >= 1024;
+            if (big && a.mcapa <= 0 && (a.src_id == 0 || std::is_same<RP, Euler5>::value)) {
                 // wavefronts per workgroup: 8 (two slices each per step, 256 VGPRs: no spills) for the register-heavy
-                // Euler core, 16 for the small systems; PCL_TUNE_YMARCH=16 / 8 forces one
-                constexpr bool heavy = RP::MEQN >= 5;
-                const bool eight = ymarch == 8 || (ymarch != 16 && heavy);
+                // Euler core, 16 for the small systems
+                constexpr int NWY = RP::MEQN >= 5 ? 8 : 16;
                 if (a.src_id != 0) {
-                    if constexpr (std::is_same<RP, Euler5>::value) {
-                        if (eight) hipLaunchKernelGGL((unsplit_ym_kernel<RP, false, true, 8>), dim3((unsigned)ntj * nseg), dim3(8 * WAVE), 0, l.stream, a, ntj, seg, qx);
-                        else hipLaunchKernelGGL((unsplit_ym_kernel<RP, false, true, 16>), dim3((unsigned)ntj * nseg), dim3(16 * WAVE), 0, l.stream, a, ntj, seg, qx);
-                    }
-                } else if (eight)
-                    hipLaunchKernelGGL((unsplit_ym_kernel<RP, IsFwave<RP>::value, false, 8>), dim3((unsigned)ntj * nseg),
-                                       dim3(8 * WAVE), 0, l.stream, a, ntj, seg, qx);
-                else
-                    hipLaunchKernelGGL((unsplit_ym_kernel<RP, IsFwave<RP>::value, false, 16>), dim3((unsigned)ntj * nseg),
-                                       dim3(16 * WAVE), 0, l.stream, a, ntj, seg, qx);
+                    if constexpr (std::is_same<RP, Euler5>::value)
+                        hipLaunchKernelGGL((unsplit_ym_kernel<RP, false, true, NWY>), dim3((unsigned)ntj * nseg),
+                                           dim3(NWY * WAVE), 0, l.stream, a, ntj, seg, qx);
+                } else
+                    hipLaunchKernelGGL((unsplit_ym_kernel<RP, IsFwave<RP>::value, false, NWY>), dim3((unsigned)ntj * nseg),
+                                       dim3(NWY * WAVE), 0, l.stream, a, ntj, seg, qx);
                 hipError_t e = hipGetLastError();
                 if (e != hipSuccess) return hip_fail(err, "unsplit y (marching) launch", e);
                 return PCL_OK;
@@ -366,24 +331,15 @@ template <class RP, int UX, int UY> int launch_unsplit_u(const SweepLaunch &l, c
     return e == hipSuccess ? PCL_OK : hip_fail(err, "unsplit launch", e);
 }
 template <class RP> int launch_unsplit_t(const SweepLaunch &l, const double *qx, std::string &err) {
-    static const int var = [] { const char *e = getenv("PCL_TUNE_UNSPLIT"); return e ? atoi(e) : 0; }();
-    switch (var) {   // slices per workgroup in the x / y phase (tools/kbench.py A/B)
-    case 1: return launch_unsplit_u<RP, 8, 8>(l, qx, err);
-    case 2: return launch_unsplit_u<RP, 16, 8>(l, qx, err);
-    case 3: return launch_unsplit_u<RP, 8, 16>(l, qx, err);
-    case 4: return launch_unsplit_u<RP, 12, 12>(l, qx, err);
-    case 5: return launch_unsplit_u<RP, 16, 16>(l, qx, err);
-    default:
-        // 16 wavefronts per workgroup leave 128 VGPRs per lane.  The Euler kernels spill ~20 registers there and are
-        // still 4 % faster than with 12 wavefronts (170 VGPRs, no spills) -- except with a capacity function, where the
-        // spill stores reach HBM (2.4 GB written per x launch at 4096^2 for 0.67 GB of results,
-        // profiles/r02_pmc_hbm.json) at equal speed: 12 there.  The sphere solver (9 + 27 aux values per lane) takes 8.
-        if constexpr (RP::NAUX >= 9) return launch_unsplit_u<RP, 8, 8>(l, qx, err);
-        else if constexpr (RP::MEQN >= 5) {
-            if (l.a.mcapa > 0) return launch_unsplit_u<RP, 12, 12>(l, qx, err);
-            return launch_unsplit_u<RP, 16, 16>(l, qx, err);
-        } else return launch_unsplit_u<RP, 16, 16>(l, qx, err);
-    }
+    // slices per workgroup in the x / y phase.  16 wavefronts per workgroup leave 128 VGPRs per lane.  The Euler kernels
+    // spill ~20 registers there and are still 4 % faster than with 12 wavefronts (170 VGPRs, no spills) -- except with a
+    // capacity function, where the spill stores reach HBM (2.4 GB written per x launch at 4096^2 for 0.67 GB of results,
+    // profiles/r02_pmc_hbm.json) at equal speed: 12 there.  The sphere solver (9 + 27 aux values per lane) takes 8.
+    if constexpr (RP::NAUX >= 9) return launch_unsplit_u<RP, 8, 8>(l, qx, err);
+    else if constexpr (RP::MEQN >= 5) {
+        if (l.a.mcapa > 0) return launch_unsplit_u<RP, 12, 12>(l, qx, err);
+        return launch_unsplit_u<RP, 16, 16>(l, qx, err);
+    } else return launch_unsplit_u<RP, 16, 16>(l, qx, err);
 }
 }  // namespace
 

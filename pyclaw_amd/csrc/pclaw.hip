@@ -45,17 +45,14 @@ struct pcl_solver {
     double *aux = nullptr;
     double *sreg[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // SharpClaw registers (0 aliases q)
     int sel = 0;          // register the put/get/bc/strip/halo calls act on
-    double *scr3[14] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                        nullptr, nullptr, nullptr};   // unsplit 3-D slice pieces
     double *stage = nullptr;  // AoS staging for host transfers (qbc-sized)
     size_t stage_bytes = 0;
     unsigned long long *cfl_dev = nullptr;
     unsigned long long *cfl_host = nullptr;  // pinned, device-visible: [0] = value, [1] = sequence number
     unsigned long long *cfl_host_dev = nullptr;  // the same words as the device sees them
     unsigned long long cfl_seq = 0;
-    int cfl_poll = 1;     // PCL_CFL_POLL=0: D2H copy + event wait instead of the mapped word
     hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr, ev_cfl = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
     double **undo_slot = nullptr;  // buffer that holds the pre-step state
     int fused_src = 0;    // source term applied inside the last pass of the dim-split step (pcl_fuse_source)
     double fused_src_p[2] = {0.0, 0.0};
@@ -290,10 +287,6 @@ SweepArgs make_args(pcl_solver *s, const double *qin, double *qout, int ids, dou
     a.src_id = (ids == 2 && s->cfg.ndim == 2) ? s->fused_src : 0;      // y pass (dim-split) / y phase (unsplit)
     a.src_p[0] = s->fused_src_p[0]; a.src_p[1] = s->fused_src_p[1];
     for (int k = 0; k < 4; k++) { a.vbc[k] = s->vbc[k]; for (int m = 0; m < 8; m++) a.vconst[k][m] = s->vconst[k][m]; }
-    static const int ablate = [] { const char *e = getenv("PCL_TUNE_ABLATE"); return e ? atoi(e) : 0; }();
-    a.ablate = ablate;
-    static const int xcd = [] { const char *e = getenv("PCL_TUNE_XCD"); return e ? atoi(e) : 5; }();
-    a.xcd = xcd;
     return a;
 }
 
@@ -548,23 +541,12 @@ int do_sweep3(pcl_solver *s, const double *qin, double *qout, int dir, double dt
     return rc;
 }
 
-// unsplit 3-D step (step3.f): for x, y, z in turn, every slice's pieces into scratch planes and the ordered combine into
-// t1 (kernels in classic3.hpp).  All three directions read the same qold = q.
+// unsplit 3-D step (step3.f): for x, y, z in turn, every slice's pieces applied in the reference's order to t1
+// (march3p_kernel, classic3.hpp).  All three directions read the same qold = q.
 int do_unsplit3(pcl_solver *s, double dt) {
     const int m3 = s->cfg.method[2] / 10, m4 = s->cfg.method[2] - 10 * m3;
     if (m3 < 0 || m3 > 2 || m4 < 0 || m4 > 2 || (m4 > 0 && m3 == 0))
         return fail(PCL_EINVAL, "3-D order_trans must be 0, 10, 11, 20, 21 or 22 (flux3.f:46-73)");
-    const size_t qbytes = ((size_t)s->total + 16) * sizeof(double);
-    // the marching kernels (classic3.hpp) keep the slices' pieces in registers and LDS; only the scratch-plane form
-    // (PCL_TUNE_UNSPLIT3=0, kept for A/B runs) needs the 14 plane sets
-    static const int marching = [] { const char *e = getenv("PCL_TUNE_UNSPLIT3"); return e ? atoi(e) : 1; }();
-    for (int k = 0; k < 14 && !marching; k++) {
-        if (s->scr3[k]) continue;
-        double *raw = nullptr;
-        HIP_TRY(hipMalloc((void **)&raw, qbytes));
-        HIP_TRY(hipMemsetAsync(raw, 0, qbytes, s->stream));
-        s->scr3[k] = raw + s->lead;
-    }
     const int mbc = s->cfg.mbc;
     const long st[3] = {1, s->pitch, s->pitch * s->J};
     const int n[3] = {s->I, s->J, s->K};
@@ -577,7 +559,6 @@ int do_unsplit3(pcl_solver *s, double dt) {
         l.a.dx = s->cfg.d[d];
         l.a.s_al = st[d]; l.a.n_al = n[d]; l.a.m_al = s->cfg.n[d];
         l.a.vbc_on = 0;
-        for (int k = 0; k < 14; k++) l.scr[k] = s->scr3[k];
         l.qacc = s->t1;
         l.s_e = st[e]; l.s_f = st[f]; l.n_e = n[e]; l.n_f = n[f]; l.m_e = s->cfg.n[e]; l.m_f = s->cfg.n[f];
         l.m3 = m3; l.m4 = m4;
@@ -661,31 +642,21 @@ int read_cfl(pcl_solver *s, double *cfl) {
     return read_cfl_end(s, cfl);
 }
 int read_cfl_end(pcl_solver *s, double *cfl) {
-    if (s->cfl_poll) {
-        // One single-thread kernel behind the sweeps hands the word over through host memory the device can
-        // write (the value, then a sequence number with release semantics at system scope) and re-zeroes it;
-        // the host polls the sequence number.  ~3 us per step less than a D2H copy + event wait.
-        const unsigned long long seq = ++s->cfl_seq;
-        hipLaunchKernelGGL(cfl_handover, dim3(1), dim3(1), 0, s->stream, s->cfl_dev, s->cfl_host_dev, seq);
-        HIP_TRY(hipGetLastError());
-        unsigned long long *flag = s->cfl_host + 1;
-        long spins = 0;
-        while (__atomic_load_n(flag, __ATOMIC_ACQUIRE) != seq) {
-            if (++spins > 4000000) {   // a long while without an answer: let the runtime report what happened
-                HIP_TRY(hipStreamSynchronize(s->stream));
-                if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) != seq) return fail(PCL_EHIP, "CFL hand-over never arrived");
-                break;
-            }
-            __builtin_ia32_pause();
+    // One single-thread kernel behind the sweeps hands the word over through host memory the device can
+    // write (the value, then a sequence number with release semantics at system scope) and re-zeroes it;
+    // the host polls the sequence number.  ~3 us per step less than a D2H copy + event wait.
+    const unsigned long long seq = ++s->cfl_seq;
+    hipLaunchKernelGGL(cfl_handover, dim3(1), dim3(1), 0, s->stream, s->cfl_dev, s->cfl_host_dev, seq);
+    HIP_TRY(hipGetLastError());
+    unsigned long long *flag = s->cfl_host + 1;
+    long spins = 0;
+    while (__atomic_load_n(flag, __ATOMIC_ACQUIRE) != seq) {
+        if (++spins > 4000000) {   // a long while without an answer: let the runtime report what happened
+            HIP_TRY(hipStreamSynchronize(s->stream));
+            if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) != seq) return fail(PCL_EHIP, "CFL hand-over never arrived");
+            break;
         }
-    } else {
-        HIP_TRY(hipMemcpyAsync(s->cfl_host, s->cfl_dev, sizeof(unsigned long long), hipMemcpyDeviceToHost,
-                               s->stream));
-        HIP_TRY(hipEventRecord(s->ev_cfl, s->stream));
-        // Invariant: the CFL word is zero whenever no step is in flight.  Re-zeroing it here, behind the
-        // read-back, keeps the reset off the critical path (the host only waits for the copy).
-        HIP_TRY(hipMemsetAsync(s->cfl_dev, 0, sizeof(unsigned long long), s->stream));
-        HIP_TRY(hipEventSynchronize(s->ev_cfl));
+        __builtin_ia32_pause();
     }
     double v;
     memcpy(&v, s->cfl_host, sizeof(double));
@@ -846,10 +817,8 @@ int pcl_create(const pcl_config *cfg, pcl_solver **out) {
     if (e == hipSuccess) e = hipMalloc((void **)&s->cfl_dev, 64);
     if (e == hipSuccess) e = hipHostMalloc((void **)&s->cfl_host, 64, hipHostMallocDefault);
     if (e == hipSuccess) { memset(s->cfl_host, 0, 64); e = hipHostGetDevicePointer((void **)&s->cfl_host_dev, s->cfl_host, 0); }
-    { const char *p = getenv("PCL_CFL_POLL"); s->cfl_poll = p ? atoi(p) : 1; }
     if (e == hipSuccess) e = hipEventCreate(&s->ev0);
     if (e == hipSuccess) e = hipEventCreate(&s->ev1);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&s->ev_cfl, hipEventDisableTiming);
     if (e == hipSuccess) e = hipMemsetAsync(s->cfl_dev, 0, 64, s->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
     if (e != hipSuccess) {
@@ -875,15 +844,12 @@ void pcl_destroy(pcl_solver *s) {
     for (auto &e : s->evpool) hipEventDestroy(e);
     for (double *p : {s->q, s->t1, s->t2, s->t3, s->bak, s->aux, s->stage})
         if (p) hipFree(p - s->lead);
-    for (double *p : s->scr3)
-        if (p) hipFree(p - s->lead);
     for (int k = 1; k < 5; k++)
         if (s->sreg[k]) hipFree(s->sreg[k] - s->lead);
     hipFree(s->cfl_dev);
     if (s->cfl_host) hipHostFree(s->cfl_host);
     if (s->ev0) hipEventDestroy(s->ev0);
     if (s->ev1) hipEventDestroy(s->ev1);
-    if (s->ev_cfl) hipEventDestroy(s->ev_cfl);
     if (s->stream) hipStreamDestroy(s->stream);
     delete s;
 }

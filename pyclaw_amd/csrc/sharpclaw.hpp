@@ -220,11 +220,9 @@ template <int IXY, int TA = T_ACROSS_S> __device__ __forceinline__ int stile_at(
     return IXY == 1 ? (m * TA + ac) * WAVE + al : (m * WAVE + al) * TA + (ac ^ ((al >> 1) & (TA - 1)));
 }
 
-#ifndef PCL_SHARP_OCC
-#define PCL_SHARP_OCC 4     // workgroups per CU the register budget is sized for (A/B: build with -DPCL_SHARP_OCC=3)
-#endif
+// register budget: 4 workgroups per CU (3 with capacity); sized for 3 the step is 2 % slower
 template <class RP, int IXY, bool CAPA, int LIM, int K = 3, bool SRC = false>
-__global__ __launch_bounds__(256, CAPA ? 3 : PCL_SHARP_OCC) void sharp_kernel(SweepArgs a, int ntiles_across, int ntiles_along) {
+__global__ __launch_bounds__(256, CAPA ? 3 : 4) void sharp_kernel(SweepArgs a, int ntiles_across, int ntiles_along) {
     constexpr int MEQN = RP::MEQN, MWAVES = RP::MWAVES;
     constexpr int SHALO = K, SSTRIP = sstrip(K);      // a.mbc == K (checked by the launcher)
     static_assert(K == 3 || LIM == 2, "orders above 5 exist for the PyWENO form only");
@@ -384,14 +382,6 @@ __global__ __launch_bounds__(256, CAPA ? 3 : PCL_SHARP_OCC) void sharp_kernel(Sw
                 // last pass of a stage: the RK combination of sharpclaw.py:168-206 (same expressions as rk_kernel).
                 // Branch-free on purpose: with a scalar branch per op the ROCm 7.2 backend left the store base
                 // of the op-5 path undefined in the 1-D instantiation (memory fault at address 0).
-#ifdef PCL_SHARP_BRANCHY   /* diagnostic build only: the form that faulted in round 1 */
-                switch (a.rk_op) {
-                case 0: a.qout[at] = dq; break;
-                case 1: a.rk_d[at] = a.rk_a[at] + dq / a.rk_ca; break;
-                case 2: a.rk_d[at] = a.rk_ca * a.rk_a[at] + a.rk_cb * (a.rk_b[at] + dq); break;
-                case 5: a.rk_d[at] = a.rk_a[at] + a.rk_cb * a.rk_b[at] + a.rk_cc * dq; break;
-                }
-#else
                 double r = dq;
                 if (a.rk_op != 0) {
                     const double av = a.rk_a[at], bv = a.rk_b[at];
@@ -413,7 +403,6 @@ __global__ __launch_bounds__(256, CAPA ? 3 : PCL_SHARP_OCC) void sharp_kernel(Sw
                 }
                 double *dst = a.rk_op != 0 ? a.rk_d : a.qout;
                 dst[at] = r;
-#endif
             }
         }
     }

@@ -70,8 +70,6 @@ struct SweepArgs {
     double dt, dx;    // separately, for the 1-D capa form dt/(dx*capa) (step1.f:70)
     RpParams par;
     unsigned long long *cfl;  // device word holding the running max (as ordered bits)
-    int xcd;          // XCD-aware block order in the kernels whose tiles share cache lines (classic.hpp)
-    int ablate;       // diagnostic only (tools/kbench.py): bit0 = skip the arithmetic (copy through)
     // "virtual ghost cells": the x pass of the dim-split step evaluates the boundary conditions while it
     // loads (a ghost cell is an index remap of an interior cell, or a constant): no ghost-fill launches.
     // vbc[2*idim+side] = -1 (read memory) | PCL_BC_OUTFLOW | PERIODIC | REFLECTING | PCL_BC_CUSTOM (= vconst)
@@ -106,10 +104,9 @@ struct SweepArgs {
     double src_p[2];
 };
 
-// unsplit 3-D (classic3.hpp): one direction's slices into 14 scratch plane sets, then the ordered combine
+// unsplit 3-D (classic3.hpp): one direction's slices, applied in the reference's order by the marching kernel
 struct Unsplit3Launch {
     SweepArgs a;          // qin = qold; s_al/n_al/m_al, dtd, par, mthlim, order, cfl as for sweep3
-    double *scr[14];
     double *qacc;         // the new state being accumulated
     long s_e, s_f;
     int n_e, n_f, m_e, m_f;

@@ -4,5 +4,4 @@ timeout -k 10 600 python -m pytest tests/test_gpu_classic.py tests/test_gpu_apps
 $B | pick default &&
 $B --state dense | pick dense &&
 $B --state developed | pick developed &&
-PCL_TUNE_ABLATE=1 $B | pick copy_only &&
 PCL_TUNE_FUSED_STEP=0 $B | pick twopass

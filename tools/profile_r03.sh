@@ -5,8 +5,7 @@
 #      roofline.traffic from it; written into the box's profiles/ first, so the lines of step 2 carry THIS build's bytes);
 #   2. rocprofv3 --kernel-trace --stats of the same commands, the bench JSON of the SAME run next to it;
 #   3. SQ issue counters of the dense state (one-kernel step; PCL_TUNE_FUSED_STEP=0: the two passes) and of the SharpClaw
-#      right-hand side, and SQ_LDS_BANK_CONFLICT of the y pass with the swizzled tile (the build)
-#      and with the padded round-1 tile (build/libs/libpyclaw_amd_ypad.so, -DPCL_YTILE_PAD=1).
+#      right-hand side, and SQ_LDS_BANK_CONFLICT of the y pass with the swizzled tile.
 # Usage: tools/profile_r03.sh <tag> <commit>
 set -e
 TAG=${1:-r03}
@@ -67,9 +66,6 @@ rocprofv3 --pmc $SQA --kernel-trace --output-format csv -d $OUT/sq_sharp_a -- py
 export PCL_TUNE_FUSED_STEP=0
 rocprofv3 --pmc $SQA --kernel-trace --output-format csv -d $OUT/sq_2p_a -- python3 ${CMD[exact_dense]} --steps 3 --warmup 1 > $OUT/sq_2p_a.log 2>&1
 rocprofv3 --pmc $SQB --kernel-trace --output-format csv -d $OUT/sq_2p_b -- python3 ${CMD[exact_dense]} --steps 3 --warmup 1 > $OUT/sq_2p_b.log 2>&1
-export PCL_LIB_OVERRIDE=$R/build/libs/libpyclaw_amd_ypad.so
-rocprofv3 --pmc $SQB --kernel-trace --output-format csv -d $OUT/sq_2p_b_ypad -- python3 ${CMD[exact_dense]} --steps 3 --warmup 1 > $OUT/sq_2p_b_ypad.log 2>&1
-unset PCL_LIB_OVERRIDE
 export PCL_TUNE_FUSED_STEP=1
 echo "sq done"
 python3 - $OUT $TAG $COMMIT <<'PY'
@@ -79,10 +75,8 @@ with open("%s/summary/%s_pmc_sq.txt" % (out, tag), "w") as fo:
     fo.write("rocprofv3 --pmc <SQ counters> --kernel-trace -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-states "
              "--state dense   (commit %s)\n  sq_a / sq_b: --math exact (the one-kernel step), two passes of 8 counters;  sq_fast_a: --math fast;\n"
              "  sq_sharp_a: bench.py --solver sharpclaw (the SharpClaw right-hand side);\n"
-             "  sq_2p_a / sq_2p_b: PCL_TUNE_FUSED_STEP=0, the x pass + y pass form of the same step;\n"
-             "  sq_2p_b_ypad: the sq_2p_b counters with build/libs/libpyclaw_amd_ypad.so (-DPCL_YTILE_PAD=1: the y-pass tile padded to 17 "
-             "doubles per row instead of XOR-swizzled) -- the before / after pair for SQ_LDS_BANK_CONFLICT\n" % commit)
-    for sub in ("sq_a", "sq_b", "sq_fast_a", "sq_sharp_a", "sq_2p_a", "sq_2p_b", "sq_2p_b_ypad"):
+             "  sq_2p_a / sq_2p_b: PCL_TUNE_FUSED_STEP=0, the x pass + y pass form of the same step\n" % commit)
+    for sub in ("sq_a", "sq_b", "sq_fast_a", "sq_sharp_a", "sq_2p_a", "sq_2p_b"):
         acc = collections.defaultdict(lambda: collections.defaultdict(float)); n = collections.defaultdict(int)
         for f in glob.glob(out + "/%s/**/*counter_collection.csv" % sub, recursive=True):
             for r in csv.DictReader(open(f)):
