@@ -331,6 +331,12 @@ int pcl_kernel_timing_read(pcl_solver *s, double *ms_total, long *launches);
  * and sampled launch count of the one-kernel step (pcl_kernel_timing_read holds the two passes), and the steps each
  * form has run. */
 int pcl_step_form_stats(pcl_solver *s, double *ms_total, long *launches, long *steps_one_kernel, long *steps_two_pass);
+/* Quiet tiles of the one-kernel step (on by default): a tile whose update was the identity in the previous step, with
+ * its 8 neighbours, is not computed again -- same bits, same Courant number.  enable = 0 computes every tile.  Any call
+ * other than the step itself and read-only calls makes the next step compute every tile. */
+int pcl_tile_skip(pcl_solver *s, int enable);
+/* tiles the last one-kernel step computed and skipped (both 0 when no one-kernel step of the whole block has run) */
+int pcl_tile_skip_stats(pcl_solver *s, long *computed, long *skipped);
 /* hyperbolic steps (classic) / right-hand sides (SharpClaw) attempted since pcl_create, rejected ones included */
 int pcl_step_count(pcl_solver *s, long *steps);
 

@@ -58,8 +58,21 @@ __device__ __forceinline__ int wave_row(int w, int k) {
 __device__ __forceinline__ int fswz(int r) { return F_ROWS >= 32 ? r : r * (32 / F_ROWS); }
 __device__ __forceinline__ int ftile_at(int m, int r, int c) { return (m * F_ROWS + r) * F_COLS + (c ^ fswz(r)); }
 
+// Quiet tiles.  A tile is quiet in a launch when every x-sweep and every y-sweep wavefront took the
+// no-jump shortcut (and, under the fused source, every cell it stored satisfies euler_radial_source_fixed): its owned
+// cells leave the kernel as they came, whatever dt.  tq_out[tile] gets one byte per wavefront (TQ_QUIET or 0), tq_cfl
+// the quiet wavefront's largest |speed| of each sweep, before the multiplication by dt/d.  With tq_skip set, tq_in
+// holds the words of the previous launch, which ran on the swapped buffer pair (its output is this launch's input, its
+// input this launch's output) with the same solver: a tile off the frame whose 3 x 3 neighbourhood was quiet there
+// reads the same 16 x 64 cells again, would be quiet again, and its owned cells in qout already hold the result.
+constexpr unsigned TQ_QUIET = 1u, TQ_ALL = 0x01010101u;
+static_assert(F_WAVES == 4, "one quiet byte per wavefront in a 32-bit word");
+
 template <class RP, bool FWAVE, bool SRC>
-__global__ __launch_bounds__(F_THREADS, 1024 / F_THREADS) void step2ds_kernel(SweepArgs a, int ntx, int nty) {
+__global__ __launch_bounds__(F_THREADS, 1024 / F_THREADS) void step2ds_kernel(SweepArgs a, int ntx, int nty,
+                                                                              const unsigned *__restrict__ tq_in,
+                                                                              unsigned *__restrict__ tq_out,
+                                                                              double2 *__restrict__ tq_cfl, int tq_skip) {
     constexpr int MEQN = RP::MEQN;
     static_assert(RP::NAUX == 0, "solvers without aux arrays");
     static_assert(!SRC || MEQN == 5, "fused source: the Euler solver");
@@ -102,6 +115,27 @@ __global__ __launch_bounds__(F_THREADS, 1024 / F_THREADS) void step2ds_kernel(Sw
     }
     const int x0 = a.mbc - HALO + tx * F_OWN_C;      // array column of tile column 0 (a.mbc == HALO: checked by the launcher)
     const int y0 = a.mbc - HALO + ty * F_OWN_R;
+    const int tile_id = ty * ntx + tx;
+
+    // ---- quiet-tile skip: 9 scalar loads, the whole workgroup returns before any barrier ------------------------
+    // (off the frame: the 16 x 64 load reads interior cells only, so 1 <= tx < ntx - 1 and 1 <= ty < nty - 1)
+    if (tq_skip && x0 >= a.mbc && y0 >= a.mbc && x0 + F_COLS <= a.mbc + a.mx && y0 + F_ROWS <= a.mbc + a.my) {
+        const int wq = __builtin_amdgcn_readfirstlane(threadIdx.x / WAVE);
+        const double2 c = tq_cfl[tile_id * F_WAVES + wq];
+        const unsigned *w = tq_in + tile_id - ntx - 1;
+        bool quiet = true;
+#pragma unroll
+        for (int dy = 0; dy < 3; dy++)
+#pragma unroll
+            for (int dx = 0; dx < 3; dx++) quiet = quiet & (w[dy * ntx + dx] == TQ_ALL);
+        if (quiet) {
+            if (threadIdx.x == 0) tq_out[tile_id] = TQ_ALL;
+            // the computed path publishes max over lanes of max(fl(dtd * cflx), fl(dtd_t * cfly)); rounding is monotone
+            // and dt/d > 0, so max_l fl(d * s_l) = fl(d * max_l s_l): these are the same bits
+            cfl_publish(a.cfl, dmax(a.dtd * c.x, a.dtd_t * c.y));
+            return;
+        }
+    }
 
     // ---- load ----------------------------------------------------------------------------------------------------
     const bool full_tile = x0 + F_COLS <= a.I && y0 + F_ROWS <= a.J;
@@ -158,6 +192,7 @@ __global__ __launch_bounds__(F_THREADS, 1024 / F_THREADS) void step2ds_kernel(Sw
 
     const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x / WAVE;
     double cflx = 0.0, cfly = 0.0;
+    bool quiet = true;                                // wave-uniform: every sweep of this wavefront took the shortcut
 
     // ---- x sweeps of the tile's rows (step2ds.f:83-146) --------------------------------------------------------
     {
@@ -177,6 +212,7 @@ __global__ __launch_bounds__(F_THREADS, 1024 / F_THREADS) void step2ds_kernel(Sw
             const bool nojump = lane_core<RP, 1, false, FWAVE, false>(q, a.dtd, 1.0, cfl_ok && (F_RX == 1 || y0 + r < a.J), a, qn,
                                                                       cflx, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
                                                                       nullptr, &memo);
+            quiet = quiet && nojump;
             if (owned && !nojump) {
 #pragma unroll
                 for (int m = 0; m < MEQN; m++) tile[ftile_at(m, r, cl)] = qn[m];
@@ -215,6 +251,7 @@ __global__ __launch_bounds__(F_THREADS, 1024 / F_THREADS) void step2ds_kernel(Sw
             const bool nojump = lane_core<RP, 2, false, FWAVE, false>(q, ay.dtd, 1.0, row_cfl && col_ok, ay, qn, cfly,
                                                                       nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
                                                                       nullptr, &memo);
+            quiet = quiet && nojump;
             if (row_owned && col_int && !nojump) {
 #pragma unroll
                 for (int m = 0; m < MEQN; m++) tile[ftile_at(m, rl, c)] = qn[m];
@@ -226,6 +263,7 @@ __global__ __launch_bounds__(F_THREADS, 1024 / F_THREADS) void step2ds_kernel(Sw
     // ---- store: the tile's own interior cells --------------------------------------------------------------------
     const bool all_interior = full_tile && x0 + HALO >= a.mbc && x0 + HALO + F_OWN_C <= a.mbc + a.mx && y0 + HALO >= a.mbc &&
                               y0 + HALO + F_OWN_R <= a.mbc + a.my;
+    bool src_fixed = true;                            // every cell this lane stored is a fixed point of the source
     if (all_interior) {
         constexpr int PAIRS = F_OWN_C / 2, SLOTS = PAIRS * F_OWN_R;
 #pragma unroll
@@ -242,6 +280,8 @@ __global__ __launch_bounds__(F_THREADS, 1024 / F_THREADS) void step2ds_kernel(Sw
                 }
                 if constexpr (SRC) {
                     const double2 rad = *reinterpret_cast<const double2 *>(&a.aux[g]);
+                    src_fixed = src_fixed && euler_radial_source_fixed(v[0].x, v[1].x, v[2].x, v[3].x, rad.x) &&
+                                euler_radial_source_fixed(v[0].y, v[1].y, v[2].y, v[3].y, rad.y);
                     euler_radial_source(v[0].x, v[1].x, v[2].x, v[3].x, rad.x, a.dt, a.src_p[0], a.src_p[1]);
                     euler_radial_source(v[0].y, v[1].y, v[2].y, v[3].y, rad.y, a.dt, a.src_p[0], a.src_p[1]);
                 }
@@ -259,11 +299,29 @@ __global__ __launch_bounds__(F_THREADS, 1024 / F_THREADS) void step2ds_kernel(Sw
                 double v[MEQN];
 #pragma unroll
                 for (int m = 0; m < MEQN; m++) v[m] = tile[ftile_at(m, r, c)];
-                if constexpr (SRC) euler_radial_source(v[0], v[1], v[2], v[3], a.aux[g], a.dt, a.src_p[0], a.src_p[1]);
+                if constexpr (SRC) {
+                    src_fixed = src_fixed && euler_radial_source_fixed(v[0], v[1], v[2], v[3], a.aux[g]);
+                    euler_radial_source(v[0], v[1], v[2], v[3], a.aux[g], a.dt, a.src_p[0], a.src_p[1]);
+                }
 #pragma unroll
                 for (int m = 0; m < MEQN; m++) a.qout[m * a.plane + g] = v[m];
             }
         }
+    }
+    if (tq_out) {
+        // this wavefront's quiet byte and, where it is quiet, its two Courant maxima before dt/d (read back by the
+        // tile's skipped launches)
+        if constexpr (SRC) quiet = quiet && __all(src_fixed);
+        if (quiet) {
+            double cx = cflx, cy = cfly;
+#pragma unroll
+            for (int off = 32; off >= 1; off >>= 1) {
+                cx = dmax(cx, __shfl_xor(cx, off, WAVE));
+                cy = dmax(cy, __shfl_xor(cy, off, WAVE));
+            }
+            if (lane == 0) tq_cfl[tile_id * F_WAVES + wv] = make_double2(cx, cy);
+        }
+        if (lane == 0) reinterpret_cast<unsigned char *>(tq_out + tile_id)[wv] = quiet ? TQ_QUIET : 0u;
     }
     // the two passes have their own dt/d: the larger Courant number of the two is the step's (step2ds.f:136,181)
     cfl_publish(a.cfl, dmax(cfl_value<false>(cflx, a.dtd), cfl_value<false>(cfly, a.dtd_t)));

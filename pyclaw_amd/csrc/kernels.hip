@@ -134,13 +134,15 @@ template <class RP> int launch_step2ds_t(const SweepLaunch &l, std::string &err)
     if (a.src_id != 0) {
         if constexpr (std::is_same<RP, Euler5>::value) {
             if (a.src_id != 1) { err = "fused source: Euler radial source"; return PCL_EINVAL; }
-            hipLaunchKernelGGL((step2ds_kernel<RP, FW, true>), grid, dim3(F_THREADS), 0, l.stream, a, ntx, nty);
+            hipLaunchKernelGGL((step2ds_kernel<RP, FW, true>), grid, dim3(F_THREADS), 0, l.stream, a, ntx, nty,
+                           l.tq_in, l.tq_out, l.tq_cfl, l.tq_skip);
         } else {
             err = "fused source: only the Euler solver has it";
             return PCL_EINVAL;
         }
     } else
-        hipLaunchKernelGGL((step2ds_kernel<RP, FW, false>), grid, dim3(F_THREADS), 0, l.stream, a, ntx, nty);
+        hipLaunchKernelGGL((step2ds_kernel<RP, FW, false>), grid, dim3(F_THREADS), 0, l.stream, a, ntx, nty,
+                           l.tq_in, l.tq_out, l.tq_cfl, l.tq_skip);
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? PCL_OK : hip_fail(err, "step2ds launch", e);
 }

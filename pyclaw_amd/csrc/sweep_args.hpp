@@ -39,6 +39,18 @@ __host__ __device__ inline void euler_radial_source(double &q0, double &q1, doub
     q0 = n0; q1 = n1; q2 = n2; q3 = n3;
 }
 
+// A cell euler_radial_source returns bit for bit, for every dt in (0, 2^20], |gamma1|, |ndm1| <= 2^20 (checked by the
+// host per launch) and any contraction of its expressions: v = +0 makes every increment a signed zero, q0 and q3 are
+// non-zero and q1 is not -0 (q - (+-0) = q), and the bounds keep every factor in front of that zero finite
+// (|k| <= 2^740, |k rho u| <= 2^920, |press| <= 2^320).  Proof in DESIGN.md 4.1a.  Quiet tiles of the one-kernel step
+// under the fused source require it of every cell they store.
+__host__ __device__ inline bool euler_radial_source_fixed(double q0, double q1, double q2, double q3, double rad) {
+    return __builtin_bit_cast(unsigned long long, q2) == 0ull && __builtin_bit_cast(unsigned long long, q1) != (1ull << 63) &&
+           q0 >= 0x1p-60 && q0 <= 0x1p60 && q1 >= -0x1p60 && q1 <= 0x1p60 && q3 > 0.0 && q3 <= 0x1p60 &&
+           (rad >= 0x1p-700 || rad <= -0x1p-700);
+}
+constexpr double SRC_FIXED_BOUND = 0x1p20;   // the host's per-launch bound on dt, |gamma1| and |ndim - 1|
+
 // SharpClaw form of the same source (apps/euler/2d/shockbubble/shockbubble.py:95-122, dq_Euler_radial): the increment
 // dt * psi(q) of one cell, in the operation order of the numpy callback (-dt*(ndim-1)/rad is one array, then the
 // products left to right); the energy-equation tracer component gets 0.
@@ -134,6 +146,12 @@ struct SweepLaunch {
     int lim_type;  // SharpClaw reconstruction (2 PyWENO weno5, 3 legacy weno5)
     int char_decomp = 0;   // SharpClaw: 1 = wave-based reconstruction (1-D: tvd2_wave / weno5_wave)
     hipStream_t stream;
+    // one-kernel step only (classic_fused.hpp, quiet tiles): the per-tile words of the previous launch and of this one,
+    // the per-wavefront Courant maxima, 1 = skip tiles whose neighbourhood was quiet.  tq_out null: no bookkeeping
+    const unsigned *tq_in = nullptr;
+    unsigned *tq_out = nullptr;
+    double2 *tq_cfl = nullptr;
+    int tq_skip = 0;
 };
 
 // defined in kernels.hip, once per arithmetic mode; returns 0 or a PCL_E* code + message

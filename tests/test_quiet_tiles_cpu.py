@@ -1,0 +1,42 @@
+"""
+CPU: the quiet tiles of the one-kernel step (classic_fused.hpp) rely on a whitelist.  The words of one
+launch may decide the next only if nothing but the step itself and read-only calls came in between, so every C entry
+point that takes a solver and is not on the list below must invalidate them (pcl_solver::tq_drop) before anything
+else.  A new entry point fails here until it does so or is added to the list.
+"""
+import os
+import re
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SRC = os.path.join(ROOT, "pyclaw_amd", "csrc", "pclaw.hip")
+
+# the step itself carries the words on (internally: only its one-kernel form of the whole block), the rest only read
+CARRY = {"pcl_step_hyperbolic", "pcl_bc_step"}
+READ_ONLY = {"pcl_destroy", "pcl_get_q", "pcl_get_strip", "pcl_get_cells", "pcl_sync", "pcl_timer_start",
+             "pcl_timer_stop", "pcl_kernel_timing", "pcl_step_count", "pcl_kernel_timing_read", "pcl_step_form_stats",
+             "pcl_tile_skip_stats"}
+
+
+def entry_points():
+    src = open(SRC).read()
+    out = {}
+    for m in re.finditer(r"^(?:int|void) (pcl_\w+)\(pcl_solver \*s\b[^{;]*\{\n", src, re.M):
+        out[m.group(1)] = src[m.end():m.end() + 400].split("\n")[0]
+    return out
+
+
+def test_every_other_entry_point_invalidates_first():
+    eps = entry_points()
+    assert len(eps) >= 40 and CARRY <= set(eps) and READ_ONLY <= set(eps)
+    for name, first_line in eps.items():
+        if name in CARRY or name in READ_ONLY:
+            continue
+        assert first_line.strip().startswith("if (s) s->tq_drop();"), (name, first_line)
+
+
+def test_step_entry_points_drop_then_restore():
+    src = open(SRC).read()
+    for name in CARRY:
+        body = src[src.index("int %s(pcl_solver *s" % name):]
+        body = body[:body.index("\n}\n")]
+        assert "const bool tq_keep = s->tq_valid;\n    s->tq_drop();" in body, name
