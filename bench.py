@@ -3,7 +3,7 @@
 bench.py -- headline benchmark: Mcell.steps/s of the classic dimension-split step on the
 2-D Euler shock-bubble problem (BASELINE.json configs[2]: 4096 x 4096 cells on one MI355X).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--nx 4096 --ny 4096] [--dump-outputs DIR]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--nx 4096 --ny 4096] [--dump-outputs DIR] [--full]
 
 One "step" = one accepted pass of the hot path on the block resident in HBM: ghost-cell
 fill (+ halo exchange when N > 1), x sweep, y sweep, device CFL reduction, the 8-byte CFL
@@ -17,15 +17,17 @@ a 4096 x 4096 block of a (4096*px) x (4096*py) grid, halo exchange over RCCL, CF
 `--global NX NY` fixes the GLOBAL grid instead (strong scaling): `--gpus 8 --global 8192 8192` is BASELINE
 configs[3] (8192 x 8192 on a 2 x 4 processor grid, 4096 x 2048 cells per GPU); config.workload says which.
 
-Besides the headline (the shock-bubble initial condition of BASELINE configs[2]) the default single-GPU line
-carries the same K steps on two other states of the same grid, because the kernels' cost depends on the state:
-`dense_state` (a jump at every interface, all five wave families present everywhere: the input-independent
-figure for the kernels) and `developed_state` (the reference regression's own t = 0.2 solution, shock through
-the bubble, interpolated to the benchmark grid).  When K is small a `sustained` object adds a 1000-step run.
+A plain run does only what the headline needs: set up, warm up, time the K steps, write --dump-outputs, print.
+`--full` adds, on one GPU, the measurements that take runs of their own, because the kernels' cost depends on
+the state: the same K steps on two other states of the same grid, `dense_state` (a jump at every interface,
+all five wave families present everywhere: the input-independent figure for the kernels) and `developed_state`
+(the reference regression's own t = 0.2 solution, shock through the bubble, interpolated to the benchmark grid);
+`app_figure` (source term on), `app_run` (the problem from t = 0 to 0.2), `fast_math` (the other arithmetic
+mode), a 1000-step `sustained` run when K is small, and "cpu_baseline" (the reference Fortran / the C port of
+it timed on the host's cores).  --no-states, --no-app-run and --no-cpu-baseline trim what --full adds.
 
-Prints ONE JSON line on rank 0 (contract in the task statement), with two extra objects:
-"roofline" (dominant sweep kernel, HIP-event timed inside the timed region) and
-"cpu_baseline" (the reference Fortran / the C port of it timed on this box's host cores).
+Prints ONE JSON line on rank 0 (contract in the task statement), with a "roofline" object (dominant sweep
+kernel, HIP-event timed inside the timed region).
 """
 import argparse
 import json
@@ -425,11 +427,16 @@ def main():
     ap.add_argument("--ny", type=int, default=4096, help="cells per GPU block in y (weak scaling)")
     ap.add_argument("--global", dest="glob", type=int, nargs=2, metavar=("NX", "NY"), default=None,
                     help="fix the GLOBAL grid (strong scaling): --gpus 8 --global 8192 8192 = BASELINE configs[3]")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need (one GPU, 2-D Euler classic step): the dense_state / "
+                         "developed_state / app_figure / app_run / sustained / fast_math objects and the CPU baselines")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the cpu_baseline object")
     ap.add_argument("--no-states", action="store_true",
-                    help="skip the dense_state / developed_state / sustained objects of the default line")
+                    help="--full without the dense_state / developed_state / app_figure / app_run / sustained / "
+                         "fast_math objects")
     ap.add_argument("--no-app-run", dest="no_app_run", action="store_true",
-                    help="skip the app_run object (the shock-bubble problem from t = 0 to 0.2 on the benchmark grid, ~10 s)")
+                    help="--full without the app_run object (the shock-bubble problem from t = 0 to 0.2 on the benchmark "
+                         "grid, ~5 s)")
     ap.add_argument("--state", choices=["bubble", "dense", "developed"], default="bubble",
                     help="state the main timed run starts from (profile runs of the dense / developed state: "
                          "tools/profile_round.sh); anything but bubble implies --no-states")
@@ -665,8 +672,8 @@ def main():
                 "headline = shock-bubble initial condition (BASELINE configs[2]): mostly undisturbed gas; wavefronts "
                 "without a jump take an exact shortcut and absent wave families skip the limiter (bit-identical "
                 "results).  The kernels' cost depends on the state: see dense_state (input-independent figure) and "
-                "developed_state in this same line")
-        if headline and size == 1 and args.math == "exact" and not args.no_states:
+                "developed_state in the line of bench.py --full")
+        if args.full and headline and size == 1 and args.math == "exact" and not args.no_states:
             desc_dense = "rho=1+.1U, mx=.1U, my=.05U, E=2.5+.1U, tracer=U (U uniform random per cell): a jump at every interface, all five wave families everywhere"
             desc_dev = ("the reference regression's t=0.2 solution (test/euler/2d/shockbubble.py, 160x40, shock through "
                         "the bubble) interpolated bilinearly to this grid")
@@ -694,7 +701,7 @@ def main():
                                     "roofline_frac": byt4 / (dur4 * 1e-3) / 1e9 / HBM_PEAK_GBS,
                                     "roofline_frac_whole_step": 2.0 * bytes_pass / (el4 / 1000) / 1e9 / HBM_PEAK_GBS,
                                     "avg_ms": lab4, "result_finite": fin4}
-        if size == 1 and headline and args.math == "exact" and (args.extras or not args.no_states):
+        if size == 1 and headline and args.math == "exact" and (args.extras or (args.full and not args.no_states)):
             # the second arithmetic mode (FMA contraction, reciprocal-multiply division, one-step Newton sqrt;
             # tests/test_gpu_apps.py holds it to the north-star tolerance rtol 1e-12 on the reference goldens) on the
             # headline state and on the dense state
@@ -714,7 +721,8 @@ def main():
                              % ("UNSPLIT (step3, order_trans 22)" if args.unsplit else "dim-split (step3ds)"))
         elif args.unsplit and args.solver == "classic" and args.app == "bubble":
             out["metric"] = "Mcell*steps/s, 2-D Euler classic UNSPLIT step (step2, order_trans 2) (+ achieved HBM GB/s in roofline)"
-        if size == 1 and not args.no_cpu_baseline and args.ndim == 2 and args.solver == "classic" and args.app == "bubble":
+        if args.full and size == 1 and not args.no_cpu_baseline and args.ndim == 2 and args.solver == "classic" \
+                and args.app == "bubble":
             try:
                 out["cpu_baseline"] = cpu_baseline(args.nx, args.ny)
             except Exception as e:      # the oracle is optional infrastructure, never the product

@@ -1,8 +1,8 @@
 #!/bin/bash
-# default bench line (incl. app_run), unsplit PMC passes, halo overhead table
+# full bench line (incl. app_run), unsplit PMC passes, halo overhead table
 set -x
 R=$GRAFT_REPO_ROOT
-python bench.py > gpurun_out/r03_bench_default.json 2> gpurun_out/r03_bench_default.err
+python bench.py --full > r03_bench_default.json 2> r03_bench_default.err
 cd /tmp && export TMPDIR=/tmp
 for C in FETCH_SIZE WRITE_SIZE; do
   rocprofv3 --pmc $C --kernel-trace --output-format csv -d $R/gpurun_out/prof_r03a/pmc_unsplit_$C -- python3 $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-states --unsplit > /dev/null 2>&1
