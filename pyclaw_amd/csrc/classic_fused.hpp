@@ -61,18 +61,85 @@ __device__ __forceinline__ int ftile_at(int m, int r, int c) { return (m * F_ROW
 // Quiet tiles.  A tile is quiet in a launch when every x-sweep and every y-sweep wavefront took the
 // no-jump shortcut (and, under the fused source, every cell it stored satisfies euler_radial_source_fixed): its owned
 // cells leave the kernel as they came, whatever dt.  tq_out[tile] gets one byte per wavefront (TQ_QUIET or 0), tq_cfl
-// the quiet wavefront's largest |speed| of each sweep, before the multiplication by dt/d.  With tq_skip set, tq_in
-// holds the words of the previous launch, which ran on the swapped buffer pair (its output is this launch's input, its
+// the quiet wavefront's largest |speed| of each sweep, before the multiplication by dt/d.  A skipping launch reads the
+// words tq_in of the previous launch, which ran on the swapped buffer pair (its output is this launch's input, its
 // input this launch's output) with the same solver: a tile off the frame whose 3 x 3 neighbourhood was quiet there
 // reads the same 16 x 64 cells again, would be quiet again, and its owned cells in qout already hold the result.
+// tile_list_kernel settles those tiles and lists the others; step2ds_kernel then runs over the list only.
 constexpr unsigned TQ_QUIET = 1u, TQ_ALL = 0x01010101u;
 static_assert(F_WAVES == 4, "one quiet byte per wavefront in a 32-bit word");
 
+// Tile list of a skipping launch (one thread per tile, tiles in row-major order): a tile off the frame whose 3 x 3
+// neighbourhood was quiet in the previous launch is skipped -- its word becomes TQ_ALL again and its four cached
+// Courant maxima times dt/d are published -- every other tile is appended to list.  Within a workgroup's range of tiles
+// the list keeps their order (ballot and prefix), the ranges take their places with one atomic each.  count was
+// zeroed by the previous list launch; this one zeroes count_next for the next (nothing reads it in between).
+constexpr int TL_THREADS = 256;
+__global__ __launch_bounds__(TL_THREADS) void tile_list_kernel(int ntx, int nty, int mbc, int mx, int my, double dtd,
+                                                               double dtd_t, unsigned long long *cfl,
+                                                               const unsigned *__restrict__ tq_in,
+                                                               unsigned *__restrict__ tq_out,
+                                                               const double2 *__restrict__ tq_cfl, int *__restrict__ list,
+                                                               int *count, int *count_next) {
+    __shared__ int wbase[TL_THREADS / WAVE];
+    __shared__ int base;
+    const int t = blockIdx.x * TL_THREADS + threadIdx.x;
+    const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x / WAVE;
+    if (t == 0) *count_next = 0;
+    bool skip = false;
+    unsigned long long bits = 0;                     // this tile's largest published Courant number (bits); 0 publishes nothing
+    if (t < ntx * nty) {
+        // off the frame (the tile's 16 x 64 load reads interior cells only): 1 <= tx < ntx - 1, 1 <= ty < nty - 1
+        const int tx = t % ntx, ty = t / ntx;
+        const int x0 = mbc - HALO + tx * F_OWN_C, y0 = mbc - HALO + ty * F_OWN_R;
+        if (x0 >= mbc && y0 >= mbc && x0 + F_COLS <= mbc + mx && y0 + F_ROWS <= mbc + my) {
+            const unsigned *w = tq_in + t - ntx - 1;
+            skip = true;
+#pragma unroll
+            for (int dy = 0; dy < 3; dy++)
+#pragma unroll
+                for (int dx = 0; dx < 3; dx++) skip = skip & (w[dy * ntx + dx] == TQ_ALL);
+        }
+        if (skip) {
+            tq_out[t] = TQ_ALL;
+            // the computed path publishes max over lanes of max(fl(dtd * cflx), fl(dtd_t * cfly)) per wavefront, a
+            // skipping workgroup did the same with the cached maxima (rounding is monotone and dt/d > 0: the same bits);
+            // the Courant word is an atomic max of bit patterns, so the max of the bits of the four is what they give
+#pragma unroll
+            for (int wq = 0; wq < F_WAVES; wq++) {
+                const double2 c = tq_cfl[t * F_WAVES + wq];
+                const unsigned long long b = (unsigned long long)__double_as_longlong(dmax(dtd * c.x, dtd_t * c.y));
+                bits = b > bits ? b : bits;
+            }
+        }
+    }
+    cfl_publish_bits(cfl, bits);
+    const unsigned long long keep = __ballot(t < ntx * nty && !skip);
+    if (lane == 0) wbase[wv] = __popcll(keep);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int n = 0;
+#pragma unroll
+        for (int k = 0; k < TL_THREADS / WAVE; k++) {
+            const int c = wbase[k];
+            wbase[k] = n;
+            n += c;
+        }
+        base = n ? atomicAdd(count, n) : 0;
+    }
+    __syncthreads();
+    if ((keep >> lane) & 1) list[base + wbase[wv] + __popcll(keep & ((1ull << lane) - 1))] = t;
+}
+
+// Full launches: workgroup b takes tile b (through the chunked order below).  List launches (tq_list set, one
+// workgroup per tile of the grid): workgroup b takes list entry b, through the same order; the workgroups past the
+// list's end (*tq_count) return at once.  Dispatch order puts the listed tiles first.
 template <class RP, bool FWAVE, bool SRC>
 __global__ __launch_bounds__(F_THREADS, 1024 / F_THREADS) void step2ds_kernel(SweepArgs a, int ntx, int nty,
-                                                                              const unsigned *__restrict__ tq_in,
                                                                               unsigned *__restrict__ tq_out,
-                                                                              double2 *__restrict__ tq_cfl, int tq_skip) {
+                                                                              double2 *__restrict__ tq_cfl,
+                                                                              const int *__restrict__ tq_list,
+                                                                              const int *tq_count) {
     constexpr int MEQN = RP::MEQN;
     static_assert(RP::NAUX == 0, "solvers without aux arrays");
     static_assert(!SRC || MEQN == 5, "fused source: the Euler solver");
@@ -83,10 +150,13 @@ __global__ __launch_bounds__(F_THREADS, 1024 / F_THREADS) void step2ds_kernel(Sw
     // windows still walk the grid in row order: without arithmetic 0.288 -> 0.274 ms, the shock-bubble step 0.331 ->
     // 0.330 (16 x 64, before the memo).  The XCD-contiguous order of xcd_logical_block costs this kernel 2-3 % although
     // it saves HBM reads; column bands per XCD (a tile's four neighbours on the same XCD) measured 25 % slower on the
-    // shock-bubble state, equal without arithmetic.
+    // shock-bubble state, equal without arithmetic.  A list launch takes its list entries in the same order.
     int bid = blockIdx.x;
-    const int nb = gridDim.x, win = bid >> 6;
+    const int nb = tq_list ? min(*tq_count, ntx * nty) : (int)gridDim.x;
+    if (bid >= nb) return;                           // past the list: the whole workgroup, before any barrier
+    const int win = bid >> 6;
     if ((win + 1) << 6 <= nb) bid = (win << 6) + ((bid & 7) << 3) + ((bid >> 3) & 7);
+    if (tq_list) bid = tq_list[bid];
     int tx = bid % ntx, ty = bid / ntx;
     if (a.sub != 0) {
         // decomposed block (pclaw.hip): the tiles inside box = [ty_lo, ty_hi) x [tx_lo, tx_hi) read no ghost cell a
@@ -116,26 +186,6 @@ __global__ __launch_bounds__(F_THREADS, 1024 / F_THREADS) void step2ds_kernel(Sw
     const int x0 = a.mbc - HALO + tx * F_OWN_C;      // array column of tile column 0 (a.mbc == HALO: checked by the launcher)
     const int y0 = a.mbc - HALO + ty * F_OWN_R;
     const int tile_id = ty * ntx + tx;
-
-    // ---- quiet-tile skip: 9 scalar loads, the whole workgroup returns before any barrier ------------------------
-    // (off the frame: the 16 x 64 load reads interior cells only, so 1 <= tx < ntx - 1 and 1 <= ty < nty - 1)
-    if (tq_skip && x0 >= a.mbc && y0 >= a.mbc && x0 + F_COLS <= a.mbc + a.mx && y0 + F_ROWS <= a.mbc + a.my) {
-        const int wq = __builtin_amdgcn_readfirstlane(threadIdx.x / WAVE);
-        const double2 c = tq_cfl[tile_id * F_WAVES + wq];
-        const unsigned *w = tq_in + tile_id - ntx - 1;
-        bool quiet = true;
-#pragma unroll
-        for (int dy = 0; dy < 3; dy++)
-#pragma unroll
-            for (int dx = 0; dx < 3; dx++) quiet = quiet & (w[dy * ntx + dx] == TQ_ALL);
-        if (quiet) {
-            if (threadIdx.x == 0) tq_out[tile_id] = TQ_ALL;
-            // the computed path publishes max over lanes of max(fl(dtd * cflx), fl(dtd_t * cfly)); rounding is monotone
-            // and dt/d > 0, so max_l fl(d * s_l) = fl(d * max_l s_l): these are the same bits
-            cfl_publish(a.cfl, dmax(a.dtd * c.x, a.dtd_t * c.y));
-            return;
-        }
-    }
 
     // ---- load ----------------------------------------------------------------------------------------------------
     const bool full_tile = x0 + F_COLS <= a.I && y0 + F_ROWS <= a.J;

@@ -130,19 +130,30 @@ template <class RP> int launch_step2ds_t(const SweepLaunch &l, std::string &err)
         nblocks = a.sub == 1 ? inside : nblocks - inside;
         if (nblocks == 0) return PCL_OK;
     }
-    const dim3 grid(nblocks);
-    if (a.src_id != 0) {
-        if constexpr (std::is_same<RP, Euler5>::value) {
-            if (a.src_id != 1) { err = "fused source: Euler radial source"; return PCL_EINVAL; }
-            hipLaunchKernelGGL((step2ds_kernel<RP, FW, true>), grid, dim3(F_THREADS), 0, l.stream, a, ntx, nty,
-                           l.tq_in, l.tq_out, l.tq_cfl, l.tq_skip);
-        } else {
-            err = "fused source: only the Euler solver has it";
+    if (a.src_id != 0 && !(std::is_same<RP, Euler5>::value && a.src_id == 1)) {
+        err = "fused source: only the Euler solver's radial source";
+        return PCL_EINVAL;
+    }
+    // a skipping launch: the tile list in front, then the step over the list (classic_fused.hpp)
+    const bool list = l.tq_skip != 0;
+    if (list) {
+        if (a.sub != 0 || !l.tq_in || !l.tq_out || !l.tq_cfl || !l.tq_list || !l.tq_count || !l.tq_count_next) {
+            err = "step2ds tile list: the whole block, with its bookkeeping";
             return PCL_EINVAL;
         }
+        hipLaunchKernelGGL(tile_list_kernel, dim3((nblocks + TL_THREADS - 1) / TL_THREADS), dim3(TL_THREADS), 0, l.stream,
+                           ntx, nty, a.mbc, a.mx, a.my, a.dtd, a.dtd_t, a.cfl, l.tq_in, l.tq_out, l.tq_cfl, l.tq_list,
+                           l.tq_count, l.tq_count_next);
+    }
+    const dim3 grid(nblocks);
+    const int *tl = list ? l.tq_list : nullptr, *tc = list ? l.tq_count : nullptr;
+    if (a.src_id != 0) {
+        if constexpr (std::is_same<RP, Euler5>::value)
+            hipLaunchKernelGGL((step2ds_kernel<RP, FW, true>), grid, dim3(F_THREADS), 0, l.stream, a, ntx, nty, l.tq_out,
+                               l.tq_cfl, tl, tc);
     } else
-        hipLaunchKernelGGL((step2ds_kernel<RP, FW, false>), grid, dim3(F_THREADS), 0, l.stream, a, ntx, nty,
-                           l.tq_in, l.tq_out, l.tq_cfl, l.tq_skip);
+        hipLaunchKernelGGL((step2ds_kernel<RP, FW, false>), grid, dim3(F_THREADS), 0, l.stream, a, ntx, nty, l.tq_out,
+                           l.tq_cfl, tl, tc);
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? PCL_OK : hip_fail(err, "step2ds launch", e);
 }

@@ -107,6 +107,10 @@ struct pcl_solver {
     };
     unsigned *tq[2] = {nullptr, nullptr};
     double2 *tq_cfl = nullptr;
+    // the tile list of a skipping launch and its two counts (a skipping launch fills tq_count[tq_par] and zeroes the
+    // other for the next one)
+    int *tq_list = nullptr, *tq_count = nullptr;
+    int tq_par = 0;
     int tq_ntx = 0, tq_nty = 0;
     int tq_enable = 1;              // pcl_tile_skip
     int tq_cur = 0;
@@ -531,12 +535,23 @@ int do_step2ds(pcl_solver *s, const double *qin, double *qout, double dt, int su
         l.tq_out = s->tq[s->tq_cur ^ 1];
         l.tq_cfl = s->tq_cfl;
         l.tq_skip = skip ? 1 : 0;
+        l.tq_list = s->tq_list;
+        l.tq_count = s->tq_count + s->tq_par;
+        l.tq_count_next = s->tq_count + (s->tq_par ^ 1);
     }
     s->tq_drop();
     s->tq_stats = 0;
     std::string err;
     int rc = PCL_BY_MATH(s->cfg.math, launch_step2ds(l, err));
     if (rc) fail(rc, err);
+    if (book && l.tq_skip) {
+        if (rc) {
+            // whatever the list launch did or did not do: both counts back to zero
+            hipMemsetAsync(s->tq_count, 0, 2 * sizeof(int), stream);
+        } else {
+            s->tq_par ^= 1;
+        }
+    }
     if (book && !rc) {
         s->tq_cur ^= 1;
         s->tq_valid = true;
@@ -873,6 +888,9 @@ int pcl_create(const pcl_config *cfg, pcl_solver **out) {
         for (auto &w : s->tq)
             if (e == hipSuccess) e = hipMalloc((void **)&w, nt * sizeof(unsigned));
         if (e == hipSuccess) e = hipMalloc((void **)&s->tq_cfl, nt * 4 * sizeof(double2));
+        if (e == hipSuccess) e = hipMalloc((void **)&s->tq_list, nt * sizeof(int));
+        if (e == hipSuccess) e = hipMalloc((void **)&s->tq_count, 2 * sizeof(int));
+        if (e == hipSuccess) e = hipMemsetAsync(s->tq_count, 0, 2 * sizeof(int), s->stream);
     }
     const int nmax = cfg->meqn > cfg->maux ? cfg->meqn : cfg->maux;
     s->stage_bytes = (size_t)nmax * s->I * s->J * s->K * sizeof(double);
@@ -913,6 +931,8 @@ void pcl_destroy(pcl_solver *s) {
     for (unsigned *w : s->tq)
         if (w) hipFree(w);
     if (s->tq_cfl) hipFree(s->tq_cfl);
+    if (s->tq_list) hipFree(s->tq_list);
+    if (s->tq_count) hipFree(s->tq_count);
     if (s->cfl_host) hipHostFree(s->cfl_host);
     if (s->ev0) hipEventDestroy(s->ev0);
     if (s->ev1) hipEventDestroy(s->ev1);
@@ -1817,32 +1837,36 @@ int pcl_tile_skip(pcl_solver *s, int enable) {
     return PCL_OK;
 }
 
-// tiles the last one-kernel launch computed / skipped, derived from the words it read: a tile off the frame skipped
-// exactly when it and its 8 neighbours were quiet there (classic_fused.hpp).  Nothing counted: both 0.
+// tiles the last one-kernel launch computed / skipped: a skipping launch counted the tiles it listed
+// (classic_fused.hpp: tile_list_kernel), a launch without skipping computed all.  Nothing counted: both 0.
 int pcl_tile_skip_stats(pcl_solver *s, long *computed, long *skipped) {
     if (!s || !computed || !skipped) return fail(PCL_EINVAL, "null argument");
     *computed = *skipped = 0;
     if (!s->tq_stats) return PCL_OK;
-    const int ntx = s->tq_ntx, nty = s->tq_nty, mbc = s->cfg.mbc, mx = s->cfg.n[0], my = s->cfg.n[1];
-    const long nt = (long)ntx * nty;
-    long sk = 0;
+    const long nt = (long)s->tq_ntx * s->tq_nty;
+    long n = nt;
     if (s->tq_stats == 2) {
         HIP_TRY(hipSetDevice(s->cfg.device));
-        std::vector<unsigned> w((size_t)nt);
+        int c = 0;
         HIP_TRY(hipStreamSynchronize(s->stream));
-        HIP_TRY(hipMemcpy(w.data(), s->tq[s->tq_cur ^ 1], (size_t)nt * sizeof(unsigned), hipMemcpyDeviceToHost));
-        for (int ty = 0; ty < nty; ty++)
-            for (int tx = 0; tx < ntx; tx++) {
-                const int x0 = mbc - 2 + 60 * tx, y0 = mbc - 2 + 12 * ty;
-                if (x0 < mbc || y0 < mbc || x0 + 64 > mbc + mx || y0 + 16 > mbc + my) continue;   // frame tile
-                bool quiet = true;
-                for (int dy = -1; dy <= 1; dy++)
-                    for (int dx = -1; dx <= 1; dx++) quiet = quiet && w[(size_t)(ty + dy) * ntx + tx + dx] == 0x01010101u;
-                sk += quiet;
-            }
+        HIP_TRY(hipMemcpy(&c, s->tq_count + (s->tq_par ^ 1), sizeof(int), hipMemcpyDeviceToHost));
+        n = c;
     }
-    *computed = nt - sk;
-    *skipped = sk;
+    *computed = n;
+    *skipped = nt - n;
+    return PCL_OK;
+}
+
+int pcl_tile_words(pcl_solver *s, unsigned *host, int *ntx, int *nty) {
+    if (s) s->tq_drop();                  // quiet tiles: not a read-only call (pcl_solver::tq_valid)
+    if (!s || !ntx || !nty) return fail(PCL_EINVAL, "null argument");
+    *ntx = s->tq_ntx;
+    *nty = s->tq_nty;
+    if (!host) return PCL_OK;
+    if (s->tq_stats != 2) return fail(PCL_ESTATE, "pcl_tile_words: the last one-kernel step did not skip");
+    HIP_TRY(hipSetDevice(s->cfg.device));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    HIP_TRY(hipMemcpy(host, s->tq[s->tq_cur ^ 1], (size_t)s->tq_ntx * s->tq_nty * sizeof(unsigned), hipMemcpyDeviceToHost));
     return PCL_OK;
 }
 

@@ -147,11 +147,15 @@ struct SweepLaunch {
     int char_decomp = 0;   // SharpClaw: 1 = wave-based reconstruction (1-D: tvd2_wave / weno5_wave)
     hipStream_t stream;
     // one-kernel step only (classic_fused.hpp, quiet tiles): the per-tile words of the previous launch and of this one,
-    // the per-wavefront Courant maxima, 1 = skip tiles whose neighbourhood was quiet.  tq_out null: no bookkeeping
+    // the per-wavefront Courant maxima, 1 = skip tiles whose neighbourhood was quiet.  tq_out null: no bookkeeping.
+    // A skipping launch lists the tiles it computes in tq_list (one int per tile) and their number in *tq_count (zero
+    // on entry), and zeroes *tq_count_next for the next skipping launch.
     const unsigned *tq_in = nullptr;
     unsigned *tq_out = nullptr;
     double2 *tq_cfl = nullptr;
     int tq_skip = 0;
+    int *tq_list = nullptr;
+    int *tq_count = nullptr, *tq_count_next = nullptr;
 };
 
 // defined in kernels.hip, once per arithmetic mode; returns 0 or a PCL_E* code + message
