@@ -335,11 +335,13 @@ int pcl_step_form_stats(pcl_solver *s, double *ms_total, long *launches, long *s
  * its 8 neighbours, is not computed again -- same bits, same Courant number.  enable = 0 computes every tile.  Any call
  * other than the step itself and read-only calls makes the next step compute every tile. */
 int pcl_tile_skip(pcl_solver *s, int enable);
-/* tiles the last one-kernel step computed and skipped (both 0 when no one-kernel step of the whole block has run) */
+/* tiles the last one-kernel step computed and skipped (both 0 when no one-kernel step of the whole block has run); a
+ * skipping step ran over the tile list built behind the step before it, in the kernel that handed its Courant number
+ * over */
 int pcl_tile_skip_stats(pcl_solver *s, long *computed, long *skipped);
 /* internal, for the test suite only (not part of the user API): the tile grid (*ntx x *nty tiles of 12 x 60 owned cells) and, when host is not null and the last one-kernel
- * step could skip, the per-tile quiet words it read (row-major, one byte per wavefront); makes the next step compute
- * every tile */
+ * step could skip, the per-tile quiet words it read (row-major, one byte per wavefront; not the words the list built
+ * behind it wrote); makes the next step compute every tile */
 int pcl_tile_words(pcl_solver *s, unsigned *host, int *ntx, int *nty);
 /* hyperbolic steps (classic) / right-hand sides (SharpClaw) attempted since pcl_create, rejected ones included */
 int pcl_step_count(pcl_solver *s, long *steps);

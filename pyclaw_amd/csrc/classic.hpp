@@ -144,18 +144,6 @@ __device__ __forceinline__ void cfl_publish(unsigned long long *word, double v) 
         if (bits > seen) atomicMax(word, bits);
     }
 }
-// the same word, one bit pattern per lane: the atomic max of the largest pattern of the wavefront
-__device__ __forceinline__ void cfl_publish_bits(unsigned long long *word, unsigned long long bits) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        const unsigned long long o = __shfl_xor(bits, off, WAVE);
-        bits = o > bits ? o : bits;
-    }
-    if ((threadIdx.x & (WAVE - 1)) == 0) {
-        const unsigned long long seen = __hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (bits > seen) atomicMax(word, bits);
-    }
-}
 
 // Courant number of one interface (flux2.f:109-117): max over the waves of dtdx(i)*s and -dtdx(i-1)*s.
 // Without a capacity function dtdx is one positive number for the whole grid, and rounding is monotone:

@@ -61,33 +61,49 @@ __device__ __forceinline__ int ftile_at(int m, int r, int c) { return (m * F_ROW
 // Quiet tiles.  A tile is quiet in a launch when every x-sweep and every y-sweep wavefront took the
 // no-jump shortcut (and, under the fused source, every cell it stored satisfies euler_radial_source_fixed): its owned
 // cells leave the kernel as they came, whatever dt.  tq_out[tile] gets one byte per wavefront (TQ_QUIET or 0), tq_cfl
-// the quiet wavefront's largest |speed| of each sweep, before the multiplication by dt/d.  A skipping launch reads the
-// words tq_in of the previous launch, which ran on the swapped buffer pair (its output is this launch's input, its
-// input this launch's output) with the same solver: a tile off the frame whose 3 x 3 neighbourhood was quiet there
-// reads the same 16 x 64 cells again, would be quiet again, and its owned cells in qout already hold the result.
-// tile_list_kernel settles those tiles and lists the others; step2ds_kernel then runs over the list only.
+// the quiet wavefront's largest |speed| of each sweep, before the multiplication by dt/d.  A tile off the frame whose
+// 3 x 3 neighbourhood was quiet in launch n reads the same 16 x 64 cells in launch n + 1 if that launch runs on the
+// swapped buffer pair (its input is launch n's output, its output launch n's input) with the same solver: it would be
+// quiet again, and its owned cells in qout already hold the result.  The rule reads launch n's words and the grid, not
+// dt, so handover_list_kernel lists launch n + 1's tiles right behind launch n; step2ds_kernel then runs over the list.
 constexpr unsigned TQ_QUIET = 1u, TQ_ALL = 0x01010101u;
 static_assert(F_WAVES == 4, "one quiet byte per wavefront in a 32-bit word");
 
-// Tile list of a skipping launch (one thread per tile, tiles in row-major order): a tile off the frame whose 3 x 3
-// neighbourhood was quiet in the previous launch is skipped -- its word becomes TQ_ALL again and its four cached
-// Courant maxima times dt/d are published -- every other tile is appended to list.  Within a workgroup's range of tiles
-// the list keeps their order (ballot and prefix), the ranges take their places with one atomic each.  count was
-// zeroed by the previous list launch; this one zeroes count_next for the next (nothing reads it in between).
+// The Courant hand-over behind a one-kernel launch of the whole block, with the next launch's tile list.  Workgroup 0
+// does what cfl_handover (pclaw.hip) does and nothing else: read the step's word, re-zero it, store the value and then
+// the sequence number to host memory (system-scope release), so the host's poll waits for nothing else; it also zeroes
+// *other for the hand-over after next.  Workgroups 1.. take one tile per thread (row-major): a tile off the frame whose
+// 3 x 3 neighbourhood was quiet in tq_in (the launch just run) is skipped by the next launch -- its word in tq_out, the
+// next launch's words, becomes TQ_ALL, and its cached Courant maxima go into next->cx / next->cy (an atomic max of bit
+// patterns: doubles >= +0, dt-free; the next launch multiplies by dt/d) -- every other tile is
+// appended to list.  Within a workgroup's range of tiles the list keeps their order (ballot and prefix), the ranges
+// take their places with one atomic each.  *next was zeroed by the hand-over before the previous one.
 constexpr int TL_THREADS = 256;
-__global__ __launch_bounds__(TL_THREADS) void tile_list_kernel(int ntx, int nty, int mbc, int mx, int my, double dtd,
-                                                               double dtd_t, unsigned long long *cfl,
-                                                               const unsigned *__restrict__ tq_in,
-                                                               unsigned *__restrict__ tq_out,
-                                                               const double2 *__restrict__ tq_cfl, int *__restrict__ list,
-                                                               int *count, int *count_next) {
+__global__ __launch_bounds__(TL_THREADS) void handover_list_kernel(unsigned long long *cfl, unsigned long long *host,
+                                                                   unsigned long long seq, int ntx, int nty, int mbc,
+                                                                   int mx, int my, const unsigned *__restrict__ tq_in,
+                                                                   unsigned *__restrict__ tq_out,
+                                                                   const double2 *__restrict__ tq_cfl,
+                                                                   int *__restrict__ list, TileNext *next,
+                                                                   TileNext *other) {
     __shared__ int wbase[TL_THREADS / WAVE];
     __shared__ int base;
-    const int t = blockIdx.x * TL_THREADS + threadIdx.x;
+    if (blockIdx.x == 0) {
+        if (threadIdx.x == 0) {
+            const unsigned long long v = *cfl;
+            *cfl = 0;                    // invariant: the word is zero whenever no step is in flight
+            __hip_atomic_store(host, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            __hip_atomic_store(host + 1, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+            other->count = 0;
+            other->cx = 0;
+            other->cy = 0;
+        }
+        return;
+    }
+    const int t = (blockIdx.x - 1) * TL_THREADS + threadIdx.x;
     const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x / WAVE;
-    if (t == 0) *count_next = 0;
     bool skip = false;
-    unsigned long long bits = 0;                     // this tile's largest published Courant number (bits); 0 publishes nothing
+    unsigned long long bx = 0, by = 0;               // the skipped tile's largest cached maxima (bits); 0 adds nothing
     if (t < ntx * nty) {
         // off the frame (the tile's 16 x 64 load reads interior cells only): 1 <= tx < ntx - 1, 1 <= ty < nty - 1
         const int tx = t % ntx, ty = t / ntx;
@@ -102,18 +118,26 @@ __global__ __launch_bounds__(TL_THREADS) void tile_list_kernel(int ntx, int nty,
         }
         if (skip) {
             tq_out[t] = TQ_ALL;
-            // the computed path publishes max over lanes of max(fl(dtd * cflx), fl(dtd_t * cfly)) per wavefront, a
-            // skipping workgroup did the same with the cached maxima (rounding is monotone and dt/d > 0: the same bits);
-            // the Courant word is an atomic max of bit patterns, so the max of the bits of the four is what they give
 #pragma unroll
             for (int wq = 0; wq < F_WAVES; wq++) {
                 const double2 c = tq_cfl[t * F_WAVES + wq];
-                const unsigned long long b = (unsigned long long)__double_as_longlong(dmax(dtd * c.x, dtd_t * c.y));
-                bits = b > bits ? b : bits;
+                const unsigned long long x = (unsigned long long)__double_as_longlong(c.x);
+                const unsigned long long y = (unsigned long long)__double_as_longlong(c.y);
+                bx = x > bx ? x : bx;
+                by = y > by ? y : by;
             }
         }
     }
-    cfl_publish_bits(cfl, bits);
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        const unsigned long long ox = __shfl_xor(bx, off, WAVE), oy = __shfl_xor(by, off, WAVE);
+        bx = ox > bx ? ox : bx;
+        by = oy > by ? oy : by;
+    }
+    if (lane == 0) {
+        if (bx) atomicMax(&next->cx, bx);
+        if (by) atomicMax(&next->cy, by);
+    }
     const unsigned long long keep = __ballot(t < ntx * nty && !skip);
     if (lane == 0) wbase[wv] = __popcll(keep);
     __syncthreads();
@@ -125,21 +149,22 @@ __global__ __launch_bounds__(TL_THREADS) void tile_list_kernel(int ntx, int nty,
             wbase[k] = n;
             n += c;
         }
-        base = n ? atomicAdd(count, n) : 0;
+        base = n ? atomicAdd(&next->count, n) : 0;
     }
     __syncthreads();
     if ((keep >> lane) & 1) list[base + wbase[wv] + __popcll(keep & ((1ull << lane) - 1))] = t;
 }
 
 // Full launches: workgroup b takes tile b (through the chunked order below).  List launches (tq_list set, one
-// workgroup per tile of the grid): workgroup b takes list entry b, through the same order; the workgroups past the
-// list's end (*tq_count) return at once.  Dispatch order puts the listed tiles first.
+// workgroup per tile of the grid): workgroup 0 first publishes the Courant number of the skipped tiles, dt/d times the
+// maxima tq_next holds; then workgroup b takes list entry b, through the same order, and the workgroups past the
+// list's end (tq_next->count) return at once.  Dispatch order puts the listed tiles first.
 template <class RP, bool FWAVE, bool SRC>
 __global__ __launch_bounds__(F_THREADS, 1024 / F_THREADS) void step2ds_kernel(SweepArgs a, int ntx, int nty,
                                                                               unsigned *__restrict__ tq_out,
                                                                               double2 *__restrict__ tq_cfl,
                                                                               const int *__restrict__ tq_list,
-                                                                              const int *tq_count) {
+                                                                              const TileNext *tq_next) {
     constexpr int MEQN = RP::MEQN;
     static_assert(RP::NAUX == 0, "solvers without aux arrays");
     static_assert(!SRC || MEQN == 5, "fused source: the Euler solver");
@@ -152,7 +177,15 @@ __global__ __launch_bounds__(F_THREADS, 1024 / F_THREADS) void step2ds_kernel(Sw
     // it saves HBM reads; column bands per XCD (a tile's four neighbours on the same XCD) measured 25 % slower on the
     // shock-bubble state, equal without arithmetic.  A list launch takes its list entries in the same order.
     int bid = blockIdx.x;
-    const int nb = tq_list ? min(*tq_count, ntx * nty) : (int)gridDim.x;
+    if (tq_list && bid == 0 && threadIdx.x == 0) {
+        // the skipped tiles' Courant number: max over tiles and wavefronts of dmax(fl(dtd * cx), fl(dtd_t * cy)) is
+        // dmax(fl(dtd * max cx), fl(dtd_t * max cy)) (the same bits); 0 publishes nothing
+        const double c = dmax(a.dtd * __longlong_as_double((long long)tq_next->cx),
+                              a.dtd_t * __longlong_as_double((long long)tq_next->cy));
+        const unsigned long long bits = (unsigned long long)__double_as_longlong(c);
+        if (bits) atomicMax(a.cfl, bits);
+    }
+    const int nb = tq_list ? min(tq_next->count, ntx * nty) : (int)gridDim.x;
     if (bid >= nb) return;                           // past the list: the whole workgroup, before any barrier
     const int win = bid >> 6;
     if ((win + 1) << 6 <= nb) bid = (win << 6) + ((bid & 7) << 3) + ((bid >> 3) & 7);

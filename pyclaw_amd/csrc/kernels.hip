@@ -134,26 +134,21 @@ template <class RP> int launch_step2ds_t(const SweepLaunch &l, std::string &err)
         err = "fused source: only the Euler solver's radial source";
         return PCL_EINVAL;
     }
-    // a skipping launch: the tile list in front, then the step over the list (classic_fused.hpp)
-    const bool list = l.tq_skip != 0;
-    if (list) {
-        if (a.sub != 0 || !l.tq_in || !l.tq_out || !l.tq_cfl || !l.tq_list || !l.tq_count || !l.tq_count_next) {
-            err = "step2ds tile list: the whole block, with its bookkeeping";
-            return PCL_EINVAL;
-        }
-        hipLaunchKernelGGL(tile_list_kernel, dim3((nblocks + TL_THREADS - 1) / TL_THREADS), dim3(TL_THREADS), 0, l.stream,
-                           ntx, nty, a.mbc, a.mx, a.my, a.dtd, a.dtd_t, a.cfl, l.tq_in, l.tq_out, l.tq_cfl, l.tq_list,
-                           l.tq_count, l.tq_count_next);
+    // a list launch: the tiles the hand-over+list kernel behind the previous launch listed (classic_fused.hpp); one
+    // workgroup per tile of the grid, those past the list's end return at once
+    const bool list = l.tq_list != nullptr;
+    if (list && (a.sub != 0 || !l.tq_out || !l.tq_cfl || !l.tq_next)) {
+        err = "step2ds tile list: the whole block, with its bookkeeping";
+        return PCL_EINVAL;
     }
     const dim3 grid(nblocks);
-    const int *tl = list ? l.tq_list : nullptr, *tc = list ? l.tq_count : nullptr;
     if (a.src_id != 0) {
         if constexpr (std::is_same<RP, Euler5>::value)
             hipLaunchKernelGGL((step2ds_kernel<RP, FW, true>), grid, dim3(F_THREADS), 0, l.stream, a, ntx, nty, l.tq_out,
-                               l.tq_cfl, tl, tc);
+                               l.tq_cfl, l.tq_list, l.tq_next);
     } else
         hipLaunchKernelGGL((step2ds_kernel<RP, FW, false>), grid, dim3(F_THREADS), 0, l.stream, a, ntx, nty, l.tq_out,
-                           l.tq_cfl, tl, tc);
+                           l.tq_cfl, l.tq_list, l.tq_next);
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? PCL_OK : hip_fail(err, "step2ds launch", e);
 }
@@ -255,6 +250,22 @@ bool step2ds_interior_box(const SweepArgs &a, int box[4], int ntiles[2]) {
     ntiles[0] = nty;
     ntiles[1] = ntx;
     return box[0] < box[1] && box[2] < box[3];
+}
+// the Courant hand-over behind a one-kernel launch of the whole block, with the next launch's tile list
+// (classic_fused.hpp: handover_list_kernel; no arithmetic, the same in every mode)
+int launch_tile_handover(const TileHandover &h, std::string &err) {
+    if (!h.cfl || !h.host || !h.tq_in || !h.tq_out || !h.tq_cfl || !h.tq_list || !h.next || !h.other || h.next == h.other ||
+        h.ntx <= 0 || h.nty <= 0) {
+        err = "tile hand-over: bad arguments";
+        return PCL_EINVAL;
+    }
+    const unsigned nt = (unsigned)h.ntx * (unsigned)h.nty;
+    // workgroup 0: the hand-over; workgroups 1..: the tiles
+    hipLaunchKernelGGL(handover_list_kernel, dim3(1 + (nt + TL_THREADS - 1) / TL_THREADS), dim3(TL_THREADS), 0, h.stream,
+                       h.cfl, h.host, h.seq, h.ntx, h.nty, h.mbc, h.mx, h.my, h.tq_in, h.tq_out, h.tq_cfl, h.tq_list,
+                       h.next, h.other);
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? PCL_OK : hip_fail(err, "tile hand-over launch", e);
 }
 bool x_interior_box(const SweepArgs &a, int box[4], int ntiles[2]) {
     using T = TileShape<1>;

@@ -94,23 +94,28 @@ struct pcl_solver {
     void ghosts_mark(const double *buf) { if (!ghosts_filled(buf)) { ghost_ok[1] = ghost_ok[0]; ghost_ok[0] = buf; } }
     void ghosts_drop(const double *buf) { for (auto &g : ghost_ok) if (g == buf) g = nullptr; }
     void ghosts_drop_all() { ghost_ok[0] = ghost_ok[1] = nullptr; }
-    // Quiet tiles of the one-kernel dim-split step (classic_fused.hpp): one 32-bit word per tile in two
-    // arrays (a launch reads tq[tq_cur] and writes the other), per-wavefront Courant maxima.  tq_valid: the last launch
-    // was a one-kernel step of the whole block, tq_last_in -> tq_last_out with the settings tq_key, and since then only
-    // the swap of pcl_step_hyperbolic and read-only calls have happened.  Fail-safe: every C entry point that is not
-    // on that list calls tq_drop() first (tests/test_quiet_tiles_cpu.py checks the source for it).
+    // Quiet tiles of the one-kernel dim-split step (classic_fused.hpp): one 32-bit word per tile in three
+    // arrays (a launch reads tq[tq_cur] and writes tq[tq_cur + 1], the list built behind it writes the skipped tiles'
+    // words of the next launch into the third), per-wavefront Courant maxima.  tq_valid: the last launch was a
+    // one-kernel step of the whole block, tq_last_in -> tq_last_out with the settings tq_key, and since then only the
+    // swap of pcl_step_hyperbolic and read-only calls have happened.  Fail-safe: every C entry point that is not on that
+    // list calls tq_drop() first (tests/test_quiet_tiles_cpu.py checks the source for it).
     struct TqKey {
         int rp, fwave, math, src;
         double src_p[2];
         pcl::RpParams par;
         bool operator==(const TqKey &o) const { return memcmp(this, &o, sizeof(TqKey)) == 0; }
     };
-    unsigned *tq[2] = {nullptr, nullptr};
+    unsigned *tq[3] = {nullptr, nullptr, nullptr};
     double2 *tq_cfl = nullptr;
-    // the tile list of a skipping launch and its two counts (a skipping launch fills tq_count[tq_par] and zeroes the
-    // other for the next one)
-    int *tq_list = nullptr, *tq_count = nullptr;
-    int tq_par = 0;
+    // The next launch's tile list: handover_list_kernel builds it behind a one-kernel launch of the whole block
+    // (tq_hand, set by that launch, read by read_cfl_end) into tq_list and tq_next[tq_nx - 1] (tq_listed once
+    // enqueued).  The next launch runs over the list only if it may skip (do_step2ds); any other step drops it.
+    int *tq_list = nullptr;
+    pcl::TileNext *tq_next = nullptr;   // three, rotating: the next hand-over fills tq_next[tq_nx], zeroes tq_next[tq_nx + 1]
+    int tq_nx = 0;
+    bool tq_hand = false, tq_listed = false;
+    int tq_stat_nx = 0;                 // the block of the list the last skipping launch ran over (pcl_tile_skip_stats)
     int tq_ntx = 0, tq_nty = 0;
     int tq_enable = 1;              // pcl_tile_skip
     int tq_cur = 0;
@@ -525,40 +530,36 @@ int do_step2ds(pcl_solver *s, const double *qin, double *qout, double dt, int su
     key.src_p[1] = a.src_p[1];
     key.par = a.par;
     if (book) {
-        // the previous launch ran on the swapped pair with the same settings and nothing has happened since; under the
-        // fused source its fixed-point test (euler_radial_source_fixed) holds for these dt, gamma1 and ndim - 1
+        // the previous launch ran on the swapped pair with the same settings, the list behind it was built and nothing
+        // has happened since; under the fused source its fixed-point test (euler_radial_source_fixed) holds for these
+        // dt, gamma1 and ndim - 1; dt is positive and finite (the skipped tiles' Courant number: DESIGN.md 4.1a)
         const bool src_ok = a.src_id == 0 || (dt <= SRC_FIXED_BOUND && fabs(a.src_p[0]) <= SRC_FIXED_BOUND &&
                                                fabs(a.src_p[1]) <= SRC_FIXED_BOUND);
-        const bool skip = s->tq_enable && s->tq_valid && s->tq_last_in == qout && s->tq_last_out == qin &&
-                          s->tq_key == key && src_ok;
-        l.tq_in = s->tq[s->tq_cur];
-        l.tq_out = s->tq[s->tq_cur ^ 1];
+        const bool skip = s->tq_enable && s->tq_valid && s->tq_listed && s->tq_last_in == qout &&
+                          s->tq_last_out == qin && s->tq_key == key && src_ok && dt > 0.0 && dt < HUGE_VAL;
+        l.tq_out = s->tq[(s->tq_cur + 1) % 3];
         l.tq_cfl = s->tq_cfl;
-        l.tq_skip = skip ? 1 : 0;
-        l.tq_list = s->tq_list;
-        l.tq_count = s->tq_count + s->tq_par;
-        l.tq_count_next = s->tq_count + (s->tq_par ^ 1);
+        if (skip) {
+            l.tq_list = s->tq_list;
+            l.tq_next = s->tq_next + (s->tq_nx + 2) % 3;
+        }
     }
     s->tq_drop();
+    s->tq_listed = false;
+    s->tq_hand = false;
     s->tq_stats = 0;
     std::string err;
     int rc = PCL_BY_MATH(s->cfg.math, launch_step2ds(l, err));
     if (rc) fail(rc, err);
-    if (book && l.tq_skip) {
-        if (rc) {
-            // whatever the list launch did or did not do: both counts back to zero
-            hipMemsetAsync(s->tq_count, 0, 2 * sizeof(int), stream);
-        } else {
-            s->tq_par ^= 1;
-        }
-    }
     if (book && !rc) {
-        s->tq_cur ^= 1;
+        s->tq_cur = (s->tq_cur + 1) % 3;
         s->tq_valid = true;
         s->tq_last_in = qin;
         s->tq_last_out = qout;
         s->tq_key = key;
-        s->tq_stats = l.tq_skip ? 2 : 1;
+        s->tq_stats = l.tq_list ? 2 : 1;
+        s->tq_stat_nx = (s->tq_nx + 2) % 3;
+        s->tq_hand = s->tq_enable != 0;       // read_cfl_end builds the next launch's list behind this one
     }
     if (timed) {
         hipEventRecord(t.b, stream);
@@ -713,10 +714,44 @@ int read_cfl(pcl_solver *s, double *cfl) {
 int read_cfl_end(pcl_solver *s, double *cfl) {
     // One single-thread kernel behind the sweeps hands the word over through host memory the device can
     // write (the value, then a sequence number with release semantics at system scope) and re-zeroes it;
-    // the host polls the sequence number.  ~3 us per step less than a D2H copy + event wait.
+    // the host polls the sequence number.  ~3 us per step less than a D2H copy + event wait.  Behind a one-kernel
+    // launch of the whole block, the same hand-over is workgroup 0 of a kernel whose other workgroups list the next
+    // launch's tiles (classic_fused.hpp: handover_list_kernel) while the host turns round.
     const unsigned long long seq = ++s->cfl_seq;
-    hipLaunchKernelGGL(cfl_handover, dim3(1), dim3(1), 0, s->stream, s->cfl_dev, s->cfl_host_dev, seq);
-    HIP_TRY(hipGetLastError());
+    const bool hand = s->tq_hand;
+    s->tq_hand = false;
+    s->tq_listed = false;
+    if (hand) {
+        TileHandover h;
+        h.cfl = s->cfl_dev;
+        h.host = s->cfl_host_dev;
+        h.seq = seq;
+        h.ntx = s->tq_ntx;
+        h.nty = s->tq_nty;
+        h.mbc = s->cfg.mbc;
+        h.mx = s->cfg.n[0];
+        h.my = s->cfg.n[1];
+        h.tq_in = s->tq[s->tq_cur];
+        h.tq_out = s->tq[(s->tq_cur + 1) % 3];
+        h.tq_cfl = s->tq_cfl;
+        h.tq_list = s->tq_list;
+        h.next = s->tq_next + s->tq_nx;
+        h.other = s->tq_next + (s->tq_nx + 1) % 3;
+        h.stream = s->stream;
+        std::string err;
+        // (no arithmetic: the exact build serves every mode)
+        if (int rc = pcl::exact::launch_tile_handover(h, err)) {
+            // nothing ran: the list state back to its start (every block zero)
+            (void)hipMemsetAsync(s->tq_next, 0, 3 * sizeof(pcl::TileNext), s->stream);
+            s->tq_nx = 0;
+            return fail(rc, err);
+        }
+        s->tq_listed = true;
+        s->tq_nx = (s->tq_nx + 1) % 3;
+    } else {
+        hipLaunchKernelGGL(cfl_handover, dim3(1), dim3(1), 0, s->stream, s->cfl_dev, s->cfl_host_dev, seq);
+        HIP_TRY(hipGetLastError());
+    }
     unsigned long long *flag = s->cfl_host + 1;
     long spins = 0;
     while (__atomic_load_n(flag, __ATOMIC_ACQUIRE) != seq) {
@@ -889,8 +924,8 @@ int pcl_create(const pcl_config *cfg, pcl_solver **out) {
             if (e == hipSuccess) e = hipMalloc((void **)&w, nt * sizeof(unsigned));
         if (e == hipSuccess) e = hipMalloc((void **)&s->tq_cfl, nt * 4 * sizeof(double2));
         if (e == hipSuccess) e = hipMalloc((void **)&s->tq_list, nt * sizeof(int));
-        if (e == hipSuccess) e = hipMalloc((void **)&s->tq_count, 2 * sizeof(int));
-        if (e == hipSuccess) e = hipMemsetAsync(s->tq_count, 0, 2 * sizeof(int), s->stream);
+        if (e == hipSuccess) e = hipMalloc((void **)&s->tq_next, 3 * sizeof(pcl::TileNext));
+        if (e == hipSuccess) e = hipMemsetAsync(s->tq_next, 0, 3 * sizeof(pcl::TileNext), s->stream);
     }
     const int nmax = cfg->meqn > cfg->maux ? cfg->meqn : cfg->maux;
     s->stage_bytes = (size_t)nmax * s->I * s->J * s->K * sizeof(double);
@@ -932,7 +967,7 @@ void pcl_destroy(pcl_solver *s) {
         if (w) hipFree(w);
     if (s->tq_cfl) hipFree(s->tq_cfl);
     if (s->tq_list) hipFree(s->tq_list);
-    if (s->tq_count) hipFree(s->tq_count);
+    if (s->tq_next) hipFree(s->tq_next);
     if (s->cfl_host) hipHostFree(s->cfl_host);
     if (s->ev0) hipEventDestroy(s->ev0);
     if (s->ev1) hipEventDestroy(s->ev1);
@@ -1837,8 +1872,9 @@ int pcl_tile_skip(pcl_solver *s, int enable) {
     return PCL_OK;
 }
 
-// tiles the last one-kernel launch computed / skipped: a skipping launch counted the tiles it listed
-// (classic_fused.hpp: tile_list_kernel), a launch without skipping computed all.  Nothing counted: both 0.
+// tiles the last one-kernel launch computed / skipped: a skipping launch ran over the list built behind the launch
+// before it (classic_fused.hpp: handover_list_kernel), counted in tq_next[tq_stat_nx] (the hand-overs behind it leave
+// that block alone until the next launch); a launch without skipping computed all.  Nothing counted: both 0.
 int pcl_tile_skip_stats(pcl_solver *s, long *computed, long *skipped) {
     if (!s || !computed || !skipped) return fail(PCL_EINVAL, "null argument");
     *computed = *skipped = 0;
@@ -1849,7 +1885,7 @@ int pcl_tile_skip_stats(pcl_solver *s, long *computed, long *skipped) {
         HIP_TRY(hipSetDevice(s->cfg.device));
         int c = 0;
         HIP_TRY(hipStreamSynchronize(s->stream));
-        HIP_TRY(hipMemcpy(&c, s->tq_count + (s->tq_par ^ 1), sizeof(int), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(&c, &s->tq_next[s->tq_stat_nx].count, sizeof(int), hipMemcpyDeviceToHost));
         n = c;
     }
     *computed = n;
@@ -1866,7 +1902,8 @@ int pcl_tile_words(pcl_solver *s, unsigned *host, int *ntx, int *nty) {
     if (s->tq_stats != 2) return fail(PCL_ESTATE, "pcl_tile_words: the last one-kernel step did not skip");
     HIP_TRY(hipSetDevice(s->cfg.device));
     HIP_TRY(hipStreamSynchronize(s->stream));
-    HIP_TRY(hipMemcpy(host, s->tq[s->tq_cur ^ 1], (size_t)s->tq_ntx * s->tq_nty * sizeof(unsigned), hipMemcpyDeviceToHost));
+    // the words the last launch read (the list built behind it writes the third array)
+    HIP_TRY(hipMemcpy(host, s->tq[(s->tq_cur + 2) % 3], (size_t)s->tq_ntx * s->tq_nty * sizeof(unsigned), hipMemcpyDeviceToHost));
     return PCL_OK;
 }
 

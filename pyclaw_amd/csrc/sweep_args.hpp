@@ -137,6 +137,15 @@ struct RkLaunch {
     int op;
 };
 
+// The tile list's small state (classic_fused.hpp): the number of listed tiles and the largest cached Courant maxima
+// (bit patterns of doubles >= +0, before dt/d) of the x and y sweeps over the tiles it skips.  Three of them, rotating:
+// a hand-over+list launch fills one and zeroes the one the hand-over after it fills; the third keeps the list the last
+// launch ran over (pcl_tile_skip_stats).
+struct TileNext {
+    int count, pad;
+    unsigned long long cx, cy;
+};
+
 struct SweepLaunch {
     SweepArgs a;
     int ndim;   // 1 or 2
@@ -146,16 +155,29 @@ struct SweepLaunch {
     int lim_type;  // SharpClaw reconstruction (2 PyWENO weno5, 3 legacy weno5)
     int char_decomp = 0;   // SharpClaw: 1 = wave-based reconstruction (1-D: tvd2_wave / weno5_wave)
     hipStream_t stream;
-    // one-kernel step only (classic_fused.hpp, quiet tiles): the per-tile words of the previous launch and of this one,
-    // the per-wavefront Courant maxima, 1 = skip tiles whose neighbourhood was quiet.  tq_out null: no bookkeeping.
-    // A skipping launch lists the tiles it computes in tq_list (one int per tile) and their number in *tq_count (zero
-    // on entry), and zeroes *tq_count_next for the next skipping launch.
-    const unsigned *tq_in = nullptr;
+    // one-kernel step only (classic_fused.hpp, quiet tiles): this launch's per-tile words and per-wavefront Courant
+    // maxima (tq_out null: no bookkeeping).  A list launch (tq_list set) computes the tq_next->count tiles a
+    // hand-over+list kernel listed behind the previous launch and publishes the Courant number of those it skips.
     unsigned *tq_out = nullptr;
     double2 *tq_cfl = nullptr;
-    int tq_skip = 0;
+    const int *tq_list = nullptr;
+    const TileNext *tq_next = nullptr;
+};
+
+// The Courant hand-over behind a one-kernel launch of the whole block, with the next launch's tile list
+// (classic_fused.hpp: handover_list_kernel): the words of the launch just enqueued (tq_in), the next launch's words
+// (tq_out, TQ_ALL for the tiles it skips), the list, and two TileNext blocks (next is filled, other zeroed).
+struct TileHandover {
+    unsigned long long *cfl = nullptr;      // the device Courant word (read, re-zeroed)
+    unsigned long long *host = nullptr;     // device view of the host block: [0] value, [1] sequence number
+    unsigned long long seq = 0;
+    int ntx = 0, nty = 0, mbc = 0, mx = 0, my = 0;
+    const unsigned *tq_in = nullptr;
+    unsigned *tq_out = nullptr;
+    const double2 *tq_cfl = nullptr;
     int *tq_list = nullptr;
-    int *tq_count = nullptr, *tq_count_next = nullptr;
+    TileNext *next = nullptr, *other = nullptr;
+    hipStream_t stream;
 };
 
 // defined in kernels.hip, once per arithmetic mode; returns 0 or a PCL_E* code + message
@@ -166,6 +188,7 @@ int launch_step2ds(const SweepLaunch &l, std::string &err);   // whole dim-split
 // ntiles[0], ntiles[1] = row tiles / tiles along a row of the x pass
 bool x_interior_box(const SweepArgs &a, int box[4], int ntiles[2]);
 bool step2ds_interior_box(const SweepArgs &a, int box[4], int ntiles[2]);   // the same for the one-kernel step: (nty, ntx)
+int launch_tile_handover(const TileHandover &h, std::string &err);   // Courant hand-over + next tile list (bit-only)
 int launch_sweep3(const SweepLaunch &l, std::string &err);   // 3-D dim-split sweep, l.ids = direction 1..3
 int launch_unsplit3(const Unsplit3Launch &l, std::string &err);   // unsplit 3-D: slices + combine of one direction
 int launch_unsplit(const SweepLaunch &l, const double *qx, std::string &err);  // scratch-free unsplit phase
