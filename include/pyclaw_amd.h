@@ -343,6 +343,10 @@ int pcl_tile_skip_stats(pcl_solver *s, long *computed, long *skipped);
  * step could skip, the per-tile quiet words it read (row-major, one byte per wavefront; not the words the list built
  * behind it wrote); makes the next step compute every tile */
 int pcl_tile_words(pcl_solver *s, unsigned *host, int *ntx, int *nty);
+/* internal, for the test suite only: the listed tiles of the last one-kernel step by class -- *na had computed something
+ * in the step before, *nq had been quiet there (both 0 when that step did not run over a list); makes the next step
+ * compute every tile */
+int pcl_tile_list_classes(pcl_solver *s, long *na, long *nq);
 /* hyperbolic steps (classic) / right-hand sides (SharpClaw) attempted since pcl_create, rejected ones included */
 int pcl_step_count(pcl_solver *s, long *steps);
 

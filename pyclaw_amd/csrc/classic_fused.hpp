@@ -76,8 +76,10 @@ static_assert(F_WAVES == 4, "one quiet byte per wavefront in a 32-bit word");
 // 3 x 3 neighbourhood was quiet in tq_in (the launch just run) is skipped by the next launch -- its word in tq_out, the
 // next launch's words, becomes TQ_ALL, and its cached Courant maxima go into next->cx / next->cy (an atomic max of bit
 // patterns: doubles >= +0, dt-free; the next launch multiplies by dt/d) -- every other tile is
-// appended to list.  Within a workgroup's range of tiles the list keeps their order (ballot and prefix), the ranges
-// take their places with one atomic each.  *next was zeroed by the hand-over before the previous one.
+// listed, in two classes: class A (its own word in tq_in is not TQ_ALL: it computed something) from the front of list,
+// class Q (quiet itself, listed for a neighbour or the frame) from the back, downward from index ntx * nty - 1.  Within
+// a workgroup's range of tiles each class keeps their order (ballot and prefix), the ranges take their places with one
+// atomic per class (next->na, next->nq).  *next was zeroed by the hand-over before the previous one.
 constexpr int TL_THREADS = 256;
 __global__ __launch_bounds__(TL_THREADS) void handover_list_kernel(unsigned long long *cfl, unsigned long long *host,
                                                                    unsigned long long seq, int ntx, int nty, int mbc,
@@ -86,15 +88,16 @@ __global__ __launch_bounds__(TL_THREADS) void handover_list_kernel(unsigned long
                                                                    const double2 *__restrict__ tq_cfl,
                                                                    int *__restrict__ list, TileNext *next,
                                                                    TileNext *other) {
-    __shared__ int wbase[TL_THREADS / WAVE];
-    __shared__ int base;
+    __shared__ int wbase[2][TL_THREADS / WAVE];
+    __shared__ int base[2];
     if (blockIdx.x == 0) {
         if (threadIdx.x == 0) {
             const unsigned long long v = *cfl;
             *cfl = 0;                    // invariant: the word is zero whenever no step is in flight
             __hip_atomic_store(host, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
             __hip_atomic_store(host + 1, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-            other->count = 0;
+            other->na = 0;
+            other->nq = 0;
             other->cx = 0;
             other->cy = 0;
         }
@@ -102,12 +105,13 @@ __global__ __launch_bounds__(TL_THREADS) void handover_list_kernel(unsigned long
     }
     const int t = (blockIdx.x - 1) * TL_THREADS + threadIdx.x;
     const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x / WAVE;
-    bool skip = false;
+    bool skip = false, own_quiet = false;
     unsigned long long bx = 0, by = 0;               // the skipped tile's largest cached maxima (bits); 0 adds nothing
     if (t < ntx * nty) {
         // off the frame (the tile's 16 x 64 load reads interior cells only): 1 <= tx < ntx - 1, 1 <= ty < nty - 1
         const int tx = t % ntx, ty = t / ntx;
         const int x0 = mbc - HALO + tx * F_OWN_C, y0 = mbc - HALO + ty * F_OWN_R;
+        own_quiet = tq_in[t] == TQ_ALL;
         if (x0 >= mbc && y0 >= mbc && x0 + F_COLS <= mbc + mx && y0 + F_ROWS <= mbc + my) {
             const unsigned *w = tq_in + t - ntx - 1;
             skip = true;
@@ -138,27 +142,39 @@ __global__ __launch_bounds__(TL_THREADS) void handover_list_kernel(unsigned long
         if (bx) atomicMax(&next->cx, bx);
         if (by) atomicMax(&next->cy, by);
     }
-    const unsigned long long keep = __ballot(t < ntx * nty && !skip);
-    if (lane == 0) wbase[wv] = __popcll(keep);
+    // class A (c = 0) and class Q (c = 1): the workgroup's prefix per wavefront, one atomic per class
+    const bool listed = t < ntx * nty && !skip;
+    const unsigned long long keep[2] = {__ballot(listed && !own_quiet), __ballot(listed && own_quiet)};
+    if (lane == 0) {
+        wbase[0][wv] = __popcll(keep[0]);
+        wbase[1][wv] = __popcll(keep[1]);
+    }
     __syncthreads();
-    if (threadIdx.x == 0) {
+    if (threadIdx.x < 2) {
+        const int c = threadIdx.x;
         int n = 0;
 #pragma unroll
         for (int k = 0; k < TL_THREADS / WAVE; k++) {
-            const int c = wbase[k];
-            wbase[k] = n;
-            n += c;
+            const int m = wbase[c][k];
+            wbase[c][k] = n;
+            n += m;
         }
-        base = n ? atomicAdd(&next->count, n) : 0;
+        base[c] = n ? atomicAdd(c ? &next->nq : &next->na, n) : 0;
     }
     __syncthreads();
-    if ((keep >> lane) & 1) list[base + wbase[wv] + __popcll(keep & ((1ull << lane) - 1))] = t;
+    if (listed) {
+        const int c = own_quiet ? 1 : 0;
+        const int i = base[c] + wbase[c][wv] + __popcll(keep[c] & ((1ull << lane) - 1));
+        list[c ? ntx * nty - 1 - i : i] = t;
+    }
 }
 
 // Full launches: workgroup b takes tile b (through the chunked order below).  List launches (tq_list set, one
 // workgroup per tile of the grid): workgroup 0 first publishes the Courant number of the skipped tiles, dt/d times the
-// maxima tq_next holds; then workgroup b takes list entry b, through the same order, and the workgroups past the
-// list's end (tq_next->count) return at once.  Dispatch order puts the listed tiles first.
+// maxima tq_next holds; then workgroup b takes the b-th listed tile, through the same order -- the na tiles of class A
+// from the front of the list, then the nq of class Q from its back -- and the workgroups past the list's end return at
+// once.  Dispatch order puts the listed tiles first and, among them, the tiles that compute (those
+// set the kernel's end when they wait for a slot behind the quiet ones).
 template <class RP, bool FWAVE, bool SRC>
 __global__ __launch_bounds__(F_THREADS, 1024 / F_THREADS) void step2ds_kernel(SweepArgs a, int ntx, int nty,
                                                                               unsigned *__restrict__ tq_out,
@@ -185,11 +201,15 @@ __global__ __launch_bounds__(F_THREADS, 1024 / F_THREADS) void step2ds_kernel(Sw
         const unsigned long long bits = (unsigned long long)__double_as_longlong(c);
         if (bits) atomicMax(a.cfl, bits);
     }
-    const int nb = tq_list ? min(tq_next->count, ntx * nty) : (int)gridDim.x;
+    const int nt = ntx * nty;
+    const int na = tq_list ? min(tq_next->na, nt) : 0;
+    const int nb = tq_list ? min(na + tq_next->nq, nt) : (int)gridDim.x;
     if (bid >= nb) return;                           // past the list: the whole workgroup, before any barrier
     const int win = bid >> 6;
     if ((win + 1) << 6 <= nb) bid = (win << 6) + ((bid & 7) << 3) + ((bid >> 3) & 7);
-    if (tq_list) bid = tq_list[bid];
+    // class Q: the tile's own word was TQ_ALL in the launch before (handover_list_kernel)
+    const bool class_q = tq_list && bid >= na;
+    if (tq_list) bid = tq_list[class_q ? nt - 1 - (bid - na) : bid];
     int tx = bid % ntx, ty = bid / ntx;
     if (a.sub != 0) {
         // decomposed block (pclaw.hip): the tiles inside box = [ty_lo, ty_hi) x [tx_lo, tx_hi) read no ghost cell a
@@ -341,13 +361,29 @@ __global__ __launch_bounds__(F_THREADS, 1024 / F_THREADS) void step2ds_kernel(Sw
             }
         }
     }
+    // A class-Q tile quiet again needs no store: the launch before left it quiet, so its owned cells in
+    // qout (that launch's input) equal qin (that launch's output), and quiet now they are also this launch's result.
+    // Not under the fused source, whose fixed-point test needs the stored cells.  Each wavefront leaves its quiet flag
+    // in halo row 0 of column F_CY * wv: only this wavefront's y sweep reads that cell, and the store does not.
+    if (!SRC && class_q && lane == 0) {
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        tile[ftile_at(0, 0, F_CY * wv)] = quiet ? 1.0 : 0.0;
+    }
     __syncthreads();
+    bool keep_store = true;
+    if (!SRC && class_q) {
+        keep_store = false;
+#pragma unroll
+        for (int w = 0; w < F_WAVES; w++) keep_store = keep_store || tile[ftile_at(0, 0, F_CY * w)] == 0.0;
+    }
 
     // ---- store: the tile's own interior cells --------------------------------------------------------------------
     const bool all_interior = full_tile && x0 + HALO >= a.mbc && x0 + HALO + F_OWN_C <= a.mbc + a.mx && y0 + HALO >= a.mbc &&
                               y0 + HALO + F_OWN_R <= a.mbc + a.my;
     bool src_fixed = true;                            // every cell this lane stored is a fixed point of the source
-    if (all_interior) {
+    if (!keep_store) {
+        // qout holds this launch's result already
+    } else if (all_interior) {
         constexpr int PAIRS = F_OWN_C / 2, SLOTS = PAIRS * F_OWN_R;
 #pragma unroll
         for (int k = 0; k < (SLOTS + F_THREADS - 1) / F_THREADS; k++) {

@@ -1883,13 +1883,29 @@ int pcl_tile_skip_stats(pcl_solver *s, long *computed, long *skipped) {
     long n = nt;
     if (s->tq_stats == 2) {
         HIP_TRY(hipSetDevice(s->cfg.device));
-        int c = 0;
+        int c[2] = {0, 0};
         HIP_TRY(hipStreamSynchronize(s->stream));
-        HIP_TRY(hipMemcpy(&c, &s->tq_next[s->tq_stat_nx].count, sizeof(int), hipMemcpyDeviceToHost));
-        n = c;
+        HIP_TRY(hipMemcpy(c, &s->tq_next[s->tq_stat_nx].na, 2 * sizeof(int), hipMemcpyDeviceToHost));
+        n = (long)c[0] + c[1];
     }
     *computed = n;
     *skipped = nt - n;
+    return PCL_OK;
+}
+
+// the two classes of the list the last one-kernel launch ran over (classic_fused.hpp: handover_list_kernel): class A
+// computed something in the launch before, class Q was quiet there; both 0 when that launch did not run over a list
+int pcl_tile_list_classes(pcl_solver *s, long *na, long *nq) {
+    if (s) s->tq_drop();                  // quiet tiles: not a read-only call (pcl_solver::tq_valid)
+    if (!s || !na || !nq) return fail(PCL_EINVAL, "null argument");
+    *na = *nq = 0;
+    if (s->tq_stats != 2) return PCL_OK;
+    HIP_TRY(hipSetDevice(s->cfg.device));
+    int c[2] = {0, 0};
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    HIP_TRY(hipMemcpy(c, &s->tq_next[s->tq_stat_nx].na, 2 * sizeof(int), hipMemcpyDeviceToHost));
+    *na = c[0];
+    *nq = c[1];
     return PCL_OK;
 }
 

@@ -137,12 +137,13 @@ struct RkLaunch {
     int op;
 };
 
-// The tile list's small state (classic_fused.hpp): the number of listed tiles and the largest cached Courant maxima
-// (bit patterns of doubles >= +0, before dt/d) of the x and y sweeps over the tiles it skips.  Three of them, rotating:
+// The tile list's small state (classic_fused.hpp): the number of listed tiles of class A (they computed something in the
+// launch before; from the list's front) and of class Q (quiet there; from its back), and the largest cached Courant
+// maxima (bit patterns of doubles >= +0, before dt/d) of the x and y sweeps over the tiles it skips.  Three of them, rotating:
 // a hand-over+list launch fills one and zeroes the one the hand-over after it fills; the third keeps the list the last
 // launch ran over (pcl_tile_skip_stats).
 struct TileNext {
-    int count, pad;
+    int na, nq;
     unsigned long long cx, cy;
 };
 
@@ -156,7 +157,7 @@ struct SweepLaunch {
     int char_decomp = 0;   // SharpClaw: 1 = wave-based reconstruction (1-D: tvd2_wave / weno5_wave)
     hipStream_t stream;
     // one-kernel step only (classic_fused.hpp, quiet tiles): this launch's per-tile words and per-wavefront Courant
-    // maxima (tq_out null: no bookkeeping).  A list launch (tq_list set) computes the tq_next->count tiles a
+    // maxima (tq_out null: no bookkeeping).  A list launch (tq_list set) computes the tq_next->na + nq tiles a
     // hand-over+list kernel listed behind the previous launch and publishes the Courant number of those it skips.
     unsigned *tq_out = nullptr;
     double2 *tq_cfl = nullptr;
