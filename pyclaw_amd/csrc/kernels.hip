@@ -114,6 +114,7 @@ int launch_sweep(const SweepLaunch &l, std::string &err) {
 // the whole dimension-split 2-D step, qin -> qout (classic_fused.hpp); l.a as for the x pass + a.dtd_t = dt/dy and
 // a.src_id of the step.  The host (pclaw.hip: fused_step_ok) only sends what the kernel covers.
 namespace {
+static_assert(F_OWN_C == TILE_OWN_C && F_OWN_R == TILE_OWN_R, "the host counts tiles with TILE_OWN_* (sweep_args.hpp)");
 template <class RP> int launch_step2ds_t(const SweepLaunch &l, std::string &err) {
     const SweepArgs &a = l.a;
     constexpr bool FW = IsFwave<RP>::value;

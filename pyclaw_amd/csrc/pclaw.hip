@@ -15,6 +15,7 @@
 #include "../../include/pyclaw_amd.h"
 #include "sweep_args.hpp"
 #include "halo.hpp"
+#include "quiet_tiles.hpp"
 
 namespace {
 
@@ -94,36 +95,7 @@ struct pcl_solver {
     void ghosts_mark(const double *buf) { if (!ghosts_filled(buf)) { ghost_ok[1] = ghost_ok[0]; ghost_ok[0] = buf; } }
     void ghosts_drop(const double *buf) { for (auto &g : ghost_ok) if (g == buf) g = nullptr; }
     void ghosts_drop_all() { ghost_ok[0] = ghost_ok[1] = nullptr; }
-    // Quiet tiles of the one-kernel dim-split step (classic_fused.hpp): one 32-bit word per tile in three
-    // arrays (a launch reads tq[tq_cur] and writes tq[tq_cur + 1], the list built behind it writes the skipped tiles'
-    // words of the next launch into the third), per-wavefront Courant maxima.  tq_valid: the last launch was a
-    // one-kernel step of the whole block, tq_last_in -> tq_last_out with the settings tq_key, and since then only the
-    // swap of pcl_step_hyperbolic and read-only calls have happened.  Fail-safe: every C entry point that is not on that
-    // list calls tq_drop() first (tests/test_quiet_tiles_cpu.py checks the source for it).
-    struct TqKey {
-        int rp, fwave, math, src;
-        double src_p[2];
-        pcl::RpParams par;
-        bool operator==(const TqKey &o) const { return memcmp(this, &o, sizeof(TqKey)) == 0; }
-    };
-    unsigned *tq[3] = {nullptr, nullptr, nullptr};
-    double2 *tq_cfl = nullptr;
-    // The next launch's tile list: handover_list_kernel builds it behind a one-kernel launch of the whole block
-    // (tq_hand, set by that launch, read by read_cfl_end) into tq_list and tq_next[tq_nx - 1] (tq_listed once
-    // enqueued).  The next launch runs over the list only if it may skip (do_step2ds); any other step drops it.
-    int *tq_list = nullptr;
-    pcl::TileNext *tq_next = nullptr;   // three, rotating: the next hand-over fills tq_next[tq_nx], zeroes tq_next[tq_nx + 1]
-    int tq_nx = 0;
-    bool tq_hand = false, tq_listed = false;
-    int tq_stat_nx = 0;                 // the block of the list the last skipping launch ran over (pcl_tile_skip_stats)
-    int tq_ntx = 0, tq_nty = 0;
-    int tq_enable = 1;              // pcl_tile_skip
-    int tq_cur = 0;
-    bool tq_valid = false;
-    const double *tq_last_in = nullptr, *tq_last_out = nullptr;
-    TqKey tq_key;
-    int tq_stats = 0;               // the last one-kernel launch: 0 none (or no bookkeeping), 1 computed every tile, 2 could skip
-    void tq_drop() { tq_valid = false; }
+    pcl::QuietTiles qt;             // quiet tiles of the one-kernel dim-split step: state and invariants in quiet_tiles.hpp
 };
 
 static inline double *&cur(pcl_solver *s) { return s->sel == 0 ? s->q : s->sreg[s->sel]; }
@@ -346,6 +318,28 @@ int drain_timing(pcl_solver *s) {
     return PCL_OK;
 }
 
+// HIP events around one launch (pcl_kernel_timing); `on` false: nothing is enqueued
+struct LaunchTimer {
+    pcl_solver *s;
+    hipStream_t stream;
+    bool on;
+    pcl_solver::Timed t{};
+    LaunchTimer(pcl_solver *s_, bool on_, int which, bool count, hipStream_t stream_) : s(s_), stream(stream_), on(on_) {
+        if (!on) return;
+        t.a = get_event(s);
+        t.b = get_event(s);
+        t.which = which;
+        t.count = count;
+        hipEventRecord(t.a, stream);
+    }
+    void end() {
+        if (!on) return;
+        hipEventRecord(t.b, stream);
+        s->timed.push_back(t);
+        if (s->timed.size() >= 2048) drain_timing(s);
+    }
+};
+
 // Ghost frame of the unsplit step in ONE launch: every cell outside the interior gets its boundary value -- the
 // composition of the per-side fills of solver.py:354-452 (x sides first, then y sides over the x-filled columns, so a
 // corner cell is the y rule applied to an x-ghost cell) written as an index remap, like the dim-split x pass does
@@ -442,15 +436,8 @@ int do_sweep(pcl_solver *s, const double *qin, double *qout, int ids, double dt,
                            s->cfg.meqn, s->I, s->J, s->cfg.mbc, s->pitch, s->plane, f);
         HIP_TRY(hipGetLastError());
     }
-    pcl_solver::Timed t{};
-    const bool timed = timing_on(s) && !on;  // a launch on the halo stream runs beside the interior: not timed
-    if (timed) {
-        t.a = get_event(s);
-        t.b = get_event(s);
-        t.which = ids - 1;
-        t.count = sub != 2;
-        hipEventRecord(t.a, stream);
-    }
+    // (a launch on the halo stream runs beside the interior: not timed)
+    LaunchTimer timer(s, timing_on(s) && !on, ids - 1, sub != 2, stream);
     SweepLaunch l;
     l.a = a;
     l.ndim = s->cfg.ndim;
@@ -461,11 +448,7 @@ int do_sweep(pcl_solver *s, const double *qin, double *qout, int ids, double dt,
     std::string err;
     int rc = PCL_BY_MATH(s->cfg.math, launch_sweep(l, err));
     if (rc) fail(rc, err);
-    if (timed) {
-        hipEventRecord(t.b, stream);
-        s->timed.push_back(t);
-        if (s->timed.size() >= 2048) drain_timing(s);
-    }
+    timer.end();
     return rc;
 }
 
@@ -494,7 +477,8 @@ bool twopass_overlap_ok(const pcl_solver *s) {
                              (rp == PCL_RP_EULER5_2D || rp == PCL_RP_ACOUSTICS_2D || rp == PCL_RP_ADVECTION_2D || rp == PCL_RP_SHALLOW_2D);
     return !(onek_family && s->overlap_dflt);
 }
-int do_step2ds(pcl_solver *s, const double *qin, double *qout, double dt, int sub = 0, const int *box = nullptr,
+// carry: the quiet-tile words of the previous launch still hold (QuietTiles::take_valid at the step's entry point)
+int do_step2ds(pcl_solver *s, const double *qin, double *qout, double dt, bool carry, int sub = 0, const int *box = nullptr,
                hipStream_t on = nullptr) {
     hipStream_t stream = on ? on : s->stream;
     SweepArgs a = make_args(s, qin, qout, 1, dt);
@@ -502,15 +486,7 @@ int do_step2ds(pcl_solver *s, const double *qin, double *qout, double dt, int su
     a.src_id = s->fused_src;
     a.sub = sub;
     if (sub) for (int k = 0; k < 4; k++) a.box[k] = box[k];
-    pcl_solver::Timed t{};
-    const bool timed = timing_on(s) && !on;
-    if (timed) {
-        t.a = get_event(s);
-        t.b = get_event(s);
-        t.which = 2;
-        t.count = sub != 2;
-        hipEventRecord(t.a, stream);
-    }
+    LaunchTimer timer(s, timing_on(s) && !on, 2, sub != 2, stream);
     SweepLaunch l;
     l.a = a;
     l.ndim = 2;
@@ -518,54 +494,14 @@ int do_step2ds(pcl_solver *s, const double *qin, double *qout, double dt, int su
     l.ids = 1;
     l.fwave = s->cfg.fwave;
     l.stream = stream;
-    // quiet tiles: the whole block only (a decomposed block's ghost frame and tile subsets are left out)
-    const bool book = sub == 0 && !s->halo.active && s->tq[0];
-    pcl_solver::TqKey key;
-    memset(&key, 0, sizeof(key));     // (compared bytewise)
-    key.rp = s->cfg.rp;
-    key.fwave = s->cfg.fwave;
-    key.math = s->cfg.math;
-    key.src = a.src_id;
-    key.src_p[0] = a.src_p[0];
-    key.src_p[1] = a.src_p[1];
-    key.par = a.par;
-    if (book) {
-        // the previous launch ran on the swapped pair with the same settings, the list behind it was built and nothing
-        // has happened since; under the fused source its fixed-point test (euler_radial_source_fixed) holds for these
-        // dt, gamma1 and ndim - 1; dt is positive and finite (the skipped tiles' Courant number: DESIGN.md 4.1a)
-        const bool src_ok = a.src_id == 0 || (dt <= SRC_FIXED_BOUND && fabs(a.src_p[0]) <= SRC_FIXED_BOUND &&
-                                               fabs(a.src_p[1]) <= SRC_FIXED_BOUND);
-        const bool skip = s->tq_enable && s->tq_valid && s->tq_listed && s->tq_last_in == qout &&
-                          s->tq_last_out == qin && s->tq_key == key && src_ok && dt > 0.0 && dt < HUGE_VAL;
-        l.tq_out = s->tq[(s->tq_cur + 1) % 3];
-        l.tq_cfl = s->tq_cfl;
-        if (skip) {
-            l.tq_list = s->tq_list;
-            l.tq_next = s->tq_next + (s->tq_nx + 2) % 3;
-        }
-    }
-    s->tq_drop();
-    s->tq_listed = false;
-    s->tq_hand = false;
-    s->tq_stats = 0;
+    // quiet tiles (quiet_tiles.hpp): the whole block only (a decomposed block's ghost frame and tile subsets are left out)
+    const QuietTiles::Key key(s->cfg.rp, s->cfg.fwave, s->cfg.math, a);
+    const bool book = s->qt.plan(l, qin, qout, key, dt, sub == 0 && !s->halo.active, carry);
     std::string err;
     int rc = PCL_BY_MATH(s->cfg.math, launch_step2ds(l, err));
     if (rc) fail(rc, err);
-    if (book && !rc) {
-        s->tq_cur = (s->tq_cur + 1) % 3;
-        s->tq_valid = true;
-        s->tq_last_in = qin;
-        s->tq_last_out = qout;
-        s->tq_key = key;
-        s->tq_stats = l.tq_list ? 2 : 1;
-        s->tq_stat_nx = (s->tq_nx + 2) % 3;
-        s->tq_hand = s->tq_enable != 0;       // read_cfl_end builds the next launch's list behind this one
-    }
-    if (timed) {
-        hipEventRecord(t.b, stream);
-        s->timed.push_back(t);
-        if (s->timed.size() >= 2048) drain_timing(s);
-    }
+    if (book && !rc) s->qt.launched(l, qin, qout, key);
+    timer.end();
     return rc;
 }
 
@@ -585,14 +521,7 @@ int do_sweep3(pcl_solver *s, const double *qin, double *qout, int dir, double dt
     a.lo_ac = mbc - 1; a.hi_ac = mbc + s->cfg.n[ac];   // slices 0..m+1: one ghost layer (step3ds.f:110-111)
     a.lo_b = mbc - 1; a.hi_b = mbc + s->cfg.n[bt];
     a.vbc_on = 0;
-    pcl_solver::Timed t{};
-    if (timing_on(s)) {
-        t.a = get_event(s);
-        t.b = get_event(s);
-        t.which = dir == 1 ? 0 : 1;
-        t.count = true;
-        hipEventRecord(t.a, s->stream);
-    }
+    LaunchTimer timer(s, timing_on(s), dir == 1 ? 0 : 1, true, s->stream);
     SweepLaunch l;
     l.a = a;
     l.ndim = 3;
@@ -603,11 +532,7 @@ int do_sweep3(pcl_solver *s, const double *qin, double *qout, int dir, double dt
     std::string err;
     int rc = PCL_BY_MATH(s->cfg.math, launch_sweep3(l, err));
     if (rc) fail(rc, err);
-    if (timing_on(s)) {
-        hipEventRecord(t.b, s->stream);
-        s->timed.push_back(t);
-        if (s->timed.size() >= 2048) drain_timing(s);
-    }
+    timer.end();
     return rc;
 }
 
@@ -635,10 +560,9 @@ int do_unsplit3(pcl_solver *s, double dt) {
         l.dty = dt / s->cfg.d[e]; l.dtz = dt / s->cfg.d[f];
         l.dir = dir; l.rp = s->cfg.rp; l.stream = s->stream;
         (void)mbc;
-        pcl_solver::Timed t{};
-        if (timing_on(s)) { t.a = get_event(s); t.b = get_event(s); t.which = dir == 1 ? 0 : 1; t.count = true; hipEventRecord(t.a, s->stream); }
+        LaunchTimer timer(s, timing_on(s), dir == 1 ? 0 : 1, true, s->stream);
         int rc = PCL_BY_MATH(s->cfg.math, launch_unsplit3(l, err));
-        if (timing_on(s)) { hipEventRecord(t.b, s->stream); s->timed.push_back(t); }
+        timer.end();
         if (rc) return fail(rc, err);
     }
     return PCL_OK;
@@ -666,10 +590,9 @@ static int unsplit_phase(pcl_solver *s, int ids, double dt, int sub, hipStream_t
     l.a.dtd_t = dt / s->cfg.d[2 - ids];
     l.a.sub = sub;
     l.ndim = 2; l.rp = s->cfg.rp; l.ids = ids; l.fwave = s->cfg.fwave; l.stream = stream;
-    pcl_solver::Timed t{};
-    if (timing_on(s)) { t.a = get_event(s); t.b = get_event(s); t.which = ids - 1; t.count = sub != 2; hipEventRecord(t.a, stream); }
+    LaunchTimer timer(s, timing_on(s), ids - 1, sub != 2, stream);
     int rc = PCL_BY_MATH(s->cfg.math, launch_unsplit(l, s->t1, err));
-    if (timing_on(s)) { hipEventRecord(t.b, stream); s->timed.push_back(t); }
+    timer.end();
     if (rc) return fail(rc, err);
     return PCL_OK;
 }
@@ -718,36 +641,20 @@ int read_cfl_end(pcl_solver *s, double *cfl) {
     // launch of the whole block, the same hand-over is workgroup 0 of a kernel whose other workgroups list the next
     // launch's tiles (classic_fused.hpp: handover_list_kernel) while the host turns round.
     const unsigned long long seq = ++s->cfl_seq;
-    const bool hand = s->tq_hand;
-    s->tq_hand = false;
-    s->tq_listed = false;
-    if (hand) {
-        TileHandover h;
+    TileHandover h;
+    if (s->qt.handover(h)) {
         h.cfl = s->cfl_dev;
         h.host = s->cfl_host_dev;
         h.seq = seq;
-        h.ntx = s->tq_ntx;
-        h.nty = s->tq_nty;
         h.mbc = s->cfg.mbc;
         h.mx = s->cfg.n[0];
         h.my = s->cfg.n[1];
-        h.tq_in = s->tq[s->tq_cur];
-        h.tq_out = s->tq[(s->tq_cur + 1) % 3];
-        h.tq_cfl = s->tq_cfl;
-        h.tq_list = s->tq_list;
-        h.next = s->tq_next + s->tq_nx;
-        h.other = s->tq_next + (s->tq_nx + 1) % 3;
         h.stream = s->stream;
         std::string err;
         // (no arithmetic: the exact build serves every mode)
-        if (int rc = pcl::exact::launch_tile_handover(h, err)) {
-            // nothing ran: the list state back to its start (every block zero)
-            (void)hipMemsetAsync(s->tq_next, 0, 3 * sizeof(pcl::TileNext), s->stream);
-            s->tq_nx = 0;
-            return fail(rc, err);
-        }
-        s->tq_listed = true;
-        s->tq_nx = (s->tq_nx + 1) % 3;
+        const int rc = pcl::exact::launch_tile_handover(h, err);
+        s->qt.handed_over(rc == PCL_OK, s->stream);
+        if (rc) return fail(rc, err);
     } else {
         hipLaunchKernelGGL(cfl_handover, dim3(1), dim3(1), 0, s->stream, s->cfl_dev, s->cfl_host_dev, seq);
         HIP_TRY(hipGetLastError());
@@ -916,16 +823,8 @@ int pcl_create(const pcl_config *cfg, pcl_solver **out) {
     }
     if (cfg->maux > 0) alloc(&s->aux, (size_t)s->plane * cfg->maux * sizeof(double));
     if (cfg->kind == PCL_KIND_CLASSIC && cfg->ndim == 2 && cfg->mbc == 2) {
-        // quiet-tile words and Courant maxima of the one-kernel step (its 16 x 64 tiles own 12 x 60 cells)
-        s->tq_ntx = (cfg->n[0] + 59) / 60;
-        s->tq_nty = (cfg->n[1] + 11) / 12;
-        const size_t nt = (size_t)s->tq_ntx * s->tq_nty;
-        for (auto &w : s->tq)
-            if (e == hipSuccess) e = hipMalloc((void **)&w, nt * sizeof(unsigned));
-        if (e == hipSuccess) e = hipMalloc((void **)&s->tq_cfl, nt * 4 * sizeof(double2));
-        if (e == hipSuccess) e = hipMalloc((void **)&s->tq_list, nt * sizeof(int));
-        if (e == hipSuccess) e = hipMalloc((void **)&s->tq_next, 3 * sizeof(pcl::TileNext));
-        if (e == hipSuccess) e = hipMemsetAsync(s->tq_next, 0, 3 * sizeof(pcl::TileNext), s->stream);
+        // quiet tiles of the one-kernel step
+        if (e == hipSuccess) e = s->qt.create(cfg->n[0], cfg->n[1], s->stream);
     }
     const int nmax = cfg->meqn > cfg->maux ? cfg->meqn : cfg->maux;
     s->stage_bytes = (size_t)nmax * s->I * s->J * s->K * sizeof(double);
@@ -963,11 +862,7 @@ void pcl_destroy(pcl_solver *s) {
     for (int k = 1; k < 5; k++)
         if (s->sreg[k]) hipFree(s->sreg[k] - s->lead);
     hipFree(s->cfl_dev);
-    for (unsigned *w : s->tq)
-        if (w) hipFree(w);
-    if (s->tq_cfl) hipFree(s->tq_cfl);
-    if (s->tq_list) hipFree(s->tq_list);
-    if (s->tq_next) hipFree(s->tq_next);
+    s->qt.destroy();
     if (s->cfl_host) hipHostFree(s->cfl_host);
     if (s->ev0) hipEventDestroy(s->ev0);
     if (s->ev1) hipEventDestroy(s->ev1);
@@ -994,7 +889,7 @@ static int put_array(pcl_solver *s, const double *host, double *dev, int nm, int
 }
 
 int pcl_put_q(pcl_solver *s, const double *host, int with_ghosts) {
-    if (s) s->tq_drop();                  // quiet tiles: not a read-only call (pcl_solver::tq_valid)
+    if (s) s->qt.invalidate();            // quiet tiles: not a read-only call (quiet_tiles.hpp)
     if (s) s->ghosts_drop_all();          // exchange-ahead: whatever filled the ghost frames no longer holds
     if (!s || !host) return fail(PCL_EINVAL, "null argument");
     HIP_TRY(hipSetDevice(s->cfg.device));
@@ -1003,7 +898,7 @@ int pcl_put_q(pcl_solver *s, const double *host, int with_ghosts) {
 }
 
 int pcl_put_aux(pcl_solver *s, const double *host) {
-    if (s) s->tq_drop();                  // quiet tiles: not a read-only call (pcl_solver::tq_valid)
+    if (s) s->qt.invalidate();            // quiet tiles: not a read-only call (quiet_tiles.hpp)
     if (!s || !host) return fail(PCL_EINVAL, "null argument");
     if (s->cfg.maux <= 0) return fail(PCL_EINVAL, "solver was created with maux == 0");
     HIP_TRY(hipSetDevice(s->cfg.device));
@@ -1060,7 +955,7 @@ int pcl_get_strip(pcl_solver *s, int idim, int side, int width, double *host) {
 }
 
 int pcl_put_strip(pcl_solver *s, int idim, int side, int width, const double *host) {
-    if (s) s->tq_drop();                  // quiet tiles: not a read-only call (pcl_solver::tq_valid)
+    if (s) s->qt.invalidate();            // quiet tiles: not a read-only call (quiet_tiles.hpp)
     if (s) s->ghosts_drop_all();          // exchange-ahead: whatever filled the ghost frames no longer holds
     if (!s || !host) return fail(PCL_EINVAL, "null argument");
     HIP_TRY(hipSetDevice(s->cfg.device));
@@ -1079,7 +974,7 @@ int pcl_put_strip(pcl_solver *s, int idim, int side, int width, const double *ho
 
 // the same for the aux array: a ghost strip computed by a Python aux-BC callback on the host (decomposed runs)
 int pcl_put_aux_strip(pcl_solver *s, int idim, int side, int width, const double *host) {
-    if (s) s->tq_drop();                  // quiet tiles: not a read-only call (pcl_solver::tq_valid)
+    if (s) s->qt.invalidate();            // quiet tiles: not a read-only call (quiet_tiles.hpp)
     if (!s || !host) return fail(PCL_EINVAL, "null argument");
     if (s->cfg.maux <= 0 || !s->aux) return fail(PCL_ESTATE, "pcl_put_aux_strip: no aux array on the device");
     HIP_TRY(hipSetDevice(s->cfg.device));
@@ -1166,7 +1061,7 @@ static int bc_launch(pcl_solver *s, int idim, int side, int type, const double *
 }
 
 int pcl_bc(pcl_solver *s, int idim, int side, int bctype) {
-    if (s) s->tq_drop();                  // quiet tiles: not a read-only call (pcl_solver::tq_valid)
+    if (s) s->qt.invalidate();            // quiet tiles: not a read-only call (quiet_tiles.hpp)
     if (s) s->ghosts_drop_all();          // exchange-ahead: whatever filled the ghost frames no longer holds
     if (!s) return fail(PCL_EINVAL, "null argument");
     if (idim < 0 || idim >= s->cfg.ndim || side < 0 || side > 1) return fail(PCL_EINVAL, "bad idim/side");
@@ -1185,7 +1080,7 @@ int pcl_bc(pcl_solver *s, int idim, int side, int bctype) {
 }
 
 int pcl_bc_aux(pcl_solver *s, int idim, int side, int bctype) {
-    if (s) s->tq_drop();                  // quiet tiles: not a read-only call (pcl_solver::tq_valid)
+    if (s) s->qt.invalidate();            // quiet tiles: not a read-only call (quiet_tiles.hpp)
     if (!s) return fail(PCL_EINVAL, "null argument");
     if (s->cfg.maux <= 0) return PCL_OK;
     if (idim < 0 || idim >= s->cfg.ndim || side < 0 || side > 1) return fail(PCL_EINVAL, "bad idim/side");
@@ -1196,7 +1091,7 @@ int pcl_bc_aux(pcl_solver *s, int idim, int side, int bctype) {
 }
 
 int pcl_bc_const(pcl_solver *s, int idim, int side, const double *state) {
-    if (s) s->tq_drop();                  // quiet tiles: not a read-only call (pcl_solver::tq_valid)
+    if (s) s->qt.invalidate();            // quiet tiles: not a read-only call (quiet_tiles.hpp)
     if (s) s->ghosts_drop_all();          // exchange-ahead: whatever filled the ghost frames no longer holds
     if (!s || !state) return fail(PCL_EINVAL, "null argument");
     if (idim < 0 || idim >= s->cfg.ndim || side < 0 || side > 1) return fail(PCL_EINVAL, "bad idim/side");
@@ -1206,7 +1101,7 @@ int pcl_bc_const(pcl_solver *s, int idim, int side, const double *state) {
 }
 
 int pcl_sweep(pcl_solver *s, int ids, double dt, double *cfl) {
-    if (s) s->tq_drop();                  // quiet tiles: not a read-only call (pcl_solver::tq_valid)
+    if (s) s->qt.invalidate();            // quiet tiles: not a read-only call (quiet_tiles.hpp)
     if (s) s->ghosts_drop_all();          // exchange-ahead: whatever filled the ghost frames no longer holds
     if (!s || !cfl) return fail(PCL_EINVAL, "null argument");
     if (s->cfg.kind != PCL_KIND_CLASSIC) return fail(PCL_ESTATE, "classic call on a SharpClaw solver");
@@ -1219,12 +1114,9 @@ int pcl_sweep(pcl_solver *s, int ids, double dt, double *cfl) {
     return read_cfl(s, cfl);
 }
 
-int pcl_step_hyperbolic(pcl_solver *s, double dt, double *cfl) {
-    if (s) s->ghosts_drop_all();          // exchange-ahead: whatever filled the ghost frames no longer holds
-    if (!s || !cfl) return fail(PCL_EINVAL, "null argument");
-    // quiet tiles: only the one-kernel form of the step below carries the words of the previous launch on
-    const bool tq_keep = s->tq_valid;
-    s->tq_drop();
+// the body of pcl_step_hyperbolic.  carry: the quiet-tile words of the previous launch still hold; only the one-kernel
+// form of the step carries them on
+static int step_hyperbolic(pcl_solver *s, double dt, double *cfl, bool carry) {
     if (s->cfg.kind != PCL_KIND_CLASSIC) return fail(PCL_ESTATE, "classic call on a SharpClaw solver");
     HIP_TRY(hipSetDevice(s->cfg.device));
     if (s->cfg.ndim == 3) {  // Godunov splitting x, y, z (clawpack.py:674-690)
@@ -1264,8 +1156,7 @@ int pcl_step_hyperbolic(pcl_solver *s, double dt, double *cfl) {
         }
         const auto t0 = std::chrono::steady_clock::now();
         if (form == 1) {
-            s->tq_valid = tq_keep;
-            if (int rc = do_step2ds(s, s->q, s->t2, dt)) return bail(s, rc);
+            if (int rc = do_step2ds(s, s->q, s->t2, dt, carry)) return bail(s, rc);
         } else {
             if (int rc = do_sweep(s, s->q, s->t1, 1, dt)) return bail(s, rc);
             if (int rc = do_sweep(s, s->t1, s->t2, 2, dt)) return bail(s, rc);
@@ -1291,12 +1182,17 @@ int pcl_step_hyperbolic(pcl_solver *s, double dt, double *cfl) {
     return read_cfl(s, cfl);
 }
 
+int pcl_step_hyperbolic(pcl_solver *s, double dt, double *cfl) {
+    if (s) s->ghosts_drop_all();          // exchange-ahead: whatever filled the ghost frames no longer holds
+    if (!s || !cfl) return fail(PCL_EINVAL, "null argument");
+    return step_hyperbolic(s, dt, cfl, s->qt.take_valid());
+}
+
 int pcl_bc_step(pcl_solver *s, const int *bc, const double *cstate, double dt, double *cfl) {
     if (!s || !bc || !cfl) return fail(PCL_EINVAL, "null argument");
     // quiet tiles: only the whole block's step with the boundary conditions evaluated while loading (no ghost fill, no
-    // exchange: pcl_step_hyperbolic below) carries the words of the previous launch on
-    const bool tq_keep = s->tq_valid;
-    s->tq_drop();
+    // exchange: the fused step below) carries the words of the previous launch on
+    const bool carry = s->qt.take_valid();
     if (s->cfg.kind != PCL_KIND_CLASSIC) return fail(PCL_ESTATE, "classic call on a SharpClaw solver");
     HIP_TRY(hipSetDevice(s->cfg.device));
     for (int k = 0; k < 2 * s->cfg.ndim; k++) {
@@ -1390,7 +1286,7 @@ int pcl_bc_step(pcl_solver *s, const int *bc, const double *cstate, double dt, d
         s->vbc_on = 1;
         // the x pass of the two-pass step, or the whole step where one kernel does both sweeps
         auto first = [&](int sub, hipStream_t on) {
-            return onek ? do_step2ds(s, s->q, s->t2, dt, sub, box, on) : do_sweep(s, s->q, s->t1, 1, dt, sub, box, on);
+            return onek ? do_step2ds(s, s->q, s->t2, dt, false, sub, box, on) : do_sweep(s, s->q, s->t1, 1, dt, sub, box, on);
         };
         if (onek) s->ghosts_drop(s->t2);             // the step writes that buffer's interior: its frame is stale
         if (onek && s->overlap == 1 && s->exchange_ahead && s->ghosts_filled(s->q)) {
@@ -1427,7 +1323,8 @@ int pcl_bc_step(pcl_solver *s, const int *bc, const double *cstate, double dt, d
             rc = s->halo.exchange(s->q, s->cfg.meqn, s->pitch, s->plane, err) ? fail(PCL_ECOMM, err) : PCL_OK;
             if (rc) { s->vbc_on = 0; s->ghosts_drop_all(); return bail(s, rc); }
             s->form_seq_tune = 1;
-            rc = pcl_step_hyperbolic(s, dt, cfl);       // swaps the buffers, reads the (all-reduced) Courant number
+            s->ghosts_drop_all();
+            rc = step_hyperbolic(s, dt, cfl, false);    // swaps the buffers, reads the (all-reduced) Courant number
             s->form_seq_tune = 0;
             s->vbc_on = 0;
             return rc;
@@ -1502,8 +1399,8 @@ int pcl_bc_step(pcl_solver *s, const int *bc, const double *cstate, double dt, d
         }
         s->vbc_on = 1;
         s->form_seq_tune = s->halo.active ? 1 : 0;      // a decomposed block behind its exchange: the faster form, too
-        s->tq_valid = tq_keep && !s->halo.active;
-        const int rc = pcl_step_hyperbolic(s, dt, cfl);
+        s->ghosts_drop_all();
+        const int rc = step_hyperbolic(s, dt, cfl, carry && !s->halo.active);
         s->form_seq_tune = 0;
         s->vbc_on = 0;
         return rc;
@@ -1517,11 +1414,12 @@ int pcl_bc_step(pcl_solver *s, const int *bc, const double *cstate, double dt, d
                                : bc_launch(s, idim, side, t, nullptr);
             if (rc) return rc;
         }
-    return pcl_step_hyperbolic(s, dt, cfl);
+    s->ghosts_drop_all();
+    return step_hyperbolic(s, dt, cfl, false);
 }
 
 int pcl_undo_step(pcl_solver *s) {
-    if (s) s->tq_drop();                  // quiet tiles: not a read-only call (pcl_solver::tq_valid)
+    if (s) s->qt.invalidate();            // quiet tiles: not a read-only call (quiet_tiles.hpp)
     if (!s) return fail(PCL_EINVAL, "null argument");
     if (!s->undo_slot) return fail(PCL_ESTATE, "no step to undo");
     std::swap(s->q, *s->undo_slot);
@@ -1530,7 +1428,7 @@ int pcl_undo_step(pcl_solver *s) {
 }
 
 int pcl_backup(pcl_solver *s) {
-    if (s) s->tq_drop();                  // quiet tiles: not a read-only call (pcl_solver::tq_valid)
+    if (s) s->qt.invalidate();            // quiet tiles: not a read-only call (quiet_tiles.hpp)
     if (!s) return fail(PCL_EINVAL, "null argument");
     HIP_TRY(hipSetDevice(s->cfg.device));
     const size_t qbytes = (size_t)s->total * sizeof(double);
@@ -1544,7 +1442,7 @@ int pcl_backup(pcl_solver *s) {
 }
 
 int pcl_restore(pcl_solver *s) {
-    if (s) s->tq_drop();                  // quiet tiles: not a read-only call (pcl_solver::tq_valid)
+    if (s) s->qt.invalidate();            // quiet tiles: not a read-only call (quiet_tiles.hpp)
     if (s) s->ghosts_drop_all();          // exchange-ahead: whatever filled the ghost frames no longer holds
     if (!s) return fail(PCL_EINVAL, "null argument");
     if (!s->bak) return fail(PCL_ESTATE, "pcl_restore without pcl_backup");
@@ -1556,7 +1454,7 @@ int pcl_restore(pcl_solver *s) {
 }
 
 int pcl_src(pcl_solver *s, int src_id, double dt, const double *params, int nparams) {
-    if (s) s->tq_drop();                  // quiet tiles: not a read-only call (pcl_solver::tq_valid)
+    if (s) s->qt.invalidate();            // quiet tiles: not a read-only call (quiet_tiles.hpp)
     if (s) s->ghosts_drop_all();          // exchange-ahead: whatever filled the ghost frames no longer holds
     if (!s) return fail(PCL_EINVAL, "null argument");
     HIP_TRY(hipSetDevice(s->cfg.device));
@@ -1582,7 +1480,7 @@ int pcl_src(pcl_solver *s, int src_id, double dt, const double *params, int npar
 }
 
 int pcl_fuse_source(pcl_solver *s, int src_id, const double *params, int nparams) {
-    if (s) s->tq_drop();                  // quiet tiles: not a read-only call (pcl_solver::tq_valid)
+    if (s) s->qt.invalidate();            // quiet tiles: not a read-only call (quiet_tiles.hpp)
     if (!s) return fail(PCL_EINVAL, "null argument");
     if (src_id == 0) { s->fused_src = 0; return PCL_OK; }
     if (src_id != PCL_SRC_EULER_RADIAL) return fail(PCL_EINVAL, "pcl_fuse_source: only the Euler radial source can be fused");
@@ -1597,7 +1495,7 @@ int pcl_fuse_source(pcl_solver *s, int src_id, const double *params, int nparams
 }
 
 int pcl_sharp_fuse_dq_src(pcl_solver *s, int src_id, const double *params, int nparams) {
-    if (s) s->tq_drop();                  // quiet tiles: not a read-only call (pcl_solver::tq_valid)
+    if (s) s->qt.invalidate();            // quiet tiles: not a read-only call (quiet_tiles.hpp)
     if (!s) return fail(PCL_EINVAL, "null argument");
     if (s->cfg.kind != PCL_KIND_SHARPCLAW) return fail(PCL_EINVAL, "pcl_sharp_fuse_dq_src: not a SharpClaw solver");
     if (src_id == 0) { s->fused_src = 0; return PCL_OK; }
@@ -1614,7 +1512,7 @@ int pcl_sharp_fuse_dq_src(pcl_solver *s, int src_id, const double *params, int n
 }
 
 int pcl_select(pcl_solver *s, int reg) {
-    if (s) s->tq_drop();                  // quiet tiles: not a read-only call (pcl_solver::tq_valid)
+    if (s) s->qt.invalidate();            // quiet tiles: not a read-only call (quiet_tiles.hpp)
     if (s) s->ghosts_drop_all();          // exchange-ahead: whatever filled the ghost frames no longer holds
     if (!s) return fail(PCL_EINVAL, "null argument");
     if (reg == 0) { s->sel = 0; return PCL_OK; }
@@ -1637,10 +1535,9 @@ static int sharp_pass(pcl_solver *s, int ids, double dt, int rk_op, const double
     l.ndim = s->cfg.ndim; l.rp = s->cfg.rp; l.ids = ids; l.fwave = s->cfg.fwave;
     l.lim_type = s->cfg.lim_type; l.stream = stream;
     l.char_decomp = s->cfg.method[4];          // SharpClaw: clawparams.char_decomp travels in method(5) (unused by it)
-    pcl_solver::Timed t{};
-    if (timing_on(s)) { t.a = get_event(s); t.b = get_event(s); t.which = ids - 1; t.count = sub != 2; hipEventRecord(t.a, stream); }
+    LaunchTimer timer(s, timing_on(s), ids - 1, sub != 2, stream);
     int rc = PCL_BY_MATH(s->cfg.math, launch_sharp(l, err));
-    if (timing_on(s)) { hipEventRecord(t.b, stream); s->timed.push_back(t); if (s->timed.size() >= 2048) drain_timing(s); }
+    timer.end();
     if (rc) return fail(rc, err);
     return PCL_OK;
 }
@@ -1745,12 +1642,12 @@ static int sharp_dq_impl(pcl_solver *s, const int *bc, const double *cstate, dou
 }
 
 int pcl_sharp_dq(pcl_solver *s, double dt, double *cfl) {
-    if (s) s->tq_drop();                  // quiet tiles: not a read-only call (pcl_solver::tq_valid)
+    if (s) s->qt.invalidate();            // quiet tiles: not a read-only call (quiet_tiles.hpp)
     return sharp_dq_impl(s, nullptr, nullptr, dt, cfl);
 }
 
 int pcl_sharp_bc_dq(pcl_solver *s, const int *bc, const double *cstate, double dt, double *cfl) {
-    if (s) s->tq_drop();                  // quiet tiles: not a read-only call (pcl_solver::tq_valid)
+    if (s) s->qt.invalidate();            // quiet tiles: not a read-only call (quiet_tiles.hpp)
     if (!bc) return fail(PCL_EINVAL, "null argument");
     return sharp_dq_impl(s, bc, cstate, dt, cfl);
 }
@@ -1784,19 +1681,19 @@ static int sharp_stage_impl(pcl_solver *s, const int *bc, const double *cstate, 
 
 int pcl_sharp_stage(pcl_solver *s, double dt, int op, int D, int A, int B, double ca, double cb, double cc,
                     double cfl_max, double *cfl) {
-    if (s) s->tq_drop();                  // quiet tiles: not a read-only call (pcl_solver::tq_valid)
+    if (s) s->qt.invalidate();            // quiet tiles: not a read-only call (quiet_tiles.hpp)
     return sharp_stage_impl(s, nullptr, nullptr, dt, op, D, A, B, ca, cb, cc, cfl_max, cfl);
 }
 
 int pcl_sharp_bc_stage(pcl_solver *s, const int *bc, const double *cstate, double dt, int op, int D, int A, int B,
                        double ca, double cb, double cc, double cfl_max, double *cfl) {
-    if (s) s->tq_drop();                  // quiet tiles: not a read-only call (pcl_solver::tq_valid)
+    if (s) s->qt.invalidate();            // quiet tiles: not a read-only call (quiet_tiles.hpp)
     if (!bc) return fail(PCL_EINVAL, "null argument");
     return sharp_stage_impl(s, bc, cstate, dt, op, D, A, B, ca, cb, cc, cfl_max, cfl);
 }
 
 int pcl_rk_op(pcl_solver *s, int op, int D, int A, int B, int Cc, double ca, double cb, double cc) {
-    if (s) s->tq_drop();                  // quiet tiles: not a read-only call (pcl_solver::tq_valid)
+    if (s) s->qt.invalidate();            // quiet tiles: not a read-only call (quiet_tiles.hpp)
     if (!s) return fail(PCL_EINVAL, "null argument");
     if (s->cfg.kind != PCL_KIND_SHARPCLAW) return fail(PCL_ESTATE, "SharpClaw call on a classic solver");
     if (op < 1 || op > 6) return fail(PCL_EINVAL, "unknown RK op");
@@ -1866,26 +1763,31 @@ int pcl_step_form_stats(pcl_solver *s, double *ms_total, long *launches, long *s
 }
 
 int pcl_tile_skip(pcl_solver *s, int enable) {
-    if (s) s->tq_drop();                  // quiet tiles: not a read-only call (pcl_solver::tq_valid)
+    if (s) s->qt.invalidate();            // quiet tiles: not a read-only call (quiet_tiles.hpp)
     if (!s) return fail(PCL_EINVAL, "null argument");
-    s->tq_enable = enable ? 1 : 0;
+    s->qt.set_enabled(enable != 0);
+    return PCL_OK;
+}
+
+// na, nq of the list the last one-kernel launch ran over (last_launch() == LIST; classic_fused.hpp: handover_list_kernel)
+static int read_list_classes(pcl_solver *s, int c[2]) {
+    HIP_TRY(hipSetDevice(s->cfg.device));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    HIP_TRY(hipMemcpy(c, &s->qt.ran_over()->na, 2 * sizeof(int), hipMemcpyDeviceToHost));
     return PCL_OK;
 }
 
 // tiles the last one-kernel launch computed / skipped: a skipping launch ran over the list built behind the launch
-// before it (classic_fused.hpp: handover_list_kernel), counted in tq_next[tq_stat_nx] (the hand-overs behind it leave
-// that block alone until the next launch); a launch without skipping computed all.  Nothing counted: both 0.
+// before it; a launch without skipping computed all.  Nothing counted: both 0.
 int pcl_tile_skip_stats(pcl_solver *s, long *computed, long *skipped) {
     if (!s || !computed || !skipped) return fail(PCL_EINVAL, "null argument");
     *computed = *skipped = 0;
-    if (!s->tq_stats) return PCL_OK;
-    const long nt = (long)s->tq_ntx * s->tq_nty;
+    if (s->qt.last_launch() == pcl::QuietTiles::NONE) return PCL_OK;
+    const long nt = (long)s->qt.ntx * s->qt.nty;
     long n = nt;
-    if (s->tq_stats == 2) {
-        HIP_TRY(hipSetDevice(s->cfg.device));
+    if (s->qt.last_launch() == pcl::QuietTiles::LIST) {
         int c[2] = {0, 0};
-        HIP_TRY(hipStreamSynchronize(s->stream));
-        HIP_TRY(hipMemcpy(c, &s->tq_next[s->tq_stat_nx].na, 2 * sizeof(int), hipMemcpyDeviceToHost));
+        if (int rc = read_list_classes(s, c)) return rc;
         n = (long)c[0] + c[1];
     }
     *computed = n;
@@ -1893,33 +1795,30 @@ int pcl_tile_skip_stats(pcl_solver *s, long *computed, long *skipped) {
     return PCL_OK;
 }
 
-// the two classes of the list the last one-kernel launch ran over (classic_fused.hpp: handover_list_kernel): class A
-// computed something in the launch before, class Q was quiet there; both 0 when that launch did not run over a list
+// the two classes of that list: class A computed something in the launch before, class Q was quiet there; both 0 when
+// the last launch did not run over a list
 int pcl_tile_list_classes(pcl_solver *s, long *na, long *nq) {
-    if (s) s->tq_drop();                  // quiet tiles: not a read-only call (pcl_solver::tq_valid)
+    if (s) s->qt.invalidate();            // quiet tiles: not a read-only call (quiet_tiles.hpp)
     if (!s || !na || !nq) return fail(PCL_EINVAL, "null argument");
     *na = *nq = 0;
-    if (s->tq_stats != 2) return PCL_OK;
-    HIP_TRY(hipSetDevice(s->cfg.device));
+    if (s->qt.last_launch() != pcl::QuietTiles::LIST) return PCL_OK;
     int c[2] = {0, 0};
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    HIP_TRY(hipMemcpy(c, &s->tq_next[s->tq_stat_nx].na, 2 * sizeof(int), hipMemcpyDeviceToHost));
+    if (int rc = read_list_classes(s, c)) return rc;
     *na = c[0];
     *nq = c[1];
     return PCL_OK;
 }
 
 int pcl_tile_words(pcl_solver *s, unsigned *host, int *ntx, int *nty) {
-    if (s) s->tq_drop();                  // quiet tiles: not a read-only call (pcl_solver::tq_valid)
+    if (s) s->qt.invalidate();            // quiet tiles: not a read-only call (quiet_tiles.hpp)
     if (!s || !ntx || !nty) return fail(PCL_EINVAL, "null argument");
-    *ntx = s->tq_ntx;
-    *nty = s->tq_nty;
+    *ntx = s->qt.ntx;
+    *nty = s->qt.nty;
     if (!host) return PCL_OK;
-    if (s->tq_stats != 2) return fail(PCL_ESTATE, "pcl_tile_words: the last one-kernel step did not skip");
+    if (s->qt.last_launch() != pcl::QuietTiles::LIST) return fail(PCL_ESTATE, "pcl_tile_words: the last one-kernel step did not skip");
     HIP_TRY(hipSetDevice(s->cfg.device));
     HIP_TRY(hipStreamSynchronize(s->stream));
-    // the words the last launch read (the list built behind it writes the third array)
-    HIP_TRY(hipMemcpy(host, s->tq[(s->tq_cur + 2) % 3], (size_t)s->tq_ntx * s->tq_nty * sizeof(unsigned), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(host, s->qt.words_read(), (size_t)s->qt.ntx * s->qt.nty * sizeof(unsigned), hipMemcpyDeviceToHost));
     return PCL_OK;
 }
 
@@ -2210,7 +2109,7 @@ int pcl_comm_check(int nranks, int rank, const int neighbors[8]) {
 }
 
 int pcl_comm_init(pcl_solver *s, int nranks, int rank, const char uid[128], const int neighbors[8]) {
-    if (s) s->tq_drop();                  // quiet tiles: not a read-only call (pcl_solver::tq_valid)
+    if (s) s->qt.invalidate();            // quiet tiles: not a read-only call (quiet_tiles.hpp)
     if (!s || !uid || !neighbors) return fail(PCL_EINVAL, "null argument");
     // argument validation BEFORE anything reaches RCCL (whose own diagnostics for these mistakes is a bare
     // "invalid usage" from ncclCommInitRank)
@@ -2241,7 +2140,7 @@ int pcl_comm_init(pcl_solver *s, int nranks, int rank, const char uid[128], cons
 
 int pcl_comm_init_host(pcl_solver *s, int nranks, int rank, const int neighbors[8], pcl_host_exchange_fn xfn,
                        pcl_host_reduce_fn rfn, void *user) {
-    if (s) s->tq_drop();                  // quiet tiles: not a read-only call (pcl_solver::tq_valid)
+    if (s) s->qt.invalidate();            // quiet tiles: not a read-only call (quiet_tiles.hpp)
     if (!s || !neighbors || !xfn || !rfn) return fail(PCL_EINVAL, "null argument");
     if (int rc = pcl_comm_check(nranks, rank, neighbors)) return rc;
     HIP_TRY(hipSetDevice(s->cfg.device));
@@ -2265,7 +2164,7 @@ int pcl_comm_init_host(pcl_solver *s, int nranks, int rank, const int neighbors[
 }
 
 int pcl_halo_can_overlap(pcl_solver *s, int *yes) {
-    if (s) s->tq_drop();                  // quiet tiles: not a read-only call (pcl_solver::tq_valid)
+    if (s) s->qt.invalidate();            // quiet tiles: not a read-only call (quiet_tiles.hpp)
     if (!s || !yes) return fail(PCL_EINVAL, "null argument");
     int box[4], ntiles[2];
     const bool base = s->halo.active && s->cfg.kind == PCL_KIND_CLASSIC && s->cfg.ndim == 2 && s->cfg.method[2] < 0 &&
@@ -2278,7 +2177,7 @@ int pcl_halo_can_overlap(pcl_solver *s, int *yes) {
 }
 
 int pcl_halo_exchange_ahead(pcl_solver *s, int on) {
-    if (s) s->tq_drop();                  // quiet tiles: not a read-only call (pcl_solver::tq_valid)
+    if (s) s->qt.invalidate();            // quiet tiles: not a read-only call (quiet_tiles.hpp)
     if (!s) return fail(PCL_EINVAL, "null argument");
     if (on) {
         int yes = 0;
@@ -2297,7 +2196,7 @@ int pcl_halo_exchange_ahead(pcl_solver *s, int on) {
 }
 
 int pcl_halo_exchange(pcl_solver *s) {
-    if (s) s->tq_drop();                  // quiet tiles: not a read-only call (pcl_solver::tq_valid)
+    if (s) s->qt.invalidate();            // quiet tiles: not a read-only call (quiet_tiles.hpp)
     if (s) s->ghosts_drop_all();          // exchange-ahead: whatever filled the ghost frames no longer holds
     if (!s) return fail(PCL_EINVAL, "null argument");
     HIP_TRY(hipSetDevice(s->cfg.device));
@@ -2307,7 +2206,7 @@ int pcl_halo_exchange(pcl_solver *s) {
 }
 
 int pcl_halo_exchange_aux(pcl_solver *s) {
-    if (s) s->tq_drop();                  // quiet tiles: not a read-only call (pcl_solver::tq_valid)
+    if (s) s->qt.invalidate();            // quiet tiles: not a read-only call (quiet_tiles.hpp)
     if (!s) return fail(PCL_EINVAL, "null argument");
     if (s->cfg.maux <= 0) return PCL_OK;
     HIP_TRY(hipSetDevice(s->cfg.device));
@@ -2324,7 +2223,7 @@ int pcl_halo_region(int dir, int send, int I, int J, int mbc, int out[4]) {
 }
 
 int pcl_allreduce_max(pcl_solver *s, double *value) {
-    if (s) s->tq_drop();                  // quiet tiles: not a read-only call (pcl_solver::tq_valid)
+    if (s) s->qt.invalidate();            // quiet tiles: not a read-only call (quiet_tiles.hpp)
     if (!s || !value) return fail(PCL_EINVAL, "null argument");
     HIP_TRY(hipSetDevice(s->cfg.device));
     std::string err;

@@ -1,0 +1,175 @@
+// quiet_tiles.hpp -- host state of the quiet tiles of the one-kernel dim-split step (host only, included by pclaw.hip;
+// the kernels: classic_fused.hpp, the proofs: DESIGN.md 4.1a).
+//
+// Device memory: three word arrays W[0..2] (one 32-bit word per tile), the per-wavefront Courant maxima C, the tile
+// list L and three TileNext blocks N[0..2].  Two counters rotate them: c (words) advances with every booked launch, x
+// (blocks) with every hand-over that built a list.  With c and x taken in front of launch n (indices modulo 3):
+//
+//                                  reads                       writes                            then
+//   launch n        plan()         L, N[x+2] if it skips       W[c+1], C (computed tiles)        c += 1
+//   hand-over n     handover()     W[c+1], C                   W[c+2] (tiles n + 1 skips), L,    x += 1
+//                                                              N[x] filled, N[x+1] zeroed
+//   launch n + 1    plan()         L, N[x] if it skips         W[c+2], C (computed tiles)
+//   a hook between                 W[c]   (words_read)         nothing
+//                                  N[x+2] (ran_over)
+//
+// N[x] is filled with atomics, so it must be zero: the hand-over before zeroed it.  A launch with skipping switched off,
+// or one whose step fails before its hand-over, advances c and not x; one counter for both would then have the next
+// hand-over fill a block that nobody zeroed, so there are two.  A hand-over launch that fails zeroes all three blocks
+// and restarts x at 0.
+//
+// Flags, and the only events that change them:
+//   valid    the last launch was a booked one, last_in -> last_out with last_key, and since then only the buffer swap of
+//            the step and read-only calls have happened.  Set by launched(); cleared by invalidate() (the first statement
+//            of every C entry point that is neither a step nor read-only: tests/test_quiet_tiles_cpu.py), by take_valid()
+//            (the step entry points; the value travels down to plan() as `carry`) and by plan().
+//   hand     a hand-over with a list is due behind the last launch.  Set by launched() while skipping is enabled;
+//            cleared by handover() and plan().
+//   listed   L and N[x-1] hold the list of the next launch.  Set by handed_over(true); cleared by handover() (every
+//            Courant read-back: a later step of another form drops the list) and plan().
+//   last     what the last launch was (NONE / ALL / LIST), for the hooks.  Set by launched(); cleared by plan().
+#pragma once
+#include <cmath>
+#include <cstring>
+#include <hip/hip_runtime.h>
+
+#include "sweep_args.hpp"
+
+namespace pcl {
+
+class QuietTiles {
+public:
+    // the settings two launches must share for the words of one to decide the other (compared bytewise)
+    struct Key {
+        int rp, fwave, math, src;
+        double src_p[2];
+        RpParams par;
+        Key(int rp_, int fwave_, int math_, const SweepArgs &a) {
+            memset(this, 0, sizeof(Key));
+            rp = rp_; fwave = fwave_; math = math_; src = a.src_id;
+            src_p[0] = a.src_p[0]; src_p[1] = a.src_p[1];
+            par = a.par;
+        }
+        Key() { memset(this, 0, sizeof(Key)); }
+        bool operator==(const Key &o) const { return memcmp(this, &o, sizeof(Key)) == 0; }
+    };
+    enum Last { NONE = 0, ALL = 1, LIST = 2 };   // no booked launch / it computed every tile / it ran over the list
+
+    int ntx = 0, nty = 0;
+
+    // mx x my interior cells; the blocks are zeroed on `stream`
+    hipError_t create(int mx, int my, hipStream_t stream) {
+        ntx = (mx + TILE_OWN_C - 1) / TILE_OWN_C;
+        nty = (my + TILE_OWN_R - 1) / TILE_OWN_R;
+        const size_t nt = (size_t)ntx * nty;
+        hipError_t e = hipSuccess;
+        for (auto &w : words)
+            if (e == hipSuccess) e = hipMalloc((void **)&w, nt * sizeof(unsigned));
+        if (e == hipSuccess) e = hipMalloc((void **)&cfl, nt * 4 * sizeof(double2));
+        if (e == hipSuccess) e = hipMalloc((void **)&list, nt * sizeof(int));
+        if (e == hipSuccess) e = hipMalloc((void **)&next, 3 * sizeof(TileNext));
+        if (e == hipSuccess) e = hipMemsetAsync(next, 0, 3 * sizeof(TileNext), stream);
+        return e;
+    }
+    void destroy() {
+        for (unsigned *w : words)
+            if (w) hipFree(w);
+        if (cfl) hipFree(cfl);
+        if (list) hipFree(list);
+        if (next) hipFree(next);
+    }
+
+    void invalidate() { valid = false; }
+    bool take_valid() { const bool v = valid; valid = false; return v; }
+    void set_enabled(bool on) { enabled = on; }
+
+    // In front of a one-kernel launch qin -> qout: fills l.tq_* and returns true if the launch is booked (`whole`: the
+    // whole undecomposed block).  Every flag is cleared; launched() sets them again.
+    bool plan(SweepLaunch &l, const double *qin, const double *qout, const Key &key, double dt, bool whole, bool carry) {
+        const bool book = whole && words[0];
+        if (book) {
+            l.tq_out = written_next();
+            l.tq_cfl = cfl;
+            if (may_skip(qin, qout, key, dt, carry)) {
+                l.tq_list = list;
+                l.tq_next = block(2);
+            }
+        }
+        valid = hand = listed = false;
+        last = NONE;
+        return book;
+    }
+    // the booked launch was enqueued
+    void launched(const SweepLaunch &l, const double *qin, const double *qout, const Key &key) {
+        c = (c + 1) % 3;
+        valid = true;
+        last_in = qin;
+        last_out = qout;
+        last_key = key;
+        last = l.tq_list ? LIST : ALL;
+        stat = block(2);
+        hand = enabled;
+    }
+
+    // In front of the Courant hand-over: true if it takes the next launch's list with it, h's tile fields filled.
+    bool handover(TileHandover &h) {
+        const bool due = hand;
+        hand = listed = false;
+        if (due) {
+            h.ntx = ntx;
+            h.nty = nty;
+            h.tq_in = written();
+            h.tq_out = written_next();
+            h.tq_cfl = cfl;
+            h.tq_list = list;
+            h.next = block(0);
+            h.other = block(1);
+        }
+        return due;
+    }
+    // ok: that hand-over was enqueued; not ok: nothing ran, the list state back to its start (every block zero)
+    void handed_over(bool ok, hipStream_t stream) {
+        if (ok) {
+            listed = true;
+            x = (x + 1) % 3;
+        } else {
+            (void)hipMemsetAsync(next, 0, 3 * sizeof(TileNext), stream);
+            x = 0;
+        }
+    }
+
+    // for the hooks, behind the last launch
+    Last last_launch() const { return last; }
+    const unsigned *words_read() const { return words[(c + 2) % 3]; }   // the words its list was built from
+    const TileNext *ran_over() const { return stat; }                   // the block of that list (last_launch() == LIST)
+
+private:
+    unsigned *words[3] = {nullptr, nullptr, nullptr};
+    double2 *cfl = nullptr;
+    int *list = nullptr;
+    TileNext *next = nullptr;
+    int c = 0, x = 0;
+    const TileNext *stat = nullptr;
+    bool enabled = true;                // pcl_tile_skip
+    bool valid = false, hand = false, listed = false;
+    Last last = NONE;
+    const double *last_in = nullptr, *last_out = nullptr;
+    Key last_key;
+
+    unsigned *written() const { return words[c]; }                  // by the last launch
+    unsigned *written_next() const { return words[(c + 1) % 3]; }   // by the next launch and, for the tiles it skips, the list kernel
+    TileNext *block(int k) const { return next + (x + k) % 3; }     // 0: the next hand-over fills it, 1: zeroes it, 2: the last one filled it
+
+    // The next launch may run over the list: skipping is on, the previous launch ran on the swapped pair with the same
+    // settings, the list behind it was built and nothing has happened since (carry); under the fused source its
+    // fixed-point test (euler_radial_source_fixed) holds for these dt, gamma1 and ndim - 1; dt is positive and finite
+    // (the skipped tiles' Courant number: DESIGN.md 4.1a).
+    bool may_skip(const double *qin, const double *qout, const Key &key, double dt, bool carry) const {
+        const bool src_ok = key.src == 0 || (dt <= SRC_FIXED_BOUND && fabs(key.src_p[0]) <= SRC_FIXED_BOUND &&
+                                             fabs(key.src_p[1]) <= SRC_FIXED_BOUND);
+        return enabled && carry && listed && last_in == qout && last_out == qin && last_key == key && src_ok && dt > 0.0 &&
+               dt < HUGE_VAL;
+    }
+};
+
+}  // namespace pcl

@@ -146,6 +146,8 @@ struct TileNext {
     int na, nq;
     unsigned long long cx, cy;
 };
+// cells a tile of the one-kernel step owns, for the host's tile counts (kernels.hip ties them to F_OWN_C, F_OWN_R)
+constexpr int TILE_OWN_C = 60, TILE_OWN_R = 12;
 
 struct SweepLaunch {
     SweepArgs a;
