@@ -326,13 +326,17 @@ int pcl_timer_stop(pcl_solver *s, float *ms);
 int pcl_kernel_timing(pcl_solver *s, int enable);
 int pcl_kernel_timing_read(pcl_solver *s, double *ms_total, long *launches);
 /* The dimension-split 2-D step has two forms with identical results (step2ds.f:83-159 as x pass + y pass, or both sweeps
- * in one kernel, q through HBM once per step); one block of an aux-free solver runs the faster one, re-measured every 256
- * steps (PCL_TUNE_FUSED_STEP = 0 / 1 pins a form).  Since the last pcl_kernel_timing reset: cumulative device time (ms)
+ * in one kernel, q through HBM once per step); under pcl_step_hyperbolic / pcl_bc_step one block runs the faster one,
+ * re-measured every 256 steps (PCL_TUNE_FUSED_STEP = 0 / 1 pins a form).  The one-kernel form exists for mbc = 2 and
+ * euler_5wave_2d, acoustics_2d, advection_2d, shallow_2d, vc_acoustics_2d, vc_advection_2d and psystem_fwave_2d, with or
+ * without a capacity function (aux planes and aux(mcapa) are staged in the kernel's tile next to q); decomposed blocks of
+ * the last three, and of any solver with a capacity function, keep the two passes, as does mbc > 2.  Since the last pcl_kernel_timing reset: cumulative device time (ms)
  * and sampled launch count of the one-kernel step (pcl_kernel_timing_read holds the two passes), and the steps each
  * form has run. */
 int pcl_step_form_stats(pcl_solver *s, double *ms_total, long *launches, long *steps_one_kernel, long *steps_two_pass);
 /* Quiet tiles of the one-kernel step (on by default): a tile whose update was the identity in the previous step, with
- * its 8 neighbours, is not computed again -- same bits, same Courant number.  enable = 0 computes every tile.  Any call
+ * its 8 neighbours, is not computed again -- same bits, same Courant number.  enable = 0 computes every tile.  Solvers
+ * that read aux arrays and states with a capacity function compute every tile of every step.  Any call
  * other than the step itself and read-only calls makes the next step compute every tile. */
 int pcl_tile_skip(pcl_solver *s, int enable);
 /* tiles the last one-kernel step computed and skipped (both 0 when no one-kernel step of the whole block has run); a

@@ -4,8 +4,8 @@
 // Reference path: src/fortran/2d/classic/step2ds.f:83-159 (both loops), flux2.f, limiter.f; boundary conditions as
 // the x pass of sweep_kernel evaluates them while loading (solver.py:354-452), the app's radial source applied to the
 // finished cell while storing (clawpack.py:156-159) -- the same lane_core, the same order of operations, the same bits
-// as the two-pass form (classic.hpp), which stays the path for decomposed blocks, capacity functions, aux-carrying
-// Riemann solvers and mbc != 2.
+// as the two-pass form (classic.hpp), which stays the path for mbc != 2, for decomposed blocks of solvers with aux arrays
+// or a capacity function, and for solvers the launcher (kernels.hip: launch_step2ds) has no instantiation of.
 //
 // Tile: 16 rows x 64 columns of q with a 2-cell halo on every side, all MEQN planes in LDS (Euler: 40 KB, four
 // workgroups of 256 threads per CU; the round's first form was 32 x 64 with 512 threads, two per CU -- measured
@@ -175,16 +175,40 @@ __global__ __launch_bounds__(TL_THREADS) void handover_list_kernel(unsigned long
 // from the front of the list, then the nq of class Q from its back -- and the workgroups past the list's end return at
 // once.  Dispatch order puts the listed tiles first and, among them, the tiles that compute (those
 // set the kernel's end when they wait for a slot behind the quiet ones).
-template <class RP, bool FWAVE, bool SRC>
-__global__ __launch_bounds__(F_THREADS, 1024 / F_THREADS) void step2ds_kernel(SweepArgs a, int ntx, int nty,
+//
+// Solvers with cell-wise coefficients (RP::NAUX > 0) and capacity functions (CAPA): the tile holds more planes, laid out
+// as sweep_kernel's (classic.hpp) -- q (0 .. MEQN-1), the capacity function aux(mcapa) (CAPA), then the RP::NAUX aux
+// components the normal solver reads -- with the same halo and the same swizzle.  aux is the same for both sweeps, is
+// loaded once per tile and never written; its ghost cells are real memory (auxbc is filled at setup), so the boundary
+// remap of the load applies to the q planes alone.  Each sweep hands lane_core the cell's dt/d divided by its capa and
+// the staged aux values exactly as the pass of sweep_kernel does: the same bits.  A tile plane is 8 KB and a CU has
+// 160 KB of LDS: up to 5 planes run four workgroups per CU, 6 three, 7 to 10 two (fused_wgs: also the register budget).
+// The quiet-tile bookkeeping (tq_*) is for the aux-free instantiations without capa only: the launcher refuses it here.
+template <class RP, bool CAPA> constexpr int fused_planes() { return RP::MEQN + (CAPA ? 1 : 0) + RP::NAUX; }
+template <class RP> constexpr bool fused_aux_same() {
+    bool ok = true;
+    if constexpr (RP::NAUX > 0)
+        for (int k = 0; k < RP::NAUX; k++) ok = ok && aux_idx<RP, 1>(k) == aux_idx<RP, 2>(k);
+    return ok;
+}
+constexpr int fused_wgs(int planes) { return planes <= 5 ? 1024 / F_THREADS : (20 / planes >= 1 ? 20 / planes : 1); }
+template <class RP, bool FWAVE, bool SRC, bool CAPA = false>
+__global__ __launch_bounds__(F_THREADS, fused_wgs(fused_planes<RP, CAPA>())) void step2ds_kernel(SweepArgs a, int ntx, int nty,
                                                                               unsigned *__restrict__ tq_out,
                                                                               double2 *__restrict__ tq_cfl,
                                                                               const int *__restrict__ tq_list,
                                                                               const TileNext *tq_next) {
     constexpr int MEQN = RP::MEQN;
-    static_assert(RP::NAUX == 0, "solvers without aux arrays");
-    static_assert(!SRC || MEQN == 5, "fused source: the Euler solver");
-    __shared__ __attribute__((aligned(16))) double tile[MEQN * F_ROWS * F_COLS];
+    constexpr int NAUX = RP::NAUX, PAUX = MEQN + (CAPA ? 1 : 0), NP = PAUX + NAUX, NX = NP - MEQN;
+    static_assert(!SRC || (MEQN == 5 && NX == 0), "fused source: the Euler solver, no capacity function");
+    static_assert(NP * F_ROWS * F_COLS * sizeof(double) <= 80 * 1024, "two workgroups per CU at least");
+    __shared__ __attribute__((aligned(16))) double tile[NP * F_ROWS * F_COLS];
+    // where tile plane MEQN + e comes from in a.aux (one set for both sweeps: checked against aux_idx<RP, 2> below)
+    auto xplane = [&](int e) -> long {
+        if (CAPA && e == 0) return (long)(a.mcapa - 1) * a.plane;
+        return (long)aux_idx<RP, 1>(e - (CAPA ? 1 : 0)) * a.plane;
+    };
+    static_assert(fused_aux_same<RP>(), "one staging serves both sweeps: the normal solver reads the same aux planes in x and y");
 
     // Chunked order: the hardware deals consecutive workgroups to the 8 XCDs in turn; in every window of 64 tiles each
     // XCD takes 8 CONSECUTIVE tiles of a tile row (they share partial lines and halo columns in that XCD's L2) while the
@@ -256,6 +280,14 @@ __global__ __launch_bounds__(F_THREADS, 1024 / F_THREADS) void step2ds_kernel(Sw
                 if (fswz(r) & 1) { const double t = v.x; v.x = v.y; v.y = t; }       // the swizzle swaps the pair in odd rows
                 *reinterpret_cast<double2 *>(&tile[(m * F_ROWS + r) * F_COLS + ((c ^ fswz(r)) & ~1)]) = v;
             }
+            if constexpr (NX > 0) {
+#pragma unroll
+                for (int e = 0; e < NX; e++) {
+                    double2 v = *reinterpret_cast<const double2 *>(&a.aux[xplane(e) + g]);
+                    if (fswz(r) & 1) { const double t = v.x; v.x = v.y; v.y = t; }
+                    *reinterpret_cast<double2 *>(&tile[((MEQN + e) * F_ROWS + r) * F_COLS + ((c ^ fswz(r)) & ~1)]) = v;
+                }
+            }
         }
     } else {
 #pragma unroll
@@ -286,6 +318,11 @@ __global__ __launch_bounds__(F_THREADS, 1024 / F_THREADS) void step2ds_kernel(Sw
 #pragma unroll
                 for (int m = 0; m < MEQN; m++) tile[ftile_at(m, r, c)] = a.qin[m * a.plane + g];
             }
+            if constexpr (NX > 0) {          // the cell's own aux, on the frame too (ghost cells of aux are real memory)
+                const long ga = (long)gy * a.pitch + gx;
+#pragma unroll
+                for (int e = 0; e < NX; e++) tile[ftile_at(MEQN + e, r, c)] = a.aux[xplane(e) + ga];
+            }
         }
     }
     // no workgroup barrier here: a wavefront sweeps exactly the four rows it loaded (the LDS operations of one
@@ -312,9 +349,22 @@ __global__ __launch_bounds__(F_THREADS, 1024 / F_THREADS) void step2ds_kernel(Sw
 #pragma unroll
             for (int m = 0; m < MEQN; m++) q[m] = tile[ftile_at(m, r, cl)];
             // nojump (wave-uniform): the cells go back as they came, nothing to put back
-            const bool nojump = lane_core<RP, 1, false, FWAVE, false>(q, a.dtd, 1.0, cfl_ok && (F_RX == 1 || y0 + r < a.J), a, qn,
-                                                                      cflx, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                                                                      nullptr, &memo);
+            bool nojump;
+            if constexpr (NX > 0) {
+                // dtdx1d(i) = dtdx / aux(mcapa,i,j) (step2ds.f:95-99) and the solver's aux values, as sweep_kernel's x pass
+                double capa = 1.0, dtdx_c = a.dtd, auxv[NAUX > 0 ? NAUX : 1];
+                if constexpr (CAPA) {
+                    capa = tile[ftile_at(MEQN, r, cl)];
+                    dtdx_c = a.dtd / capa;
+                }
+#pragma unroll
+                for (int m = 0; m < NAUX; m++) auxv[m] = tile[ftile_at(PAUX + m, r, cl)];
+                nojump = lane_core<RP, 1, CAPA, FWAVE, false>(q, dtdx_c, capa, cfl_ok && (F_RX == 1 || y0 + r < a.J), a, qn, cflx,
+                                                              nullptr, nullptr, nullptr, NAUX > 0 ? auxv : nullptr);
+            } else
+                nojump = lane_core<RP, 1, false, FWAVE, false>(q, a.dtd, 1.0, cfl_ok && (F_RX == 1 || y0 + r < a.J), a, qn,
+                                                               cflx, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                                               nullptr, &memo);
             quiet = quiet && nojump;
             if (owned && !nojump) {
 #pragma unroll
@@ -351,9 +401,22 @@ __global__ __launch_bounds__(F_THREADS, 1024 / F_THREADS) void step2ds_kernel(Sw
             double q[MEQN], qn[MEQN];
 #pragma unroll
             for (int m = 0; m < MEQN; m++) q[m] = tile[ftile_at(m, rl, c)];
-            const bool nojump = lane_core<RP, 2, false, FWAVE, false>(q, ay.dtd, 1.0, row_cfl && col_ok, ay, qn, cfly,
-                                                                      nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                                                                      nullptr, &memo);
+            bool nojump;
+            if constexpr (NX > 0) {
+                // dtdy1d(j) = dtdy / aux(mcapa,i,j) (step2ds.f:179-183), as sweep_kernel's y pass
+                double capa = 1.0, dtdy_c = ay.dtd, auxv[NAUX > 0 ? NAUX : 1];
+                if constexpr (CAPA) {
+                    capa = tile[ftile_at(MEQN, rl, c)];
+                    dtdy_c = ay.dtd / capa;
+                }
+#pragma unroll
+                for (int m = 0; m < NAUX; m++) auxv[m] = tile[ftile_at(PAUX + m, rl, c)];
+                nojump = lane_core<RP, 2, CAPA, FWAVE, false>(q, dtdy_c, capa, row_cfl && col_ok, ay, qn, cfly, nullptr, nullptr,
+                                                              nullptr, NAUX > 0 ? auxv : nullptr);
+            } else
+                nojump = lane_core<RP, 2, false, FWAVE, false>(q, ay.dtd, 1.0, row_cfl && col_ok, ay, qn, cfly,
+                                                               nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                                               nullptr, &memo);
             quiet = quiet && nojump;
             if (row_owned && col_int && !nojump) {
 #pragma unroll
@@ -443,7 +506,7 @@ __global__ __launch_bounds__(F_THREADS, 1024 / F_THREADS) void step2ds_kernel(Sw
         if (lane == 0) reinterpret_cast<unsigned char *>(tq_out + tile_id)[wv] = quiet ? TQ_QUIET : 0u;
     }
     // the two passes have their own dt/d: the larger Courant number of the two is the step's (step2ds.f:136,181)
-    cfl_publish(a.cfl, dmax(cfl_value<false>(cflx, a.dtd), cfl_value<false>(cfly, a.dtd_t)));
+    cfl_publish(a.cfl, dmax(cfl_value<CAPA>(cflx, a.dtd), cfl_value<CAPA>(cfly, a.dtd_t)));
 }
 
 }  // namespace PCL_NS

@@ -119,7 +119,11 @@ template <class RP> int launch_step2ds_t(const SweepLaunch &l, std::string &err)
     const SweepArgs &a = l.a;
     constexpr bool FW = IsFwave<RP>::value;
     if ((l.fwave != 0) != FW) { err = "solver.fwave does not match the Riemann solver"; return PCL_EINVAL; }
-    if (a.mbc != HALO || a.mcapa > 0) { err = "step2ds kernel: mbc = 2, no capacity function"; return PCL_EINVAL; }
+    if (a.mbc != HALO) { err = "step2ds kernel: mbc = 2"; return PCL_EINVAL; }
+    const bool capa = a.mcapa > 0;
+    if ((capa || RP::NAUX > 0) && !a.aux) { err = "step2ds kernel: this solver reads aux arrays and there are none"; return PCL_EINVAL; }
+    // quiet tiles: the bookkeeping of the aux-free instantiations without a capacity function only (classic_fused.hpp)
+    if ((capa || RP::NAUX > 0) && (l.tq_out || l.tq_list)) { err = "step2ds kernel: no quiet-tile bookkeeping with aux arrays"; return PCL_EINVAL; }
     const int ntx = (a.mx + F_OWN_C - 1) / F_OWN_C, nty = (a.my + F_OWN_R - 1) / F_OWN_R;
     unsigned nblocks = (unsigned)ntx * (unsigned)nty;
     if (a.sub != 0) {
@@ -131,8 +135,8 @@ template <class RP> int launch_step2ds_t(const SweepLaunch &l, std::string &err)
         nblocks = a.sub == 1 ? inside : nblocks - inside;
         if (nblocks == 0) return PCL_OK;
     }
-    if (a.src_id != 0 && !(std::is_same<RP, Euler5>::value && a.src_id == 1)) {
-        err = "fused source: only the Euler solver's radial source";
+    if (a.src_id != 0 && !(std::is_same<RP, Euler5>::value && a.src_id == 1 && !capa)) {
+        err = "fused source: only the Euler solver's radial source, no capacity function";
         return PCL_EINVAL;
     }
     // a list launch: the tiles the hand-over+list kernel behind the previous launch listed (classic_fused.hpp); one
@@ -147,7 +151,10 @@ template <class RP> int launch_step2ds_t(const SweepLaunch &l, std::string &err)
         if constexpr (std::is_same<RP, Euler5>::value)
             hipLaunchKernelGGL((step2ds_kernel<RP, FW, true>), grid, dim3(F_THREADS), 0, l.stream, a, ntx, nty, l.tq_out,
                                l.tq_cfl, l.tq_list, l.tq_next);
-    } else
+    } else if (capa)
+        hipLaunchKernelGGL((step2ds_kernel<RP, FW, false, true>), grid, dim3(F_THREADS), 0, l.stream, a, ntx, nty, l.tq_out,
+                           l.tq_cfl, l.tq_list, l.tq_next);
+    else
         hipLaunchKernelGGL((step2ds_kernel<RP, FW, false>), grid, dim3(F_THREADS), 0, l.stream, a, ntx, nty, l.tq_out,
                            l.tq_cfl, l.tq_list, l.tq_next);
     hipError_t e = hipGetLastError();
@@ -159,7 +166,10 @@ int launch_step2ds(const SweepLaunch &l, std::string &err) {
     if (l.rp == PCL_RP_ACOUSTICS_2D) return launch_step2ds_t<Acoustics2D>(l, err);
     if (l.rp == PCL_RP_ADVECTION_2D) return launch_step2ds_t<Advection2D>(l, err);
     if (l.rp == PCL_RP_SHALLOW_2D) return launch_step2ds_t<Shallow2D>(l, err);
-    err = "step2ds kernel: Riemann solvers without aux arrays only";
+    if (l.rp == PCL_RP_VC_ACOUSTICS_2D) return launch_step2ds_t<VcAcoustics2D>(l, err);
+    if (l.rp == PCL_RP_VC_ADVECTION_2D) return launch_step2ds_t<VcAdvection2D>(l, err);
+    if (l.rp == PCL_RP_PSYSTEM_FWAVE_2D) return launch_step2ds_t<PSystem2D>(l, err);
+    err = "step2ds kernel: no instantiation for this Riemann solver";
     return PCL_EINVAL;
 }
 

@@ -452,25 +452,36 @@ int do_sweep(pcl_solver *s, const double *qin, double *qout, int ids, double dt,
     return rc;
 }
 
-// The dimension-split 2-D step as ONE kernel (classic_fused.hpp): two ghost layers, Riemann solvers without aux
-// arrays, no capacity function.  PCL_TUNE_FUSED_STEP=0 keeps the two passes.
+// The dimension-split 2-D step as ONE kernel (classic_fused.hpp): two ghost layers, up to 5 equations, the Riemann
+// solvers launch_step2ds has an instantiation of -- with or without a capacity function.  The solvers with aux arrays
+// (fused_aux_family) and every solver with a capacity function take it as a whole block only: their decomposed blocks
+// keep the two passes with the overlap.  PCL_TUNE_FUSED_STEP=0 keeps the two passes.
 // sub/box: tile subset (interior / rim of a decomposed block), `on`: the halo stream for the rim launch.
 int fused_step_mode() {
     static const int on = [] { const char *e = getenv("PCL_TUNE_FUSED_STEP"); return e ? atoi(e) : 2; }();
     return on;
 }
+// the one-kernel step stages aux planes next to q: a solver with cell-wise coefficients, or any solver with a capacity function
+bool fused_aux_family(const pcl_solver *s) {
+    const int rp = s->cfg.rp;
+    return s->cfg.method[5] > 0 || rp == PCL_RP_VC_ACOUSTICS_2D || rp == PCL_RP_VC_ADVECTION_2D || rp == PCL_RP_PSYSTEM_FWAVE_2D;
+}
 bool fused_step_ok(const pcl_solver *s) {
     const int on = fused_step_mode();
     const int rp = s->cfg.rp;
-    return on && s->cfg.ndim == 2 && s->cfg.method[2] < 0 && s->cfg.mbc == 2 && s->cfg.method[5] <= 0 && s->cfg.meqn <= 5 &&
-           (rp == PCL_RP_EULER5_2D || rp == PCL_RP_ACOUSTICS_2D || rp == PCL_RP_ADVECTION_2D || rp == PCL_RP_SHALLOW_2D);
+    const bool plain = rp == PCL_RP_EULER5_2D || rp == PCL_RP_ACOUSTICS_2D || rp == PCL_RP_ADVECTION_2D || rp == PCL_RP_SHALLOW_2D;
+    const bool vc = rp == PCL_RP_VC_ACOUSTICS_2D || rp == PCL_RP_VC_ADVECTION_2D || rp == PCL_RP_PSYSTEM_FWAVE_2D;
+    if (!(on && s->cfg.ndim == 2 && s->cfg.method[2] < 0 && s->cfg.mbc == 2 && s->cfg.meqn <= 5 && (plain || vc))) return false;
+    // whole blocks only, and not under the fused source (Euler without a capacity function: pcl_fuse_source)
+    return !fused_aux_family(s) || (!s->halo.active && s->aux && s->fused_src == 0);
 }
 // The two-pass dim-split step of a decomposed block with its interior x tiles BESIDE the exchange.  For the solver
 // family of the one-kernel step (aux-free, no capacity function: an x pass register-allocated for four workgroups per
 // CU) the interior launch starves the halo stream's pack / Send-Recv kernels (44 / 77 us instead of 6 / 34) and the step
 // is slower than with the exchange in front (4096 x 2048 Euler block: 0.489 against 0.320 ms), so those blocks -- too
 // thin for one-kernel tiles, mbc > 2, PCL_TUNE_FUSED_STEP=0 -- take the exchange in front unless PCL_HALO_OVERLAP=1 is
-// set explicitly (tests, A/B).  Solvers with aux arrays or a capacity function keep the overlap.
+// set explicitly (tests, A/B).  Solvers with aux arrays or a capacity function keep the overlap (their decomposed blocks
+// never take the one-kernel step: fused_step_ok).
 bool twopass_overlap_ok(const pcl_solver *s) {
     const int rp = s->cfg.rp;
     const bool onek_family = s->cfg.ndim == 2 && s->cfg.method[2] < 0 && s->cfg.method[5] <= 0 &&
@@ -494,9 +505,11 @@ int do_step2ds(pcl_solver *s, const double *qin, double *qout, double dt, bool c
     l.ids = 1;
     l.fwave = s->cfg.fwave;
     l.stream = stream;
-    // quiet tiles (quiet_tiles.hpp): the whole block only (a decomposed block's ghost frame and tile subsets are left out)
+    // quiet tiles (quiet_tiles.hpp): the whole block only (a decomposed block's ghost frame and tile subsets are left out),
+    // and not where aux planes are staged (the key of the remembered state does not cover pcl_put_aux, and with a
+    // capacity function a tile's cached Courant maxima are not dt-free)
     const QuietTiles::Key key(s->cfg.rp, s->cfg.fwave, s->cfg.math, a);
-    const bool book = s->qt.plan(l, qin, qout, key, dt, sub == 0 && !s->halo.active, carry);
+    const bool book = s->qt.plan(l, qin, qout, key, dt, sub == 0 && !s->halo.active && !fused_aux_family(s), carry);
     std::string err;
     int rc = PCL_BY_MATH(s->cfg.math, launch_step2ds(l, err));
     if (rc) fail(rc, err);
