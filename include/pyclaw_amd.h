@@ -401,6 +401,13 @@ int pcl_allreduce_max(pcl_solver *s, double *value);
  * cells next to that edge/corner) or FILLED from direction dir (send=0: ghost cells).  dir:
  * 0..7 = W,E,S,N,SW,SE,NW,NE.  Exactly the geometry the device pack/unpack kernels use. */
 int pcl_halo_region(int dir, int send, int I, int J, int mbc, int out_i0_j0_ni_nj[4]);
+/* Host-only helper (no GPU needed): the ghost-cell rule of the built-in boundary conditions (solver.py:384-452) as the
+ * kernels apply it.  Cell k of a dimension of n cells (ghosts included, width mbc) whose lower / upper side has the
+ * type lo / hi (PCL_BC_*, or -1: no fill on that side) takes its value from cell out[0]; out[1] = 1: the normal
+ * momentum component changes sign (reflecting; never for an aux array); out[2] = 1: the value is the constant state
+ * of side out[3] (0 lower, 1 upper) instead (PCL_BC_CUSTOM).  An interior cell, and a ghost cell of a side without a
+ * fill, maps to itself. */
+int pcl_ghost_map(int k, int n, int mbc, int lo, int hi, int out_src_neg_cst_side[4]);
 
 /* ---- debug / self-test --------------------------------------------------------------- */
 /* Runs the wavefront neighbour-shift primitive on 64 values: left[l]=in[l-1],

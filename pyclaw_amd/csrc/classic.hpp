@@ -21,6 +21,8 @@
 #include <hip/hip_runtime.h>
 #include <type_traits>
 
+#include "ghost_rule.hpp"
+
 // Streaming access to the state arrays.  Every pass reads each cell of q once (plus a 2-cell halo) and writes it once,
 // and the arrays (671 MB per 4096^2 Euler state) are far larger than L2 + the 256 MB Infinity Cache, so nothing a pass
 // touches is still cached when the next pass wants it: nontemporal loads / stores stop the lines from displacing each
@@ -491,28 +493,6 @@ template <int IXY> struct TileShape {
     }
 };
 constexpr int LINE = 16;  // doubles per 128-byte line
-
-// Boundary condition of one side as an index remap (solver.py:384-452): ghost index k of a dimension
-// with n cells (ghosts included) reads interior index `src`; `neg` = reflecting (negate the normal
-// momentum component), `cst` = constant inflow state.
-struct VbcMap { int src; bool neg, cst; int side; };
-__device__ __forceinline__ VbcMap vbc_map(int k, int n, int mbc, int lo, int hi) {
-    VbcMap r{k, false, false, 0};
-    if (k < mbc && lo >= 0) {
-        r.side = 0;
-        if (lo == 1) r.src = mbc;                       // outflow
-        else if (lo == 2) r.src = n - 2 * mbc + k;      // periodic
-        else if (lo == 3) { r.src = 2 * mbc - 1 - k; r.neg = true; }
-        else r.cst = true;
-    } else if (k >= n - mbc && hi >= 0) {
-        r.side = 1;
-        if (hi == 1) r.src = n - mbc - 1;
-        else if (hi == 2) r.src = k - (n - 2 * mbc);    // q[n-mbc+t] = q[mbc+t]
-        else if (hi == 3) { r.src = 2 * (n - mbc) - 1 - k; r.neg = true; }
-        else r.cst = true;
-    }
-    return r;
-}
 
 // Workgroups are handed to the 8 XCDs round-robin (blockIdx % 8) and every XCD has its own L2.  Tiles that share
 // cache lines (the unsplit kernels' 60-cell / 14-column pieces are not line-aligned) should therefore run on
