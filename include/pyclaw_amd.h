@@ -327,7 +327,9 @@ int pcl_kernel_timing(pcl_solver *s, int enable);
 int pcl_kernel_timing_read(pcl_solver *s, double *ms_total, long *launches);
 /* The dimension-split 2-D step has two forms with identical results (step2ds.f:83-159 as x pass + y pass, or both sweeps
  * in one kernel, q through HBM once per step); under pcl_step_hyperbolic / pcl_bc_step one block runs the faster one,
- * re-measured every 256 steps (PCL_TUNE_FUSED_STEP = 0 / 1 pins a form).  The one-kernel form exists for mbc = 2 and
+ * decided afresh every 256 steps: where the last one-kernel launch ran over a tile list of at most a quarter of the tiles the
+ * one kernel stays without a trial (a rule on the state, not on timing), otherwise a few steps of each form are timed
+ * (PCL_TUNE_FUSED_STEP = 0 / 1 pins a form).  The one-kernel form exists for mbc = 2 and
  * euler_5wave_2d, acoustics_2d, advection_2d, shallow_2d, vc_acoustics_2d, vc_advection_2d and psystem_fwave_2d, with or
  * without a capacity function (aux planes and aux(mcapa) are staged in the kernel's tile next to q); decomposed blocks of
  * the last three, and of any solver with a capacity function, keep the two passes, as does mbc > 2.  Since the last pcl_kernel_timing reset: cumulative device time (ms)

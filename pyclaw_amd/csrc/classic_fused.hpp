@@ -71,8 +71,10 @@ static_assert(F_WAVES == 4, "one quiet byte per wavefront in a 32-bit word");
 
 // The Courant hand-over behind a one-kernel launch of the whole block, with the next launch's tile list.  Workgroup 0
 // does what cfl_handover (pclaw.hip) does and nothing else: read the step's word, re-zero it, store the value and then
-// the sequence number to host memory (system-scope release), so the host's poll waits for nothing else; it also zeroes
-// *other for the hand-over after next.  Workgroups 1.. take one tile per thread (row-major): a tile off the frame whose
+// the sequence number to host memory (system-scope release), so the host's poll waits for nothing else; next to the value
+// it leaves the number of tiles the launch just run was dispatched for (the na + nq of the list it ran over, *ran, or
+// every tile: the host's form-trial gate, pclaw.hip), and it zeroes *other for the hand-over after next.  Workgroups 1..
+// take one tile per thread (row-major): a tile off the frame whose
 // 3 x 3 neighbourhood was quiet in tq_in (the launch just run) is skipped by the next launch -- its word in tq_out, the
 // next launch's words, becomes TQ_ALL, and its cached Courant maxima go into next->cx / next->cy (an atomic max of bit
 // patterns: doubles >= +0, dt-free; the next launch multiplies by dt/d) -- every other tile is
@@ -87,14 +89,17 @@ __global__ __launch_bounds__(TL_THREADS) void handover_list_kernel(unsigned long
                                                                    unsigned *__restrict__ tq_out,
                                                                    const double2 *__restrict__ tq_cfl,
                                                                    int *__restrict__ list, TileNext *next,
-                                                                   TileNext *other) {
+                                                                   TileNext *other, const TileNext *ran) {
     __shared__ int wbase[2][TL_THREADS / WAVE];
     __shared__ int base[2];
     if (blockIdx.x == 0) {
         if (threadIdx.x == 0) {
             const unsigned long long v = *cfl;
             *cfl = 0;                    // invariant: the word is zero whenever no step is in flight
+            const int nt = ntx * nty;
+            const int ran_over = ran ? min(ran->na + ran->nq, nt) : nt;
             __hip_atomic_store(host, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            __hip_atomic_store(host + 2, (unsigned long long)ran_over, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
             __hip_atomic_store(host + 1, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
             other->na = 0;
             other->nq = 0;

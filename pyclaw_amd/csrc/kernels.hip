@@ -274,7 +274,7 @@ int launch_tile_handover(const TileHandover &h, std::string &err) {
     // workgroup 0: the hand-over; workgroups 1..: the tiles
     hipLaunchKernelGGL(handover_list_kernel, dim3(1 + (nt + TL_THREADS - 1) / TL_THREADS), dim3(TL_THREADS), 0, h.stream,
                        h.cfl, h.host, h.seq, h.ntx, h.nty, h.mbc, h.mx, h.my, h.tq_in, h.tq_out, h.tq_cfl, h.tq_list,
-                       h.next, h.other);
+                       h.next, h.other, h.ran);
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? PCL_OK : hip_fail(err, "tile hand-over launch", e);
 }

@@ -7,12 +7,15 @@
 //
 //                                  reads                       writes                            then
 //   launch n        plan()         L, N[x+2] if it skips       W[c+1], C (computed tiles)        c += 1
-//   hand-over n     handover()     W[c+1], C                   W[c+2] (tiles n + 1 skips), L,    x += 1
-//                                                              N[x] filled, N[x+1] zeroed
+//   hand-over n     handover()     W[c+1], C, N[x+2] if        W[c+2] (tiles n + 1 skips), L,    x += 1
+//                                  launch n ran over a list    N[x] filled, N[x+1] zeroed,
+//                                  (its na + nq)               host word [2] (tiles launch n ran)
 //   launch n + 1    plan()         L, N[x] if it skips         W[c+2], C (computed tiles)
 //   a hook between                 W[c]   (words_read)         nothing
 //                                  N[x+2] (ran_over)
 //
+// Host word [2] (next to the Courant number [0] and the sequence number [1]) is read by the form-trial gate of
+// step_hyperbolic (pclaw.hip) while list_count_current() holds: no read-back, no wait.
 // N[x] is filled with atomics, so it must be zero: the hand-over before zeroed it.  A launch with skipping switched off,
 // or one whose step fails before its hand-over, advances c and not x; one counter for both would then have the next
 // hand-over fill a block that nobody zeroed, so there are two.  A hand-over launch that fails zeroes all three blocks
@@ -124,6 +127,7 @@ public:
             h.tq_list = list;
             h.next = block(0);
             h.other = block(1);
+            h.ran = last == LIST ? stat : nullptr;
         }
         return due;
     }
@@ -142,6 +146,9 @@ public:
     Last last_launch() const { return last; }
     const unsigned *words_read() const { return words[(c + 2) % 3]; }   // the words its list was built from
     const TileNext *ran_over() const { return stat; }                   // the block of that list (last_launch() == LIST)
+    // The last launch ran over a list and the launch to come would run over the next one (carry: QuietTiles::take_valid
+    // at the step's entry point): the count its hand-over left in host memory describes the state as it is now.
+    bool list_count_current(bool carry) const { return carry && last == LIST && listed; }
 
 private:
     unsigned *words[3] = {nullptr, nullptr, nullptr};

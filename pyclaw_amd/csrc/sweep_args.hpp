@@ -169,10 +169,11 @@ struct SweepLaunch {
 
 // The Courant hand-over behind a one-kernel launch of the whole block, with the next launch's tile list
 // (classic_fused.hpp: handover_list_kernel): the words of the launch just enqueued (tq_in), the next launch's words
-// (tq_out, TQ_ALL for the tiles it skips), the list, and two TileNext blocks (next is filled, other zeroed).
+// (tq_out, TQ_ALL for the tiles it skips), the list, and two TileNext blocks (next is filled, other zeroed); ran is the
+// block of the list the launch just enqueued ran over (null: it computed every tile).
 struct TileHandover {
     unsigned long long *cfl = nullptr;      // the device Courant word (read, re-zeroed)
-    unsigned long long *host = nullptr;     // device view of the host block: [0] value, [1] sequence number
+    unsigned long long *host = nullptr;     // device view of the host block: [0] value, [1] sequence number, [2] tiles dispatched
     unsigned long long seq = 0;
     int ntx = 0, nty = 0, mbc = 0, mx = 0, my = 0;
     const unsigned *tq_in = nullptr;
@@ -180,6 +181,7 @@ struct TileHandover {
     const double2 *tq_cfl = nullptr;
     int *tq_list = nullptr;
     TileNext *next = nullptr, *other = nullptr;
+    const TileNext *ran = nullptr;
     hipStream_t stream;
 };
 
