@@ -353,6 +353,13 @@ int pcl_tile_words(pcl_solver *s, unsigned *host, int *ntx, int *nty);
  * in the step before, *nq had been quiet there (both 0 when that step did not run over a list); makes the next step
  * compute every tile */
 int pcl_tile_list_classes(pcl_solver *s, long *na, long *nq);
+/* The ring check of the one-kernel step's listed tiles (on by default): a listed tile that was quiet in the step before
+ * compares the cells around its own with them and, where all are equal, is done without loading the tile -- same bits,
+ * same Courant number.  enable = 0: every listed tile is loaded and swept.  Not under the fused source. */
+int pcl_tile_ring(pcl_solver *s, int enable);
+/* internal, for the test suite only: how many listed tiles of the last one-kernel step the ring check settled (0 when
+ * that step did not run over a list); makes the next step compute every tile */
+int pcl_tile_ring_stats(pcl_solver *s, long *short_path);
 /* hyperbolic steps (classic) / right-hand sides (SharpClaw) attempted since pcl_create, rejected ones included */
 int pcl_step_count(pcl_solver *s, long *steps);
 

@@ -174,6 +174,62 @@ __global__ __launch_bounds__(TL_THREADS) void handover_list_kernel(unsigned long
     }
 }
 
+// The ring check of a class-Q tile: its owned interior cells all compare equal to one state S (the
+// launch before found the whole window uniform and left them as they were), so the window is uniform again exactly
+// when every OTHER cell of it, taken as the load phase would put it into the tile, compares equal to S -- == on every
+// component, as lane_core's no-jump test: a NaN is unequal, +0 equals -0.  S is the tile's first owned cell (tile row
+// and column HALO: interior in every tile).  Tiles loaded straight take the ring in 16-byte pairs, rows 0-1 and 14-15
+// and the two halo pairs of rows 2-13 (152 pairs, one per thread); frame and partial tiles take the cells of the
+// scalar load, four per thread, less the owned interior ones.  One flag per wavefront in flags[0 .. F_WAVES-1] (the
+// tile, not loaded yet), one barrier: the same answer in every thread of the workgroup.
+template <int MEQN, class LOAD>
+__device__ __forceinline__ bool ring_uniform(const SweepArgs &a, int x0, int y0, bool straight, bool vbc, double *flags,
+                                             const LOAD &load_mapped_cell) {
+    static_assert(HALO == 2, "a 16-byte pair is the halo columns of one side");
+    double s[MEQN];
+    const long g0 = (long)(y0 + HALO) * a.pitch + (x0 + HALO);
+#pragma unroll
+    for (int m = 0; m < MEQN; m++) s[m] = a.qin[m * a.plane + g0];
+    bool eq = true;
+    if (straight) {
+        constexpr int ROWP = 2 * HALO * F_PPR, SIDEP = 2 * F_OWN_R;     // pairs of the four halo rows, of the sides
+        static_assert(ROWP + SIDEP <= F_THREADS, "one pair per thread");
+        const int t = threadIdx.x;
+        if (t < ROWP + SIDEP) {
+            const int k = t < ROWP ? t / F_PPR : (t - ROWP) / 2;
+            const int r = t < ROWP ? (k < HALO ? k : F_ROWS - 2 * HALO + k) : HALO + k;
+            const int c = t < ROWP ? 2 * (t % F_PPR) : (((t - ROWP) & 1) ? F_COLS - HALO : 0);
+            const long g = (long)(y0 + r) * a.pitch + (x0 + c);
+#pragma unroll
+            for (int m = 0; m < MEQN; m++) {
+                const double2 v = *reinterpret_cast<const double2 *>(&a.qin[m * a.plane + g]);
+                eq = eq & (v.x == s[m]) & (v.y == s[m]);
+            }
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < F_ROWS * F_COLS / F_THREADS; k++) {
+            const int r = wave_row(threadIdx.x / WAVE, k) + (threadIdx.x & (WAVE - 1)) / F_COLS, c = threadIdx.x & (F_COLS - 1);
+            const int gx = x0 + c, gy = y0 + r;
+            const bool own = r >= HALO && r < F_ROWS - HALO && c >= HALO && c < F_COLS - HALO && gx >= a.mbc &&
+                             gx < a.mbc + a.mx && gy >= a.mbc && gy < a.mbc + a.my;
+            if (!own) {
+                double v[MEQN];
+                load_mapped_cell(vbc, gx < a.I ? gx : a.I - 1, gy < a.J ? gy : a.J - 1, v);
+#pragma unroll
+                for (int m = 0; m < MEQN; m++) eq = eq & (v[m] == s[m]);
+            }
+        }
+    }
+    const bool weq = __all(eq);
+    if ((threadIdx.x & (WAVE - 1)) == 0) flags[threadIdx.x / WAVE] = weq ? 1.0 : 0.0;
+    __syncthreads();
+    bool all = true;
+#pragma unroll
+    for (int w = 0; w < F_WAVES; w++) all = all & (flags[w] == 1.0);
+    return all;
+}
+
 // Full launches: workgroup b takes tile b (through the chunked order below).  List launches (tq_list set, one
 // workgroup per tile of the grid): workgroup 0 first publishes the Courant number of the skipped tiles, dt/d times the
 // maxima tq_next holds; then workgroup b takes the b-th listed tile, through the same order -- the na tiles of class A
@@ -202,7 +258,8 @@ __global__ __launch_bounds__(F_THREADS, fused_wgs(fused_planes<RP, CAPA>())) voi
                                                                               unsigned *__restrict__ tq_out,
                                                                               double2 *__restrict__ tq_cfl,
                                                                               const int *__restrict__ tq_list,
-                                                                              const TileNext *tq_next) {
+                                                                              const TileNext *tq_next,
+                                                                              unsigned *__restrict__ tq_ring, unsigned ring_seq) {
     constexpr int MEQN = RP::MEQN;
     constexpr int NAUX = RP::NAUX, PAUX = MEQN + (CAPA ? 1 : 0), NP = PAUX + NAUX, NX = NP - MEQN;
     static_assert(!SRC || (MEQN == 5 && NX == 0), "fused source: the Euler solver, no capacity function");
@@ -214,6 +271,33 @@ __global__ __launch_bounds__(F_THREADS, fused_wgs(fused_planes<RP, CAPA>())) voi
         return (long)aux_idx<RP, 1>(e - (CAPA ? 1 : 0)) * a.plane;
     };
     static_assert(fused_aux_same<RP>(), "one staging serves both sweeps: the normal solver reads the same aux planes in x and y");
+
+    // One cell of the tile as the load phase puts it there: array cell (gx, gy), already clamped to the array.  On a frame
+    // tile of a device-side boundary condition (vbc) a ghost cell is its source cell, mirrored, or the side's constant:
+    // qbc = Y(X(q)), x sides first, then y sides over the x-filled array (solver.py:354-381).  (A lambda over the kernel's
+    // own argument block: through a reference parameter the selects between two constants cost every instance scratch.)
+    auto load_mapped_cell = [&a](bool vbc, int gx, int gy, double (&v)[MEQN]) {
+        if (vbc) {
+            const VbcMap mi = vbc_map(gx, a.I, a.mbc, a.vbc[0], a.vbc[1]);
+            const VbcMap mj = vbc_map(gy, a.J, a.mbc, a.vbc[2], a.vbc[3]);
+            const long gs = (long)mj.src * a.pitch + mi.src;
+#pragma unroll
+            for (int m = 0; m < MEQN; m++) {
+                double w = a.qin[m * a.plane + gs];
+                if (m == 1) w = mi.neg ? -w : w;
+                const double cx = mi.side ? a.vconst[1][m] : a.vconst[0][m];
+                w = mi.cst ? cx : w;
+                if (m == 2) w = mj.neg ? -w : w;
+                const double cy = mj.side ? a.vconst[3][m] : a.vconst[2][m];
+                w = mj.cst ? cy : w;
+                v[m] = w;
+            }
+        } else {
+            const long g = (long)gy * a.pitch + gx;
+#pragma unroll
+            for (int m = 0; m < MEQN; m++) v[m] = a.qin[m * a.plane + g];
+        }
+    };
 
     // Chunked order: the hardware deals consecutive workgroups to the 8 XCDs in turn; in every window of 64 tiles each
     // XCD takes 8 CONSECUTIVE tiles of a tile row (they share partial lines and halo columns in that XCD's L2) while the
@@ -273,6 +357,25 @@ __global__ __launch_bounds__(F_THREADS, fused_wgs(fused_planes<RP, CAPA>())) voi
     const bool full_tile = x0 + F_COLS <= a.I && y0 + F_ROWS <= a.J;
     const bool vbc_tile = a.vbc_on && ((x0 < a.mbc && a.vbc[0] >= 0) || (x0 + F_COLS > a.I - a.mbc && a.vbc[1] >= 0) ||
                                        (y0 < a.mbc && a.vbc[2] >= 0) || (y0 + F_ROWS > a.J - a.mbc && a.vbc[3] >= 0));
+    if constexpr (!SRC && !FWAVE && NX == 0) {
+        // A class-Q tile whose ring compares equal to its owned cells is quiet again: every sweep would
+        // take the shortcut, qout holds the result, and the wavefronts' cached maxima are what they would compute.  Each
+        // wavefront leaves its quiet byte and publishes its Courant number; tq_ring gets the launch's number (the test
+        // hook pcl_tile_ring_stats counts them).  tq_ring null: the check is switched off (pcl_tile_ring).
+        if (class_q && tq_ring) {                     // workgroup-uniform
+            if (ring_uniform<MEQN>(a, x0, y0, full_tile && !vbc_tile, vbc_tile, tile, load_mapped_cell)) {
+                const int wv = threadIdx.x / WAVE;
+                const double2 c = tq_cfl[tile_id * F_WAVES + wv];
+                if ((threadIdx.x & (WAVE - 1)) == 0) {
+                    reinterpret_cast<unsigned char *>(tq_out + tile_id)[wv] = TQ_QUIET;
+                    if (wv == 0) tq_ring[tile_id] = ring_seq;
+                }
+                cfl_publish(a.cfl, dmax(a.dtd * c.x, a.dtd_t * c.y));
+                return;
+            }
+            __syncthreads();                          // the flags lie in the tile: every wavefront has read them
+        }
+    }
     if (full_tile && !vbc_tile) {
 #pragma unroll
         for (int k = 0; k < F_ROWS * F_COLS / 2 / F_THREADS; k++) {
@@ -302,27 +405,10 @@ __global__ __launch_bounds__(F_THREADS, fused_wgs(fused_planes<RP, CAPA>())) voi
             int gx = x0 + c, gy = y0 + r;
             gx = gx < a.I ? gx : a.I - 1;            // past the edge: repeat the last cell (never feeds a stored value)
             gy = gy < a.J ? gy : a.J - 1;
-            if (vbc_tile) {
-                // qbc = Y(X(q)): x sides first, then y sides over the x-filled array (solver.py:354-381)
-                const VbcMap mi = vbc_map(gx, a.I, a.mbc, a.vbc[0], a.vbc[1]);
-                const VbcMap mj = vbc_map(gy, a.J, a.mbc, a.vbc[2], a.vbc[3]);
-                const long gs = (long)mj.src * a.pitch + mi.src;
+            double v[MEQN];
+            load_mapped_cell(vbc_tile, gx, gy, v);
 #pragma unroll
-                for (int m = 0; m < MEQN; m++) {
-                    double v = a.qin[m * a.plane + gs];
-                    if (m == 1) v = mi.neg ? -v : v;
-                    const double cx = mi.side ? a.vconst[1][m] : a.vconst[0][m];
-                    v = mi.cst ? cx : v;
-                    if (m == 2) v = mj.neg ? -v : v;
-                    const double cy = mj.side ? a.vconst[3][m] : a.vconst[2][m];
-                    v = mj.cst ? cy : v;
-                    tile[ftile_at(m, r, c)] = v;
-                }
-            } else {
-                const long g = (long)gy * a.pitch + gx;
-#pragma unroll
-                for (int m = 0; m < MEQN; m++) tile[ftile_at(m, r, c)] = a.qin[m * a.plane + g];
-            }
+            for (int m = 0; m < MEQN; m++) tile[ftile_at(m, r, c)] = v[m];
             if constexpr (NX > 0) {          // the cell's own aux, on the frame too (ghost cells of aux are real memory)
                 const long ga = (long)gy * a.pitch + gx;
 #pragma unroll

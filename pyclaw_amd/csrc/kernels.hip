@@ -142,7 +142,7 @@ template <class RP> int launch_step2ds_t(const SweepLaunch &l, std::string &err)
     // a list launch: the tiles the hand-over+list kernel behind the previous launch listed (classic_fused.hpp); one
     // workgroup per tile of the grid, those past the list's end return at once
     const bool list = l.tq_list != nullptr;
-    if (list && (a.sub != 0 || !l.tq_out || !l.tq_cfl || !l.tq_next)) {
+    if ((list && (a.sub != 0 || !l.tq_out || !l.tq_cfl || !l.tq_next)) || (l.tq_ring && !list)) {
         err = "step2ds tile list: the whole block, with its bookkeeping";
         return PCL_EINVAL;
     }
@@ -150,13 +150,13 @@ template <class RP> int launch_step2ds_t(const SweepLaunch &l, std::string &err)
     if (a.src_id != 0) {
         if constexpr (std::is_same<RP, Euler5>::value)
             hipLaunchKernelGGL((step2ds_kernel<RP, FW, true>), grid, dim3(F_THREADS), 0, l.stream, a, ntx, nty, l.tq_out,
-                               l.tq_cfl, l.tq_list, l.tq_next);
+                               l.tq_cfl, l.tq_list, l.tq_next, l.tq_ring, l.ring_seq);
     } else if (capa)
         hipLaunchKernelGGL((step2ds_kernel<RP, FW, false, true>), grid, dim3(F_THREADS), 0, l.stream, a, ntx, nty, l.tq_out,
-                           l.tq_cfl, l.tq_list, l.tq_next);
+                           l.tq_cfl, l.tq_list, l.tq_next, l.tq_ring, l.ring_seq);
     else
         hipLaunchKernelGGL((step2ds_kernel<RP, FW, false>), grid, dim3(F_THREADS), 0, l.stream, a, ntx, nty, l.tq_out,
-                           l.tq_cfl, l.tq_list, l.tq_next);
+                           l.tq_cfl, l.tq_list, l.tq_next, l.tq_ring, l.ring_seq);
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? PCL_OK : hip_fail(err, "step2ds launch", e);
 }

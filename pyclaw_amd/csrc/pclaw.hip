@@ -1732,6 +1732,29 @@ int pcl_tile_list_classes(pcl_solver *s, long *na, long *nq) {
     return PCL_OK;
 }
 
+// the ring check of class-Q tiles (classic_fused.hpp: ring_uniform) on / off; off, every listed tile takes the full path
+int pcl_tile_ring(pcl_solver *s, int enable) {
+    if (s) s->qt.invalidate();            // quiet tiles: not a read-only call (quiet_tiles.hpp)
+    if (!s) return fail(PCL_EINVAL, "null argument");
+    s->qt.set_ring(enable != 0);
+    return PCL_OK;
+}
+
+// listed tiles of the last one-kernel launch that its ring check settled (they returned in front of the load); 0 when
+// that launch did not run over a list
+int pcl_tile_ring_stats(pcl_solver *s, long *short_path) {
+    if (s) s->qt.invalidate();            // quiet tiles: not a read-only call (quiet_tiles.hpp)
+    if (!s || !short_path) return fail(PCL_EINVAL, "null argument");
+    *short_path = 0;
+    if (s->qt.last_launch() != pcl::QuietTiles::LIST) return PCL_OK;
+    std::vector<unsigned> marks((size_t)s->qt.ntx * s->qt.nty);
+    HIP_TRY(hipSetDevice(s->cfg.device));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    HIP_TRY(hipMemcpy(marks.data(), s->qt.ring_marks(), marks.size() * sizeof(unsigned), hipMemcpyDeviceToHost));
+    for (unsigned m : marks) *short_path += m == s->qt.ring_number();
+    return PCL_OK;
+}
+
 int pcl_tile_words(pcl_solver *s, unsigned *host, int *ntx, int *nty) {
     if (s) s->qt.invalidate();            // quiet tiles: not a read-only call (quiet_tiles.hpp)
     if (!s || !ntx || !nty) return fail(PCL_EINVAL, "null argument");

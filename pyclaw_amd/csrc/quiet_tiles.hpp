@@ -2,17 +2,21 @@
 // the kernels: classic_fused.hpp, the proofs: DESIGN.md 4.1a).
 //
 // Device memory: three word arrays W[0..2] (one 32-bit word per tile), the per-wavefront Courant maxima C, the tile
-// list L and three TileNext blocks N[0..2].  Two counters rotate them: c (words) advances with every booked launch, x
-// (blocks) with every hand-over that built a list.  With c and x taken in front of launch n (indices modulo 3):
+// list L, the ring marks R (one 32-bit word per tile) and three TileNext blocks N[0..2].  Two counters rotate them: c
+// (words) advances with every booked launch, x (blocks) with every hand-over that built a list; r numbers the booked
+// launches.  With c and x taken in front of launch n (indices modulo 3):
 //
 //                                  reads                       writes                            then
-//   launch n        plan()         L, N[x+2] if it skips       W[c+1], C (computed tiles)        c += 1
+//   launch n        plan()         L, N[x+2] if it skips       W[c+1], C (computed tiles),       c += 1, r += 1
+//                                                              R := r (tiles its ring check
+//                                                              settled, classic_fused.hpp)
 //   hand-over n     handover()     W[c+1], C, N[x+2] if        W[c+2] (tiles n + 1 skips), L,    x += 1
 //                                  launch n ran over a list    N[x] filled, N[x+1] zeroed,
 //                                  (its na + nq)               host word [2] (tiles launch n ran)
-//   launch n + 1    plan()         L, N[x] if it skips         W[c+2], C (computed tiles)
+//   launch n + 1    plan()         L, N[x] if it skips         W[c+2], C (computed tiles), R
 //   a hook between                 W[c]   (words_read)         nothing
 //                                  N[x+2] (ran_over)
+//                                  R      (ring_marks: the words equal to r)
 //
 // Host word [2] (next to the Courant number [0] and the sequence number [1]) is read by the form-trial gate of
 // step_hyperbolic (pclaw.hip) while list_count_current() holds: no read-back, no wait.
@@ -70,6 +74,8 @@ public:
             if (e == hipSuccess) e = hipMalloc((void **)&w, nt * sizeof(unsigned));
         if (e == hipSuccess) e = hipMalloc((void **)&cfl, nt * 4 * sizeof(double2));
         if (e == hipSuccess) e = hipMalloc((void **)&list, nt * sizeof(int));
+        if (e == hipSuccess) e = hipMalloc((void **)&ring, nt * sizeof(unsigned));
+        if (e == hipSuccess) e = hipMemsetAsync(ring, 0, nt * sizeof(unsigned), stream);
         if (e == hipSuccess) e = hipMalloc((void **)&next, 3 * sizeof(TileNext));
         if (e == hipSuccess) e = hipMemsetAsync(next, 0, 3 * sizeof(TileNext), stream);
         return e;
@@ -79,12 +85,14 @@ public:
             if (w) hipFree(w);
         if (cfl) hipFree(cfl);
         if (list) hipFree(list);
+        if (ring) hipFree(ring);
         if (next) hipFree(next);
     }
 
     void invalidate() { valid = false; }
     bool take_valid() { const bool v = valid; valid = false; return v; }
     void set_enabled(bool on) { enabled = on; }
+    void set_ring(bool on) { ring_on = on; }
 
     // In front of a one-kernel launch qin -> qout: fills l.tq_* and returns true if the launch is booked (`whole`: the
     // whole undecomposed block).  Every flag is cleared; launched() sets them again.
@@ -93,9 +101,12 @@ public:
         if (book) {
             l.tq_out = written_next();
             l.tq_cfl = cfl;
+            if (++ring_seq == 0) ring_seq = 1;          // 0 is what create() left in R
+            l.ring_seq = ring_seq;
             if (may_skip(qin, qout, key, dt, carry)) {
                 l.tq_list = list;
                 l.tq_next = block(2);
+                if (ring_on) l.tq_ring = ring;
             }
         }
         valid = hand = listed = false;
@@ -146,6 +157,8 @@ public:
     Last last_launch() const { return last; }
     const unsigned *words_read() const { return words[(c + 2) % 3]; }   // the words its list was built from
     const TileNext *ran_over() const { return stat; }                   // the block of that list (last_launch() == LIST)
+    const unsigned *ring_marks() const { return ring; }                 // a tile its ring check settled holds ring_number()
+    unsigned ring_number() const { return ring_seq; }
     // The last launch ran over a list and the launch to come would run over the next one (carry: QuietTiles::take_valid
     // at the step's entry point): the count its hand-over left in host memory describes the state as it is now.
     bool list_count_current(bool carry) const { return carry && last == LIST && listed; }
@@ -158,6 +171,9 @@ private:
     int c = 0, x = 0;
     const TileNext *stat = nullptr;
     bool enabled = true;                // pcl_tile_skip
+    unsigned *ring = nullptr;
+    unsigned ring_seq = 0;              // the number of the last booked launch
+    bool ring_on = true;                // pcl_tile_ring
     bool valid = false, hand = false, listed = false;
     Last last = NONE;
     const double *last_in = nullptr, *last_out = nullptr;

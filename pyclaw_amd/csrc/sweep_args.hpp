@@ -165,6 +165,10 @@ struct SweepLaunch {
     double2 *tq_cfl = nullptr;
     const int *tq_list = nullptr;
     const TileNext *tq_next = nullptr;
+    // the ring check of a list launch's class-Q tiles (null: off): a tile settled by it leaves ring_seq, the number of
+    // this launch, in its word of tq_ring (pcl_tile_ring_stats)
+    unsigned *tq_ring = nullptr;
+    unsigned ring_seq = 0;
 };
 
 // The Courant hand-over behind a one-kernel launch of the whole block, with the next launch's tile list
