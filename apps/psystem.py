@@ -1,0 +1,81 @@
+"""
+The p-system in a two-material checkerboard (the reference's apps/psystem set-up): strain eps and momenta (rho u, rho v),
+    eps_t - u_x - v_y = 0,   (rho u)_t - sigma(eps, x, y)_x = 0,   (rho v)_t - sigma(eps, x, y)_y = 0,
+solved with the f-wave Riemann solver ``rp_psystem_fwave_2d`` (``solver.fwave = True``) by the classic dimension-split
+step or by SharpClaw (WENO5, SSP104).  aux = (density, modulus K, stress-law flag, strain copy): flag 1 is the linear
+law sigma = K eps, anything else sigma = exp(K eps) - 1.  The medium does not change in time and neither solver here
+needs the strain copy of aux(4) (only the transverse solver of the unsplit classic step reads it), so there is no
+before-step hook.
+"""
+import numpy as np
+
+# the two materials (density, modulus) and the period of the pattern in x and y; each tile is half a period wide
+MATERIALS = ((1.0, 1.0), (4.0, 4.0))
+PERIOD = (1.0, 1.0)
+
+
+def checkerboard(xc, yc, linearity=2):
+    """aux (4, len(xc), len(yc)) of the checkerboard: a cell belongs to material 0 where the half-period tiles it lies
+    in have the same parity in x and y, to material 1 elsewhere."""
+    tx = np.floor(2.0 * np.asarray(xc) / PERIOD[0]).astype(np.int64)
+    ty = np.floor(2.0 * np.asarray(yc) / PERIOD[1]).astype(np.int64)
+    second = ((tx[:, None] + ty[None, :]) % 2) != 0
+    aux = np.zeros((4, len(xc), len(yc)), order='F')
+    aux[0] = np.where(second, MATERIALS[1][0], MATERIALS[0][0])
+    aux[1] = np.where(second, MATERIALS[1][1], MATERIALS[0][1])
+    aux[2] = float(linearity)
+    return aux
+
+
+def stress_pulse(state, amplitude, x0, y0, varx, vary):
+    """q at rest with a Gaussian STRESS pulse: the strain is the stress law inverted cell by cell."""
+    X, Y = state.grid.c_center
+    sigma = amplitude * np.exp(-(X - x0) ** 2 / (2.0 * varx) - (Y - y0) ** 2 / (2.0 * vary))
+    K, flag = state.aux[1], state.aux[2]
+    state.q[0] = np.where(flag == 1.0, sigma / K, np.log1p(sigma) / K)
+    state.q[1] = 0.0
+    state.q[2] = 0.0
+    state.aux[3] = state.q[0]
+
+
+def psystem2D(pyclaw, mx=200, my=200, solver_type='classic', lower=(0.25, 0.25), upper=(20.25, 20.25), bc='reference',
+              linearity=2, amplitude=10.0, center=(0.25, 0.25), var=(0.5, 0.5), lim_type=2, time_integrator='SSP104',
+              tfinal=20.0, nout=10, math='exact', run=True):
+    """bc = 'reference': walls on the lower sides, extrapolation on the upper ones (the pulse sits in the corner, one
+    quarter of a symmetric problem); 'periodic': periodic in both directions (the domain should hold whole periods).
+    Returns the controller (run or not)."""
+    if solver_type == 'classic':
+        solver = pyclaw.ClawSolver2D()
+        solver.dim_split = True                       # no transverse solver: aux(4) is never read
+        solver.limiters = pyclaw.limiters.tvd.superbee
+        solver.cfl_max, solver.cfl_desired = 0.9, 0.8
+    else:
+        solver = pyclaw.SharpClawSolver2D()
+        solver.lim_type = lim_type
+        solver.time_integrator = time_integrator
+    solver.math = math
+    solver.rp = pyclaw.riemann.rp_psystem_fwave_2d
+    solver.fwave = True
+    solver.mwaves = 2
+    for k in range(2):
+        if bc == 'periodic':
+            solver.bc_lower[k] = solver.bc_upper[k] = pyclaw.BC.periodic
+        else:
+            solver.bc_lower[k], solver.bc_upper[k] = pyclaw.BC.reflecting, pyclaw.BC.outflow
+        solver.aux_bc_lower[k], solver.aux_bc_upper[k] = solver.bc_lower[k], solver.bc_upper[k]
+    grid = pyclaw.Grid([pyclaw.Dimension('x', lower[0], upper[0], mx), pyclaw.Dimension('y', lower[1], upper[1], my)])
+    state = pyclaw.State(grid, 3, 4)
+    state.aux[...] = checkerboard(grid.x.center, grid.y.center, linearity)
+    stress_pulse(state, amplitude, center[0], center[1], var[0], var[1])
+    # the fastest sound speed at rest, sqrt(sigma'(eps) / rho), for the first step
+    K, rho = state.aux[1], state.aux[0]
+    bulk = np.where(state.aux[2] == 1.0, K, K * np.exp(K * state.q[0]))
+    solver.dt_initial = 0.5 * solver.cfl_desired * np.min(grid.d) / np.sqrt(bulk / rho).max()
+    claw = pyclaw.Controller()
+    claw.keep_copy = True
+    claw.solution = pyclaw.Solution(state)
+    claw.solver = solver
+    claw.tfinal, claw.nout = tfinal, nout
+    if run:
+        claw.run()
+    return claw

@@ -54,7 +54,8 @@ extern "C" {
 #define PCL_RP_SHALLOW_1D 5     /* rp1_shallow_roe_with_efix.f    cparam: g                       */
 #define PCL_RP_ADVECTION_COLOR_1D 6 /* rp1_advection_color.f; aux(1) = velocity at the cell's left edge */
 #define PCL_RP_ELASTICITY_FWAVE_1D 7 /* rp1_nonlinear_elasticity_fwave.f (stegoton); F-WAVE solver: fwave = 1;  */
-                                     /* aux(1)=rho, aux(2)=K, aux(3)=1: sigma=K eps, else exp(K eps)-1          */
+                                     /* aux(1)=rho, aux(2)=K, aux(3)=1: sigma=K eps, else exp(K eps)-1;         */
+                                     /* classic solver only (PCL_KIND_SHARPCLAW is refused)                     */
 #define PCL_RP_ACOUSTICS_2D 10 /* rpn2/rpt2_acoustics.f     cparam: rho,bulk,cc,zz      */
 #define PCL_RP_EULER5_2D 11    /* rpn2/rpt2_euler_5wave.f   cparam: gamma,gamma1        */
 #define PCL_RP_ADVECTION_2D 12  /* rpn2/rpt2_advection.f      cparam: u,v                  */
@@ -65,6 +66,7 @@ extern "C" {
                                     /* -> rp_params g, dx, dy; aux = the 16 components of apps/shallow-sphere/setaux.f:10-25;      */
                                     /* the unsplit step follows the app's step2qcor.f (conservation fix qcor.f) instead of step2.f */
 #define PCL_RP_PSYSTEM_FWAVE_2D 17 /* rpn2/rpt2_psystem.f (test/psystem/Makefile:5); F-WAVE solver: fwave = 1; aux as above + aux(4)=eps */
+                                   /* (read by rpt2 only); classic and SharpClaw (weno_order 5: mbc 3), fwave = 1 for both      */
 #define PCL_RP_VC_ACOUSTICS_3D 20 /* rpn3_vc_acoustics.f (test/acoustics/3d/Makefile); aux(1)=Z, aux(2)=c; dim-split only */
 
 /* boundary condition types = pyclaw.BC (src/pyclaw/solver.py:17-23) */
@@ -183,13 +185,17 @@ int pcl_step3(int rp, const double *rp_params, int meqn, int mwaves, int maux, i
  * q and dq are (meqn, mx+2mbc[, my+2mbc]) with mbc = (weno_order+1)/2 = 3..9 (clawparams.weno_order is
  * implied by mbc: lim_type 2 with mbc = k runs weno(2k-1); lim_type 1 and 3 take mbc = 3); dq's interior receives
  * dt*dq/dt, its ghost cells are zeroed.  The F90 module state the reference sets through
- * clawparams/workspace/reconstruct (lim_type, mcapa, dx, mwaves) is passed explicitly. */
+ * clawparams/workspace/reconstruct (lim_type, mcapa, dx, mwaves) is passed explicitly; clawparams.fwave follows the
+ * Riemann solver (set for PCL_RP_PSYSTEM_FWAVE_2D, the one f-wave solver these calls take), as sharpclaw.py:269 sets
+ * it from the solver object. */
 /* clawparams.mthlim, part of the F90 module state the reference sets before calling flux1/flux2
  * (sharpclaw.py:268); read by lim_type = 1 (tvd2) only, indexed by component.  Default: all 1 (minmod). */
 int pcl_sharp_module_mthlim(const int *mthlim, int n);
 /* clawparams.char_decomp of the same module state (sharpclaw.py:262), read by pcl_sharp_flux1: 0 = component-wise
  * reconstruction, 1 = wave-based (1d/sharpclaw/flux1.f90:80-107: rp1 on the cell averages, then tvd2_wave for
- * lim_type 1 -- mthlim indexed by WAVE there -- or weno5_wave for lim_type 2; reconstruct.f90:393-478,728-806).
+ * lim_type 1 -- mthlim indexed by WAVE there -- or weno5_wave for lim_type 2; reconstruct.f90:393-478,728-806), for
+ * the six 1-D solvers PCL_RP_ADVECTION_1D .. PCL_RP_ADVECTION_COLOR_1D, with aux arrays and a capacity function
+ * (mcapa) where the solver or the caller has them; mbc 3, no f-wave solver.
  * 2 and 3 need a user-supplied evec routine the reference only stubs (evec.f90:13-14), and the 2-D flux1.f90 calls
  * rpn2 with a wrong argument list on the char_decomp = 1 path (2d/sharpclaw/flux1.f90:86): neither can run in the
  * reference, neither is offered.  A resident solver takes the value in cfg.method[4] (method(5), unused by SharpClaw). */

@@ -471,8 +471,12 @@ template <class RP> int launch_sharp1w(const SweepLaunch &l, std::string &err) {
     const SweepArgs &a = l.a;
     const int nstrips = (a.mx + sstrip(3) - 1) / sstrip(3);
     const dim3 grid((unsigned)((nstrips + 3) / 4));
-    if (l.lim_type == 1) hipLaunchKernelGGL((sharp1w_kernel<RP, 1>), grid, dim3(256), 0, l.stream, a, nstrips);
-    else hipLaunchKernelGGL((sharp1w_kernel<RP, 2>), grid, dim3(256), 0, l.stream, a, nstrips);
+    const bool capa = a.mcapa > 0;
+#define PCL_SHARP1W_LAUNCH(LIM_, CAPA_) \
+    hipLaunchKernelGGL((sharp1w_kernel<RP, LIM_, CAPA_>), grid, dim3(256), 0, l.stream, a, nstrips)
+    if (l.lim_type == 1) { if (capa) PCL_SHARP1W_LAUNCH(1, true); else PCL_SHARP1W_LAUNCH(1, false); }
+    else { if (capa) PCL_SHARP1W_LAUNCH(2, true); else PCL_SHARP1W_LAUNCH(2, false); }
+#undef PCL_SHARP1W_LAUNCH
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? PCL_OK : hip_fail(err, "sharp (wave-based) launch", e);
 }
@@ -480,10 +484,14 @@ template <class RP> int launch_sharp1w(const SweepLaunch &l, std::string &err) {
 
 int launch_sharp(const SweepLaunch &l, std::string &err) {
     const int rp = l.rp;
+    if ((l.fwave != 0) != (rp == PCL_RP_PSYSTEM_FWAVE_2D)) {
+        err = "solver.fwave must be True for an f-wave Riemann solver and only for one";
+        return PCL_EINVAL;
+    }
     if (l.char_decomp == 1) {
         // 1d/sharpclaw/flux1.f90:80-107 (the 2-D flux1.f90 calls rpn2 with a wrong argument list there and cannot run)
-        if (l.ndim != 1 || l.a.mbc != 3 || (l.lim_type != 1 && l.lim_type != 2) || l.a.mcapa > 0 || l.a.src_id != 0) {
-            err = "SharpClaw char_decomp = 1: 1-D, lim_type 1 (tvd2_wave) or 2 (weno5_wave), mbc 3, no capacity function";
+        if (l.ndim != 1 || l.a.mbc != 3 || (l.lim_type != 1 && l.lim_type != 2) || l.fwave || l.a.src_id != 0) {
+            err = "SharpClaw char_decomp = 1: 1-D, lim_type 1 (tvd2_wave) or 2 (weno5_wave), mbc 3, no f-wave solver";
             return PCL_EINVAL;
         }
         if (rp == PCL_RP_ADVECTION_1D) return launch_sharp1w<Advection1D>(l, err);
@@ -491,7 +499,8 @@ int launch_sharp(const SweepLaunch &l, std::string &err) {
         if (rp == PCL_RP_BURGERS_1D) return launch_sharp1w<Burgers1D>(l, err);
         if (rp == PCL_RP_EULER_1D) return launch_sharp1w<Euler1D>(l, err);
         if (rp == PCL_RP_SHALLOW_1D) return launch_sharp1w<Shallow1D>(l, err);
-        err = "SharpClaw char_decomp = 1: Riemann solvers without aux arrays (advection, acoustics, Burgers, Euler, shallow water in 1-D)";
+        if (rp == PCL_RP_ADVECTION_COLOR_1D) return launch_sharp1w<AdvectionColor1D>(l, err);
+        err = "SharpClaw char_decomp = 1: advection, colour equation, acoustics, Burgers, Euler, shallow water in 1-D";
         return PCL_EINVAL;
     }
     if (l.ndim == 1) {
@@ -509,6 +518,7 @@ int launch_sharp(const SweepLaunch &l, std::string &err) {
         if (rp == PCL_RP_VC_ADVECTION_2D) return launch_sharp_t<VcAdvection2D, 1>(l, err);
         if (rp == PCL_RP_SHALLOW_SPHERE_2D) return launch_sharp_t<ShallowSphere, 1>(l, err);
         if (rp == PCL_RP_EULER5_2D) return launch_sharp_t<Euler5, 1, true>(l, err);
+        if (rp == PCL_RP_PSYSTEM_FWAVE_2D) return launch_sharp_t<PSystem2D, 1>(l, err);
     } else {
         if (rp == PCL_RP_ACOUSTICS_2D) return launch_sharp_t<Acoustics2D, 2, true>(l, err);
         if (rp == PCL_RP_ADVECTION_2D) return launch_sharp_t<Advection2D, 2, true>(l, err);
@@ -517,6 +527,7 @@ int launch_sharp(const SweepLaunch &l, std::string &err) {
         if (rp == PCL_RP_VC_ADVECTION_2D) return launch_sharp_t<VcAdvection2D, 2>(l, err);
         if (rp == PCL_RP_SHALLOW_SPHERE_2D) return launch_sharp_t<ShallowSphere, 2>(l, err);
         if (rp == PCL_RP_EULER5_2D) return launch_sharp_t<Euler5, 2, true>(l, err);
+        if (rp == PCL_RP_PSYSTEM_FWAVE_2D) return launch_sharp_t<PSystem2D, 2>(l, err);
     }
     err = "Riemann solver id does not match the grid dimension";
     return PCL_EINVAL;

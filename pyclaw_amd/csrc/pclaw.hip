@@ -721,9 +721,9 @@ int pcl_create(const pcl_config *cfg, pcl_solver **out) {
         // with a wrong argument list on that path, 2d/sharpclaw/flux1.f90:86); 2 and 3 need a user-supplied evec routine
         // the reference only stubs (evec.f90:13-14)
         if (cfg->method[4] != 1) return fail(PCL_EINVAL, "SharpClaw: char_decomp must be 0 or 1 (2, 3 need a user evec routine)");
-        if (cfg->ndim != 1 || cfg->mbc != 3 || (cfg->lim_type != 1 && cfg->lim_type != 2) || cfg->method[5] != 0 || cfg->fwave)
+        if (cfg->ndim != 1 || cfg->mbc != 3 || (cfg->lim_type != 1 && cfg->lim_type != 2) || cfg->fwave)
             return fail(PCL_EINVAL, "SharpClaw char_decomp = 1: 1-D, lim_type 1 (tvd2_wave) or 2 (weno5_wave), weno_order 5, "
-                                    "no capacity function, no f-wave solver");
+                                    "no f-wave solver");
     }
     if (cfg->kind == PCL_KIND_SHARPCLAW && cfg->lim_type == 1 && cfg->meqn > PCL_MAX_WAVES)
         return fail(PCL_EINVAL, "SharpClaw tvd2: mthlim is indexed by component, meqn <= PCL_MAX_WAVES");
@@ -747,7 +747,10 @@ int pcl_create(const pcl_config *cfg, pcl_solver **out) {
         if (cfg->maux < 3) return fail(PCL_EINVAL, "f-wave elasticity solvers need aux(1)=rho, aux(2)=K, aux(3)=stress-law flag");
         if (cfg->rp == PCL_RP_PSYSTEM_FWAVE_2D && cfg->method[2] > 0 && cfg->maux < 4)
             return fail(PCL_EINVAL, "rpt2_psystem reads aux(4) = strain of the neighbouring rows (the app's b4step fills it)");
-        if (cfg->kind == PCL_KIND_SHARPCLAW) return fail(PCL_EINVAL, "f-wave solvers are wired for the classic solvers only");
+        // SharpClaw reads amdq, apdq and s alone (char_decomp 0), so the p-system's f-wave solver serves it as it is; the
+        // 1-D elasticity solver has no rp1 in the SharpClaw oracle (nothing to check a kernel against): classic only
+        if (cfg->kind == PCL_KIND_SHARPCLAW && cfg->rp == PCL_RP_ELASTICITY_FWAVE_1D)
+            return fail(PCL_EINVAL, "elasticity_fwave_1d is wired for the classic solver only");
     } else if (cfg->fwave) {
         return fail(PCL_EINVAL, "cfg.fwave = 1 needs an f-wave Riemann solver (PCL_RP_ELASTICITY_FWAVE_1D, PCL_RP_PSYSTEM_FWAVE_2D)");
     }
@@ -1974,6 +1977,8 @@ static int host_sharp(int ndim, int rp, const double *rp_params, int lim_type, i
     pcl_config c = layer1_config(ndim, rp, rp_params, meqn, mwaves, maux, mbc, mx, my, 0, dx, dy, 0.0);
     c.method[1] = 2; c.method[5] = mcapa; c.method[6] = maux;
     c.kind = PCL_KIND_SHARPCLAW; c.lim_type = lim_type;
+    // clawparams.fwave follows the Riemann solver (sharpclaw.py:269): flux1 / flux2 carry no argument for it
+    c.fwave = rp == PCL_RP_ELASTICITY_FWAVE_1D || rp == PCL_RP_PSYSTEM_FWAVE_2D;
     return layer1_run(c, q, aux, dq, L1_SHARP_DQ, 0, dt, cfl);
 }
 

@@ -415,8 +415,12 @@ __global__ __launch_bounds__(256, CAPA ? 3 : 4) void sharp_kernel(SweepArgs a, i
 // INTERFACE from them: q^-(i-1/2) = qr(i-1) and q^+(i-1/2) = ql(i).  One lane = one cell = the interface on its left:
 // lane l solves (l-1, l), fetches the waves of the interfaces l-2, l-1, l+1, l+2 by DPP shifts, builds qm = qr(l-1) and
 // qp = ql(l), solves the interface problem (qm, qp) and the problem inside the cell (qp, the right lane's qm).  Halo 3
-// like WENO5: lanes 3..60 are stored.  Solvers without aux arrays, no capacity function.  Operation order of
-// oracle/sharpclaw_oracle.c: weno5_wave / tvd2_wave (== the reference's Fortran bit for bit, tests/golden/ref_recon_wave.npz).
+// like WENO5: lanes 3..60 are stored.  Operation order of oracle/sharpclaw_oracle.c: weno5_wave / tvd2_wave (== the
+// reference's Fortran bit for bit, tests/golden/ref_recon_wave.npz).
+// Aux arrays (NAUX > 0): each lane loads its cell's components once; rp1(q, q) and the interface problem see (left
+// lane's aux, own aux), the problem inside the cell (own, own): flux1.f90:173-178 sets auxr(:,i-1) = aux(:,i).
+// Capacity function (CAPA): dtdx = dt/(dx*capa(i)) per cell; the Courant number of interface i takes dtdx(i) for the
+// right-going and dtdx(i-1) (the left lane's, by DPP) for the left-going speeds, the update the cell's own.
 template <int MEQN>
 __device__ __forceinline__ double dot_m(const double (&a)[MEQN], const double (&b)[MEQN]) {
     double d = a[0] * b[0];
@@ -479,10 +483,9 @@ __device__ __forceinline__ double tvd2_wave_limiter(double r, int meth) {
     return 0.0;
 }
 
-template <class RP, int LIM>
+template <class RP, int LIM, bool CAPA>
 __global__ __launch_bounds__(256) void sharp1w_kernel(SweepArgs a, int nstrips) {
-    constexpr int MEQN = RP::MEQN, MWAVES = RP::MWAVES, SH = 3, SS = sstrip(SH);
-    static_assert(RP::NAUX == 0, "wave-based reconstruction: solvers without aux arrays");
+    constexpr int MEQN = RP::MEQN, MWAVES = RP::MWAVES, NAUX = RP::NAUX, SH = 3, SS = sstrip(SH);
     static_assert(LIM == 1 || LIM == 2, "tvd2_wave / weno5_wave");
     using Cell = typename RP::Cell;
     const int lane = threadIdx.x & (WAVE - 1);
@@ -496,8 +499,21 @@ __global__ __launch_bounds__(256) void sharp1w_kernel(SweepArgs a, int nstrips) 
     double q[MEQN];
 #pragma unroll
     for (int m = 0; m < MEQN; m++) q[m] = a.qin[m * a.plane + cc];
+    double auxv[NAUX > 0 ? NAUX : 1], auxl[NAUX > 0 ? NAUX : 1];      // the cell's aux values, the left cell's
+#pragma unroll
+    for (int m = 0; m < NAUX; m++) {
+        auxv[m] = a.aux[aux_idx<RP, 1>(m) * a.plane + cc];
+        auxl[m] = from_left(auxv[m]);
+    }
+    auto precell = [&](const double *qe, const double *ax) {
+        if constexpr (NAUX > 0) return RP::template precell<1>(qe, a.par, ax);
+        else return RP::template precell<1>(qe, a.par);
+    };
+    double dtdx_c = a.dtd;
+    if constexpr (CAPA) dtdx_c = a.dt / (a.dx * a.aux[(long)(a.mcapa - 1) * a.plane + cc]);   // flux1.f90:60
+    const double dtdx_l = CAPA ? from_left(dtdx_c) : dtdx_c;
     // rp1(q1d, q1d): the waves between the cell averages, interface `lane` = (lane-1, lane)
-    const Cell c0 = RP::template precell<1>(q, a.par);
+    const Cell c0 = precell(q, auxv);
     const Cell cm = struct_from_left(c0);
     double w0[MWAVES][MEQN], s0[MWAVES], t_am[MEQN], t_ap[MEQN];
     RP::template solve<1>(cm, c0, a.par, w0, s0, t_am, t_ap);
@@ -551,24 +567,24 @@ __global__ __launch_bounds__(256) void sharp1w_kernel(SweepArgs a, int nstrips) 
         }
     }
     // interface problem (qr(i-1), ql(i)) and the problem inside the cell (ql(i), qr(i)): flux1.f90:125-187
-    const Cell em = RP::template precell<1>(qm, a.par), ep = RP::template precell<1>(qp, a.par);
+    const Cell em = precell(qm, auxl), ep = precell(qp, auxv);
     double wave[MWAVES][MEQN], s[MWAVES], amdq[MEQN], apdq[MEQN], amdq2[MEQN], apdq2[MEQN];
     RP::template solve<1>(em, ep, a.par, wave, s, amdq, apdq);
     double cflmax = 0.0;
     if (cfl_ok) {
 #pragma unroll
-        for (int mw = 0; mw < MWAVES; mw++) cflmax = dmax(dmax(cflmax, a.dtd * s[mw]), -a.dtd * s[mw]);
+        for (int mw = 0; mw < MWAVES; mw++) cflmax = dmax(dmax(cflmax, dtdx_c * s[mw]), -dtdx_l * s[mw]);
     }
     double qmr[MEQN];
 #pragma unroll
     for (int m = 0; m < MEQN; m++) qmr[m] = from_right(qm[m]);          // qr(i) = the right lane's q^-
-    const Cell er = RP::template precell<1>(qmr, a.par);
+    const Cell er = precell(qmr, auxv);                                 // both edge states carry the cell's own aux
     RP::template solve<1>(ep, er, a.par, wave, s, amdq2, apdq2);
     const Recip by_ca(a.rk_op == 1 ? a.rk_ca : 1.0);
 #pragma unroll
     for (int m = 0; m < MEQN; m++) {      // the shift must run with every lane active
         const double amdq_r = from_right(amdq[m]);
-        const double dq = -(a.dtd * (amdq_r + apdq[m] + amdq2[m] + apdq2[m]));
+        const double dq = -(dtdx_c * (amdq_r + apdq[m] + amdq2[m] + apdq2[m]));
         if (owned) {
             const long at = m * a.plane + cc;
             double r = dq;

@@ -12,8 +12,10 @@ reference's numpy expressions do).
 Implemented reconstruction: ``lim_type=2`` with ``weno_order`` 5 .. 17 (the PyWENO-generated ``weno5`` ...
 ``weno17``, float32-rounded literals included; orders above 5 for the 1-D solvers and advection_2d, acoustics_2d,
 euler_5wave_2d) and ``lim_type=3`` (the legacy ``weno5`` of reconstruct.f90,
-the one the reference's golden ``test/ac_sc_solution`` was produced with); ``char_decomp=0``,
-``tfluct_solver=False``.
+the one the reference's golden ``test/ac_sc_solution`` was produced with) and ``lim_type=1`` (tvd2);
+``char_decomp=0``, or ``1`` (wave-based reconstruction) in 1-D with ``lim_type`` 1 or 2; ``tfluct_solver=False``.
+``solver.fwave`` is ``True`` for ``rp_psystem_fwave_2d`` and only for it (``rp_elasticity_fwave_1d`` is a classic-only
+solver).
 """
 import ctypes
 
