@@ -366,6 +366,13 @@ int pcl_tile_ring(pcl_solver *s, int enable);
 /* internal, for the test suite only: how many listed tiles of the last one-kernel step the ring check settled (0 when
  * that step did not run over a list); makes the next step compute every tile */
 int pcl_tile_ring_stats(pcl_solver *s, long *short_path);
+/* Row reuse of the one-kernel step (on by default): an x sweep whose row, halo columns included, holds the same bits as
+ * the row the wavefront swept before it takes that row's result instead of computing it again -- same bits, same
+ * Courant number.  enable = 0: every row is swept.  Solvers without aux arrays and without a capacity function. */
+int pcl_tile_rowreuse(pcl_solver *s, int enable);
+/* internal, for the test suite only: the x sweeps the last one-kernel step of the whole block reused, over the tiles it
+ * computed (0 when none has run); makes the next step compute every tile */
+int pcl_tile_rowreuse_stats(pcl_solver *s, long *sweeps_reused);
 /* hyperbolic steps (classic) / right-hand sides (SharpClaw) attempted since pcl_create, rejected ones included */
 int pcl_step_count(pcl_solver *s, long *steps);
 

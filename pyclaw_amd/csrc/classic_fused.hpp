@@ -259,7 +259,8 @@ __global__ __launch_bounds__(F_THREADS, fused_wgs(fused_planes<RP, CAPA>())) voi
                                                                               double2 *__restrict__ tq_cfl,
                                                                               const int *__restrict__ tq_list,
                                                                               const TileNext *tq_next,
-                                                                              unsigned *__restrict__ tq_ring, unsigned ring_seq) {
+                                                                              unsigned *__restrict__ tq_ring, unsigned ring_seq,
+                                                                              unsigned *__restrict__ tq_reuse, int rowreuse) {
     constexpr int MEQN = RP::MEQN;
     constexpr int NAUX = RP::NAUX, PAUX = MEQN + (CAPA ? 1 : 0), NP = PAUX + NAUX, NX = NP - MEQN;
     static_assert(!SRC || (MEQN == 5 && NX == 0), "fused source: the Euler solver, no capacity function");
@@ -431,16 +432,58 @@ __global__ __launch_bounds__(F_THREADS, fused_wgs(fused_planes<RP, CAPA>())) voi
         const int ca = x0 + cl;
         const bool owned = (ca >= a.mbc) && (ca < a.mbc + a.mx) && cl >= HALO && cl < F_COLS - HALO;
         const bool cfl_ok = (ca >= a.mbc) && (ca <= a.mbc + a.mx) && cl >= 1;
+        // Row reuse: lane_core of an x sweep is a function of the row's q, a.dtd, the column masks owned /
+        // cfl_ok and a -- with F_RX == 1 nothing in it depends on the row -- so a row that holds, in all 64 columns of the
+        // window and all components, the same BITS as the row this wavefront swept before it (64-bit integer compares: -0
+        // is not +0, equal NaN bits are equal) gets the same bits back.  Bit k of `same`: sweep k repeats sweep k - 1
+        // (wave-uniform; the chain runs through reused rows too).  Taken here, in front of the first sweep, while every row
+        // still holds its input; the rows the loop skips trail in the order and take no bit.  The wavefront leaves the
+        // number of sweeps it reuses right away (one byte; wavefront 0 the launch's number), so nothing outlives the pass.
+        unsigned same = 0;
+        if constexpr (NX == 0) {
+            static_assert(F_RX == 1, "row reuse: one row per sweep, the column masks are the same for every row");
+            if (rowreuse) {                           // kernel argument: uniform
+                long long p[MEQN];
+#pragma unroll
+                for (int m = 0; m < MEQN; m++) p[m] = __double_as_longlong(tile[ftile_at(m, wave_row(wv, 0), cl)]);
+#pragma unroll
+                for (int k = 1; k < F_NS; k++) {
+                    bool eq = true;
+#pragma unroll
+                    for (int m = 0; m < MEQN; m++) {
+                        const long long v = __double_as_longlong(tile[ftile_at(m, wave_row(wv, k), cl)]);
+                        eq = eq & (v == p[m]);
+                        p[m] = v;
+                    }
+                    if (__all(eq) && y0 + wave_row(wv, k) < a.J) same |= 1u << k;
+                }
+                if (tq_reuse && lane == 0) {
+                    reinterpret_cast<unsigned char *>(tq_reuse + 2 * tile_id + 1)[wv] = (unsigned char)__popc(same);
+                    if (wv == 0) tq_reuse[2 * tile_id] = ring_seq;
+                }
+            }
+        }
         NoJumpMemo<MEQN> memo;
+        bool nojump = false;                          // of the sweep before (wave-uniform)
 #pragma unroll 1
         for (int k = 0; k < F_NS; k++) {
             const int r0 = wave_row(wv, k), r = r0 + lane / F_COLS;
             if (y0 + r0 >= a.J) continue;             // wave-uniform
+            if (NX == 0 && ((same >> k) & 1u)) {
+                // the row before again: its shortcut, or its result from its LDS row (this lane wrote that cell itself;
+                // halo columns keep their input, as behind a computed sweep).  cflx holds these speeds already.
+                quiet = quiet && nojump;
+                if (owned && !nojump) {
+                    const int rp = wave_row(wv, k - 1);
+#pragma unroll
+                    for (int m = 0; m < MEQN; m++) tile[ftile_at(m, r, cl)] = tile[ftile_at(m, rp, cl)];
+                }
+                continue;
+            }
             double q[MEQN], qn[MEQN];
 #pragma unroll
             for (int m = 0; m < MEQN; m++) q[m] = tile[ftile_at(m, r, cl)];
             // nojump (wave-uniform): the cells go back as they came, nothing to put back
-            bool nojump;
             if constexpr (NX > 0) {
                 // dtdx1d(i) = dtdx / aux(mcapa,i,j) (step2ds.f:95-99) and the solver's aux values, as sweep_kernel's x pass
                 double capa = 1.0, dtdx_c = a.dtd, auxv[NAUX > 0 ? NAUX : 1];

@@ -1758,6 +1758,32 @@ int pcl_tile_ring_stats(pcl_solver *s, long *short_path) {
     return PCL_OK;
 }
 
+// the x sweeps of the one-kernel step that repeat the row before them bit for bit take its result (classic_fused.hpp)
+// on / off; off, every row is swept
+int pcl_tile_rowreuse(pcl_solver *s, int enable) {
+    if (s) s->qt.invalidate();            // quiet tiles: not a read-only call (quiet_tiles.hpp)
+    if (!s) return fail(PCL_EINVAL, "null argument");
+    s->qt.set_rowreuse(enable != 0);
+    return PCL_OK;
+}
+
+// x sweeps the last one-kernel launch of the whole block reused, over the tiles it computed (summed here from the bytes
+// the wavefronts left; a tile the launch skipped, or its ring check settled, holds an older launch's number)
+int pcl_tile_rowreuse_stats(pcl_solver *s, long *sweeps_reused) {
+    if (s) s->qt.invalidate();            // quiet tiles: not a read-only call (quiet_tiles.hpp)
+    if (!s || !sweeps_reused) return fail(PCL_EINVAL, "null argument");
+    *sweeps_reused = 0;
+    if (s->qt.last_launch() == pcl::QuietTiles::NONE) return PCL_OK;
+    std::vector<unsigned> u(2 * (size_t)s->qt.ntx * s->qt.nty);
+    HIP_TRY(hipSetDevice(s->cfg.device));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    HIP_TRY(hipMemcpy(u.data(), s->qt.reuse_counts(), u.size() * sizeof(unsigned), hipMemcpyDeviceToHost));
+    for (size_t t = 0; t < u.size(); t += 2)
+        if (u[t] == s->qt.ring_number())
+            for (int w = 0; w < 4; w++) *sweeps_reused += (u[t + 1] >> (8 * w)) & 0xffu;
+    return PCL_OK;
+}
+
 int pcl_tile_words(pcl_solver *s, unsigned *host, int *ntx, int *nty) {
     if (s) s->qt.invalidate();            // quiet tiles: not a read-only call (quiet_tiles.hpp)
     if (!s || !ntx || !nty) return fail(PCL_EINVAL, "null argument");

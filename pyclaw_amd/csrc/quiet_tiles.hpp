@@ -2,14 +2,16 @@
 // the kernels: classic_fused.hpp, the proofs: DESIGN.md 4.1a).
 //
 // Device memory: three word arrays W[0..2] (one 32-bit word per tile), the per-wavefront Courant maxima C, the tile
-// list L, the ring marks R (one 32-bit word per tile) and three TileNext blocks N[0..2].  Two counters rotate them: c
+// list L, the ring marks R (one 32-bit word per tile), the row-reuse counts U (two words per tile: the launch's number and
+// one byte per wavefront) and three TileNext blocks N[0..2].  Two counters rotate them: c
 // (words) advances with every booked launch, x (blocks) with every hand-over that built a list; r numbers the booked
 // launches.  With c and x taken in front of launch n (indices modulo 3):
 //
 //                                  reads                       writes                            then
 //   launch n        plan()         L, N[x+2] if it skips       W[c+1], C (computed tiles),       c += 1, r += 1
 //                                                              R := r (tiles its ring check
-//                                                              settled, classic_fused.hpp)
+//                                                              settled, classic_fused.hpp),
+//                                                              U (computed tiles: r and the counts)
 //   hand-over n     handover()     W[c+1], C, N[x+2] if        W[c+2] (tiles n + 1 skips), L,    x += 1
 //                                  launch n ran over a list    N[x] filled, N[x+1] zeroed,
 //                                  (its na + nq)               host word [2] (tiles launch n ran)
@@ -17,6 +19,7 @@
 //   a hook between                 W[c]   (words_read)         nothing
 //                                  N[x+2] (ran_over)
 //                                  R      (ring_marks: the words equal to r)
+//                                  U      (reuse_counts: the tiles whose first word equals r)
 //
 // Host word [2] (next to the Courant number [0] and the sequence number [1]) is read by the form-trial gate of
 // step_hyperbolic (pclaw.hip) while list_count_current() holds: no read-back, no wait.
@@ -76,6 +79,8 @@ public:
         if (e == hipSuccess) e = hipMalloc((void **)&list, nt * sizeof(int));
         if (e == hipSuccess) e = hipMalloc((void **)&ring, nt * sizeof(unsigned));
         if (e == hipSuccess) e = hipMemsetAsync(ring, 0, nt * sizeof(unsigned), stream);
+        if (e == hipSuccess) e = hipMalloc((void **)&reuse, 2 * nt * sizeof(unsigned));
+        if (e == hipSuccess) e = hipMemsetAsync(reuse, 0, 2 * nt * sizeof(unsigned), stream);
         if (e == hipSuccess) e = hipMalloc((void **)&next, 3 * sizeof(TileNext));
         if (e == hipSuccess) e = hipMemsetAsync(next, 0, 3 * sizeof(TileNext), stream);
         return e;
@@ -86,6 +91,7 @@ public:
         if (cfl) hipFree(cfl);
         if (list) hipFree(list);
         if (ring) hipFree(ring);
+        if (reuse) hipFree(reuse);
         if (next) hipFree(next);
     }
 
@@ -93,12 +99,16 @@ public:
     bool take_valid() { const bool v = valid; valid = false; return v; }
     void set_enabled(bool on) { enabled = on; }
     void set_ring(bool on) { ring_on = on; }
+    void set_rowreuse(bool on) { reuse_on = on; }
 
     // In front of a one-kernel launch qin -> qout: fills l.tq_* and returns true if the launch is booked (`whole`: the
-    // whole undecomposed block).  Every flag is cleared; launched() sets them again.
+    // whole undecomposed block).  Every flag is cleared; launched() sets them again.  The row-reuse switch goes to every
+    // launch, booked or not (tile subsets of a decomposed block: the same kernel); its counts only to a booked one.
     bool plan(SweepLaunch &l, const double *qin, const double *qout, const Key &key, double dt, bool whole, bool carry) {
         const bool book = whole && words[0];
+        l.rowreuse = reuse_on ? 1 : 0;
         if (book) {
+            l.tq_reuse = reuse;
             l.tq_out = written_next();
             l.tq_cfl = cfl;
             if (++ring_seq == 0) ring_seq = 1;          // 0 is what create() left in R
@@ -159,6 +169,8 @@ public:
     const TileNext *ran_over() const { return stat; }                   // the block of that list (last_launch() == LIST)
     const unsigned *ring_marks() const { return ring; }                 // a tile its ring check settled holds ring_number()
     unsigned ring_number() const { return ring_seq; }
+    const unsigned *reuse_counts() const { return reuse; }              // per tile: the number of the launch that computed it
+                                                                        // last, then its x sweeps reused, a byte per wavefront
     // The last launch ran over a list and the launch to come would run over the next one (carry: QuietTiles::take_valid
     // at the step's entry point): the count its hand-over left in host memory describes the state as it is now.
     bool list_count_current(bool carry) const { return carry && last == LIST && listed; }
@@ -174,6 +186,8 @@ private:
     unsigned *ring = nullptr;
     unsigned ring_seq = 0;              // the number of the last booked launch
     bool ring_on = true;                // pcl_tile_ring
+    unsigned *reuse = nullptr;
+    bool reuse_on = true;               // pcl_tile_rowreuse
     bool valid = false, hand = false, listed = false;
     Last last = NONE;
     const double *last_in = nullptr, *last_out = nullptr;

@@ -169,6 +169,11 @@ struct SweepLaunch {
     // this launch, in its word of tq_ring (pcl_tile_ring_stats)
     unsigned *tq_ring = nullptr;
     unsigned ring_seq = 0;
+    // row reuse of the x sweeps (classic_fused.hpp; 0: off).  tq_reuse (null: not counted): two words per tile, a computed
+    // tile leaves ring_seq in the first and its wavefronts their reused sweeps in the bytes of the second
+    // (pcl_tile_rowreuse_stats)
+    int rowreuse = 1;
+    unsigned *tq_reuse = nullptr;
 };
 
 // The Courant hand-over behind a one-kernel launch of the whole block, with the next launch's tile list
