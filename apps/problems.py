@@ -93,6 +93,36 @@ def dq_euler_radial(solver, state, dt):
     return dq
 
 
+# The two callbacks above for ONE cell, as cell-function bodies (pyclaw.CellSource / pyclaw.CellDqSource): the same
+# expressions in the same order, so that the 'exact' arithmetic gives the same bits.  p[0] = gamma1, p[1] = ndim.
+EULER_RAD_CELL_SRC = """
+const double gamma1 = p[0], ndm1 = p[1] - 1.0, dt = c.dt, dt2 = dt / 2., rad = aux[0];
+double rho = q[0], u = q[1] / rho, v = q[2] / rho;
+double press = gamma1 * (q[3] - 0.5 * rho * (u * u + v * v));
+const double s0 = q[0] - dt2 * ndm1 / rad * q[2];
+const double s1 = q[1] - dt2 * ndm1 / rad * rho * u * v;
+const double s2 = q[2] - dt2 * ndm1 / rad * rho * v * v;
+const double s3 = q[3] - dt2 * ndm1 / rad * v * (q[3] + press);
+rho = s0; u = s1 / rho; v = s2 / rho;
+press = gamma1 * (s3 - 0.5 * rho * (u * u + v * v));
+q[0] = q[0] - dt * ndm1 / rad * s2;
+q[1] = q[1] - dt * ndm1 / rad * rho * u * v;
+q[2] = q[2] - dt * ndm1 / rad * rho * v * v;
+q[3] = q[3] - dt * ndm1 / rad * v * (s3 + press);
+"""
+
+DQ_EULER_RAD_CELL_SRC = """
+const double gamma1 = p[0], ndm1 = p[1] - 1.0, dt = c.dt, rad = aux[0];
+const double rho = q[0], u = q[1] / rho, v = q[2] / rho;
+const double press = gamma1 * (q[3] - 0.5 * rho * (u * u + v * v));
+dq[0] = -dt * ndm1 / rad * q[2];
+dq[1] = -dt * ndm1 / rad * rho * u * v;
+dq[2] = -dt * ndm1 / rad * rho * v * v;
+dq[3] = -dt * ndm1 / rad * v * (q[3] + press);
+dq[4] = 0;
+"""
+
+
 def shockbubble(pyclaw, mx=160, my=40, tfinal=0.2, device_callbacks=False, with_src=True,
                 dim_split=True, order_trans=2, dt_initial=0.005, nout=1, run=True, math='exact',
                 solver_type='classic', time_integrator='SSP104'):

@@ -2,16 +2,21 @@
 The p-system in a two-material checkerboard (the reference's apps/psystem set-up): strain eps and momenta (rho u, rho v),
     eps_t - u_x - v_y = 0,   (rho u)_t - sigma(eps, x, y)_x = 0,   (rho v)_t - sigma(eps, x, y)_y = 0,
 solved with the f-wave Riemann solver ``rp_psystem_fwave_2d`` (``solver.fwave = True``) by the classic dimension-split
-step or by SharpClaw (WENO5, SSP104).  aux = (density, modulus K, stress-law flag, strain copy): flag 1 is the linear
-law sigma = K eps, anything else sigma = exp(K eps) - 1.  The medium does not change in time and neither solver here
-needs the strain copy of aux(4) (only the transverse solver of the unsplit classic step reads it), so there is no
-before-step hook.
+step, by the unsplit classic step or by SharpClaw (WENO5, SSP104).  aux = (density, modulus K, stress-law flag, strain
+copy): flag 1 is the linear law sigma = K eps, anything else sigma = exp(K eps) - 1.  The medium does not change in
+time.  Only the transverse solver of the unsplit classic step reads the strain copy of aux(4), which has to follow the
+strain: ``solver_type='classic_unsplit'`` refreshes it before every step with a start_step cell function that writes
+aux on the device (the reference app's b4step); the other two solver types need no before-step hook.
 """
 import numpy as np
 
 # the two materials (density, modulus) and the period of the pattern in x and y; each tile is half a period wide
 MATERIALS = ((1.0, 1.0), (4.0, 4.0))
 PERIOD = (1.0, 1.0)
+
+
+# before every step of the unsplit classic solver: aux(4) = strain
+STRAIN_COPY = "aux[3] = q[0];"
 
 
 def checkerboard(xc, yc, linearity=2):
@@ -47,6 +52,13 @@ def psystem2D(pyclaw, mx=200, my=200, solver_type='classic', lower=(0.25, 0.25),
     if solver_type == 'classic':
         solver = pyclaw.ClawSolver2D()
         solver.dim_split = True                       # no transverse solver: aux(4) is never read
+        solver.limiters = pyclaw.limiters.tvd.superbee
+        solver.cfl_max, solver.cfl_desired = 0.9, 0.8
+    elif solver_type == 'classic_unsplit':
+        solver = pyclaw.ClawSolver2D()
+        solver.dim_split = False
+        solver.order_trans = 2                        # rpt2_psystem reads aux(4) = strain of the neighbouring rows
+        solver.start_step = pyclaw.CellStartStep(STRAIN_COPY, writes_aux=True)
         solver.limiters = pyclaw.limiters.tvd.superbee
         solver.cfl_max, solver.cfl_desired = 0.9, 0.8
     else:

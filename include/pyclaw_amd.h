@@ -217,6 +217,8 @@ void pcl_destroy(pcl_solver *s);
 int pcl_put_q(pcl_solver *s, const double *host, int with_ghosts);
 int pcl_get_q(pcl_solver *s, double *host, int with_ghosts);
 int pcl_put_aux(pcl_solver *s, const double *host_auxbc); /* always with ghosts (auxbc)   */
+int pcl_get_aux(pcl_solver *s, double *host_auxbc);       /* its twin: the resident aux, ghosts included (a start_step
+                                                           * cell function may have written it, see below)        */
 
 /* Ghost fill of one side of one dimension on the device: solver.py:384-452.
  * side 0 = lower, 1 = upper.  PCL_BC_CUSTOM is not accepted here: use the strip calls
@@ -278,6 +280,47 @@ int pcl_src(pcl_solver *s, int src_id, double dt, const double *params, int npar
  * pcl_src: same arithmetic, same bits.  src_id = PCL_SRC_EULER_RADIAL with params {gamma1, ndim}, or 0 to switch it
  * off.  A rejected step discards the pass' output with the rest (pcl_undo_step), as step() returns before the source. */
 int pcl_fuse_source(pcl_solver *s, int src_id, const double *params, int nparams);
+
+/* ---- cell functions: user-written per-cell arithmetic on the resident arrays ----------------------------------
+ * The reference's step_src / dq_src / start_step callbacks are arbitrary numpy code on host arrays.  A cell function is
+ * the same arithmetic for ONE cell, given as the text of a C++ function body; the library compiles it at run time
+ * (libhiprtc, opened on first use; the architecture this library was built for, no device needed) into a wrapper kernel
+ * that runs it over the interior cells of the resident arrays: one read and one write of the components it assigns,
+ * ghost cells never touched.  The body sees
+ *     q[MEQN]      the cell's state (const for a dq_src)          aux[MAUX]   const unless compiled with writes_aux
+ *     dq[MEQN]     dq_src only: zero on entry, afterwards deltaq = deltaq + dq[m] (sharpclaw.py:232-235)
+ *     c.t, c.dt    time and step length                            p[16]       the parameters of this launch
+ *     c.i[NDIM]    GLOBAL 0-based interior indices                 c.d[NDIM]   cell sizes
+ *     c.x[NDIM]    cell centre, lower + (i + 0.5) * d with the global i (grid.py)
+ * and whatever `preamble` (helper functions, file scope) declares.  Diagnostics carry the body's own line numbers behind
+ * the kind's name ("step_src:2:...").  math: PCL_MATH_EXACT / _STRICT compile without FMA contraction and with IEEE
+ * division and square root, like the library's own source kernels; PCL_MATH_FAST allows contraction. */
+#define PCL_CELLFN_STEP_SRC 1
+#define PCL_CELLFN_DQ_SRC 2
+#define PCL_CELLFN_START_STEP 3
+#define PCL_CELLFN_MAX_PARAMS 16
+typedef struct pcl_cellfn pcl_cellfn;
+/* Compile (host only, no device needed).  Functions are cached per process by (kind, body, preamble, meqn, maux, ndim,
+ * math, writes_aux): compiling the same text again returns the cached handle with one more reference.  *code_size (may
+ * be NULL) = bytes of the code object.  A compile error is PCL_EINVAL with the compiler's log in pcl_last_error().
+ * writes_aux: aux[] is writable in the body (PCL_CELLFN_START_STEP only, maux > 0). */
+int pcl_cellfn_compile(int kind, const char *body, const char *preamble, int meqn, int maux, int ndim, int math,
+                       int writes_aux, pcl_cellfn **out, long *code_size);
+int pcl_cellfn_release(pcl_cellfn *f);          /* drops one reference; the compiled function stays cached for
+                                                 * the life of the process (host memory: its code object) */
+/* compiles done and cache hits of this process */
+int pcl_cellfn_stats(long *compiles, long *cache_hits);
+/* Host-only argument check of pcl_cellfn_apply: the handle is live and was compiled for these shape constants. */
+int pcl_cellfn_check(const pcl_cellfn *f, int meqn, int maux, int ndim);
+/* Where the handle's block sits in the global grid: lower[ndim] = lower edge of the GLOBAL grid, nstart[ndim] = global
+ * index of the block's first interior cell (both 0 until set). */
+int pcl_cellfn_geometry(pcl_solver *s, const double *lower, const int *nstart);
+/* One launch on the solver's stream over the interior cells of the SELECTED register (pcl_select); a dq_src reads the
+ * selected register and adds into PCL_REG_DQ.  params[nparams <= 16] travel by value with the launch.  Like pcl_src it
+ * makes the next one-kernel step compute every tile and the next step exchange its halo again.  The module is loaded
+ * into the handle's device on first use and unloaded by pcl_destroy.  After a function that wrote aux the caller
+ * refreshes the aux ghost cells: pcl_halo_exchange_aux, then pcl_bc_aux per dimension and side. */
+int pcl_cellfn_apply(pcl_solver *s, pcl_cellfn *f, double t, double dt, const double *params, int nparams);
 
 /* ---- SharpClaw (kind = PCL_KIND_SHARPCLAW) ----------------------------------------------------- */
 /* Which register the put/get/bc/strip/halo calls act on (default PCL_REG_Q): the RK stages get

@@ -72,6 +72,7 @@ PROTOTYPES = {
     "pcl_put_q": (C.c_int, [C.c_void_p, dp, C.c_int]),
     "pcl_get_q": (C.c_int, [C.c_void_p, dp, C.c_int]),
     "pcl_put_aux": (C.c_int, [C.c_void_p, dp]),
+    "pcl_get_aux": (C.c_int, [C.c_void_p, dp]),
     "pcl_bc": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "pcl_bc_const": (C.c_int, [C.c_void_p, C.c_int, C.c_int, dp]),
     "pcl_bc_aux": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
@@ -87,6 +88,13 @@ PROTOTYPES = {
     "pcl_restore": (C.c_int, [C.c_void_p]),
     "pcl_src": (C.c_int, [C.c_void_p, C.c_int, C.c_double, dp, C.c_int]),
     "pcl_fuse_source": (C.c_int, [C.c_void_p, C.c_int, dp, C.c_int]),
+    "pcl_cellfn_compile": (C.c_int, [C.c_int, C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                     C.POINTER(C.c_void_p), C.POINTER(C.c_long)]),
+    "pcl_cellfn_release": (C.c_int, [C.c_void_p]),
+    "pcl_cellfn_stats": (C.c_int, [C.POINTER(C.c_long), C.POINTER(C.c_long)]),
+    "pcl_cellfn_check": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    "pcl_cellfn_geometry": (C.c_int, [C.c_void_p, dp, ip]),
+    "pcl_cellfn_apply": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_double, dp, C.c_int]),
     "pcl_select": (C.c_int, [C.c_void_p, C.c_int]),
     "pcl_sharp_fuse_dq_src": (C.c_int, [C.c_void_p, C.c_int, dp, C.c_int]),
     "pcl_sharp_dq": (C.c_int, [C.c_void_p, C.c_double, dp]),

@@ -12,14 +12,15 @@ unchanged; 'Python' (the reference's pure-numpy 1-D kernel) is not provided.
 import numpy as np
 
 from . import _lib, riemann
-from .solver import Solver
+from .solver import CellFunction, CellStartStep, Solver
 
 
 class DeviceSource(object):
     """A source-term step (``solver.step_src``) that libpyclaw_amd applies on the device.
 
     A plain Python ``step_src(solver,state,dt)`` still works, but forces a device->host->device
-    round trip of q per call (arbitrary numpy code cannot run on the GPU)."""
+    round trip of q per call (arbitrary numpy code cannot run on the GPU); ``CellSource`` takes the same per-cell
+    arithmetic as a few lines of C++ and runs it on the resident state."""
 
     def apply(self, solver, state, dt):
         raise NotImplementedError
@@ -44,6 +45,24 @@ class SphereCoriolisSource(DeviceSource):
 
     def apply(self, solver, state, dt):
         _lib.check(_lib.lib().pcl_src(solver._h, 2, dt, None, 0))
+
+
+class CellSource(CellFunction, DeviceSource):
+    """A source-term step (``solver.step_src``) as a cell function (see ``CellFunction``): the body updates ``q[MEQN]``
+    in place over ``c.dt``, the dt the Python ``step_src(solver, state, dt)`` would receive (half the step under Strang
+    splitting).
+
+    A cell source is never fused into the last pass of the hyperbolic step: it is one launch of its own and costs one
+    read and one write of the q components it assigns (and of nothing else).  Like any unfused source it keeps
+    exchange-ahead off in a decomposed run."""
+
+    kind = 1
+
+    def __init__(self, body, params=(), preamble=""):
+        CellFunction.__init__(self, body, params, preamble)
+
+    def apply(self, solver, state, dt):
+        self.launch(solver, state.t, dt)
 
 
 class ClawSolver(Solver):
@@ -81,7 +100,9 @@ class ClawSolver(Solver):
         state = solution.states[0]
         if self._fuse_key != (id(self.step_src), self.src_split):      # changed after setup(): decide again
             self._decide_src_fusion(state)
-        if self.start_step is not None:
+        if isinstance(self.start_step, CellStartStep):
+            self.start_step.apply(self, state)        # on the resident state, no round trip
+        elif self.start_step is not None:
             self._pull(state)
             self.start_step(self, solution)
             self._push(state)
@@ -240,6 +261,7 @@ class ClawSolver(Solver):
         self.allocate_bc_arrays(state)
         self._setup_halo(state)
         self._upload_aux(state)
+        self._setup_cell_functions(state)
         self._rp_id = rp.id
         self._src_fused = False          # a fresh device handle
         self._decide_src_fusion(state)

@@ -1,0 +1,289 @@
+// cellfn.hpp -- user-written cell functions: a C++ function body given as text, compiled at run time for the library's
+// architecture and launched as one pointwise pass over the interior cells of the resident arrays (step_src, dq_src and
+// start_step of the Python drivers).
+//
+// The wrapper kernel below is kept as text.  The user's preamble and body are spliced into it, MEQN / MAUX / NDIM and
+// the kind arrive as -D constants (q[MEQN] and aux[MAUX] unroll into registers), and hiprtc compiles the whole for
+// PCL_ARCH without asking any device.  One lane = one interior cell, x fastest, 256 threads per workgroup; ghost cells
+// are never read or written.  A component is stored only where its bits differ from the bits that were loaded: for a
+// component the body never assigns the comparison folds at compile time, and the store and then the load disappear
+// from the code object (the built-in source kernels leave such planes alone in the same way).
+//
+// libhiprtc is dlopen()ed on first use, like librccl in halo.hpp: a library without it loads and runs every other path.
+#pragma once
+#include <dlfcn.h>
+#include <hip/hip_runtime.h>
+#include <hip/hiprtc.h>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <map>
+#include <mutex>
+#include <string>
+#include <vector>
+
+#ifndef PCL_ARCH
+#define PCL_ARCH "gfx950"
+#endif
+
+#define PCL_CELLFN_MAX_PARAMS 16
+
+// by-value argument of the wrapper kernel; the text below declares the same struct for the device compile
+struct pcl_cell_args {
+    double *q;          // the selected register
+    double *dq;         // dq_src: the increment register
+    double *aux;
+    long pitch, plane, slab;        // doubles between rows, components and (3-D) k-planes
+    int n[3];           // interior cells of this block
+    int mbc;
+    int nstart[3];      // global index of this block's first interior cell
+    int pad_;
+    double lower[3], d[3];
+    double t, dt;
+    double p[PCL_CELLFN_MAX_PARAMS];
+};
+
+namespace pcl {
+
+static const char *const kCellfnHead = R"PCLSRC(
+struct pcl_cell {
+    double t, dt;
+    int i[NDIM];
+    double x[NDIM];
+    double d[NDIM];
+};
+struct pcl_cell_args {
+    double *q;
+    double *dq;
+    double *aux;
+    long pitch, plane, slab;
+    int n[3];
+    int mbc;
+    int nstart[3];
+    int pad_;
+    double lower[3], d[3];
+    double t, dt;
+    double p[16];
+};
+#define PCL_MAUXN (MAUX > 0 ? MAUX : 1)
+#if KIND == 2
+#define PCL_Q_QUAL const
+#else
+#define PCL_Q_QUAL
+#endif
+#if WRITES_AUX
+#define PCL_AUX_QUAL
+#else
+#define PCL_AUX_QUAL const
+#endif
+)PCLSRC";
+
+// between preamble and body
+static const char *const kCellfnOpen = R"PCLSRC(
+__device__ __forceinline__ void pcl_cell_body(PCL_Q_QUAL double (&q)[MEQN], double (&dq)[MEQN],
+                                              PCL_AUX_QUAL double (&aux)[PCL_MAUXN], const pcl_cell &c,
+                                              const double (&p)[16]) {
+)PCLSRC";
+
+static const char *const kCellfnTail = R"PCLSRC(
+}
+#line 1 "pcl_cellfn_wrapper"
+__device__ __forceinline__ bool pcl_bits_differ(double a, double b) {
+    return __builtin_bit_cast(unsigned long long, a) != __builtin_bit_cast(unsigned long long, b);
+}
+extern "C" __global__ void __launch_bounds__(256) pcl_cellfn(const pcl_cell_args a) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= a.n[0]) return;
+    const int j = NDIM > 1 ? (int)blockIdx.y : 0, k = NDIM > 2 ? (int)blockIdx.z : 0;
+    long g = i + a.mbc;
+    if (NDIM > 1) g += (long)(j + a.mbc) * a.pitch;
+    if (NDIM > 2) g += (long)(k + a.mbc) * a.slab;
+    pcl_cell c;
+    c.t = a.t;
+    c.dt = a.dt;
+    const int loc[3] = {i, j, k};
+    for (int n = 0; n < NDIM; n++) {
+        c.i[n] = loc[n] + a.nstart[n];
+        c.d[n] = a.d[n];
+        c.x[n] = a.lower[n] + (c.i[n] + 0.5) * a.d[n];
+    }
+    double q0[MEQN], q[MEQN], dq[MEQN], aux0[PCL_MAUXN], aux[PCL_MAUXN];
+    for (int m = 0; m < MEQN; m++) { q0[m] = a.q[m * a.plane + g]; q[m] = q0[m]; dq[m] = 0.0; }
+    for (int m = 0; m < PCL_MAUXN; m++) { aux0[m] = MAUX > 0 ? a.aux[m * a.plane + g] : 0.0; aux[m] = aux0[m]; }
+    pcl_cell_body(q, dq, aux, c, a.p);
+#if KIND == 2
+    for (int m = 0; m < MEQN; m++) {
+        const double old = a.dq[m * a.plane + g];
+        const double now = old + dq[m];
+        if (pcl_bits_differ(now, old)) a.dq[m * a.plane + g] = now;
+    }
+#else
+    for (int m = 0; m < MEQN; m++)
+        if (pcl_bits_differ(q[m], q0[m])) a.q[m * a.plane + g] = q[m];
+#endif
+#if WRITES_AUX
+    for (int m = 0; m < MAUX; m++)
+        if (pcl_bits_differ(aux[m], aux0[m])) a.aux[m * a.plane + g] = aux[m];
+#endif
+}
+)PCLSRC";
+
+static inline const char *cellfn_kind_name(int kind) {
+    return kind == 1 ? "step_src" : kind == 2 ? "dq_src" : kind == 3 ? "start_step" : nullptr;
+}
+
+// ---- libhiprtc, loaded on first use ---------------------------------------------------------------------------
+struct HiprtcApi {
+    bool ok = false;
+    decltype(&hiprtcCreateProgram) hiprtcCreateProgram = nullptr;
+    decltype(&hiprtcCompileProgram) hiprtcCompileProgram = nullptr;
+    decltype(&hiprtcGetProgramLogSize) hiprtcGetProgramLogSize = nullptr;
+    decltype(&hiprtcGetProgramLog) hiprtcGetProgramLog = nullptr;
+    decltype(&hiprtcGetCodeSize) hiprtcGetCodeSize = nullptr;
+    decltype(&hiprtcGetCode) hiprtcGetCode = nullptr;
+    decltype(&hiprtcDestroyProgram) hiprtcDestroyProgram = nullptr;
+    decltype(&hiprtcGetErrorString) hiprtcGetErrorString = nullptr;
+};
+static inline HiprtcApi &hiprtc_api() {
+    static HiprtcApi a;
+    return a;
+}
+
+// PCL_HIPRTC_LIB names the one file to open instead (a private ROCm tree; tests point it at a file that does not
+// exist).  Otherwise: the versioned sonames, the plain name, then the lib directory the HIP runtime itself was loaded from.
+static inline int hiprtc_load(std::string &err) {
+    HiprtcApi &a = hiprtc_api();
+    if (a.ok) return 0;
+    void *h = nullptr;
+    std::string tried;
+    auto open = [&](const std::string &name) {
+        if (h) return;
+        h = dlopen(name.c_str(), RTLD_NOW | RTLD_LOCAL);
+        if (!h) tried += (tried.empty() ? "" : "; ") + std::string(dlerror());
+    };
+    if (const char *over = getenv("PCL_HIPRTC_LIB")) {
+        open(over);
+    } else {
+        open("libhiprtc.so.7");
+        open("libhiprtc.so.6");
+        open("libhiprtc.so");
+        Dl_info info;
+        if (!h && dladdr((void *)&hipGetDeviceCount, &info) && info.dli_fname) {
+            std::string dir(info.dli_fname);
+            const size_t slash = dir.rfind('/');
+            if (slash != std::string::npos) open(dir.substr(0, slash + 1) + "libhiprtc.so");
+        }
+    }
+    if (!h) { err = "cell functions need libhiprtc, which could not be opened: " + tried; return -1; }
+#define PCL_SYM(name)                                                      \
+    a.name = (decltype(a.name))dlsym(h, #name);                            \
+    if (!a.name) { err = "libhiprtc lacks " #name; return -1; }
+    PCL_SYM(hiprtcCreateProgram) PCL_SYM(hiprtcCompileProgram) PCL_SYM(hiprtcGetProgramLogSize)
+    PCL_SYM(hiprtcGetProgramLog) PCL_SYM(hiprtcGetCodeSize) PCL_SYM(hiprtcGetCode) PCL_SYM(hiprtcDestroyProgram)
+    PCL_SYM(hiprtcGetErrorString)
+#undef PCL_SYM
+    a.ok = true;
+    return 0;
+}
+
+}  // namespace pcl
+
+// ---- compiled functions, cached per process --------------------------------------------------------------------
+struct pcl_cellfn {
+    long id = 0;                // never reused: the solvers' loaded modules are keyed by it
+    int kind = 0, meqn = 0, maux = 0, ndim = 0, math = 0, writes_aux = 0;
+    int refs = 0;
+    std::string key;
+    std::vector<char> code;     // the code object
+};
+
+namespace pcl {
+
+// No destructor work that touches HIP: the cache holds host memory only (the modules loaded from it belong to the
+// solver handles and are unloaded by pcl_destroy).
+struct CellfnCache {
+    std::mutex mu;
+    std::map<std::string, pcl_cellfn *> by_key;
+    std::map<const pcl_cellfn *, long> live;
+    long next_id = 1, compiles = 0, hits = 0;
+};
+static inline CellfnCache &cellfn_cache() {
+    static CellfnCache *c = new CellfnCache();     // never destroyed: handles may outlive static destruction order
+    return *c;
+}
+
+static inline std::string cellfn_key(int kind, const char *body, const char *preamble, int meqn, int maux, int ndim, int math,
+                                     int writes_aux) {
+    std::string k = std::to_string(kind) + "," + std::to_string(meqn) + "," + std::to_string(maux) + "," +
+                    std::to_string(ndim) + "," + std::to_string(math) + "," + std::to_string(writes_aux) + ",";
+    k += std::to_string(strlen(preamble)) + ":";
+    k += preamble;
+    k += body;
+    return k;
+}
+
+// hiprtc compile of head + preamble + body + tail; math: 0 exact, 1 fast, 2 strict.  0 = ok, else err holds the log
+static inline int cellfn_build(int kind, const char *body, const char *preamble, int meqn, int maux, int ndim, int math,
+                               int writes_aux, std::vector<char> &code, std::string &err) {
+    if (hiprtc_load(err)) return -1;
+    HiprtcApi &a = hiprtc_api();
+    const char *kname = cellfn_kind_name(kind);
+    std::string src = kCellfnHead;
+    src += "#line 1 \"preamble\"\n";
+    src += preamble;
+    src += "\n#line 1 \"pcl_cellfn_wrapper\"\n";
+    src += kCellfnOpen;
+    src += std::string("#line 1 \"") + kname + "\"\n";
+    src += body;
+    src += "\n";
+    src += kCellfnTail;
+    hiprtcProgram prog = nullptr;
+    hiprtcResult r = a.hiprtcCreateProgram(&prog, src.c_str(), "pcl_cellfn.hip", 0, nullptr, nullptr);
+    if (r != HIPRTC_SUCCESS) { err = std::string("hiprtcCreateProgram: ") + a.hiprtcGetErrorString(r); return -1; }
+    // exact / strict: what pclaw.hip itself is built with (no contraction; / and sqrt are IEEE either way)
+    const std::string d_meqn = "-DMEQN=" + std::to_string(meqn), d_maux = "-DMAUX=" + std::to_string(maux),
+                      d_ndim = "-DNDIM=" + std::to_string(ndim), d_kind = "-DKIND=" + std::to_string(kind),
+                      d_waux = "-DWRITES_AUX=" + std::to_string(writes_aux ? 1 : 0);
+    const char *opts[] = {"--offload-arch=" PCL_ARCH, "-O3", "-std=c++17",
+                          math == 1 ? "-ffp-contract=fast" : "-ffp-contract=off",
+                          d_meqn.c_str(), d_maux.c_str(), d_ndim.c_str(), d_kind.c_str(), d_waux.c_str()};
+    r = a.hiprtcCompileProgram(prog, (int)(sizeof(opts) / sizeof(opts[0])), opts);
+    if (r != HIPRTC_SUCCESS) {
+        size_t n = 0;
+        std::string log;
+        if (a.hiprtcGetProgramLogSize(prog, &n) == HIPRTC_SUCCESS && n > 1) {
+            log.resize(n);
+            a.hiprtcGetProgramLog(prog, &log[0]);
+            while (!log.empty() && (log.back() == '\0' || log.back() == '\n')) log.pop_back();
+        }
+        err = std::string("cell function (") + kname + ") does not compile: " + a.hiprtcGetErrorString(r) + "\n" + log;
+        a.hiprtcDestroyProgram(&prog);
+        return -1;
+    }
+    size_t size = 0;
+    r = a.hiprtcGetCodeSize(prog, &size);
+    if (r == HIPRTC_SUCCESS && size > 0) {
+        code.resize(size);
+        r = a.hiprtcGetCode(prog, code.data());
+    }
+    a.hiprtcDestroyProgram(&prog);
+    if (r != HIPRTC_SUCCESS || size == 0) { err = std::string("hiprtcGetCode: ") + a.hiprtcGetErrorString(r); return -1; }
+    if (const char *dir = getenv("PCL_CELLFN_DUMP")) {     // diagnostics: keep the code object for a disassembler
+        static int seq = 0;
+        const std::string path = std::string(dir) + "/" + kname + "_" + std::to_string(seq++) + ".co";
+        if (FILE *fp = fopen(path.c_str(), "wb")) { fwrite(code.data(), 1, code.size(), fp); fclose(fp); }
+    }
+    return 0;
+}
+
+// the modules one solver handle has loaded, by function id; unloaded by pcl_destroy, never by a static destructor
+struct CellfnModules {
+    struct Loaded { hipModule_t mod; hipFunction_t fn; };
+    std::map<long, Loaded> by_id;
+    void unload_all() {
+        for (auto &kv : by_id) (void)hipModuleUnload(kv.second.mod);
+        by_id.clear();
+    }
+};
+
+}  // namespace pcl

@@ -17,6 +17,7 @@
 #include "ghost_rule.hpp"
 #include "halo.hpp"
 #include "quiet_tiles.hpp"
+#include "cellfn.hpp"
 
 namespace {
 
@@ -101,6 +102,11 @@ struct pcl_solver {
     void ghosts_drop(const double *buf) { for (auto &g : ghost_ok) if (g == buf) g = nullptr; }
     void ghosts_drop_all() { ghost_ok[0] = ghost_ok[1] = nullptr; }
     pcl::QuietTiles qt;             // quiet tiles of the one-kernel dim-split step: state and invariants in quiet_tiles.hpp
+    // cell functions (cellfn.hpp): the modules this handle has loaded, and where the block sits in the global grid
+    // (pcl_cellfn_geometry; c.i and c.x of a body are global)
+    pcl::CellfnModules cellfn;
+    double cf_lower[3] = {0.0, 0.0, 0.0};
+    int cf_nstart[3] = {0, 0, 0};
 };
 
 static inline double *&cur(pcl_solver *s) { return s->sel == 0 ? s->q : s->sreg[s->sel]; }
@@ -682,7 +688,7 @@ int check_device() {
 extern "C" {
 
 const char *pcl_last_error(void) { return g_err.c_str(); }
-int pcl_version(void) { return 100; }
+int pcl_version(void) { return 101; }
 int pcl_device_count(void) {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess) return 0;
@@ -830,6 +836,7 @@ void pcl_destroy(pcl_solver *s) {
     if (s->stream) hipStreamSynchronize(s->stream);
     if (s->hstream) hipStreamSynchronize(s->hstream);
     s->halo.destroy();
+    s->cellfn.unload_all();     // here, never from a static destructor: the HIP runtime is still alive
     if (s->ev_h0) hipEventDestroy(s->ev_h0);
     if (s->ev_h1) hipEventDestroy(s->ev_h1);
     if (s->ev_y) hipEventDestroy(s->ev_y);
@@ -913,6 +920,16 @@ int pcl_put_aux(pcl_solver *s, const double *host) {
     if (s->cfg.maux <= 0) return fail(PCL_EINVAL, "solver was created with maux == 0");
     HIP_TRY(hipSetDevice(s->cfg.device));
     return upload(s, host, s->aux, s->cfg.maux, Window(s, 1));
+}
+
+int pcl_get_aux(pcl_solver *s, double *host) {
+    if (s) s->qt.invalidate();
+    // (a read, but the quiet tiles' rule is a whitelist -- quiet_tiles.hpp; tests/test_quiet_tiles_cpu.py holds the list --
+    // and an entry point that is not on it invalidates first; the price is one step that computes every tile)
+    if (!s || !host) return fail(PCL_EINVAL, "null argument");
+    if (s->cfg.maux <= 0 || !s->aux) return fail(PCL_EINVAL, "solver was created with maux == 0");
+    HIP_TRY(hipSetDevice(s->cfg.device));
+    return download(s, s->aux, host, s->cfg.maux, Window(s, 1));
 }
 
 int pcl_get_q(pcl_solver *s, double *host, int with_ghosts) {
@@ -1451,6 +1468,151 @@ int pcl_src(pcl_solver *s, int src_id, double dt, const double *params, int npar
         return PCL_OK;
     }
     return fail(PCL_EINVAL, "unknown source id");
+}
+
+// ---- cell functions (cellfn.hpp) ----------------------------------------------------------------------------------
+int pcl_cellfn_compile(int kind, const char *body, const char *preamble, int meqn, int maux, int ndim, int math,
+                       int writes_aux, pcl_cellfn **out, long *code_size) {
+    if (!body || !out) return fail(PCL_EINVAL, "null argument");
+    *out = nullptr;
+    if (!preamble) preamble = "";
+    if (!cellfn_kind_name(kind)) return fail(PCL_EINVAL, "pcl_cellfn_compile: kind must be PCL_CELLFN_STEP_SRC, _DQ_SRC or _START_STEP");
+    if (meqn < 1 || meqn > 64 || maux < 0 || maux > 64) return fail(PCL_EINVAL, "pcl_cellfn_compile: 1 <= meqn <= 64 and 0 <= maux <= 64");
+    if (ndim < 1 || ndim > 3) return fail(PCL_EINVAL, "pcl_cellfn_compile: ndim must be 1, 2 or 3");
+    if (math != PCL_MATH_EXACT && math != PCL_MATH_FAST && math != PCL_MATH_STRICT) return fail(PCL_EINVAL, "unknown math mode");
+    if (writes_aux && kind != PCL_CELLFN_START_STEP)
+        return fail(PCL_EINVAL, "pcl_cellfn_compile: only a start_step cell function may write aux");
+    if (writes_aux && maux == 0) return fail(PCL_EINVAL, "pcl_cellfn_compile: writes_aux needs an aux array (maux == 0)");
+    writes_aux = writes_aux ? 1 : 0;
+    CellfnCache &c = cellfn_cache();
+    std::lock_guard<std::mutex> lock(c.mu);
+    const std::string key = cellfn_key(kind, body, preamble, meqn, maux, ndim, math, writes_aux);
+    auto it = c.by_key.find(key);
+    pcl_cellfn *f = nullptr;
+    if (it != c.by_key.end()) {
+        f = it->second;
+        c.hits++;
+    } else {
+        std::vector<char> code;
+        std::string err;
+        if (cellfn_build(kind, body, preamble, meqn, maux, ndim, math, writes_aux, code, err)) return fail(PCL_EINVAL, err);
+        f = new pcl_cellfn();
+        f->id = c.next_id++;
+        f->kind = kind; f->meqn = meqn; f->maux = maux; f->ndim = ndim; f->math = math; f->writes_aux = writes_aux;
+        f->key = key;
+        f->code.swap(code);
+        c.by_key[key] = f;
+        c.live[f] = f->id;
+        c.compiles++;
+    }
+    f->refs++;
+    *out = f;
+    if (code_size) *code_size = (long)f->code.size();
+    return PCL_OK;
+}
+
+int pcl_cellfn_release(pcl_cellfn *f) {
+    if (!f) return PCL_OK;
+    CellfnCache &c = cellfn_cache();
+    std::lock_guard<std::mutex> lock(c.mu);
+    if (!c.live.count(f)) return fail(PCL_EINVAL, "pcl_cellfn_release: not a live cell function handle");
+    if (f->refs <= 0) return fail(PCL_EINVAL, "pcl_cellfn_release: released more often than compiled");
+    // The entry stays in the cache (host memory only, a few KB of code object per distinct text): the same text compiled
+    // again later is a cache hit, a handle never dangles, and the modules a solver has loaded stay one per distinct text.
+    f->refs--;
+    return PCL_OK;
+}
+
+int pcl_cellfn_stats(long *compiles, long *cache_hits) {
+    CellfnCache &c = cellfn_cache();
+    std::lock_guard<std::mutex> lock(c.mu);
+    if (compiles) *compiles = c.compiles;
+    if (cache_hits) *cache_hits = c.hits;
+    return PCL_OK;
+}
+
+static int cellfn_check_locked(CellfnCache &c, const pcl_cellfn *f, int meqn, int maux, int ndim) {
+    if (!f || !c.live.count(f)) return fail(PCL_EINVAL, "not a live cell function handle");
+    if (f->meqn != meqn || f->maux != maux || f->ndim != ndim)
+        return fail(PCL_EINVAL, "cell function was compiled for meqn=" + std::to_string(f->meqn) + " maux=" + std::to_string(f->maux) +
+                                    " ndim=" + std::to_string(f->ndim) + ", the solver has meqn=" + std::to_string(meqn) +
+                                    " maux=" + std::to_string(maux) + " ndim=" + std::to_string(ndim));
+    return PCL_OK;
+}
+
+int pcl_cellfn_check(const pcl_cellfn *f, int meqn, int maux, int ndim) {
+    CellfnCache &c = cellfn_cache();
+    std::lock_guard<std::mutex> lock(c.mu);
+    return cellfn_check_locked(c, f, meqn, maux, ndim);
+}
+
+int pcl_cellfn_geometry(pcl_solver *s, const double *lower, const int *nstart) {
+    if (s) s->qt.invalidate();            // quiet tiles: not a read-only call (quiet_tiles.hpp)
+    if (!s || !lower || !nstart) return fail(PCL_EINVAL, "null argument");
+    for (int k = 0; k < s->cfg.ndim; k++) {
+        if (nstart[k] < 0) return fail(PCL_EINVAL, "pcl_cellfn_geometry: nstart must be >= 0");
+        s->cf_lower[k] = lower[k];
+        s->cf_nstart[k] = nstart[k];
+    }
+    return PCL_OK;
+}
+
+int pcl_cellfn_apply(pcl_solver *s, pcl_cellfn *f, double t, double dt, const double *params, int nparams) {
+    if (s) s->qt.invalidate();            // quiet tiles: not a read-only call (quiet_tiles.hpp)
+    if (s) s->ghosts_drop_all();          // exchange-ahead: whatever filled the ghost frames no longer holds
+    if (nparams < 0 || nparams > PCL_CELLFN_MAX_PARAMS)
+        return fail(PCL_EINVAL, "pcl_cellfn_apply: a cell function takes at most 16 parameters");
+    if (!s || !f || (nparams > 0 && !params)) return fail(PCL_EINVAL, "null argument");
+    pcl_cell_args a;
+    memset(&a, 0, sizeof(a));
+    long id = 0;
+    int kind = 0;
+    const void *code = nullptr;
+    {
+        CellfnCache &c = cellfn_cache();
+        std::lock_guard<std::mutex> lock(c.mu);
+        if (int rc = cellfn_check_locked(c, f, s->cfg.meqn, s->cfg.maux, s->cfg.ndim)) return rc;
+        id = f->id;
+        kind = f->kind;
+        code = f->code.data();        // stays put while the caller holds its reference
+    }
+    if (kind == PCL_CELLFN_DQ_SRC && s->cfg.kind != PCL_KIND_SHARPCLAW)
+        return fail(PCL_EINVAL, "pcl_cellfn_apply: a dq_src cell function needs a SharpClaw solver (the dq register)");
+    if (s->cfg.maux > 0 && !s->aux) return fail(PCL_ESTATE, "pcl_cellfn_apply: no aux array on the device");
+    HIP_TRY(hipSetDevice(s->cfg.device));
+    auto it = s->cellfn.by_id.find(id);
+    if (it == s->cellfn.by_id.end()) {
+        CellfnModules::Loaded l;
+        HIP_TRY(hipModuleLoadData(&l.mod, code));
+        hipError_t e = hipModuleGetFunction(&l.fn, l.mod, "pcl_cellfn");
+        if (e != hipSuccess) {
+            (void)hipModuleUnload(l.mod);
+            return fail(PCL_EHIP, std::string("hipModuleGetFunction(pcl_cellfn): ") + hipGetErrorString(e));
+        }
+        it = s->cellfn.by_id.emplace(id, l).first;
+    }
+    a.q = cur(s);
+    a.dq = kind == PCL_CELLFN_DQ_SRC ? s->sreg[PCL_REG_DQ] : nullptr;
+    a.aux = s->aux;
+    a.pitch = s->pitch;
+    a.plane = s->plane;
+    a.slab = s->pitch * s->J;
+    a.mbc = s->cfg.mbc;
+    for (int k = 0; k < 3; k++) {
+        a.n[k] = k < s->cfg.ndim ? s->cfg.n[k] : 1;
+        a.nstart[k] = s->cf_nstart[k];
+        a.lower[k] = s->cf_lower[k];
+        a.d[k] = s->cfg.d[k];
+    }
+    a.t = t;
+    a.dt = dt;
+    for (int k = 0; k < nparams; k++) a.p[k] = params[k];
+    if (a.n[1] > 65535 || a.n[2] > 65535) return fail(PCL_EINVAL, "pcl_cellfn_apply: more than 65535 rows or planes");
+    size_t size = sizeof(a);
+    void *config[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &a, HIP_LAUNCH_PARAM_BUFFER_SIZE, &size, HIP_LAUNCH_PARAM_END};
+    HIP_TRY(hipModuleLaunchKernel(it->second.fn, (unsigned)((a.n[0] + 255) / 256), (unsigned)a.n[1], (unsigned)a.n[2], 256, 1, 1,
+                                  0, s->stream, nullptr, config));
+    return PCL_OK;
 }
 
 int pcl_fuse_source(pcl_solver *s, int src_id, const double *params, int nparams) {

@@ -22,7 +22,7 @@ import ctypes
 import numpy as np
 
 from . import _lib, riemann
-from .solver import Solver
+from .solver import CellFunction, CellStartStep, Solver
 
 Q, S1, S2, DQ, TMP = 0, 1, 2, 3, 4
 
@@ -86,6 +86,25 @@ class EulerRadialDqSource(DeviceDqSource):
         return dq
 
 
+class CellDqSource(CellFunction, DeviceDqSource):
+    """A SharpClaw source term (``solver.dq_src``) as a cell function (see ``CellFunction``): the body reads the stage's
+    ``q[MEQN]`` (const) and fills ``dq[MEQN]``, zero on entry, with what the Python ``dq_src(solver, state, dt)`` would
+    return for this cell; ``deltaq = deltaq + dq[m]`` follows on the device.  ``c.t`` is the stage time, ``c.dt`` the
+    step length.
+
+    It is never fused into the last pass of a stage: every stage runs its directional passes, this launch (one read of
+    q, one read and write of deltaq) and the Runge-Kutta combination as separate kernels."""
+
+    kind = 2
+    src_id = 0
+
+    def __init__(self, body, params=(), preamble=""):
+        CellFunction.__init__(self, body, params, preamble)
+
+    def __call__(self, solver, state, dt):
+        raise NotImplementedError("a CellDqSource runs on the device only")
+
+
 class _StageState(object):
     """What a Python custom-BC callback sees of an RK stage: time, grid, aux (solver.py:283-291)."""
 
@@ -132,7 +151,9 @@ class SharpClawSolver(Solver):
     def step(self, solution):
         """Evolve q over one time step (sharpclaw.py:152-210).  Registers: q, s1, s2, dq on device."""
         state = solution.states[0]
-        if self.start_step is not start_step:
+        if isinstance(self.start_step, CellStartStep):
+            self.start_step.apply(self, state)        # on the resident state, no round trip
+        elif self.start_step is not start_step:
             self._pull(state)
             self.start_step(self, solution)
             self._push(state)
@@ -212,12 +233,21 @@ class SharpClawSolver(Solver):
         self.dq_hyperbolic(reg, t)
         if self.cfl.get_cached_max() > self.cfl_max:
             raise CFLError('cfl_max exceeded')
-        if self.dq_src is not None and not self._dq_src_fused:
+        if isinstance(self.dq_src, CellDqSource):
+            # deltaq += dq_src(stage) by a cell function on the resident registers
+            L = _lib.lib()
+            _lib.check(L.pcl_select(self._h, reg))
+            try:
+                self.dq_src.launch(self, t, self.dt)
+            finally:
+                _lib.check(L.pcl_select(self._h, Q))
+        elif self.dq_src is not None and not self._dq_src_fused:
             # arbitrary Python: round trip of the stage through the host
             L = _lib.lib()
             st = self._stage
             st.t = t
             st.q = np.empty(self._state.q.shape, order='F')
+            self._pull_aux(self._state)        # the stage shares the state's aux array (time-dependent aux)
             _lib.check(L.pcl_select(self._h, reg))
             _lib.check(L.pcl_get_q(self._h, _lib.d(st.q), 0))
             extra = _lib.fortran64(self.dq_src(self, st, self.dt))
@@ -329,6 +359,7 @@ class SharpClawSolver(Solver):
         self.allocate_bc_arrays(state)
         self._setup_halo(state)
         self._upload_aux(state)
+        self._setup_cell_functions(state)
 
     def _custom_bc(self, state, dim, idim, side, fn):
         # Python custom BCs on a stage: same strip protocol as the base class, `state` carries stage time

@@ -70,6 +70,109 @@ class SphereMirrorBC(DeviceBC):
         _lib.check(_lib.lib().pcl_bc(solver._h, idim, side, 4))
 
 
+class CellFunction(object):
+    """Per-cell arithmetic written by the user as the text of a C++ function body, compiled at ``setup()`` for the
+    library's architecture and run on the resident arrays as one pointwise pass over the interior cells: what a Python
+    ``step_src`` / ``dq_src`` / ``start_step`` does with numpy on the host, without the device->host->device round trip.
+
+    The body sees ``q[MEQN]``, ``aux[MAUX]`` (const), ``c.t``, ``c.dt``, the GLOBAL 0-based interior indices
+    ``c.i[NDIM]``, the cell centre ``c.x[NDIM]`` (``lower + (i + 0.5) * d``, as ``grid.x.center`` computes it), the cell
+    sizes ``c.d[NDIM]`` and ``p[]``, up to 16 doubles taken from ``params`` at every launch (reassigning ``params``
+    between steps never recompiles).  ``preamble`` holds helper functions.  Neighbour cells are not available.
+    ``solver.math`` is part of the compile: 'exact' and 'strict' evaluate the body without FMA contraction and with IEEE
+    division and square root, 'fast' allows contraction.  A body that does not compile raises at ``setup()`` with the
+    compiler's log, whose line numbers are the body's own."""
+
+    kind = 0
+    MAX_PARAMS = 16
+
+    def __init__(self, body, params=(), preamble="", writes_aux=False):
+        self.body = str(body)
+        self.preamble = str(preamble)
+        self.writes_aux = bool(writes_aux)
+        self.params = params
+        self._fn = None            # pcl_cellfn handle and the constants it was compiled for
+        self._key = None
+        self.code_size = 0
+
+    @property
+    def params(self):
+        return self._params
+
+    @params.setter
+    def params(self, values):
+        values = np.array(values, dtype=np.float64).reshape(-1)
+        if len(values) > self.MAX_PARAMS:
+            raise ValueError("a cell function takes at most %d parameters, got %d" % (self.MAX_PARAMS, len(values)))
+        self._params = values
+
+    def compile(self, meqn, maux, ndim, math='exact'):
+        """Compile for these shape constants (no device needed; cached per process).  Raises with the compiler's log."""
+        import ctypes
+        if math not in ('exact', 'fast', 'strict'):
+            raise Exception("math must be 'exact', 'fast' or 'strict'")
+        key = (int(meqn), int(maux), int(ndim), math, self.body, self.preamble, self.writes_aux)
+        if self._fn is not None and self._key == key:
+            return self
+        if self.writes_aux and maux == 0:
+            raise ValueError("writes_aux needs an aux array: the state has maux == 0")
+        L = _lib.lib()
+        fn, size = ctypes.c_void_p(), ctypes.c_long(0)
+        rc = L.pcl_cellfn_compile(self.kind, self.body.encode(), self.preamble.encode(), key[0], key[1], key[2],
+                                  {'exact': 0, 'fast': 1, 'strict': 2}[math], int(self.writes_aux), ctypes.byref(fn),
+                                  ctypes.byref(size))
+        _lib.check(rc)
+        self.release()
+        self._fn, self._key, self.code_size = fn, key, int(size.value)
+        return self
+
+    def release(self):
+        if self._fn is not None:
+            _lib.lib().pcl_cellfn_release(self._fn)
+            self._fn = None
+            self._key = None
+
+    def __del__(self):
+        try:
+            self.release()
+        except Exception:
+            pass
+
+    def _compile_for(self, solver, state):
+        return self.compile(state.meqn, state.maux, solver.ndim, solver.math)
+
+    def launch(self, solver, t, dt):
+        """One pass over the interior cells of the solver's selected register."""
+        # compiled here when the object was assigned after setup() or its text was changed since (a cache look-up otherwise)
+        self._compile_for(solver, solver._state)
+        p = self._params
+        _lib.check(_lib.lib().pcl_cellfn_apply(solver._h, self._fn, float(t), float(dt), _lib.d(p) if len(p) else None,
+                                               len(p)))
+        solver._host_stale = True
+
+
+class CellStartStep(CellFunction):
+    """A before-step hook (``solver.start_step``) as a cell function: ``q`` is read/write, ``c.t`` is the time at the
+    start of the step.  Accepted by the classic and the SharpClaw solvers in place of a Python
+    ``start_step(solver, solution)``, and treated like one everywhere else: the step keeps a copied backup of q, and a
+    rejected step restores it.
+
+    ``writes_aux=True`` makes ``aux[MAUX]`` writable as well (time-dependent aux, e.g. ``aux[3] = q[0];`` for the
+    p-system's strain copy).  After the launch the solver fills the aux ghost cells again on the device -- halo exchange
+    in a decomposed run, then the aux boundary conditions per dimension and side -- and ``state.aux`` on the host is
+    refreshed when control returns to the caller or a Python callback is about to see the state.  A Python
+    ``user_aux_bc_lower`` / ``user_aux_bc_upper`` cannot follow a changing aux (it is evaluated once, on the host) and is
+    refused at ``setup()``."""
+
+    kind = 3
+
+    def apply(self, solver, state):
+        self.launch(solver, state.t, solver.dt)
+        if self.writes_aux:
+            solver._refresh_aux_ghosts(state)
+            solver._aux_host_stale = True
+
+
 class Solver(object):
     r"""Pyclaw solver superclass; see the reference docstring (solver.py:25-125)."""
 
@@ -107,6 +210,7 @@ class Solver(object):
         self._resident = False       # True while the HBM copy is the authoritative q
         self._pinned = False         # begin_resident()/end_resident(): keep q in HBM across calls
         self._host_stale = False
+        self._aux_host_stale = False  # a start_step cell function wrote aux on the device since the last download
         self._state = None
 
     # ------------------------------------------------------------------ validation
@@ -170,6 +274,38 @@ class Solver(object):
                 state.q = np.empty(state.q.shape, order='F')
             _lib.check(_lib.lib().pcl_get_q(self._h, _lib.d(state.q), 0))
             self._host_stale = False
+        self._pull_aux(state)
+
+    def _pull_aux(self, state):
+        """HBM -> state.aux (host) and the solver's auxbc, if a start_step cell function has written aux on the device
+        since the last download (CellStartStep(writes_aux=True)).  Runs wherever Python code is about to see the state:
+        with _pull, and in front of a Python custom-BC callback."""
+        if self._aux_host_stale and self._h is not None:
+            _lib.check(_lib.lib().pcl_get_aux(self._h, _lib.d(self.auxbc)))
+            interior = (slice(None),) + (slice(self.mbc, -self.mbc),) * self.ndim
+            state.aux[...] = self.auxbc[interior]
+            self._aux_host_stale = False
+
+    # ------------------------------------------------------------------ cell functions
+    def _cell_functions(self):
+        fns = [getattr(self, name, None) for name in ('start_step', 'step_src', 'dq_src')]
+        return [f for f in fns if isinstance(f, CellFunction)]
+
+    def _setup_cell_functions(self, state):
+        """Called by setup() once the device handle exists: tell the library where this block sits in the global grid
+        (a body's c.i and c.x are global) and compile the cell functions among start_step / step_src / dq_src."""
+        dims = state.grid.dimensions
+        lower = np.array([dim.lower for dim in dims], dtype=np.float64)
+        nstart = np.array([dim.nstart for dim in dims], dtype=np.int32)
+        _lib.check(_lib.lib().pcl_cellfn_geometry(self._h, _lib.d(lower), _lib.i(nstart)))
+        self._state = state
+        self._aux_host_stale = False
+        for fn in self._cell_functions():
+            if fn.writes_aux and (self.user_aux_bc_lower is not None or self.user_aux_bc_upper is not None):
+                raise NotImplementedError("a start_step that writes aux cannot be combined with a Python user_aux_bc_lower / "
+                                          "user_aux_bc_upper: the callback is evaluated once on the host and cannot "
+                                          "follow a changing aux")
+            fn._compile_for(self, state)
 
     # ------------------------------------------------------------------ boundary conditions
     def allocate_bc_arrays(self, state):
@@ -281,6 +417,7 @@ class Solver(object):
         # Plain Python callback (state,dim,t,qbc,mbc): give it the reference's full qbc array
         # (solver.py:404-405), then send back only the ghost layers of this side.
         L = _lib.lib()
+        self._pull_aux(state)          # a stage's _StageState shares the aux array of the solver's state
         _lib.check(L.pcl_get_q(self._h, _lib.d(self.qbc), 1))
         fn(state, dim, state.t, self.qbc, self.mbc)
         idx = [slice(None)] * self.qbc.ndim
@@ -346,7 +483,15 @@ class Solver(object):
         _lib.check(L.pcl_put_aux(self._h, _lib.d(_lib.fortran64(self.auxbc))))
         if not self._halo_active:
             return
-        _lib.check(L.pcl_halo_exchange_aux(self._h))
+        self._refresh_aux_ghosts(state)
+
+    def _refresh_aux_ghosts(self, state):
+        """Ghost cells of the resident aux from its interior, on the device, in the reference's order: halo exchange in a
+        decomposed run, then the physical aux BCs per dimension, lower then upper (solver.py:492-523).  Runs behind the
+        upload of a decomposed run and behind every start_step cell function that writes aux."""
+        L = _lib.lib()
+        if self._halo_active:
+            _lib.check(L.pcl_halo_exchange_aux(self._h))
         for idim, dim in enumerate(state.grid.dimensions):
             whole = self._at_lower(dim) and self._at_upper(dim)
             for side, at_edge, bcs in ((0, self._at_lower(dim), self.aux_bc_lower),
