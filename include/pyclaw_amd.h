@@ -416,6 +416,16 @@ int pcl_tile_rowreuse(pcl_solver *s, int enable);
 /* internal, for the test suite only: the x sweeps the last one-kernel step of the whole block reused, over the tiles it
  * computed (0 when none has run); makes the next step compute every tile */
 int pcl_tile_rowreuse_stats(pcl_solver *s, long *sweeps_reused);
+/* Column shortcut of the one-kernel step (on by default): a y sweep whose four columns are each constant over the 16
+ * rows of the tile's window, while the columns differ from each other, computes the wave speeds of its cells and stores
+ * nothing -- the update of every stored cell is the identity there.  Not taken where a stored cell holds a -0 or a
+ * non-finite component.  Same bits, same Courant number, same quiet words.  enable = 0: such sweeps run the full solve.
+ * Solvers without aux arrays and without a capacity function. */
+int pcl_tile_ycol(pcl_solver *s, int enable);
+/* internal, for the test suite only: the y-sweep calls (four columns each) of the last one-kernel step of the whole block
+ * that took the column shortcut, over the tiles it computed (0 when none has run); makes the next step compute every
+ * tile */
+int pcl_tile_ycol_stats(pcl_solver *s, long *groups);
 /* hyperbolic steps (classic) / right-hand sides (SharpClaw) attempted since pcl_create, rejected ones included */
 int pcl_step_count(pcl_solver *s, long *steps);
 

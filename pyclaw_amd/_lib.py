@@ -120,6 +120,8 @@ PROTOTYPES = {
     "pcl_tile_ring_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_long)]),
     "pcl_tile_rowreuse": (C.c_int, [C.c_void_p, C.c_int]),
     "pcl_tile_rowreuse_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_long)]),
+    "pcl_tile_ycol": (C.c_int, [C.c_void_p, C.c_int]),
+    "pcl_tile_ycol_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_long)]),
     "pcl_comm_unique_id": (C.c_int, [C.c_char_p]),
     "pcl_comm_init": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_char_p, ip]),
     "pcl_comm_check": (C.c_int, [C.c_int, C.c_int, ip]),

@@ -179,6 +179,9 @@ template <bool CAPA> __device__ __forceinline__ double cfl_value(double cflmax, 
 // (v_readlane), the test is MEQN compares against scalar operands, and a hit skips precell + speeds (two square
 // roots, a handful of quotients) -- in undisturbed gas strip after strip has the same state.  Same bits: equal q gives
 // equal speeds (+0 == -0 compares equal and cannot change a |speed|).
+// `valid`: bit 0 says the key holds a state; the bits above it are the caller's (the y sweeps of the one-kernel step count
+// their column shortcuts there: a counter of its own, carried through the sweep loop next to this one, cost the
+// Shallow2D instance two VGPRs and one wave per SIMD, profiles/r14_resource_usage.txt).
 template <int MEQN> struct NoJumpMemo {
     double key[MEQN];
     double m;
@@ -202,14 +205,24 @@ __device__ __forceinline__ double uniform_from_lane1(double x) {
 // F3 (3-D, flux3.f:236-252 + step3ds.f:177-181): correction coefficients carry the 0.5 like the 1-D code
 // (fadd = cqxx), the update is associated like the 2-D one ((q + qadd) - dtdx*(fadd(i+1)-fadd(i))).
 // auxv: this cell's aux values for Riemann solvers with RP::NAUX > 0.
-template <class RP, int IXY, bool CAPA, bool FWAVE, bool DIM1, bool TRANS = false, bool F3 = false>
+//
+// SEG < WAVE (the y sweeps of the one-kernel step, classic_fused.hpp: the wavefront holds WAVE / SEG columns of SEG rows,
+// lanes SEG*h .. SEG*h + SEG-1 = column h) with seg_on set: the column shortcut, DESIGN.md 4.1a round 14.  The no-jump
+// test masks the first lane of every column instead of lane 0 alone; where it passes and the wave-uniform test fails,
+// every column is constant along the sweep, the update of every cell the caller stores is the identity, and only the
+// speeds of each lane's own cell are needed.  `stored`: the caller puts this lane's result back; such a lane must hold
+// neither a -0 nor a non-finite component (the full solve turns -0 into +0 and an infinity into a NaN), else the full
+// path runs.  *col_taken (wave-uniform) tells the caller that qn was not written.  The return value stays what it was:
+// true only on the wave-uniform path.
+template <class RP, int IXY, bool CAPA, bool FWAVE, bool DIM1, bool TRANS = false, bool F3 = false, int SEG = WAVE>
 __device__ __forceinline__ bool lane_core(const double (&q)[RP::MEQN], double dtdx_c, double capa,
                                           bool cfl_ok, const SweepArgs &a,
                                           double (&qn)[RP::MEQN], double &cflmax,
                                           double *df = nullptr, double *g1 = nullptr, double *g2 = nullptr,
                                           const double *auxv = nullptr, const double *auxb = nullptr,
                                           const double *auxa = nullptr, const double *auxo = nullptr,
-                                          NoJumpMemo<RP::MEQN> *memo = nullptr) {   // returns: the no-jump shortcut was taken (wave-uniform)
+                                          NoJumpMemo<RP::MEQN> *memo = nullptr,   // returns: the no-jump shortcut was taken (wave-uniform)
+                                          bool seg_on = false, bool stored = false, bool *col_taken = nullptr) {
     constexpr int MEQN = RP::MEQN, MWAVES = RP::MWAVES;
     using Cell = typename RP::Cell;
 
@@ -222,10 +235,22 @@ __device__ __forceinline__ bool lane_core(const double (&q)[RP::MEQN], double dt
     // Cell equals this lane's bit for bit, so the Roe average is taken of (c, c).  Same speeds, same Courant number.
     if constexpr (!FWAVE && RP::NAUX == 0) {
         const bool lane0 = (threadIdx.x & (WAVE - 1)) == 0;   // lane 0 has no left cell
+        // Ballots against a scalar mask of the lanes whose left cell is not theirs to compare with: lane 0, or the first
+        // lane of every column (seg_on: uniform).  A wavefront with a jump inside a column leaves after the same single
+        // compare either way.
+        unsigned long long skip = 1ull;
+        if constexpr (SEG < WAVE) {
+            unsigned long long firsts = 0;
+#pragma unroll
+            for (int l = 0; l < WAVE; l += SEG) firsts |= 1ull << l;
+            skip = seg_on ? firsts : 1ull;
+        }
         // (every shift runs with all lanes active, outside the short-circuit expressions: a DPP read of a lane that is
         // masked off returns nothing useful)
         const double ql0 = from_left(q[0]);
-        bool same = __all(lane0 || ql0 == q[0]);
+        const unsigned long long eq0 = __ballot(ql0 == q[0]);
+        bool same = (eq0 | skip) == ~0ull;
+        bool col = false;      // wave-uniform: every column is constant, the wavefront is not
         if (same) {      // wave-uniform
             double ql[MEQN];
 #pragma unroll
@@ -233,11 +258,26 @@ __device__ __forceinline__ bool lane_core(const double (&q)[RP::MEQN], double dt
             bool rest = true;
 #pragma unroll
             for (int m = 1; m < MEQN; m++) rest = rest & (ql[m] == q[m]);
-            same = __all(lane0 || rest);
+            const unsigned long long eq = eq0 & __ballot(rest);
+            same = (eq | skip) == ~0ull;
+            if constexpr (SEG < WAVE) {
+                if (same && (eq | 1ull) != ~0ull) {
+                    // seg_on, and the columns differ from each other.  Integer tests of the bit patterns: a stored lane
+                    // with a -0 (sign bit alone) or an all-ones exponent sends the wavefront down the full path.
+                    bool bad = false;
+#pragma unroll
+                    for (int m = 0; m < MEQN; m++) {
+                        const unsigned long long b = (unsigned long long)__double_as_longlong(q[m]);
+                        bad = bad | (b == 0x8000000000000000ull) | ((b & 0x7ff0000000000000ull) == 0x7ff0000000000000ull);
+                    }
+                    col = !__any(stored && bad);
+                    same = col;
+                }
+            }
         }
         if (same) {
             if constexpr (!CAPA && !TRANS) {
-                if (memo && memo->valid) {       // wave-uniform: the state of the last jump-free strip again?
+                if (memo && (memo->valid & 1) && !col) {   // wave-uniform: the state of the last jump-free strip again?
                     bool hit = true;
 #pragma unroll
                     for (int m = 0; m < MEQN; m++) hit = hit & (q[m] == memo->key[m]);
@@ -257,20 +297,26 @@ __device__ __forceinline__ bool lane_core(const double (&q)[RP::MEQN], double dt
             if (__all(finite || lane0)) {
                 cfl_accumulate<CAPA, MWAVES>(s, dtdx_c, dtdx_l, cfl_ok, cflmax);
                 if constexpr (!CAPA && !TRANS) {
-                    if (memo) {                  // every lane holds this cell: lane 1's copy is the wavefront's
+                    // every lane holds this cell: lane 1's copy is the wavefront's.  Not on the column path, where each
+                    // lane has its own column's speeds: the memo keeps what it holds
+                    if (memo && !col) {
                         double mx = fabs(s[0]);
 #pragma unroll
                         for (int mw = 1; mw < MWAVES; mw++) mx = dmax(mx, fabs(s[mw]));
                         memo->m = uniform_from_lane1(mx);
 #pragma unroll
                         for (int m = 0; m < MEQN; m++) memo->key[m] = uniform_from_lane1(q[m]);
-                        memo->valid = 1;
+                        memo->valid |= 1;
                     }
                 }
 #pragma unroll
                 for (int m = 0; m < MEQN; m++) {
                     if constexpr (TRANS) { qn[m] = 0.0; df[m] = 0.0; g1[m] = 0.0; g2[m] = 0.0; }  // the slice's pieces
                     else qn[m] = q[m];
+                }
+                if constexpr (SEG < WAVE) {
+                    if (col) *col_taken = true;  // the caller stores nothing; not a no-jump sweep for the quiet words
+                    return !col;
                 }
                 return true;
             }

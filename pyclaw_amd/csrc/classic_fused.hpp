@@ -260,7 +260,8 @@ __global__ __launch_bounds__(F_THREADS, fused_wgs(fused_planes<RP, CAPA>())) voi
                                                                               const int *__restrict__ tq_list,
                                                                               const TileNext *tq_next,
                                                                               unsigned *__restrict__ tq_ring, unsigned ring_seq,
-                                                                              unsigned *__restrict__ tq_reuse, int rowreuse) {
+                                                                              unsigned *__restrict__ tq_reuse, int rowreuse,
+                                                                              unsigned *__restrict__ tq_ycol, int ycol) {
     constexpr int MEQN = RP::MEQN;
     constexpr int NAUX = RP::NAUX, PAUX = MEQN + (CAPA ? 1 : 0), NP = PAUX + NAUX, NX = NP - MEQN;
     static_assert(!SRC || (MEQN == 5 && NX == 0), "fused source: the Euler solver, no capacity function");
@@ -535,7 +536,7 @@ __global__ __launch_bounds__(F_THREADS, fused_wgs(fused_planes<RP, CAPA>())) voi
             double q[MEQN], qn[MEQN];
 #pragma unroll
             for (int m = 0; m < MEQN; m++) q[m] = tile[ftile_at(m, rl, c)];
-            bool nojump;
+            bool nojump, colcut = false;
             if constexpr (NX > 0) {
                 // dtdy1d(j) = dtdy / aux(mcapa,i,j) (step2ds.f:179-183), as sweep_kernel's y pass
                 double capa = 1.0, dtdy_c = ay.dtd, auxv[NAUX > 0 ? NAUX : 1];
@@ -547,15 +548,28 @@ __global__ __launch_bounds__(F_THREADS, fused_wgs(fused_planes<RP, CAPA>())) voi
                 for (int m = 0; m < NAUX; m++) auxv[m] = tile[ftile_at(PAUX + m, rl, c)];
                 nojump = lane_core<RP, 2, CAPA, FWAVE, false>(q, dtdy_c, capa, row_cfl && col_ok, ay, qn, cfly, nullptr, nullptr,
                                                               nullptr, NAUX > 0 ? auxv : nullptr);
-            } else
-                nojump = lane_core<RP, 2, false, FWAVE, false>(q, ay.dtd, 1.0, row_cfl && col_ok, ay, qn, cfly,
-                                                               nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                                                               nullptr, &memo);
+            } else {
+                // Column shortcut: the four columns differ from each other and each is constant
+                // over its 16 rows -- the inflow strip, a front planar in x.  Only the interfaces at rl == 0 carry a jump, and
+                // those reach rows 15 and 0 alone, which are never stored: every stored cell keeps its bits, so each lane
+                // takes the speeds of its own cell and nothing goes back.  Not a no-jump sweep for `quiet`: TQ_ALL means one
+                // state in the whole window.
+                nojump = lane_core<RP, 2, false, FWAVE, false, false, false, F_ROWS>(q, ay.dtd, 1.0, row_cfl && col_ok, ay, qn, cfly,
+                                                                                     nullptr, nullptr, nullptr, nullptr, nullptr,
+                                                                                     nullptr, nullptr, &memo, ycol != 0,
+                                                                                     row_owned && col_int, &colcut);
+                memo.valid += colcut ? 2 : 0;         // the wavefront's count, above the memo's valid bit (classic.hpp)
+            }
             quiet = quiet && nojump;
-            if (row_owned && col_int && !nojump) {
+            if (row_owned && col_int && !nojump && !colcut) {
 #pragma unroll
                 for (int m = 0; m < MEQN; m++) tile[ftile_at(m, rl, c)] = qn[m];
             }
+        }
+        // the wavefront leaves its count (one byte; wavefront 0 the launch's number), as the row reuse does
+        if (NX == 0 && tq_ycol && lane == 0) {
+            reinterpret_cast<unsigned char *>(tq_ycol + 2 * tile_id + 1)[wv] = (unsigned char)(memo.valid >> 1);
+            if (wv == 0) tq_ycol[2 * tile_id] = ring_seq;
         }
     }
     // A class-Q tile quiet again needs no store: the launch before left it quiet, so its owned cells in

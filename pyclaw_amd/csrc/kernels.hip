@@ -150,13 +150,13 @@ template <class RP> int launch_step2ds_t(const SweepLaunch &l, std::string &err)
     if (a.src_id != 0) {
         if constexpr (std::is_same<RP, Euler5>::value)
             hipLaunchKernelGGL((step2ds_kernel<RP, FW, true>), grid, dim3(F_THREADS), 0, l.stream, a, ntx, nty, l.tq_out,
-                               l.tq_cfl, l.tq_list, l.tq_next, l.tq_ring, l.ring_seq, l.tq_reuse, l.rowreuse);
+                               l.tq_cfl, l.tq_list, l.tq_next, l.tq_ring, l.ring_seq, l.tq_reuse, l.rowreuse, l.tq_ycol, l.ycol);
     } else if (capa)
         hipLaunchKernelGGL((step2ds_kernel<RP, FW, false, true>), grid, dim3(F_THREADS), 0, l.stream, a, ntx, nty, l.tq_out,
-                           l.tq_cfl, l.tq_list, l.tq_next, l.tq_ring, l.ring_seq, l.tq_reuse, l.rowreuse);
+                           l.tq_cfl, l.tq_list, l.tq_next, l.tq_ring, l.ring_seq, l.tq_reuse, l.rowreuse, l.tq_ycol, l.ycol);
     else
         hipLaunchKernelGGL((step2ds_kernel<RP, FW, false>), grid, dim3(F_THREADS), 0, l.stream, a, ntx, nty, l.tq_out,
-                           l.tq_cfl, l.tq_list, l.tq_next, l.tq_ring, l.ring_seq, l.tq_reuse, l.rowreuse);
+                           l.tq_cfl, l.tq_list, l.tq_next, l.tq_ring, l.ring_seq, l.tq_reuse, l.rowreuse, l.tq_ycol, l.ycol);
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? PCL_OK : hip_fail(err, "step2ds launch", e);
 }

@@ -688,7 +688,7 @@ int check_device() {
 extern "C" {
 
 const char *pcl_last_error(void) { return g_err.c_str(); }
-int pcl_version(void) { return 101; }
+int pcl_version(void) { return 102; }
 int pcl_device_count(void) {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess) return 0;
@@ -1943,6 +1943,32 @@ int pcl_tile_rowreuse_stats(pcl_solver *s, long *sweeps_reused) {
     for (size_t t = 0; t < u.size(); t += 2)
         if (u[t] == s->qt.ring_number())
             for (int w = 0; w < 4; w++) *sweeps_reused += (u[t + 1] >> (8 * w)) & 0xffu;
+    return PCL_OK;
+}
+
+// the y sweeps of the one-kernel step whose four columns are each constant over the window's rows take the speeds of
+// their own cells and store nothing (classic_fused.hpp: the column shortcut) on / off; off, they run the full solve
+int pcl_tile_ycol(pcl_solver *s, int enable) {
+    if (s) s->qt.invalidate();            // quiet tiles: not a read-only call (quiet_tiles.hpp)
+    if (!s) return fail(PCL_EINVAL, "null argument");
+    s->qt.set_ycol(enable != 0);
+    return PCL_OK;
+}
+
+// y-sweep calls (four columns each) of the last one-kernel launch of the whole block that took the column shortcut, over
+// the tiles it computed (summed here from the bytes the wavefronts left, as pcl_tile_rowreuse_stats)
+int pcl_tile_ycol_stats(pcl_solver *s, long *groups) {
+    if (s) s->qt.invalidate();            // quiet tiles: not a read-only call (quiet_tiles.hpp)
+    if (!s || !groups) return fail(PCL_EINVAL, "null argument");
+    *groups = 0;
+    if (s->qt.last_launch() == pcl::QuietTiles::NONE) return PCL_OK;
+    std::vector<unsigned> u(2 * (size_t)s->qt.ntx * s->qt.nty);
+    HIP_TRY(hipSetDevice(s->cfg.device));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    HIP_TRY(hipMemcpy(u.data(), s->qt.ycol_counts(), u.size() * sizeof(unsigned), hipMemcpyDeviceToHost));
+    for (size_t t = 0; t < u.size(); t += 2)
+        if (u[t] == s->qt.ring_number())
+            for (int w = 0; w < 4; w++) *groups += (u[t + 1] >> (8 * w)) & 0xffu;
     return PCL_OK;
 }
 

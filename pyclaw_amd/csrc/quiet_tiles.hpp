@@ -2,8 +2,8 @@
 // the kernels: classic_fused.hpp, the proofs: DESIGN.md 4.1a).
 //
 // Device memory: three word arrays W[0..2] (one 32-bit word per tile), the per-wavefront Courant maxima C, the tile
-// list L, the ring marks R (one 32-bit word per tile), the row-reuse counts U (two words per tile: the launch's number and
-// one byte per wavefront) and three TileNext blocks N[0..2].  Two counters rotate them: c
+// list L, the ring marks R (one 32-bit word per tile), the row-reuse counts U and the column-shortcut counts Y (each two
+// words per tile: the launch's number and one byte per wavefront) and three TileNext blocks N[0..2].  Two counters rotate them: c
 // (words) advances with every booked launch, x (blocks) with every hand-over that built a list; r numbers the booked
 // launches.  With c and x taken in front of launch n (indices modulo 3):
 //
@@ -11,7 +11,7 @@
 //   launch n        plan()         L, N[x+2] if it skips       W[c+1], C (computed tiles),       c += 1, r += 1
 //                                                              R := r (tiles its ring check
 //                                                              settled, classic_fused.hpp),
-//                                                              U (computed tiles: r and the counts)
+//                                                              U, Y (computed tiles: r and the counts)
 //   hand-over n     handover()     W[c+1], C, N[x+2] if        W[c+2] (tiles n + 1 skips), L,    x += 1
 //                                  launch n ran over a list    N[x] filled, N[x+1] zeroed,
 //                                  (its na + nq)               host word [2] (tiles launch n ran)
@@ -20,6 +20,7 @@
 //                                  N[x+2] (ran_over)
 //                                  R      (ring_marks: the words equal to r)
 //                                  U      (reuse_counts: the tiles whose first word equals r)
+//                                  Y      (ycol_counts: the same)
 //
 // Host word [2] (next to the Courant number [0] and the sequence number [1]) is read by the form-trial gate of
 // step_hyperbolic (pclaw.hip) while list_count_current() holds: no read-back, no wait.
@@ -81,6 +82,8 @@ public:
         if (e == hipSuccess) e = hipMemsetAsync(ring, 0, nt * sizeof(unsigned), stream);
         if (e == hipSuccess) e = hipMalloc((void **)&reuse, 2 * nt * sizeof(unsigned));
         if (e == hipSuccess) e = hipMemsetAsync(reuse, 0, 2 * nt * sizeof(unsigned), stream);
+        if (e == hipSuccess) e = hipMalloc((void **)&ycol, 2 * nt * sizeof(unsigned));
+        if (e == hipSuccess) e = hipMemsetAsync(ycol, 0, 2 * nt * sizeof(unsigned), stream);
         if (e == hipSuccess) e = hipMalloc((void **)&next, 3 * sizeof(TileNext));
         if (e == hipSuccess) e = hipMemsetAsync(next, 0, 3 * sizeof(TileNext), stream);
         return e;
@@ -92,6 +95,7 @@ public:
         if (list) hipFree(list);
         if (ring) hipFree(ring);
         if (reuse) hipFree(reuse);
+        if (ycol) hipFree(ycol);
         if (next) hipFree(next);
     }
 
@@ -100,15 +104,19 @@ public:
     void set_enabled(bool on) { enabled = on; }
     void set_ring(bool on) { ring_on = on; }
     void set_rowreuse(bool on) { reuse_on = on; }
+    void set_ycol(bool on) { ycol_on = on; }
 
     // In front of a one-kernel launch qin -> qout: fills l.tq_* and returns true if the launch is booked (`whole`: the
-    // whole undecomposed block).  Every flag is cleared; launched() sets them again.  The row-reuse switch goes to every
-    // launch, booked or not (tile subsets of a decomposed block: the same kernel); its counts only to a booked one.
+    // whole undecomposed block).  Every flag is cleared; launched() sets them again.  The row-reuse and column-shortcut
+    // switches go to every launch, booked or not (tile subsets of a decomposed block: the same kernel); their counts only
+    // to a booked one.
     bool plan(SweepLaunch &l, const double *qin, const double *qout, const Key &key, double dt, bool whole, bool carry) {
         const bool book = whole && words[0];
         l.rowreuse = reuse_on ? 1 : 0;
+        l.ycol = ycol_on ? 1 : 0;
         if (book) {
             l.tq_reuse = reuse;
+            l.tq_ycol = ycol;
             l.tq_out = written_next();
             l.tq_cfl = cfl;
             if (++ring_seq == 0) ring_seq = 1;          // 0 is what create() left in R
@@ -171,6 +179,8 @@ public:
     unsigned ring_number() const { return ring_seq; }
     const unsigned *reuse_counts() const { return reuse; }              // per tile: the number of the launch that computed it
                                                                         // last, then its x sweeps reused, a byte per wavefront
+    const unsigned *ycol_counts() const { return ycol; }                // the same layout: its y-sweep calls that took the
+                                                                        // column shortcut
     // The last launch ran over a list and the launch to come would run over the next one (carry: QuietTiles::take_valid
     // at the step's entry point): the count its hand-over left in host memory describes the state as it is now.
     bool list_count_current(bool carry) const { return carry && last == LIST && listed; }
@@ -188,6 +198,8 @@ private:
     bool ring_on = true;                // pcl_tile_ring
     unsigned *reuse = nullptr;
     bool reuse_on = true;               // pcl_tile_rowreuse
+    unsigned *ycol = nullptr;
+    bool ycol_on = true;                // pcl_tile_ycol
     bool valid = false, hand = false, listed = false;
     Last last = NONE;
     const double *last_in = nullptr, *last_out = nullptr;

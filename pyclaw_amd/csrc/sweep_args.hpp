@@ -174,6 +174,10 @@ struct SweepLaunch {
     // (pcl_tile_rowreuse_stats)
     int rowreuse = 1;
     unsigned *tq_reuse = nullptr;
+    // column shortcut of the y sweeps (classic_fused.hpp; 0: off).  tq_ycol (null: not counted): two words per tile, as
+    // tq_reuse -- ring_seq and, a byte per wavefront, its y-sweep calls that took the shortcut (pcl_tile_ycol_stats)
+    int ycol = 1;
+    unsigned *tq_ycol = nullptr;
 };
 
 // The Courant hand-over behind a one-kernel launch of the whole block, with the next launch's tile list
