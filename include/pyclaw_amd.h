@@ -429,6 +429,37 @@ int pcl_tile_ycol_stats(pcl_solver *s, long *groups);
 /* hyperbolic steps (classic) / right-hand sides (SharpClaw) attempted since pcl_create, rejected ones included */
 int pcl_step_count(pcl_solver *s, long *steps);
 
+/* ---- step ahead: the next step is enqueued before pcl_bc_step returns ------------------------------------------
+ * A caller that steps with a variable dt learns a step's Courant number when pcl_bc_step returns, computes the next dt
+ * and comes back; the device idles meanwhile.  Armed (on != 0; off by default), pcl_bc_step enqueues the step after the
+ * one it was asked for itself, before it returns, whenever that step ran as the one-kernel dim-split 2-D step over the
+ * whole undecomposed block (mbc 2, no aux arrays, no capacity function), its Courant number c is finite with
+ * 0 < c < cfl_max, and the step to come is an ordinary one-kernel step of its form window: with the boundary spec of
+ * that call and dt' = pcl_step_ahead_dt(dt, c, cfl_desired, dt_max) (on = 1: the loop of evolve_to_time(tend)) or
+ * dt' = dt (on = 2: a caller that keeps dt after an accepted step, as evolve_to_time does when it is called for one
+ * step at a time).  Only short launches are run ahead of -- the last one ran over at most 4096 tiles or a quarter of
+ * the grid -- since what is saved is one host turn-round per step and what a wrong guess costs is a whole launch.  The
+ * state is not advanced and nothing is counted.  The next pcl_bc_step ADOPTS the pending step -- the result becomes the state, the counters advance, the call
+ * waits for the Courant number -- if its dt has the same 64 bits as dt', its bc and constant states are bytewise the
+ * same, and only read-only calls (pcl_get_q, pcl_get_cells, pcl_get_strip, pcl_sync, the timers, pcl_step_count,
+ * pcl_step_form_stats; they see the state the caller knows) came in between.  Otherwise the pending step is DROPPED: a
+ * finished kernel whose output nobody uses; the call proceeds as if nothing had been enqueued, and its one-kernel launch
+ * computes every tile.  A drop with nothing in between means the caller follows another rule: the next step is not run
+ * ahead of, then the next two, four, ... up to 64 while that goes on; an adopted step ends it.  Results are the same bits either way: an adopted step is the launch the call would have made.
+ * pcl_undo_step, the tile hooks (pcl_tile_words, pcl_tile_list_classes, pcl_tile_*_stats) and pcl_step_ahead itself
+ * drop a pending step first; behind such a drop pcl_tile_skip_stats still reports the last step the caller asked for,
+ * the other hooks report nothing (as behind a step that was no one-kernel step).
+ * The one restriction, and why arming is explicit: the launch enqueued ahead overwrites the pre-step buffer of the step
+ * just taken, so behind an ACCEPTED step (c < cfl_max) of an armed solver pcl_undo_step returns PCL_ESTATE.  A step
+ * with c >= cfl_max is never run ahead of: it can be undone and retaken as before. */
+int pcl_step_ahead(pcl_solver *s, int on, double cfl_desired, double cfl_max, double dt_max);
+/* the dt of that rule: x = dt * cfl_desired / cfl evaluated left to right in double, then x < dt_max ? x : dt_max --
+ * what Python's min(dt_max, dt * cfl_desired / cfl) gives, bit for bit; a pure host function */
+double pcl_step_ahead_dt(double dt, double cfl, double cfl_desired, double dt_max);
+/* steps enqueued ahead since pcl_create, adopted, dropped; not a read-only call: a pending step is dropped by the
+ * next pcl_bc_step */
+int pcl_step_ahead_stats(pcl_solver *s, long *enqueued, long *adopted, long *dropped);
+
 /* ---- multi-GPU: one block per process, RCCL over xGMI -------------------------------- */
 /* Replaces PETSc DMDA globalToLocal (src/petclaw/state.py:254-269) and Vec.max
  * (src/petclaw/cfl.py:29-31).  uid is the 128-byte ncclUniqueId produced by

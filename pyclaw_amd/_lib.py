@@ -112,6 +112,9 @@ PROTOTYPES = {
     "pcl_kernel_timing_read": (C.c_int, [C.c_void_p, dp, C.POINTER(C.c_long)]),
     "pcl_step_form_stats": (C.c_int, [C.c_void_p, dp, C.POINTER(C.c_long), C.POINTER(C.c_long), C.POINTER(C.c_long)]),
     "pcl_step_count": (C.c_int, [C.c_void_p, C.POINTER(C.c_long)]),
+    "pcl_step_ahead": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_double]),
+    "pcl_step_ahead_dt": (C.c_double, [C.c_double] * 4),
+    "pcl_step_ahead_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_long), C.POINTER(C.c_long), C.POINTER(C.c_long)]),
     "pcl_tile_skip": (C.c_int, [C.c_void_p, C.c_int]),
     "pcl_tile_skip_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_long), C.POINTER(C.c_long)]),
     "pcl_tile_words": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),

@@ -299,6 +299,33 @@ class ClawSolver(Solver):
             _lib.check(_lib.lib().pcl_halo_exchange_ahead(self._h, 2 if onek else 1))
             self.exchange_ahead = True
 
+    def _arm_step_ahead(self, state, one_step=False, off=False):
+        """Resident mode (begin_resident ... end_resident) of the dimension-split 2-D solver on one block: the library
+        enqueues the next step before pcl_bc_step returns, with the dt the loop of evolve_to_time is about to compute,
+        and the next call adopts it if it asks for exactly that step (pcl_step_ahead, include/pyclaw_amd.h) -- the same
+        bits, one host turn-round less per step.  Only where nothing but the hyperbolic step touches q between two
+        steps; pcl_undo_step behind an accepted step is given up for it, and evolve_to_time undoes rejected steps
+        only.  The library is told when the settings change, not every call: telling it drops what is pending.
+        PCL_STEP_AHEAD=0 keeps it off."""
+        import os
+        on = bool(not off and self._h is not None and self._pinned and self.dt_variable and self.start_step is None
+                  and (self.step_src is None or (self.src_split == 1 and self._src_fused))
+                  and self.ndim == 2 and getattr(self, 'dim_split', False) and not self._halo_active
+                  and os.environ.get("PCL_STEP_AHEAD", "1") != "0"
+                  and self._device_bc_spec(state) is not None)
+        # evolve_to_time leaves its loop behind an accepted step before it chooses the next dt when it is called for one
+        # step (tend is None): that caller takes the same dt again (rule 2); evolve_to_time(tend) applies the rule (1)
+        want = ((2 if one_step else 1, float(self.cfl_desired), float(self.cfl_max), float(self.dt_max)) if on
+                else (0, 0.0, 0.0, 0.0))
+        sent = getattr(self, '_step_ahead_sent', None)
+        if want == sent or self._h is None or (sent is None and not on):
+            return
+        L = _lib.lib()
+        if not hasattr(L, "pcl_step_ahead"):           # an older build of the library (PCL_LIB_OVERRIDE)
+            return
+        _lib.check(L.pcl_step_ahead(self._h, want[0], want[1], want[2], want[3]))
+        self._step_ahead_sent = want
+
     def _decide_src_fusion(self, state):
         """Godunov-split device source of the 2-D Euler step: applied by the y pass / y phase while it stores its
         results (one read + write of q less per step; PCL_FUSE_SRC=0 keeps the separate source kernel).  Decided at
@@ -314,6 +341,7 @@ class ClawSolver(Solver):
         self._fuse_key = (id(self.step_src), self.src_split)
 
     def teardown(self):
+        self._arm_step_ahead(None, off=True)
         super(ClawSolver, self).teardown()
 
 

@@ -82,7 +82,11 @@ static_assert(F_WAVES == 4, "one quiet byte per wavefront in a 32-bit word");
 // class Q (quiet itself, listed for a neighbour or the frame) from the back, downward from index ntx * nty - 1.  Within
 // a workgroup's range of tiles each class keeps their order (ballot and prefix), the ranges take their places with one
 // atomic per class (next->na, next->nq).  *next was zeroed by the hand-over before the previous one.
-constexpr int TL_THREADS = 256;
+// Every atomic of the launch lands on the one TileNext block, where they serialise, so a workgroup is
+// 1024 tiles and issues at most four: the maxima of its 16 wavefronts meet in LDS behind the barrier the prefix needs
+// anyway, one thread issues the max of each word, and none when it is 0 (the same word: an integer max of the same set
+// of patterns, in any grouping).
+constexpr int TL_THREADS = 1024, TL_WAVES = TL_THREADS / WAVE;
 __global__ __launch_bounds__(TL_THREADS) void handover_list_kernel(unsigned long long *cfl, unsigned long long *host,
                                                                    unsigned long long seq, int ntx, int nty, int mbc,
                                                                    int mx, int my, const unsigned *__restrict__ tq_in,
@@ -90,8 +94,9 @@ __global__ __launch_bounds__(TL_THREADS) void handover_list_kernel(unsigned long
                                                                    const double2 *__restrict__ tq_cfl,
                                                                    int *__restrict__ list, TileNext *next,
                                                                    TileNext *other, const TileNext *ran) {
-    __shared__ int wbase[2][TL_THREADS / WAVE];
+    __shared__ int wbase[2][TL_WAVES];
     __shared__ int base[2];
+    __shared__ unsigned long long wmax[2][TL_WAVES];
     if (blockIdx.x == 0) {
         if (threadIdx.x == 0) {
             const unsigned long long v = *cfl;
@@ -143,14 +148,12 @@ __global__ __launch_bounds__(TL_THREADS) void handover_list_kernel(unsigned long
         bx = ox > bx ? ox : bx;
         by = oy > by ? oy : by;
     }
-    if (lane == 0) {
-        if (bx) atomicMax(&next->cx, bx);
-        if (by) atomicMax(&next->cy, by);
-    }
     // class A (c = 0) and class Q (c = 1): the workgroup's prefix per wavefront, one atomic per class
     const bool listed = t < ntx * nty && !skip;
     const unsigned long long keep[2] = {__ballot(listed && !own_quiet), __ballot(listed && own_quiet)};
     if (lane == 0) {
+        wmax[0][wv] = bx;
+        wmax[1][wv] = by;
         wbase[0][wv] = __popcll(keep[0]);
         wbase[1][wv] = __popcll(keep[1]);
     }
@@ -159,12 +162,17 @@ __global__ __launch_bounds__(TL_THREADS) void handover_list_kernel(unsigned long
         const int c = threadIdx.x;
         int n = 0;
 #pragma unroll
-        for (int k = 0; k < TL_THREADS / WAVE; k++) {
+        for (int k = 0; k < TL_WAVES; k++) {
             const int m = wbase[c][k];
             wbase[c][k] = n;
             n += m;
         }
         base[c] = n ? atomicAdd(c ? &next->nq : &next->na, n) : 0;
+    } else if (wv == 1 && lane < 2) {        // another wavefront than the prefix': the workgroup's two maxima
+        unsigned long long b = 0;
+#pragma unroll
+        for (int k = 0; k < TL_WAVES; k++) b = wmax[lane][k] > b ? wmax[lane][k] : b;
+        if (b) atomicMax(lane ? &next->cy : &next->cx, b);
     }
     __syncthreads();
     if (listed) {

@@ -83,6 +83,7 @@ struct pcl_solver {
     double form_t[2] = {0, 0};      // best (smallest) wall time of a trial step of each form in this window
     bool form_gated = false;        // this window's trials are skipped: the tile count settled the form
     long form_steps[2] = {0, 0};    // steps run in each form (pcl_step_form_stats)
+    int form_was = -1;              // the form step_hyperbolic's dim-split 2-D branch last took (step ahead)
     pcl::Halo halo;
     // halo exchange overlapped with the interior of the x pass (pcl_bc_step, dim-split 2-D)
     hipStream_t hstream = nullptr;
@@ -102,6 +103,28 @@ struct pcl_solver {
     void ghosts_drop(const double *buf) { for (auto &g : ghost_ok) if (g == buf) g = nullptr; }
     void ghosts_drop_all() { ghost_ok[0] = ghost_ok[1] = nullptr; }
     pcl::QuietTiles qt;             // quiet tiles of the one-kernel dim-split step: state and invariants in quiet_tiles.hpp
+    // Step ahead (pcl_step_ahead).  Armed, pcl_bc_step enqueues the step after the one it was asked for before it
+    // returns, with the dt the caller's rule gives (pcl_step_ahead_dt) and the boundary spec of this call: q -> t2 and
+    // its hand-over, q and t2 NOT swapped, no counter advanced.  The next pcl_bc_step adopts it if it asks for exactly
+    // that step (the same dt bits, the same spec, nothing but read-only calls in between) -- then it only waits for it --
+    // and drops it otherwise (ahead_drop): a finished kernel whose output nobody uses.
+    struct Ahead {
+        bool armed = false, pending = false;
+        int rule = 1;                       // the caller's dt after an accepted step: 1 pcl_step_ahead_dt, 2 the same dt again
+        // a pending step that was not the one asked for, although nothing came in between, cost a launch for nothing: the
+        // next `pause` steps are not run ahead of, twice as many after every such miss in a row (at most 64)
+        int miss = 0, pause = 0;
+        double cfl_desired = 0.0, cfl_max = 0.0, dt_max = 0.0;
+        double dt = 0.0;                    // of the pending step
+        unsigned long long seq = 0;         // of its hand-over
+        int vbc[4] = {-1, -1, -1, -1};      // its boundary spec, as set_vbc reads one
+        double vconst[4][8] = {};
+        long enqueued = 0, adopted = 0, dropped = 0;
+        // tiles the last step the caller asked for was dispatched for (host word [2] of its hand-over, read before the
+        // pending hand-over overwrites it; -1: that step was no booked launch), and the same once the pending step is
+        // dropped, for pcl_tile_skip_stats: the dropped launch took the device's record of it along
+        long asked_ran = -1, report = -1;
+    } ahead;
     // cell functions (cellfn.hpp): the modules this handle has loaded, and where the block sits in the global grid
     // (pcl_cellfn_geometry; c.i and c.x of a body are global)
     pcl::CellfnModules cellfn;
@@ -593,7 +616,9 @@ int read_cfl_begin(pcl_solver *s) {
     }
     return PCL_OK;
 }
-int read_cfl_end(pcl_solver *s, double *cfl) {
+// (two halves: the hand-over is enqueued, then the host polls for it; a step enqueued ahead has the first half at the
+// end of one pcl_bc_step call and the second in the next)
+int cfl_handover_enqueue(pcl_solver *s) {
     // One single-thread kernel behind the sweeps hands the word over through host memory the device can
     // write (the value, then a sequence number with release semantics at system scope) and re-zeroes it;
     // the host polls the sequence number.  ~3 us per step less than a D2H copy + event wait.  Behind a one-kernel
@@ -618,6 +643,9 @@ int read_cfl_end(pcl_solver *s, double *cfl) {
         hipLaunchKernelGGL(cfl_handover, dim3(1), dim3(1), 0, s->stream, s->cfl_dev, s->cfl_host_dev, seq);
         HIP_TRY(hipGetLastError());
     }
+    return PCL_OK;
+}
+int cfl_poll(pcl_solver *s, unsigned long long seq, double *cfl) {
     unsigned long long *flag = s->cfl_host + 1;
     long spins = 0;
     while (__atomic_load_n(flag, __ATOMIC_ACQUIRE) != seq) {
@@ -632,6 +660,10 @@ int read_cfl_end(pcl_solver *s, double *cfl) {
     memcpy(&v, s->cfl_host, sizeof(double));
     *cfl = v;
     return PCL_OK;
+}
+int read_cfl_end(pcl_solver *s, double *cfl) {
+    if (int rc = cfl_handover_enqueue(s)) return rc;
+    return cfl_poll(s, s->cfl_seq, cfl);
 }
 int read_cfl(pcl_solver *s, double *cfl) {
     if (int rc = read_cfl_begin(s)) return rc;
@@ -688,7 +720,7 @@ int check_device() {
 extern "C" {
 
 const char *pcl_last_error(void) { return g_err.c_str(); }
-int pcl_version(void) { return 102; }
+int pcl_version(void) { return 103; }
 int pcl_device_count(void) {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess) return 0;
@@ -1093,6 +1125,22 @@ int pcl_sweep(pcl_solver *s, int ids, double dt, double *cfl) {
     return read_cfl(s, cfl);
 }
 
+// Step ahead (pcl_solver::Ahead): the pending step is not the one anybody asked for.  Its launch and its hand-over are
+// enqueued and will run: t2 holds a result nobody uses, q is the state, the Courant word is zero again and the sequence
+// counter is past the hand-over.  Only the quiet-tile state has to forget it (QuietTiles::drop).
+static void ahead_drop(pcl_solver *s) {
+    if (!s->ahead.pending) return;
+    s->ahead.pending = false;
+    s->ahead.dropped++;
+    s->ahead.report = s->ahead.asked_ran;
+    s->qt.drop();
+}
+
+// one block: the faster form of the dim-split 2-D step, decided afresh every FORM_WINDOW steps (pcl_solver::form_now)
+constexpr long FORM_WINDOW = 256;
+constexpr int FORM_TRIAL = 3;       // timed steps per form at the start of a window (the first one untimed)
+constexpr long FORM_T0 = 64;        // the trials start 64 steps into a window: a short run never meets them
+
 // the body of pcl_step_hyperbolic.  carry: the quiet-tile words of the previous launch still hold; only the one-kernel
 // form of the step carries them on
 static int step_hyperbolic(pcl_solver *s, double dt, double *cfl, bool carry) {
@@ -1112,16 +1160,12 @@ static int step_hyperbolic(pcl_solver *s, double dt, double *cfl, bool carry) {
         if (int rc = do_sweep(s, s->q, s->t1, 1, dt)) return bail(s, rc);
         commit_step(s, s->t1);
     } else if (s->cfg.method[2] < 0) {  // dimensional splitting, clawpack.py:538-546
-        // one block: the faster form of the step, decided afresh every FORM_WINDOW steps (pcl_solver::form_now)
-        constexpr long FORM_WINDOW = 256;
-        constexpr int FORM_TRIAL = 3;       // timed steps per form at the start of a window (the first one untimed)
         const bool can = fused_step_ok(s);
         // (a decomposed block whose exchange runs in front of the step, pcl_bc_step: every rank picks for itself -- both
         // forms see the same ghost frame, give the same bits and leave the order on the communicator alone)
         const bool tune = can && fused_step_mode() == 2 && (!s->halo.active || s->form_seq_tune);
         int form = can ? 1 : 0;
         bool trial = false;                 // this step is one of the window's trial steps
-        constexpr long FORM_T0 = 64;        // the trials start 64 steps into a window: a short run never meets them
         if (tune) {
             const long k = s->form_step % FORM_WINDOW - FORM_T0;
             if (k == 0) {
@@ -1144,6 +1188,7 @@ static int step_hyperbolic(pcl_solver *s, double dt, double *cfl, bool carry) {
                 form = s->form_now;
             }
         }
+        s->form_was = form;
         const auto t0 = std::chrono::steady_clock::now();
         if (form == 1) {
             if (int rc = do_step2ds(s, s->q, s->t2, dt, carry)) return bail(s, rc);
@@ -1173,7 +1218,10 @@ static int step_hyperbolic(pcl_solver *s, double dt, double *cfl, bool carry) {
 int pcl_step_hyperbolic(pcl_solver *s, double dt, double *cfl) {
     if (s) s->ghosts_drop_all();          // exchange-ahead: whatever filled the ghost frames no longer holds
     if (!s || !cfl) return fail(PCL_EINVAL, "null argument");
-    return step_hyperbolic(s, dt, cfl, s->qt.take_valid());
+    const bool carry = s->qt.take_valid();
+    ahead_drop(s);
+    s->ahead.report = -1;
+    return step_hyperbolic(s, dt, cfl, carry);
 }
 
 static int check_bc_spec(pcl_solver *s, const int *bc, const double *cstate, bool unsplit_only = false) {
@@ -1366,6 +1414,90 @@ static int step_ghost_fills(pcl_solver *s, const int *bc, const double *cstate, 
     return step_hyperbolic(s, dt, cfl, false);
 }
 
+// ---- step ahead (pcl_solver::Ahead) ----
+// The dt evolve_to_time takes after an accepted step with Courant number cfl > 0: min(dt_max, dt * cfl_desired / cfl) as
+// Python evaluates it -- the product, then the quotient, each rounded to double, then the smaller of the two with dt_max
+// winning ties and unordered comparisons.  No contraction, no reciprocal, no reordering: a multiply feeding a divide is
+// nothing a host compiler fuses, and this file is built with -ffp-contract=off all the same.
+double pcl_step_ahead_dt(double dt, double cfl, double cfl_desired, double dt_max) {
+    const double x = dt * cfl_desired / cfl;
+    return x < dt_max ? x : dt_max;
+}
+
+// the step to come (form_step as it stands) takes the one-kernel form as a plain step of its window: not the step at
+// which the window's form is decided (k == 0, the gate; k == 2 (FORM_TRIAL + 1), the trials' verdict), not a trial step
+static bool ahead_next_is_plain_onek(const pcl_solver *s) {
+    if (!fused_step_ok(s)) return false;
+    if (fused_step_mode() != 2) return true;
+    const long k = s->form_step % FORM_WINDOW - FORM_T0;
+    if (k == 0) return false;
+    if (!s->form_gated && k >= 0 && k <= 2 * (FORM_TRIAL + 1)) return false;
+    return s->form_now == 1;
+}
+
+// At the end of a pcl_bc_step call that ran the one-kernel form over the whole block with the list hand-over behind it
+// and read the Courant number c: enqueue the step after it.  The host has read word [0] of this step, so the pending
+// hand-over may overwrite it.
+static int ahead_enqueue(pcl_solver *s, const int *bc, const double *cstate, double dt, double c) {
+    pcl_solver::Ahead &a = s->ahead;
+    if (!a.armed || s->halo.active || fused_aux_family(s) || s->cfg.mbc != 2 || s->sel != 0 || s->form_was != 1 ||
+        !s->qt.list_behind_last())
+        return PCL_OK;
+    if (!(c > 0.0 && c < a.cfl_max)) return PCL_OK;      // (a NaN fails both; an infinite c is not below cfl_max)
+    if (!ahead_next_is_plain_onek(s)) return PCL_OK;
+    if (a.pause > 0) {
+        a.pause--;
+        return PCL_OK;
+    }
+    // Short launches only: the step ahead saves one host turn-round (about 10 us) per step and costs one launch for
+    // nothing whenever the caller turns out to want something else, the last step of a run included.  The launch to
+    // come runs over about as many tiles as the one just run (host word [2]): at most a quarter of the grid (the bound
+    // of the form gate, step_hyperbolic) or 4096 tiles, four rounds of the 1024 workgroups the chip holds at a time.
+    const long ran = (long)__atomic_load_n(s->cfl_host + 2, __ATOMIC_RELAXED);
+    if (ran > 4096 && 4 * ran > (long)s->qt.ntx * s->qt.nty) return PCL_OK;
+    const double dt1 = a.rule == 2 ? dt : pcl_step_ahead_dt(dt, c, a.cfl_desired, a.dt_max);
+    a.asked_ran = ran;
+    set_vbc(s, bc, cstate, 2 * s->cfg.ndim);
+    VbcScope vbc_scope(s);
+    memcpy(a.vbc, s->vbc, sizeof(a.vbc));
+    memcpy(a.vconst, s->vconst, sizeof(a.vconst));
+    // the launch overwrites the pre-step buffer of the step just taken: nothing to undo from here on
+    s->undo_slot = nullptr;
+    if (int rc = do_step2ds(s, s->q, s->t2, dt1, true)) return bail(s, rc);
+    if (int rc = cfl_handover_enqueue(s)) return rc;
+    a.dt = dt1;
+    a.seq = s->cfl_seq;
+    a.pending = true;
+    a.enqueued++;
+    return PCL_OK;
+}
+
+// the caller asks for exactly the pending step: the same dt bits, the same boundary spec, nothing in between
+static bool ahead_matches(const pcl_solver *s, const int *bc, const double *cstate, double dt, bool carry) {
+    const pcl_solver::Ahead &a = s->ahead;
+    if (!a.armed || !carry || memcmp(&dt, &a.dt, sizeof(double)) != 0) return false;
+    for (int k = 0; k < 4; k++) {
+        if (bc[k] != a.vbc[k]) return false;
+        if (bc[k] == PCL_BC_CUSTOM && memcmp(cstate + k * PCL_MAX_RP_PARAMS, a.vconst[k], sizeof(a.vconst[k])) != 0) return false;
+    }
+    return true;
+}
+
+// what the ordinary path does behind the launch pair: the result becomes the state, the counters advance, the host polls
+static int ahead_adopt(pcl_solver *s, double *cfl) {
+    s->ahead.pending = false;
+    s->ahead.adopted++;
+    s->ahead.miss = 0;
+    s->qt.adopted(true);            // (ahead_matches: the flag was taken as true)
+    commit_step(s, s->t2);
+    s->form_steps[1]++;
+    s->form_was = 1;
+    if (int rc = read_cfl_begin(s)) return rc;
+    const int rc = cfl_poll(s, s->ahead.seq, cfl);
+    if (fused_step_mode() == 2) s->form_step++;
+    return rc;
+}
+
 int pcl_bc_step(pcl_solver *s, const int *bc, const double *cstate, double dt, double *cfl) {
     if (!s || !bc || !cfl) return fail(PCL_EINVAL, "null argument");
     // quiet tiles: only the whole block's step with the boundary conditions evaluated while loading (no ghost fill, no
@@ -1374,6 +1506,19 @@ int pcl_bc_step(pcl_solver *s, const int *bc, const double *cstate, double dt, d
     if (s->cfg.kind != PCL_KIND_CLASSIC) return fail(PCL_ESTATE, "classic call on a SharpClaw solver");
     HIP_TRY(hipSetDevice(s->cfg.device));
     if (int rc = check_bc_spec(s, bc, cstate, true)) return rc;
+    if (s->ahead.pending) {
+        if (ahead_matches(s, bc, cstate, dt, carry)) {
+            if (int rc = ahead_adopt(s, cfl)) return rc;
+            return ahead_enqueue(s, bc, cstate, dt, *cfl);
+        }
+        if (carry && s->ahead.armed) {      // nothing came in between: the caller's rule is not the one it armed with
+            s->ahead.miss = std::min(s->ahead.miss + 1, 7);
+            s->ahead.pause = 1 << (s->ahead.miss - 1);
+        }
+        ahead_drop(s);
+    }
+    s->form_was = -1;
+    s->ahead.report = -1;
     // Dimension-split steps (and 1-D): the first pass evaluates the boundary conditions while it
     // loads its tiles -- no ghost-fill launches (each costs ~5 us of launch latency per step).
     const bool fused = s->cfg.meqn <= 8 && (s->cfg.ndim == 1 || (s->cfg.ndim == 2 && s->cfg.method[2] < 0));
@@ -1405,12 +1550,16 @@ int pcl_bc_step(pcl_solver *s, const int *bc, const double *cstate, double dt, d
     }
     if (s->cfg.ndim == 2 && s->cfg.method[2] >= 0 && s->sel == 0) return step_unsplit2(s, bc, cstate, dt, cfl);
     if (overlapped) return step_overlapped(s, bc, cstate, dt, cfl, onek, box);
-    if (fused) return step_loading_bcs(s, bc, cstate, dt, cfl, carry);
+    if (fused) {
+        if (int rc = step_loading_bcs(s, bc, cstate, dt, cfl, carry)) return rc;
+        return ahead_enqueue(s, bc, cstate, dt, *cfl);
+    }
     return step_ghost_fills(s, bc, cstate, dt, cfl);
 }
 
 int pcl_undo_step(pcl_solver *s) {
     if (s) s->qt.invalidate();            // quiet tiles: not a read-only call (quiet_tiles.hpp)
+    if (s) ahead_drop(s);                 // (behind a step enqueued ahead the pre-step buffer is gone: PCL_ESTATE)
     if (!s) return fail(PCL_EINVAL, "null argument");
     if (!s->undo_slot) return fail(PCL_ESTATE, "no step to undo");
     std::swap(s->q, *s->undo_slot);
@@ -1850,6 +1999,31 @@ int pcl_step_form_stats(pcl_solver *s, double *ms_total, long *launches, long *s
     return PCL_OK;
 }
 
+// Step ahead on / off (off by default).  cfl_desired, cfl_max, dt_max: the caller's rule for the next dt after an
+// accepted step (on = 1: pcl_step_ahead_dt; on = 2: the same dt again), and the bound below which a step counts as
+// accepted.
+int pcl_step_ahead(pcl_solver *s, int on, double cfl_desired, double cfl_max, double dt_max) {
+    if (s) s->qt.invalidate();            // quiet tiles: not a read-only call (quiet_tiles.hpp)
+    if (!s) return fail(PCL_EINVAL, "null argument");
+    ahead_drop(s);
+    s->ahead.armed = on != 0;
+    s->ahead.rule = on == 2 ? 2 : 1;
+    s->ahead.miss = s->ahead.pause = 0;
+    s->ahead.cfl_desired = cfl_desired;
+    s->ahead.cfl_max = cfl_max;
+    s->ahead.dt_max = dt_max;
+    return PCL_OK;
+}
+// steps enqueued ahead since pcl_create, and what became of them (a pending one is in neither of the last two)
+int pcl_step_ahead_stats(pcl_solver *s, long *enqueued, long *adopted, long *dropped) {
+    if (s) s->qt.invalidate();            // quiet tiles: not a read-only call (quiet_tiles.hpp)
+    if (!s || !enqueued || !adopted || !dropped) return fail(PCL_EINVAL, "null argument");
+    *enqueued = s->ahead.enqueued;
+    *adopted = s->ahead.adopted;
+    *dropped = s->ahead.dropped;
+    return PCL_OK;
+}
+
 int pcl_tile_skip(pcl_solver *s, int enable) {
     if (s) s->qt.invalidate();            // quiet tiles: not a read-only call (quiet_tiles.hpp)
     if (!s) return fail(PCL_EINVAL, "null argument");
@@ -1869,9 +2043,16 @@ static int read_list_classes(pcl_solver *s, int c[2]) {
 // before it; a launch without skipping computed all.  Nothing counted: both 0.
 int pcl_tile_skip_stats(pcl_solver *s, long *computed, long *skipped) {
     if (!s || !computed || !skipped) return fail(PCL_EINVAL, "null argument");
+    ahead_drop(s);                        // it reports on the last launch the caller asked for
     *computed = *skipped = 0;
-    if (s->qt.last_launch() == pcl::QuietTiles::NONE) return PCL_OK;
     const long nt = (long)s->qt.ntx * s->qt.nty;
+    if (s->qt.last_launch() == pcl::QuietTiles::NONE && s->ahead.report >= 0) {
+        // a step enqueued ahead was dropped behind the last step the caller asked for: that step's count as the host kept it
+        *computed = s->ahead.report;
+        *skipped = nt - s->ahead.report;
+        return PCL_OK;
+    }
+    if (s->qt.last_launch() == pcl::QuietTiles::NONE) return PCL_OK;
     long n = nt;
     if (s->qt.last_launch() == pcl::QuietTiles::LIST) {
         int c[2] = {0, 0};
@@ -1887,6 +2068,7 @@ int pcl_tile_skip_stats(pcl_solver *s, long *computed, long *skipped) {
 // the last launch did not run over a list
 int pcl_tile_list_classes(pcl_solver *s, long *na, long *nq) {
     if (s) s->qt.invalidate();            // quiet tiles: not a read-only call (quiet_tiles.hpp)
+    if (s) ahead_drop(s);                 // they report on the last launch the caller asked for
     if (!s || !na || !nq) return fail(PCL_EINVAL, "null argument");
     *na = *nq = 0;
     if (s->qt.last_launch() != pcl::QuietTiles::LIST) return PCL_OK;
@@ -1909,6 +2091,7 @@ int pcl_tile_ring(pcl_solver *s, int enable) {
 // that launch did not run over a list
 int pcl_tile_ring_stats(pcl_solver *s, long *short_path) {
     if (s) s->qt.invalidate();            // quiet tiles: not a read-only call (quiet_tiles.hpp)
+    if (s) ahead_drop(s);                 // they report on the last launch the caller asked for
     if (!s || !short_path) return fail(PCL_EINVAL, "null argument");
     *short_path = 0;
     if (s->qt.last_launch() != pcl::QuietTiles::LIST) return PCL_OK;
@@ -1933,6 +2116,7 @@ int pcl_tile_rowreuse(pcl_solver *s, int enable) {
 // the wavefronts left; a tile the launch skipped, or its ring check settled, holds an older launch's number)
 int pcl_tile_rowreuse_stats(pcl_solver *s, long *sweeps_reused) {
     if (s) s->qt.invalidate();            // quiet tiles: not a read-only call (quiet_tiles.hpp)
+    if (s) ahead_drop(s);                 // they report on the last launch the caller asked for
     if (!s || !sweeps_reused) return fail(PCL_EINVAL, "null argument");
     *sweeps_reused = 0;
     if (s->qt.last_launch() == pcl::QuietTiles::NONE) return PCL_OK;
@@ -1959,6 +2143,7 @@ int pcl_tile_ycol(pcl_solver *s, int enable) {
 // the tiles it computed (summed here from the bytes the wavefronts left, as pcl_tile_rowreuse_stats)
 int pcl_tile_ycol_stats(pcl_solver *s, long *groups) {
     if (s) s->qt.invalidate();            // quiet tiles: not a read-only call (quiet_tiles.hpp)
+    if (s) ahead_drop(s);                 // they report on the last launch the caller asked for
     if (!s || !groups) return fail(PCL_EINVAL, "null argument");
     *groups = 0;
     if (s->qt.last_launch() == pcl::QuietTiles::NONE) return PCL_OK;
@@ -1974,6 +2159,7 @@ int pcl_tile_ycol_stats(pcl_solver *s, long *groups) {
 
 int pcl_tile_words(pcl_solver *s, unsigned *host, int *ntx, int *nty) {
     if (s) s->qt.invalidate();            // quiet tiles: not a read-only call (quiet_tiles.hpp)
+    if (s) ahead_drop(s);                 // they report on the last launch the caller asked for
     if (!s || !ntx || !nty) return fail(PCL_EINVAL, "null argument");
     *ntx = s->qt.ntx;
     *nty = s->qt.nty;

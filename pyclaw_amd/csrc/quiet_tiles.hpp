@@ -33,12 +33,14 @@
 //   valid    the last launch was a booked one, last_in -> last_out with last_key, and since then only the buffer swap of
 //            the step and read-only calls have happened.  Set by launched(); cleared by invalidate() (the first statement
 //            of every C entry point that is neither a step nor read-only: tests/test_quiet_tiles_cpu.py), by take_valid()
-//            (the step entry points; the value travels down to plan() as `carry`) and by plan().
+//            (the step entry points; the value travels down to plan() as `carry`) and by plan().  adopted() gives the
+//            taken value back when the step asked for is the launch it was set for (a step enqueued ahead).
 //   hand     a hand-over with a list is due behind the last launch.  Set by launched() while skipping is enabled;
 //            cleared by handover() and plan().
 //   listed   L and N[x-1] hold the list of the next launch.  Set by handed_over(true); cleared by handover() (every
 //            Courant read-back: a later step of another form drops the list) and plan().
 //   last     what the last launch was (NONE / ALL / LIST), for the hooks.  Set by launched(); cleared by plan().
+// drop() clears all four: a step that was enqueued ahead of the caller and not adopted (pclaw.hip: step ahead).
 #pragma once
 #include <cmath>
 #include <cstring>
@@ -101,6 +103,19 @@ public:
 
     void invalidate() { valid = false; }
     bool take_valid() { const bool v = valid; valid = false; return v; }
+    // A step enqueued ahead (pclaw.hip: step ahead) that nobody asked for: its launch and its hand-over ran, its result is
+    // not the state.  Every flag down, as plan() leaves them: the next launch computes every tile and lists afresh.  c, x
+    // and r have moved on with the launch and its hand-over, which is what keeps the words and the blocks consistent.
+    void drop() {
+        valid = hand = listed = false;
+        last = NONE;
+    }
+    // The step entry point took the flag (true: nothing but read-only calls since the launch) and found that the launch
+    // it was set for is the very step it is asked for (pclaw.hip: ahead_adopt): nothing is launched, so launched() does
+    // not set it again -- the flag goes back as it was taken.
+    void adopted(bool taken) { valid = taken; }
+    // the last launch was a booked one with the next launch's list behind it, and nothing has happened since
+    bool list_behind_last() const { return valid && listed; }
     void set_enabled(bool on) { enabled = on; }
     void set_ring(bool on) { ring_on = on; }
     void set_rowreuse(bool on) { reuse_on = on; }

@@ -244,6 +244,7 @@ class Solver(object):
         if self._h is not None:
             _lib.lib().pcl_destroy(self._h)
             self._h = None
+        self._step_ahead_sent = None         # (what the handle was last told: pcl_step_ahead)
         self._resident = False
 
     def __del__(self):
@@ -607,6 +608,7 @@ class Solver(object):
         state = solution.state
         if not self._pinned:
             self._push(state)
+        self._arm_step_ahead(state, take_one_step)
         try:
             for n in range(self.max_steps):
                 state = solution.state
@@ -675,6 +677,11 @@ class Solver(object):
         self._pull(solution.state)
         self._pinned = False
         self._resident = False
+        self._arm_step_ahead(solution.state)         # no longer pinned: disarms
+
+    # Resident mode runs one step ahead where the library can (pcl_step_ahead; ClawSolver decides): nothing here
+    def _arm_step_ahead(self, state, one_step=False):
+        pass
 
     # backup/restore of the resident state; subclasses pick the cheap form when legal
     def _backup(self, state):
