@@ -298,6 +298,7 @@ int pcl_fuse_source(pcl_solver *s, int src_id, const double *params, int nparams
 #define PCL_CELLFN_STEP_SRC 1
 #define PCL_CELLFN_DQ_SRC 2
 #define PCL_CELLFN_START_STEP 3
+#define PCL_CELLFN_BC 4         /* a boundary condition: its own body surface and launch, pcl_cellbc_apply below */
 #define PCL_CELLFN_MAX_PARAMS 16
 typedef struct pcl_cellfn pcl_cellfn;
 /* Compile (host only, no device needed).  Functions are cached per process by (kind, body, preamble, meqn, maux, ndim,
@@ -310,7 +311,7 @@ int pcl_cellfn_release(pcl_cellfn *f);          /* drops one reference; the comp
                                                  * the life of the process (host memory: its code object) */
 /* compiles done and cache hits of this process */
 int pcl_cellfn_stats(long *compiles, long *cache_hits);
-/* Host-only argument check of pcl_cellfn_apply: the handle is live and was compiled for these shape constants. */
+/* Host-only argument check of pcl_cellfn_apply / pcl_cellbc_apply: the handle is live and was compiled for these shape constants. */
 int pcl_cellfn_check(const pcl_cellfn *f, int meqn, int maux, int ndim);
 /* Where the handle's block sits in the global grid: lower[ndim] = lower edge of the GLOBAL grid, nstart[ndim] = global
  * index of the block's first interior cell (both 0 until set). */
@@ -321,6 +322,21 @@ int pcl_cellfn_geometry(pcl_solver *s, const double *lower, const int *nstart);
  * into the handle's device on first use and unloaded by pcl_destroy.  After a function that wrote aux the caller
  * refreshes the aux ghost cells: pcl_halo_exchange_aux, then pcl_bc_aux per dimension and side. */
 int pcl_cellfn_apply(pcl_solver *s, pcl_cellfn *f, double t, double dt, const double *params, int nparams);
+/* A boundary condition as a cell function (kind PCL_CELLFN_BC; writes_aux = 0): one launch on the solver's stream over the
+ * ghost cells of side (idim, side: 0 lower, 1 upper) of the SELECTED register -- mbc layers times the WHOLE ghosted
+ * extent of the transverse dimensions, corner cells included, one lane per ghost cell.  The body sees
+ *     q[MEQN]      the ghost cell, read/write, initialised with     aux[MAUX]   the ghost cell's own aux, const
+ *                  its current contents                              p[16]       the parameters of this launch
+ *     c.t          time of the state being filled (stage time)      c.idim, c.side
+ *     c.g          layer, 0 = next to the boundary face .. mbc-1    c.d[NDIM]   cell sizes
+ *     c.i[NDIM]    GLOBAL 0-based indices of the ghost cell (negative on a lower side, >= n on an upper side, in the
+ *                  normal and in the transverse directions);  c.x[NDIM] = lower + (i + 0.5) * d
+ *     qin(m, r), auxin(m, r)   component m of the cell r cells inward from the boundary face on this ghost cell's own
+ *                  normal line (r = 0: the first interior cell); r is clamped to [0, n[idim] - 1]
+ * A component is stored only where its bits changed.  The caller keeps the order of apply_q_bcs: halo exchange, then per
+ * dimension lower and upper, only on blocks that own that boundary.  The argument checks are host-only and come first;
+ * otherwise the bookkeeping of pcl_bc_const. */
+int pcl_cellbc_apply(pcl_solver *s, pcl_cellfn *f, int idim, int side, double t, const double *params, int nparams);
 
 /* ---- SharpClaw (kind = PCL_KIND_SHARPCLAW) ----------------------------------------------------- */
 /* Which register the put/get/bc/strip/halo calls act on (default PCL_REG_Q): the RK stages get

@@ -9,6 +9,9 @@
 // component the body never assigns the comparison folds at compile time, and the store and then the load disappear
 // from the code object (the built-in source kernels leave such planes alone in the same way).
 //
+// A fourth kind, the boundary condition (PCL_CELLFN_BC; pyclaw.CellBC), has a wrapper of its own further
+// down: one lane = one ghost cell of one side, the body's only neighbour reads go inward along the lane's own normal line.
+//
 // libhiprtc is dlopen()ed on first use, like librccl in halo.hpp: a library without it loads and runs every other path.
 #pragma once
 #include <dlfcn.h>
@@ -40,6 +43,21 @@ struct pcl_cell_args {
     int pad_;
     double lower[3], d[3];
     double t, dt;
+    double p[PCL_CELLFN_MAX_PARAMS];
+};
+
+// the same for the boundary-condition wrapper (pcl_cellbc below)
+struct pcl_cellbc_args {
+    double *q;          // the selected register
+    const double *aux;
+    long pitch, plane, slab;
+    int n[3];           // interior cells of this block
+    int mbc;
+    int nstart[3];
+    int idim, side;     // the side this launch fills
+    int ext[3];         // cells with ghosts: the transverse extent of the launch
+    double lower[3], d[3];
+    double t;
     double p[PCL_CELLFN_MAX_PARAMS];
 };
 
@@ -128,9 +146,113 @@ extern "C" __global__ void __launch_bounds__(256) pcl_cellfn(const pcl_cell_args
 }
 )PCLSRC";
 
-static inline const char *cellfn_kind_name(int kind) {
-    return kind == 1 ? "step_src" : kind == 2 ? "dq_src" : kind == 3 ? "start_step" : nullptr;
+// ---- the boundary-condition kind ------------------------------------------------------------------------------------
+// One lane = one ghost cell of side (idim, side): mbc layers times the whole ghosted extent of the transverse
+// dimensions, corner cells included (the reference hands its callback the full qbc, and the y fill sees the x-filled
+// ghosts).  The lanes are numbered x fastest over that box, 256 to a workgroup: a y or z side stores whole rows
+// coalesced; an x side is mbc columns wide, so a wavefront touches 64 / mbc rows -- strided, and O(perimeter).
+// idim and side are run-time fields: one code object serves every side of a solver.
+// qin(m, r) / auxin(m, r) read component m of the cell r cells inward from the boundary face on the lane's own normal
+// line, r clamped to the interior [0, n[idim] - 1]: the address is always an interior cell of the block, which no lane
+// of a side launch writes.
+static const char *const kCellbcHead = R"PCLSRC(
+struct pcl_cell {
+    double t;
+    int idim, side, g;
+    int i[NDIM];
+    double x[NDIM];
+    double d[NDIM];
+};
+struct pcl_cellbc_args {
+    double *q;
+    const double *aux;
+    long pitch, plane, slab;
+    int n[3];
+    int mbc;
+    int nstart[3];
+    int idim, side;
+    int ext[3];
+    double lower[3], d[3];
+    double t;
+    double p[16];
+};
+#define PCL_MAUXN (MAUX > 0 ? MAUX : 1)
+struct pcl_inward {
+    const double *q, *aux;
+    long plane, line, stride;       // line: the lane's cell offset with the normal coordinate at the first ghosted cell
+    int n, mbc, side;
+    __device__ __forceinline__ long at(int r) const {
+        r = r < 0 ? 0 : r > n - 1 ? n - 1 : r;
+        return line + (long)(side == 0 ? mbc + r : mbc + n - 1 - r) * stride;
+    }
+    __device__ __forceinline__ double qin(int m, int r) const { return q[m * plane + at(r)]; }
+    __device__ __forceinline__ double auxin(int m, int r) const { return MAUX > 0 ? aux[m * plane + at(r)] : 0.0; }
+};
+)PCLSRC";
+
+static const char *const kCellbcOpen = R"PCLSRC(
+__device__ __forceinline__ void pcl_cell_body(double (&q)[MEQN], const double (&aux)[PCL_MAUXN], const pcl_cell &c,
+                                              const double (&p)[16], const pcl_inward &pcl_in) {
+    const auto qin = [&pcl_in](int m, int r) { return pcl_in.qin(m, r); };
+    const auto auxin = [&pcl_in](int m, int r) { return pcl_in.auxin(m, r); };
+    (void)qin; (void)auxin;
+)PCLSRC";
+
+static const char *const kCellbcTail = R"PCLSRC(
 }
+#line 1 "pcl_cellbc_wrapper"
+__device__ __forceinline__ bool pcl_bits_differ(double a, double b) {
+    return __builtin_bit_cast(unsigned long long, a) != __builtin_bit_cast(unsigned long long, b);
+}
+extern "C" __global__ void __launch_bounds__(256) pcl_cellbc(const pcl_cellbc_args a) {
+    // the box of this side in ghosted indices: mbc cells along idim, everything across
+    int e[3] = {1, 1, 1};
+    for (int n = 0; n < NDIM; n++) e[n] = n == a.idim ? a.mbc : a.ext[n];
+    const long lane = (long)blockIdx.x * 256 + threadIdx.x;
+    if (lane >= (long)e[0] * e[1] * e[2]) return;
+    int pos[3];
+    pos[0] = (int)(lane % e[0]);
+    pos[1] = (int)(lane / e[0] % e[1]);
+    pos[2] = (int)(lane / ((long)e[0] * e[1]));
+    const long st[3] = {1, a.pitch, a.slab};
+    pcl_cell c;
+    c.t = a.t;
+    c.idim = a.idim;
+    c.side = a.side;
+    c.g = 0;
+    pcl_inward in;
+    in.q = a.q; in.aux = a.aux; in.plane = a.plane; in.line = 0; in.stride = 1;
+    in.n = 1; in.mbc = a.mbc; in.side = a.side;
+    long g = 0;
+    for (int n = 0; n < NDIM; n++) {
+        int k = pos[n];             // ghosted index of the cell along n
+        if (n == a.idim) {
+            c.g = a.side == 0 ? a.mbc - 1 - k : k;
+            if (a.side) k += a.mbc + a.n[n];
+            in.stride = st[n];
+            in.n = a.n[n];
+        } else {
+            in.line += k * st[n];
+        }
+        g += k * st[n];
+        c.i[n] = k - a.mbc + a.nstart[n];
+        c.d[n] = a.d[n];
+        c.x[n] = a.lower[n] + (c.i[n] + 0.5) * a.d[n];
+    }
+    double q0[MEQN], q[MEQN], aux[PCL_MAUXN];
+    for (int m = 0; m < MEQN; m++) { q0[m] = a.q[m * a.plane + g]; q[m] = q0[m]; }
+    for (int m = 0; m < PCL_MAUXN; m++) aux[m] = MAUX > 0 ? a.aux[m * a.plane + g] : 0.0;
+    pcl_cell_body(q, aux, c, a.p, in);
+    for (int m = 0; m < MEQN; m++)
+        if (pcl_bits_differ(q[m], q0[m])) a.q[m * a.plane + g] = q[m];
+}
+)PCLSRC";
+
+static inline const char *cellfn_kind_name(int kind) {
+    return kind == 1 ? "step_src" : kind == 2 ? "dq_src" : kind == 3 ? "start_step" : kind == 4 ? "bc" : nullptr;
+}
+// the __global__ function of a kind's wrapper
+static inline const char *cellfn_entry_name(int kind) { return kind == 4 ? "pcl_cellbc" : "pcl_cellfn"; }
 
 // ---- libhiprtc, loaded on first use ---------------------------------------------------------------------------
 struct HiprtcApi {
@@ -228,15 +350,16 @@ static inline int cellfn_build(int kind, const char *body, const char *preamble,
     if (hiprtc_load(err)) return -1;
     HiprtcApi &a = hiprtc_api();
     const char *kname = cellfn_kind_name(kind);
-    std::string src = kCellfnHead;
+    const bool bc = kind == 4;
+    std::string src = bc ? kCellbcHead : kCellfnHead;
     src += "#line 1 \"preamble\"\n";
     src += preamble;
     src += "\n#line 1 \"pcl_cellfn_wrapper\"\n";
-    src += kCellfnOpen;
+    src += bc ? kCellbcOpen : kCellfnOpen;
     src += std::string("#line 1 \"") + kname + "\"\n";
     src += body;
     src += "\n";
-    src += kCellfnTail;
+    src += bc ? kCellbcTail : kCellfnTail;
     hiprtcProgram prog = nullptr;
     hiprtcResult r = a.hiprtcCreateProgram(&prog, src.c_str(), "pcl_cellfn.hip", 0, nullptr, nullptr);
     if (r != HIPRTC_SUCCESS) { err = std::string("hiprtcCreateProgram: ") + a.hiprtcGetErrorString(r); return -1; }

@@ -1625,7 +1625,7 @@ int pcl_cellfn_compile(int kind, const char *body, const char *preamble, int meq
     if (!body || !out) return fail(PCL_EINVAL, "null argument");
     *out = nullptr;
     if (!preamble) preamble = "";
-    if (!cellfn_kind_name(kind)) return fail(PCL_EINVAL, "pcl_cellfn_compile: kind must be PCL_CELLFN_STEP_SRC, _DQ_SRC or _START_STEP");
+    if (!cellfn_kind_name(kind)) return fail(PCL_EINVAL, "pcl_cellfn_compile: kind must be PCL_CELLFN_STEP_SRC, _DQ_SRC, _START_STEP or _BC");
     if (meqn < 1 || meqn > 64 || maux < 0 || maux > 64) return fail(PCL_EINVAL, "pcl_cellfn_compile: 1 <= meqn <= 64 and 0 <= maux <= 64");
     if (ndim < 1 || ndim > 3) return fail(PCL_EINVAL, "pcl_cellfn_compile: ndim must be 1, 2 or 3");
     if (math != PCL_MATH_EXACT && math != PCL_MATH_FAST && math != PCL_MATH_STRICT) return fail(PCL_EINVAL, "unknown math mode");
@@ -1706,6 +1706,24 @@ int pcl_cellfn_geometry(pcl_solver *s, const double *lower, const int *nstart) {
     return PCL_OK;
 }
 
+// the function of a compiled cell function in this handle's device: its module is loaded on first use
+static int cellfn_loaded(pcl_solver *s, long id, int kind, const void *code, hipFunction_t *fn) {
+    auto it = s->cellfn.by_id.find(id);
+    if (it == s->cellfn.by_id.end()) {
+        CellfnModules::Loaded l;
+        HIP_TRY(hipModuleLoadData(&l.mod, code));
+        const char *entry = cellfn_entry_name(kind);
+        hipError_t e = hipModuleGetFunction(&l.fn, l.mod, entry);
+        if (e != hipSuccess) {
+            (void)hipModuleUnload(l.mod);
+            return fail(PCL_EHIP, std::string("hipModuleGetFunction(") + entry + "): " + hipGetErrorString(e));
+        }
+        it = s->cellfn.by_id.emplace(id, l).first;
+    }
+    *fn = it->second.fn;
+    return PCL_OK;
+}
+
 int pcl_cellfn_apply(pcl_solver *s, pcl_cellfn *f, double t, double dt, const double *params, int nparams) {
     if (s) s->qt.invalidate();            // quiet tiles: not a read-only call (quiet_tiles.hpp)
     if (s) s->ghosts_drop_all();          // exchange-ahead: whatever filled the ghost frames no longer holds
@@ -1725,21 +1743,14 @@ int pcl_cellfn_apply(pcl_solver *s, pcl_cellfn *f, double t, double dt, const do
         kind = f->kind;
         code = f->code.data();        // stays put while the caller holds its reference
     }
+    if (kind == PCL_CELLFN_BC)
+        return fail(PCL_EINVAL, "pcl_cellfn_apply: a boundary-condition cell function runs through pcl_cellbc_apply");
     if (kind == PCL_CELLFN_DQ_SRC && s->cfg.kind != PCL_KIND_SHARPCLAW)
         return fail(PCL_EINVAL, "pcl_cellfn_apply: a dq_src cell function needs a SharpClaw solver (the dq register)");
     if (s->cfg.maux > 0 && !s->aux) return fail(PCL_ESTATE, "pcl_cellfn_apply: no aux array on the device");
     HIP_TRY(hipSetDevice(s->cfg.device));
-    auto it = s->cellfn.by_id.find(id);
-    if (it == s->cellfn.by_id.end()) {
-        CellfnModules::Loaded l;
-        HIP_TRY(hipModuleLoadData(&l.mod, code));
-        hipError_t e = hipModuleGetFunction(&l.fn, l.mod, "pcl_cellfn");
-        if (e != hipSuccess) {
-            (void)hipModuleUnload(l.mod);
-            return fail(PCL_EHIP, std::string("hipModuleGetFunction(pcl_cellfn): ") + hipGetErrorString(e));
-        }
-        it = s->cellfn.by_id.emplace(id, l).first;
-    }
+    hipFunction_t fn = nullptr;
+    if (int rc = cellfn_loaded(s, id, kind, code, &fn)) return rc;
     a.q = cur(s);
     a.dq = kind == PCL_CELLFN_DQ_SRC ? s->sreg[PCL_REG_DQ] : nullptr;
     a.aux = s->aux;
@@ -1759,8 +1770,65 @@ int pcl_cellfn_apply(pcl_solver *s, pcl_cellfn *f, double t, double dt, const do
     if (a.n[1] > 65535 || a.n[2] > 65535) return fail(PCL_EINVAL, "pcl_cellfn_apply: more than 65535 rows or planes");
     size_t size = sizeof(a);
     void *config[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &a, HIP_LAUNCH_PARAM_BUFFER_SIZE, &size, HIP_LAUNCH_PARAM_END};
-    HIP_TRY(hipModuleLaunchKernel(it->second.fn, (unsigned)((a.n[0] + 255) / 256), (unsigned)a.n[1], (unsigned)a.n[2], 256, 1, 1,
+    HIP_TRY(hipModuleLaunchKernel(fn, (unsigned)((a.n[0] + 255) / 256), (unsigned)a.n[1], (unsigned)a.n[2], 256, 1, 1,
                                   0, s->stream, nullptr, config));
+    return PCL_OK;
+}
+
+int pcl_cellbc_apply(pcl_solver *s, pcl_cellfn *f, int idim, int side, double t, const double *params, int nparams) {
+    if (s) s->qt.invalidate();            // quiet tiles: not a read-only call (quiet_tiles.hpp)
+    if (s) s->ghosts_drop_all();          // exchange-ahead: whatever filled the ghost frames no longer holds
+    // host-only checks first, in an order that needs no solver for the ones that do not depend on it
+    if (nparams < 0 || nparams > PCL_CELLFN_MAX_PARAMS)
+        return fail(PCL_EINVAL, "pcl_cellbc_apply: a cell function takes at most 16 parameters");
+    if (idim < 0 || idim > 2 || side < 0 || side > 1) return fail(PCL_EINVAL, "pcl_cellbc_apply: bad idim/side");
+    if (!f || (nparams > 0 && !params)) return fail(PCL_EINVAL, "null argument");
+    long id = 0;
+    const void *code = nullptr;
+    {
+        CellfnCache &c = cellfn_cache();
+        std::lock_guard<std::mutex> lock(c.mu);
+        if (!c.live.count(f)) return fail(PCL_EINVAL, "not a live cell function handle");
+        if (f->kind != PCL_CELLFN_BC)
+            return fail(PCL_EINVAL, std::string("pcl_cellbc_apply: the handle is a ") + cellfn_kind_name(f->kind) +
+                                        " cell function, not a boundary condition");
+        if (!s) return fail(PCL_EINVAL, "null argument");
+        if (int rc = cellfn_check_locked(c, f, s->cfg.meqn, s->cfg.maux, s->cfg.ndim)) return rc;
+        id = f->id;
+        code = f->code.data();        // stays put while the caller holds its reference
+    }
+    if (idim >= s->cfg.ndim) return fail(PCL_EINVAL, "pcl_cellbc_apply: bad idim/side");
+    if (s->cfg.maux > 0 && !s->aux) return fail(PCL_ESTATE, "pcl_cellbc_apply: no aux array on the device");
+    HIP_TRY(hipSetDevice(s->cfg.device));
+    hipFunction_t fn = nullptr;
+    if (int rc = cellfn_loaded(s, id, PCL_CELLFN_BC, code, &fn)) return rc;
+    pcl_cellbc_args a;
+    memset(&a, 0, sizeof(a));
+    a.q = cur(s);
+    a.aux = s->aux;
+    a.pitch = s->pitch;
+    a.plane = s->plane;
+    a.slab = s->pitch * s->J;
+    a.mbc = s->cfg.mbc;
+    a.idim = idim;
+    a.side = side;
+    const int ext[3] = {s->I, s->J, s->K};
+    long lanes = 1;
+    for (int k = 0; k < 3; k++) {
+        a.n[k] = k < s->cfg.ndim ? s->cfg.n[k] : 1;
+        a.ext[k] = ext[k];
+        a.nstart[k] = s->cf_nstart[k];
+        a.lower[k] = s->cf_lower[k];
+        a.d[k] = s->cfg.d[k];
+        lanes *= k == idim ? s->cfg.mbc : ext[k];
+    }
+    a.t = t;
+    for (int k = 0; k < nparams; k++) a.p[k] = params[k];
+    const long groups = (lanes + 255) / 256;
+    if (groups > 0x7fffffffL) return fail(PCL_EINVAL, "pcl_cellbc_apply: too many ghost cells for one launch");
+    size_t size = sizeof(a);
+    void *config[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &a, HIP_LAUNCH_PARAM_BUFFER_SIZE, &size, HIP_LAUNCH_PARAM_END};
+    HIP_TRY(hipModuleLaunchKernel(fn, (unsigned)groups, 1, 1, 256, 1, 1, 0, s->stream, nullptr, config));
     return PCL_OK;
 }
 

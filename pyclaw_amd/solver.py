@@ -173,6 +173,54 @@ class CellStartStep(CellFunction):
             solver._aux_host_stale = True
 
 
+class CellBC(CellFunction, DeviceBC):
+    """A custom boundary condition as a cell function (see ``CellFunction``): assigned to ``solver.user_bc_lower`` and /
+    or ``user_bc_upper`` (with ``bc_lower[idim] = BC.custom``) in place of a Python ``bc(state, dim, t, qbc, mbc)``.  The
+    body is compiled at ``setup()`` and run as one launch per custom side over the ghost cells of that side, on the
+    resident arrays -- nothing goes through the host.
+
+    One lane is one ghost cell.  A launch covers ``mbc`` layers times the whole ghosted extent of the transverse
+    dimensions, corner cells included, at the place ``apply_q_bcs`` gives a callback: behind the halo exchange, per
+    dimension, lower then upper, on the blocks that own that boundary (so the y fill sees x-filled ghosts).  The body sees
+
+    * ``q[MEQN]``, writable, initialised with the ghost cell's current contents; ``aux[MAUX]`` (const), the ghost
+      cell's own aux; ``p[]`` as for every cell function;
+    * ``c.t``, the time of the state being filled (the stage time in a SharpClaw stage); ``c.idim``, ``c.side``
+      (0 lower, 1 upper); ``c.g``, the layer, 0 next to the boundary face up to ``mbc - 1``;
+    * ``c.i[NDIM]``, the GLOBAL 0-based indices of the ghost cell -- negative on a lower side, >= n on an upper side,
+      in the normal and in the transverse directions --, ``c.x[NDIM] = lower + (i + 0.5) * d`` and ``c.d[NDIM]``;
+    * ``qin(m, r)`` and ``auxin(m, r)``: component ``m`` of the cell ``r`` cells inward from the boundary face on this
+      ghost cell's own line along the normal, ``r = 0`` the first interior cell.  ``r`` is clamped to
+      ``[0, n[idim] - 1]``; ``m`` is the caller's responsibility, like ``q[m]``.  These are the only neighbour reads:
+      no launch reads a cell it writes.
+
+    ``c.idim`` and ``c.side`` are run-time fields, so one object (and one compiled kernel) serves every dimension and
+    both sides; ``dims`` restricts it to some dimensions, as on ``ConstantStateBC``.  A component is stored only where
+    its bits changed.  ``SphereMirrorBC`` cannot be written this way (it reads across the transverse direction).
+
+    ``_device_bc_spec`` is ``None`` for a solver with a ``CellBC``: every step runs ``apply_q_bcs`` followed by
+    ``pcl_step_hyperbolic`` (``pcl_sharp_stage`` / ``pcl_sharp_dq``), with step-ahead and exchange-ahead off -- the
+    fused ``pcl_bc_step`` knows the built-in fills only."""
+
+    kind = 4
+
+    def __init__(self, body, params=(), preamble="", dims=None):
+        CellFunction.__init__(self, body, params, preamble)
+        self.dims = dims
+
+    def apply(self, solver, idim, side, state=None):
+        """Fill the ghost cells of side (idim, side) of the solver's selected register; ``state.t`` is the body's c.t."""
+        if self.dims is not None and idim not in self.dims:
+            return
+        if state is None:
+            state = solver._state
+        self._compile_for(solver, solver._state)       # (a cache look-up unless assigned or changed after setup())
+        p = self._params
+        _lib.check(_lib.lib().pcl_cellbc_apply(solver._h, self._fn, int(idim), int(side), float(state.t),
+                                               _lib.d(p) if len(p) else None, len(p)))
+        solver._host_stale = True
+
+
 class Solver(object):
     r"""Pyclaw solver superclass; see the reference docstring (solver.py:25-125)."""
 
@@ -289,12 +337,13 @@ class Solver(object):
 
     # ------------------------------------------------------------------ cell functions
     def _cell_functions(self):
-        fns = [getattr(self, name, None) for name in ('start_step', 'step_src', 'dq_src')]
+        fns = [getattr(self, name, None) for name in ('start_step', 'step_src', 'dq_src', 'user_bc_lower', 'user_bc_upper')]
         return [f for f in fns if isinstance(f, CellFunction)]
 
     def _setup_cell_functions(self, state):
         """Called by setup() once the device handle exists: tell the library where this block sits in the global grid
-        (a body's c.i and c.x are global) and compile the cell functions among start_step / step_src / dq_src."""
+        (a body's c.i and c.x are global) and compile the cell functions among start_step / step_src / dq_src and the
+        custom boundary conditions."""
         dims = state.grid.dimensions
         lower = np.array([dim.lower for dim in dims], dtype=np.float64)
         nstart = np.array([dim.nstart for dim in dims], dtype=np.int32)
@@ -412,6 +461,9 @@ class Solver(object):
     def _custom_bc(self, state, dim, idim, side, fn):
         if fn is None:
             raise Exception("Custom BC requested but user_bc_%s is not set" % ("lower", "upper")[side])
+        if isinstance(fn, CellBC):
+            fn.apply(self, idim, side, state)       # the state carries the time (a stage's, in SharpClaw)
+            return
         if isinstance(fn, DeviceBC):
             fn.apply(self, idim, side)
             return
