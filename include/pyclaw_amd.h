@@ -530,6 +530,20 @@ int pcl_halo_region(int dir, int send, int I, int J, int mbc, int out_i0_j0_ni_n
  * of side out[3] (0 lower, 1 upper) instead (PCL_BC_CUSTOM).  An interior cell, and a ghost cell of a side without a
  * fill, maps to itself. */
 int pcl_ghost_map(int k, int n, int mbc, int lo, int hi, int out_src_neg_cst_side[4]);
+/* Host-only helpers (no GPU needed), for the test suite: the two host state machines of the dim-split 2-D step driven
+ * through n scripted events, each on a fresh object, the decisions written to out[i].
+ * pcl_step_form_trace (csrc/step_form.hpp), event[i]: 0 a step, begin(can = a[i], tune = b[i], listed[i], ntiles) then
+ * end(seconds[i]): out = form | 2 * timed; 1 next_is_plain_onek(can = a[i], mode = b[i]); 2 adopted(mode = b[i]) and
+ * 3 ran(form = a[i]) and 4 forget_last(): out = last(); 5 out = the steps counted in form a[i].
+ * pcl_step_ahead_trace (csrc/step_ahead.hpp), armed once with the first four arguments; event i has the spec bc[4 i ..],
+ * cstate[32 i ..]; event[i]: 0 out = wants(c = x[i], ran[i], ntiles[i], next_plain_onek = flag[i]); 1 out_dt =
+ * next_dt(dt = x[i], c = y[i]); 2 enqueued(dt = x[i], seq = i, spec, ran[i]); 3 out = matches(spec, dt = x[i],
+ * carry = flag[i]); 4 missed(); 5 adopted(); 6 out = dropped(), out_dt = the tile count then reported. */
+int pcl_step_form_trace(long n, const int *event, const int *a, const int *b, const long *listed, long ntiles,
+                        const double *seconds, int *out);
+int pcl_step_ahead_trace(int on, double cfl_desired, double cfl_max, double dt_max, long n, const int *event,
+                         const int *flag, const double *x, const double *y, const long *ran, const long *ntiles,
+                         const int *bc, const double *cstate, int *out, double *out_dt);
 
 /* ---- debug / self-test --------------------------------------------------------------- */
 /* Runs the wavefront neighbour-shift primitive on 64 values: left[l]=in[l-1],

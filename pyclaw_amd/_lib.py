@@ -137,6 +137,9 @@ PROTOTYPES = {
     "pcl_allreduce_max": (C.c_int, [C.c_void_p, dp]),
     "pcl_halo_region": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, ip]),
     "pcl_ghost_map": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, ip]),
+    "pcl_step_form_trace": (C.c_int, [C.c_long, ip, ip, ip, C.POINTER(C.c_long), C.c_long, dp, ip]),
+    "pcl_step_ahead_trace": (C.c_int, [C.c_int, C.c_double, C.c_double, C.c_double, C.c_long, ip, ip, dp, dp,
+                                       C.POINTER(C.c_long), C.POINTER(C.c_long), ip, dp, ip, dp]),
     "pcl_debug_wave_shift": (C.c_int, [dp, dp, dp]),
 }
 
