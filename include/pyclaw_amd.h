@@ -67,7 +67,8 @@ extern "C" {
                                     /* the unsplit step follows the app's step2qcor.f (conservation fix qcor.f) instead of step2.f */
 #define PCL_RP_PSYSTEM_FWAVE_2D 17 /* rpn2/rpt2_psystem.f (test/psystem/Makefile:5); F-WAVE solver: fwave = 1; aux as above + aux(4)=eps */
                                    /* (read by rpt2 only); classic and SharpClaw (weno_order 5: mbc 3), fwave = 1 for both      */
-#define PCL_RP_VC_ACOUSTICS_3D 20 /* rpn3_vc_acoustics.f (test/acoustics/3d/Makefile); aux(1)=Z, aux(2)=c; dim-split only */
+#define PCL_RP_VC_ACOUSTICS_3D 20 /* rpn3_vc_acoustics.f (test/acoustics/3d/Makefile); aux(1)=Z, aux(2)=c; dim-split, and unsplit  */
+                                  /* (rpt3/rptt3_vc_acoustics.f) without a capacity function                                   */
 
 /* boundary condition types = pyclaw.BC (src/pyclaw/solver.py:17-23) */
 #define PCL_BC_CUSTOM 0
@@ -130,6 +131,12 @@ typedef struct pcl_config {
 const char *pcl_last_error(void);
 int pcl_version(void);
 int pcl_device_count(void);                     /* never initialises a context          */
+/* What the library knows about the built-in Riemann solver `rp`, read off the solver itself; touches no GPU.
+ * info = ndim, meqn, mwaves, naux (aux components the normal solver reads), fwave (an f-wave solver: cfg.fwave must be
+ * 1), onek / onek_aux (the one-kernel dimension-split 2-D step has it, without / with its aux arrays staged), sharp
+ * (SharpClaw kernels, weno_order 5), sharp_high (weno_order 7..17 too), sharp_wave (char_decomp = 1).
+ * PCL_EINVAL for an id no solver has. */
+int pcl_rp_info(int rp, int info[10]);
 
 /* ---- layer 1: f2py-shaped stateless calls on host arrays ---------------------------- */
 /* Stateless for the caller like the f2py modules; internally the device buffers of the last call are kept and reused

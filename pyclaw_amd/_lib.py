@@ -48,6 +48,7 @@ PROTOTYPES = {
     "pcl_last_error": (C.c_char_p, []),
     "pcl_version": (C.c_int, []),
     "pcl_device_count": (C.c_int, []),
+    "pcl_rp_info": (C.c_int, [C.c_int, ip]),
     "pcl_layer1_release": (None, []),
     "pcl_layer1_math": (C.c_int, [C.c_int]),
     "pcl_step1": (C.c_int, [C.c_int, dp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, dp, dp,

@@ -332,7 +332,7 @@ class ClawSolver(Solver):
         setup and again by step() whenever step_src / src_split were changed afterwards."""
         import os
         fuse = (isinstance(self.step_src, EulerRadialSource) and self.src_split == 1 and self.ndim == 2
-                and self._rp_id == 11 and state.mcapa < 0 and os.environ.get("PCL_FUSE_SRC", "1") != "0")
+                and self._rp_id == riemann.rp_euler_5wave_2d.id and state.mcapa < 0 and os.environ.get("PCL_FUSE_SRC", "1") != "0")
         if fuse:
             _lib.check(_lib.lib().pcl_fuse_source(self._h, 1, _lib.d(self.step_src.params), 2))
         elif self._src_fused:

@@ -25,6 +25,30 @@ int hip_fail(std::string &err, const char *what, hipError_t e) {
     return PCL_EHIP;
 }
 
+// Every built-in Riemann solver, once.  with(rp, f) calls f(RpTag<RP>{}) for the solver whose ID is rp and returns what f
+// returns: a PCL_* code, or RP_NONE where that solver has no kernel of the kind asked for; RP_NONE too if no solver has
+// the id.  What f instantiates under `if constexpr` on the solver's traits (rp.hpp) is all that gets built.
+constexpr int RP_NONE = 1;      // no PCL_* code is positive
+template <class RP> struct RpTag { using type = RP; };
+template <class... RP> struct RpList {
+    template <class F> static int with(int rp, F &&f) {
+        int rc = RP_NONE;
+        (void)((rp == RP::ID && ((rc = f(RpTag<RP>{})), true)) || ...);
+        return rc;
+    }
+    static const RpFacts *facts(int rp) {
+        static constexpr RpFacts table[] = {{RP::ID, RP::NDIM, RP::MEQN, RP::MWAVES, RP::NAUX, IsFwave<RP>::value,
+                                             RP::ONEK && RP::NAUX == 0, RP::ONEK && RP::NAUX > 0, RP::SHARP,
+                                             RP::SHARP_HIGH, RP::SHARP_WAVE}...};
+        for (const RpFacts &f : table)
+            if (f.id == rp) return &f;
+        return nullptr;
+    }
+};
+using Solvers = RpList<Advection1D, Acoustics1D, Burgers1D, Euler1D, Shallow1D, AdvectionColor1D, Elasticity1D, Acoustics2D,
+                       Euler5, Advection2D, Shallow2D, VcAcoustics2D, VcAdvection2D, ShallowSphere, PSystem2D, VcAcoustics3D>;
+int not_built(std::string &err, const char *why) { err = why; return PCL_EINVAL; }
+
 template <class RP, int IXY, bool DIM1> int launch(const SweepLaunch &l, std::string &err) {
     using T = TileShape<IXY>;
     const SweepArgs &a = l.a;
@@ -76,39 +100,15 @@ template <class RP, int IXY, bool DIM1> int launch(const SweepLaunch &l, std::st
 
 // one directional sweep qin -> qout; ids 1 = x (or the 1-D step), 2 = y
 int launch_sweep(const SweepLaunch &l, std::string &err) {
-    const int rp = l.rp;
-    if (l.ndim == 1) {
-        if (rp == PCL_RP_ADVECTION_1D) return launch<Advection1D, 1, true>(l, err);
-        if (rp == PCL_RP_ACOUSTICS_1D) return launch<Acoustics1D, 1, true>(l, err);
-        if (rp == PCL_RP_BURGERS_1D) return launch<Burgers1D, 1, true>(l, err);
-        if (rp == PCL_RP_EULER_1D) return launch<Euler1D, 1, true>(l, err);
-        if (rp == PCL_RP_SHALLOW_1D) return launch<Shallow1D, 1, true>(l, err);
-        if (rp == PCL_RP_ADVECTION_COLOR_1D) return launch<AdvectionColor1D, 1, true>(l, err);
-        if (rp == PCL_RP_ELASTICITY_FWAVE_1D) return launch<Elasticity1D, 1, true>(l, err);
-        err = "Riemann solver id is not a 1-D solver";
-        return PCL_EINVAL;
-    }
-    if (l.ids == 1) {
-        if (rp == PCL_RP_ACOUSTICS_2D) return launch<Acoustics2D, 1, false>(l, err);
-        if (rp == PCL_RP_ADVECTION_2D) return launch<Advection2D, 1, false>(l, err);
-        if (rp == PCL_RP_SHALLOW_2D) return launch<Shallow2D, 1, false>(l, err);
-        if (rp == PCL_RP_VC_ACOUSTICS_2D) return launch<VcAcoustics2D, 1, false>(l, err);
-        if (rp == PCL_RP_VC_ADVECTION_2D) return launch<VcAdvection2D, 1, false>(l, err);
-        if (rp == PCL_RP_SHALLOW_SPHERE_2D) return launch<ShallowSphere, 1, false>(l, err);
-        if (rp == PCL_RP_PSYSTEM_FWAVE_2D) return launch<PSystem2D, 1, false>(l, err);
-        if (rp == PCL_RP_EULER5_2D) return launch<Euler5, 1, false>(l, err);
-    } else {
-        if (rp == PCL_RP_ACOUSTICS_2D) return launch<Acoustics2D, 2, false>(l, err);
-        if (rp == PCL_RP_ADVECTION_2D) return launch<Advection2D, 2, false>(l, err);
-        if (rp == PCL_RP_SHALLOW_2D) return launch<Shallow2D, 2, false>(l, err);
-        if (rp == PCL_RP_VC_ACOUSTICS_2D) return launch<VcAcoustics2D, 2, false>(l, err);
-        if (rp == PCL_RP_VC_ADVECTION_2D) return launch<VcAdvection2D, 2, false>(l, err);
-        if (rp == PCL_RP_SHALLOW_SPHERE_2D) return launch<ShallowSphere, 2, false>(l, err);
-        if (rp == PCL_RP_PSYSTEM_FWAVE_2D) return launch<PSystem2D, 2, false>(l, err);
-        if (rp == PCL_RP_EULER5_2D) return launch<Euler5, 2, false>(l, err);
-    }
-    err = "Riemann solver id is not a 2-D solver";
-    return PCL_EINVAL;
+    const int rc = Solvers::with(l.rp, [&](auto tag) {
+        using RP = typename decltype(tag)::type;
+        if constexpr (RP::NDIM == 1) return l.ndim == 1 ? launch<RP, 1, true>(l, err) : RP_NONE;
+        else if constexpr (RP::NDIM == 2)
+            return l.ndim == 1 ? RP_NONE : l.ids == 1 ? launch<RP, 1, false>(l, err) : launch<RP, 2, false>(l, err);
+        else return RP_NONE;
+    });
+    if (rc != RP_NONE) return rc;
+    return not_built(err, l.ndim == 1 ? "Riemann solver id is not a 1-D solver" : "Riemann solver id is not a 2-D solver");
 }
 
 // the whole dimension-split 2-D step, qin -> qout (classic_fused.hpp); l.a as for the x pass + a.dtd_t = dt/dy and
@@ -162,22 +162,19 @@ template <class RP> int launch_step2ds_t(const SweepLaunch &l, std::string &err)
 }
 }  // namespace
 int launch_step2ds(const SweepLaunch &l, std::string &err) {
-    if (l.rp == PCL_RP_EULER5_2D) return launch_step2ds_t<Euler5>(l, err);
-    if (l.rp == PCL_RP_ACOUSTICS_2D) return launch_step2ds_t<Acoustics2D>(l, err);
-    if (l.rp == PCL_RP_ADVECTION_2D) return launch_step2ds_t<Advection2D>(l, err);
-    if (l.rp == PCL_RP_SHALLOW_2D) return launch_step2ds_t<Shallow2D>(l, err);
-    if (l.rp == PCL_RP_VC_ACOUSTICS_2D) return launch_step2ds_t<VcAcoustics2D>(l, err);
-    if (l.rp == PCL_RP_VC_ADVECTION_2D) return launch_step2ds_t<VcAdvection2D>(l, err);
-    if (l.rp == PCL_RP_PSYSTEM_FWAVE_2D) return launch_step2ds_t<PSystem2D>(l, err);
-    err = "step2ds kernel: no instantiation for this Riemann solver";
-    return PCL_EINVAL;
+    const int rc = Solvers::with(l.rp, [&](auto tag) {
+        using RP = typename decltype(tag)::type;
+        if constexpr (RP::ONEK) return launch_step2ds_t<RP>(l, err);
+        else return RP_NONE;
+    });
+    return rc != RP_NONE ? rc : not_built(err, "step2ds kernel: no instantiation for this Riemann solver");
 }
 
 // 3-D dimension-split sweep along direction l.ids (classic.hpp: sweep3_kernel)
 int launch_sweep3(const SweepLaunch &l, std::string &err) {
     const SweepArgs &a = l.a;
     if (l.fwave) { err = "fwave: no 3-D f-wave Riemann solver is built in"; return PCL_EINVAL; }
-    if (l.rp != PCL_RP_VC_ACOUSTICS_3D) { err = "Riemann solver id is not a 3-D solver"; return PCL_EINVAL; }
+    if (l.rp != VcAcoustics3D::ID) { err = "Riemann solver id is not a 3-D solver"; return PCL_EINVAL; }
     const int n_ac = l.ids == 1 ? a.n_ac : a.n_ac + (LINE - a.mbc);  // y, z: columns counted from the line boundary
     const int ac = l.ids == 1 ? 4 : 16, adv = l.ids == 1 ? 4 * STRIP : STRIP;   // tile shape, classic.hpp
     const int ntiles_ac = (n_ac + ac - 1) / ac, ntiles_al = (a.m_al + adv - 1) / adv;
@@ -240,7 +237,7 @@ template <class RP, int DIR> int launch_unsplit3_t(const Unsplit3Launch &l, std:
 }  // namespace
 
 int launch_unsplit3(const Unsplit3Launch &l, std::string &err) {
-    if (l.rp != PCL_RP_VC_ACOUSTICS_3D) { err = "Riemann solver id is not a 3-D solver with transverse solvers"; return PCL_EINVAL; }
+    if (l.rp != VcAcoustics3D::ID) { err = "Riemann solver id is not a 3-D solver with transverse solvers"; return PCL_EINVAL; }
     if (l.a.mcapa > 0) { err = "3-D: capacity function not implemented"; return PCL_EINVAL; }
     if (l.dir == 1) return launch_unsplit3_t<VcAcoustics3D, 1>(l, err);
     if (l.dir == 2) return launch_unsplit3_t<VcAcoustics3D, 2>(l, err);
@@ -248,6 +245,8 @@ int launch_unsplit3(const Unsplit3Launch &l, std::string &err) {
 }
 
 #if !PCL_FAST
+// the host layer's view of the solver list (sweep_args.hpp: RpFacts; nothing in it depends on the arithmetic mode)
+const RpFacts *rp_facts(int rp) { return Solvers::facts(rp); }
 // the same for the one-kernel step (classic_fused.hpp): tile (ty, tx) reads rows mbc-2+F_OWN_R*ty .. +F_ROWS-1 and columns
 // mbc-2+60*tx .. +63; box = [ty_lo, ty_hi) x [tx_lo, tx_hi), ntiles = (nty, ntx)
 bool step2ds_interior_box(const SweepArgs &a, int box[4], int ntiles[2]) {
@@ -379,20 +378,15 @@ template <class RP> int launch_unsplit_t(const SweepLaunch &l, const double *qx,
 }  // namespace
 
 int launch_unsplit(const SweepLaunch &l, const double *qx, std::string &err) {
-    if ((l.fwave != 0) != (l.rp == PCL_RP_PSYSTEM_FWAVE_2D)) {
-        err = "solver.fwave must be True for an f-wave Riemann solver and only for one";
-        return PCL_EINVAL;
-    }
-    if (l.rp == PCL_RP_PSYSTEM_FWAVE_2D) return launch_unsplit_t<PSystem2D>(l, qx, err);
-    if (l.rp == PCL_RP_ACOUSTICS_2D) return launch_unsplit_t<Acoustics2D>(l, qx, err);
-    if (l.rp == PCL_RP_ADVECTION_2D) return launch_unsplit_t<Advection2D>(l, qx, err);
-    if (l.rp == PCL_RP_SHALLOW_2D) return launch_unsplit_t<Shallow2D>(l, qx, err);
-    if (l.rp == PCL_RP_VC_ACOUSTICS_2D) return launch_unsplit_t<VcAcoustics2D>(l, qx, err);
-    if (l.rp == PCL_RP_VC_ADVECTION_2D) return launch_unsplit_t<VcAdvection2D>(l, qx, err);
-    if (l.rp == PCL_RP_EULER5_2D) return launch_unsplit_t<Euler5>(l, qx, err);
-    if (l.rp == PCL_RP_SHALLOW_SPHERE_2D) return launch_unsplit_t<ShallowSphere>(l, qx, err);
-    err = "Riemann solver id is not a 2-D solver";
-    return PCL_EINVAL;
+    const RpFacts *f = Solvers::facts(l.rp);       // the flag follows the solver, among those this step has
+    if ((l.fwave != 0) != (f && f->ndim == 2 && f->fwave))
+        return not_built(err, "solver.fwave must be True for an f-wave Riemann solver and only for one");
+    const int rc = Solvers::with(l.rp, [&](auto tag) {
+        using RP = typename decltype(tag)::type;
+        if constexpr (RP::NDIM == 2) return launch_unsplit_t<RP>(l, qx, err);
+        else return RP_NONE;
+    });
+    return rc != RP_NONE ? rc : not_built(err, "Riemann solver id is not a 2-D solver");
 }
 
 // SharpClaw: dq of one direction (x writes dq, y accumulates)
@@ -446,7 +440,7 @@ template <class RP, int IXY, int K> int launch_sharp_k(const SweepLaunch &l, std
 }
 // mbc = (weno_order+1)/2 (sharpclaw.py:479).  HIGH = this solver also has the kernels of weno_order 7..17 (mbc 4..9):
 // the 1-D solvers, 2-D advection, acoustics and Euler; the others are built for mbc = 3 only.
-template <class RP, int IXY, bool HIGH = false> int launch_sharp_t(const SweepLaunch &l, std::string &err) {
+template <class RP, int IXY, bool HIGH> int launch_sharp_t(const SweepLaunch &l, std::string &err) {
     if (l.a.mbc == 3) return launch_sharp_k<RP, IXY, 3>(l, err);
     if constexpr (HIGH) {
         switch (l.a.mbc) {
@@ -483,54 +477,30 @@ template <class RP> int launch_sharp1w(const SweepLaunch &l, std::string &err) {
 }  // namespace
 
 int launch_sharp(const SweepLaunch &l, std::string &err) {
-    const int rp = l.rp;
-    if ((l.fwave != 0) != (rp == PCL_RP_PSYSTEM_FWAVE_2D)) {
-        err = "solver.fwave must be True for an f-wave Riemann solver and only for one";
-        return PCL_EINVAL;
-    }
+    const RpFacts *f = Solvers::facts(l.rp);       // the flag follows the solver, among those with SharpClaw kernels
+    if ((l.fwave != 0) != (f && f->sharp && f->fwave))
+        return not_built(err, "solver.fwave must be True for an f-wave Riemann solver and only for one");
     if (l.char_decomp == 1) {
         // 1d/sharpclaw/flux1.f90:80-107 (the 2-D flux1.f90 calls rpn2 with a wrong argument list there and cannot run)
-        if (l.ndim != 1 || l.a.mbc != 3 || (l.lim_type != 1 && l.lim_type != 2) || l.fwave || l.a.src_id != 0) {
-            err = "SharpClaw char_decomp = 1: 1-D, lim_type 1 (tvd2_wave) or 2 (weno5_wave), mbc 3, no f-wave solver";
-            return PCL_EINVAL;
-        }
-        if (rp == PCL_RP_ADVECTION_1D) return launch_sharp1w<Advection1D>(l, err);
-        if (rp == PCL_RP_ACOUSTICS_1D) return launch_sharp1w<Acoustics1D>(l, err);
-        if (rp == PCL_RP_BURGERS_1D) return launch_sharp1w<Burgers1D>(l, err);
-        if (rp == PCL_RP_EULER_1D) return launch_sharp1w<Euler1D>(l, err);
-        if (rp == PCL_RP_SHALLOW_1D) return launch_sharp1w<Shallow1D>(l, err);
-        if (rp == PCL_RP_ADVECTION_COLOR_1D) return launch_sharp1w<AdvectionColor1D>(l, err);
-        err = "SharpClaw char_decomp = 1: advection, colour equation, acoustics, Burgers, Euler, shallow water in 1-D";
-        return PCL_EINVAL;
+        if (l.ndim != 1 || l.a.mbc != 3 || (l.lim_type != 1 && l.lim_type != 2) || l.fwave || l.a.src_id != 0)
+            return not_built(err, "SharpClaw char_decomp = 1: 1-D, lim_type 1 (tvd2_wave) or 2 (weno5_wave), mbc 3, no f-wave solver");
+        const int rc = Solvers::with(l.rp, [&](auto tag) {
+            using RP = typename decltype(tag)::type;
+            if constexpr (RP::SHARP_WAVE) return launch_sharp1w<RP>(l, err);
+            else return RP_NONE;
+        });
+        return rc != RP_NONE ? rc
+                             : not_built(err, "SharpClaw char_decomp = 1: advection, colour equation, acoustics, Burgers, Euler, shallow water in 1-D");
     }
-    if (l.ndim == 1) {
-        if (rp == PCL_RP_ADVECTION_1D) return launch_sharp_t<Advection1D, 1, true>(l, err);
-        if (rp == PCL_RP_ACOUSTICS_1D) return launch_sharp_t<Acoustics1D, 1, true>(l, err);
-        if (rp == PCL_RP_BURGERS_1D) return launch_sharp_t<Burgers1D, 1, true>(l, err);
-        if (rp == PCL_RP_EULER_1D) return launch_sharp_t<Euler1D, 1, true>(l, err);
-        if (rp == PCL_RP_SHALLOW_1D) return launch_sharp_t<Shallow1D, 1, true>(l, err);
-        if (rp == PCL_RP_ADVECTION_COLOR_1D) return launch_sharp_t<AdvectionColor1D, 1, true>(l, err);
-    } else if (l.ids == 1) {
-        if (rp == PCL_RP_ACOUSTICS_2D) return launch_sharp_t<Acoustics2D, 1, true>(l, err);
-        if (rp == PCL_RP_ADVECTION_2D) return launch_sharp_t<Advection2D, 1, true>(l, err);
-        if (rp == PCL_RP_SHALLOW_2D) return launch_sharp_t<Shallow2D, 1>(l, err);
-        if (rp == PCL_RP_VC_ACOUSTICS_2D) return launch_sharp_t<VcAcoustics2D, 1>(l, err);
-        if (rp == PCL_RP_VC_ADVECTION_2D) return launch_sharp_t<VcAdvection2D, 1>(l, err);
-        if (rp == PCL_RP_SHALLOW_SPHERE_2D) return launch_sharp_t<ShallowSphere, 1>(l, err);
-        if (rp == PCL_RP_EULER5_2D) return launch_sharp_t<Euler5, 1, true>(l, err);
-        if (rp == PCL_RP_PSYSTEM_FWAVE_2D) return launch_sharp_t<PSystem2D, 1>(l, err);
-    } else {
-        if (rp == PCL_RP_ACOUSTICS_2D) return launch_sharp_t<Acoustics2D, 2, true>(l, err);
-        if (rp == PCL_RP_ADVECTION_2D) return launch_sharp_t<Advection2D, 2, true>(l, err);
-        if (rp == PCL_RP_SHALLOW_2D) return launch_sharp_t<Shallow2D, 2>(l, err);
-        if (rp == PCL_RP_VC_ACOUSTICS_2D) return launch_sharp_t<VcAcoustics2D, 2>(l, err);
-        if (rp == PCL_RP_VC_ADVECTION_2D) return launch_sharp_t<VcAdvection2D, 2>(l, err);
-        if (rp == PCL_RP_SHALLOW_SPHERE_2D) return launch_sharp_t<ShallowSphere, 2>(l, err);
-        if (rp == PCL_RP_EULER5_2D) return launch_sharp_t<Euler5, 2, true>(l, err);
-        if (rp == PCL_RP_PSYSTEM_FWAVE_2D) return launch_sharp_t<PSystem2D, 2>(l, err);
-    }
-    err = "Riemann solver id does not match the grid dimension";
-    return PCL_EINVAL;
+    const int rc = Solvers::with(l.rp, [&](auto tag) {
+        using RP = typename decltype(tag)::type;
+        if constexpr (RP::SHARP && RP::NDIM == 1) return l.ndim == 1 ? launch_sharp_t<RP, 1, RP::SHARP_HIGH>(l, err) : RP_NONE;
+        else if constexpr (RP::SHARP && RP::NDIM == 2)
+            return l.ndim == 1 ? RP_NONE
+                 : l.ids == 1 ? launch_sharp_t<RP, 1, RP::SHARP_HIGH>(l, err) : launch_sharp_t<RP, 2, RP::SHARP_HIGH>(l, err);
+        else return RP_NONE;
+    });
+    return rc != RP_NONE ? rc : not_built(err, "Riemann solver id does not match the grid dimension");
 }
 
 int launch_rk(const RkLaunch &r, hipStream_t stream, std::string &err) {

@@ -417,30 +417,14 @@ int fused_step_mode() {
     static const int on = [] { const char *e = getenv("PCL_TUNE_FUSED_STEP"); return e ? atoi(e) : 2; }();
     return on;
 }
-// What the host layer knows about each built-in Riemann solver: the sizes pcl_create insists on, and whether
-// launch_step2ds has an instantiation of it -- onek: without aux planes, onek_aux: with the solver's cell-wise
-// coefficients staged next to q.
-struct SolverFacts { int rp, ndim, meqn, mwaves; bool onek, onek_aux; };
-constexpr SolverFacts SOLVERS[] = {
-    {PCL_RP_ADVECTION_1D, 1, 1, 1, false, false},        {PCL_RP_ACOUSTICS_1D, 1, 2, 2, false, false},
-    {PCL_RP_BURGERS_1D, 1, 1, 1, false, false},          {PCL_RP_EULER_1D, 1, 3, 3, false, false},
-    {PCL_RP_SHALLOW_1D, 1, 2, 2, false, false},          {PCL_RP_ADVECTION_COLOR_1D, 1, 1, 1, false, false},
-    {PCL_RP_ELASTICITY_FWAVE_1D, 1, 2, 2, false, false}, {PCL_RP_PSYSTEM_FWAVE_2D, 2, 3, 2, false, true},
-    {PCL_RP_ADVECTION_2D, 2, 1, 1, true, false},         {PCL_RP_SHALLOW_2D, 2, 3, 3, true, false},
-    {PCL_RP_VC_ACOUSTICS_2D, 2, 3, 2, false, true},      {PCL_RP_VC_ADVECTION_2D, 2, 1, 1, false, true},
-    {PCL_RP_SHALLOW_SPHERE_2D, 2, 4, 3, false, false},   {PCL_RP_ACOUSTICS_2D, 2, 3, 2, true, false},
-    {PCL_RP_EULER5_2D, 2, 5, 5, true, false},            {PCL_RP_VC_ACOUSTICS_3D, 3, 4, 2, false, false},
-};
-const SolverFacts *solver_facts(int rp) {
-    for (const SolverFacts &f : SOLVERS)
-        if (f.rp == rp) return &f;
-    return nullptr;
-}
+// What the host layer knows about each built-in Riemann solver (sweep_args.hpp: RpFacts), read off the solver's struct
+// where the kernels are compiled; null for an id no solver has.
+const pcl::RpFacts *solver_facts(int rp) { return pcl::exact::rp_facts(rp); }
 // the one-kernel step stages aux planes next to q: a solver with cell-wise coefficients, or any solver with a capacity function
 bool fused_aux_family(const pcl_solver *s) { return s->cfg.method[5] > 0 || solver_facts(s->cfg.rp)->onek_aux; }
 bool fused_step_ok(const pcl_solver *s) {
     const int on = fused_step_mode();
-    const SolverFacts *f = solver_facts(s->cfg.rp);
+    const pcl::RpFacts *f = solver_facts(s->cfg.rp);
     if (!(on && s->cfg.ndim == 2 && s->cfg.method[2] < 0 && s->cfg.mbc == 2 && s->cfg.meqn <= 5 && (f->onek || f->onek_aux))) return false;
     // whole blocks only, and not under the fused source (Euler without a capacity function: pcl_fuse_source)
     return !fused_aux_family(s) || (!s->halo.active && s->aux && s->fused_src == 0);
@@ -687,11 +671,18 @@ int check_device() {
 extern "C" {
 
 const char *pcl_last_error(void) { return g_err.c_str(); }
-int pcl_version(void) { return 103; }
+int pcl_version(void) { return 104; }
 int pcl_device_count(void) {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess) return 0;
     return n;
+}
+int pcl_rp_info(int rp, int info[10]) {
+    const pcl::RpFacts *f = solver_facts(rp);
+    if (!f || !info) return fail(PCL_EINVAL, !info ? "null argument" : "unknown Riemann solver id");
+    const int v[10] = {f->ndim, f->meqn, f->mwaves, f->naux, f->fwave, f->onek, f->onek_aux, f->sharp, f->sharp_high, f->sharp_wave};
+    std::copy(v, v + 10, info);
+    return PCL_OK;
 }
 
 int pcl_create(const pcl_config *cfg, pcl_solver **out) {
@@ -735,7 +726,7 @@ int pcl_create(const pcl_config *cfg, pcl_solver **out) {
     if (cfg->mwaves < 1 || cfg->mwaves > PCL_MAX_WAVES) return fail(PCL_EINVAL, "bad mwaves");
     if (cfg->math != PCL_MATH_EXACT && cfg->math != PCL_MATH_FAST && cfg->math != PCL_MATH_STRICT)
         return fail(PCL_EINVAL, "unknown math mode");
-    const SolverFacts *facts = solver_facts(cfg->rp);
+    const pcl::RpFacts *facts = solver_facts(cfg->rp);
     if (!facts) return fail(PCL_EINVAL, "unknown Riemann solver id");
     if (cfg->meqn != facts->meqn || cfg->mwaves != facts->mwaves || cfg->ndim != facts->ndim)
         return fail(PCL_EINVAL, "meqn/mwaves/ndim do not match the Riemann solver");
@@ -747,7 +738,7 @@ int pcl_create(const pcl_config *cfg, pcl_solver **out) {
     if (cfg->rp == PCL_RP_VC_ACOUSTICS_2D || cfg->rp == PCL_RP_VC_ADVECTION_2D) {
         if (cfg->maux < 2) return fail(PCL_EINVAL, "this Riemann solver needs two aux components (impedance/sound speed or the edge velocities)");
     }
-    if (cfg->rp == PCL_RP_ELASTICITY_FWAVE_1D || cfg->rp == PCL_RP_PSYSTEM_FWAVE_2D) {
+    if (facts->fwave) {
         if (!cfg->fwave) return fail(PCL_EINVAL, "this Riemann solver returns f-waves: cfg.fwave must be 1 (classic1fw / classic2fw)");
         if (cfg->maux < 3) return fail(PCL_EINVAL, "f-wave elasticity solvers need aux(1)=rho, aux(2)=K, aux(3)=stress-law flag");
         if (cfg->rp == PCL_RP_PSYSTEM_FWAVE_2D && cfg->method[2] > 0 && cfg->maux < 4)
@@ -2304,7 +2295,8 @@ static int host_sharp(int ndim, int rp, const double *rp_params, int lim_type, i
     c.method[1] = 2; c.method[5] = mcapa; c.method[6] = maux;
     c.kind = PCL_KIND_SHARPCLAW; c.lim_type = lim_type;
     // clawparams.fwave follows the Riemann solver (sharpclaw.py:269): flux1 / flux2 carry no argument for it
-    c.fwave = rp == PCL_RP_ELASTICITY_FWAVE_1D || rp == PCL_RP_PSYSTEM_FWAVE_2D;
+    const pcl::RpFacts *facts = solver_facts(rp);
+    c.fwave = facts && facts->fwave;
     return layer1_run(c, q, aux, dq, L1_SHARP_DQ, 0, dt, cfl);
 }
 

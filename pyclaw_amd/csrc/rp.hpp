@@ -14,8 +14,10 @@
 //   template<int IXY> precell(q, par) -> Cell
 //   template<int IXY> solve(L, R, par, wave, s, amdq, apdq)
 //   template<int IXY> transverse(L, R, par, asdq, bmasdq, bpasdq)   (rpt2)
+//   ID (its PCL_RP_* value), NDIM, and which kernels have an instantiation of it (RpDefaults below)
 #pragma once
 #include <hip/hip_runtime.h>
+#include "../../include/pyclaw_amd.h"
 #include "sweep_args.hpp"
 
 #ifndef PCL_NS
@@ -176,11 +178,23 @@ __device__ __forceinline__ double fdiv_ieee(double n, double d) {
 #endif
 }
 
+// ---- which kernels a solver has ---------------------------------------------------------------
+// Every solver has the dimension-split sweep of its dimension (and the 2-D ones the unsplit step).  The rest a solver
+// states where it is true; the solver list of kernels.hip instantiates exactly what these say:
+//   ONEK        the one-kernel dimension-split 2-D step (classic_fused.hpp)
+//   SHARP       the SharpClaw kernels, weno_order 5 (sharpclaw.hpp);  SHARP_HIGH  ... and those of weno_order 7..17
+//   SHARP_WAVE  the wave-based 1-D SharpClaw kernel (char_decomp = 1)
+struct RpDefaults {
+    static constexpr bool ONEK = false, SHARP = false, SHARP_HIGH = false, SHARP_WAVE = false;
+};
+
 // ------------------------------------------------------------------------------------
 // 1-D advection, q_t + u q_x = 0  (third-party rp1_advection.f, restated)
 // ------------------------------------------------------------------------------------
-struct Advection1D {
+struct Advection1D : RpDefaults {
+    static constexpr int ID = PCL_RP_ADVECTION_1D, NDIM = 1;
     static constexpr int MEQN = 1, MWAVES = 1, NCELL = 1, NAUX = 0;
+    static constexpr bool SHARP = true, SHARP_HIGH = true, SHARP_WAVE = true;
     struct Cell { double q[1]; };
     template <int IXY> __device__ static constexpr bool nz(int, int) { return true; }
     template <int IXY>
@@ -208,8 +222,10 @@ struct Advection1D {
 // 1-D colour equation q_t + u(x) q_x = 0 (third-party rp1_advection_color.f, restated): aux(1) of a cell is the
 // velocity at its LEFT edge, so interface i uses the right cell's value
 // ------------------------------------------------------------------------------------
-struct AdvectionColor1D {
+struct AdvectionColor1D : RpDefaults {
+    static constexpr int ID = PCL_RP_ADVECTION_COLOR_1D, NDIM = 1;
     static constexpr int MEQN = 1, MWAVES = 1, NCELL = 2, NAUX = 1, NAUX_T = 1;
+    static constexpr bool SHARP = true, SHARP_HIGH = true, SHARP_WAVE = true;
     template <int IXY> __host__ __device__ static constexpr int aux_index(int k) { return k; }
     template <int IXY> __host__ __device__ static constexpr int auxt_index(int k) { return k; }
     struct Cell { double q[1]; double u; };
@@ -236,8 +252,10 @@ struct AdvectionColor1D {
 // ------------------------------------------------------------------------------------
 // 1-D Burgers' equation with the transonic entropy fix (third-party rp1_burgers.f90, restated)
 // ------------------------------------------------------------------------------------
-struct Burgers1D {
+struct Burgers1D : RpDefaults {
+    static constexpr int ID = PCL_RP_BURGERS_1D, NDIM = 1;
     static constexpr int MEQN = 1, MWAVES = 1, NCELL = 1, NAUX = 0;
+    static constexpr bool SHARP = true, SHARP_HIGH = true, SHARP_WAVE = true;
     struct Cell { double q[1]; };
     template <int IXY> __device__ static constexpr bool nz(int, int) { return true; }
     template <int IXY>
@@ -265,8 +283,10 @@ struct Burgers1D {
 // the vendored 2-D solver below without its shear and tracer waves); par = gamma, gamma1.
 // Plain IEEE operations in the order of the C restatement (oracle/classic_oracle.c: rp1_euler).
 // ------------------------------------------------------------------------------------
-struct Euler1D {
+struct Euler1D : RpDefaults {
+    static constexpr int ID = PCL_RP_EULER_1D, NDIM = 1;
     static constexpr int MEQN = 3, MWAVES = 3, NCELL = 3, NAUX = 0;
+    static constexpr bool SHARP = true, SHARP_HIGH = true, SHARP_WAVE = true;
     struct Cell { double q[3]; };
     template <int IXY> __device__ static constexpr bool nz(int, int) { return true; }
     template <int IXY>
@@ -349,8 +369,10 @@ struct Euler1D {
 // 1-D shallow water, Roe solver + Harten-Hyman entropy fix (third-party rp1_shallow_roe_with_efix.f, restated);
 // q = (h, hu); par = g.  Same operation order as oracle/classic_oracle.c: rp1_shallow.
 // ------------------------------------------------------------------------------------
-struct Shallow1D {
+struct Shallow1D : RpDefaults {
+    static constexpr int ID = PCL_RP_SHALLOW_1D, NDIM = 1;
     static constexpr int MEQN = 2, MWAVES = 2, NCELL = 2, NAUX = 0;
+    static constexpr bool SHARP = true, SHARP_HIGH = true, SHARP_WAVE = true;
     struct Cell { double q[2]; };
     template <int IXY> __device__ static constexpr bool nz(int, int) { return true; }
     template <int IXY>
@@ -412,8 +434,10 @@ struct Shallow1D {
 // ------------------------------------------------------------------------------------
 // 2-D constant-coefficient advection (third-party rpn2_advection.f / rpt2_advection.f, restated); par = u, v
 // ------------------------------------------------------------------------------------
-struct Advection2D {
+struct Advection2D : RpDefaults {
+    static constexpr int ID = PCL_RP_ADVECTION_2D, NDIM = 2;
     static constexpr int MEQN = 1, MWAVES = 1, NCELL = 1, NAUX = 0;
+    static constexpr bool ONEK = true, SHARP = true, SHARP_HIGH = true;
     struct Cell { double q[1]; };
     template <int IXY> __device__ static constexpr bool nz(int, int) { return true; }
     template <int IXY>
@@ -446,8 +470,10 @@ struct Advection2D {
 // ------------------------------------------------------------------------------------
 // 1-D acoustics (third-party rp1_acoustics.f, restated); par = rho,bulk,cc,zz
 // ------------------------------------------------------------------------------------
-struct Acoustics1D {
+struct Acoustics1D : RpDefaults {
+    static constexpr int ID = PCL_RP_ACOUSTICS_1D, NDIM = 1;
     static constexpr int MEQN = 2, MWAVES = 2, NCELL = 2, NAUX = 0;
+    static constexpr bool SHARP = true, SHARP_HIGH = true, SHARP_WAVE = true;
     struct Cell { double q[2]; };
     template <int IXY> __device__ static constexpr bool nz(int, int) { return true; }
     template <int IXY>
@@ -477,8 +503,10 @@ struct Acoustics1D {
 // 2-D acoustics (third-party rpn2_acoustics.f / rpt2_acoustics.f, restated)
 // q = (p, u, v); par = rho,bulk,cc,zz
 // ------------------------------------------------------------------------------------
-struct Acoustics2D {
+struct Acoustics2D : RpDefaults {
+    static constexpr int ID = PCL_RP_ACOUSTICS_2D, NDIM = 2;
     static constexpr int MEQN = 3, MWAVES = 2, NCELL = 3, NAUX = 0;
+    static constexpr bool ONEK = true, SHARP = true, SHARP_HIGH = true;
     struct Cell { double q[3]; };
     template <int IXY> __device__ static constexpr bool nz(int /*mw*/, int m) {
         return m == 0 || m == (IXY == 1 ? 1 : 2);
@@ -520,8 +548,10 @@ struct Acoustics2D {
 
 // ---- 2-D colour equation with edge velocities (third-party rpn2_vc_advection.f / rpt2_vc_advection.f, restated):
 // aux(1) = u at the cell's left edge, aux(2) = v at its bottom edge
-struct VcAdvection2D {
+struct VcAdvection2D : RpDefaults {
+    static constexpr int ID = PCL_RP_VC_ADVECTION_2D, NDIM = 2;
     static constexpr int MEQN = 1, MWAVES = 1, NAUX = 2, NAUX_T = 2;
+    static constexpr bool ONEK = true, SHARP = true;
     template <int IXY> __host__ __device__ static constexpr int aux_index(int k) { return k; }
     template <int IXY> __host__ __device__ static constexpr int auxt_index(int k) { return k; }
     struct Cell { double q[1]; double u, v; };
@@ -559,8 +589,10 @@ struct VcAdvection2D {
 // ---- 2-D acoustics with cell-wise impedance and sound speed (third-party rpn2_vc_acoustics.f, restated: the
 // formulas of VcAcoustics3D below); q = (p, u, v); aux(1) = Z, aux(2) = c.  The transverse solver
 // (rpt2_vc_acoustics.f, restated) needs the aux values of the two neighbouring slices: transverse_vc.
-struct VcAcoustics2D {
+struct VcAcoustics2D : RpDefaults {
+    static constexpr int ID = PCL_RP_VC_ACOUSTICS_2D, NDIM = 2;
     static constexpr int MEQN = 3, MWAVES = 2, NAUX = 2, NAUX_T = 2;
+    static constexpr bool ONEK = true, SHARP = true;
     template <int IXY> __host__ __device__ static constexpr int aux_index(int k) { return k; }
     template <int IXY> __host__ __device__ static constexpr int auxt_index(int k) { return k; }
     struct Cell { double q[3]; double z, c; };
@@ -615,7 +647,8 @@ struct VcAcoustics2D {
 // ---- 3-D acoustics with cell-wise impedance and sound speed (third-party rpn3_vc_acoustics.f, restated;
 // named by the reference's test/acoustics/3d/Makefile) --------------------------------------------------
 // q = (p, u, v, w); aux(1) = Z, aux(2) = c.  DIR = 1,2,3 selects the normal velocity q(DIR).
-struct VcAcoustics3D {
+struct VcAcoustics3D : RpDefaults {
+    static constexpr int ID = PCL_RP_VC_ACOUSTICS_3D, NDIM = 3;
     static constexpr int MEQN = 4, MWAVES = 2, NAUX = 2, NAUX_T = 2;
     // the transverse solvers are driven by the pressure component alone (classic3.hpp: slice3_pieces_p)
     static constexpr bool T3_PRESSURE = true;
@@ -663,8 +696,10 @@ struct VcAcoustics3D {
 // rpn2_shallow_roe_with_efix.f / rpt2_shallow_roe_with_efix.f, restated); q = (h, hu, hv); par = g.
 // Plain IEEE operations in the order of oracle/classic_oracle.c: rpn2_shallow / rpt2_shallow.
 // ------------------------------------------------------------------------------------
-struct Shallow2D {
+struct Shallow2D : RpDefaults {
+    static constexpr int ID = PCL_RP_SHALLOW_2D, NDIM = 2;
     static constexpr int MEQN = 3, MWAVES = 3, NCELL = 3, NAUX = 0;
+    static constexpr bool ONEK = true, SHARP = true;
     struct Cell { double q[3]; };
     // wave(m,mw) sparsity: wave 2 carries only the transverse momentum
     template <int IXY> __device__ static constexpr bool nz(int mw, int m) {
@@ -773,9 +808,12 @@ struct Shallow2D {
 __device__ __forceinline__ double ps_sigma(double eps, double K, double lin) { return lin == 1.0 ? K * eps : exp(K * eps) - 1.0; }
 __device__ __forceinline__ double ps_sigmap(double eps, double K, double lin) { return lin == 1.0 ? K : K * exp(K * eps); }
 
-template <int NEQ> struct FwaveElastic {
+template <int NEQ> struct FwaveElastic : RpDefaults {
+    // NEQ = 2: elasticity in 1-D, classic only; NEQ = 3: the p-system in 2-D
+    static constexpr int ID = NEQ == 2 ? PCL_RP_ELASTICITY_FWAVE_1D : PCL_RP_PSYSTEM_FWAVE_2D, NDIM = NEQ == 2 ? 1 : 2;
     static constexpr int MEQN = NEQ, MWAVES = 2, NAUX = 3, NAUX_T = 4;
     static constexpr bool IS_FWAVE = true;
+    static constexpr bool ONEK = NEQ == 3, SHARP = NEQ == 3;
     template <int IXY> __host__ __device__ static constexpr int aux_index(int k) { return k; }
     template <int IXY> __host__ __device__ static constexpr int auxt_index(int k) { return k; }
     struct Cell { double q[NEQ]; double rho, un, sig, c, z; };
@@ -839,8 +877,10 @@ using PSystem2D = FwaveElastic<3>;
 // vector (9 components: aux_index); the transverse solves need the OTHER direction's edge + radial vector of the
 // cell itself and of its two neighbours across (auxt_index).
 // ------------------------------------------------------------------------------------
-struct ShallowSphere {
+struct ShallowSphere : RpDefaults {
+    static constexpr int ID = PCL_RP_SHALLOW_SPHERE_2D, NDIM = 2;
     static constexpr int MEQN = 4, MWAVES = 3, NAUX = 9, NAUX_T = 9;
+    static constexpr bool SHARP = true;
     static constexpr bool HAS_QCOR = true;   // the app replaces step2.f by step2qcor.f (Makefile:16)
     template <int IXY> __host__ __device__ static constexpr int aux_index(int k) {
         return k < 6 ? (IXY == 1 ? 1 + k : 7 + k) : 13 + (k - 6);
@@ -1052,8 +1092,10 @@ struct ShallowSphere {
 // the Harten-Hyman entropy fix: development/rp_approaches/rpn2_euler_5wave.f:87-298,
 // transverse split rpt2_euler_5wave_rec_loc.f:50-116.  par = gamma, gamma1.
 // ------------------------------------------------------------------------------------
-struct Euler5 {
+struct Euler5 : RpDefaults {
+    static constexpr int ID = PCL_RP_EULER5_2D, NDIM = 2;
     static constexpr int MEQN = 5, MWAVES = 5, NCELL = 12, NAUX = 0;
+    static constexpr bool ONEK = true, SHARP = true, SHARP_HIGH = true;
     struct Cell {
         double q[5];
         double rs;      // sqrt(rho)                       rpn2:88-89

@@ -198,8 +198,15 @@ struct TileHandover {
     hipStream_t stream;
 };
 
+// What the host layer knows about a built-in Riemann solver, read off its struct in rp.hpp through the solver list of
+// kernels.hip: the sizes pcl_create insists on, and which kernels have an instantiation of it -- onek / onek_aux: the
+// one-kernel step (launch_step2ds) without aux planes / with the solver's cell-wise coefficients staged next to q;
+// sharp: the SharpClaw kernels, sharp_high: those of weno_order 7..17 too, sharp_wave: the wave-based 1-D kernel.
+struct RpFacts { int id, ndim, meqn, mwaves, naux; bool fwave, onek, onek_aux, sharp, sharp_high, sharp_wave; };
+
 // defined in kernels.hip, once per arithmetic mode; returns 0 or a PCL_E* code + message
 namespace exact {
+const RpFacts *rp_facts(int rp);    // null: no built-in solver has this id (the same in every mode)
 int launch_sweep(const SweepLaunch &l, std::string &err);
 int launch_step2ds(const SweepLaunch &l, std::string &err);   // whole dim-split 2-D step in one kernel (classic_fused.hpp)
 // x-pass tiles [tb_lo,tb_hi) x [ta_lo,ta_hi) that read no ghost cell; false if there are none

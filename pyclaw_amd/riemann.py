@@ -61,7 +61,7 @@ rp_euler_5wave_2d = RiemannSolver("euler_5wave_2d", 11, 2, 5, 5, ["gamma", "gamm
 rp_shallow_sphere_2d = RiemannSolver("shallow_sphere_2d", 16, 2, 4, 3, ["g"], True, grid_params=True)
 
 # 3-D acoustics, impedance and sound speed per cell in aux(1), aux(2) (test/acoustics/3d/Makefile:
-# rpn3_vc_acoustics.f; the transverse rpt3/rptt3 of the unsplit algorithm are not built: dim_split only)
+# rpn3_vc_acoustics.f; dimension-split, and unsplit with rpt3/rptt3_vc_acoustics.f where there is no capacity function)
 rp_vc_acoustics_3d = RiemannSolver("vc_acoustics_3d", 20, 3, 4, 2, [])
 
 _ALL = [rp_elasticity_fwave_1d, rp_psystem_fwave_2d, rp_advection_1d, rp_acoustics_1d, rp_advection_color_1d, rp_burgers_1d, rp_euler_1d, rp_shallow_1d, rp_advection_2d, rp_shallow_2d, rp_vc_acoustics_2d, rp_vc_advection_2d, rp_acoustics_2d, rp_euler_5wave_2d, rp_shallow_sphere_2d, rp_vc_acoustics_3d]

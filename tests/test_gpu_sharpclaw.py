@@ -258,3 +258,40 @@ def test_char_decomp_refusals():
         with pytest.raises(NotImplementedError):
             s1.setup(None)
     assert L.lib().pcl_sharp_module_char_decomp(2) != 0
+
+
+def test_solver_table_refusals_keep_their_text():
+    """What the host layer decides from its record of the solver, message for message: the wave-based reconstruction on
+    the 1-D f-wave solver (the flag follows the solver in pcl_sharp_flux1, so pcl_create stops it before the launch code
+    could), and cfg.fwave = 1 with a solver that returns waves."""
+    from pyclaw_amd import _lib as L
+    lib = L.lib()
+    mx, mbc = 9, 3
+    q = np.asfortranarray(np.random.default_rng(2).standard_normal((2, mx + 2 * mbc)))
+    aux = np.ones((3, mx + 2 * mbc), order="F")
+    dq = np.full_like(q, 7.0)
+    cfl = C.c_double()
+    L.check(lib.pcl_sharp_module_char_decomp(1))
+    try:
+        rc = lib.pcl_sharp_flux1(O.RP_ELASTICITY_FWAVE_1D, L.d(np.zeros(8)), 2, 2, 2, 3, 0, mbc, mx, L.d(q), L.d(dq),
+                                 L.d(aux), 1.0 / mx, 0.01, C.cast(C.byref(cfl), L.dp))
+    finally:
+        L.check(lib.pcl_sharp_module_char_decomp(0))
+    assert rc == L.EINVAL
+    assert lib.pcl_last_error() == (b"SharpClaw char_decomp = 1: 1-D, lim_type 1 (tvd2_wave) or 2 (weno5_wave), "
+                                    b"weno_order 5, no f-wave solver")
+    assert np.all(dq == 7.0)
+    for kind in (0, 1):
+        cfg = L.Config()
+        cfg.ndim = 1
+        cfg.n[0], cfg.d[0] = mx, 1.0 / mx
+        cfg.mbc = 2 + kind
+        cfg.meqn, cfg.mwaves, cfg.rp = 2, 2, O.RP_ACOUSTICS_1D
+        cfg.method[1] = 2
+        cfg.mthlim[0] = cfg.mthlim[1] = 4
+        cfg.kind, cfg.lim_type = kind, 2 * kind
+        cfg.fwave = 1
+        h = C.c_void_p()
+        assert lib.pcl_create(C.byref(cfg), C.byref(h)) == L.EINVAL and not h.value
+        assert lib.pcl_last_error() == (b"cfg.fwave = 1 needs an f-wave Riemann solver (PCL_RP_ELASTICITY_FWAVE_1D, "
+                                        b"PCL_RP_PSYSTEM_FWAVE_2D)")

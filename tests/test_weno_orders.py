@@ -207,6 +207,80 @@ def test_hip_flux1_acoustics1d_bitexact(coracle, order, mx):
     assert cfl == cfl_ref
 
 
+def _small_case(name, g):
+    """ndim, rp, meqn, mwaves, par, q, aux of one solver at 9 (x 5) cells with g ghost layers"""
+    rng = np.random.default_rng(sum(ord(c) for c in name))
+    n1, n2 = (9 + 2 * g,), (9 + 2 * g, 5 + 2 * g)
+    if name == "advection_1d":
+        return 1, O.RP_ADVECTION_1D, 1, 1, [0.7], rng.standard_normal((1,) + n1), None
+    if name == "burgers_1d":
+        return 1, O.RP_BURGERS_1D, 1, 1, [], rng.standard_normal((1,) + n1), None        # both signs: transonic fix
+    if name == "advection_color_1d":
+        return 1, O.RP_ADVECTION_COLOR_1D, 1, 1, [], rng.random((1,) + n1), 1.5 * (rng.random((1,) + n1) - 0.3)
+    if name == "shallow_1d":
+        h = 0.5 + rng.random(n1)
+        return 1, O.RP_SHALLOW_1D, 2, 2, [9.81], np.stack([h, h * 0.3 * rng.standard_normal(n1)]), None
+    if name == "euler_1d":
+        rho, u, p = 0.5 + rng.random(n1), 0.3 * rng.standard_normal(n1), 0.5 + rng.random(n1)
+        return 1, O.RP_EULER_1D, 3, 3, [1.4, 0.4], np.stack([rho, rho * u, p / 0.4 + 0.5 * rho * u * u]), None
+    if name == "advection_2d":
+        return 2, O.RP_ADVECTION_2D, 1, 1, [0.8, -0.6], rng.random((1,) + n2), None
+    assert name == "acoustics_2d"
+    return 2, O.RP_ACOUSTICS_2D, 3, 2, [1.0, 4.0, 2.0, 2.0], rng.standard_normal((3,) + n2), None
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name,order", [("advection_1d", 5)] + [(n, 7) for n in (
+    "advection_1d", "burgers_1d", "advection_color_1d", "shallow_1d", "euler_1d", "advection_2d", "acoustics_2d")])
+def test_hip_flux_of_the_solvers_not_run_elsewhere(coracle, name, order):
+    """The solvers whose weno_order 7..17 kernels the two tests above do not run (they take euler_5wave_2d and
+    acoustics_1d), at order 7 (mbc 4), and advection_1d at order 5, which no other test takes through the component-wise
+    kernel: 9 (x 5) cells == the oracle, bit for bit, Courant number included."""
+    from pyclaw_amd import _lib as L
+    g, mx, my = (order + 1) // 2, 9, 5
+    ndim, rp, meqn, mwaves, par, q, aux = _small_case(name, g)
+    q = np.asfortranarray(q)
+    aux = None if aux is None else np.asfortranarray(aux)
+    maux = 0 if aux is None else aux.shape[0]
+    p8 = np.array(list(par) + [0.0] * (8 - len(par)))
+    dx, dy, dt = 1.0 / mx, 0.8 / my, 0.01 / mx
+    dq = np.zeros_like(q)
+    cfl = C.c_double()
+    coracle.set_weno_order(order)
+    if ndim == 1:
+        ref, cfl_ref = coracle.sharp_flux1(rp, p8, 2, mwaves, 0, g, mx, q, aux, dx, dt)
+        L.check(L.lib().pcl_sharp_flux1(rp, L.d(p8), 2, meqn, mwaves, maux, 0, g, mx, L.d(q), L.d(dq),
+                                        None if aux is None else L.d(aux), dx, dt, C.cast(C.byref(cfl), L.dp)))
+        inner = (slice(None), slice(g, -g))
+    else:
+        ref, cfl_ref = coracle.sharp_flux2(rp, p8, 2, mwaves, 0, g, mx, my, q, aux, dx, dy, dt)
+        L.check(L.lib().pcl_sharp_flux2(rp, L.d(p8), 2, meqn, mwaves, maux, 0, g, mx, my, L.d(q), L.d(dq), None, dx, dy,
+                                        dt, C.cast(C.byref(cfl), L.dp)))
+        inner = (slice(None), slice(g, -g), slice(g, -g))
+    assert np.isfinite(ref[inner]).all() and np.abs(ref[inner]).max() > 0
+    assert np.array_equal(dq[inner], ref[inner]), np.abs(dq[inner] - ref[inner]).max()
+    assert cfl.value == cfl_ref and cfl.value > 0
+
+
+@pytest.mark.gpu
+def test_order7_is_refused_for_a_weno5_only_solver():
+    """shallow_2d has the SharpClaw kernels of weno_order 5 alone: mbc 4 passes pcl_create and ends in the launch code's
+    refusal, before anything is launched (dq stays as it was)."""
+    from pyclaw_amd import _lib as L
+    g, mx, my = 4, 9, 5
+    rng = np.random.default_rng(13)
+    h = 0.5 + rng.random((mx + 2 * g, my + 2 * g))
+    q = np.asfortranarray(np.stack([h, 0.1 * h, -0.2 * h]))
+    dq = np.full_like(q, 7.0)
+    cfl = C.c_double()
+    rc = L.lib().pcl_sharp_flux2(O.RP_SHALLOW_2D, L.d(np.array([9.81] + [0.0] * 7)), 2, 3, 3, 0, 0, g, mx, my, L.d(q),
+                                 L.d(dq), None, 1.0 / mx, 1.0 / my, 0.001, C.cast(C.byref(cfl), L.dp))
+    assert rc == L.EINVAL
+    assert L.lib().pcl_last_error() == (b"SharpClaw: this Riemann solver is built for weno_order 5 (mbc 3) only; orders 7..17 "
+                                        b"exist for the 1-D solvers and for advection_2d, acoustics_2d, euler_5wave_2d")
+    assert np.all(dq == 7.0)
+
+
 @pytest.mark.gpu
 def test_acoustics1d_weno17_app(coracle):
     """the reference's weno17 regression through SharpClawSolver1D on the GPU: the gate, and the oracle replay bit for bit"""
