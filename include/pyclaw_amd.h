@@ -502,7 +502,12 @@ int pcl_comm_init(pcl_solver *s, int nranks, int rank, const char uid[128],
  * pcl_halo_can_overlap tells whether this rank's block qualifies (decomposed, dim-split 2-D, interior x-pass tiles,
  * PCL_HALO_OVERLAP=1); the caller agrees over all ranks (pyclaw_amd/clawpack.py) and then switches it on everywhere.
  * pcl_halo_can_overlap: 0 no, 1 yes, 2 yes and the block can also run the one-kernel form of the step (both sweeps in
- * one launch) with interior / rim tile subsets.  That form sends the new state's halo behind its RIM tiles, beside the
+ * one launch) with interior / rim tile subsets.  The rule (csrc/halo_plan.hpp: OverlapPlan::offers): 0 unless a
+ * communicator is set up, the solver takes the classic dimension-split 2-D step with at most 8 equations and
+ * PCL_HALO_OVERLAP is 1 (set or not); else 2 if the block may take the one-kernel step and its tiles leave an interior
+ * box; else 1 if the x pass' tiles leave an interior box and the two-pass overlap is not off by default -- it is, with
+ * PCL_HALO_OVERLAP not set, for the aux-free solvers of the one-kernel step without a capacity function; else 0.  The
+ * one-kernel form sends the new state's halo behind its RIM tiles, beside the
  * interior launch and BEFORE the Courant number's all-reduce: on = 2 selects that order and is only valid when every
  * rank reported 2; on = 1 keeps the two-pass order (all-reduce, then the exchange) on every rank. */
 int pcl_halo_can_overlap(pcl_solver *s, int *yes);
@@ -537,7 +542,7 @@ int pcl_halo_region(int dir, int send, int I, int J, int mbc, int out_i0_j0_ni_n
  * of side out[3] (0 lower, 1 upper) instead (PCL_BC_CUSTOM).  An interior cell, and a ghost cell of a side without a
  * fill, maps to itself. */
 int pcl_ghost_map(int k, int n, int mbc, int lo, int hi, int out_src_neg_cst_side[4]);
-/* Host-only helpers (no GPU needed), for the test suite: the two host state machines of the dim-split 2-D step driven
+/* Host-only helpers (no GPU needed), for the test suite: three host state machines of the dim-split 2-D step driven
  * through n scripted events, each on a fresh object, the decisions written to out[i].
  * pcl_step_form_trace (csrc/step_form.hpp), event[i]: 0 a step, begin(can = a[i], tune = b[i], listed[i], ntiles) then
  * end(seconds[i]): out = form | 2 * timed; 1 next_is_plain_onek(can = a[i], mode = b[i]); 2 adopted(mode = b[i]) and
@@ -545,12 +550,20 @@ int pcl_ghost_map(int k, int n, int mbc, int lo, int hi, int out_src_neg_cst_sid
  * pcl_step_ahead_trace (csrc/step_ahead.hpp), armed once with the first four arguments; event i has the spec bc[4 i ..],
  * cstate[32 i ..]; event[i]: 0 out = wants(c = x[i], ran[i], ntiles[i], next_plain_onek = flag[i]); 1 out_dt =
  * next_dt(dt = x[i], c = y[i]); 2 enqueued(dt = x[i], seq = i, spec, ran[i]); 3 out = matches(spec, dt = x[i],
- * carry = flag[i]); 4 missed(); 5 adopted(); 6 out = dropped(), out_dt = the tile count then reported. */
+ * carry = flag[i]); 4 missed(); 5 adopted(); 6 out = dropped(), out_dt = the tile count then reported.
+ * pcl_halo_plan_trace (csrc/halo_plan.hpp).  Facts are the bits active 1, split2 2, sel0 4, onek_ok 8, onek_family 16,
+ * onek_box 32, x_box 64; buffers are ids 1..7 (distinct addresses inside the function), 0 the null buffer.  event[i]:
+ * 0 configure(overlap = a[i], set = b[i]); 1 set_exchange_ahead(a[i]); 2 out = offers(facts a[i]); 3 plan(facts a[i],
+ * state buffer b[i]): out = order | 8 * onek | 16 * have | 32 * send_ahead, order 0 not overlapped, 1 rim first,
+ * 2 exchange in front, 3 test order, 4 interior first; 4 out = filled(a[i]); 5 exchanged(a[i]); 6 written(a[i]);
+ * 7 touched(); 8 failed(); 9 out = unsplit_overlaps(active = a[i]); 10 out = sharp_overlaps(active = a[i], ndim = b[i]);
+ * 11 out = frame_sequential(overlapping = a[i]). */
 int pcl_step_form_trace(long n, const int *event, const int *a, const int *b, const long *listed, long ntiles,
                         const double *seconds, int *out);
 int pcl_step_ahead_trace(int on, double cfl_desired, double cfl_max, double dt_max, long n, const int *event,
                          const int *flag, const double *x, const double *y, const long *ran, const long *ntiles,
                          const int *bc, const double *cstate, int *out, double *out_dt);
+int pcl_halo_plan_trace(long n, const int *event, const int *a, const int *b, int *out);
 
 /* ---- debug / self-test --------------------------------------------------------------- */
 /* Runs the wavefront neighbour-shift primitive on 64 values: left[l]=in[l-1],

@@ -141,6 +141,7 @@ PROTOTYPES = {
     "pcl_step_form_trace": (C.c_int, [C.c_long, ip, ip, ip, C.POINTER(C.c_long), C.c_long, dp, ip]),
     "pcl_step_ahead_trace": (C.c_int, [C.c_int, C.c_double, C.c_double, C.c_double, C.c_long, ip, ip, dp, dp,
                                        C.POINTER(C.c_long), C.POINTER(C.c_long), ip, dp, ip, dp]),
+    "pcl_halo_plan_trace": (C.c_int, [C.c_long, ip, ip, ip, ip]),
     "pcl_debug_wave_shift": (C.c_int, [dp, dp, dp]),
 }
 

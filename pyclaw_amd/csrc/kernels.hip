@@ -249,7 +249,7 @@ int launch_unsplit3(const Unsplit3Launch &l, std::string &err) {
 const RpFacts *rp_facts(int rp) { return Solvers::facts(rp); }
 // the same for the one-kernel step (classic_fused.hpp): tile (ty, tx) reads rows mbc-2+F_OWN_R*ty .. +F_ROWS-1 and columns
 // mbc-2+60*tx .. +63; box = [ty_lo, ty_hi) x [tx_lo, tx_hi), ntiles = (nty, ntx)
-bool step2ds_interior_box(const SweepArgs &a, int box[4], int ntiles[2]) {
+bool step2ds_interior_box(const BlockGeom &a, int box[4], int ntiles[2]) {
     const int ntx = (a.mx + F_OWN_C - 1) / F_OWN_C, nty = (a.my + F_OWN_R - 1) / F_OWN_R;
     box[0] = 1;
     const int roomy = a.my + HALO - F_ROWS;       // F_OWN_R*ty + F_ROWS <= my + 2
@@ -277,7 +277,7 @@ int launch_tile_handover(const TileHandover &h, std::string &err) {
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? PCL_OK : hip_fail(err, "tile hand-over launch", e);
 }
-bool x_interior_box(const SweepArgs &a, int box[4], int ntiles[2]) {
+bool x_interior_box(const BlockGeom &a, int box[4], int ntiles[2]) {
     using T = TileShape<1>;
     constexpr int ADV = T::NSTRIP * STRIP;  // cells a tile advances along the row
     const int ntb = (a.J + T::ACROSS - 1) / T::ACROSS, nta = (a.mx + ADV - 1) / ADV;

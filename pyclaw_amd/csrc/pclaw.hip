@@ -19,6 +19,7 @@
 #include "quiet_tiles.hpp"
 #include "step_form.hpp"
 #include "step_ahead.hpp"
+#include "halo_plan.hpp"
 #include "cellfn.hpp"
 
 namespace {
@@ -73,23 +74,13 @@ struct pcl_solver {
     long kt_n[3] = {0, 0, 0};
     pcl::StepForm form;   // which form of the dimension-split 2-D step runs: state and rule in step_form.hpp
     pcl::Halo halo;
-    // halo exchange overlapped with the interior of the x pass (pcl_bc_step, dim-split 2-D)
+    // A decomposed block's step beside its halo exchange: mode, plan, launch order and ghost-frame marks in halo_plan.hpp;
+    // here the halo stream, its fork / join events and the fork event of an exchange sent ahead (ev_y), and the interior
+    // boxes of the block's tiles (comm_ready)
+    pcl::OverlapPlan plan;
     hipStream_t hstream = nullptr;
-    hipEvent_t ev_h0 = nullptr, ev_h1 = nullptr;
-    int overlap = 1;
-    bool overlap_dflt = true;       // PCL_HALO_OVERLAP not set: the library picks per kernel family (twopass_overlap_ok)
-    // Exchange-ahead (pcl_halo_exchange_ahead): the halo exchange of the NEW state is enqueued on the halo stream
-    // right behind the y pass that produced it, so it runs through the hand-over of the Courant number, the host's
-    // accept / retake decision and the first tiles of the next x pass instead of in front of that pass' rim tiles.
-    // ghost_ok[] names the buffers whose ghost frame such an exchange (or the one at the start of a step) has filled
-    // and nothing has touched since: the state itself and, for a retaken step, the pre-step state (pcl_undo_step).
-    int exchange_ahead = 0;
-    hipEvent_t ev_y = nullptr;
-    const double *ghost_ok[2] = {nullptr, nullptr};
-    bool ghosts_filled(const double *buf) const { return buf && (ghost_ok[0] == buf || ghost_ok[1] == buf); }
-    void ghosts_mark(const double *buf) { if (!ghosts_filled(buf)) { ghost_ok[1] = ghost_ok[0]; ghost_ok[0] = buf; } }
-    void ghosts_drop(const double *buf) { for (auto &g : ghost_ok) if (g == buf) g = nullptr; }
-    void ghosts_drop_all() { ghost_ok[0] = ghost_ok[1] = nullptr; }
+    hipEvent_t ev_h0 = nullptr, ev_h1 = nullptr, ev_y = nullptr;
+    pcl::InteriorBox box_onek, box_x;       // of the one-kernel step's tiles / of the x pass' tiles
     pcl::QuietTiles qt;             // quiet tiles of the one-kernel dim-split step: state and invariants in quiet_tiles.hpp
     pcl::StepAhead ahead; // step ahead (pcl_step_ahead): decisions and counters in step_ahead.hpp
     // cell functions (cellfn.hpp): the modules this handle has loaded, and where the block sits in the global grid
@@ -429,16 +420,21 @@ bool fused_step_ok(const pcl_solver *s) {
     // whole blocks only, and not under the fused source (Euler without a capacity function: pcl_fuse_source)
     return !fused_aux_family(s) || (!s->halo.active && s->aux && s->fused_src == 0);
 }
-// The two-pass dim-split step of a decomposed block with its interior x tiles BESIDE the exchange.  For the solver
-// family of the one-kernel step (aux-free, no capacity function: an x pass register-allocated for four workgroups per
-// CU) the interior launch starves the halo stream's pack / Send-Recv kernels (44 / 77 us instead of 6 / 34) and the step
-// is slower than with the exchange in front (4096 x 2048 Euler block: 0.489 against 0.320 ms), so those blocks -- too
-// thin for one-kernel tiles, mbc > 2, PCL_TUNE_FUSED_STEP=0 -- take the exchange in front unless PCL_HALO_OVERLAP=1 is
-// set explicitly (tests, A/B).  Solvers with aux arrays or a capacity function keep the overlap (their decomposed blocks
-// never take the one-kernel step: fused_step_ok).
-bool twopass_overlap_ok(const pcl_solver *s) {
-    const bool onek_family = s->cfg.ndim == 2 && s->cfg.method[2] < 0 && s->cfg.method[5] <= 0 && solver_facts(s->cfg.rp)->onek;
-    return !(onek_family && s->overlap_dflt);
+// What the halo plan asks about the block (halo_plan.hpp: OverlapPlan::Facts).  A handle without a communicator leaves at
+// the first test with every fact false, any other step than the classic dimension-split 2-D one at the second (both
+// rules of the plan begin with these two).
+OverlapPlan::Facts block_facts(const pcl_solver *s) {
+    OverlapPlan::Facts f{};
+    if (!s->halo.active) return f;
+    f.active = true;
+    f.split2 = s->cfg.kind == PCL_KIND_CLASSIC && s->cfg.ndim == 2 && s->cfg.method[2] < 0 && s->cfg.meqn <= 8;
+    if (!f.split2) return f;
+    f.sel0 = s->sel == 0;
+    f.onek_ok = fused_step_ok(s);
+    f.onek_family = s->cfg.method[5] <= 0 && solver_facts(s->cfg.rp)->onek;
+    f.onek_box = s->box_onek.any;
+    f.x_box = s->box_x.any;
+    return f;
 }
 // carry: the quiet-tile words of the previous launch still hold (QuietTiles::take_valid at the step's entry point)
 int do_step2ds(pcl_solver *s, const double *qin, double *qout, double dt, bool carry, int sub = 0, const int *box = nullptr,
@@ -646,7 +642,7 @@ int halo_join(pcl_solver *s, int rc) { return halo_join_wait(s, halo_join_mark(s
 // see the stale frame).  !ov: frame, then all tiles, pass(0, ..), on the solver stream.
 // pass(sub, stream) and frame(stream) return a PCL_ code.
 template <class Pass, class Frame> int framed_x_pass(pcl_solver *s, bool ov, Pass pass, Frame frame) {
-    const bool seq = !ov || s->overlap == 2;
+    const bool seq = s->plan.frame_sequential(ov);
     const hipStream_t hs = seq ? s->stream : s->hstream;
     int rc = PCL_OK;
     if (ov && seq) rc = pass(1, s->stream);
@@ -671,7 +667,7 @@ int check_device() {
 extern "C" {
 
 const char *pcl_last_error(void) { return g_err.c_str(); }
-int pcl_version(void) { return 104; }
+int pcl_version(void) { return 105; }
 int pcl_device_count(void) {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess) return 0;
@@ -897,7 +893,7 @@ static int download(pcl_solver *s, const double *dev, double *host, int nm, cons
 
 int pcl_put_q(pcl_solver *s, const double *host, int with_ghosts) {
     if (s) s->qt.invalidate();            // quiet tiles: not a read-only call (quiet_tiles.hpp)
-    if (s) s->ghosts_drop_all();          // exchange-ahead: whatever filled the ghost frames no longer holds
+    if (s) s->plan.touched();             // exchange-ahead: whatever filled the ghost frames no longer holds
     if (!s || !host) return fail(PCL_EINVAL, "null argument");
     HIP_TRY(hipSetDevice(s->cfg.device));
     s->undo_slot = nullptr;
@@ -938,7 +934,7 @@ int pcl_get_strip(pcl_solver *s, int idim, int side, int width, double *host) {
 
 int pcl_put_strip(pcl_solver *s, int idim, int side, int width, const double *host) {
     if (s) s->qt.invalidate();            // quiet tiles: not a read-only call (quiet_tiles.hpp)
-    if (s) s->ghosts_drop_all();          // exchange-ahead: whatever filled the ghost frames no longer holds
+    if (s) s->plan.touched();             // exchange-ahead: whatever filled the ghost frames no longer holds
     if (!s || !host) return fail(PCL_EINVAL, "null argument");
     HIP_TRY(hipSetDevice(s->cfg.device));
     Window w;
@@ -1030,7 +1026,7 @@ static int sphere_mirror_launch(pcl_solver *s, int side, hipStream_t stream) {
 
 int pcl_bc(pcl_solver *s, int idim, int side, int bctype) {
     if (s) s->qt.invalidate();            // quiet tiles: not a read-only call (quiet_tiles.hpp)
-    if (s) s->ghosts_drop_all();          // exchange-ahead: whatever filled the ghost frames no longer holds
+    if (s) s->plan.touched();             // exchange-ahead: whatever filled the ghost frames no longer holds
     if (!s) return fail(PCL_EINVAL, "null argument");
     if (idim < 0 || idim >= s->cfg.ndim || side < 0 || side > 1) return fail(PCL_EINVAL, "bad idim/side");
     HIP_TRY(hipSetDevice(s->cfg.device));
@@ -1056,7 +1052,7 @@ int pcl_bc_aux(pcl_solver *s, int idim, int side, int bctype) {
 
 int pcl_bc_const(pcl_solver *s, int idim, int side, const double *state) {
     if (s) s->qt.invalidate();            // quiet tiles: not a read-only call (quiet_tiles.hpp)
-    if (s) s->ghosts_drop_all();          // exchange-ahead: whatever filled the ghost frames no longer holds
+    if (s) s->plan.touched();             // exchange-ahead: whatever filled the ghost frames no longer holds
     if (!s || !state) return fail(PCL_EINVAL, "null argument");
     if (idim < 0 || idim >= s->cfg.ndim || side < 0 || side > 1) return fail(PCL_EINVAL, "bad idim/side");
     HIP_TRY(hipSetDevice(s->cfg.device));
@@ -1072,7 +1068,7 @@ static void commit_step(pcl_solver *s, double *&buf) {
 
 int pcl_sweep(pcl_solver *s, int ids, double dt, double *cfl) {
     if (s) s->qt.invalidate();            // quiet tiles: not a read-only call (quiet_tiles.hpp)
-    if (s) s->ghosts_drop_all();          // exchange-ahead: whatever filled the ghost frames no longer holds
+    if (s) s->plan.touched();             // exchange-ahead: whatever filled the ghost frames no longer holds
     if (!s || !cfl) return fail(PCL_EINVAL, "null argument");
     if (s->cfg.kind != PCL_KIND_CLASSIC) return fail(PCL_ESTATE, "classic call on a SharpClaw solver");
     if (ids < 1 || ids > s->cfg.ndim) return fail(PCL_EINVAL, "bad ids");
@@ -1136,7 +1132,7 @@ static int step_hyperbolic(pcl_solver *s, double dt, double *cfl, bool carry, bo
 }
 
 int pcl_step_hyperbolic(pcl_solver *s, double dt, double *cfl) {
-    if (s) s->ghosts_drop_all();          // exchange-ahead: whatever filled the ghost frames no longer holds
+    if (s) s->plan.touched();             // exchange-ahead: whatever filled the ghost frames no longer holds
     if (!s || !cfl) return fail(PCL_EINVAL, "null argument");
     const bool carry = s->qt.take_valid();
     ahead_drop(s);
@@ -1185,7 +1181,7 @@ static int step_unsplit2(pcl_solver *s, const int *bc, const double *cstate, dou
     // (the overlapped form only where PCL_HALO_OVERLAP is set explicitly: with the round's marching y phase and the
     // interior-first order it measures SLOWER than the exchange in front -- 4096 x 2048 Euler block, self-neighbours:
     // no comm 0.675, exchange in front 0.726, overlapped 0.927 ms per step; dense state 1.111 / 1.145 / 1.241)
-    const bool ov = s->halo.active && s->overlap && !s->overlap_dflt;    // else: everything on the solver stream, in order
+    const bool ov = s->plan.unsplit_overlaps(s->halo.active);            // else: everything on the solver stream, in order
     int rc = framed_x_pass(
         s, ov, [&](int sub, hipStream_t st) { return unsplit_phase(s, 1, dt, sub, st); },
         [&](hipStream_t hs) {
@@ -1200,25 +1196,30 @@ static int step_unsplit2(pcl_solver *s, const int *bc, const double *cstate, dou
 }
 
 // Plan: the overlapped dimension-split 2-D step of a decomposed block.  The halo exchange runs on its own stream while
-// the x pass (onek: the one-kernel step) does the tiles of `box`, which read no ghost cell; the rim tiles follow once
-// the ghost frame has arrived.  Three orders, and the test order of PCL_HALO_OVERLAP=2.
-static int step_overlapped(pcl_solver *s, const int *bc, const double *cstate, double dt, double *cfl, bool onek,
-                           const int *box) {
+// the x pass (p.onek: the one-kernel step) does the tiles of `box`, which read no ghost cell; the rim tiles follow once
+// the ghost frame has arrived.  Which of the four launch orders runs is the plan's choice (halo_plan.hpp: OverlapPlan::plan),
+// here each order is run as chosen.
+static int step_overlapped(pcl_solver *s, const int *bc, const double *cstate, double dt, double *cfl,
+                           const OverlapPlan::Step &p, const int *box) {
     VbcScope vbc_scope(s, pcl::BcSpec(bc, cstate, 4));
     // a failed step leaves no ghost frame marked as filled
-    struct DropOnFail {
+    struct FailedUnlessDone {
         pcl_solver *s;
-        bool ok = false;
-        ~DropOnFail() { if (!ok) s->ghosts_drop_all(); }
-    } ghosts{s};
+        bool done = false;
+        ~FailedUnlessDone() { if (!done) s->plan.failed(); }
+    } step{s};
     std::string err;
-    int rc;
+    int rc = PCL_OK;
     // the x pass of the two-pass step, or the whole step where one kernel does both sweeps
     auto first = [&](int sub, hipStream_t on) {
-        return onek ? do_step2ds(s, s->q, s->t2, dt, false, sub, box, on) : do_sweep(s, s->q, s->t1, 1, dt, sub, box, on);
+        return p.onek ? do_step2ds(s, s->q, s->t2, dt, false, sub, box, on) : do_sweep(s, s->q, s->t1, 1, dt, sub, box, on);
     };
-    if (onek) s->ghosts_drop(s->t2);             // the step writes that buffer's interior: its frame is stale
-    if (onek && s->overlap == 1 && s->exchange_ahead && s->ghosts_filled(s->q)) {
+    auto exchange = [&](double *buf, hipStream_t on) {
+        return s->halo.exchange(buf, s->cfg.meqn, s->pitch, s->plane, err, on) ? fail(PCL_ECOMM, err) : PCL_OK;
+    };
+    if (p.onek) s->plan.written(s->t2);          // the step writes that buffer's interior: its frame is stale
+    switch (p.order) {
+    case OverlapPlan::RIM_FIRST: {
         // One kernel per step and the halo of THIS state already sent ahead: the rim tiles (everything a neighbour
         // needs of the new state, and everything that reads the ghost frame) go first, on the halo stream behind the
         // exchange that filled the frame; the new state's halo follows them there at once -- it travels while the
@@ -1229,16 +1230,16 @@ static int step_overlapped(pcl_solver *s, const int *bc, const double *cstate, d
         rc = first(2, s->hstream);
         const hipError_t mark = halo_join_mark(s);
         if (!rc) rc = first(1, nullptr);
-        if (!rc && s->halo.exchange(s->t2, s->cfg.meqn, s->pitch, s->plane, err, s->hstream)) rc = fail(PCL_ECOMM, err);
+        if (!rc) rc = exchange(s->t2, s->hstream);
         rc = halo_join_wait(s, mark, rc);
         if (rc) return bail(s, rc);
         s->form.ran(1);
         commit_step(s, s->t2);
-        s->ghosts_mark(s->q);
-        ghosts.ok = true;
+        s->plan.exchanged(s->q);
+        step.done = true;
         return read_cfl(s, cfl);
     }
-    if (onek && s->overlap == 1 && !s->exchange_ahead) {
+    case OverlapPlan::EXCHANGE_IN_FRONT:
         // One kernel per step, no exchange-ahead: the exchange runs in front of the step on the solver stream and
         // the step is ONE launch.  (An interior launch beside the exchange and a rim launch behind it, the two-pass
         // step's scheme, costs this kernel more than it hides: it fills every CU's LDS and registers, the rim
@@ -1247,56 +1248,58 @@ static int step_overlapped(pcl_solver *s, const int *bc, const double *cstate, d
         // Behind the exchange the block steps like a single one: ONE launch or, where every cell is active, the x
         // pass + y pass -- the faster form, timed afresh every 256 steps by this rank for itself (step_form.hpp;
         // 4096^2 block, dense state: one kernel 1.01 ms, two passes 0.86).
-        rc = s->halo.exchange(s->q, s->cfg.meqn, s->pitch, s->plane, err) ? fail(PCL_ECOMM, err) : PCL_OK;
-        if (rc) return bail(s, rc);
-        s->ghosts_drop_all();
+        if (int rx = exchange(s->q, nullptr)) return bail(s, rx);
+        s->plan.touched();                       // no frame stays marked: the step swaps the buffers
         return step_hyperbolic(s, dt, cfl, false, true);    // swaps the buffers, reads the (all-reduced) Courant number
-    }
-    if (s->overlap == 2) {
+    case OverlapPlan::TEST_ORDER:
         // test mode (PCL_HALO_OVERLAP=2): same launches on ONE stream with the interior tiles strictly
         // BEFORE the exchange -- an interior tile that read a ghost cell would see the stale frame
         rc = first(1, nullptr);
-        if (!rc && s->halo.exchange(s->q, s->cfg.meqn, s->pitch, s->plane, err)) rc = fail(PCL_ECOMM, err);
+        if (!rc) rc = exchange(s->q, nullptr);
         if (!rc) rc = first(2, nullptr);
-    } else {
-        // exchange-ahead: the previous step (or a retaken step's first attempt) already exchanged this buffer's
-        // halo on the halo stream; the rim tiles queue up behind it there
-        const bool have = s->exchange_ahead && s->ghosts_filled(s->q);
-        if (!have)
+        break;
+    case OverlapPlan::INTERIOR_FIRST:
+        // p.have, exchange-ahead: the previous step (or a retaken step's first attempt) already exchanged this
+        // buffer's halo on the halo stream; the rim tiles queue up behind it there
+        if (!p.have)
             if (int rf = halo_fork(s, s->ev_h0)) return bail(s, rf);      // q of the previous step is complete
         // The interior tiles go FIRST: the step starts on an idle device (the host has just read the previous
         // Courant number), and the host needs some tens of microseconds to enqueue the group of Send/Recv -- with
         // the interior launch already queued the device works through that time instead of waiting for it
         rc = first(1, nullptr);      // interior tiles, concurrent with the exchange
-        if (!rc && !have) {
-            if (s->halo.exchange(s->q, s->cfg.meqn, s->pitch, s->plane, err, s->hstream)) rc = fail(PCL_ECOMM, err);
-            else s->ghosts_mark(s->q);
+        if (!rc && !p.have) {
+            rc = exchange(s->q, s->hstream);
+            if (!rc) s->plan.exchanged(s->q);
         }
         // rim tiles (ghost frame + physical BCs) behind the exchange on ITS stream: they start as soon as
         // the frame has arrived and fill the machine next to the interior kernel's tail
         if (!rc) rc = first(2, s->hstream);
         rc = halo_join(s, rc);
+        break;
+    case OverlapPlan::NOT_OVERLAPPED:
+        return fail(PCL_ESTATE, "step_overlapped without an overlapped plan");
     }
+    // the tail of the last two orders
     if (rc) return bail(s, rc);
-    if (!onek) {
-        s->ghosts_drop(s->t2);                   // the y pass writes that buffer, ghost rows included
+    if (!p.onek) {
+        s->plan.written(s->t2);                  // the y pass writes that buffer, ghost rows included
         if (int rc2 = do_sweep(s, s->t1, s->t2, 2, dt)) return bail(s, rc2);
     }
-    s->form.ran(onek ? 1 : 0);
+    s->form.ran(p.onek ? 1 : 0);
     commit_step(s, s->t2);
-    if (s->exchange_ahead && s->overlap == 1) {
+    if (p.send_ahead) {
         // The new state's halo travels NOW, behind the y pass, on the halo stream: through the Courant number's
         // hand-over and the host's decision.  If the step is rejected the exchange was for nothing -- the pre-step
         // buffer comes back (pcl_undo_step) with its own ghost frame still filled.  The CFL all-reduce is
         // enqueued FIRST (read_cfl's issue order on the communicator: all-reduce, then this group, on every rank).
         if (int rc3 = read_cfl_begin(s)) return rc3;
         if (int rf = halo_fork(s, s->ev_y, "exchange-ahead fork: ")) return bail(s, rf);
-        if (s->halo.exchange(s->q, s->cfg.meqn, s->pitch, s->plane, err, s->hstream)) return bail(s, fail(PCL_ECOMM, err));
-        s->ghosts_mark(s->q);
-        ghosts.ok = true;
+        if (int rx = exchange(s->q, s->hstream)) return bail(s, rx);
+        s->plan.exchanged(s->q);
+        step.done = true;
         return read_cfl_end(s, cfl);
     }
-    ghosts.ok = true;
+    step.done = true;
     return read_cfl(s, cfl);
 }
 
@@ -1305,7 +1308,6 @@ static int step_overlapped(pcl_solver *s, const int *bc, const double *cstate, d
 static int step_loading_bcs(pcl_solver *s, const int *bc, const double *cstate, double dt, double *cfl, bool carry) {
     if (int rc = exchange_in_front(s)) return rc;
     VbcScope vbc_scope(s, pcl::BcSpec(bc, cstate, 2 * s->cfg.ndim));
-    s->ghosts_drop_all();
     // (a decomposed block behind its exchange: the faster form, too)
     return step_hyperbolic(s, dt, cfl, carry && !s->halo.active, s->halo.active);
 }
@@ -1319,7 +1321,6 @@ static int step_ghost_fills(pcl_solver *s, const int *bc, const double *cstate, 
             if (t < 0) continue;
             if (int rc = bc_side(s, idim, side, t, cstate)) return rc;
         }
-    s->ghosts_drop_all();
     return step_hyperbolic(s, dt, cfl, false, false);
 }
 
@@ -1386,32 +1387,24 @@ int pcl_bc_step(pcl_solver *s, const int *bc, const double *cstate, double dt, d
     const bool fused = s->cfg.meqn <= 8 && (s->cfg.ndim == 1 || (s->cfg.ndim == 2 && s->cfg.method[2] < 0));
     // Decomposed dim-split 2-D step: the halo exchange runs on its own stream while the x pass does the
     // tiles that read no ghost cell; the rim tiles follow once the ghost frame has arrived.
-    int box[4], ntiles[2];
-    // both sweeps in one kernel (its own, taller tiles) where such tiles leave an interior; thin blocks keep the x pass'
-    // 4-row tiles for the overlap
-    bool onek = fused_step_ok(s), overlapped = false;
-    if (s->halo.active && fused && s->cfg.ndim == 2 && s->overlap && s->sel == 0) {
-        // (exchange-ahead in the two-pass order, agreed by the ranks because some block is too thin for one-kernel tiles:
-        // this rank keeps that order too)
-        if (s->exchange_ahead == 1) onek = false;
-        if (onek && pcl::exact::step2ds_interior_box(make_args(s, s->q, s->t2, 1, dt), box, ntiles)) overlapped = true;
-        else {
-            onek = false;
-            overlapped = (twopass_overlap_ok(s) || s->exchange_ahead == 1) &&
-                         pcl::exact::x_interior_box(make_args(s, s->q, s->t1, 1, dt), box, ntiles);
-        }
-    }
-    if (!overlapped) s->ghosts_drop_all();       // exchange-ahead lives in the overlapped dimension-split step only
+    // Both sweeps in one kernel (its own, taller tiles) where such tiles leave an interior; thin blocks keep the x pass'
+    // 4-row tiles for the overlap.  Whether, in which form and in which launch order: OverlapPlan::plan; any other answer
+    // than an overlapped step has dropped every ghost-frame mark.
+    const OverlapPlan::Step plan = s->plan.plan(block_facts(s), s->q);
+    const bool overlapped = plan.order != OverlapPlan::NOT_OVERLAPPED;
+    int box[4];
     if (overlapped) {
+        const pcl::InteriorBox &in = plan.onek ? s->box_onek : s->box_x;
+        std::copy(in.box, in.box + 4, box);
         // a side without a neighbour block gets its ghost cells from the boundary conditions the kernel evaluates
         // while loading -- nothing there waits for the exchange, so the interior box reaches that edge
         if (!s->halo.has(pcl::S)) box[0] = 0;
-        if (!s->halo.has(pcl::N)) box[1] = ntiles[0];
+        if (!s->halo.has(pcl::N)) box[1] = in.ntiles[0];
         if (!s->halo.has(pcl::W)) box[2] = 0;
-        if (!s->halo.has(pcl::E)) box[3] = ntiles[1];
+        if (!s->halo.has(pcl::E)) box[3] = in.ntiles[1];
     }
     if (s->cfg.ndim == 2 && s->cfg.method[2] >= 0 && s->sel == 0) return step_unsplit2(s, bc, cstate, dt, cfl);
-    if (overlapped) return step_overlapped(s, bc, cstate, dt, cfl, onek, box);
+    if (overlapped) return step_overlapped(s, bc, cstate, dt, cfl, plan, box);
     if (fused) {
         if (int rc = step_loading_bcs(s, bc, cstate, dt, cfl, carry)) return rc;
         return ahead_enqueue(s, spec, dt, *cfl);
@@ -1445,7 +1438,7 @@ int pcl_backup(pcl_solver *s) {
 
 int pcl_restore(pcl_solver *s) {
     if (s) s->qt.invalidate();            // quiet tiles: not a read-only call (quiet_tiles.hpp)
-    if (s) s->ghosts_drop_all();          // exchange-ahead: whatever filled the ghost frames no longer holds
+    if (s) s->plan.touched();             // exchange-ahead: whatever filled the ghost frames no longer holds
     if (!s) return fail(PCL_EINVAL, "null argument");
     if (!s->bak) return fail(PCL_ESTATE, "pcl_restore without pcl_backup");
     HIP_TRY(hipSetDevice(s->cfg.device));
@@ -1457,7 +1450,7 @@ int pcl_restore(pcl_solver *s) {
 
 int pcl_src(pcl_solver *s, int src_id, double dt, const double *params, int nparams) {
     if (s) s->qt.invalidate();            // quiet tiles: not a read-only call (quiet_tiles.hpp)
-    if (s) s->ghosts_drop_all();          // exchange-ahead: whatever filled the ghost frames no longer holds
+    if (s) s->plan.touched();             // exchange-ahead: whatever filled the ghost frames no longer holds
     if (!s) return fail(PCL_EINVAL, "null argument");
     HIP_TRY(hipSetDevice(s->cfg.device));
     if (src_id == PCL_SRC_EULER_RADIAL) {
@@ -1588,7 +1581,7 @@ static int cellfn_loaded(pcl_solver *s, long id, int kind, const void *code, hip
 
 int pcl_cellfn_apply(pcl_solver *s, pcl_cellfn *f, double t, double dt, const double *params, int nparams) {
     if (s) s->qt.invalidate();            // quiet tiles: not a read-only call (quiet_tiles.hpp)
-    if (s) s->ghosts_drop_all();          // exchange-ahead: whatever filled the ghost frames no longer holds
+    if (s) s->plan.touched();             // exchange-ahead: whatever filled the ghost frames no longer holds
     if (nparams < 0 || nparams > PCL_CELLFN_MAX_PARAMS)
         return fail(PCL_EINVAL, "pcl_cellfn_apply: a cell function takes at most 16 parameters");
     if (!s || !f || (nparams > 0 && !params)) return fail(PCL_EINVAL, "null argument");
@@ -1639,7 +1632,7 @@ int pcl_cellfn_apply(pcl_solver *s, pcl_cellfn *f, double t, double dt, const do
 
 int pcl_cellbc_apply(pcl_solver *s, pcl_cellfn *f, int idim, int side, double t, const double *params, int nparams) {
     if (s) s->qt.invalidate();            // quiet tiles: not a read-only call (quiet_tiles.hpp)
-    if (s) s->ghosts_drop_all();          // exchange-ahead: whatever filled the ghost frames no longer holds
+    if (s) s->plan.touched();             // exchange-ahead: whatever filled the ghost frames no longer holds
     // host-only checks first, in an order that needs no solver for the ones that do not depend on it
     if (nparams < 0 || nparams > PCL_CELLFN_MAX_PARAMS)
         return fail(PCL_EINVAL, "pcl_cellbc_apply: a cell function takes at most 16 parameters");
@@ -1728,7 +1721,7 @@ int pcl_sharp_fuse_dq_src(pcl_solver *s, int src_id, const double *params, int n
 
 int pcl_select(pcl_solver *s, int reg) {
     if (s) s->qt.invalidate();            // quiet tiles: not a read-only call (quiet_tiles.hpp)
-    if (s) s->ghosts_drop_all();          // exchange-ahead: whatever filled the ghost frames no longer holds
+    if (s) s->plan.touched();             // exchange-ahead: whatever filled the ghost frames no longer holds
     if (!s) return fail(PCL_EINVAL, "null argument");
     if (reg == 0) { s->sel = 0; return PCL_OK; }
     if (s->cfg.kind != PCL_KIND_SHARPCLAW || reg < 0 || reg > 4) return fail(PCL_EINVAL, "bad register");
@@ -1790,7 +1783,7 @@ static int sharp_passes(pcl_solver *s, double dt, int rk_op, const double *ra, c
     int first = 1;
     if (bc) {
         rc = framed_x_pass(
-            s, s->halo.active && s->overlap && s->cfg.ndim == 2, [&](int sub, hipStream_t st) { return pass(1, sub, st); },
+            s, s->plan.sharp_overlaps(s->halo.active, s->cfg.ndim), [&](int sub, hipStream_t st) { return pass(1, sub, st); },
             [&](hipStream_t hs) { return sharp_frame(s, bc, cstate, hs); });
         first = 2;
     }
@@ -2328,7 +2321,8 @@ static hipError_t create_halo_stream(hipStream_t *st) {
     return hipStreamCreateWithPriority(st, hipStreamNonBlocking, greatest);
 }
 
-// what both communicator set-ups end with: the halo stream and its events, and the overlap mode
+// what both communicator set-ups end with: the halo stream and its events, the overlap mode, and the interior boxes of
+// a 2-D block's tiles (they depend on the block's extents alone)
 static int comm_ready(pcl_solver *s) {
     if (!s->hstream) {
         HIP_TRY(create_halo_stream(&s->hstream));
@@ -2336,8 +2330,12 @@ static int comm_ready(pcl_solver *s) {
         HIP_TRY(hipEventCreateWithFlags(&s->ev_h1, hipEventDisableTiming));
     }
     const char *e = getenv("PCL_HALO_OVERLAP");
-    s->overlap = e ? atoi(e) : 1;
-    s->overlap_dflt = e == nullptr;
+    s->plan.configure(e ? atoi(e) : 1, e != nullptr);
+    if (s->cfg.ndim == 2) {
+        const pcl::BlockGeom g{s->cfg.n[0], s->cfg.n[1], s->cfg.mbc, s->I, s->J};
+        s->box_onek.any = pcl::exact::step2ds_interior_box(g, s->box_onek.box, s->box_onek.ntiles);
+        s->box_x.any = pcl::exact::x_interior_box(g, s->box_x.box, s->box_x.ntiles);
+    }
     return PCL_OK;
 }
 
@@ -2410,13 +2408,8 @@ int pcl_comm_init_host(pcl_solver *s, int nranks, int rank, const int neighbors[
 int pcl_halo_can_overlap(pcl_solver *s, int *yes) {
     if (s) s->qt.invalidate();            // quiet tiles: not a read-only call (quiet_tiles.hpp)
     if (!s || !yes) return fail(PCL_EINVAL, "null argument");
-    int box[4], ntiles[2];
-    const bool base = s->halo.active && s->cfg.kind == PCL_KIND_CLASSIC && s->cfg.ndim == 2 && s->cfg.method[2] < 0 &&
-                      s->cfg.meqn <= 8 && s->overlap == 1;
     // 2: this block can also run the one-kernel step with interior / rim tile subsets; 1: the two-pass step only
-    *yes = !base ? 0
-           : (fused_step_ok(s) && pcl::exact::step2ds_interior_box(make_args(s, s->q, s->t2, 1, 1.0), box, ntiles)) ? 2
-           : (twopass_overlap_ok(s) && pcl::exact::x_interior_box(make_args(s, s->q, s->t1, 1, 1.0), box, ntiles)) ? 1 : 0;
+    *yes = s->plan.offers(block_facts(s));
     return PCL_OK;
 }
 
@@ -2434,14 +2427,13 @@ int pcl_halo_exchange_ahead(pcl_solver *s, int on) {
     }
     // 1: the two-pass step's order on the communicator (all-reduce, then the new state's exchange); 2: the one-kernel
     // step's (the exchange behind the rim tiles, then the all-reduce).  Every rank of a run must hold the same value.
-    s->exchange_ahead = on == 2 ? 2 : on ? 1 : 0;
-    s->ghosts_drop_all();
+    s->plan.set_exchange_ahead(on);
     return PCL_OK;
 }
 
 int pcl_halo_exchange(pcl_solver *s) {
     if (s) s->qt.invalidate();            // quiet tiles: not a read-only call (quiet_tiles.hpp)
-    if (s) s->ghosts_drop_all();          // exchange-ahead: whatever filled the ghost frames no longer holds
+    if (s) s->plan.touched();             // exchange-ahead: whatever filled the ghost frames no longer holds
     if (!s) return fail(PCL_EINVAL, "null argument");
     HIP_TRY(hipSetDevice(s->cfg.device));
     std::string err;
@@ -2513,6 +2505,12 @@ int pcl_step_ahead_trace(int on, double cfl_desired, double cfl_max, double dt_m
         else return fail(PCL_EINVAL, "bad event");
     }
     return PCL_OK;
+}
+
+int pcl_halo_plan_trace(long n, const int *event, const int *a, const int *b, int *out) {
+    if (n < 0 || !event || !a || !b || !out) return fail(PCL_EINVAL, "bad argument");
+    const char *bad = pcl::overlap_plan_trace(n, event, a, b, out);
+    return bad ? fail(PCL_EINVAL, bad) : PCL_OK;
 }
 
 int pcl_allreduce_max(pcl_solver *s, double *value) {

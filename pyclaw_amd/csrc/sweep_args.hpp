@@ -204,6 +204,12 @@ struct TileHandover {
 // sharp: the SharpClaw kernels, sharp_high: those of weno_order 7..17 too, sharp_wave: the wave-based 1-D kernel.
 struct RpFacts { int id, ndim, meqn, mwaves, naux; bool fwave, onek, onek_aux, sharp, sharp_high, sharp_wave; };
 
+// A 2-D block as the interior-box functions see it: interior cells, ghost layers, cells with ghosts.
+struct BlockGeom { int mx, my, mbc, I, J; };
+// The tiles of a pass that read no ghost cell: box = [lo, hi) of the tile rows, [lo, hi) of the tiles along a row;
+// ntiles = the counts of either; any: the box is not empty.
+struct InteriorBox { bool any = false; int box[4] = {0, 0, 0, 0}, ntiles[2] = {0, 0}; };
+
 // defined in kernels.hip, once per arithmetic mode; returns 0 or a PCL_E* code + message
 namespace exact {
 const RpFacts *rp_facts(int rp);    // null: no built-in solver has this id (the same in every mode)
@@ -211,8 +217,8 @@ int launch_sweep(const SweepLaunch &l, std::string &err);
 int launch_step2ds(const SweepLaunch &l, std::string &err);   // whole dim-split 2-D step in one kernel (classic_fused.hpp)
 // x-pass tiles [tb_lo,tb_hi) x [ta_lo,ta_hi) that read no ghost cell; false if there are none
 // ntiles[0], ntiles[1] = row tiles / tiles along a row of the x pass
-bool x_interior_box(const SweepArgs &a, int box[4], int ntiles[2]);
-bool step2ds_interior_box(const SweepArgs &a, int box[4], int ntiles[2]);   // the same for the one-kernel step: (nty, ntx)
+bool x_interior_box(const BlockGeom &a, int box[4], int ntiles[2]);
+bool step2ds_interior_box(const BlockGeom &a, int box[4], int ntiles[2]);   // the same for the one-kernel step: (nty, ntx)
 int launch_tile_handover(const TileHandover &h, std::string &err);   // Courant hand-over + next tile list (bit-only)
 int launch_sweep3(const SweepLaunch &l, std::string &err);   // 3-D dim-split sweep, l.ids = direction 1..3
 int launch_unsplit3(const Unsplit3Launch &l, std::string &err);   // unsplit 3-D: slices + combine of one direction
