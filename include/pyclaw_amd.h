@@ -246,8 +246,32 @@ int pcl_put_aux_strip(pcl_solver *s, int idim, int side, int width, const double
  * after every step): gather `ncell` interior cells (0-based interior indices ij[2*c], ij[2*c+1];
  * the second is ignored in 1-D; on a 3-D grid the tuples are triples ij[3*c], ij[3*c+1], ij[3*c+2]) of the resident q -- and of aux when `aux` is not NULL -- into
  * q[ncell][meqn] / aux[ncell][maux].  One small kernel + one D2H of ncell*(meqn+maux) doubles
- * instead of reading the whole state back every step. */
+ * instead of reading the whole state back every step.  Read-only for the bits, not for the time: the call ends with a
+ * synchronisation of the solver's stream, so behind a pcl_bc_step that has enqueued the next step ahead (pcl_step_ahead)
+ * it waits for that whole step as well.  A caller that wants the gauge cells of EVERY step uses the gauge log below. */
 int pcl_get_cells(pcl_solver *s, int ncell, const int *ij, double *q, double *aux);
+/* Device gauge log: the same cells recorded by every step itself, read whenever the caller likes.  While the log is armed,
+ * pcl_bc_step and pcl_step_hyperbolic enqueue one more small kernel behind the step (every plan and form of it; behind an
+ * adopted step of pcl_step_ahead too, in front of the step they enqueue ahead) that copies the gauge cells of the NEW
+ * state into the next record of a device-resident log -- on the solver's stream, no synchronisation, no host copy.  There
+ * is no per-step call by design: it would have to make the next one-kernel step compute every tile and drop a step
+ * enqueued ahead, every step.
+ * pcl_gauge_log arms: ij as for pcl_get_cells (checked the same way: PCL_EINVAL for a cell outside the interior), uploaded
+ * once; capacity >= 1 records of ncell * per doubles, per = meqn + maux (maux counts when the handle has an aux array; per
+ * is fixed while the log is armed, and a step that finds it changed fails with PCL_ESTATE).  Arming again replaces the log
+ * and its counters; ncell = 0 disarms and frees, as pcl_destroy does.  Classic solvers only: PCL_ESTATE on a SharpClaw
+ * handle (its stages are not steps).
+ * A step with the log full (capacity records held) fails with PCL_ESTATE before it launches anything: the log never
+ * writes past its end.  pcl_undo_step and pcl_restore take the record of the last step back with the step, once: a
+ * rejected step leaves no record, and the retake writes the same slot.
+ * pcl_gauge_log_read: ONE device-to-host copy of the *nrecords records held and one synchronisation; out[r][c][m], record
+ * major (oldest first), then cell, then the meqn components of q, then the aux components.  The log is empty afterwards.
+ * PCL_EINVAL, and nothing read, when max_records is smaller than the records held.
+ * pcl_gauge_log_stats: records written, records taken back and reads since the log was armed.
+ * None of the three is a read-only call: a step enqueued ahead is dropped by the next pcl_bc_step. */
+int pcl_gauge_log(pcl_solver *s, int ncell, const int *ij, int capacity);
+int pcl_gauge_log_read(pcl_solver *s, int max_records, double *out, int *nrecords);
+int pcl_gauge_log_stats(pcl_solver *s, long *recorded, long *popped, long *reads);
 
 /* One homogeneous step of length dt on the resident state (ghost cells must be filled):
  * dim-split  = step2ds(ids=1) then step2ds(ids=2)          clawpack.py:538-546
@@ -557,13 +581,18 @@ int pcl_ghost_map(int k, int n, int mbc, int lo, int hi, int out_src_neg_cst_sid
  * state buffer b[i]): out = order | 8 * onek | 16 * have | 32 * send_ahead, order 0 not overlapped, 1 rim first,
  * 2 exchange in front, 3 test order, 4 interior first; 4 out = filled(a[i]); 5 exchanged(a[i]); 6 written(a[i]);
  * 7 touched(); 8 failed(); 9 out = unsplit_overlaps(active = a[i]); 10 out = sharp_overlaps(active = a[i], ndim = b[i]);
- * 11 out = frame_sequential(overlapping = a[i]). */
+ * 11 out = frame_sequential(overlapping = a[i]).
+ * pcl_gauge_log_trace (csrc/gauge_log.hpp): event[i]: 0 arm with capacity a[i]; 1 a step, value = the slot it writes or
+ * -1 (refused: the log is full); 2 pcl_undo_step and 3 pcl_restore, value = 1 if a record was taken back; 4 a read, value
+ * = the records it returns; 5 disarm.  out[4 i ..] = value, records held, whether the last step's record is still the
+ * newest (what an undo would take), armed -- all behind the event. */
 int pcl_step_form_trace(long n, const int *event, const int *a, const int *b, const long *listed, long ntiles,
                         const double *seconds, int *out);
 int pcl_step_ahead_trace(int on, double cfl_desired, double cfl_max, double dt_max, long n, const int *event,
                          const int *flag, const double *x, const double *y, const long *ran, const long *ntiles,
                          const int *bc, const double *cstate, int *out, double *out_dt);
 int pcl_halo_plan_trace(long n, const int *event, const int *a, const int *b, int *out);
+int pcl_gauge_log_trace(long n, const int *event, const int *a, int *out);
 
 /* ---- debug / self-test --------------------------------------------------------------- */
 /* Runs the wavefront neighbour-shift primitive on 64 values: left[l]=in[l-1],

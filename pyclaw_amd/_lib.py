@@ -81,6 +81,9 @@ PROTOTYPES = {
     "pcl_put_strip": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, dp]),
     "pcl_put_aux_strip": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, dp]),
     "pcl_get_cells": (C.c_int, [C.c_void_p, C.c_int, ip, dp, dp]),
+    "pcl_gauge_log": (C.c_int, [C.c_void_p, C.c_int, ip, C.c_int]),
+    "pcl_gauge_log_read": (C.c_int, [C.c_void_p, C.c_int, dp, ip]),
+    "pcl_gauge_log_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_long), C.POINTER(C.c_long), C.POINTER(C.c_long)]),
     "pcl_step_hyperbolic": (C.c_int, [C.c_void_p, C.c_double, dp]),
     "pcl_undo_step": (C.c_int, [C.c_void_p]),
     "pcl_bc_step": (C.c_int, [C.c_void_p, ip, dp, C.c_double, dp]),
@@ -142,6 +145,7 @@ PROTOTYPES = {
     "pcl_step_ahead_trace": (C.c_int, [C.c_int, C.c_double, C.c_double, C.c_double, C.c_long, ip, ip, dp, dp,
                                        C.POINTER(C.c_long), C.POINTER(C.c_long), ip, dp, ip, dp]),
     "pcl_halo_plan_trace": (C.c_int, [C.c_long, ip, ip, ip, ip]),
+    "pcl_gauge_log_trace": (C.c_int, [C.c_long, ip, ip, ip]),
     "pcl_debug_wave_shift": (C.c_int, [dp, dp, dp]),
 }
 

@@ -100,6 +100,7 @@ class ClawSolver(Solver):
         state = solution.states[0]
         if self._fuse_key != (id(self.step_src), self.src_split):      # changed after setup(): decide again
             self._decide_src_fusion(state)
+            self._gauge_log_decide()         # (what runs behind the hyperbolic step may have changed with it)
         if isinstance(self.start_step, CellStartStep):
             self.start_step.apply(self, state)        # on the resident state, no round trip
         elif self.start_step is not None:
@@ -160,6 +161,11 @@ class ClawSolver(Solver):
 
     def check_cfl_settings(self):
         pass
+
+    def _gauge_log_eligible(self):
+        # the record is taken behind the hyperbolic step: nothing may touch q behind it inside step().  start_step (device
+        # or Python), Python boundary callbacks and CellBC all run in front of it.
+        return self.step_src is None or (self.src_split == 1 and self._src_fused)
 
     def step_hyperbolic(self, solution):
         r"""One homogeneous step on the resident state (clawpack.py:299-323,510-555)."""

@@ -20,6 +20,7 @@
 #include "step_form.hpp"
 #include "step_ahead.hpp"
 #include "halo_plan.hpp"
+#include "gauge_log.hpp"
 #include "cellfn.hpp"
 
 namespace {
@@ -83,6 +84,11 @@ struct pcl_solver {
     pcl::InteriorBox box_onek, box_x;       // of the one-kernel step's tiles / of the x pass' tiles
     pcl::QuietTiles qt;             // quiet tiles of the one-kernel dim-split step: state and invariants in quiet_tiles.hpp
     pcl::StepAhead ahead; // step ahead (pcl_step_ahead): decisions and counters in step_ahead.hpp
+    // device gauge log (pcl_gauge_log): slots and counters in gauge_log.hpp; here the gauge cells' index tuples and the
+    // records, capacity * ncell * per doubles, both device memory
+    pcl::GaugeLog glog;
+    int *glog_ij = nullptr;
+    double *glog_buf = nullptr;
     // cell functions (cellfn.hpp): the modules this handle has loaded, and where the block sits in the global grid
     // (pcl_cellfn_geometry; c.i and c.x of a body are global)
     pcl::CellfnModules cellfn;
@@ -834,6 +840,8 @@ void pcl_destroy(pcl_solver *s) {
     for (int k = 1; k < 5; k++)
         if (s->sreg[k]) hipFree(s->sreg[k] - s->lead);
     hipFree(s->cfl_dev);
+    if (s->glog_ij) hipFree(s->glog_ij);
+    if (s->glog_buf) hipFree(s->glog_buf);
     s->qt.destroy();
     if (s->cfl_host) hipHostFree(s->cfl_host);
     if (s->ev0) hipEventDestroy(s->ev0);
@@ -997,6 +1005,118 @@ int pcl_get_cells(pcl_solver *s, int ncell, const int *ij, double *q, double *au
     return PCL_OK;
 }
 
+// ---- device gauge log (pcl::GaugeLog, gauge_log.hpp: which slot, what a rejected step takes back, when it refuses) ----
+// One record: the gauge cells of q (and aux) into log[(slot * ncell + c) * per + m], one thread per (cell, component), the
+// cell addressing of gather_cells_kernel.  ij is device-resident, uploaded once when the log was armed.
+__global__ void gauge_record_kernel(const double *q, const double *aux, const int *ij, double *log, int slot, int ncell,
+                                    int nq, int na, int mbc, int ndim, long pitch, long plane, long slab) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    const int per = nq + na;
+    if (t >= ncell * per) return;
+    const int c = t / per, m = t % per;
+    const int st = ndim > 2 ? 3 : 2;
+    const long cell = (long)(ndim > 2 ? ij[st * c + 2] + mbc : 0) * slab + (long)(ndim > 1 ? ij[st * c + 1] + mbc : 0) * pitch +
+                      ij[st * c] + mbc;
+    log[((long)slot * ncell + c) * per + m] = m < nq ? q[m * plane + cell] : aux[(m - nq) * plane + cell];
+}
+
+static void gauge_log_free(pcl_solver *s) {
+    if (s->glog_ij) hipFree(s->glog_ij);
+    if (s->glog_buf) hipFree(s->glog_buf);
+    s->glog_ij = nullptr;
+    s->glog_buf = nullptr;
+    s->glog.disarm();
+}
+
+// At the top of a step entry point, before anything is launched: an armed log must have room for this step's record
+static int gauge_log_ready(pcl_solver *s) {
+    if (!s->glog.is_armed()) return PCL_OK;
+    if (s->glog.full()) return fail(PCL_ESTATE, "gauge log is full: pcl_gauge_log_read before the next step");
+    // (the aux buffer exists from pcl_create on for maux > 0, so the stride cannot change under an armed log today)
+    if (s->glog.stride() != s->cfg.meqn + (s->aux ? s->cfg.maux : 0))
+        return fail(PCL_ESTATE, "gauge log was armed without aux: arm it again behind pcl_put_aux");
+    return PCL_OK;
+}
+
+// Behind the point where a step's result has become the state (commit_step), in front of any ahead_enqueue of the same
+// call: the record of the NEW state, on the solver stream, no synchronisation, no host copy.  Why nothing overwrites what
+// it reads: the record of state n is enqueued in call n; the launch that overwrites state n's buffer is step n + 2 (step
+// n + 1 reads it and writes the other buffer), enqueued at the earliest in call n + 1 (ahead_enqueue); everything is on
+// one stream.  A step enqueued ahead records nothing until it is adopted; a dropped one never records.
+static int gauge_record(pcl_solver *s) {
+    if (!s->glog.is_armed()) return PCL_OK;
+    const int slot = s->glog.slot_for_step();
+    if (slot < 0) return fail(PCL_ESTATE, "gauge log is full");          // (gauge_log_ready has asked before the step)
+    const int ncell = s->glog.cells(), nq = s->cfg.meqn, na = s->glog.stride() - nq;
+    hipLaunchKernelGGL(gauge_record_kernel, dim3((ncell * (nq + na) + 255) / 256), dim3(256), 0, s->stream, cur(s), s->aux,
+                       s->glog_ij, s->glog_buf, slot, ncell, nq, na, s->cfg.mbc, s->cfg.ndim, s->pitch, s->plane,
+                       s->pitch * s->J);
+    HIP_TRY(hipGetLastError());
+    return PCL_OK;
+}
+static inline int gauge_recorded(pcl_solver *s, int rc) { return rc ? rc : gauge_record(s); }
+
+int pcl_gauge_log(pcl_solver *s, int ncell, const int *ij, int capacity) {
+    if (s) s->qt.invalidate();            // quiet tiles: not a read-only call (quiet_tiles.hpp)
+    if (!s) return fail(PCL_EINVAL, "null argument");
+    HIP_TRY(hipSetDevice(s->cfg.device));
+    if (ncell == 0) {                     // disarm
+        HIP_TRY(hipStreamSynchronize(s->stream));       // a record may still be in flight
+        gauge_log_free(s);
+        return PCL_OK;
+    }
+    if (s->cfg.kind != PCL_KIND_CLASSIC) return fail(PCL_ESTATE, "pcl_gauge_log: classic solvers only");
+    if (ncell < 0 || !ij || capacity < 1) return fail(PCL_EINVAL, "pcl_gauge_log: bad argument");
+    const int st = s->cfg.ndim > 2 ? 3 : 2;
+    for (int c = 0; c < ncell; c++) {
+        const int i = ij[st * c], j = s->cfg.ndim > 1 ? ij[st * c + 1] : 0, k = s->cfg.ndim > 2 ? ij[st * c + 2] : 0;
+        if (i < 0 || i >= s->cfg.n[0] || j < 0 || j >= (s->cfg.ndim > 1 ? s->cfg.n[1] : 1) ||
+            k < 0 || k >= (s->cfg.ndim > 2 ? s->cfg.n[2] : 1))
+            return fail(PCL_EINVAL, "pcl_gauge_log: cell index outside the interior");
+    }
+    const int per = s->cfg.meqn + (s->aux ? s->cfg.maux : 0);
+    const size_t rec = (size_t)ncell * per;
+    if (rec > (size_t)1 << 24 || rec * capacity > (size_t)1 << 28)       // (2 GiB of log, and int thread indices)
+        return fail(PCL_EINVAL, "pcl_gauge_log: ncell * (meqn + maux) * capacity is too large");
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    gauge_log_free(s);
+    const size_t idx_bytes = (size_t)ncell * st * sizeof(int);
+    hipError_t e = hipMalloc((void **)&s->glog_ij, idx_bytes);
+    if (e == hipSuccess) e = hipMalloc((void **)&s->glog_buf, rec * capacity * sizeof(double));
+    // (pageable host memory: the copy has left `ij` when the call returns)
+    if (e == hipSuccess) e = hipMemcpyAsync(s->glog_ij, ij, idx_bytes, hipMemcpyHostToDevice, s->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
+    if (e != hipSuccess) {
+        gauge_log_free(s);
+        return fail(PCL_EHIP, std::string("pcl_gauge_log: ") + hipGetErrorString(e));
+    }
+    s->glog.arm(ncell, per, capacity);
+    return PCL_OK;
+}
+
+int pcl_gauge_log_read(pcl_solver *s, int max_records, double *out, int *nrecords) {
+    if (s) s->qt.invalidate();            // quiet tiles: not a read-only call (quiet_tiles.hpp)
+    if (!s || !nrecords || (!out && max_records > 0)) return fail(PCL_EINVAL, "null argument");
+    if (!s->glog.is_armed()) return fail(PCL_ESTATE, "pcl_gauge_log_read: the log is not armed");
+    const int n = s->glog.held();
+    if (max_records < n) return fail(PCL_EINVAL, "pcl_gauge_log_read: max_records is smaller than the records held");
+    HIP_TRY(hipSetDevice(s->cfg.device));
+    if (n > 0)
+        HIP_TRY(hipMemcpyAsync(out, s->glog_buf, (size_t)n * s->glog.cells() * s->glog.stride() * sizeof(double),
+                               hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    s->glog.taken();
+    *nrecords = n;
+    return PCL_OK;
+}
+
+int pcl_gauge_log_stats(pcl_solver *s, long *recorded, long *popped, long *reads) {
+    if (s) s->qt.invalidate();            // quiet tiles: not a read-only call (quiet_tiles.hpp)
+    if (!s || !recorded || !popped || !reads) return fail(PCL_EINVAL, "null argument");
+    s->glog.stats(recorded, popped, reads);
+    return PCL_OK;
+}
+
 static int bc_launch(pcl_solver *s, int idim, int side, int type, const double *cstate, bool aux = false,
                      hipStream_t on = nullptr) {
     const hipStream_t stream = on ? on : s->stream;
@@ -1135,9 +1255,10 @@ int pcl_step_hyperbolic(pcl_solver *s, double dt, double *cfl) {
     if (s) s->plan.touched();             // exchange-ahead: whatever filled the ghost frames no longer holds
     if (!s || !cfl) return fail(PCL_EINVAL, "null argument");
     const bool carry = s->qt.take_valid();
+    if (int rc = gauge_log_ready(s)) return rc;
     ahead_drop(s);
     s->ahead.forget_report();
-    return step_hyperbolic(s, dt, cfl, carry, false);
+    return gauge_recorded(s, step_hyperbolic(s, dt, cfl, carry, false));
 }
 
 static int check_bc_spec(pcl_solver *s, const int *bc, const double *cstate, bool unsplit_only = false) {
@@ -1359,6 +1480,8 @@ static int ahead_adopt(pcl_solver *s, double *cfl) {
     s->qt.adopted(true);            // (StepAhead::matches: the flag was taken as true)
     commit_step(s, s->t2);
     s->form.adopted(fused_step_mode());
+    // (the gauge record in front of the poll: the device copies the cells while the host waits and turns round)
+    if (int rc = gauge_record(s)) return rc;
     if (int rc = read_cfl_begin(s)) return rc;
     return cfl_poll(s, s->ahead.pending_seq(), cfl);
 }
@@ -1371,6 +1494,7 @@ int pcl_bc_step(pcl_solver *s, const int *bc, const double *cstate, double dt, d
     if (s->cfg.kind != PCL_KIND_CLASSIC) return fail(PCL_ESTATE, "classic call on a SharpClaw solver");
     HIP_TRY(hipSetDevice(s->cfg.device));
     if (int rc = check_bc_spec(s, bc, cstate, true)) return rc;
+    if (int rc = gauge_log_ready(s)) return rc;
     const pcl::BcSpec spec(bc, cstate, 2 * s->cfg.ndim);
     if (s->ahead.is_pending()) {
         if (s->ahead.matches(spec, dt, carry)) {
@@ -1403,13 +1527,14 @@ int pcl_bc_step(pcl_solver *s, const int *bc, const double *cstate, double dt, d
         if (!s->halo.has(pcl::W)) box[2] = 0;
         if (!s->halo.has(pcl::E)) box[3] = in.ntiles[1];
     }
-    if (s->cfg.ndim == 2 && s->cfg.method[2] >= 0 && s->sel == 0) return step_unsplit2(s, bc, cstate, dt, cfl);
-    if (overlapped) return step_overlapped(s, bc, cstate, dt, cfl, plan, box);
+    // (every plan: the gauge record of the new state behind the step, gauge_record)
+    if (s->cfg.ndim == 2 && s->cfg.method[2] >= 0 && s->sel == 0) return gauge_recorded(s, step_unsplit2(s, bc, cstate, dt, cfl));
+    if (overlapped) return gauge_recorded(s, step_overlapped(s, bc, cstate, dt, cfl, plan, box));
     if (fused) {
-        if (int rc = step_loading_bcs(s, bc, cstate, dt, cfl, carry)) return rc;
+        if (int rc = gauge_recorded(s, step_loading_bcs(s, bc, cstate, dt, cfl, carry))) return rc;
         return ahead_enqueue(s, spec, dt, *cfl);
     }
-    return step_ghost_fills(s, bc, cstate, dt, cfl);
+    return gauge_recorded(s, step_ghost_fills(s, bc, cstate, dt, cfl));
 }
 
 int pcl_undo_step(pcl_solver *s) {
@@ -1419,6 +1544,7 @@ int pcl_undo_step(pcl_solver *s) {
     if (!s->undo_slot) return fail(PCL_ESTATE, "no step to undo");
     std::swap(s->q, *s->undo_slot);
     s->undo_slot = nullptr;
+    s->glog.pop();                        // gauge log: the undone step's record goes with it
     return PCL_OK;
 }
 
@@ -1445,6 +1571,7 @@ int pcl_restore(pcl_solver *s) {
     HIP_TRY(hipMemcpyAsync(s->q, s->bak, (size_t)s->total * sizeof(double), hipMemcpyDeviceToDevice,
                            s->stream));
     s->undo_slot = nullptr;
+    s->glog.pop();                        // gauge log: a rejected step's record goes with it
     return PCL_OK;
 }
 
@@ -2505,6 +2632,12 @@ int pcl_step_ahead_trace(int on, double cfl_desired, double cfl_max, double dt_m
         else return fail(PCL_EINVAL, "bad event");
     }
     return PCL_OK;
+}
+
+int pcl_gauge_log_trace(long n, const int *event, const int *a, int *out) {
+    if (n < 0 || !event || !a || !out) return fail(PCL_EINVAL, "bad argument");
+    const char *bad = pcl::gauge_log_trace(n, event, a, out);
+    return bad ? fail(PCL_EINVAL, bad) : PCL_OK;
 }
 
 int pcl_halo_plan_trace(long n, const int *event, const int *a, const int *b, int *out) {

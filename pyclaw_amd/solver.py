@@ -226,7 +226,9 @@ class Solver(object):
 
     _required_attrs = ['dt_initial', 'dt_max', 'cfl_max', 'cfl_desired', 'max_steps', 'dt_variable',
                        'mbc']
-    _default_attr_values = {'dt_initial': 0.1, 'dt_max': 1e99, 'max_steps': 1000, 'dt_variable': True}
+    # gauge_log / gauge_log_capacity: the device gauge log of evolve_to_time(tend), see write_gauge_values
+    _default_attr_values = {'dt_initial': 0.1, 'dt_max': 1e99, 'max_steps': 1000, 'dt_variable': True,
+                            'gauge_log': True, 'gauge_log_capacity': 1024}
 
     def __init__(self, data=None):
         self.logger = logging.getLogger('evolve')
@@ -260,6 +262,12 @@ class Solver(object):
         self._host_stale = False
         self._aux_host_stale = False  # a start_step cell function wrote aux on the device since the last download
         self._state = None
+        # device gauge log: what the handle's log was armed with (gauge cells, capacity), whether write_gauge_values
+        # is on the logged path, and the times of the records the device holds
+        self._glog_key = None
+        self._glog_on = False
+        self._glog_times = []
+        self._glog_call = None       # (solution, tend is not None) of the evolve_to_time call in progress
 
     # ------------------------------------------------------------------ validation
     def is_valid(self):
@@ -286,12 +294,14 @@ class Solver(object):
             if _lib.lib().pcl_step_form_stats(self._h, ctypes.byref(ms), ctypes.byref(n), ctypes.byref(s1),
                                               ctypes.byref(s0)) == 0:
                 self.status["step_forms"] = {"one_kernel": int(s1.value), "two_pass": int(s0.value)}
+        self._gauge_log_disarm()
         self._release()
 
     def _release(self):
         if self._h is not None:
-            _lib.lib().pcl_destroy(self._h)
-            self._h = None
+            _lib.lib().pcl_destroy(self._h)      # (frees an armed gauge log with the rest: no library call of its own here,
+            self._h = None                       # this also runs from __del__)
+        self._glog_key, self._glog_on, self._glog_times = None, False, []
         self._step_ahead_sent = None         # (what the handle was last told: pcl_step_ahead)
         self._resident = False
 
@@ -661,7 +671,10 @@ class Solver(object):
         if not self._pinned:
             self._push(state)
         self._arm_step_ahead(state, take_one_step)
+        self._glog_call = (solution, not take_one_step)
+        failed = True                # until the loop has ended without an exception
         try:
+            self._gauge_log_decide()
             for n in range(self.max_steps):
                 state = solution.state
                 if (not take_one_step) and solution.t + self.dt > tend and tstart < tend:
@@ -704,10 +717,20 @@ class Solver(object):
                         self.status['dtmax'] = max(self.dt, self.status['dtmax'])
                     else:
                         self.dt = self.dt_max
+            failed = False
         finally:
-            if not self._pinned:
-                self._pull(solution.state)
-                self._resident = False
+            # the gauge files are complete whenever evolve_to_time has returned.  (Behind an exception of the loop the
+            # device may hold the record of a step that was never accepted: what was accepted is written, and one record
+            # more is not an error of its own.)
+            try:
+                if self._glog_key is not None:
+                    self._gauge_log_flush(strict=not failed)
+            finally:
+                self._glog_on = False
+                self._glog_call = None
+                if not self._pinned:
+                    self._pull(solution.state)
+                    self._resident = False
 
         if self.dt_variable and (not take_one_step) and solution.t < tend \
                 and self.status['numsteps'] == self.max_steps:
@@ -744,12 +767,89 @@ class Solver(object):
         self._host_stale = True
 
     # ------------------------------------------------------------------ gauges
+    def _gauge_log_eligible(self):
+        """Whether the steps of this solver can record their gauge cells themselves (ClawSolver decides)."""
+        return False
+
+    def _gauge_log_decide(self):
+        """Put write_gauge_values on the logged or on the direct path.  At the entry of evolve_to_time, and again by
+        ClawSolver.step when it has decided the source fusion afresh.  Before any switch the records held are written, so
+        the lines of a file stay in the order of the steps."""
+        solution, has_tend = self._glog_call if self._glog_call is not None else (None, False)
+        gauges = solution.state.grid.gauges if solution is not None else []
+        if not gauges and self._glog_key is None:        # (the common case, every call of a run without gauges)
+            self._glog_on = False
+            return
+        import os
+        on = bool(has_tend and gauges and self.gauge_log and os.environ.get("PCL_GAUGE_LOG", "1") != "0"
+                  and self._h is not None and self._resident and self._gauge_log_eligible()
+                  and hasattr(_lib.lib(), "pcl_gauge_log"))        # (an older build of the library, PCL_LIB_OVERRIDE)
+        if not on:
+            if self._glog_key is not None:
+                self._gauge_log_flush()
+                self._gauge_log_disarm()      # the direct path: the steps stop recording
+            self._glog_on = False
+            return
+        capacity = max(1, int(self.gauge_log_capacity))
+        key = (tuple(tuple(int(i) for i in g) for g in gauges), capacity)
+        if key != self._glog_key:
+            self._gauge_log_flush()
+            ij = np.zeros((len(gauges), 3 if self.ndim > 2 else 2), dtype=np.int32)      # (i, j) pairs; (i, j, k) in 3-D
+            for c, g in enumerate(gauges):
+                ij[c, :len(g)] = g
+            self._glog_key = None            # (a failed arming has freed the log that was there)
+            _lib.check(_lib.lib().pcl_gauge_log(self._h, len(gauges), _lib.i(ij), capacity))
+            self._glog_key = key
+        self._glog_on = True
+
+    def _gauge_log_disarm(self):
+        if self._glog_key is not None and self._h is not None:
+            _lib.check(_lib.lib().pcl_gauge_log(self._h, 0, None, 0))
+        self._glog_key = None
+        self._glog_on = False
+        self._glog_times = []
+
+    def _gauge_log_flush(self, strict=True):
+        """Read the records the device holds -- one per accepted step since the last flush -- and write their lines."""
+        import ctypes
+        times = self._glog_times
+        if self._glog_key is None or self._h is None or self._glog_call is None:
+            return
+        solution = self._glog_call[0]
+        state, grid = solution.state, solution.state.grid
+        ncell, capacity = len(self._glog_key[0]), self._glog_key[1]
+        per = state.meqn + state.maux
+        nmax = min(capacity, len(times) + 1)         # (room for one record too many: reported below, not by the library)
+        out = np.empty((nmax, ncell, per))
+        nrec = ctypes.c_int(0)
+        _lib.check(_lib.lib().pcl_gauge_log_read(self._h, nmax, _lib.d(out), ctypes.byref(nrec)))
+        self._glog_times = []
+        if nrec.value != len(times) and (strict or nrec.value < len(times)):
+            raise Exception("gauge log: the device holds %d records for %d accepted steps" % (nrec.value, len(times)))
+        compute = self.compute_gauge_values or default_compute_gauge_values
+        for r, t in enumerate(times):
+            for i in range(ncell):
+                p = compute(out[r, i, :state.meqn], out[r, i, state.meqn:])
+                grid.gauge_files[i].write(str(t) + ' ' + ' '.join(str(j) for j in p) + '\n')
+
     def write_gauge_values(self, solution):
         r"""solver.py:731-741.  While the state is resident the gauge cells are gathered on the device
-        (pcl_get_cells: ngauges*(meqn+maux) doubles over PCIe) instead of pulling the whole q."""
+        (pcl_get_cells: ngauges*(meqn+maux) doubles over PCIe) instead of pulling the whole q.
+
+        Inside ``evolve_to_time(tend)`` of a classic solver whose steps end with the hyperbolic step (no source, or the
+        fused one) nothing is gathered here at all: every step has recorded its gauge cells into a log on the device
+        (``pcl_gauge_log``), this method notes the time, and the lines are written when the log is read -- at
+        ``gauge_log_capacity`` records, and before ``evolve_to_time`` returns.  Same lines, same bytes;
+        ``compute_gauge_values(q, aux)`` is called then, not after each step, so it must be a function of its arguments
+        alone.  ``solver.gauge_log = False`` (or PCL_GAUGE_LOG=0) keeps the gather after every step."""
         grid = solution.state.grid
         gauges = grid.gauges
         if not gauges:
+            return
+        if self._glog_on:
+            self._glog_times.append(solution.t)
+            if len(self._glog_times) >= self._glog_key[1]:
+                self._gauge_log_flush()
             return
         state = solution.state
         compute = self.compute_gauge_values or default_compute_gauge_values
