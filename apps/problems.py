@@ -123,6 +123,55 @@ dq[4] = 0;
 """
 
 
+# Normal Riemann solvers as bodies for pyclaw.CellRiemann: ql, qr, p[8] and the constant ixy in; wave, s, amdq, apdq out
+# (zero on entry).  The first four restate built-in solvers expression by expression (pyclaw_amd/csrc/rp.hpp), so that
+# the 'exact' arithmetic gives the bits of the built-in path; their p[] is the built-in solver's cparam.
+ACOUSTICS_1D_RP = """
+const double cc = p[2], zz = p[3];
+const double d1 = qr[0] - ql[0];
+const double d2 = qr[1] - ql[1];
+const double a1 = (-d1 + zz * d2) / (2.0 * zz);
+const double a2 = (d1 + zz * d2) / (2.0 * zz);
+wave[0][0] = -a1 * zz; wave[0][1] = a1; s[0] = -cc;
+wave[1][0] = a2 * zz;  wave[1][1] = a2; s[1] = cc;
+for (int m = 0; m < 2; m++) { amdq[m] = s[0] * wave[0][m]; apdq[m] = s[1] * wave[1][m]; }
+"""
+
+# Burgers' equation with the transonic entropy fix
+BURGERS_1D_RP = """
+wave[0][0] = qr[0] - ql[0];
+s[0] = 0.5 * (ql[0] + qr[0]);
+const bool transonic = qr[0] > 0.0 && ql[0] < 0.0;
+amdq[0] = transonic ? -0.5 * (ql[0] * ql[0]) : dmin(s[0], 0.0) * wave[0][0];
+apdq[0] = transonic ? 0.5 * (qr[0] * qr[0]) : dmax(s[0], 0.0) * wave[0][0];
+"""
+
+# p = u, v
+ADVECTION_2D_RP = """
+const double vel = p[ixy - 1];
+wave[0][0] = qr[0] - ql[0];
+s[0] = vel;
+amdq[0] = dmin(vel, 0.0) * wave[0][0];
+apdq[0] = dmax(vel, 0.0) * wave[0][0];
+"""
+
+# q = (p, u, v); p = rho, bulk, cc, zz.  The transverse velocity's wave components stay the zeros they are on entry.
+ACOUSTICS_2D_RP = """
+constexpr int mu = (ixy == 1) ? 1 : 2;
+const double cc = p[2], zz = p[3];
+const double d1 = qr[0] - ql[0];
+const double d2 = qr[mu] - ql[mu];
+const double a1 = (-d1 + zz * d2) / (2.0 * zz);
+const double a2 = (d1 + zz * d2) / (2.0 * zz);
+wave[0][0] = -a1 * zz; wave[0][mu] = a1; s[0] = -cc;
+wave[1][0] = a2 * zz;  wave[1][mu] = a2; s[1] = cc;
+for (int m = 0; m < 3; m++) { amdq[m] = s[0] * wave[0][m]; apdq[m] = s[1] * wave[1][m]; }
+"""
+
+# A system the library does not have: scalar 2-D Burgers, q_t + (q^2/2)_x + (q^2/2)_y = 0 -- the 1-D body either way
+BURGERS_2D_RP = BURGERS_1D_RP
+
+
 def shockbubble(pyclaw, mx=160, my=40, tfinal=0.2, device_callbacks=False, with_src=True,
                 dim_split=True, order_trans=2, dt_initial=0.005, nout=1, run=True, math='exact',
                 solver_type='classic', time_integrator='SSP104'):

@@ -69,6 +69,9 @@ extern "C" {
                                    /* (read by rpt2 only); classic and SharpClaw (weno_order 5: mbc 3), fwave = 1 for both      */
 #define PCL_RP_VC_ACOUSTICS_3D 20 /* rpn3_vc_acoustics.f (test/acoustics/3d/Makefile); aux(1)=Z, aux(2)=c; dim-split, and unsplit  */
                                   /* (rpt3/rptt3_vc_acoustics.f) without a capacity function                                   */
+#define PCL_RP_CELL 100 /* a user-written normal Riemann solver compiled at run time (pcl_cellrp_compile / _attach below):  */
+                        /* meqn, mwaves <= 8 from the config, rp_params = the body's p[8]; classic 1-D and dimension-split  */
+                        /* 2-D steps in wave form, no capacity function.  Not a built-in solver: pcl_rp_info refuses the id */
 
 /* boundary condition types = pyclaw.BC (src/pyclaw/solver.py:17-23) */
 #define PCL_BC_CUSTOM 0
@@ -368,6 +371,33 @@ int pcl_cellfn_apply(pcl_solver *s, pcl_cellfn *f, double t, double dt, const do
  * dimension lower and upper, only on blocks that own that boundary.  The argument checks are host-only and come first;
  * otherwise the bookkeeping of pcl_bc_const. */
 int pcl_cellbc_apply(pcl_solver *s, pcl_cellfn *f, int idim, int side, double t, const double *params, int nparams);
+
+/* ---- user-written Riemann solvers (cfg.rp = PCL_RP_CELL) ---------------------------------------------------------
+ * The normal Riemann solver of one interface (Clawpack's rp1 / rpn2) as the text of a C++ function body.  The library
+ * wraps it in a solver struct and compiles its own sweep kernel (the text of csrc/classic.hpp, with the flags of the
+ * arithmetic mode `math`) with it at run time: the classic 1-D step and the x and y passes of the dimension-split 2-D
+ * step then run the user's solver with the tiles, limiter, jump-free shortcut and Courant reduction of the built-in
+ * solvers.  The body sees
+ *     ql[MEQN], qr[MEQN]   the cells left and right of the interface (const)     p[8]   cfg.rp_params / pcl_cellrp_params
+ *     ixy                  compile-time constant: 1 = x (always in 1-D), 2 = y
+ *     wave[MWAVES][MEQN], s[MWAVES], amdq[MEQN], apdq[MEQN]   the results, zero on entry
+ * the helpers of csrc/rp.hpp (dmax, dmin, dsqrt, fdiv, Recip) and whatever `preamble` declares.  For bitwise-equal ql
+ * and qr the waves and fluctuations must be zero (any consistent solver): a wavefront without a jump takes the speeds
+ * alone.  Diagnostics carry the body's line numbers ("riemann:3:...", "preamble:1:...").
+ * Compile is host-only and shares the per-process cache and counters of the cell functions (pcl_cellfn_stats); the key
+ * is (body, preamble, meqn, mwaves, ndim, math).  1 <= meqn, mwaves <= 8, ndim 1 or 2. */
+typedef struct pcl_cellrp pcl_cellrp;
+int pcl_cellrp_compile(const char *body, const char *preamble, int meqn, int mwaves, int ndim, int math, pcl_cellrp **out,
+                       long *code_size);
+int pcl_cellrp_release(pcl_cellrp *r);
+/* Host-only: the handle is live and was compiled for these constants (what pcl_cellrp_attach asks of it). */
+int pcl_cellrp_check(const pcl_cellrp *r, int meqn, int mwaves, int ndim, int math);
+/* Gives a PCL_RP_CELL solver its Riemann solver: the module is loaded into the handle's device (one attached at a time;
+ * pcl_destroy unloads it).  Until then every step of such a solver is refused with PCL_ESTATE. */
+int pcl_cellrp_attach(pcl_solver *s, pcl_cellrp *r);
+/* The body's p[0..nparams-1] from the next sweep on (nparams <= 8; the rest are zero): they travel by value with every
+ * launch, so changing them compiles nothing. */
+int pcl_cellrp_params(pcl_solver *s, const double *params, int nparams);
 
 /* ---- SharpClaw (kind = PCL_KIND_SHARPCLAW) ----------------------------------------------------- */
 /* Which register the put/get/bc/strip/halo calls act on (default PCL_REG_Q): the RK stages get

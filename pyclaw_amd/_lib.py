@@ -100,6 +100,12 @@ PROTOTYPES = {
     "pcl_cellfn_geometry": (C.c_int, [C.c_void_p, dp, ip]),
     "pcl_cellfn_apply": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_double, dp, C.c_int]),
     "pcl_cellbc_apply": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, dp, C.c_int]),
+    "pcl_cellrp_compile": (C.c_int, [C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p),
+                                     C.POINTER(C.c_long)]),
+    "pcl_cellrp_release": (C.c_int, [C.c_void_p]),
+    "pcl_cellrp_check": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "pcl_cellrp_attach": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "pcl_cellrp_params": (C.c_int, [C.c_void_p, dp, C.c_int]),
     "pcl_select": (C.c_int, [C.c_void_p, C.c_int]),
     "pcl_sharp_fuse_dq_src": (C.c_int, [C.c_void_p, C.c_int, dp, C.c_int]),
     "pcl_sharp_dq": (C.c_int, [C.c_void_p, C.c_double, dp]),

@@ -90,6 +90,8 @@ class ClawSolver(Solver):
         self._src_fused = False
         self._fuse_key = None
         self._rp_id = None
+        self._user_rp = None         # the riemann.CellRiemann of this setup() and the params the library last got
+        self._user_rp_sent = None
         self._cfl_out = None
         self._cfl_ptr = None
         super(ClawSolver, self).__init__(data)
@@ -175,6 +177,8 @@ class ClawSolver(Solver):
         if cfl is None:            # one c_double + its pointer for the solver's lifetime
             cfl = self._cfl_out = ctypes.c_double(0.0)
             self._cfl_ptr = ctypes.cast(ctypes.byref(cfl), _lib.dp)
+        if self._user_rp is not None:
+            self._send_user_rp_params()
         spec = self._device_bc_spec(state)
         if spec is not None:
             # every ghost fill runs on the device: BCs + step in one library call
@@ -227,6 +231,9 @@ class ClawSolver(Solver):
         self.set_method(state)
 
         rp = riemann.get(self.rp) if self.rp is not None else self._default_rp(state)
+        user_rp = isinstance(rp, riemann.CellRiemann)
+        if user_rp:
+            self._check_user_rp(state)
         if rp.ndim != self.ndim:
             raise Exception("Riemann solver %s is %d-D but the solver is %d-D" % (rp.name, rp.ndim, self.ndim))
         if rp.mwaves != self.mwaves:
@@ -234,6 +241,8 @@ class ClawSolver(Solver):
         if rp.meqn != state.meqn:
             raise Exception("state.meqn=%d but Riemann solver %s has %d equations" % (state.meqn, rp.name, rp.meqn))
         params = rp.all_params(state)                 # the cparam common block (state.py:142-162)
+        if user_rp:
+            rp.compile(self.math)                  # raises with the compiler's log before any device work
 
         self._release()
         cfg = _lib.Config()
@@ -263,6 +272,9 @@ class ClawSolver(Solver):
         h = ctypes.c_void_p()
         _lib.check(_lib.lib().pcl_create(ctypes.byref(cfg), ctypes.byref(h)))
         self._h = h
+        self._user_rp, self._user_rp_sent = (rp, np.array(params)) if user_rp else (None, None)
+        if user_rp:
+            _lib.check(_lib.lib().pcl_cellrp_attach(self._h, rp._rp))
 
         self.allocate_bc_arrays(state)
         self._setup_halo(state)
@@ -272,6 +284,32 @@ class ClawSolver(Solver):
         self._src_fused = False          # a fresh device handle
         self._decide_src_fusion(state)
         self._decide_exchange_ahead(state)
+
+    def _check_user_rp(self, state):
+        """What a user-written Riemann solver (riemann.CellRiemann) does not serve, each refused with its reason."""
+        from . import parallel
+        if self.ndim == 3:
+            raise NotImplementedError("CellRiemann: the user-written solver is compiled into the 1-D and 2-D sweep kernels; "
+                                      "ClawSolver3D has no sweep for it")
+        if self.ndim == 2 and not self.dim_split:
+            raise NotImplementedError("CellRiemann: dim_split = False needs a transverse Riemann solver (rpt2); the body "
+                                      "is the normal solver only, so the 2-D step is the dimension-split one")
+        if self.fwave:
+            raise NotImplementedError("CellRiemann: fwave = True is not served: the body returns waves, and the f-wave "
+                                      "form of the sweep has no user-written instantiation")
+        if state.mcapa >= 0:
+            raise NotImplementedError("CellRiemann: state.mcapa (a capacity function) is not served: the user-written "
+                                      "solver is compiled into the sweep without one")
+        if state.decomp is not None and parallel.world_size() > 1:
+            raise NotImplementedError("CellRiemann: more than one rank is not served: a user-written solver runs on one "
+                                      "block (the decomposed step's plans know the built-in solvers only)")
+
+    def _send_user_rp_params(self):
+        """CellRiemann.params reassigned since the last step: they travel by value with the next sweeps, no compile."""
+        p = self._user_rp.params
+        if len(p) != len(self._user_rp_sent) or not np.array_equal(p, self._user_rp_sent):
+            _lib.check(_lib.lib().pcl_cellrp_params(self._h, _lib.d(p) if len(p) else None, len(p)))
+            self._user_rp_sent = p.copy()
 
     def _decide_exchange_ahead(self, state):
         """Decomposed dimension-split 2-D runs: let the library send the new state's halo right behind the y pass

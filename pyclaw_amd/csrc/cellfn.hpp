@@ -265,6 +265,8 @@ struct HiprtcApi {
     decltype(&hiprtcGetCode) hiprtcGetCode = nullptr;
     decltype(&hiprtcDestroyProgram) hiprtcDestroyProgram = nullptr;
     decltype(&hiprtcGetErrorString) hiprtcGetErrorString = nullptr;
+    decltype(&hiprtcAddNameExpression) hiprtcAddNameExpression = nullptr;      // cellrp.hpp: the symbols of template kernels
+    decltype(&hiprtcGetLoweredName) hiprtcGetLoweredName = nullptr;
 };
 static inline HiprtcApi &hiprtc_api() {
     static HiprtcApi a;
@@ -302,7 +304,7 @@ static inline int hiprtc_load(std::string &err) {
     if (!a.name) { err = "libhiprtc lacks " #name; return -1; }
     PCL_SYM(hiprtcCreateProgram) PCL_SYM(hiprtcCompileProgram) PCL_SYM(hiprtcGetProgramLogSize)
     PCL_SYM(hiprtcGetProgramLog) PCL_SYM(hiprtcGetCodeSize) PCL_SYM(hiprtcGetCode) PCL_SYM(hiprtcDestroyProgram)
-    PCL_SYM(hiprtcGetErrorString)
+    PCL_SYM(hiprtcGetErrorString) PCL_SYM(hiprtcAddNameExpression) PCL_SYM(hiprtcGetLoweredName)
 #undef PCL_SYM
     a.ok = true;
     return 0;
@@ -319,6 +321,8 @@ struct pcl_cellfn {
     std::vector<char> code;     // the code object
 };
 
+struct pcl_cellrp;      // a compiled Riemann solver (cellrp.hpp): same cache, same counters
+
 namespace pcl {
 
 // No destructor work that touches HIP: the cache holds host memory only (the modules loaded from it belong to the
@@ -327,6 +331,8 @@ struct CellfnCache {
     std::mutex mu;
     std::map<std::string, pcl_cellfn *> by_key;
     std::map<const pcl_cellfn *, long> live;
+    std::map<std::string, pcl_cellrp *> rp_by_key;
+    std::map<const pcl_cellrp *, long> rp_live;
     long next_id = 1, compiles = 0, hits = 0;
 };
 static inline CellfnCache &cellfn_cache() {

@@ -18,8 +18,10 @@
 // Contents: lane_core | sweep_kernel (step2ds / step1) | unsplit_x/y_kernel (step2, step2qcor) |
 // sweep3_kernel (step3ds); the unsplit 3-D step is classic3.hpp.
 #pragma once
+#ifndef __HIPCC_RTC__       // (the run-time compile of cellrp.hpp reads this header as text: hiprtc has neither)
 #include <hip/hip_runtime.h>
 #include <type_traits>
+#endif
 
 #include "ghost_rule.hpp"
 
@@ -111,10 +113,13 @@ template <class RP> __host__ __device__ constexpr bool aux_plane_used_y(int p) {
     }
     return u;
 }
-template <class RP, class = void> struct IsFwave : std::false_type {};
-template <class RP> struct IsFwave<RP, std::void_t<decltype(RP::IS_FWAVE)>> : std::bool_constant<RP::IS_FWAVE> {};
-template <class RP, class = void> struct HasQcor : std::false_type {};
-template <class RP> struct HasQcor<RP, std::void_t<decltype(RP::HAS_QCOR)>> : std::bool_constant<RP::HAS_QCOR> {};
+// (own constants instead of <type_traits>: hiprtc compiles this header without the standard library)
+template <bool B> struct BoolConst { static constexpr bool value = B; };
+template <class...> using VoidOf = void;
+template <class RP, class = void> struct IsFwave : BoolConst<false> {};
+template <class RP> struct IsFwave<RP, VoidOf<decltype(RP::IS_FWAVE)>> : BoolConst<RP::IS_FWAVE> {};
+template <class RP, class = void> struct HasQcor : BoolConst<false> {};
+template <class RP> struct HasQcor<RP, VoidOf<decltype(RP::HAS_QCOR)>> : BoolConst<RP::HAS_QCOR> {};
 template <class RP> __host__ __device__ constexpr bool has_qcor() { return HasQcor<RP>::value; }
 
 // philim.f:19-55

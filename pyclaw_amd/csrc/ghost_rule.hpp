@@ -2,7 +2,9 @@
 // The sweep kernels evaluate it while they load their tiles (classic.hpp, classic_fused.hpp), the ghost-fill and frame
 // kernels of pclaw.hip apply it in memory, and pcl_ghost_map answers it on the host (tests/test_ghost_rule_cpu.py).
 #pragma once
+#ifndef __HIPCC_RTC__
 #include <hip/hip_runtime.h>
+#endif
 
 #include "../../include/pyclaw_amd.h"
 

@@ -49,25 +49,52 @@ using Solvers = RpList<Advection1D, Acoustics1D, Burgers1D, Euler1D, Shallow1D, 
                        Euler5, Advection2D, Shallow2D, VcAcoustics2D, VcAdvection2D, ShallowSphere, PSystem2D, VcAcoustics3D>;
 int not_built(std::string &err, const char *why) { err = why; return PCL_EINVAL; }
 
-template <class RP, int IXY, bool DIM1> int launch(const SweepLaunch &l, std::string &err) {
+// The grid of sweep_kernel<., IXY, ., ., DIM1> over l.a: the same for every solver, built in or compiled at run time
+// (nblocks == 0: the tile subset is empty, nothing to launch).
+struct SweepGrid { unsigned nblocks; int ntiles_across, ntiles_along; };
+template <int IXY, bool DIM1> int sweep_grid(const SweepArgs &a, SweepGrid &g, std::string &err) {
     using T = TileShape<IXY>;
-    const SweepArgs &a = l.a;
     const int n_across = IXY == 1 ? a.J : a.I + (LINE - a.mbc);  // y: columns counted from the line boundary
     const int m_along = IXY == 1 ? a.mx : a.my;
-    const int ntiles_across = (n_across + T::ACROSS - 1) / T::ACROSS;
-    const int ntiles_along = (m_along + T::NSTRIP * STRIP - 1) / (T::NSTRIP * STRIP);
-    unsigned nblocks = (unsigned)ntiles_across * (unsigned)ntiles_along;
+    g.ntiles_across = (n_across + T::ACROSS - 1) / T::ACROSS;
+    g.ntiles_along = (m_along + T::NSTRIP * STRIP - 1) / (T::NSTRIP * STRIP);
+    g.nblocks = (unsigned)g.ntiles_across * (unsigned)g.ntiles_along;
     if (a.sub != 0) {
-        if (IXY != 1 || DIM1 || a.box[0] < 0 || a.box[1] > ntiles_across || a.box[2] < 0 ||
-            a.box[3] > ntiles_along || a.box[0] >= a.box[1] || a.box[2] >= a.box[3]) {
+        if (IXY != 1 || DIM1 || a.box[0] < 0 || a.box[1] > g.ntiles_across || a.box[2] < 0 ||
+            a.box[3] > g.ntiles_along || a.box[0] >= a.box[1] || a.box[2] >= a.box[3]) {
             err = "tile subset: bad box";
             return PCL_EINVAL;
         }
         const unsigned inside = (unsigned)(a.box[1] - a.box[0]) * (unsigned)(a.box[3] - a.box[2]);
-        nblocks = a.sub == 1 ? inside : nblocks - inside;
-        if (nblocks == 0) return PCL_OK;
+        g.nblocks = a.sub == 1 ? inside : g.nblocks - inside;
     }
-    const dim3 grid(nblocks);
+    return PCL_OK;
+}
+
+// A user-written Riemann solver (cellrp.hpp): l.user_fn is sweep_kernel<UserRp, IXY, false, false, DIM1> of a module
+// compiled at run time from the text of classic.hpp, so the kernel's parameters are those of the launches below.
+template <int IXY, bool DIM1> int launch_user(const SweepLaunch &l, std::string &err) {
+    if (!l.user_fn) { err = "user-written Riemann solver: no compiled solver is attached (pcl_cellrp_attach)"; return PCL_ESTATE; }
+    if (l.fwave || l.a.mcapa > 0 || l.a.src_id != 0) {
+        err = "user-written Riemann solver: wave form only, no capacity function, no fused source";
+        return PCL_EINVAL;
+    }
+    SweepGrid g;
+    if (int rc = sweep_grid<IXY, DIM1>(l.a, g, err)) return rc;
+    if (g.nblocks == 0) return PCL_OK;
+    SweepArgs a = l.a;
+    void *params[] = {&a, &g.ntiles_across, &g.ntiles_along};
+    hipError_t e = hipModuleLaunchKernel(l.user_fn, g.nblocks, 1, 1, 256, 1, 1, 0, l.stream, params, nullptr);
+    return e == hipSuccess ? PCL_OK : hip_fail(err, "sweep launch (user-written Riemann solver)", e);
+}
+
+template <class RP, int IXY, bool DIM1> int launch(const SweepLaunch &l, std::string &err) {
+    const SweepArgs &a = l.a;
+    SweepGrid g;
+    if (int rc = sweep_grid<IXY, DIM1>(a, g, err)) return rc;
+    if (g.nblocks == 0) return PCL_OK;
+    const int ntiles_across = g.ntiles_across, ntiles_along = g.ntiles_along;
+    const dim3 grid(g.nblocks);
     constexpr bool FW = IsFwave<RP>::value;       // f-wave solvers run the flux2fw.f / step1fw.f form of the kernel
     if ((l.fwave != 0) != FW) {
         err = FW ? "this Riemann solver returns f-waves: set solver.fwave = True (classic1fw / classic2fw)"
@@ -100,6 +127,8 @@ template <class RP, int IXY, bool DIM1> int launch(const SweepLaunch &l, std::st
 
 // one directional sweep qin -> qout; ids 1 = x (or the 1-D step), 2 = y
 int launch_sweep(const SweepLaunch &l, std::string &err) {
+    if (l.rp == PCL_RP_CELL)
+        return l.ndim == 1 ? launch_user<1, true>(l, err) : l.ids == 1 ? launch_user<1, false>(l, err) : launch_user<2, false>(l, err);
     const int rc = Solvers::with(l.rp, [&](auto tag) {
         using RP = typename decltype(tag)::type;
         if constexpr (RP::NDIM == 1) return l.ndim == 1 ? launch<RP, 1, true>(l, err) : RP_NONE;

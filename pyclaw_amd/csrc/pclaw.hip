@@ -22,6 +22,7 @@
 #include "halo_plan.hpp"
 #include "gauge_log.hpp"
 #include "cellfn.hpp"
+#include "cellrp.hpp"
 
 namespace {
 
@@ -94,6 +95,8 @@ struct pcl_solver {
     pcl::CellfnModules cellfn;
     double cf_lower[3] = {0.0, 0.0, 0.0};
     int cf_nstart[3] = {0, 0, 0};
+    // cfg.rp == PCL_RP_CELL: the user-written Riemann solver's module (cellrp.hpp, pcl_cellrp_attach)
+    pcl::CellrpModule cellrp;
 };
 
 static inline double *&cur(pcl_solver *s) { return s->sel == 0 ? s->q : s->sreg[s->sel]; }
@@ -372,6 +375,7 @@ SweepLaunch make_launch(const pcl_solver *s, const SweepArgs &a, int ndim, int i
     l.ids = ids;
     l.fwave = s->cfg.fwave;
     l.stream = stream;
+    if (l.rp == PCL_RP_CELL && ndim <= 2) l.user_fn = s->cellrp.fn[ids - 1];     // null: nothing attached, refused by the launcher
     return l;
 }
 
@@ -416,7 +420,12 @@ int fused_step_mode() {
 }
 // What the host layer knows about each built-in Riemann solver (sweep_args.hpp: RpFacts), read off the solver's struct
 // where the kernels are compiled; null for an id no solver has.
-const pcl::RpFacts *solver_facts(int rp) { return pcl::exact::rp_facts(rp); }
+// A user-written solver (PCL_RP_CELL, cellrp.hpp) has the two sweeps and nothing else: a record with everything off, so
+// that the one-kernel step, quiet tiles, step ahead and the overlap plans never choose it.  Its sizes are the config's.
+const pcl::RpFacts *solver_facts(int rp) {
+    static const pcl::RpFacts cell = {PCL_RP_CELL, 0, 0, 0, 0, false, false, false, false, false, false};
+    return rp == PCL_RP_CELL ? &cell : pcl::exact::rp_facts(rp);
+}
 // the one-kernel step stages aux planes next to q: a solver with cell-wise coefficients, or any solver with a capacity function
 bool fused_aux_family(const pcl_solver *s) { return s->cfg.method[5] > 0 || solver_facts(s->cfg.rp)->onek_aux; }
 bool fused_step_ok(const pcl_solver *s) {
@@ -673,14 +682,14 @@ int check_device() {
 extern "C" {
 
 const char *pcl_last_error(void) { return g_err.c_str(); }
-int pcl_version(void) { return 105; }
+int pcl_version(void) { return 106; }
 int pcl_device_count(void) {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess) return 0;
     return n;
 }
 int pcl_rp_info(int rp, int info[10]) {
-    const pcl::RpFacts *f = solver_facts(rp);
+    const pcl::RpFacts *f = rp == PCL_RP_CELL ? nullptr : solver_facts(rp);    // built-in solvers only
     if (!f || !info) return fail(PCL_EINVAL, !info ? "null argument" : "unknown Riemann solver id");
     const int v[10] = {f->ndim, f->meqn, f->mwaves, f->naux, f->fwave, f->onek, f->onek_aux, f->sharp, f->sharp_high, f->sharp_wave};
     std::copy(v, v + 10, info);
@@ -730,7 +739,19 @@ int pcl_create(const pcl_config *cfg, pcl_solver **out) {
         return fail(PCL_EINVAL, "unknown math mode");
     const pcl::RpFacts *facts = solver_facts(cfg->rp);
     if (!facts) return fail(PCL_EINVAL, "unknown Riemann solver id");
-    if (cfg->meqn != facts->meqn || cfg->mwaves != facts->mwaves || cfg->ndim != facts->ndim)
+    if (cfg->rp == PCL_RP_CELL) {
+        // a user-written normal solver (cellrp.hpp): sizes from the config; it serves the classic 1-D step and the two
+        // passes of the dimension-split 2-D step, in wave form, without a capacity function
+        if (cfg->kind != PCL_KIND_CLASSIC)
+            return fail(PCL_EINVAL, "PCL_RP_CELL: a user-written Riemann solver runs in the classic sweeps only, not under SharpClaw");
+        if (cfg->ndim == 3) return fail(PCL_EINVAL, "PCL_RP_CELL: a user-written Riemann solver is 1-D or 2-D (ndim == 3)");
+        if (cfg->fwave) return fail(PCL_EINVAL, "PCL_RP_CELL: a user-written Riemann solver returns waves, not f-waves (cfg.fwave must be 0)");
+        if (cfg->method[5] != 0) return fail(PCL_EINVAL, "PCL_RP_CELL: no capacity function with a user-written Riemann solver (mcapa must be 0)");
+        if (cfg->ndim == 2 && cfg->method[2] >= 0)
+            return fail(PCL_EINVAL, "PCL_RP_CELL: the unsplit step needs a transverse solver; a user-written solver has the "
+                                    "dimension-split step only (method[2] < 0)");
+        if (cfg->meqn < 1 || cfg->meqn > PCL_MAX_WAVES) return fail(PCL_EINVAL, "PCL_RP_CELL: 1 <= meqn <= 8");
+    } else if (cfg->meqn != facts->meqn || cfg->mwaves != facts->mwaves || cfg->ndim != facts->ndim)
         return fail(PCL_EINVAL, "meqn/mwaves/ndim do not match the Riemann solver");
     for (int d = 0; d < cfg->ndim; d++)
         if (cfg->n[d] < 1) return fail(PCL_EINVAL, "grid extent must be >= 1");
@@ -829,6 +850,7 @@ void pcl_destroy(pcl_solver *s) {
     if (s->hstream) hipStreamSynchronize(s->hstream);
     s->halo.destroy();
     s->cellfn.unload_all();     // here, never from a static destructor: the HIP runtime is still alive
+    s->cellrp.unload();
     if (s->ev_h0) hipEventDestroy(s->ev_h0);
     if (s->ev_h1) hipEventDestroy(s->ev_h1);
     if (s->ev_y) hipEventDestroy(s->ev_y);
@@ -1677,6 +1699,111 @@ int pcl_cellfn_check(const pcl_cellfn *f, int meqn, int maux, int ndim) {
     return cellfn_check_locked(c, f, meqn, maux, ndim);
 }
 
+// ---- user-written Riemann solvers (cellrp.hpp) ---------------------------------------------------------------------
+int pcl_cellrp_compile(const char *body, const char *preamble, int meqn, int mwaves, int ndim, int math, pcl_cellrp **out,
+                       long *code_size) {
+    if (!body || !out) return fail(PCL_EINVAL, "null argument");
+    *out = nullptr;
+    if (!preamble) preamble = "";
+    if (meqn < 1 || meqn > PCL_MAX_WAVES || mwaves < 1 || mwaves > PCL_MAX_WAVES)
+        return fail(PCL_EINVAL, "pcl_cellrp_compile: 1 <= meqn <= 8 and 1 <= mwaves <= 8");
+    if (ndim < 1 || ndim > 2) return fail(PCL_EINVAL, "pcl_cellrp_compile: ndim must be 1 or 2 (the classic 1-D and dimension-split 2-D sweeps)");
+    if (math != PCL_MATH_EXACT && math != PCL_MATH_FAST && math != PCL_MATH_STRICT) return fail(PCL_EINVAL, "unknown math mode");
+    CellfnCache &c = cellfn_cache();
+    std::lock_guard<std::mutex> lock(c.mu);
+    const std::string key = cellrp_key(body, preamble, meqn, mwaves, ndim, math);
+    auto it = c.rp_by_key.find(key);
+    pcl_cellrp *r = nullptr;
+    if (it != c.rp_by_key.end()) {
+        r = it->second;
+        c.hits++;
+    } else {
+        std::vector<char> code;
+        std::string err, sym[2];
+        if (cellrp_build(body, preamble, meqn, mwaves, ndim, math, code, sym, err)) return fail(PCL_EINVAL, err);
+        r = new pcl_cellrp();
+        r->id = c.next_id++;
+        r->meqn = meqn; r->mwaves = mwaves; r->ndim = ndim; r->math = math;
+        r->key = key;
+        r->code.swap(code);
+        r->sym[0] = sym[0]; r->sym[1] = sym[1];
+        c.rp_by_key[key] = r;
+        c.rp_live[r] = r->id;
+        c.compiles++;
+    }
+    r->refs++;
+    *out = r;
+    if (code_size) *code_size = (long)r->code.size();
+    return PCL_OK;
+}
+
+int pcl_cellrp_release(pcl_cellrp *r) {
+    if (!r) return PCL_OK;
+    CellfnCache &c = cellfn_cache();
+    std::lock_guard<std::mutex> lock(c.mu);
+    if (!c.rp_live.count(r)) return fail(PCL_EINVAL, "pcl_cellrp_release: not a live Riemann solver handle");
+    if (r->refs <= 0) return fail(PCL_EINVAL, "pcl_cellrp_release: released more often than compiled");
+    r->refs--;      // the entry stays cached, like a cell function's (pcl_cellfn_release)
+    return PCL_OK;
+}
+
+static int cellrp_check_locked(CellfnCache &c, const pcl_cellrp *r, int meqn, int mwaves, int ndim, int math) {
+    if (!r || !c.rp_live.count(r)) return fail(PCL_EINVAL, "not a live Riemann solver handle (pcl_cellrp_compile)");
+    if (r->meqn != meqn || r->mwaves != mwaves || r->ndim != ndim || r->math != math)
+        return fail(PCL_EINVAL, "Riemann solver was compiled for meqn=" + std::to_string(r->meqn) + " mwaves=" + std::to_string(r->mwaves) +
+                                    " ndim=" + std::to_string(r->ndim) + " math=" + std::to_string(r->math) + ", the solver has meqn=" +
+                                    std::to_string(meqn) + " mwaves=" + std::to_string(mwaves) + " ndim=" + std::to_string(ndim) +
+                                    " math=" + std::to_string(math));
+    return PCL_OK;
+}
+
+int pcl_cellrp_check(const pcl_cellrp *r, int meqn, int mwaves, int ndim, int math) {
+    CellfnCache &c = cellfn_cache();
+    std::lock_guard<std::mutex> lock(c.mu);
+    return cellrp_check_locked(c, r, meqn, mwaves, ndim, math);
+}
+
+int pcl_cellrp_attach(pcl_solver *s, pcl_cellrp *r) {
+    if (s) s->qt.invalidate();            // quiet tiles: not a read-only call (quiet_tiles.hpp)
+    if (!s) return fail(PCL_EINVAL, "null argument");
+    if (s->cfg.rp != PCL_RP_CELL) return fail(PCL_EINVAL, "pcl_cellrp_attach: the solver was not created with cfg.rp = PCL_RP_CELL");
+    long id;
+    const void *code;
+    std::string sym[2];
+    {   // (the entry is never freed: code and names stay valid outside the lock)
+        CellfnCache &c = cellfn_cache();
+        std::lock_guard<std::mutex> lock(c.mu);
+        if (int rc = cellrp_check_locked(c, r, s->cfg.meqn, s->cfg.mwaves, s->cfg.ndim, s->cfg.math)) return rc;
+        id = r->id; code = r->code.data(); sym[0] = r->sym[0]; sym[1] = r->sym[1];
+    }
+    if (s->cellrp.id == id) return PCL_OK;
+    HIP_TRY(hipSetDevice(s->cfg.device));
+    HIP_TRY(hipStreamSynchronize(s->stream));       // a sweep of the module attached before may still run
+    s->cellrp.unload();
+    pcl::CellrpModule m;
+    HIP_TRY(hipModuleLoadData(&m.mod, code));
+    for (int k = 0; k < s->cfg.ndim; k++) {
+        hipError_t e = hipModuleGetFunction(&m.fn[k], m.mod, sym[k].c_str());
+        if (e != hipSuccess) {
+            (void)hipModuleUnload(m.mod);
+            return fail(PCL_EHIP, "hipModuleGetFunction(" + sym[k] + "): " + hipGetErrorString(e));
+        }
+    }
+    m.id = id;
+    s->cellrp = m;
+    return PCL_OK;
+}
+
+int pcl_cellrp_params(pcl_solver *s, const double *params, int nparams) {
+    if (s) s->qt.invalidate();            // quiet tiles: not a read-only call (quiet_tiles.hpp)
+    if (nparams < 0 || nparams > PCL_CELLRP_MAX_PARAMS)
+        return fail(PCL_EINVAL, "pcl_cellrp_params: a Riemann solver body takes at most 8 parameters");
+    if (!s || (nparams > 0 && !params)) return fail(PCL_EINVAL, "null argument");
+    if (s->cfg.rp != PCL_RP_CELL) return fail(PCL_EINVAL, "pcl_cellrp_params: the solver was not created with cfg.rp = PCL_RP_CELL");
+    for (int k = 0; k < PCL_MAX_RP_PARAMS; k++) s->cfg.rp_params[k] = k < nparams ? params[k] : 0.0;
+    return PCL_OK;
+}
+
 int pcl_cellfn_geometry(pcl_solver *s, const double *lower, const int *nstart) {
     if (s) s->qt.invalidate();            // quiet tiles: not a read-only call (quiet_tiles.hpp)
     if (!s || !lower || !nstart) return fail(PCL_EINVAL, "null argument");
@@ -2247,6 +2374,9 @@ bool same_shape(const pcl_config &a, const pcl_config &b) {
 // a handle for this configuration: the cached one (its scalars refreshed) or a new one that replaces it
 int g_l1_math = PCL_MATH_EXACT;     // arithmetic mode of the f2py-shaped calls (pcl_layer1_math)
 int layer1_handle(const pcl_config &c, pcl_solver **out) {
+    if (c.rp == PCL_RP_CELL)
+        return fail(PCL_EINVAL, "the stateless calls take a built-in Riemann solver; a user-written one (PCL_RP_CELL) is "
+                                "attached to a solver handle (pcl_cellrp_attach)");
     if (g_l1.s && same_shape(g_l1.s->cfg, c)) {
         g_l1.s->cfg = c;      // method, mthlim, rp_params, d: read at launch time only
         g_l1.s->undo_slot = nullptr;
@@ -2415,7 +2545,7 @@ static int host_sharp(int ndim, int rp, const double *rp_params, int lim_type, i
     c.method[1] = 2; c.method[5] = mcapa; c.method[6] = maux;
     c.kind = PCL_KIND_SHARPCLAW; c.lim_type = lim_type;
     // clawparams.fwave follows the Riemann solver (sharpclaw.py:269): flux1 / flux2 carry no argument for it
-    const pcl::RpFacts *facts = solver_facts(rp);
+    const pcl::RpFacts *facts = solver_facts(rp);      // (PCL_RP_CELL: everything off; pcl_create refuses it for SharpClaw)
     c.fwave = facts && facts->fwave;
     return layer1_run(c, q, aux, dq, L1_SHARP_DQ, 0, dt, cfl);
 }
@@ -2496,6 +2626,7 @@ int pcl_comm_check(int nranks, int rank, const int neighbors[8]) {
 int pcl_comm_init(pcl_solver *s, int nranks, int rank, const char uid[128], const int neighbors[8]) {
     if (s) s->qt.invalidate();            // quiet tiles: not a read-only call (quiet_tiles.hpp)
     if (!s || !uid || !neighbors) return fail(PCL_EINVAL, "null argument");
+    if (s->cfg.rp == PCL_RP_CELL) return fail(PCL_EINVAL, "pcl_comm_init: a user-written Riemann solver (PCL_RP_CELL) runs on one block only");
     // argument validation BEFORE anything reaches RCCL (whose own diagnostics for these mistakes is a bare
     // "invalid usage" from ncclCommInitRank)
     if (int rc = pcl_comm_check(nranks, rank, neighbors)) return rc;
@@ -2519,6 +2650,7 @@ int pcl_comm_init_host(pcl_solver *s, int nranks, int rank, const int neighbors[
                        pcl_host_reduce_fn rfn, void *user) {
     if (s) s->qt.invalidate();            // quiet tiles: not a read-only call (quiet_tiles.hpp)
     if (!s || !neighbors || !xfn || !rfn) return fail(PCL_EINVAL, "null argument");
+    if (s->cfg.rp == PCL_RP_CELL) return fail(PCL_EINVAL, "pcl_comm_init_host: a user-written Riemann solver (PCL_RP_CELL) runs on one block only");
     if (int rc = pcl_comm_check(nranks, rank, neighbors)) return rc;
     HIP_TRY(hipSetDevice(s->cfg.device));
     std::string err;

@@ -16,7 +16,9 @@
 //   template<int IXY> transverse(L, R, par, asdq, bmasdq, bpasdq)   (rpt2)
 //   ID (its PCL_RP_* value), NDIM, and which kernels have an instantiation of it (RpDefaults below)
 #pragma once
+#ifndef __HIPCC_RTC__
 #include <hip/hip_runtime.h>
+#endif
 #include "../../include/pyclaw_amd.h"
 #include "sweep_args.hpp"
 

@@ -1,8 +1,12 @@
 // sweep_args.hpp -- plain launch descriptor shared by the host TU (pclaw.hip) and the two
 // kernel TUs (kernels.hip compiled once per arithmetic mode).
+// The run-time compile of a user-written Riemann solver (cellrp.hpp) reads this text too: what hiprtc cannot take --
+// the standard headers and the host-side launch descriptors -- sits behind __HIPCC_RTC__.
 #pragma once
+#ifndef __HIPCC_RTC__
 #include <hip/hip_runtime.h>
 #include <string>
+#endif
 
 namespace pcl {
 
@@ -116,6 +120,7 @@ struct SweepArgs {
     double src_p[2];
 };
 
+#ifndef __HIPCC_RTC__       // from here on: host-side launch descriptors and the launchers' declarations
 // unsplit 3-D (classic3.hpp): one direction's slices, applied in the reference's order by the marching kernel
 struct Unsplit3Launch {
     SweepArgs a;          // qin = qold; s_al/n_al/m_al, dtd, par, mthlim, order, cfl as for sweep3
@@ -158,6 +163,9 @@ struct SweepLaunch {
     int lim_type;  // SharpClaw reconstruction (2 PyWENO weno5, 3 legacy weno5)
     int char_decomp = 0;   // SharpClaw: 1 = wave-based reconstruction (1-D: tvd2_wave / weno5_wave)
     hipStream_t stream;
+    // rp == PCL_RP_CELL (a user-written Riemann solver, cellrp.hpp): sweep_kernel<UserRp, ids, ...> of the module the
+    // solver handle has loaded; launch_sweep launches it over the grid it computes for the built-in solvers
+    hipFunction_t user_fn = nullptr;
     // one-kernel step only (classic_fused.hpp, quiet tiles): this launch's per-tile words and per-wavefront Courant
     // maxima (tq_out null: no bookkeeping).  A list launch (tq_list set) computes the tq_next->na + nq tiles a
     // hand-over+list kernel listed behind the previous launch and publishes the Courant number of those it skips.
@@ -245,5 +253,6 @@ int launch_unsplit(const SweepLaunch &l, const double *qx, std::string &err);
 int launch_sharp(const SweepLaunch &l, std::string &err);
 int launch_rk(const RkLaunch &r, hipStream_t stream, std::string &err);
 }
+#endif  // !__HIPCC_RTC__
 
 }  // namespace pcl

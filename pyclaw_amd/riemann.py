@@ -6,7 +6,9 @@ The reference picks the Riemann solver when the app's f2py module is linked
 ``cparam`` common block filled from ``state.aux_global`` (src/pyclaw/state.py:142-162).
 Here a solver is named on the Solver object (``solver.rp = riemann.rp_euler_5wave_2d`` or
 the string ``'euler_5wave_2d'``); ``cparam`` lists the aux_global keys in common-block order.
+A solver of the user's own is a ``CellRiemann``: C++ text compiled at ``setup()``, outside the table of built-in solvers.
 """
+import numpy as np
 
 
 class RiemannSolver(object):
@@ -66,6 +68,84 @@ rp_vc_acoustics_3d = RiemannSolver("vc_acoustics_3d", 20, 3, 4, 2, [])
 
 _ALL = [rp_elasticity_fwave_1d, rp_psystem_fwave_2d, rp_advection_1d, rp_acoustics_1d, rp_advection_color_1d, rp_burgers_1d, rp_euler_1d, rp_shallow_1d, rp_advection_2d, rp_shallow_2d, rp_vc_acoustics_2d, rp_vc_advection_2d, rp_acoustics_2d, rp_euler_5wave_2d, rp_shallow_sphere_2d, rp_vc_acoustics_3d]
 BY_NAME = dict((r.name, r) for r in _ALL)
+
+
+PCL_RP_CELL = 100      # include/pyclaw_amd.h: not a built-in id, outside _ALL
+
+
+class CellRiemann(RiemannSolver):
+    """A user-written NORMAL Riemann solver (Clawpack's rp1 / rpn2, one interface at a time) as the text of a C++
+    function body: ``solver.rp = CellRiemann(body, meqn, mwaves, ndim, params)`` on ``ClawSolver1D`` / ``ClawSolver2D``.
+    It is compiled at ``setup()`` into the library's own sweep kernel and runs in the classic 1-D step and in the two
+    passes of the dimension-split 2-D step with the tiles, limiter and Courant reduction of the built-in solvers.
+
+    The body sees ``ql[MEQN]``, ``qr[MEQN]`` (the cells left and right of the interface), ``p[8]`` (``params``;
+    reassigning them between steps compiles nothing), the compile-time constant ``ixy`` (1 = x, always in 1-D; 2 = y)
+    and assigns ``wave[MWAVES][MEQN]``, ``s[MWAVES]``, ``amdq[MEQN]``, ``apdq[MEQN]``, all zero on entry.  The helpers
+    of the built-in solvers (``dmax``, ``dmin``, ``dsqrt``, ``fdiv``, ``Recip``) are in scope; ``preamble`` holds helper
+    functions.  For bitwise-equal ``ql`` and ``qr`` the waves and fluctuations must be zero.  The body does not see
+    ``aux``.  No unsplit step (there is no transverse solver), no f-waves, no capacity function, no SharpClaw, no
+    3-D, one block; the 2-D step always runs as two passes."""
+
+    MAX_PARAMS = 8
+
+    def __init__(self, body, meqn, mwaves, ndim, params=(), preamble="", name="user"):
+        RiemannSolver.__init__(self, name, PCL_RP_CELL, int(ndim), int(meqn), int(mwaves), ())
+        if not 1 <= self.meqn <= 8 or not 1 <= self.mwaves <= 8:
+            raise ValueError("CellRiemann: 1 <= meqn <= 8 and 1 <= mwaves <= 8, got meqn=%d mwaves=%d" % (self.meqn, self.mwaves))
+        if self.ndim not in (1, 2):
+            raise ValueError("CellRiemann: ndim must be 1 or 2 (the classic 1-D and dimension-split 2-D sweeps), got %d" % self.ndim)
+        self.body = str(body)
+        self.preamble = str(preamble)
+        self.params = params
+        self._rp = None            # pcl_cellrp handle and what it was compiled for
+        self._key = None
+        self.code_size = 0
+
+    @property
+    def params(self):
+        return self._params
+
+    @params.setter
+    def params(self, values):
+        values = np.array(values, dtype=np.float64).reshape(-1)
+        if len(values) > self.MAX_PARAMS:
+            raise ValueError("a Riemann solver body takes at most %d parameters, got %d" % (self.MAX_PARAMS, len(values)))
+        self._params = values
+
+    def all_params(self, state):
+        return [float(v) for v in self._params]
+
+    def compile(self, math='exact'):
+        """Compile (no device needed; cached per process).  Raises with the compiler's log, whose line numbers are the
+        body's ("riemann:<n>") or the preamble's ("preamble:<n>")."""
+        import ctypes
+        from . import _lib
+        if math not in ('exact', 'fast', 'strict'):
+            raise Exception("math must be 'exact', 'fast' or 'strict'")
+        key = (self.meqn, self.mwaves, self.ndim, math, self.body, self.preamble)
+        if self._rp is not None and self._key == key:
+            return self
+        rp, size = ctypes.c_void_p(), ctypes.c_long(0)
+        _lib.check(_lib.lib().pcl_cellrp_compile(self.body.encode(), self.preamble.encode(), self.meqn, self.mwaves, self.ndim,
+                                                 {'exact': 0, 'fast': 1, 'strict': 2}[math], ctypes.byref(rp),
+                                                 ctypes.byref(size)))
+        self.release()
+        self._rp, self._key, self.code_size = rp, key, int(size.value)
+        return self
+
+    def release(self):
+        if self._rp is not None:
+            from . import _lib
+            _lib.lib().pcl_cellrp_release(self._rp)
+            self._rp = None
+            self._key = None
+
+    def __del__(self):
+        try:
+            self.release()
+        except Exception:
+            pass
 
 
 def get(rp):

@@ -316,6 +316,9 @@ class SharpClawSolver(Solver):
         if self.rp is None:
             raise Exception("solver.rp is not set: choose a Riemann solver from pyclaw_amd.riemann")
         rp = riemann.get(self.rp)
+        if isinstance(rp, riemann.CellRiemann):
+            raise NotImplementedError("CellRiemann: the SharpClaw solvers are not served: a user-written Riemann solver is "
+                                      "compiled into the classic sweep kernel only (ClawSolver1D / ClawSolver2D)")
         if rp.ndim != self.ndim or rp.mwaves != self.mwaves or rp.meqn != state.meqn:
             raise Exception("Riemann solver %s does not match ndim/mwaves/meqn of the problem" % rp.name)
         params = rp.all_params(state)

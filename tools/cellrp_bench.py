@@ -1,0 +1,129 @@
+#!/usr/bin/env python
+"""
+What a user-written Riemann solver costs per step on the resident 4096^2 acoustics problem, three ways:
+
+  (a) two_pass  the built-in acoustics_2d solver held to the two-pass form of the step (PCL_TUNE_FUSED_STEP=0)
+  (b) user      the same solver as a pyclaw.CellRiemann (problems.ACOUSTICS_2D_RP): always two passes
+  (c) default   the built-in solver on its default path (the one-kernel step with its quiet tiles)
+
+(a) and (b) run the same kernel template over the same tiles; (b) against (c) is the price of not having the one-kernel
+step.  PCL_TUNE_FUSED_STEP is read once per process, so every measurement is a child process of its own: `--reps` rounds
+of a, b, c in turn.  A child sets the problem up, takes `--warmup` steps and times `--steps` calls of step_hyperbolic at
+a fixed dt with device events, on two states: "pulse", the app's initial condition (most of the box is at rest), and
+"dense", the same with noise on every component of every cell.  Prints one JSON line with median (min - max) ms per
+step, and the hiprtc compile time of the user solver as the children saw it; needs a GPU.
+
+  python tools/cellrp_bench.py [--n 4096] [--steps 20] [--warmup 3] [--reps 7] [--out FILE]
+"""
+import argparse
+import ctypes
+import json
+import os
+import subprocess
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+VARIANTS = ("two_pass", "user", "default")
+
+
+def child(args):
+    import pyclaw_amd as pyclaw
+    from pyclaw_amd import _lib
+    from apps import problems
+    L = _lib.lib()
+    if L.pcl_device_count() < 1:
+        raise SystemExit("cellrp_bench: no HIP device (nothing here can be measured without one)")
+    claw = problems.acoustics2D(pyclaw, mx=args.n, my=args.n, run=False, math=args.math)
+    solver, solution = claw.solver, claw.solution
+    state = solution.state
+    res = {"variant": args.child}
+    if args.child == "user":
+        g = state.aux_global
+        solver.rp = pyclaw.CellRiemann(problems.ACOUSTICS_2D_RP, 3, 2, 2, params=[g['rho'], g['bulk'], g['cc'], g['zz']])
+        t0 = time.perf_counter()
+        solver.rp.compile(args.math)
+        res["compile_s"] = time.perf_counter() - t0
+    solver.setup(solution)
+    solver.dt_variable = False
+    solver.dt = 0.45 * min(state.grid.d) / state.aux_global['cc']
+    q_pulse = state.q.copy('F')
+    rng = np.random.default_rng(7)
+    q_dense = q_pulse + 0.01 * rng.standard_normal(q_pulse.shape)
+    ms = ctypes.c_float()
+    for name, q0 in (("pulse", q_pulse), ("dense", q_dense)):
+        state.q[...] = q0
+        solver.begin_resident(solution)
+        for _ in range(args.warmup):
+            solver.step_hyperbolic(solution)
+        _lib.check(L.pcl_sync(solver._h))
+        _lib.check(L.pcl_timer_start(solver._h))
+        for _ in range(args.steps):
+            solver.step_hyperbolic(solution)
+        _lib.check(L.pcl_timer_stop(solver._h, ctypes.byref(ms)))
+        res[name + "_ms"] = ms.value / args.steps
+        res[name + "_cfl"] = solver.cfl.get_cached_max()
+        solver.end_resident(solution)
+        res[name + "_sum"] = float(np.abs(state.q).sum())         # the variants compute the same thing
+    solver.teardown()
+    res["forms"] = solver.status.get("step_forms")
+    print("CELLRP_CHILD " + json.dumps(res))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--n", type=int, default=4096)
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--math", default="exact")
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--child", default=None, choices=VARIANTS)
+    args = ap.parse_args()
+    if args.child:
+        return child(args)
+
+    runs = {v: [] for v in VARIANTS}
+    for _ in range(args.reps):
+        for v in VARIANTS:
+            env = dict(os.environ)
+            env.pop("PCL_TUNE_FUSED_STEP", None)
+            if v == "two_pass":
+                env["PCL_TUNE_FUSED_STEP"] = "0"
+            cmd = [sys.executable, os.path.abspath(__file__), "--child", v, "--n", str(args.n), "--steps", str(args.steps),
+                   "--warmup", str(args.warmup), "--math", args.math]
+            out = subprocess.run(cmd, env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=300)
+            lines = [l for l in out.stdout.splitlines() if l.startswith("CELLRP_CHILD ")]
+            if out.returncode != 0 or not lines:
+                raise SystemExit("cellrp_bench: the %s run failed (exit %d):\n%s" % (v, out.returncode, out.stdout[-2000:]))
+            runs[v].append(json.loads(lines[-1][len("CELLRP_CHILD "):]))
+
+    def spread(vals):
+        return {"median": float(np.median(vals)), "min": min(vals), "max": max(vals), "all": vals}
+    res = {"tool": "cellrp_bench", "n": args.n, "math": args.math, "steps": args.steps, "warmup": args.warmup, "reps": args.reps,
+           "compile_s": spread([r["compile_s"] for r in runs["user"]]), "forms": {v: runs[v][-1]["forms"] for v in VARIANTS},
+           "states": {}}
+    for name in ("pulse", "dense"):
+        st = {v + "_ms": spread([r[name + "_ms"] for r in runs[v]]) for v in VARIANTS}
+        sums = set(r[name + "_sum"] for v in VARIANTS for r in runs[v])
+        cfls = set(r[name + "_cfl"] for v in VARIANTS for r in runs[v])
+        st["same_result_in_every_run"] = len(sums) == 1 and len(cfls) == 1
+        a, b, c = (st[v + "_ms"] for v in VARIANTS)
+        st["user_over_two_pass"] = b["median"] / a["median"]
+        st["user_and_two_pass_spreads_overlap"] = not (b["min"] > a["max"] or a["min"] > b["max"])
+        st["user_over_default"] = b["median"] / c["median"]
+        res["states"][name] = st
+    line = json.dumps(res)
+    print(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()

@@ -1,0 +1,110 @@
+// cellrp_host_check.cpp -- the host side of the user-written Riemann solvers (csrc/cellrp.hpp, pcl_cellrp_*) on a machine
+// without a GPU: the real pclaw.hip (built with the sanitizer on its host code) linked against hip_shim.cpp.  The compile
+// is real (libhiprtc needs no device): program text, named headers, name expressions, lowered names and the shared cache
+// all run under the sanitizer.  The shim loads no module, so pcl_cellrp_attach ends in PCL_EHIP behind its host-only
+// checks and a PCL_RP_CELL handle stays without a solver: every step is refused, which is the path checked here.
+// Exit status 0 and no sanitizer report: passed.  tools/host_check/run.sh
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+
+#include "../../include/pyclaw_amd.h"
+
+#define CHECK(call)                                                                                     \
+    do {                                                                                                \
+        const int rc_ = (call);                                                                         \
+        if (rc_ != PCL_OK) {                                                                            \
+            fprintf(stderr, "%s:%d: %s -> %d: %s\n", __FILE__, __LINE__, #call, rc_, pcl_last_error()); \
+            exit(1);                                                                                    \
+        }                                                                                               \
+    } while (0)
+#define EXPECT(cond)                                                                                   \
+    do {                                                                                               \
+        if (!(cond)) {                                                                                 \
+            fprintf(stderr, "%s:%d: expected %s (%s)\n", __FILE__, __LINE__, #cond, pcl_last_error()); \
+            exit(1);                                                                                   \
+        }                                                                                              \
+    } while (0)
+
+static const char *kBurgers =
+    "wave[0][0] = qr[0] - ql[0];\n"
+    "s[0] = 0.5 * (ql[0] + qr[0]);\n"
+    "const bool transonic = qr[0] > 0.0 && ql[0] < 0.0;\n"
+    "amdq[0] = transonic ? -0.5 * (ql[0] * ql[0]) : dmin(s[0], 0.0) * wave[0][0];\n"
+    "apdq[0] = transonic ? 0.5 * (qr[0] * qr[0]) : dmax(s[0], 0.0) * wave[0][0];\n";
+
+int main() {
+    long n0 = 0, h0 = 0, n = 0, h = 0, size = 0;
+    CHECK(pcl_cellfn_stats(&n0, &h0));
+    pcl_cellrp *a = nullptr, *b = nullptr, *c = nullptr, *bad = nullptr;
+    // refusals in front of the compile
+    EXPECT(pcl_cellrp_compile(kBurgers, "", 0, 1, 2, PCL_MATH_EXACT, &bad, nullptr) == PCL_EINVAL && !bad);
+    EXPECT(pcl_cellrp_compile(kBurgers, "", 1, 9, 2, PCL_MATH_EXACT, &bad, nullptr) == PCL_EINVAL);
+    EXPECT(pcl_cellrp_compile(kBurgers, "", 1, 1, 3, PCL_MATH_EXACT, &bad, nullptr) == PCL_EINVAL);
+    EXPECT(pcl_cellrp_compile(nullptr, "", 1, 1, 2, PCL_MATH_EXACT, &bad, nullptr) == PCL_EINVAL);
+    // two passes in 2-D, one kernel in 1-D; a null preamble; the cache
+    CHECK(pcl_cellrp_compile(kBurgers, nullptr, 1, 1, 2, PCL_MATH_EXACT, &a, &size));
+    EXPECT(a && size > 0);
+    CHECK(pcl_cellrp_compile(kBurgers, "", 1, 1, 2, PCL_MATH_EXACT, &b, nullptr));
+    EXPECT(b == a);
+    CHECK(pcl_cellrp_compile(kBurgers, "__device__ inline double twice(double v) { return 2.0 * v; }\n", 1, 1, 1, PCL_MATH_FAST, &c, nullptr));
+    EXPECT(c && c != a);
+    CHECK(pcl_cellfn_stats(&n, &h));
+    EXPECT(n == n0 + 2 && h == h0 + 1);
+    // a body that does not compile: the log names the line, nothing is cached
+    EXPECT(pcl_cellrp_compile("s[0] = 1.0;\ns[0] = nothing;\n", "", 1, 1, 1, PCL_MATH_EXACT, &bad, nullptr) == PCL_EINVAL && !bad);
+    EXPECT(strstr(pcl_last_error(), "riemann:2") != nullptr);
+    CHECK(pcl_cellfn_stats(&n, &h));
+    EXPECT(n == n0 + 2 && h == h0 + 1);
+    // the handle's constants
+    CHECK(pcl_cellrp_check(a, 1, 1, 2, PCL_MATH_EXACT));
+    EXPECT(pcl_cellrp_check(a, 2, 1, 2, PCL_MATH_EXACT) == PCL_EINVAL);
+    EXPECT(pcl_cellrp_check(a, 1, 1, 2, PCL_MATH_FAST) == PCL_EINVAL);
+    EXPECT(pcl_cellrp_check(nullptr, 1, 1, 2, PCL_MATH_EXACT) == PCL_EINVAL);
+
+    // a PCL_RP_CELL solver handle
+    pcl_config cfg;
+    memset(&cfg, 0, sizeof cfg);
+    cfg.ndim = 2; cfg.n[0] = 70; cfg.n[1] = 9; cfg.mbc = 3; cfg.meqn = 1; cfg.mwaves = 1;
+    cfg.method[0] = 1; cfg.method[1] = 2; cfg.method[2] = -1;
+    cfg.mthlim[0] = 4; cfg.rp = PCL_RP_CELL; cfg.d[0] = cfg.d[1] = 0.1; cfg.math = PCL_MATH_EXACT;
+    pcl_solver *s = nullptr;
+    pcl_config wrong = cfg;
+    wrong.fwave = 1;
+    EXPECT(pcl_create(&wrong, &s) == PCL_EINVAL && !s);
+    wrong = cfg;
+    wrong.method[2] = 1;
+    EXPECT(pcl_create(&wrong, &s) == PCL_EINVAL && !s);
+    CHECK(pcl_create(&cfg, &s));
+    int info[10];
+    EXPECT(pcl_rp_info(PCL_RP_CELL, info) == PCL_EINVAL);
+    std::vector<double> q((size_t)cfg.n[0] * cfg.n[1], 1.0);
+    CHECK(pcl_put_q(s, q.data(), 0));
+    double cfl = -1.0;
+    EXPECT(pcl_step_hyperbolic(s, 0.01, &cfl) == PCL_ESTATE);
+    EXPECT(pcl_sweep(s, 2, 0.01, &cfl) == PCL_ESTATE);
+    EXPECT(pcl_cellrp_attach(s, c) == PCL_EINVAL);          // compiled for 1-D, fast
+    EXPECT(pcl_cellrp_attach(s, nullptr) == PCL_EINVAL);
+    EXPECT(pcl_cellrp_attach(s, a) == PCL_EHIP);            // host checks passed; the shim loads no module
+    EXPECT(pcl_step_hyperbolic(s, 0.01, &cfl) == PCL_ESTATE);
+    const double p9[9] = {1, 2, 3, 4, 5, 6, 7, 8, 9};
+    EXPECT(pcl_cellrp_params(s, p9, 9) == PCL_EINVAL);
+    CHECK(pcl_cellrp_params(s, p9, 8));
+    CHECK(pcl_cellrp_params(s, nullptr, 0));
+    const int nbr[8] = {-1, -1, -1, -1, -1, -1, -1, -1};
+    char uid[128] = {0};
+    EXPECT(pcl_comm_init(s, 1, 0, uid, nbr) == PCL_EINVAL);
+    pcl_destroy(s);
+
+    // references: two for a (compiled twice), one for c
+    CHECK(pcl_cellrp_release(a));
+    CHECK(pcl_cellrp_release(b));
+    EXPECT(pcl_cellrp_release(a) == PCL_EINVAL);
+    CHECK(pcl_cellrp_release(c));
+    CHECK(pcl_cellrp_release(nullptr));
+    CHECK(pcl_cellrp_compile(kBurgers, "", 1, 1, 2, PCL_MATH_EXACT, &b, nullptr));      // released, not forgotten
+    EXPECT(b == a);
+    printf("cellrp_host_check: ok\n");
+    return 0;
+}
