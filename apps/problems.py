@@ -171,6 +171,55 @@ for (int m = 0; m < 3; m++) { amdq[m] = s[0] * wave[0][m]; apdq[m] = s[1] * wave
 # A system the library does not have: scalar 2-D Burgers, q_t + (q^2/2)_x + (q^2/2)_y = 0 -- the 1-D body either way
 BURGERS_2D_RP = BURGERS_1D_RP
 
+# Solvers with cell-wise coefficients: pyclaw.CellRiemann(..., aux=...) hands the body auxl[], auxr[], the listed aux
+# components of the cells left and right of the interface.  The first three restate the built-in solvers with aux
+# (AdvectionColor1D, VcAdvection2D, VcAcoustics2D of pyclaw_amd/csrc/rp.hpp) expression by expression.
+
+# colour equation q_t + u(x) q_x = 0, aux = (0,): the velocity at the cell's LEFT edge, so the interface takes auxr
+ADVECTION_COLOR_1D_RP = """
+wave[0][0] = qr[0] - ql[0];
+s[0] = auxr[0];
+amdq[0] = dmin(auxr[0], 0.0) * wave[0][0];
+apdq[0] = dmax(auxr[0], 0.0) * wave[0][0];
+"""
+
+# 2-D colour equation, aux = (0, 1): u at the left edge, v at the bottom edge; the sweep direction picks one
+VC_ADVECTION_2D_RP = """
+const double vel = ixy == 1 ? auxr[0] : auxr[1];
+wave[0][0] = qr[0] - ql[0];
+s[0] = vel;
+amdq[0] = dmin(vel, 0.0) * wave[0][0];
+apdq[0] = dmax(vel, 0.0) * wave[0][0];
+"""
+
+# 2-D acoustics q = (p, u, v) with impedance and sound speed per cell, aux = (0, 1) = (Z, c); Z, c > 0
+VC_ACOUSTICS_2D_RP = """
+constexpr int mu = (ixy == 1) ? 1 : 2;
+const double d1 = qr[0] - ql[0];
+const double d2 = qr[mu] - ql[mu];
+const double zi = auxr[0], zim = auxl[0];
+const Recip by_zz(zim + zi);
+const double a1 = by_zz.div(-d1 + zi * d2);
+const double a2 = by_zz.div(d1 + zim * d2);
+wave[0][0] = -a1 * zim; wave[0][mu] = a1; s[0] = -auxl[1];
+wave[1][0] = a2 * zi;   wave[1][mu] = a2; s[1] = auxr[1];
+amdq[0] = s[0] * wave[0][0]; amdq[mu] = s[0] * wave[0][mu];
+apdq[0] = s[1] * wave[1][0]; apdq[mu] = s[1] * wave[1][mu];
+"""
+
+# A solver the library does not have: 1-D acoustics q = (p, u) in a layered medium, aux = (0, 1) = (Z, c) per cell
+# (Clawpack's rp1_acoustics_variable): the left-going wave travels in the left cell, the right-going one in the right
+VC_ACOUSTICS_1D_RP = """
+const double d1 = qr[0] - ql[0];
+const double d2 = qr[1] - ql[1];
+const double zi = auxr[0], zim = auxl[0];
+const double a1 = (-d1 + zi * d2) / (zim + zi);
+const double a2 = (d1 + zim * d2) / (zim + zi);
+wave[0][0] = -a1 * zim; wave[0][1] = a1; s[0] = -auxl[1];
+wave[1][0] = a2 * zi;   wave[1][1] = a2; s[1] = auxr[1];
+for (int m = 0; m < 2; m++) { amdq[m] = s[0] * wave[0][m]; apdq[m] = s[1] * wave[1][m]; }
+"""
+
 
 def shockbubble(pyclaw, mx=160, my=40, tfinal=0.2, device_callbacks=False, with_src=True,
                 dim_split=True, order_trans=2, dt_initial=0.005, nout=1, run=True, math='exact',
@@ -295,6 +344,31 @@ def acoustics2D(pyclaw, mx=100, my=100, tfinal=0.12, nout=10, dim_split=1, run=T
     if not run:
         return claw
     claw.run()
+    return claw
+
+
+def vc_acoustics2D(pyclaw, mx=100, my=100, tfinal=0.12, nout=10, run=True, math='exact', user_rp=False):
+    """The pulse of acoustics2D in a layered medium: impedance and sound speed per cell in aux(1), aux(2) -- four layers
+    in x with the sound speeds 2, 1.5, 1, 1.25 and an impedance that also varies smoothly in y.  Dimension-split, with
+    rp_vc_acoustics_2d or, user_rp=True, the same solver as the body VC_ACOUSTICS_2D_RP of a pyclaw.CellRiemann."""
+    claw = acoustics2D(pyclaw, mx=mx, my=my, tfinal=tfinal, nout=nout, run=False, math=math)
+    old = claw.solution.state
+    state = pyclaw.State(old.grid, 3, 2)
+    state.q[...] = old.q
+    X, Y = old.grid.c_center
+    layer = np.minimum((2.0 * (X + 1.0)).astype(int), 3)
+    cc = np.array([2.0, 1.5, 1.0, 1.25])[layer]
+    state.aux[0] = cc * (1.0 + 0.25 * np.sin(np.pi * Y))       # Z = rho c with a density that varies in y
+    state.aux[1] = cc
+    claw.solution = pyclaw.Solution(state)
+    solver = claw.solver
+    solver.rp = (pyclaw.CellRiemann(VC_ACOUSTICS_2D_RP, 3, 2, 2, aux=(0, 1), name="vc_acoustics_2d_user") if user_rp
+                 else pyclaw.riemann.rp_vc_acoustics_2d)
+    for k in range(2):
+        solver.aux_bc_lower[k] = solver.aux_bc_upper[k] = pyclaw.BC.outflow
+    solver.dt_initial = np.min(old.grid.d) / 2.0 * solver.cfl_desired
+    if run:
+        claw.run()
     return claw
 
 

@@ -71,7 +71,8 @@ extern "C" {
                                   /* (rpt3/rptt3_vc_acoustics.f) without a capacity function                                   */
 #define PCL_RP_CELL 100 /* a user-written normal Riemann solver compiled at run time (pcl_cellrp_compile / _attach below):  */
                         /* meqn, mwaves <= 8 from the config, rp_params = the body's p[8]; classic 1-D and dimension-split  */
-                        /* 2-D steps in wave form, no capacity function.  Not a built-in solver: pcl_rp_info refuses the id */
+                        /* 2-D steps in wave form, no capacity function; the body may read listed aux components            */
+                        /* (pcl_cellrp_compile_aux).  Not a built-in solver: pcl_rp_info refuses the id                     */
 
 /* boundary condition types = pyclaw.BC (src/pyclaw/solver.py:17-23) */
 #define PCL_BC_CUSTOM 0
@@ -389,11 +390,30 @@ int pcl_cellbc_apply(pcl_solver *s, pcl_cellfn *f, int idim, int side, double t,
 typedef struct pcl_cellrp pcl_cellrp;
 int pcl_cellrp_compile(const char *body, const char *preamble, int meqn, int mwaves, int ndim, int math, pcl_cellrp **out,
                        long *code_size);
+/* The same for a solver with cell-wise coefficients: aux_index[0..naux) lists the components of the aux array (0-based)
+ * the body reads.  The sweep stages those planes next to q in its tile, as it does for the built-in solvers with aux, and
+ * the body also sees
+ *     auxl[NAUX], auxr[NAUX]   the listed components, in list order, of the cells left and right of the interface (const);
+ *                              Clawpack's "aux(1) = the value at the left edge of cell i" is auxr[0]
+ * One list serves both sweeps; a body that reads another component per direction branches on ixy.
+ * Contract: for bitwise-equal ql and qr the waves and fluctuations must be zero WHATEVER aux holds -- a wavefront without
+ * a jump in q takes the speeds alone, each interface with its own auxl / auxr.  A flux-difference form over varying
+ * coefficients breaks this; that is an f-wave solver and is not served.
+ * The tile holds meqn + naux planes in a workgroup's 64 KB: meqn + naux <= 8 (65536 bytes / (8 bytes * the 1024 cells
+ * of the y tile)); more is PCL_EINVAL with the limit in the message, and so are naux < 0 and a negative or repeated
+ * index.  The list is part of the cache key (another order is another program); naux == 0 is pcl_cellrp_compile itself:
+ * the same program, key and handle.  Host-only. */
+int pcl_cellrp_compile_aux(const char *body, const char *preamble, int meqn, int mwaves, int ndim, int math, const int *aux_index,
+                           int naux, pcl_cellrp **out, long *code_size);
+/* Host-only: the list a live handle was compiled with; aux_index (may be null) gets *naux <= 8 entries. */
+int pcl_cellrp_aux(const pcl_cellrp *r, int *naux, int *aux_index);
 int pcl_cellrp_release(pcl_cellrp *r);
 /* Host-only: the handle is live and was compiled for these constants (what pcl_cellrp_attach asks of it). */
 int pcl_cellrp_check(const pcl_cellrp *r, int meqn, int mwaves, int ndim, int math);
 /* Gives a PCL_RP_CELL solver its Riemann solver: the module is loaded into the handle's device (one attached at a time;
- * pcl_destroy unloads it).  Until then every step of such a solver is refused with PCL_ESTATE. */
+ * pcl_destroy unloads it).  Until then every step of such a solver is refused with PCL_ESTATE.  A handle whose largest
+ * listed aux component is >= cfg.maux is refused (PCL_EINVAL, both numbers in the message) before anything is loaded, and
+ * the sweeps of a solver that reads aux are refused (PCL_EINVAL) until pcl_put_aux has uploaded the array. */
 int pcl_cellrp_attach(pcl_solver *s, pcl_cellrp *r);
 /* The body's p[0..nparams-1] from the next sweep on (nparams <= 8; the rest are zero): they travel by value with every
  * launch, so changing them compiles nothing. */

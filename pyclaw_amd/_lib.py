@@ -102,6 +102,9 @@ PROTOTYPES = {
     "pcl_cellbc_apply": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, dp, C.c_int]),
     "pcl_cellrp_compile": (C.c_int, [C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p),
                                      C.POINTER(C.c_long)]),
+    "pcl_cellrp_compile_aux": (C.c_int, [C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, ip, C.c_int,
+                                         C.POINTER(C.c_void_p), C.POINTER(C.c_long)]),
+    "pcl_cellrp_aux": (C.c_int, [C.c_void_p, ip, ip]),
     "pcl_cellrp_release": (C.c_int, [C.c_void_p]),
     "pcl_cellrp_check": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]),
     "pcl_cellrp_attach": (C.c_int, [C.c_void_p, C.c_void_p]),

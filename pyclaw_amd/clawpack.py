@@ -303,6 +303,14 @@ class ClawSolver(Solver):
         if state.decomp is not None and parallel.world_size() > 1:
             raise NotImplementedError("CellRiemann: more than one rank is not served: a user-written solver runs on one "
                                       "block (the decomposed step's plans know the built-in solvers only)")
+        rp = self.rp
+        if rp.aux:
+            # (an index past maux would be a read outside the aux allocation: the library refuses it again at attach)
+            if state.aux is None:
+                raise ValueError("CellRiemann: the body reads aux components %r and state.aux is None" % (rp.aux,))
+            if max(rp.aux) >= state.maux:
+                raise ValueError("CellRiemann: the body reads aux component %d (0-based) and state.maux = %d"
+                                 % (max(rp.aux), state.maux))
 
     def _send_user_rp_params(self):
         """CellRiemann.params reassigned since the last step: they travel by value with the next sweeps, no compile."""

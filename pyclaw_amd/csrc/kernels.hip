@@ -79,6 +79,10 @@ template <int IXY, bool DIM1> int launch_user(const SweepLaunch &l, std::string 
         err = "user-written Riemann solver: wave form only, no capacity function, no fused source";
         return PCL_EINVAL;
     }
+    if (l.user_naux > 0 && !l.a.aux) {
+        err = "user-written Riemann solver: this solver reads aux arrays and there are none (pcl_put_aux)";
+        return PCL_EINVAL;
+    }
     SweepGrid g;
     if (int rc = sweep_grid<IXY, DIM1>(l.a, g, err)) return rc;
     if (g.nblocks == 0) return PCL_OK;
@@ -276,6 +280,12 @@ int launch_unsplit3(const Unsplit3Launch &l, std::string &err) {
 #if !PCL_FAST
 // the host layer's view of the solver list (sweep_args.hpp: RpFacts; nothing in it depends on the arithmetic mode)
 const RpFacts *rp_facts(int rp) { return Solvers::facts(rp); }
+// planes (q components + staged aux components) the LDS tile of sweep_kernel holds within a workgroup's 64 KB, for both
+// tile shapes: what a user-written Riemann solver's meqn + naux may come to (cellrp.hpp)
+int sweep_tile_max_planes() {
+    constexpr int PLANE = TileShape<1>::PLANE > TileShape<2>::PLANE ? TileShape<1>::PLANE : TileShape<2>::PLANE;
+    return 65536 / ((int)sizeof(double) * PLANE);
+}
 // the same for the one-kernel step (classic_fused.hpp): tile (ty, tx) reads rows mbc-2+F_OWN_R*ty .. +F_ROWS-1 and columns
 // mbc-2+60*tx .. +63; box = [ty_lo, ty_hi) x [tx_lo, tx_hi), ntiles = (nty, ntx)
 bool step2ds_interior_box(const BlockGeom &a, int box[4], int ntiles[2]) {

@@ -97,6 +97,9 @@ struct pcl_solver {
     int cf_nstart[3] = {0, 0, 0};
     // cfg.rp == PCL_RP_CELL: the user-written Riemann solver's module (cellrp.hpp, pcl_cellrp_attach)
     pcl::CellrpModule cellrp;
+    // pcl_put_aux has been called: the aux allocation holds the caller's coefficients and not the zeros of pcl_create.
+    // A user-written solver whose body reads aux is not launched before (make_launch)
+    bool aux_put = false;
 };
 
 static inline double *&cur(pcl_solver *s) { return s->sel == 0 ? s->q : s->sreg[s->sel]; }
@@ -375,7 +378,11 @@ SweepLaunch make_launch(const pcl_solver *s, const SweepArgs &a, int ndim, int i
     l.ids = ids;
     l.fwave = s->cfg.fwave;
     l.stream = stream;
-    if (l.rp == PCL_RP_CELL && ndim <= 2) l.user_fn = s->cellrp.fn[ids - 1];     // null: nothing attached, refused by the launcher
+    if (l.rp == PCL_RP_CELL && ndim <= 2) {
+        l.user_fn = s->cellrp.fn[ids - 1];     // null: nothing attached, refused by the launcher
+        l.user_naux = s->cellrp.naux;
+        if (l.user_naux > 0 && !s->aux_put) l.a.aux = nullptr;     // nothing uploaded yet: refused by the launcher too
+    }
     return l;
 }
 
@@ -682,7 +689,7 @@ int check_device() {
 extern "C" {
 
 const char *pcl_last_error(void) { return g_err.c_str(); }
-int pcl_version(void) { return 106; }
+int pcl_version(void) { return 107; }
 int pcl_device_count(void) {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess) return 0;
@@ -935,7 +942,9 @@ int pcl_put_aux(pcl_solver *s, const double *host) {
     if (!s || !host) return fail(PCL_EINVAL, "null argument");
     if (s->cfg.maux <= 0) return fail(PCL_EINVAL, "solver was created with maux == 0");
     HIP_TRY(hipSetDevice(s->cfg.device));
-    return upload(s, host, s->aux, s->cfg.maux, Window(s, 1));
+    if (int rc = upload(s, host, s->aux, s->cfg.maux, Window(s, 1))) return rc;
+    s->aux_put = true;
+    return PCL_OK;
 }
 
 int pcl_get_aux(pcl_solver *s, double *host) {
@@ -1702,6 +1711,12 @@ int pcl_cellfn_check(const pcl_cellfn *f, int meqn, int maux, int ndim) {
 // ---- user-written Riemann solvers (cellrp.hpp) ---------------------------------------------------------------------
 int pcl_cellrp_compile(const char *body, const char *preamble, int meqn, int mwaves, int ndim, int math, pcl_cellrp **out,
                        long *code_size) {
+    return pcl_cellrp_compile_aux(body, preamble, meqn, mwaves, ndim, math, nullptr, 0, out, code_size);
+}
+
+// naux == 0 is pcl_cellrp_compile: the same program text, key and handle
+int pcl_cellrp_compile_aux(const char *body, const char *preamble, int meqn, int mwaves, int ndim, int math, const int *aux_index,
+                           int naux, pcl_cellrp **out, long *code_size) {
     if (!body || !out) return fail(PCL_EINVAL, "null argument");
     *out = nullptr;
     if (!preamble) preamble = "";
@@ -1709,9 +1724,26 @@ int pcl_cellrp_compile(const char *body, const char *preamble, int meqn, int mwa
         return fail(PCL_EINVAL, "pcl_cellrp_compile: 1 <= meqn <= 8 and 1 <= mwaves <= 8");
     if (ndim < 1 || ndim > 2) return fail(PCL_EINVAL, "pcl_cellrp_compile: ndim must be 1 or 2 (the classic 1-D and dimension-split 2-D sweeps)");
     if (math != PCL_MATH_EXACT && math != PCL_MATH_FAST && math != PCL_MATH_STRICT) return fail(PCL_EINVAL, "unknown math mode");
+    // the list of aux components: an index past the solver's maux would be a read outside the aux allocation, so every
+    // entry is checked here and the largest against cfg.maux when the handle is attached
+    if (naux < 0) return fail(PCL_EINVAL, "pcl_cellrp_compile_aux: naux must be >= 0, got " + std::to_string(naux));
+    if (naux > 0 && !aux_index) return fail(PCL_EINVAL, "null argument");
+    const int max_planes = pcl::exact::sweep_tile_max_planes();
+    if (naux > 0 && meqn + naux > max_planes)
+        return fail(PCL_EINVAL, "pcl_cellrp_compile_aux: meqn + naux = " + std::to_string(meqn + naux) + ", the sweep's tile holds at most " +
+                                    std::to_string(max_planes) + " planes (q components and listed aux components) in a workgroup's 64 KB");
+    static_assert(PCL_CELLRP_MAX_AUX >= PCL_MAX_WAVES, "pcl_cellrp_aux writes up to 8 indices");
+    if (naux > PCL_CELLRP_MAX_AUX) return fail(PCL_EINVAL, "pcl_cellrp_compile_aux: at most 8 aux components");
+    for (int i = 0; i < naux; i++) {
+        if (aux_index[i] < 0)
+            return fail(PCL_EINVAL, "pcl_cellrp_compile_aux: aux index " + std::to_string(aux_index[i]) + " is negative (0-based components of the aux array)");
+        for (int j = 0; j < i; j++)
+            if (aux_index[j] == aux_index[i])
+                return fail(PCL_EINVAL, "pcl_cellrp_compile_aux: aux index " + std::to_string(aux_index[i]) + " is listed twice");
+    }
     CellfnCache &c = cellfn_cache();
     std::lock_guard<std::mutex> lock(c.mu);
-    const std::string key = cellrp_key(body, preamble, meqn, mwaves, ndim, math);
+    const std::string key = cellrp_key(body, preamble, meqn, mwaves, ndim, math, aux_index, naux);
     auto it = c.rp_by_key.find(key);
     pcl_cellrp *r = nullptr;
     if (it != c.rp_by_key.end()) {
@@ -1720,10 +1752,12 @@ int pcl_cellrp_compile(const char *body, const char *preamble, int meqn, int mwa
     } else {
         std::vector<char> code;
         std::string err, sym[2];
-        if (cellrp_build(body, preamble, meqn, mwaves, ndim, math, code, sym, err)) return fail(PCL_EINVAL, err);
+        if (cellrp_build(body, preamble, meqn, mwaves, ndim, math, aux_index, naux, code, sym, err)) return fail(PCL_EINVAL, err);
         r = new pcl_cellrp();
         r->id = c.next_id++;
         r->meqn = meqn; r->mwaves = mwaves; r->ndim = ndim; r->math = math;
+        r->naux = naux;
+        for (int i = 0; i < naux; i++) r->aux[i] = aux_index[i];
         r->key = key;
         r->code.swap(code);
         r->sym[0] = sym[0]; r->sym[1] = sym[1];
@@ -1763,18 +1797,35 @@ int pcl_cellrp_check(const pcl_cellrp *r, int meqn, int mwaves, int ndim, int ma
     return cellrp_check_locked(c, r, meqn, mwaves, ndim, math);
 }
 
+int pcl_cellrp_aux(const pcl_cellrp *r, int *naux, int *aux_index) {
+    if (!naux) return fail(PCL_EINVAL, "null argument");
+    CellfnCache &c = cellfn_cache();
+    std::lock_guard<std::mutex> lock(c.mu);
+    if (!r || !c.rp_live.count(r)) return fail(PCL_EINVAL, "not a live Riemann solver handle (pcl_cellrp_compile)");
+    *naux = r->naux;
+    for (int i = 0; aux_index && i < r->naux; i++) aux_index[i] = r->aux[i];
+    return PCL_OK;
+}
+
 int pcl_cellrp_attach(pcl_solver *s, pcl_cellrp *r) {
     if (s) s->qt.invalidate();            // quiet tiles: not a read-only call (quiet_tiles.hpp)
     if (!s) return fail(PCL_EINVAL, "null argument");
     if (s->cfg.rp != PCL_RP_CELL) return fail(PCL_EINVAL, "pcl_cellrp_attach: the solver was not created with cfg.rp = PCL_RP_CELL");
     long id;
+    int naux;
     const void *code;
     std::string sym[2];
     {   // (the entry is never freed: code and names stay valid outside the lock)
         CellfnCache &c = cellfn_cache();
         std::lock_guard<std::mutex> lock(c.mu);
         if (int rc = cellrp_check_locked(c, r, s->cfg.meqn, s->cfg.mwaves, s->cfg.ndim, s->cfg.math)) return rc;
-        id = r->id; code = r->code.data(); sym[0] = r->sym[0]; sym[1] = r->sym[1];
+        // every aux plane the kernel stages must lie inside the solver's aux allocation of cfg.maux planes
+        int top = -1;
+        for (int i = 0; i < r->naux; i++) top = r->aux[i] > top ? r->aux[i] : top;
+        if (top >= s->cfg.maux)
+            return fail(PCL_EINVAL, "pcl_cellrp_attach: the Riemann solver reads aux component " + std::to_string(top) +
+                                        " (0-based), the solver was created with maux = " + std::to_string(s->cfg.maux));
+        id = r->id; naux = r->naux; code = r->code.data(); sym[0] = r->sym[0]; sym[1] = r->sym[1];
     }
     if (s->cellrp.id == id) return PCL_OK;
     HIP_TRY(hipSetDevice(s->cfg.device));
@@ -1790,6 +1841,7 @@ int pcl_cellrp_attach(pcl_solver *s, pcl_cellrp *r) {
         }
     }
     m.id = id;
+    m.naux = naux;
     s->cellrp = m;
     return PCL_OK;
 }

@@ -166,6 +166,7 @@ struct SweepLaunch {
     // rp == PCL_RP_CELL (a user-written Riemann solver, cellrp.hpp): sweep_kernel<UserRp, ids, ...> of the module the
     // solver handle has loaded; launch_sweep launches it over the grid it computes for the built-in solvers
     hipFunction_t user_fn = nullptr;
+    int user_naux = 0;      // aux components that solver's body reads: with any, a launch without a.aux is refused
     // one-kernel step only (classic_fused.hpp, quiet tiles): this launch's per-tile words and per-wavefront Courant
     // maxima (tq_out null: no bookkeeping).  A list launch (tq_list set) computes the tq_next->na + nq tiles a
     // hand-over+list kernel listed behind the previous launch and publishes the Courant number of those it skips.
@@ -221,6 +222,7 @@ struct InteriorBox { bool any = false; int box[4] = {0, 0, 0, 0}, ntiles[2] = {0
 // defined in kernels.hip, once per arithmetic mode; returns 0 or a PCL_E* code + message
 namespace exact {
 const RpFacts *rp_facts(int rp);    // null: no built-in solver has this id (the same in every mode)
+int sweep_tile_max_planes();        // q + aux planes a sweep_kernel tile may hold (TileShape<1/2>::PLANE against 64 KB)
 int launch_sweep(const SweepLaunch &l, std::string &err);
 int launch_step2ds(const SweepLaunch &l, std::string &err);   // whole dim-split 2-D step in one kernel (classic_fused.hpp)
 // x-pass tiles [tb_lo,tb_hi) x [ta_lo,ta_hi) that read no ghost cell; false if there are none

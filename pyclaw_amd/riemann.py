@@ -83,18 +83,41 @@ class CellRiemann(RiemannSolver):
     reassigning them between steps compiles nothing), the compile-time constant ``ixy`` (1 = x, always in 1-D; 2 = y)
     and assigns ``wave[MWAVES][MEQN]``, ``s[MWAVES]``, ``amdq[MEQN]``, ``apdq[MEQN]``, all zero on entry.  The helpers
     of the built-in solvers (``dmax``, ``dmin``, ``dsqrt``, ``fdiv``, ``Recip``) are in scope; ``preamble`` holds helper
-    functions.  For bitwise-equal ``ql`` and ``qr`` the waves and fluctuations must be zero.  The body does not see
-    ``aux``.  No unsplit step (there is no transverse solver), no f-waves, no capacity function, no SharpClaw, no
+    functions.  For bitwise-equal ``ql`` and ``qr`` the waves and fluctuations must be zero.
+
+    A solver with cell-wise coefficients names the components of ``state.aux`` its body reads: ``aux=(0, 1)``
+    (0-based).  The sweep stages those planes next to q in its tile, and the body also sees ``auxl[NAUX]`` and
+    ``auxr[NAUX]``, the listed components in list order of the cell left and of the cell right of the interface
+    (Clawpack's "aux(1) is the value at the left edge of cell i" is ``auxr[0]``).  One list serves both sweeps; a body
+    that reads another component per direction branches on ``ixy``.  With aux the contract reads: for bitwise-equal
+    ``ql`` and ``qr`` the waves and fluctuations are zero *whatever aux holds* -- a wavefront without a jump in q takes
+    the speeds alone, each interface with its own ``auxl`` / ``auxr``.  A flux-difference form over varying coefficients
+    breaks this; that is an f-wave solver and is not served.  The tile holds ``meqn + len(aux)`` planes in a
+    workgroup's 64 KB, which comes to at most 8 (``MAX_PLANES``; the library derives it from its tile shapes and
+    refuses with its own figure).  ``setup()`` needs ``state.aux`` with ``maux > max(aux)``; aux upload, aux ghost
+    cells and aux boundary conditions then run as for a built-in solver with aux, and a ``CellStartStep`` with
+    ``writes_aux=True`` is seen by the body in the same step.
+
+    No unsplit step (there is no transverse solver), no f-waves, no capacity function, no SharpClaw, no
     3-D, one block; the 2-D step always runs as two passes."""
 
     MAX_PARAMS = 8
+    MAX_PLANES = 8
 
-    def __init__(self, body, meqn, mwaves, ndim, params=(), preamble="", name="user"):
+    def __init__(self, body, meqn, mwaves, ndim, params=(), preamble="", name="user", aux=()):
         RiemannSolver.__init__(self, name, PCL_RP_CELL, int(ndim), int(meqn), int(mwaves), ())
         if not 1 <= self.meqn <= 8 or not 1 <= self.mwaves <= 8:
             raise ValueError("CellRiemann: 1 <= meqn <= 8 and 1 <= mwaves <= 8, got meqn=%d mwaves=%d" % (self.meqn, self.mwaves))
         if self.ndim not in (1, 2):
             raise ValueError("CellRiemann: ndim must be 1 or 2 (the classic 1-D and dimension-split 2-D sweeps), got %d" % self.ndim)
+        self.aux = tuple(int(k) for k in aux)
+        if any(k < 0 for k in self.aux):
+            raise ValueError("CellRiemann: aux lists 0-based components of state.aux, got a negative index in %r" % (self.aux,))
+        if len(set(self.aux)) != len(self.aux):
+            raise ValueError("CellRiemann: aux lists a component twice: %r" % (self.aux,))
+        if self.aux and self.meqn + len(self.aux) > self.MAX_PLANES:
+            raise ValueError("CellRiemann: meqn + len(aux) = %d, the sweep's tile holds at most %d planes (q components and "
+                             "listed aux components)" % (self.meqn + len(self.aux), self.MAX_PLANES))
         self.body = str(body)
         self.preamble = str(preamble)
         self.params = params
@@ -123,13 +146,18 @@ class CellRiemann(RiemannSolver):
         from . import _lib
         if math not in ('exact', 'fast', 'strict'):
             raise Exception("math must be 'exact', 'fast' or 'strict'")
-        key = (self.meqn, self.mwaves, self.ndim, math, self.body, self.preamble)
+        key = (self.meqn, self.mwaves, self.ndim, math, self.body, self.preamble, self.aux)
         if self._rp is not None and self._key == key:
             return self
         rp, size = ctypes.c_void_p(), ctypes.c_long(0)
-        _lib.check(_lib.lib().pcl_cellrp_compile(self.body.encode(), self.preamble.encode(), self.meqn, self.mwaves, self.ndim,
-                                                 {'exact': 0, 'fast': 1, 'strict': 2}[math], ctypes.byref(rp),
-                                                 ctypes.byref(size)))
+        mode = {'exact': 0, 'fast': 1, 'strict': 2}[math]
+        if self.aux:
+            _lib.check(_lib.lib().pcl_cellrp_compile_aux(self.body.encode(), self.preamble.encode(), self.meqn, self.mwaves,
+                                                         self.ndim, mode, (ctypes.c_int * len(self.aux))(*self.aux),
+                                                         len(self.aux), ctypes.byref(rp), ctypes.byref(size)))
+        else:
+            _lib.check(_lib.lib().pcl_cellrp_compile(self.body.encode(), self.preamble.encode(), self.meqn, self.mwaves,
+                                                     self.ndim, mode, ctypes.byref(rp), ctypes.byref(size)))
         self.release()
         self._rp, self._key, self.code_size = rp, key, int(size.value)
         return self

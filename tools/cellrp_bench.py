@@ -11,9 +11,14 @@ step.  PCL_TUNE_FUSED_STEP is read once per process, so every measurement is a c
 of a, b, c in turn.  A child sets the problem up, takes `--warmup` steps and times `--steps` calls of step_hyperbolic at
 a fixed dt with device events, on two states: "pulse", the app's initial condition (most of the box is at rest), and
 "dense", the same with noise on every component of every cell.  Prints one JSON line with median (min - max) ms per
-step, and the hiprtc compile time of the user solver as the children saw it; needs a GPU.
+step, and the hiprtc compile time of the user solver as the children saw it (one progress line per child goes to
+stderr); needs a GPU.
 
-  python tools/cellrp_bench.py [--n 4096] [--steps 20] [--warmup 3] [--reps 7] [--out FILE]
+--aux measures the same three ways on the problem with cell-wise coefficients instead: vc_acoustics_2d in a layered
+medium (problems.vc_acoustics2D) against its restatement as a CellRiemann that reads aux=(0, 1)
+(problems.VC_ACOUSTICS_2D_RP).  The sweeps then stage two aux planes next to q.
+
+  python tools/cellrp_bench.py [--aux] [--n 4096] [--steps 20] [--warmup 3] [--reps 7] [--out FILE]
 """
 import argparse
 import ctypes
@@ -38,19 +43,23 @@ def child(args):
     L = _lib.lib()
     if L.pcl_device_count() < 1:
         raise SystemExit("cellrp_bench: no HIP device (nothing here can be measured without one)")
-    claw = problems.acoustics2D(pyclaw, mx=args.n, my=args.n, run=False, math=args.math)
+    if args.aux:
+        claw = problems.vc_acoustics2D(pyclaw, mx=args.n, my=args.n, run=False, math=args.math, user_rp=args.child == "user")
+    else:
+        claw = problems.acoustics2D(pyclaw, mx=args.n, my=args.n, run=False, math=args.math)
     solver, solution = claw.solver, claw.solution
     state = solution.state
     res = {"variant": args.child}
     if args.child == "user":
-        g = state.aux_global
-        solver.rp = pyclaw.CellRiemann(problems.ACOUSTICS_2D_RP, 3, 2, 2, params=[g['rho'], g['bulk'], g['cc'], g['zz']])
+        if not args.aux:
+            g = state.aux_global
+            solver.rp = pyclaw.CellRiemann(problems.ACOUSTICS_2D_RP, 3, 2, 2, params=[g['rho'], g['bulk'], g['cc'], g['zz']])
         t0 = time.perf_counter()
         solver.rp.compile(args.math)
         res["compile_s"] = time.perf_counter() - t0
     solver.setup(solution)
     solver.dt_variable = False
-    solver.dt = 0.45 * min(state.grid.d) / state.aux_global['cc']
+    solver.dt = 0.45 * min(state.grid.d) / (float(state.aux[1].max()) if args.aux else state.aux_global['cc'])
     q_pulse = state.q.copy('F')
     rng = np.random.default_rng(7)
     q_dense = q_pulse + 0.01 * rng.standard_normal(q_pulse.shape)
@@ -82,6 +91,7 @@ def main():
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--math", default="exact")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--aux", action="store_true", help="the variable-coefficient problem: vc_acoustics_2d against CellRiemann(aux=(0, 1))")
     ap.add_argument("--child", default=None, choices=VARIANTS)
     args = ap.parse_args()
     if args.child:
@@ -95,16 +105,18 @@ def main():
             if v == "two_pass":
                 env["PCL_TUNE_FUSED_STEP"] = "0"
             cmd = [sys.executable, os.path.abspath(__file__), "--child", v, "--n", str(args.n), "--steps", str(args.steps),
-                   "--warmup", str(args.warmup), "--math", args.math]
+                   "--warmup", str(args.warmup), "--math", args.math] + (["--aux"] if args.aux else [])
             out = subprocess.run(cmd, env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=300)
             lines = [l for l in out.stdout.splitlines() if l.startswith("CELLRP_CHILD ")]
             if out.returncode != 0 or not lines:
                 raise SystemExit("cellrp_bench: the %s run failed (exit %d):\n%s" % (v, out.returncode, out.stdout[-2000:]))
             runs[v].append(json.loads(lines[-1][len("CELLRP_CHILD "):]))
+            print("round %d %s: pulse %.4f ms, dense %.4f ms" % (len(runs[v]), v, runs[v][-1]["pulse_ms"], runs[v][-1]["dense_ms"]),
+                  file=sys.stderr, flush=True)
 
     def spread(vals):
         return {"median": float(np.median(vals)), "min": min(vals), "max": max(vals), "all": vals}
-    res = {"tool": "cellrp_bench", "n": args.n, "math": args.math, "steps": args.steps, "warmup": args.warmup, "reps": args.reps,
+    res = {"tool": "cellrp_bench" + (" --aux" if args.aux else ""), "n": args.n, "math": args.math, "steps": args.steps, "warmup": args.warmup, "reps": args.reps,
            "compile_s": spread([r["compile_s"] for r in runs["user"]]), "forms": {v: runs[v][-1]["forms"] for v in VARIANTS},
            "states": {}}
     for name in ("pulse", "dense"):

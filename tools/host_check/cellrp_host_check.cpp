@@ -3,6 +3,8 @@
 // is real (libhiprtc needs no device): program text, named headers, name expressions, lowered names and the shared cache
 // all run under the sanitizer.  The shim loads no module, so pcl_cellrp_attach ends in PCL_EHIP behind its host-only
 // checks and a PCL_RP_CELL handle stays without a solver: every step is refused, which is the path checked here.
+// The second half does the same for solvers that read aux (pcl_cellrp_compile_aux, pcl_cellrp_aux): the list in the
+// cache key, every refusal of a list, and attach against a solver whose maux does not reach it.
 // Exit status 0 and no sanitizer report: passed.  tools/host_check/run.sh
 #include <cstdio>
 #include <cstdlib>
@@ -105,6 +107,88 @@ int main() {
     CHECK(pcl_cellrp_release(nullptr));
     CHECK(pcl_cellrp_compile(kBurgers, "", 1, 1, 2, PCL_MATH_EXACT, &b, nullptr));      // released, not forgotten
     EXPECT(b == a);
+
+    // ---- solvers that read aux: pcl_cellrp_compile_aux, pcl_cellrp_aux ----
+    static const char *kVcAdvection =
+        "const double vel = ixy == 1 ? auxr[0] : auxr[1];\n"
+        "wave[0][0] = qr[0] - ql[0];\n"
+        "s[0] = vel;\n"
+        "amdq[0] = dmin(vel, 0.0) * wave[0][0];\n"
+        "apdq[0] = dmax(vel, 0.0) * wave[0][0];\n";
+    pcl_cellrp *x01 = nullptr, *x01b = nullptr, *x10 = nullptr, *x31 = nullptr, *plain = nullptr;
+    const int l01[2] = {0, 1}, l10[2] = {1, 0}, l31[2] = {3, 1}, neg[2] = {0, -1}, twice[3] = {2, 0, 2};
+    const int many[8] = {0, 1, 2, 3, 4, 5, 6, 7};
+    CHECK(pcl_cellfn_stats(&n0, &h0));
+    // every new refusal, in front of the compiler
+    EXPECT(pcl_cellrp_compile_aux(kVcAdvection, "", 1, 1, 2, PCL_MATH_EXACT, l01, -1, &bad, nullptr) == PCL_EINVAL && !bad);
+    EXPECT(pcl_cellrp_compile_aux(kVcAdvection, "", 1, 1, 2, PCL_MATH_EXACT, nullptr, 2, &bad, nullptr) == PCL_EINVAL && !bad);
+    EXPECT(pcl_cellrp_compile_aux(kVcAdvection, "", 1, 1, 2, PCL_MATH_EXACT, neg, 2, &bad, nullptr) == PCL_EINVAL && !bad);
+    EXPECT(strstr(pcl_last_error(), "negative") != nullptr);
+    EXPECT(pcl_cellrp_compile_aux(kVcAdvection, "", 1, 1, 2, PCL_MATH_EXACT, twice, 3, &bad, nullptr) == PCL_EINVAL && !bad);
+    EXPECT(strstr(pcl_last_error(), "twice") != nullptr);
+    EXPECT(pcl_cellrp_compile_aux(kVcAdvection, "", 1, 1, 2, PCL_MATH_EXACT, many, 8, &bad, nullptr) == PCL_EINVAL && !bad);
+    EXPECT(strstr(pcl_last_error(), "meqn + naux = 9") != nullptr && strstr(pcl_last_error(), "at most 8 planes") != nullptr);
+    EXPECT(pcl_cellrp_compile_aux(kVcAdvection, "", 3, 1, 2, PCL_MATH_EXACT, many, 6, &bad, nullptr) == PCL_EINVAL && !bad);
+    CHECK(pcl_cellfn_stats(&n, &h));
+    EXPECT(n == n0 && h == h0);
+    // compile with a list; hit and miss on the list and on its order; the list comes back
+    CHECK(pcl_cellrp_compile_aux(kVcAdvection, "", 1, 1, 2, PCL_MATH_EXACT, l01, 2, &x01, &size));
+    EXPECT(x01 && size > 0);
+    CHECK(pcl_cellrp_compile_aux(kVcAdvection, nullptr, 1, 1, 2, PCL_MATH_EXACT, l01, 2, &x01b, nullptr));
+    EXPECT(x01b == x01);
+    CHECK(pcl_cellrp_compile_aux(kVcAdvection, "", 1, 1, 2, PCL_MATH_EXACT, l10, 2, &x10, nullptr));
+    CHECK(pcl_cellrp_compile_aux(kVcAdvection, "", 1, 1, 2, PCL_MATH_STRICT, l31, 2, &x31, nullptr));
+    EXPECT(x10 && x31 && x10 != x01 && x31 != x01 && x31 != x10);
+    CHECK(pcl_cellfn_stats(&n, &h));
+    EXPECT(n == n0 + 3 && h == h0 + 1);
+    int naux = -1, list[8] = {-1, -1, -1, -1, -1, -1, -1, -1};
+    CHECK(pcl_cellrp_aux(x31, &naux, list));
+    EXPECT(naux == 2 && list[0] == 3 && list[1] == 1 && list[2] == -1);
+    CHECK(pcl_cellrp_aux(x10, &naux, nullptr));
+    EXPECT(naux == 2);
+    EXPECT(pcl_cellrp_aux(nullptr, &naux, list) == PCL_EINVAL);
+    EXPECT(pcl_cellrp_aux(x01, nullptr, list) == PCL_EINVAL);
+    // an empty list is pcl_cellrp_compile: the handle of the plain compile of this text
+    CHECK(pcl_cellrp_compile_aux(kBurgers, "", 1, 1, 2, PCL_MATH_EXACT, nullptr, 0, &plain, nullptr));
+    EXPECT(plain == a);
+    CHECK(pcl_cellrp_aux(plain, &naux, list));
+    EXPECT(naux == 0 && list[0] == 3);
+    // a body that names auxl without a list does not compile
+    EXPECT(pcl_cellrp_compile("s[0] = 1.0;\ns[0] = auxl[0];\n", "", 1, 1, 1, PCL_MATH_EXACT, &bad, nullptr) == PCL_EINVAL && !bad);
+    EXPECT(strstr(pcl_last_error(), "riemann:2") != nullptr);
+    CHECK(pcl_cellrp_check(x01, 1, 1, 2, PCL_MATH_EXACT));
+    EXPECT(pcl_cellrp_check(x31, 1, 1, 2, PCL_MATH_EXACT) == PCL_EINVAL);
+
+    // a PCL_RP_CELL handle with two aux components
+    cfg.maux = 2;
+    cfg.method[6] = 2;
+    pcl_config capa = cfg;
+    capa.method[5] = 1;
+    EXPECT(pcl_create(&capa, &s) == PCL_EINVAL);            // a capacity function is still refused
+    s = nullptr;
+    CHECK(pcl_create(&cfg, &s));
+    CHECK(pcl_put_q(s, q.data(), 0));
+    const size_t ncell = (size_t)(cfg.n[0] + 2 * cfg.mbc) * (cfg.n[1] + 2 * cfg.mbc);
+    std::vector<double> aux(2 * ncell, 0.5);
+    EXPECT(pcl_cellrp_attach(s, x31) == PCL_EINVAL);        // math strict, and component 3 of 2
+    pcl_cellrp *y31 = nullptr;
+    CHECK(pcl_cellrp_compile_aux(kVcAdvection, "", 1, 1, 2, PCL_MATH_EXACT, l31, 2, &y31, nullptr));
+    EXPECT(pcl_cellrp_attach(s, y31) == PCL_EINVAL);        // maux too small: refused before the module load
+    EXPECT(strstr(pcl_last_error(), "aux component 3") != nullptr && strstr(pcl_last_error(), "maux = 2") != nullptr);
+    EXPECT(pcl_step_hyperbolic(s, 0.01, &cfl) == PCL_ESTATE);
+    CHECK(pcl_put_aux(s, aux.data()));
+    EXPECT(pcl_cellrp_attach(s, x10) == PCL_EHIP);          // host checks passed; the shim loads no module
+    EXPECT(pcl_step_hyperbolic(s, 0.01, &cfl) == PCL_ESTATE);
+    EXPECT(pcl_sweep(s, 1, 0.01, &cfl) == PCL_ESTATE);
+    EXPECT(pcl_comm_init(s, 1, 0, uid, nbr) == PCL_EINVAL);
+    pcl_destroy(s);
+    CHECK(pcl_cellrp_release(x01));
+    CHECK(pcl_cellrp_release(x01b));
+    EXPECT(pcl_cellrp_release(x01) == PCL_EINVAL);
+    CHECK(pcl_cellrp_release(x10));
+    CHECK(pcl_cellrp_release(x31));
+    CHECK(pcl_cellrp_release(y31));
+    CHECK(pcl_cellrp_release(plain));
     printf("cellrp_host_check: ok\n");
     return 0;
 }
