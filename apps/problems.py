@@ -220,6 +220,149 @@ wave[1][0] = a2 * zi;   wave[1][1] = a2; s[1] = auxr[1];
 for (int m = 0; m < 2; m++) { amdq[m] = s[0] * wave[0][m]; apdq[m] = s[1] * wave[1][m]; }
 """
 
+# Transverse Riemann solvers as bodies for pyclaw.CellRiemann(..., transverse=...): Clawpack's rpt2 for one interface, for
+# the unsplit step.  ixy is the direction of the NORMAL solve, asdq the fluctuation to split, bmasdq / bpasdq (zero on
+# entry) its down- and up-going parts.  Without aux the body sees ql, qr; with aux q1, aux1 (the cell asdq belongs to)
+# and aux_below, aux_above.  The first five restate the built-in transverse solvers of rp.hpp in their operation order.
+
+# p = u, v: the velocity across the sweep
+ADVECTION_2D_RPT = """
+const double stran = p[2 - ixy];
+bmasdq[0] = dmin(stran, 0.0) * asdq[0];
+bpasdq[0] = dmax(stran, 0.0) * asdq[0];
+"""
+
+# (the normal velocity's components stay the zeros they are on entry)
+ACOUSTICS_2D_RPT = """
+constexpr int mv = (ixy == 1) ? 2 : 1;
+const double cc = p[2], zz = p[3];
+const double a1 = (-asdq[0] + zz * asdq[mv]) / (2.0 * zz);
+const double a2 = (asdq[0] + zz * asdq[mv]) / (2.0 * zz);
+bmasdq[0] = cc * a1 * zz; bmasdq[mv] = -cc * a1;
+bpasdq[0] = cc * a2 * zz; bpasdq[mv] = cc * a2;
+"""
+
+# aux = (0, 1) = (Z, c): the down-going part enters the slice below with that slice's impedance and sound speed, the
+# up-going part the slice above
+VC_ACOUSTICS_2D_RPT = """
+constexpr int mv = (ixy == 1) ? 2 : 1;
+const double zm = aux_below[0], zz = aux1[0], zp = aux_above[0], cm = aux_below[1], cp = aux_above[1];
+const double a1 = fdiv_ieee(-asdq[0] + asdq[mv] * zz, zm + zz);
+const double a2 = fdiv_ieee(asdq[0] + asdq[mv] * zz, zz + zp);
+bmasdq[0] = cm * a1 * zm; bmasdq[mv] = -cm * a1;
+bpasdq[0] = cp * a2 * zp; bpasdq[mv] = cp * a2;
+"""
+
+# aux = (0, 1): u at the left edge, v at the bottom edge.  Down-going: the transverse velocity at the cell's own lower
+# edge; up-going: at the lower edge of the cell above
+VC_ADVECTION_2D_RPT = """
+const double own = ixy == 1 ? aux1[1] : aux1[0], above = ixy == 1 ? aux_above[1] : aux_above[0];
+bmasdq[0] = dmin(own, 0.0) * asdq[0];
+bpasdq[0] = dmax(above, 0.0) * asdq[0];
+"""
+
+# 2-D shallow water q = (h, hu, hv), p = g: Roe solver with the Harten-Hyman entropy fix (Shallow2D of rp.hpp) and its
+# transverse solver, which splits with the Roe average of the interface's two cells: the one that needs ql and qr
+SHALLOW_2D_RP = """
+constexpr int mu = (ixy == 1) ? 1 : 2, mv = (ixy == 1) ? 2 : 1;
+const double g = p[0];
+const double rh = (ql[0] + qr[0]) * 0.5;
+const double hsl = dsqrt(ql[0]), hsr = dsqrt(qr[0]), hsq2 = hsl + hsr;
+const double ru = (ql[mu] / hsl + qr[mu] / hsr) / hsq2;
+const double rv = (ql[mv] / hsl + qr[mv] / hsr) / hsq2;
+const double ra = dsqrt(g * rh);
+const double d1 = qr[0] - ql[0], d2 = qr[mu] - ql[mu], d3 = qr[mv] - ql[mv];
+const double a1 = ((ru + ra) * d1 - d2) * (0.5 / ra);
+const double a2 = -rv * d1 + d3;
+const double a3 = (-(ru - ra) * d1 + d2) * (0.5 / ra);
+wave[0][0] = a1;  wave[0][mu] = a1 * (ru - ra); wave[0][mv] = a1 * rv; s[0] = ru - ra;
+wave[1][0] = 0.0; wave[1][mu] = 0.0;            wave[1][mv] = a2;      s[1] = ru;
+wave[2][0] = a3;  wave[2][mu] = a3 * (ru + ra); wave[2][mv] = a3 * rv; s[2] = ru + ra;
+const double hl = ql[0], hr = qr[0];
+const double s0 = ql[mu] / hl - dsqrt(g * hl);
+const bool all_right = (s0 >= 0.0) && (s[0] > 0.0);
+{
+    const double h1 = hl + wave[0][0], hu1 = ql[mu] + wave[0][mu];
+    const double s1 = hu1 / h1 - dsqrt(g * h1);
+    double sfract;
+    if (s0 < 0.0 && s1 > 0.0) sfract = s0 * (s1 - s[0]) / (s1 - s0);
+    else if (s[0] < 0.0) sfract = s[0];
+    else sfract = 0.0;
+    for (int m = 0; m < 3; m++) amdq[m] = sfract * wave[0][m];
+}
+if (!(s[1] >= 0.0)) {
+    for (int m = 0; m < 3; m++) amdq[m] = amdq[m] + s[1] * wave[1][m];
+    const double s03 = qr[mu] / hr + dsqrt(g * hr);
+    const double h3 = hr - wave[2][0], hu3 = qr[mu] - wave[2][mu];
+    const double s3 = hu3 / h3 + dsqrt(g * h3);
+    double sfract = 0.0;
+    bool add = true;
+    if (s3 < 0.0 && s03 > 0.0) sfract = s3 * (s03 - s[2]) / (s03 - s3);
+    else if (s[2] < 0.0) sfract = s[2];
+    else add = false;
+    if (add) for (int m = 0; m < 3; m++) amdq[m] = amdq[m] + sfract * wave[2][m];
+}
+if (all_right) for (int m = 0; m < 3; m++) amdq[m] = 0.0;
+for (int m = 0; m < 3; m++) {
+    double df = s[0] * wave[0][m];
+    df = df + s[1] * wave[1][m];
+    df = df + s[2] * wave[2][m];
+    apdq[m] = df - amdq[m];
+}
+"""
+
+SHALLOW_2D_RPT = """
+constexpr int mu = (ixy == 1) ? 1 : 2, mv = (ixy == 1) ? 2 : 1;
+const double rh = (ql[0] + qr[0]) * 0.5;
+const double hsl = dsqrt(ql[0]), hsr = dsqrt(qr[0]), hsq2 = hsl + hsr;
+const double ru = (ql[mu] / hsl + qr[mu] / hsr) / hsq2;
+const double rv = (ql[mv] / hsl + qr[mv] / hsr) / hsq2;
+const double ra = dsqrt(p[0] * rh);
+const double a1 = (0.5 / ra) * ((rv + ra) * asdq[0] - asdq[mv]);
+const double a2 = asdq[mu] - ru * asdq[0];
+const double a3 = (0.5 / ra) * (-(rv - ra) * asdq[0] + asdq[mv]);
+double wb[3][3], sb[3];
+wb[0][0] = a1;  wb[0][mu] = a1 * ru; wb[0][mv] = a1 * (rv - ra); sb[0] = rv - ra;
+wb[1][0] = 0.0; wb[1][mu] = a2;      wb[1][mv] = 0.0;            sb[1] = rv;
+wb[2][0] = a3;  wb[2][mu] = a3 * ru; wb[2][mv] = a3 * (rv + ra); sb[2] = rv + ra;
+for (int m = 0; m < 3; m++) {
+    double m_ = 0.0, p_ = 0.0;
+    for (int mw = 0; mw < 3; mw++) {
+        m_ = m_ + dmin(sb[mw], 0.0) * wb[mw][m];
+        p_ = p_ + dmax(sb[mw], 0.0) * wb[mw][m];
+    }
+    bmasdq[m] = m_; bpasdq[m] = p_;
+}
+"""
+
+# MEQN independent advected scalars, mwaves = meqn <= 8: wave k carries component k alone, x velocity p[k], y velocity
+# -p[k] / 2 (an exact scaling, so each component is advection_2d with those two velocities bit for bit).  The largest
+# systems a CellRiemann takes: meqn = 7 and 8 run the unsplit kernels with 12 slices per workgroup.
+SCALARS_2D_RP = """
+for (int k = 0; k < MEQN; k++) {
+    const double vel = ixy == 1 ? p[k] : -0.5 * p[k];
+    wave[k][k] = qr[k] - ql[k];
+    s[k] = vel;
+    amdq[k] = dmin(vel, 0.0) * wave[k][k];
+    apdq[k] = dmax(vel, 0.0) * wave[k][k];
+}
+"""
+
+SCALARS_2D_RPT = """
+for (int k = 0; k < MEQN; k++) {
+    const double stran = ixy == 1 ? -0.5 * p[k] : p[k];
+    bmasdq[k] = dmin(stran, 0.0) * asdq[k];
+    bpasdq[k] = dmax(stran, 0.0) * asdq[k];
+}
+"""
+
+# scalar 2-D Burgers (BURGERS_2D_RP): the transverse speed is the average of the interface's two cells
+BURGERS_2D_RPT = """
+const double sb = 0.5 * (ql[0] + qr[0]);
+bmasdq[0] = dmin(sb, 0.0) * asdq[0];
+bpasdq[0] = dmax(sb, 0.0) * asdq[0];
+"""
+
 
 def shockbubble(pyclaw, mx=160, my=40, tfinal=0.2, device_callbacks=False, with_src=True,
                 dim_split=True, order_trans=2, dt_initial=0.005, nout=1, run=True, math='exact',
@@ -300,8 +443,9 @@ def ac2d_qinit(state, width=0.2):
 
 
 def acoustics2D(pyclaw, mx=100, my=100, tfinal=0.12, nout=10, dim_split=1, run=True, math='exact',
-                solver_type='classic', lim_type=2, time_integrator='SSP104', weno_order=5):
-    """test/acoustics/2d/homogeneous/acoustics.py:19-86 (classic or sharpclaw)."""
+                solver_type='classic', lim_type=2, time_integrator='SSP104', weno_order=5, user_rp=False):
+    """test/acoustics/2d/homogeneous/acoustics.py:19-86 (classic or sharpclaw).  user_rp=True (classic): the same solver
+    as the bodies ACOUSTICS_2D_RP / ACOUSTICS_2D_RPT of a pyclaw.CellRiemann, dimension-split or unsplit."""
     if solver_type == 'classic':
         solver = pyclaw.ClawSolver2D()
     else:
@@ -333,6 +477,10 @@ def acoustics2D(pyclaw, mx=100, my=100, tfinal=0.12, nout=10, dim_split=1, run=T
     state.aux_global['zz'] = zz
     state.aux_global['cc'] = cc
     ac2d_qinit(state)
+    if user_rp:
+        # (the transverse body only where the unsplit step asks for it: the split run compiles the two sweeps alone)
+        solver.rp = pyclaw.CellRiemann(ACOUSTICS_2D_RP, 3, 2, 2, params=[rho, bulk, cc, zz], name="acoustics_2d_user",
+                                       transverse=None if dim_split else ACOUSTICS_2D_RPT)
     initial_solution = pyclaw.Solution(state)
     solver.dt_initial = np.min(grid.d) / state.aux_global['cc'] * solver.cfl_desired
     claw = pyclaw.Controller()
@@ -347,11 +495,12 @@ def acoustics2D(pyclaw, mx=100, my=100, tfinal=0.12, nout=10, dim_split=1, run=T
     return claw
 
 
-def vc_acoustics2D(pyclaw, mx=100, my=100, tfinal=0.12, nout=10, run=True, math='exact', user_rp=False):
+def vc_acoustics2D(pyclaw, mx=100, my=100, tfinal=0.12, nout=10, run=True, math='exact', user_rp=False, dim_split=1):
     """The pulse of acoustics2D in a layered medium: impedance and sound speed per cell in aux(1), aux(2) -- four layers
-    in x with the sound speeds 2, 1.5, 1, 1.25 and an impedance that also varies smoothly in y.  Dimension-split, with
-    rp_vc_acoustics_2d or, user_rp=True, the same solver as the body VC_ACOUSTICS_2D_RP of a pyclaw.CellRiemann."""
-    claw = acoustics2D(pyclaw, mx=mx, my=my, tfinal=tfinal, nout=nout, run=False, math=math)
+    in x with the sound speeds 2, 1.5, 1, 1.25 and an impedance that also varies smoothly in y.  Dimension-split or
+    unsplit (dim_split=0), with rp_vc_acoustics_2d or, user_rp=True, the same solver as the bodies VC_ACOUSTICS_2D_RP /
+    VC_ACOUSTICS_2D_RPT of a pyclaw.CellRiemann."""
+    claw = acoustics2D(pyclaw, mx=mx, my=my, tfinal=tfinal, nout=nout, run=False, math=math, dim_split=dim_split)
     old = claw.solution.state
     state = pyclaw.State(old.grid, 3, 2)
     state.q[...] = old.q
@@ -362,7 +511,8 @@ def vc_acoustics2D(pyclaw, mx=100, my=100, tfinal=0.12, nout=10, run=True, math=
     state.aux[1] = cc
     claw.solution = pyclaw.Solution(state)
     solver = claw.solver
-    solver.rp = (pyclaw.CellRiemann(VC_ACOUSTICS_2D_RP, 3, 2, 2, aux=(0, 1), name="vc_acoustics_2d_user") if user_rp
+    solver.rp = (pyclaw.CellRiemann(VC_ACOUSTICS_2D_RP, 3, 2, 2, aux=(0, 1), name="vc_acoustics_2d_user",
+                                    transverse=None if dim_split else VC_ACOUSTICS_2D_RPT) if user_rp
                  else pyclaw.riemann.rp_vc_acoustics_2d)
     for k in range(2):
         solver.aux_bc_lower[k] = solver.aux_bc_upper[k] = pyclaw.BC.outflow

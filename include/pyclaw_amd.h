@@ -405,6 +405,34 @@ int pcl_cellrp_compile(const char *body, const char *preamble, int meqn, int mwa
  * the same program, key and handle.  Host-only. */
 int pcl_cellrp_compile_aux(const char *body, const char *preamble, int meqn, int mwaves, int ndim, int math, const int *aux_index,
                            int naux, pcl_cellrp **out, long *code_size);
+/* The same with a TRANSVERSE body (Clawpack's rpt2 for one interface), which opens the unsplit 2-D step (method[2] >= 0)
+ * to the solver: the code object then also holds the x and y phases of that step (csrc/classic.hpp: unsplit_x_kernel,
+ * unsplit_y_kernel) around the two bodies.  Without an aux list the transverse body sees
+ *     ql[MEQN], qr[MEQN]   the cells left and right of the interface whose fluctuation is split (const) -- the same pair
+ *                          for A-dq and for A+dq of one interface; there is no imp
+ *     asdq[MEQN], p[8]     the fluctuation and the parameters (const)
+ *     ixy                  compile-time constant: the direction of the NORMAL solve; the split is across it
+ *     bmasdq[MEQN], bpasdq[MEQN]   the down- and up-going parts, zero on entry
+ * and with one
+ *     q1[MEQN], aux1[NAUX]             the cell the fluctuation belongs to: left of the interface for A-dq, right for A+dq
+ *     aux_below[NAUX], aux_above[NAUX] the listed components of its neighbours at the lower / upper transverse index
+ * next to asdq, p, ixy and the results (a transverse body that needs both cells AND aux is not served).
+ * Contract: for asdq all zero the results are zero -- a wavefront without a jump never calls the body.
+ * Diagnostics: "transverse:<n>:...".  transverse != NULL needs ndim == 2, else PCL_EINVAL; the text is part of the cache
+ * key; transverse == NULL is pcl_cellrp_compile_aux itself: the same program, key and handle.  The unsplit kernels take
+ * 16 slices per workgroup for meqn <= 6 and 12 above (their static LDS against 160 KB).  Host-only. */
+int pcl_cellrp_compile_t(const char *body, const char *transverse, const char *preamble, int meqn, int mwaves, int ndim, int math,
+                         const int *aux_index, int naux, pcl_cellrp **out, long *code_size);
+/* Host-only: *has = 1 if the live handle was compiled with a transverse body, and then *slices (may be null) = the slices
+ * per workgroup of its unsplit kernels; else *has = 0, *slices = 0. */
+int pcl_cellrp_transverse(const pcl_cellrp *r, int *has, int *slices);
+/* pcl_create of a PCL_RP_CELL solver and pcl_cellrp_attach in one call, so that the configuration is checked against what
+ * the handle can do: method[2] >= 0 in 2-D (the unsplit step) is accepted if and only if the handle has a transverse
+ * body, else PCL_EINVAL.  Every other refusal is pcl_create's and pcl_cellrp_attach's.  All argument checks are host-only
+ * and come before the device is touched (no device, acceptable arguments: PCL_ENODEVICE).  pcl_create itself goes on
+ * refusing method[2] >= 0 for PCL_RP_CELL: it cannot know the handle.  The unsplit step of such a solver runs whole
+ * blocks in wave form without a capacity function, the y phase always in its tile form. */
+int pcl_create_cellrp(const pcl_config *cfg, pcl_cellrp *r, pcl_solver **out);
 /* Host-only: the list a live handle was compiled with; aux_index (may be null) gets *naux <= 8 entries. */
 int pcl_cellrp_aux(const pcl_cellrp *r, int *naux, int *aux_index);
 int pcl_cellrp_release(pcl_cellrp *r);
@@ -413,7 +441,9 @@ int pcl_cellrp_check(const pcl_cellrp *r, int meqn, int mwaves, int ndim, int ma
 /* Gives a PCL_RP_CELL solver its Riemann solver: the module is loaded into the handle's device (one attached at a time;
  * pcl_destroy unloads it).  Until then every step of such a solver is refused with PCL_ESTATE.  A handle whose largest
  * listed aux component is >= cfg.maux is refused (PCL_EINVAL, both numbers in the message) before anything is loaded, and
- * the sweeps of a solver that reads aux are refused (PCL_EINVAL) until pcl_put_aux has uploaded the array. */
+ * the sweeps of a solver that reads aux are refused (PCL_EINVAL) until pcl_put_aux has uploaded the array.  A solver
+ * created unsplit (pcl_create_cellrp) refuses a handle without a transverse body (PCL_EINVAL); the module attached before
+ * stays attached. */
 int pcl_cellrp_attach(pcl_solver *s, pcl_cellrp *r);
 /* The body's p[0..nparams-1] from the next sweep on (nparams <= 8; the rest are zero): they travel by value with every
  * launch, so changing them compiles nothing. */

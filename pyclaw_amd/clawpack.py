@@ -270,11 +270,16 @@ class ClawSolver(Solver):
         cfg.math = {'exact': 0, 'fast': 1, 'strict': 2}[self.math]
         import ctypes
         h = ctypes.c_void_p()
-        _lib.check(_lib.lib().pcl_create(ctypes.byref(cfg), ctypes.byref(h)))
-        self._h = h
+        if user_rp and self.ndim == 2 and not self.dim_split:
+            # the unsplit step: the library checks the configuration against the handle (its transverse body) and attaches
+            _lib.check(_lib.lib().pcl_create_cellrp(ctypes.byref(cfg), rp._rp, ctypes.byref(h)))
+            self._h = h
+        else:
+            _lib.check(_lib.lib().pcl_create(ctypes.byref(cfg), ctypes.byref(h)))
+            self._h = h
+            if user_rp:
+                _lib.check(_lib.lib().pcl_cellrp_attach(self._h, rp._rp))
         self._user_rp, self._user_rp_sent = (rp, np.array(params)) if user_rp else (None, None)
-        if user_rp:
-            _lib.check(_lib.lib().pcl_cellrp_attach(self._h, rp._rp))
 
         self.allocate_bc_arrays(state)
         self._setup_halo(state)
@@ -291,9 +296,10 @@ class ClawSolver(Solver):
         if self.ndim == 3:
             raise NotImplementedError("CellRiemann: the user-written solver is compiled into the 1-D and 2-D sweep kernels; "
                                       "ClawSolver3D has no sweep for it")
-        if self.ndim == 2 and not self.dim_split:
+        if self.ndim == 2 and not self.dim_split and not self.rp.has_transverse:
             raise NotImplementedError("CellRiemann: dim_split = False needs a transverse Riemann solver (rpt2); the body "
-                                      "is the normal solver only, so the 2-D step is the dimension-split one")
+                                      "is the normal solver only, so the 2-D step is the dimension-split one "
+                                      "(CellRiemann(..., transverse=...) gives it one)")
         if self.fwave:
             raise NotImplementedError("CellRiemann: fwave = True is not served: the body returns waves, and the f-wave "
                                       "form of the sweep has no user-written instantiation")

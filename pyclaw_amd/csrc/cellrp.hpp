@@ -48,6 +48,16 @@
 // cellrp_max_planes() = 65536 / (8 * max PLANE) -- 8, set by the 1024-double y tile; refused on the host with that sum
 // and by the static_assert below.  The list is part of the cache key; without one the program text, the key and the
 // handle are those of the first wrapper.
+//
+// A second, optional text is the TRANSVERSE solver (Clawpack's rpt2; pcl_cellrp_compile_t, CellRiemann(transverse=...)):
+// two more members of the same struct (kCellrpTrans* below, where the body's interface and contract are written down),
+// and two more name expressions, unsplit_x_kernel<UserRp, false, U, false> and unsplit_y_kernel<UserRp, false, U, false,
+// false> -- the unsplit step (classic.hpp) around the user's two bodies, launched by launch_unsplit (kernels.hip) with
+// the parameters and grids of the built-in solvers.  U, the slices per workgroup, is unsplit_user_slices(meqn)
+// (sweep_args.hpp: the one rule, read here to name the instantiations and by the run-time text to check them); the
+// handle records it and the launcher sizes its grids from the handle.  Always the tile form of the y phase: the marching
+// kernel (its static LDS is 29184 * meqn bytes) stays with the built-in solvers.  Without a transverse text the program
+// text, the key, the handle and the symbols are what they were.
 #pragma once
 #include "cellfn.hpp"
 // generated by the Makefile (embed_headers.py): PCL_RTC_FLAGS_EXACT / _FAST / _STRICT, the flags kernels_<mode>.o is built
@@ -65,6 +75,11 @@ struct pcl_cellrp {
     std::string key;
     std::vector<char> code;     // the code object
     std::string sym[2];         // lowered names: [0] the 1-D step or the x pass, [1] the y pass (2-D)
+    // a transverse body was given (2-D): the unsplit kernels are in the code object too, compiled with `slices` slices per
+    // workgroup (unsplit_user_slices, sweep_args.hpp); sym_u: [0] unsplit_x_kernel, [1] unsplit_y_kernel
+    bool trans = false;
+    int slices = 0;
+    std::string sym_u[2];
 };
 
 namespace pcl {
@@ -116,7 +131,9 @@ static const char *const kCellrpTail = R"PCLSRC(
         double wave[MWAVES][MEQN], amdq[MEQN], apdq[MEQN];
         solve<IXY>(L, R, p, wave, s, amdq, apdq);
     }
-};
+)PCLSRC";
+
+static const char *const kCellrpClose = R"PCLSRC(};
 static_assert(sizeof(double) * UserRp::MEQN * TileShape<2>::PLANE <= 65536 && sizeof(double) * UserRp::MEQN * TileShape<1>::PLANE <= 65536,
               "meqn: the LDS tile of sweep_kernel (classic.hpp) does not fit a workgroup's 64 KB");
 }  // namespace PCL_NS
@@ -170,7 +187,9 @@ static const char *const kCellrpTailAux = R"PCLSRC(
         double wave[MWAVES][MEQN], amdq[MEQN], apdq[MEQN];
         solve<IXY>(L, R, p, wave, s, amdq, apdq);
     }
-};
+)PCLSRC";
+
+static const char *const kCellrpCloseAux = R"PCLSRC(};
 static_assert(sizeof(double) * (UserRp::MEQN + UserRp::NAUX) * TileShape<2>::PLANE <= 65536 &&
                   sizeof(double) * (UserRp::MEQN + UserRp::NAUX) * TileShape<1>::PLANE <= 65536,
               "meqn + naux: the LDS tile of sweep_kernel (classic.hpp) does not fit a workgroup's 64 KB");
@@ -178,35 +197,114 @@ static_assert(sizeof(double) * (UserRp::MEQN + UserRp::NAUX) * TileShape<2>::PLA
 }  // namespace pcl
 )PCLSRC";
 
+// The transverse body (pcl_cellrp_compile_t, 2-D only): the inside of Clawpack's rpt2 for one interface, two more members
+// of the same struct, in front of its end.  Given one, the program also asks for the two unsplit kernels.
+// Without aux, transverse<IXY>(L, R, par, asdq, bm, bp) of lane_core<..., TRANS = true> (classic.hpp); the body sees
+//     const double ql[MEQN], qr[MEQN]     the cells left and right of the interface whose fluctuation is split -- the same
+//                                         pair for A-dq and for A+dq of one interface: there is no imp
+//     const double asdq[MEQN], p[8], ixy  the fluctuation, the parameters, the direction of the NORMAL solve (the split is
+//                                         across it)
+//     double bmasdq[MEQN], bpasdq[MEQN]   the down- and up-going parts, zero on entry
+// With an aux list, transverse_vc<IXY>(c1, auxo, auxb, auxa, par, asdq, bm, bp); the body sees
+//     const double q1[MEQN], aux1[NAUX]   the cell the fluctuation belongs to: left of the interface for A-dq, right of
+//                                         it for A+dq
+//     const double aux_below[NAUX], aux_above[NAUX]
+//                                         the listed components of its neighbours at the lower and the upper transverse
+//                                         index (Clawpack's aux1 / aux3 rows)
+// and asdq, p, ixy, bmasdq, bpasdq as above.  auxt_index is aux_index, so auxo repeats c1.aux and is not passed on; a
+// transverse body that needs both cells AND aux is not served.
+// Contract: for asdq all zero the results are zero.  A jump-free wavefront in the TRANS core sets the slice's pieces to
+// zero and never calls the body (classic.hpp, lane_core: both no-jump branches).
+// Diagnostics: "transverse:<n>:...", the body's own line numbers.
+static const char *const kCellrpTransOpen = R"PCLSRC(
+    template <int ixy>
+    __device__ static __forceinline__ void tbody(const double (&ql)[MEQN], const double (&qr)[MEQN], const double (&p)[8],
+                                                 const double (&asdq)[MEQN], double (&bmasdq)[MEQN], double (&bpasdq)[MEQN]) {
+)PCLSRC";
+
+static const char *const kCellrpTransTail = R"PCLSRC(
+    }
+#line 1 "pcl_cellrp_wrapper_t"
+    template <int IXY>
+    __device__ static __forceinline__ void transverse(const Cell &L, const Cell &R, const RpParams &p, const double (&asdq)[MEQN],
+                                                      double (&bm)[MEQN], double (&bp)[MEQN]) {
+#pragma unroll
+        for (int m = 0; m < MEQN; m++) { bm[m] = 0.0; bp[m] = 0.0; }
+        tbody<IXY>(L.q, R.q, p.v, asdq, bm, bp);
+    }
+)PCLSRC";
+
+static const char *const kCellrpTransOpenAux = R"PCLSRC(
+    template <int ixy>
+    __device__ static __forceinline__ void tbody(const double (&q1)[MEQN], const double (&aux1)[NAUX], const double (&aux_below)[NAUX],
+                                                 const double (&aux_above)[NAUX], const double (&p)[8], const double (&asdq)[MEQN],
+                                                 double (&bmasdq)[MEQN], double (&bpasdq)[MEQN]) {
+)PCLSRC";
+
+static const char *const kCellrpTransTailAux = R"PCLSRC(
+    }
+#line 1 "pcl_cellrp_wrapper_t"
+    // (auxo is c1.aux again: one list serves aux_index and auxt_index)
+    template <int IXY>
+    __device__ static __forceinline__ void transverse_vc(const Cell &c1, const double *, const double *auxb, const double *auxa,
+                                                         const RpParams &p, const double (&asdq)[MEQN], double (&bm)[MEQN],
+                                                         double (&bp)[MEQN]) {
+        double below[NAUX], above[NAUX];
+#pragma unroll
+        for (int k = 0; k < NAUX; k++) { below[k] = auxb[k]; above[k] = auxa[k]; }
+#pragma unroll
+        for (int m = 0; m < MEQN; m++) { bm[m] = 0.0; bp[m] = 0.0; }
+        tbody<IXY>(c1.q, c1.aux, below, above, p.v, asdq, bm, bp);
+    }
+)PCLSRC";
+
+// the slices per workgroup the host named the unsplit kernels with are the rule's, and both kernels' static LDS fits
+static const char *const kCellrpTransCheck = R"PCLSRC(
+    static constexpr int USLICES = PCL_CELLRP_USLICES;
+    static_assert(NDIM == 2, "a transverse body belongs to a 2-D solver");
+    static_assert(USLICES == unsplit_user_slices(MEQN), "slices per workgroup: not the rule of sweep_args.hpp");
+    static_assert(unsplit_x_lds_bytes(MEQN, USLICES) <= UNSPLIT_LDS_LIMIT && unsplit_y_lds_bytes(MEQN, USLICES) <= UNSPLIT_LDS_LIMIT,
+                  "the static LDS of unsplit_x_kernel / unsplit_y_kernel (classic.hpp) does not fit a workgroup's 160 KB");
+)PCLSRC";
+
 static inline const char *cellrp_ns(int math) { return math == 1 ? "fast" : math == 2 ? "strict" : "exact"; }
 
-// (without a list the key is what it was before there were lists: the same entry as pcl_cellrp_compile's)
+// (without a list the key is what it was before there were lists: the same entry as pcl_cellrp_compile's; without a
+// transverse text it is what it was before there were transverse texts)
 static inline std::string cellrp_key(const char *body, const char *preamble, int meqn, int mwaves, int ndim, int math,
-                                     const int *aux = nullptr, int naux = 0) {
-    std::string k = "rp," + std::to_string(meqn) + "," + std::to_string(mwaves) + "," + std::to_string(ndim) + "," +
-                    std::to_string(math) + ",";
+                                     const int *aux = nullptr, int naux = 0, const char *trans = nullptr) {
+    std::string k = std::string(trans ? "rpt," : "rp,") + std::to_string(meqn) + "," + std::to_string(mwaves) + "," +
+                    std::to_string(ndim) + "," + std::to_string(math) + ",";
     for (int i = 0; i < naux; i++) k += (i ? "." : "aux") + std::to_string(aux[i]);
     if (naux > 0) k += ",";
+    if (trans) { k += std::to_string(strlen(trans)) + ":"; k += trans; }
     k += std::to_string(strlen(preamble)) + ":";
     k += preamble;
     k += body;
     return k;
 }
 
-// the sweep kernels of a UserRp of this dimension, as hiprtc name expressions
-static inline std::vector<std::string> cellrp_exprs(int ndim, int math) {
+// the sweep kernels of a UserRp of this dimension, as hiprtc name expressions; uslices > 0 (a transverse body, 2-D): the
+// x and y phases of the unsplit step behind them, the tile form of either, without a capacity function or fused source
+static inline std::vector<std::string> cellrp_exprs(int ndim, int math, int uslices = 0) {
     const std::string ns = std::string("pcl::") + cellrp_ns(math) + "::";
     auto k = [&](int ixy, bool dim1) {
         return "&" + ns + "sweep_kernel<" + ns + "UserRp, " + std::to_string(ixy) + ", false, false, " + (dim1 ? "true" : "false") + ">";
     };
     if (ndim == 1) return {k(1, true)};
-    return {k(1, false), k(2, false)};
+    if (uslices <= 0) return {k(1, false), k(2, false)};
+    const std::string u = std::to_string(uslices);
+    return {k(1, false), k(2, false), "&" + ns + "unsplit_x_kernel<" + ns + "UserRp, false, " + u + ", false>",
+            "&" + ns + "unsplit_y_kernel<" + ns + "UserRp, false, " + u + ", false, false>"};
 }
 
 // hiprtc compile of the sweep kernels around body; math: 0 exact, 1 fast, 2 strict.  0 = ok, else err holds the log
 // aux[0..naux): the aux components the body reads (naux == 0: the wrapper without aux, the program text of before)
-static inline int cellrp_build(const char *body, const char *preamble, int meqn, int mwaves, int ndim, int math,
-                               const int *aux, int naux, std::vector<char> &code, std::string (&sym)[2], std::string &err) {
+// trans (null: none, the program text of before): the transverse body; uslices: the slices per workgroup of the unsplit
+// kernels it is compiled into; sym[2], sym[3]: their lowered names
+static inline int cellrp_build(const char *body, const char *trans, const char *preamble, int meqn, int mwaves, int ndim, int math,
+                               const int *aux, int naux, int uslices, std::vector<char> &code, std::string (&sym)[4],
+                               std::string &err) {
     if (hiprtc_load(err)) return -1;
     HiprtcApi &a = hiprtc_api();
     std::string src = kCellrpHead;
@@ -224,10 +322,19 @@ static inline int cellrp_build(const char *body, const char *preamble, int meqn,
     src += body;
     src += "\n";
     src += naux > 0 ? kCellrpTailAux : kCellrpTail;
+    if (trans) {
+        src += naux > 0 ? kCellrpTransOpenAux : kCellrpTransOpen;
+        src += "#line 1 \"transverse\"\n";
+        src += trans;
+        src += "\n";
+        src += naux > 0 ? kCellrpTransTailAux : kCellrpTransTail;
+        src += kCellrpTransCheck;
+    }
+    src += naux > 0 ? kCellrpCloseAux : kCellrpClose;
     hiprtcProgram prog = nullptr;
     hiprtcResult r = a.hiprtcCreateProgram(&prog, src.c_str(), "pcl_cellrp.hip", kCellrpHeaderCount, kCellrpHeaderTexts, kCellrpHeaderNames);
     if (r != HIPRTC_SUCCESS) { err = std::string("hiprtcCreateProgram: ") + a.hiprtcGetErrorString(r); return -1; }
-    const std::vector<std::string> exprs = cellrp_exprs(ndim, math);
+    const std::vector<std::string> exprs = cellrp_exprs(ndim, math, trans ? uslices : 0);
     for (const std::string &e : exprs) {
         r = a.hiprtcAddNameExpression(prog, e.c_str());
         if (r != HIPRTC_SUCCESS) {
@@ -253,6 +360,7 @@ static inline int cellrp_build(const char *body, const char *preamble, int meqn,
     flags.push_back("-DPCL_CELLRP_MWAVES=" + std::to_string(mwaves));
     flags.push_back("-DPCL_CELLRP_NDIM=" + std::to_string(ndim));
     if (naux > 0) flags.push_back("-DPCL_CELLRP_NAUX=" + std::to_string(naux));
+    if (trans) flags.push_back("-DPCL_CELLRP_USLICES=" + std::to_string(uslices));
     std::vector<const char *> opts;
     for (const std::string &f : flags) opts.push_back(f.c_str());
     r = a.hiprtcCompileProgram(prog, (int)opts.size(), opts.data());
@@ -300,9 +408,12 @@ struct CellrpModule {
     int naux = 0;               // aux components the attached solver reads: its sweeps need the aux array on the device
     hipModule_t mod = nullptr;
     hipFunction_t fn[2] = {nullptr, nullptr};      // by ids - 1
+    // the unsplit phases (by ids - 1) of a solver with a transverse body, and its slices per workgroup; else null, 0
+    hipFunction_t fn_u[2] = {nullptr, nullptr};
+    int slices = 0;
     void unload() {
         if (mod) (void)hipModuleUnload(mod);
-        mod = nullptr; fn[0] = fn[1] = nullptr; id = 0; naux = 0;
+        mod = nullptr; fn[0] = fn[1] = fn_u[0] = fn_u[1] = nullptr; id = 0; naux = 0; slices = 0;
     }
 };
 

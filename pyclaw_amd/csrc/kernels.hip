@@ -414,9 +414,43 @@ template <class RP> int launch_unsplit_t(const SweepLaunch &l, const double *qx,
         return launch_unsplit_u<RP, 16, 16>(l, qx, err);
     } else return launch_unsplit_u<RP, 16, 16>(l, qx, err);
 }
+// A user-written Riemann solver with a transverse body (cellrp.hpp): l.user_fn is unsplit_x_kernel<UserRp, false, U, false>
+// or unsplit_y_kernel<UserRp, false, U, false, false> of the module compiled at run time, U = l.user_slices as the handle
+// records it; the parameters and grids are those of launch_unsplit_u.  Always the tile form of the y phase: the marching
+// kernel stays with the built-in solvers.
+int launch_unsplit_user(const SweepLaunch &l, const double *qx, std::string &err) {
+    if (!l.user_fn || l.user_slices < 3) {
+        err = "user-written Riemann solver: no compiled solver with a transverse body is attached (pcl_cellrp_attach)";
+        return PCL_ESTATE;
+    }
+    if (l.fwave || l.a.mcapa > 0 || l.a.src_id != 0 || l.a.sub != 0) {
+        err = "user-written Riemann solver, unsplit step: wave form only, no capacity function, no fused source, whole blocks";
+        return PCL_EINVAL;
+    }
+    if (l.user_naux > 0 && !l.a.aux) {
+        err = "user-written Riemann solver: this solver reads aux arrays and there are none (pcl_put_aux)";
+        return PCL_EINVAL;
+    }
+    SweepArgs a = l.a;
+    const int U = l.user_slices;
+    hipError_t e;
+    if (l.ids == 1) {
+        int nstrips = (a.mx + STRIP - 1) / STRIP;
+        const int ntr = (a.my + (U - 2) - 1) / (U - 2);
+        void *params[] = {&a, &nstrips};
+        e = hipModuleLaunchKernel(l.user_fn, (unsigned)nstrips * ntr, 1, 1, (unsigned)U * WAVE, 1, 1, 0, l.stream, params, nullptr);
+    } else {
+        int nti = (a.mx + (U - 2) - 1) / (U - 2);
+        const int ntj = (a.my + STRIP - 1) / STRIP;
+        void *params[] = {&a, &nti, &qx};
+        e = hipModuleLaunchKernel(l.user_fn, (unsigned)nti * ntj, 1, 1, (unsigned)U * WAVE, 1, 1, 0, l.stream, params, nullptr);
+    }
+    return e == hipSuccess ? PCL_OK : hip_fail(err, "unsplit launch (user-written Riemann solver)", e);
+}
 }  // namespace
 
 int launch_unsplit(const SweepLaunch &l, const double *qx, std::string &err) {
+    if (l.rp == PCL_RP_CELL) return launch_unsplit_user(l, qx, err);
     const RpFacts *f = Solvers::facts(l.rp);       // the flag follows the solver, among those this step has
     if ((l.fwave != 0) != (f && f->ndim == 2 && f->fwave))
         return not_built(err, "solver.fwave must be True for an f-wave Riemann solver and only for one");

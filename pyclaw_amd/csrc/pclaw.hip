@@ -548,6 +548,10 @@ static int unsplit_phase(pcl_solver *s, int ids, double dt, int sub, hipStream_t
     l.a.trans = s->cfg.method[2];
     l.a.dtd_t = dt / s->cfg.d[2 - ids];
     l.a.sub = sub;
+    if (l.rp == PCL_RP_CELL) {      // the unsplit kernels of the attached module (null: nothing attached, refused by the launcher)
+        l.user_fn = s->cellrp.fn_u[ids - 1];
+        l.user_slices = s->cellrp.slices;
+    }
     LaunchTimer timer(s, timing_on(s), ids - 1, sub != 2, stream);
     int rc = PCL_BY_MATH(s->cfg.math, launch_unsplit(l, s->t1, err));
     timer.end();
@@ -689,7 +693,7 @@ int check_device() {
 extern "C" {
 
 const char *pcl_last_error(void) { return g_err.c_str(); }
-int pcl_version(void) { return 107; }
+int pcl_version(void) { return 108; }
 int pcl_device_count(void) {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess) return 0;
@@ -703,8 +707,10 @@ int pcl_rp_info(int rp, int info[10]) {
     return PCL_OK;
 }
 
-int pcl_create(const pcl_config *cfg, pcl_solver **out) {
-    if (!cfg || !out) return fail(PCL_EINVAL, "null argument");
+// pcl_create in two halves, so that pcl_create_cellrp can put what the handle must be able to do between them.
+// create_check: every test of the configuration, host-only.  cell_unsplit: a PCL_RP_CELL solver may be unsplit (the caller
+// knows the handle and checks it itself); pcl_create cannot know it and refuses.
+static int create_check(const pcl_config *cfg, bool cell_unsplit) {
     if (getenv("PCL_TRACE_ABORT")) {   // diagnostics: C backtrace on abort()
         signal(SIGABRT, [](int) {
             void *bt[64];
@@ -714,7 +720,6 @@ int pcl_create(const pcl_config *cfg, pcl_solver **out) {
             raise(SIGABRT);
         });
     }
-    *out = nullptr;
     if (cfg->ndim < 1 || cfg->ndim > 3) return fail(PCL_EINVAL, "ndim must be 1, 2 or 3");
     // the reference's default is 2 (the limiter reaches two cells); more ghost layers only widen the frame that the
     // sweeps copy through / sweep over (step2ds.f sweeps every ghost row), the strips keep their 2-cell halo
@@ -754,7 +759,7 @@ int pcl_create(const pcl_config *cfg, pcl_solver **out) {
         if (cfg->ndim == 3) return fail(PCL_EINVAL, "PCL_RP_CELL: a user-written Riemann solver is 1-D or 2-D (ndim == 3)");
         if (cfg->fwave) return fail(PCL_EINVAL, "PCL_RP_CELL: a user-written Riemann solver returns waves, not f-waves (cfg.fwave must be 0)");
         if (cfg->method[5] != 0) return fail(PCL_EINVAL, "PCL_RP_CELL: no capacity function with a user-written Riemann solver (mcapa must be 0)");
-        if (cfg->ndim == 2 && cfg->method[2] >= 0)
+        if (cfg->ndim == 2 && cfg->method[2] >= 0 && !cell_unsplit)
             return fail(PCL_EINVAL, "PCL_RP_CELL: the unsplit step needs a transverse solver; a user-written solver has the "
                                     "dimension-split step only (method[2] < 0)");
         if (cfg->meqn < 1 || cfg->meqn > PCL_MAX_WAVES) return fail(PCL_EINVAL, "PCL_RP_CELL: 1 <= meqn <= 8");
@@ -794,6 +799,11 @@ int pcl_create(const pcl_config *cfg, pcl_solver **out) {
             return fail(PCL_EINVAL, "3-D: the capacity function is built for the dimension-split step (step3ds); the unsplit step3 "
                                     "with mcapa is not");
     }
+    return PCL_OK;
+}
+
+// the device half: the handle with its buffers
+static int create_alloc(const pcl_config *cfg, pcl_solver **out) {
     if (int rc = check_device()) return rc;
     HIP_TRY(hipSetDevice(cfg->device));
 
@@ -848,6 +858,13 @@ int pcl_create(const pcl_config *cfg, pcl_solver **out) {
     }
     *out = s;
     return PCL_OK;
+}
+
+int pcl_create(const pcl_config *cfg, pcl_solver **out) {
+    if (!cfg || !out) return fail(PCL_EINVAL, "null argument");
+    *out = nullptr;
+    if (int rc = create_check(cfg, false)) return rc;
+    return create_alloc(cfg, out);
 }
 
 void pcl_destroy(pcl_solver *s) {
@@ -1717,9 +1734,18 @@ int pcl_cellrp_compile(const char *body, const char *preamble, int meqn, int mwa
 // naux == 0 is pcl_cellrp_compile: the same program text, key and handle
 int pcl_cellrp_compile_aux(const char *body, const char *preamble, int meqn, int mwaves, int ndim, int math, const int *aux_index,
                            int naux, pcl_cellrp **out, long *code_size) {
+    return pcl_cellrp_compile_t(body, nullptr, preamble, meqn, mwaves, ndim, math, aux_index, naux, out, code_size);
+}
+
+// transverse == null is pcl_cellrp_compile_aux: the same program text, key and handle.  With one (2-D only) the code
+// object also holds the two unsplit kernels, unsplit_user_slices(meqn) slices per workgroup (sweep_args.hpp)
+int pcl_cellrp_compile_t(const char *body, const char *transverse, const char *preamble, int meqn, int mwaves, int ndim, int math,
+                         const int *aux_index, int naux, pcl_cellrp **out, long *code_size) {
     if (!body || !out) return fail(PCL_EINVAL, "null argument");
     *out = nullptr;
     if (!preamble) preamble = "";
+    if (transverse && ndim != 2)
+        return fail(PCL_EINVAL, "pcl_cellrp_compile_t: a transverse body belongs to the unsplit 2-D step (ndim must be 2)");
     if (meqn < 1 || meqn > PCL_MAX_WAVES || mwaves < 1 || mwaves > PCL_MAX_WAVES)
         return fail(PCL_EINVAL, "pcl_cellrp_compile: 1 <= meqn <= 8 and 1 <= mwaves <= 8");
     if (ndim < 1 || ndim > 2) return fail(PCL_EINVAL, "pcl_cellrp_compile: ndim must be 1 or 2 (the classic 1-D and dimension-split 2-D sweeps)");
@@ -1743,7 +1769,7 @@ int pcl_cellrp_compile_aux(const char *body, const char *preamble, int meqn, int
     }
     CellfnCache &c = cellfn_cache();
     std::lock_guard<std::mutex> lock(c.mu);
-    const std::string key = cellrp_key(body, preamble, meqn, mwaves, ndim, math, aux_index, naux);
+    const std::string key = cellrp_key(body, preamble, meqn, mwaves, ndim, math, aux_index, naux, transverse);
     auto it = c.rp_by_key.find(key);
     pcl_cellrp *r = nullptr;
     if (it != c.rp_by_key.end()) {
@@ -1751,8 +1777,10 @@ int pcl_cellrp_compile_aux(const char *body, const char *preamble, int meqn, int
         c.hits++;
     } else {
         std::vector<char> code;
-        std::string err, sym[2];
-        if (cellrp_build(body, preamble, meqn, mwaves, ndim, math, aux_index, naux, code, sym, err)) return fail(PCL_EINVAL, err);
+        std::string err, sym[4];
+        const int slices = transverse ? pcl::unsplit_user_slices(meqn) : 0;
+        if (cellrp_build(body, transverse, preamble, meqn, mwaves, ndim, math, aux_index, naux, slices, code, sym, err))
+            return fail(PCL_EINVAL, err);
         r = new pcl_cellrp();
         r->id = c.next_id++;
         r->meqn = meqn; r->mwaves = mwaves; r->ndim = ndim; r->math = math;
@@ -1761,6 +1789,9 @@ int pcl_cellrp_compile_aux(const char *body, const char *preamble, int meqn, int
         r->key = key;
         r->code.swap(code);
         r->sym[0] = sym[0]; r->sym[1] = sym[1];
+        r->trans = transverse != nullptr;
+        r->slices = slices;
+        r->sym_u[0] = sym[2]; r->sym_u[1] = sym[3];
         c.rp_by_key[key] = r;
         c.rp_live[r] = r->id;
         c.compiles++;
@@ -1807,25 +1838,46 @@ int pcl_cellrp_aux(const pcl_cellrp *r, int *naux, int *aux_index) {
     return PCL_OK;
 }
 
+int pcl_cellrp_transverse(const pcl_cellrp *r, int *has, int *slices) {
+    if (!has) return fail(PCL_EINVAL, "null argument");
+    CellfnCache &c = cellfn_cache();
+    std::lock_guard<std::mutex> lock(c.mu);
+    if (!r || !c.rp_live.count(r)) return fail(PCL_EINVAL, "not a live Riemann solver handle (pcl_cellrp_compile)");
+    *has = r->trans ? 1 : 0;
+    if (slices) *slices = r->slices;
+    return PCL_OK;
+}
+
+// what attaching r to a solver of this configuration asks of the handle; host-only (the cache's lock is held)
+static int cellrp_fits_locked(CellfnCache &c, const pcl_cellrp *r, const pcl_config &cfg, const char *who) {
+    if (int rc = cellrp_check_locked(c, r, cfg.meqn, cfg.mwaves, cfg.ndim, cfg.math)) return rc;
+    // every aux plane the kernel stages must lie inside the solver's aux allocation of cfg.maux planes
+    int top = -1;
+    for (int i = 0; i < r->naux; i++) top = r->aux[i] > top ? r->aux[i] : top;
+    if (top >= cfg.maux)
+        return fail(PCL_EINVAL, std::string(who) + ": the Riemann solver reads aux component " + std::to_string(top) +
+                                    " (0-based), the solver was created with maux = " + std::to_string(cfg.maux));
+    if (cfg.ndim == 2 && cfg.method[2] >= 0 && !r->trans)
+        return fail(PCL_EINVAL, std::string(who) + ": PCL_RP_CELL: the unsplit step (method[2] >= 0) needs a handle compiled with a "
+                                    "transverse body (pcl_cellrp_compile_t)");
+    return PCL_OK;
+}
+
 int pcl_cellrp_attach(pcl_solver *s, pcl_cellrp *r) {
     if (s) s->qt.invalidate();            // quiet tiles: not a read-only call (quiet_tiles.hpp)
     if (!s) return fail(PCL_EINVAL, "null argument");
     if (s->cfg.rp != PCL_RP_CELL) return fail(PCL_EINVAL, "pcl_cellrp_attach: the solver was not created with cfg.rp = PCL_RP_CELL");
     long id;
-    int naux;
+    int naux, slices;
     const void *code;
-    std::string sym[2];
+    std::string sym[2], sym_u[2];
     {   // (the entry is never freed: code and names stay valid outside the lock)
         CellfnCache &c = cellfn_cache();
         std::lock_guard<std::mutex> lock(c.mu);
-        if (int rc = cellrp_check_locked(c, r, s->cfg.meqn, s->cfg.mwaves, s->cfg.ndim, s->cfg.math)) return rc;
-        // every aux plane the kernel stages must lie inside the solver's aux allocation of cfg.maux planes
-        int top = -1;
-        for (int i = 0; i < r->naux; i++) top = r->aux[i] > top ? r->aux[i] : top;
-        if (top >= s->cfg.maux)
-            return fail(PCL_EINVAL, "pcl_cellrp_attach: the Riemann solver reads aux component " + std::to_string(top) +
-                                        " (0-based), the solver was created with maux = " + std::to_string(s->cfg.maux));
+        // (a refusal leaves the module attached before where it is)
+        if (int rc = cellrp_fits_locked(c, r, s->cfg, "pcl_cellrp_attach")) return rc;
         id = r->id; naux = r->naux; code = r->code.data(); sym[0] = r->sym[0]; sym[1] = r->sym[1];
+        slices = r->trans ? r->slices : 0; sym_u[0] = r->sym_u[0]; sym_u[1] = r->sym_u[1];
     }
     if (s->cellrp.id == id) return PCL_OK;
     HIP_TRY(hipSetDevice(s->cfg.device));
@@ -1840,9 +1892,40 @@ int pcl_cellrp_attach(pcl_solver *s, pcl_cellrp *r) {
             return fail(PCL_EHIP, "hipModuleGetFunction(" + sym[k] + "): " + hipGetErrorString(e));
         }
     }
+    for (int k = 0; k < 2 && slices > 0; k++) {
+        hipError_t e = hipModuleGetFunction(&m.fn_u[k], m.mod, sym_u[k].c_str());
+        if (e != hipSuccess) {
+            (void)hipModuleUnload(m.mod);
+            return fail(PCL_EHIP, "hipModuleGetFunction(" + sym_u[k] + "): " + hipGetErrorString(e));
+        }
+    }
     m.id = id;
     m.naux = naux;
+    m.slices = slices;
     s->cellrp = m;
+    return PCL_OK;
+}
+
+// a PCL_RP_CELL solver with r attached, in one call: the configuration is checked against what the handle can do (the
+// unsplit step, method[2] >= 0 in 2-D, if and only if it has a transverse body) before the device is touched
+int pcl_create_cellrp(const pcl_config *cfg, pcl_cellrp *r, pcl_solver **out) {
+    if (!cfg || !out) return fail(PCL_EINVAL, "null argument");
+    *out = nullptr;
+    if (cfg->rp != PCL_RP_CELL) return fail(PCL_EINVAL, "pcl_create_cellrp: cfg.rp must be PCL_RP_CELL");
+    if (int rc = create_check(cfg, true)) return rc;
+    {
+        CellfnCache &c = cellfn_cache();
+        std::lock_guard<std::mutex> lock(c.mu);
+        if (int rc = cellrp_fits_locked(c, r, *cfg, "pcl_create_cellrp")) return rc;
+    }
+    pcl_solver *s = nullptr;
+    if (int rc = create_alloc(cfg, &s)) return rc;
+    if (int rc = pcl_cellrp_attach(s, r)) {
+        const std::string msg = g_err;      // (pcl_destroy does not touch it; kept in case it ever does)
+        pcl_destroy(s);
+        return fail(rc, msg);
+    }
+    *out = s;
     return PCL_OK;
 }
 

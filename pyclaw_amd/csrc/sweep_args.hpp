@@ -12,6 +12,24 @@ namespace pcl {
 
 constexpr int MAX_WAVES_K = 8;  // == PCL_MAX_WAVES of the C ABI
 
+// Slices per workgroup U of the unsplit kernels compiled around a user-written Riemann solver with a transverse body
+// (cellrp.hpp): the one rule, read by the host (it names the instantiations and records U in the handle, from which
+// the launcher sizes its grids) and by the run-time text (a static_assert there ties the two).  What decides it is the
+// static LDS of the two kernels (classic.hpp) against the 160 KB of a workgroup: unsplit_x_kernel holds gm and gp,
+// unsplit_y_kernel the q tile of U + 1 columns as well (staged aux planes come on top only where they still fit).
+// 16 slices up to meqn = 6 (147 KB), 12 above (meqn = 8: 148 KB; with 16 the y kernel of meqn = 7 would need 171.5 KB).
+constexpr int unsplit_user_slices(int meqn) { return meqn <= 6 ? 16 : 12; }
+constexpr long unsplit_x_lds_bytes(int meqn, int u) { return 8L * 2 * u * meqn * 64; }
+constexpr long unsplit_y_lds_bytes(int meqn, int u) { return 8L * meqn * 64 * (u + 1) + unsplit_x_lds_bytes(meqn, u); }   // 512 meqn (3u + 1)
+constexpr long UNSPLIT_LDS_LIMIT = 160 * 1024;
+constexpr bool unsplit_user_slices_fit() {
+    for (int m = 1; m <= MAX_WAVES_K; m++)
+        if (unsplit_y_lds_bytes(m, unsplit_user_slices(m)) > UNSPLIT_LDS_LIMIT || unsplit_x_lds_bytes(m, unsplit_user_slices(m)) > UNSPLIT_LDS_LIMIT)
+            return false;
+    return true;
+}
+static_assert(unsplit_user_slices_fit(), "unsplit_user_slices: the static LDS of unsplit_x/y_kernel must fit 160 KB for every meqn");
+
 struct RpParams {
     double v[8];
 };
@@ -167,6 +185,9 @@ struct SweepLaunch {
     // solver handle has loaded; launch_sweep launches it over the grid it computes for the built-in solvers
     hipFunction_t user_fn = nullptr;
     int user_naux = 0;      // aux components that solver's body reads: with any, a launch without a.aux is refused
+    // launch_unsplit: user_fn is unsplit_x_kernel / unsplit_y_kernel<UserRp, false, user_slices, ...> of that module (null:
+    // nothing attached), user_slices the U its handle was compiled with (unsplit_user_slices)
+    int user_slices = 0;
     // one-kernel step only (classic_fused.hpp, quiet tiles): this launch's per-tile words and per-wavefront Courant
     // maxima (tq_out null: no bookkeeping).  A list launch (tq_list set) computes the tq_next->na + nq tiles a
     // hand-over+list kernel listed behind the previous launch and publishes the Courant number of those it skips.

@@ -98,14 +98,28 @@ class CellRiemann(RiemannSolver):
     cells and aux boundary conditions then run as for a built-in solver with aux, and a ``CellStartStep`` with
     ``writes_aux=True`` is seen by the body in the same step.
 
-    No unsplit step (there is no transverse solver), no f-waves, no capacity function, no SharpClaw, no
-    3-D, one block; the 2-D step always runs as two passes."""
+    ``transverse`` (2-D only) is a second text, the inside of Clawpack's ``rpt2`` for one interface, and opens
+    ``ClawSolver2D(dim_split=False)`` with ``order_trans`` 0, 1 and 2 to the solver: the library then also compiles its
+    unsplit x and y kernels around the two bodies.  Without ``aux`` it sees ``ql[MEQN]``, ``qr[MEQN]`` (the cells left
+    and right of the interface whose fluctuation is split; the same pair for A-dq and A+dq, there is no ``imp``),
+    ``asdq[MEQN]``, ``p[8]`` and ``ixy`` (the direction of the *normal* solve; the split is across it) and assigns
+    ``bmasdq[MEQN]``, ``bpasdq[MEQN]``, zero on entry.  With ``aux`` it sees instead of the two cells ``q1[MEQN]``,
+    ``aux1[NAUX]`` (the cell the fluctuation belongs to: left of the interface for A-dq, right of it for A+dq) and
+    ``aux_below[NAUX]``, ``aux_above[NAUX]`` (the listed components of its neighbours at the lower and upper transverse
+    index, Clawpack's aux1 / aux3 rows).  For ``asdq`` all zero the results must be zero: a wavefront without a jump
+    never calls the body.  Its diagnostics read ``transverse:<n>``.  The dimension-split step of a solver that carries
+    a transverse body is unchanged.
+
+    Not served: a transverse body that needs both cells and aux, f-waves, a capacity function, SharpClaw, 3-D, more than
+    one block.  The dimension-split 2-D step always runs as two passes, the unsplit y phase always in its tile form
+    (the marching y kernel stays with the built-in solvers)."""
 
     MAX_PARAMS = 8
     MAX_PLANES = 8
 
-    def __init__(self, body, meqn, mwaves, ndim, params=(), preamble="", name="user", aux=()):
-        RiemannSolver.__init__(self, name, PCL_RP_CELL, int(ndim), int(meqn), int(mwaves), ())
+    def __init__(self, body, meqn, mwaves, ndim, params=(), preamble="", name="user", aux=(), transverse=None):
+        RiemannSolver.__init__(self, name, PCL_RP_CELL, int(ndim), int(meqn), int(mwaves), (),
+                               has_transverse=transverse is not None)
         if not 1 <= self.meqn <= 8 or not 1 <= self.mwaves <= 8:
             raise ValueError("CellRiemann: 1 <= meqn <= 8 and 1 <= mwaves <= 8, got meqn=%d mwaves=%d" % (self.meqn, self.mwaves))
         if self.ndim not in (1, 2):
@@ -118,7 +132,10 @@ class CellRiemann(RiemannSolver):
         if self.aux and self.meqn + len(self.aux) > self.MAX_PLANES:
             raise ValueError("CellRiemann: meqn + len(aux) = %d, the sweep's tile holds at most %d planes (q components and "
                              "listed aux components)" % (self.meqn + len(self.aux), self.MAX_PLANES))
+        if transverse is not None and self.ndim != 2:
+            raise ValueError("CellRiemann: a transverse body belongs to the unsplit 2-D step, got ndim=%d" % self.ndim)
         self.body = str(body)
+        self.transverse = None if transverse is None else str(transverse)
         self.preamble = str(preamble)
         self.params = params
         self._rp = None            # pcl_cellrp handle and what it was compiled for
@@ -141,17 +158,22 @@ class CellRiemann(RiemannSolver):
 
     def compile(self, math='exact'):
         """Compile (no device needed; cached per process).  Raises with the compiler's log, whose line numbers are the
-        body's ("riemann:<n>") or the preamble's ("preamble:<n>")."""
+        body's ("riemann:<n>"), the transverse body's ("transverse:<n>") or the preamble's ("preamble:<n>")."""
         import ctypes
         from . import _lib
         if math not in ('exact', 'fast', 'strict'):
             raise Exception("math must be 'exact', 'fast' or 'strict'")
-        key = (self.meqn, self.mwaves, self.ndim, math, self.body, self.preamble, self.aux)
+        key = (self.meqn, self.mwaves, self.ndim, math, self.body, self.preamble, self.aux, self.transverse)
         if self._rp is not None and self._key == key:
             return self
         rp, size = ctypes.c_void_p(), ctypes.c_long(0)
         mode = {'exact': 0, 'fast': 1, 'strict': 2}[math]
-        if self.aux:
+        if self.transverse is not None:
+            _lib.check(_lib.lib().pcl_cellrp_compile_t(self.body.encode(), self.transverse.encode(), self.preamble.encode(),
+                                                       self.meqn, self.mwaves, self.ndim, mode,
+                                                       (ctypes.c_int * len(self.aux))(*self.aux) if self.aux else None,
+                                                       len(self.aux), ctypes.byref(rp), ctypes.byref(size)))
+        elif self.aux:
             _lib.check(_lib.lib().pcl_cellrp_compile_aux(self.body.encode(), self.preamble.encode(), self.meqn, self.mwaves,
                                                          self.ndim, mode, (ctypes.c_int * len(self.aux))(*self.aux),
                                                          len(self.aux), ctypes.byref(rp), ctypes.byref(size)))

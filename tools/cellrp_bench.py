@@ -18,7 +18,14 @@ stderr); needs a GPU.
 medium (problems.vc_acoustics2D) against its restatement as a CellRiemann that reads aux=(0, 1)
 (problems.VC_ACOUSTICS_2D_RP).  The sweeps then stage two aux planes next to q.
 
-  python tools/cellrp_bench.py [--aux] [--n 4096] [--steps 20] [--warmup 3] [--reps 7] [--out FILE]
+--unsplit measures the unsplit step (dim_split = False, order_trans = 2) two ways instead: "builtin", the built-in
+solver, and "user", the same solver as a CellRiemann with a transverse body (problems.ACOUSTICS_2D_RPT, or with --aux
+problems.VC_ACOUSTICS_2D_RPT).  Both run unsplit_x_kernel; in the y phase the user solver always takes the tile kernel,
+the built-in solver without aux the marching kernel once the grid is large enough for it (kernels.hip: 4096^2, not
+2048^2), so at 2048^2 the two runs execute the same templates and at 4096^2 their difference is the price of that limit.
+The children also time the run-time compile of the solver with and without its transverse text.
+
+  python tools/cellrp_bench.py [--aux] [--unsplit] [--n 4096] [--steps 20] [--warmup 3] [--reps 7] [--out FILE]
 """
 import argparse
 import ctypes
@@ -34,6 +41,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 VARIANTS = ("two_pass", "user", "default")
+VARIANTS_UNSPLIT = ("builtin", "user")
 
 
 def child(args):
@@ -43,7 +51,11 @@ def child(args):
     L = _lib.lib()
     if L.pcl_device_count() < 1:
         raise SystemExit("cellrp_bench: no HIP device (nothing here can be measured without one)")
-    if args.aux:
+    if args.unsplit:
+        make = problems.vc_acoustics2D if args.aux else problems.acoustics2D
+        claw = make(pyclaw, mx=args.n, my=args.n, run=False, math=args.math, dim_split=0, user_rp=args.child == "user")
+        claw.solver.order_trans = 2
+    elif args.aux:
         claw = problems.vc_acoustics2D(pyclaw, mx=args.n, my=args.n, run=False, math=args.math, user_rp=args.child == "user")
     else:
         claw = problems.acoustics2D(pyclaw, mx=args.n, my=args.n, run=False, math=args.math)
@@ -51,7 +63,13 @@ def child(args):
     state = solution.state
     res = {"variant": args.child}
     if args.child == "user":
-        if not args.aux:
+        if args.unsplit:        # the same normal body without the transverse text, for the compile time alone
+            rp = solver.rp
+            plain = pyclaw.CellRiemann(rp.body, rp.meqn, rp.mwaves, 2, aux=rp.aux)
+            t0 = time.perf_counter()
+            plain.compile(args.math)
+            res["compile_plain_s"] = time.perf_counter() - t0
+        elif not args.aux:
             g = state.aux_global
             solver.rp = pyclaw.CellRiemann(problems.ACOUSTICS_2D_RP, 3, 2, 2, params=[g['rho'], g['bulk'], g['cc'], g['zz']])
         t0 = time.perf_counter()
@@ -92,20 +110,23 @@ def main():
     ap.add_argument("--math", default="exact")
     ap.add_argument("--out", default=None)
     ap.add_argument("--aux", action="store_true", help="the variable-coefficient problem: vc_acoustics_2d against CellRiemann(aux=(0, 1))")
-    ap.add_argument("--child", default=None, choices=VARIANTS)
+    ap.add_argument("--unsplit", action="store_true", help="the unsplit step: the built-in solver against CellRiemann(transverse=...)")
+    ap.add_argument("--child", default=None, choices=VARIANTS + VARIANTS_UNSPLIT)
     args = ap.parse_args()
     if args.child:
         return child(args)
 
-    runs = {v: [] for v in VARIANTS}
+    variants = VARIANTS_UNSPLIT if args.unsplit else VARIANTS
+    runs = {v: [] for v in variants}
     for _ in range(args.reps):
-        for v in VARIANTS:
+        for v in variants:
             env = dict(os.environ)
             env.pop("PCL_TUNE_FUSED_STEP", None)
             if v == "two_pass":
                 env["PCL_TUNE_FUSED_STEP"] = "0"
             cmd = [sys.executable, os.path.abspath(__file__), "--child", v, "--n", str(args.n), "--steps", str(args.steps),
-                   "--warmup", str(args.warmup), "--math", args.math] + (["--aux"] if args.aux else [])
+                   "--warmup", str(args.warmup), "--math", args.math] + (["--aux"] if args.aux else []) + \
+                  (["--unsplit"] if args.unsplit else [])
             out = subprocess.run(cmd, env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=300)
             lines = [l for l in out.stdout.splitlines() if l.startswith("CELLRP_CHILD ")]
             if out.returncode != 0 or not lines:
@@ -116,15 +137,23 @@ def main():
 
     def spread(vals):
         return {"median": float(np.median(vals)), "min": min(vals), "max": max(vals), "all": vals}
-    res = {"tool": "cellrp_bench" + (" --aux" if args.aux else ""), "n": args.n, "math": args.math, "steps": args.steps, "warmup": args.warmup, "reps": args.reps,
-           "compile_s": spread([r["compile_s"] for r in runs["user"]]), "forms": {v: runs[v][-1]["forms"] for v in VARIANTS},
+    res = {"tool": "cellrp_bench" + (" --aux" if args.aux else "") + (" --unsplit" if args.unsplit else ""), "n": args.n, "math": args.math, "steps": args.steps, "warmup": args.warmup, "reps": args.reps,
+           "compile_s": spread([r["compile_s"] for r in runs["user"]]), "forms": {v: runs[v][-1]["forms"] for v in variants},
            "states": {}}
+    if args.unsplit:
+        res["compile_plain_s"] = spread([r["compile_plain_s"] for r in runs["user"]])
     for name in ("pulse", "dense"):
-        st = {v + "_ms": spread([r[name + "_ms"] for r in runs[v]]) for v in VARIANTS}
-        sums = set(r[name + "_sum"] for v in VARIANTS for r in runs[v])
-        cfls = set(r[name + "_cfl"] for v in VARIANTS for r in runs[v])
+        st = {v + "_ms": spread([r[name + "_ms"] for r in runs[v]]) for v in variants}
+        sums = set(r[name + "_sum"] for v in variants for r in runs[v])
+        cfls = set(r[name + "_cfl"] for v in variants for r in runs[v])
         st["same_result_in_every_run"] = len(sums) == 1 and len(cfls) == 1
-        a, b, c = (st[v + "_ms"] for v in VARIANTS)
+        if args.unsplit:
+            a, b = (st[v + "_ms"] for v in variants)
+            st["user_over_builtin"] = b["median"] / a["median"]
+            st["user_and_builtin_spreads_overlap"] = not (b["min"] > a["max"] or a["min"] > b["max"])
+            res["states"][name] = st
+            continue
+        a, b, c = (st[v + "_ms"] for v in variants)
         st["user_over_two_pass"] = b["median"] / a["median"]
         st["user_and_two_pass_spreads_overlap"] = not (b["min"] > a["max"] or a["min"] > b["max"])
         st["user_over_default"] = b["median"] / c["median"]
