@@ -2043,3 +2043,53 @@ int orc_step3(int rp, int maxm, int meqn, int mwaves, int maux, int mbc, int mx,
     work_free(&w);
     return rc;
 }
+
+/* ======================================================================== the restated solvers, one by one
+ * For oracle/ref_rp_shim.c: the reference's own step and flux Fortran calls rp1 / rpn2 / rpt2 / rpn3 / rpt3 / rptt3 by
+ * name, and the shim answers with these.  The aux rows go in through orc_aux1d / orc_auxr1d / orc_auxb1d / orc_auxa1d
+ * as for the oracle's own drivers (1-D, 2-D) or as arguments (3-D). */
+int orc_rp1_any(int rp, const double *par, int meqn, int mwaves, int mbc, int mx, const double *ql, const double *qr,
+                double *wave, double *s, double *amdq, double *apdq)
+{
+    if (rp == RP_ELASTICITY_FWAVE_1D) {
+        if (!orc_aux1d || orc_maux1d < 3 || meqn != 2 || mwaves != 2) return -1;
+        rp_fwave_normal(2, meqn, mwaves, mbc, mx, ql, qr, wave, s, amdq, apdq);
+        return 0;
+    }
+    return orc_rp1_ptr(rp, par, meqn, mwaves, mbc, mx, ql, qr, wave, s, amdq, apdq);
+}
+
+int orc_rpt2_imp(int rp, const double *par, int ixy, int imp, int meqn, int mbc, int mx, const double *q1d,
+                 const double *asdq, double *bmasdq, double *bpasdq)
+{
+    if (imp != 1 && imp != 2) return -1;
+    return rpt2_dispatch(rp, ixy, meqn, mbc, mx, q1d, asdq, bmasdq, bpasdq, par, imp);
+}
+
+int orc_rpn3(int rp, int ixyz, int meqn, int mwaves, int maux, int mbc, int mx, const double *ql, const double *qr,
+             const double *auxl, const double *auxr, double *wave, double *s, double *amdq, double *apdq)
+{
+    if (rp != RP_VC_ACOUSTICS_3D || maux < 2 || meqn != 4 || mwaves != 2) return -1;
+    rpn3_vc_acoustics(ixyz, meqn, mwaves, maux, mbc, mx, ql, qr, auxl, auxr, wave, s, amdq, apdq);
+    return 0;
+}
+
+/* aux1 / aux2 / aux3 are (maux, nrow, 3) */
+int orc_rpt3(int rp, int ixyz, int icoor, int meqn, int maux, int mbc, int mx, int nrow, const double *aux1,
+             const double *aux2, const double *aux3, int imp, const double *asdq, double *bmasdq, double *bpasdq)
+{
+    if (rp != RP_VC_ACOUSTICS_3D || maux < 2 || meqn != 4 || (icoor != 2 && icoor != 3) || (imp != 1 && imp != 2)) return -1;
+    rpt3_vc_acoustics(ixyz, icoor, meqn, maux, mbc, mx, nrow, aux1, aux2, aux3, imp, asdq, bmasdq, bpasdq);
+    return 0;
+}
+
+int orc_rptt3(int rp, int ixyz, int icoor, int meqn, int maux, int mbc, int mx, int nrow, const double *aux1,
+              const double *aux2, const double *aux3, int imp, int impt, const double *bsasdq, double *cmbsasdq,
+              double *cpbsasdq)
+{
+    if (rp != RP_VC_ACOUSTICS_3D || maux < 2 || meqn != 4 || (icoor != 2 && icoor != 3) || (imp != 1 && imp != 2) ||
+        (impt != 1 && impt != 2))
+        return -1;
+    rptt3_vc_acoustics(ixyz, icoor, meqn, maux, mbc, mx, nrow, aux1, aux2, aux3, imp, impt, bsasdq, cmbsasdq, cpbsasdq);
+    return 0;
+}

@@ -12,6 +12,10 @@ Two back ends with the same Python call surface:
   compiled unchanged by oracle/Makefile with flang into oracle/_ref/.  f2py is not
   used: every scalar goes by reference, INTEGER*4 arrays as int32, arrays F-ordered.
 
+* ``RefClassic1D`` / ``RefClassic2D`` / ``RefClassic3D`` -- the reference's step and flux Fortran of each dimension,
+  unchanged, around THIS repository's restated Riemann solvers (oracle/ref_rp_shim.c): every solver the oracle
+  restates, aux rows and capa included.  They pin the step, not the solver formulas.
+
 Arrays follow the reference's f2py call surface (clawpack.py:538-552):
 qold/qnew/aux are Fortran-ordered float64 ``(meqn, mx+2mbc, my+2mbc)``.
 """
@@ -332,6 +336,42 @@ class COracle:
         return self.lib.orc_philim(a, b, meth)
 
 
+def _ref_step2(lib, name, maxm, mbc, mx, my, qold, qnew, aux, dx, dy, dt, method, mthlim, ids):
+    """step2ds_ / step2_ of a flang build: the 27 (28 with ids) by-reference arguments in the order of step2ds.f:2-5, work
+    arrays sized as step2.f:49-56 partitions them"""
+    meqn = qnew.shape[0]
+    method = np.ascontiguousarray(method, dtype=np.int32)
+    mthlim = np.ascontiguousarray(mthlim, dtype=np.int32)
+    mwaves = len(mthlim)
+    maux_decl = max(int(method[6]), 1)
+    n = maxm + 2 * mbc
+    qadd = np.zeros((meqn, n), order="F")
+    fadd = np.zeros((meqn, n), order="F")
+    gadd = np.zeros((meqn, 2, n), order="F")
+    q1d = np.zeros((meqn, n), order="F")
+    dtdx1d = np.zeros(n)
+    dtdy1d = np.zeros(n)
+    aux1 = np.zeros((maux_decl, n), order="F")
+    aux2 = np.zeros((maux_decl, n), order="F")
+    aux3 = np.zeros((maux_decl, n), order="F")
+    mwork = n * (5 * meqn + mwaves + meqn * mwaves)
+    work = np.zeros(mwork)
+    if aux is None:
+        aux = np.zeros((1,) + qnew.shape[1:], order="F")
+    ci = lambda v: C.byref(C.c_int(v))
+    cd = lambda v: C.byref(C.c_double(v))
+    cfl = C.c_double(0.0)
+    assert qold.flags.f_contiguous and qnew.flags.f_contiguous and aux.flags.f_contiguous
+    args = [ci(maxm), ci(meqn), ci(mwaves), ci(maux_decl), ci(mbc), ci(mx), ci(my),
+            _d(qold), _d(qnew), _d(aux), cd(dx), cd(dy), cd(dt), _i(method), _i(mthlim),
+            C.byref(cfl), _d(qadd), _d(fadd), _d(gadd), _d(q1d), _d(dtdx1d), _d(dtdy1d),
+            _d(aux1), _d(aux2), _d(aux3), _d(work), ci(mwork)]
+    if ids is not None:
+        args.append(ci(ids))
+    getattr(lib, name)(*args)
+    return qnew, cfl.value
+
+
 class RefEuler2D:
     """The reference Fortran itself (flang build under oracle/_ref/), Euler 5-wave only.
 
@@ -358,36 +398,7 @@ class RefEuler2D:
 
     def _call(self, name, par, maxm, mbc, mx, my, qold, qnew, aux, dx, dy, dt, method, mthlim, ids):
         self.cparam.gamma, self.cparam.gamma1 = float(par[0]), float(par[1])
-        meqn = qnew.shape[0]
-        method = np.ascontiguousarray(method, dtype=np.int32)
-        mthlim = np.ascontiguousarray(mthlim, dtype=np.int32)
-        mwaves = len(mthlim)
-        maux_decl = max(int(method[6]), 1)
-        n = maxm + 2 * mbc
-        qadd = np.zeros((meqn, n), order="F")
-        fadd = np.zeros((meqn, n), order="F")
-        gadd = np.zeros((meqn, 2, n), order="F")
-        q1d = np.zeros((meqn, n), order="F")
-        dtdx1d = np.zeros(n)
-        dtdy1d = np.zeros(n)
-        aux1 = np.zeros((maux_decl, n), order="F")
-        aux2 = np.zeros((maux_decl, n), order="F")
-        aux3 = np.zeros((maux_decl, n), order="F")
-        mwork = n * (5 * meqn + mwaves + meqn * mwaves)
-        work = np.zeros(mwork)
-        if aux is None:
-            aux = np.zeros((1,) + qnew.shape[1:], order="F")
-        ci = lambda v: C.byref(C.c_int(v))
-        cd = lambda v: C.byref(C.c_double(v))
-        cfl = C.c_double(0.0)
-        args = [ci(maxm), ci(meqn), ci(mwaves), ci(maux_decl), ci(mbc), ci(mx), ci(my),
-                _d(qold), _d(qnew), _d(aux), cd(dx), cd(dy), cd(dt), _i(method), _i(mthlim),
-                C.byref(cfl), _d(qadd), _d(fadd), _d(gadd), _d(q1d), _d(dtdx1d), _d(dtdy1d),
-                _d(aux1), _d(aux2), _d(aux3), _d(work), ci(mwork)]
-        if ids is not None:
-            args.append(ci(ids))
-        getattr(self.lib, name)(*args)
-        return qnew, cfl.value
+        return _ref_step2(self.lib, name, maxm, mbc, mx, my, qold, qnew, aux, dx, dy, dt, method, mthlim, ids)
 
     def step2ds(self, rp, par, maxm, mbc, mx, my, qold, qnew, aux, dx, dy, dt, method, mthlim, ids,
                 fwave=False):
@@ -400,6 +411,146 @@ class RefEuler2D:
         assert rp == RP_EULER5_2D and bool(fwave) == self.fwave
         return self._call("step2_", par, maxm, mbc, mx, my, qold, qnew, aux, dx, dy, dt, method,
                           mthlim, None)
+
+
+class _RefShim:
+    """A flang build of the reference's classic step around the restated solvers (oracle/ref_rp_shim.c).  select() names
+    the solver for the next step; done() raises if a call of the Fortran found no restated solver to answer it."""
+
+    names = {}        # fwave -> library file under oracle/_ref
+
+    def __init__(self):
+        self.libs = {}
+
+    @classmethod
+    def available(cls, fwave=False):
+        return os.path.exists(os.path.join(_HERE, "_ref", cls.names[bool(fwave)]))
+
+    def select(self, fwave, rp, par, maux):
+        fwave = bool(fwave)
+        if fwave not in self.libs:
+            path = os.path.join(_HERE, "_ref", self.names[fwave])
+            if not os.path.exists(path):
+                raise FileNotFoundError(path)
+            lib = C.CDLL(path)
+            lib.ref_shim_select.restype = None
+            lib.ref_shim_select.argtypes = [C.c_int, _dp, C.c_int]
+            lib.ref_shim_failures.restype = C.c_int
+            self.libs[fwave] = lib
+        lib = self.libs[fwave]
+        p8 = np.zeros(8)
+        if par is not None:
+            p8[:len(par)] = par
+        lib.ref_shim_select(int(rp), _d(p8), int(maux))
+        return lib
+
+    @staticmethod
+    def done(lib, rp):
+        n = lib.ref_shim_failures()
+        if n:
+            raise RuntimeError("reference build: %d Riemann-solver calls found no restated solver (rp = %d)" % (n, rp))
+
+
+class RefClassic1D(_RefShim):
+    """step1.f (libref_classic1d.so) and its f-wave twin step1fw.f (libref_classic1d_fw.so), by-reference arguments in the
+    order of step1.f:4-5 / step1fw.f:4-5"""
+
+    names = {False: "libref_classic1d.so", True: "libref_classic1d_fw.so"}
+
+    def step1(self, rp, par, mbc, mx, q, aux, dx, dt, method, mthlim, fwave=False):
+        meqn = q.shape[0]
+        method = np.ascontiguousarray(method, dtype=np.int32)
+        mthlim = np.ascontiguousarray(mthlim, dtype=np.int32)
+        mwaves = len(mthlim)
+        maux = int(method[6])
+        lib = self.select(fwave, rp, par, maux)
+        n = mx + 2 * mbc
+        if aux is None or maux == 0:
+            aux = np.zeros((1, n), order="F")
+        f = np.zeros((meqn, n), order="F")
+        wave = np.zeros((meqn, mwaves, n), order="F")
+        s = np.zeros((mwaves, n), order="F")
+        amdq = np.zeros((meqn, n), order="F")
+        apdq = np.zeros((meqn, n), order="F")
+        dtdx = np.zeros(n)
+        ci = lambda v: C.byref(C.c_int(v))
+        cd = lambda v: C.byref(C.c_double(v))
+        cfl = C.c_double(0.0)
+        assert q.flags.f_contiguous and aux.flags.f_contiguous and aux.shape == (max(maux, 1), n)
+        args = [ci(meqn), ci(mwaves), ci(mbc), ci(max(maux, 1)), ci(mx), _d(q), _d(aux), cd(dx), cd(dt), _i(method),
+                _i(mthlim), C.byref(cfl), _d(f), _d(wave), _d(s), _d(amdq), _d(apdq), _d(dtdx)]
+        if fwave:
+            args.insert(0, ci(mx))             # step1fw.f: maxmx leads
+        lib.step1_(*args)
+        self.done(lib, rp)
+        return q, cfl.value
+
+
+class RefClassic2D(_RefShim):
+    """step2ds.f / step2.f with flux2.f (libref_classic2d.so) or flux2fw.f (libref_classic2d_fw.so)"""
+
+    names = {False: "libref_classic2d.so", True: "libref_classic2d_fw.so"}
+
+    def _call(self, name, rp, par, maxm, mbc, mx, my, qold, qnew, aux, dx, dy, dt, method, mthlim, ids, fwave):
+        maux = int(np.asarray(method)[6])
+        lib = self.select(fwave, rp, par, maux)
+        if aux is not None:
+            assert aux.shape == (maux,) + qnew.shape[1:]
+        out = _ref_step2(lib, name, maxm, mbc, mx, my, qold, qnew, aux if maux > 0 else None, dx, dy, dt, method, mthlim,
+                         ids)
+        self.done(lib, rp)
+        return out
+
+    def step2ds(self, rp, par, maxm, mbc, mx, my, qold, qnew, aux, dx, dy, dt, method, mthlim, ids, fwave=False):
+        return self._call("step2ds_", rp, par, maxm, mbc, mx, my, qold, qnew, aux, dx, dy, dt, method, mthlim, ids, fwave)
+
+    def step2(self, rp, par, maxm, mbc, mx, my, qold, qnew, aux, dx, dy, dt, method, mthlim, fwave=False):
+        return self._call("step2_", rp, par, maxm, mbc, mx, my, qold, qnew, aux, dx, dy, dt, method, mthlim, None, fwave)
+
+
+class RefClassic3D(_RefShim):
+    """step3.f / step3ds.f with flux3.f (libref_classic3d.so); by-reference arguments in the order of step3.f:3-6, the work
+    array sized as step3.f:53-86 partitions it"""
+
+    names = {False: "libref_classic3d.so"}
+
+    def _call(self, name, rp, maxm, mbc, mx, my, mz, qold, qnew, aux, dx, dy, dz, dt, method, mthlim, idir):
+        meqn = qnew.shape[0]
+        method = np.ascontiguousarray(method, dtype=np.int32)
+        mthlim = np.ascontiguousarray(mthlim, dtype=np.int32)
+        mwaves = len(mthlim)
+        maux = int(method[6])
+        lib = self.select(False, rp, None, maux)
+        n = maxm + 2 * mbc
+        qadd = np.zeros((meqn, n), order="F")
+        fadd = np.zeros((meqn, n), order="F")
+        gadd = np.zeros((meqn, 2, 3, n), order="F")
+        hadd = np.zeros((meqn, 2, 3, n), order="F")
+        q1d = np.zeros((meqn, n), order="F")
+        dt1d = [np.zeros(n) for _ in range(3)]
+        aux123 = [np.zeros((maux, n, 3), order="F") for _ in range(3)]
+        mwork = n * (meqn * mwaves + mwaves + 31 * meqn)
+        work = np.zeros(mwork)
+        ci = lambda v: C.byref(C.c_int(v))
+        cd = lambda v: C.byref(C.c_double(v))
+        cfl = C.c_double(0.0)
+        assert maux > 0 and aux.shape == (maux,) + qnew.shape[1:]
+        assert qold.flags.f_contiguous and qnew.flags.f_contiguous and aux.flags.f_contiguous
+        args = [ci(maxm), ci(meqn), ci(mwaves), ci(mbc), ci(mx), ci(my), ci(mz), _d(qold), _d(qnew), _d(aux), cd(dx),
+                cd(dy), cd(dz), cd(dt), _i(method), _i(mthlim), C.byref(cfl), _d(qadd), _d(fadd), _d(gadd), _d(hadd),
+                _d(q1d), _d(dt1d[0]), _d(dt1d[1]), _d(dt1d[2]), _d(aux123[0]), _d(aux123[1]), _d(aux123[2]), ci(maux),
+                _d(work), ci(mwork)]
+        if idir is not None:
+            args.append(ci(idir))
+        getattr(lib, name)(*args)
+        self.done(lib, rp)
+        return qnew, cfl.value
+
+    def step3ds(self, rp, maxm, mbc, mx, my, mz, qold, qnew, aux, dx, dy, dz, dt, method, mthlim, idir):
+        return self._call("step3ds_", rp, maxm, mbc, mx, my, mz, qold, qnew, aux, dx, dy, dz, dt, method, mthlim, idir)
+
+    def step3(self, rp, maxm, mbc, mx, my, mz, qold, qnew, aux, dx, dy, dz, dt, method, mthlim):
+        return self._call("step3_", rp, maxm, mbc, mx, my, mz, qold, qnew, aux, dx, dy, dz, dt, method, mthlim, None)
 
 
 class RefSharp2DEuler:

@@ -3,7 +3,8 @@ What the reference's own build returned, pinned for the tests that compare with 
 
 tests/test_oracle_vs_ref.py, test_sphere.py and test_weno_orders.py compare the oracle bit for bit with the flang build
 of the reference's Fortran (oracle/_ref) and with the reference's generated weno.f90.  Both need the reference tree,
-which a checkout of this repository does not have.  For every case those tests run, tests/golden/ref_pins.json holds a
+which a checkout of this repository does not have.  tests/test_gpu_ref_pins.py holds the device to the same pins for the
+cases of tests/ref_cases.py.  For every case those tests run, tests/golden/ref_pins.json holds a
 SHA-256 digest of the reference's exact result (float64 bytes, C order, with -0.0 read as +0.0 and every NaN as one NaN:
 equal digests <=> np.array_equal(..., equal_nan=True)) and its CFL number as a hex float, so the comparison runs
 everywhere.  Where oracle/_ref is present the tests compare with the live build as well.
@@ -38,7 +39,7 @@ def digest(x):
 def _entry(out, cfl):
     e = {"out": digest(out)}
     if cfl is not None:
-        e["cfl"] = float(cfl).hex()
+        e["cfl"] = float(cfl).hex() if np.ndim(cfl) == 0 else digest(cfl)     # a group of runs: their CFL numbers as a vector
     return e
 
 

@@ -5,7 +5,10 @@ the variable-coefficient acoustics equations (third-party, absent from the refer
 PINNING.  The reference's golden test/pressure_3D.txt (test_3D_acoustics_heterogeneous: 30^3, order_trans 22, MC,
 t = 2; gate 2-norm < 1e-4, test/test_examples.py:497-514) is reproduced by the oracle with 2-norm difference 0.0
 -- every digit the file holds -- and by the HIP path bit for bit the same.  flux3.f / step3.f are in the tree but
-cannot be built without the three third-party Riemann solvers, so there is no oracle/_ref leg for this row.
+cannot be built with the reference's own Riemann solvers (third-party, absent).  They are built around the RESTATED
+rpn3 / rpt3 / rptt3 instead (oracle/ref_rp_shim.c, oracle/_ref/libref_classic3d.so): that leg pins step3.f, step3ds.f and
+all six transverse modes of flux3.f -- not the solver formulas -- for the oracle (tests/test_oracle_vs_ref.py) and for
+the device (tests/test_gpu_ref_pins.py), at every (trans, order), four limiter pairs and extents down to 1x1x1.
 """
 import ctypes as C
 import os

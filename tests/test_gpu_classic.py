@@ -189,7 +189,8 @@ def test_step2_unsplit_euler_bitexact(coracle, mx, my, trans, kind):
 @pytest.mark.parametrize("trans", [1, 2])
 @pytest.mark.parametrize("order", [1, 2])
 def test_step2_unsplit_acoustics_bitexact(coracle, trans, order):
-    """restated rpt2_acoustics (no reference golden: parity unpinned at the solver boundary)"""
+    """restated rpt2_acoustics (no reference golden: the solver's formulas are unpinned; the step2.f / flux2.f around it is
+    pinned by the reference's Fortran built around this solver, tests/test_gpu_ref_pins.py)"""
     L = _lib()
     rng = np.random.default_rng(9)
     mx, my, mbc = 70, 41, 2

@@ -1,8 +1,10 @@
 """
 GPU parity, 3-D dimension-split classic sweeps: pcl_step3ds (C ABI, f2py-shaped) against
 the C restatement of step3ds.f/flux3.f on the same seeded inputs, bit for bit.  The Riemann solver
-(rpn3_vc_acoustics, third-party, absent from the reference tree) is restated on both sides: parity is
-pinned at the app level only, through the reference's scalar result (tests/test_oracle_golden.py).
+(rpn3_vc_acoustics, third-party, absent from the reference tree) is restated on both sides: the solver's
+formulas are pinned at the app level only, through the reference's scalar result (tests/test_oracle_golden.py).
+The step around it (step3ds.f, flux3.f, with and without mcapa) is pinned by the reference's Fortran built
+around the restated solver: tests/test_gpu_ref_pins.py.
 """
 import ctypes as C
 

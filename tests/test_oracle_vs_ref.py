@@ -4,10 +4,17 @@ step2ds.f/step2.f/flux2.f/limiter.f/philim.f + the vendored Euler 5-wave solvers
 random inputs -- bit for bit.  What the reference build returns for every case is pinned in
 tests/golden/ref_pins.json (tests/ref_pins.py), so the comparison runs where oracle/_ref has not
 been built (it needs the reference tree); where it has, the live build is compared as well.
+
+The vendored Euler pair is the one solver whose source lies in the reference tree, and that build carries no aux rows.
+The last three tests run every other solver the oracle restates -- 1-D, 2-D with aux rows and capa, 3-D with all six
+transverse modes -- through the reference's own step and flux Fortran linked against the RESTATED solvers
+(oracle/ref_rp_shim.c, libref_classic*.so; cases in tests/ref_cases.py).  They pin the step around the solver; the
+third-party solver formulas are the oracle's on both sides and stay unpinned.
 """
 import numpy as np
 import pytest
 
+import ref_cases as RC
 import ref_pins as P
 from oracle import oracle as O
 
@@ -180,3 +187,60 @@ def test_fwave_form_matches_reference_flux2fw(coracle, mx, my, strong, mth):
                                 mth, fwave=True)
             P.record(case + "/trans%d" % trans, b, cb)
             assert np.array_equal(a, b) and ca == cb
+
+
+class _RefClassic:
+    """the three libref_classic builds behind the call surface of COracle"""
+
+    def __init__(self):
+        r1, r2, r3 = O.RefClassic1D(), O.RefClassic2D(), O.RefClassic3D()
+        self.step1, self.step2ds, self.step2, self.step3ds, self.step3 = r1.step1, r2.step2ds, r2.step2, r3.step3ds, r3.step3
+
+    @staticmethod
+    def available():
+        return all([O.RefClassic1D.available(), O.RefClassic1D.available(fwave=True), O.RefClassic2D.available(),
+                    O.RefClassic2D.available(fwave=True), O.RefClassic3D.available()])
+
+
+@pytest.fixture(scope="module")
+def refclassic():
+    return _RefClassic() if _RefClassic.available() else None
+
+
+def _check_block(coracle, refclassic, dim, block):
+    """every group of the block: the oracle equals the pin, and the live reference build where there is one"""
+    failed = []
+    for key, g in RC.groups(dim, block):
+        a, ca = RC.run_host(coracle, g)
+        assert not np.isnan(a).any() and (ca > 0).all(), key
+        if refclassic is not None:
+            b, cb = RC.run_host(refclassic, g)
+            assert not np.isnan(b).any(), key
+            P.record(key, b, cb)
+            if not (np.array_equal(a, b) and np.array_equal(ca, cb)):
+                failed.append(key + " (live build)")
+        try:
+            P.check(key, a, ca)
+        except AssertionError:
+            failed.append(key)
+    assert not failed, "%d groups differ from the reference: %s" % (len(failed), ", ".join(failed[:8]))
+
+
+@pytest.mark.parametrize("block", RC.blocks(1), ids=RC.block_id)
+def test_step1_matches_reference_step(coracle, refclassic, block):
+    """step1.f / step1fw.f around the restated 1-D solvers: every limiter, order 1 and 2, with and without capa"""
+    _check_block(coracle, refclassic, 1, block)
+
+
+@pytest.mark.parametrize("block", RC.blocks(2), ids=RC.block_id)
+def test_step2_aux_rows_match_reference_step(coracle, refclassic, block):
+    """step2ds.f / step2.f with flux2.f or flux2fw.f around the restated 2-D solvers: aux1 / aux2 / aux3 rows handed to
+    rpn2 / rpt2 with imp, capa as component maux+1, dimension-split ids 1, 2 and unsplit trans 0, 1, 2"""
+    _check_block(coracle, refclassic, 2, block)
+
+
+@pytest.mark.parametrize("block", RC.blocks(3), ids=RC.block_id)
+def test_step3_matches_reference_step(coracle, refclassic, block):
+    """step3.f + flux3.f in all six transverse modes and step3ds.f in its three directions (with mcapa too) around the
+    restated 3-D solvers"""
+    _check_block(coracle, refclassic, 3, block)

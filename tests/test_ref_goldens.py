@@ -79,7 +79,8 @@ def test_oracle_flux2fw_form(coracle, which):
     """flux2fw.f (classic2fw: step2ds.f / step2.f linked with flux2fw.f) built from the reference tree with the vendored
     Euler rpn2/rpt2: the oracle's fwave=1 path must reproduce the reference's own bits.  This pins the ARITHMETIC of
     flux2fw.f:145-152 (dsign(1,s) in the correction); the HIP f-wave kernels are held to the oracle by
-    tests/test_fwave.py.  (step1fw.f stays unpinned by a reference build: no rp1 lies in the reference tree.)"""
+    tests/test_fwave.py.  (step1fw.f, and flux2fw.f with aux rows, are pinned by the reference's Fortran built around the
+    restated f-wave solvers: tests/test_oracle_vs_ref.py, tests/test_gpu_ref_pins.py -- the step, not the solver formulas.)"""
     z = load("ref_flux2fw.npz")
     mx, my, shape, dx, dy, dt = shapes(z, 2)
     if which.startswith("ids"):
