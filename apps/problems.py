@@ -764,3 +764,172 @@ def rotating_flow(pyclaw, n=64, solver_type='classic', tfinal=0.3, run=True):
     if run:
         claw.run()
     return claw
+
+
+# ---------------------------------------------------------------------------------------------------
+# Cell functions that read neighbour cells (reach > 0: qn / auxn), each with its numpy twin.  A twin forms the right-hand
+# side from a padded copy of the OLD interior and then assigns, in the body's operation order, so that the 'exact'
+# arithmetic gives the same bits.
+# ---------------------------------------------------------------------------------------------------
+def pad_like_bcs(a, reach, modes, normal0=1):
+    """The interior array a[m, ...] with `reach` ghost layers, filled like apply_q_bcs: per dimension (x first, so the
+    corners match), lower then upper, each side by np.pad in the mode that equals its boundary condition --
+    'wrap' (periodic), 'edge' (zero-order extrapolation), 'wall' (mirrored, the normal component normal0 + idim negated),
+    or a sequence of one constant per component (a constant inflow state).  modes[idim] = (lower, upper) or one mode."""
+    for idim in range(a.ndim - 1):
+        mode = modes[idim]
+        lower, upper = (mode, mode) if isinstance(mode, str) else mode
+        axis = idim + 1
+        strips = []
+        for side, md in ((0, lower), (1, upper)):
+            width = [(0, 0)] * a.ndim
+            width[axis] = (reach, 0) if side == 0 else (0, reach)
+            take = [slice(None)] * a.ndim
+            take[axis] = slice(0, reach) if side == 0 else slice(a.shape[axis], None)
+            if isinstance(md, str):
+                g = np.pad(a, width, mode={'wrap': 'wrap', 'edge': 'edge', 'wall': 'symmetric'}[md])[tuple(take)].copy()
+                if md == 'wall':
+                    g[normal0 + idim] = -g[normal0 + idim]
+            else:
+                g = np.stack([np.pad(a[m], width[1:], mode='constant', constant_values=float(v))[tuple(take[1:])]
+                              for m, v in enumerate(md)])
+            strips.append(g)
+        a = np.concatenate([strips[0], a, strips[1]], axis=axis)
+    return a
+
+
+def shifted(qb, reach, off):
+    """the interior-sized window of the padded array qb at index offset off[idim]"""
+    return qb[(slice(None),) + tuple(slice(reach + o, qb.shape[k + 1] - reach + o) for k, o in enumerate(off))]
+
+
+# q_t = nu * Laplace(q), forward Euler over c.dt, second-order differences: 5 points in 2-D, 7 in 3-D.  p[0] = nu,
+# p[1] = the number of leading components it acts on (0: all of them)
+DIFFUSION_2D_CELL_SRC = """
+const int nm = p[1] > 0.0 ? (int)p[1] : MEQN;
+for (int m = 0; m < MEQN; m++) {
+    if (m >= nm) break;
+    const double lx = (qn(m, 1, 0) - 2.0 * qn(m, 0, 0) + qn(m, -1, 0)) / (c.d[0] * c.d[0]);
+    const double ly = (qn(m, 0, 1) - 2.0 * qn(m, 0, 0) + qn(m, 0, -1)) / (c.d[1] * c.d[1]);
+    q[m] = q[m] + c.dt * p[0] * (lx + ly);
+}
+"""
+
+DIFFUSION_3D_CELL_SRC = """
+const int nm = p[1] > 0.0 ? (int)p[1] : MEQN;
+for (int m = 0; m < MEQN; m++) {
+    if (m >= nm) break;
+    const double lx = (qn(m, 1, 0, 0) - 2.0 * qn(m, 0, 0, 0) + qn(m, -1, 0, 0)) / (c.d[0] * c.d[0]);
+    const double ly = (qn(m, 0, 1, 0) - 2.0 * qn(m, 0, 0, 0) + qn(m, 0, -1, 0)) / (c.d[1] * c.d[1]);
+    const double lz = (qn(m, 0, 0, 1) - 2.0 * qn(m, 0, 0, 0) + qn(m, 0, 0, -1)) / (c.d[2] * c.d[2]);
+    q[m] = q[m] + c.dt * p[0] * (lx + ly + lz);
+}
+"""
+
+
+def diffusion_src(nu, modes, ncomp=0, calls=None):
+    """numpy twin of DIFFUSION_2D_CELL_SRC / DIFFUSION_3D_CELL_SRC as a step_src(solver, state, dt); modes as for
+    pad_like_bcs.  calls: a list that gets one entry per call."""
+    def step_src(solver, state, dt):
+        if calls is not None:
+            calls.append(dt)
+        q = state.q
+        nd = q.ndim - 1
+        nm = ncomp if ncomp > 0 else q.shape[0]
+        qb = pad_like_bcs(q, 1, modes)
+        zero = (0,) * nd
+        lap = 0.0
+        for k in range(nd):
+            up, dn = tuple(int(j == k) for j in range(nd)), tuple(-int(j == k) for j in range(nd))
+            lk = (shifted(qb, 1, up) - 2.0 * shifted(qb, 1, zero) + shifted(qb, 1, dn)) / (state.grid.d[k] * state.grid.d[k])
+            lap = lk if k == 0 else lap + lk
+        q[:nm] = (q + dt * nu * lap)[:nm]
+    return step_src
+
+
+# SharpClaw dq_src: dt * nu * (4th-order Laplacian), reach = 2, 1-D and 2-D.  p[0] = nu
+LAPLACIAN4_DQ_CELL_SRC = """
+for (int m = 0; m < MEQN; m++) {
+    double lap = (-qn(m, -2) + 16.0 * qn(m, -1) - 30.0 * qn(m, 0) + 16.0 * qn(m, 1) - qn(m, 2)) / (12.0 * c.d[0] * c.d[0]);
+#if NDIM > 1
+    lap = lap + (-qn(m, 0, -2) + 16.0 * qn(m, 0, -1) - 30.0 * qn(m, 0, 0) + 16.0 * qn(m, 0, 1) - qn(m, 0, 2))
+                / (12.0 * c.d[1] * c.d[1]);
+#endif
+    dq[m] = c.dt * p[0] * lap;
+}
+"""
+
+
+def laplacian4_dq_src(nu, modes):
+    """numpy twin of LAPLACIAN4_DQ_CELL_SRC as a dq_src(solver, state, dt)"""
+    def dq_src(solver, state, dt):
+        q = state.q
+        nd = q.ndim - 1
+        qb = pad_like_bcs(q, 2, modes)
+        lap = 0.0
+        for k in range(nd):
+            at = lambda o: shifted(qb, 2, tuple(o * int(j == k) for j in range(nd)))
+            d = state.grid.d[k]
+            lk = (-at(-2) + 16.0 * at(-1) - 30.0 * at(0) + 16.0 * at(1) - at(2)) / (12.0 * d * d)
+            lap = lk if k == 0 else lap + lk
+        return dt * nu * lap
+    return dq_src
+
+
+# a force from the x gradient of a potential kept in aux(1), central difference: p[0] = its strength
+AUX_GRADIENT_CELL_SRC = """
+q[1] -= c.dt * p[0] * (auxn(0, 1, 0) - auxn(0, -1, 0)) / (2.0 * c.d[0]);
+"""
+
+
+def aux_gradient_src(g):
+    """numpy twin of AUX_GRADIENT_CELL_SRC, on the solver's ghosted aux (solver.auxbc)"""
+    def step_src(solver, state, dt):
+        mbc = solver.mbc
+        a = solver.auxbc[0][:, mbc:-mbc]
+        n = state.q.shape[1]
+        state.q[1] -= dt * g * (a[mbc + 1:mbc + 1 + n] - a[mbc - 1:mbc - 1 + n]) / (2.0 * state.grid.d[0])
+    return step_src
+
+
+# the four diagonal neighbours' mean: what shows the corner ghost cells
+DIAGONAL_MEAN_CELL_HOOK = "q[0] = 0.25 * (qn(0, 1, 1) + qn(0, -1, 1) + qn(0, 1, -1) + qn(0, -1, -1));"
+
+
+def diagonal_mean_hook(modes):
+    """numpy twin of DIAGONAL_MEAN_CELL_HOOK as a start_step(solver, solution)"""
+    def start_step(solver, solution):
+        q = solution.state.q
+        qb = pad_like_bcs(q, 1, modes)
+        q[0] = (0.25 * (shifted(qb, 1, (1, 1)) + shifted(qb, 1, (-1, 1)) + shifted(qb, 1, (1, -1)) + shifted(qb, 1, (-1, -1))))[0]
+    return start_step
+
+
+def advection2D(pyclaw, mx=37, my=21, bc_y=None):
+    """A blob carried by the constant velocity (0.5, 1) on the unit square, periodic in x and (unless bc_y is given) in
+    y, dimension-split: (solver, solution), not set up."""
+    solver = pyclaw.ClawSolver2D()
+    solver.rp = pyclaw.riemann.rp_advection_2d
+    solver.mwaves = 1
+    solver.dim_split = True
+    solver.limiters = pyclaw.limiters.tvd.MC
+    solver.bc_lower[0] = solver.bc_upper[0] = pyclaw.BC.periodic
+    solver.bc_lower[1] = solver.bc_upper[1] = pyclaw.BC.periodic if bc_y is None else bc_y
+    grid = pyclaw.Grid([pyclaw.Dimension('x', 0.0, 1.0, mx), pyclaw.Dimension('y', 0.0, 1.0, my)])
+    state = pyclaw.State(grid, 1)
+    state.aux_global['u'] = 0.5
+    state.aux_global['v'] = 1.0
+    X, Y = grid.c_center
+    state.q[0] = np.exp(-30.0 * ((X - 0.3) ** 2 + (Y - 0.6) ** 2)) + 0.1 * X + 0.05 * Y * Y
+    return solver, pyclaw.Solution(state)
+
+
+def fixed_steps(solver, solution, nsteps, dt):
+    """setup(), nsteps steps of length dt, teardown(): the final q"""
+    solver.dt_variable = False
+    solver.setup(solution)
+    solver.dt = dt
+    for n in range(nsteps):
+        solver.evolve_to_time(solution)
+    solver.teardown()
+    return solution.state.q.copy('F')

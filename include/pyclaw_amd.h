@@ -335,6 +335,7 @@ int pcl_fuse_source(pcl_solver *s, int src_id, const double *params, int nparams
 #define PCL_CELLFN_START_STEP 3
 #define PCL_CELLFN_BC 4         /* a boundary condition: its own body surface and launch, pcl_cellbc_apply below */
 #define PCL_CELLFN_MAX_PARAMS 16
+#define PCL_CELLFN_MAX_REACH 8  /* the largest mbc the library takes */
 typedef struct pcl_cellfn pcl_cellfn;
 /* Compile (host only, no device needed).  Functions are cached per process by (kind, body, preamble, meqn, maux, ndim,
  * math, writes_aux): compiling the same text again returns the cached handle with one more reference.  *code_size (may
@@ -342,6 +343,17 @@ typedef struct pcl_cellfn pcl_cellfn;
  * writes_aux: aux[] is writable in the body (PCL_CELLFN_START_STEP only, maux > 0). */
 int pcl_cellfn_compile(int kind, const char *body, const char *preamble, int meqn, int maux, int ndim, int math,
                        int writes_aux, pcl_cellfn **out, long *code_size);
+/* The same with neighbour reads (kinds _STEP_SRC, _DQ_SRC, _START_STEP; writes_aux = 0).  reach, 0..PCL_CELLFN_MAX_REACH,
+ * is the largest index offset in any dimension at which the body reads other cells, and part of the cache key;
+ * reach = 0 IS pcl_cellfn_compile (same options, key and handle).  With reach > 0 the body also sees
+ *     qn(m, di[, dj[, dk]])     component m of the cell at that index offset from the lane's own, AS IT WAS WHEN THE
+ *                               LAUNCH BEGAN (qn(m, 0) is the cell's own old value); ghost cells up to reach layers
+ *     auxn(m, di[, dj[, dk]])   the same for aux (maux > 0)
+ * Offsets are clamped to [-reach, reach] and m to the components there are, so whatever the body passes no read leaves
+ * the ghosted block as long as reach <= cfg.mbc, which pcl_cellfn_apply checks.  The ghost cells read are the caller's:
+ * fill them (pcl_halo_exchange, pcl_bc ...) in front of the launch.  qn() in a reach = 0 body is a compile error. */
+int pcl_cellfn_compile_reach(int kind, const char *body, const char *preamble, int meqn, int maux, int ndim, int math,
+                             int writes_aux, int reach, pcl_cellfn **out, long *code_size);
 int pcl_cellfn_release(pcl_cellfn *f);          /* drops one reference; the compiled function stays cached for
                                                  * the life of the process (host memory: its code object) */
 /* compiles done and cache hits of this process */
@@ -353,7 +365,10 @@ int pcl_cellfn_check(const pcl_cellfn *f, int meqn, int maux, int ndim);
 int pcl_cellfn_geometry(pcl_solver *s, const double *lower, const int *nstart);
 /* One launch on the solver's stream over the interior cells of the SELECTED register (pcl_select); a dq_src reads the
  * selected register and adds into PCL_REG_DQ.  params[nparams <= 16] travel by value with the launch.  Like pcl_src it
- * makes the next one-kernel step compute every tile and the next step exchange its halo again.  The module is loaded
+ * makes the next one-kernel step compute every tile and the next step exchange its halo again.  A function compiled
+ * with reach > 0 needs reach <= cfg.mbc (PCL_EINVAL otherwise); a step_src / start_step of that kind first copies the
+ * selected register into a scratch array of the handle (allocated at the first such launch, freed by pcl_destroy), on
+ * the solver's stream, reads that copy and stores into the register; a dq_src reads the register itself.  The module is loaded
  * into the handle's device on first use and unloaded by pcl_destroy.  After a function that wrote aux the caller
  * refreshes the aux ghost cells: pcl_halo_exchange_aux, then pcl_bc_aux per dimension and side. */
 int pcl_cellfn_apply(pcl_solver *s, pcl_cellfn *f, double t, double dt, const double *params, int nparams);

@@ -94,6 +94,8 @@ PROTOTYPES = {
     "pcl_fuse_source": (C.c_int, [C.c_void_p, C.c_int, dp, C.c_int]),
     "pcl_cellfn_compile": (C.c_int, [C.c_int, C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                      C.POINTER(C.c_void_p), C.POINTER(C.c_long)]),
+    "pcl_cellfn_compile_reach": (C.c_int, [C.c_int, C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                           C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_long)]),
     "pcl_cellfn_release": (C.c_int, [C.c_void_p]),
     "pcl_cellfn_stats": (C.c_int, [C.POINTER(C.c_long), C.POINTER(C.c_long)]),
     "pcl_cellfn_check": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int]),

@@ -54,14 +54,23 @@ class CellSource(CellFunction, DeviceSource):
 
     A cell source is never fused into the last pass of the hyperbolic step: it is one launch of its own and costs one
     read and one write of the q components it assigns (and of nothing else).  Like any unfused source it keeps
-    exchange-ahead off in a decomposed run."""
+    exchange-ahead off in a decomposed run.
+
+    ``reach > 0`` gives the body ``qn`` / ``auxn`` (see ``CellFunction``) for a source that is a difference of
+    neighbouring cells, e.g. ``q[0] += c.dt * p[0] * (qn(0, 1) - 2.0 * qn(0, 0) + qn(0, -1)) / (c.d[0] * c.d[0]);``.
+    Each launch -- the Godunov one and both Strang halves -- is then preceded by ``apply_q_bcs`` on the current state
+    and by a copy of q into the handle's snapshot array, which is what the body reads: one read and one write of all
+    ``meqn`` planes on top of the kernel's own."""
 
     kind = 1
 
-    def __init__(self, body, params=(), preamble=""):
-        CellFunction.__init__(self, body, params, preamble)
+    def __init__(self, body, params=(), preamble="", reach=0):
+        CellFunction.__init__(self, body, params, preamble, reach=reach)
 
     def apply(self, solver, state, dt):
+        if self.reach > 0:
+            self._check_reach(solver)
+            solver.apply_q_bcs(state)          # the frame left behind a hyperbolic step is stale
         self.launch(solver, state.t, dt)
 
 
@@ -234,6 +243,7 @@ class ClawSolver(Solver):
         user_rp = isinstance(rp, riemann.CellRiemann)
         if user_rp:
             self._check_user_rp(state)
+        self._check_cell_functions(state)
         if rp.ndim != self.ndim:
             raise Exception("Riemann solver %s is %d-D but the solver is %d-D" % (rp.name, rp.ndim, self.ndim))
         if rp.mwaves != self.mwaves:

@@ -5,9 +5,18 @@
 // The wrapper kernel below is kept as text.  The user's preamble and body are spliced into it, MEQN / MAUX / NDIM and
 // the kind arrive as -D constants (q[MEQN] and aux[MAUX] unroll into registers), and hiprtc compiles the whole for
 // PCL_ARCH without asking any device.  One lane = one interior cell, x fastest, 256 threads per workgroup; ghost cells
-// are never read or written.  A component is stored only where its bits differ from the bits that were loaded: for a
+// are never written.  A component is stored only where its bits differ from the bits that were loaded: for a
 // component the body never assigns the comparison folds at compile time, and the store and then the load disappear
 // from the code object (the built-in source kernels leave such planes alone in the same way).
+//
+// Neighbour reads (-DREACH=n, n > 0; pcl_cellfn_compile_reach): the body also gets qn(m, di, dj, dk) and auxn(...),
+// component m of the cell at that index offset.  Every read of q, the lane's own cell included, then comes from
+// pcl_cell_args.snap -- a copy of the selected register that pcl_cellfn_apply takes in front of the launch (dq_src: the
+// register itself, which that kind cannot write) -- and the stores go to the register: every lane sees the state as it
+// was when the launch began.  Offsets are clamped to [-REACH, REACH] and REACH <= mbc is checked at the launch, so a read
+// lands in the ghosted block whatever the body passes; the ghost cells it may land in are the caller's to fill.  Without
+// -DREACH the text compiles to what it compiled to before there was one (qn / auxn are stubs that fail to instantiate
+// with a message that names reach).
 //
 // A fourth kind, the boundary condition (PCL_CELLFN_BC; pyclaw.CellBC), has a wrapper of its own further
 // down: one lane = one ghost cell of one side, the body's only neighbour reads go inward along the lane's own normal line.
@@ -44,6 +53,9 @@ struct pcl_cell_args {
     double lower[3], d[3];
     double t, dt;
     double p[PCL_CELLFN_MAX_PARAMS];
+    // reach > 0 only (a reach = 0 launch passes the bytes in front of it): what qn() reads, laid out like q -- the
+    // snapshot of the selected register taken in front of the launch, or (dq_src, q const) the register itself
+    const double *snap;
 };
 
 // the same for the boundary-condition wrapper (pcl_cellbc below)
@@ -64,6 +76,9 @@ struct pcl_cellbc_args {
 namespace pcl {
 
 static const char *const kCellfnHead = R"PCLSRC(
+#ifndef REACH
+#define REACH 0
+#endif
 struct pcl_cell {
     double t, dt;
     int i[NDIM];
@@ -82,6 +97,9 @@ struct pcl_cell_args {
     double lower[3], d[3];
     double t, dt;
     double p[16];
+#if REACH > 0
+    const double *snap;
+#endif
 };
 #define PCL_MAUXN (MAUX > 0 ? MAUX : 1)
 #if KIND == 2
@@ -94,13 +112,56 @@ struct pcl_cell_args {
 #else
 #define PCL_AUX_QUAL const
 #endif
+#if REACH > 0
+// neighbour reads: q and aux point at the lane's own cell of the array being read.  Every offset is clamped to
+// [-REACH, REACH] and m to the components there are, so with REACH <= mbc (pcl_cellfn_apply) no argument reaches
+// outside the ghosted block; for literal arguments the clamps fold away.
+struct pcl_near {
+    const double *q, *aux;
+    long pitch, plane, slab;
+    static __device__ __forceinline__ int cl(int v, int lo, int hi) { return v < lo ? lo : v > hi ? hi : v; }
+    __device__ __forceinline__ long at(int di, int dj, int dk) const {
+        long o = cl(di, -REACH, REACH);
+        if (NDIM > 1) o += (long)cl(dj, -REACH, REACH) * pitch;
+        if (NDIM > 2) o += (long)cl(dk, -REACH, REACH) * slab;
+        return o;
+    }
+    __device__ __forceinline__ double qn(int m, int di, int dj, int dk) const {
+        return q[cl(m, 0, MEQN - 1) * plane + at(di, dj, dk)];
+    }
+    __device__ __forceinline__ double auxn(int m, int di, int dj, int dk) const {
+        return MAUX > 0 ? aux[cl(m, 0, PCL_MAUXN - 1) * plane + at(di, dj, dk)] : 0.0;
+    }
+};
+#define PCL_NEAR_PARAM , const pcl_near &pcl_nb
+#else
+// reach = 0: the names exist so that a body which uses them is told why it does not compile
+template <class...> struct pcl_no_reach { static constexpr bool value = false; };
+template <class... A> __device__ double qn(A...) {
+    static_assert(pcl_no_reach<A...>::value, "qn() reads neighbour cells: give the cell function reach > 0");
+    return 0.0;
+}
+template <class... A> __device__ double auxn(A...) {
+    static_assert(pcl_no_reach<A...>::value, "auxn() reads neighbour cells: give the cell function reach > 0");
+    return 0.0;
+}
+#define PCL_NEAR_PARAM
+#endif
 )PCLSRC";
 
 // between preamble and body
 static const char *const kCellfnOpen = R"PCLSRC(
 __device__ __forceinline__ void pcl_cell_body(PCL_Q_QUAL double (&q)[MEQN], double (&dq)[MEQN],
                                               PCL_AUX_QUAL double (&aux)[PCL_MAUXN], const pcl_cell &c,
-                                              const double (&p)[16]) {
+                                              const double (&p)[16] PCL_NEAR_PARAM) {
+#if REACH > 0
+    const auto qn = [&pcl_nb](int m, int di, int dj = 0, int dk = 0) { return pcl_nb.qn(m, di, dj, dk); };
+    (void)qn;
+#if MAUX > 0
+    const auto auxn = [&pcl_nb](int m, int di, int dj = 0, int dk = 0) { return pcl_nb.auxn(m, di, dj, dk); };
+    (void)auxn;
+#endif
+#endif
 )PCLSRC";
 
 static const char *const kCellfnTail = R"PCLSRC(
@@ -126,9 +187,21 @@ extern "C" __global__ void __launch_bounds__(256) pcl_cellfn(const pcl_cell_args
         c.x[n] = a.lower[n] + (c.i[n] + 0.5) * a.d[n];
     }
     double q0[MEQN], q[MEQN], dq[MEQN], aux0[PCL_MAUXN], aux[PCL_MAUXN];
+#if REACH > 0
+    // Every read of q, the lane's own cell included, comes from a.snap: the state as it was when the launch began.  The
+    // stores below go to a.q (a.dq), another array, so no lane sees what a lane of this launch stored.
+    for (int m = 0; m < MEQN; m++) { q0[m] = a.snap[m * a.plane + g]; q[m] = q0[m]; dq[m] = 0.0; }
+    for (int m = 0; m < PCL_MAUXN; m++) { aux0[m] = MAUX > 0 ? a.aux[m * a.plane + g] : 0.0; aux[m] = aux0[m]; }
+    pcl_near nb;
+    nb.q = a.snap + g;
+    nb.aux = MAUX > 0 ? a.aux + g : nullptr;
+    nb.pitch = a.pitch; nb.plane = a.plane; nb.slab = a.slab;
+    pcl_cell_body(q, dq, aux, c, a.p, nb);
+#else
     for (int m = 0; m < MEQN; m++) { q0[m] = a.q[m * a.plane + g]; q[m] = q0[m]; dq[m] = 0.0; }
     for (int m = 0; m < PCL_MAUXN; m++) { aux0[m] = MAUX > 0 ? a.aux[m * a.plane + g] : 0.0; aux[m] = aux0[m]; }
     pcl_cell_body(q, dq, aux, c, a.p);
+#endif
 #if KIND == 2
     for (int m = 0; m < MEQN; m++) {
         const double old = a.dq[m * a.plane + g];
@@ -315,7 +388,7 @@ static inline int hiprtc_load(std::string &err) {
 // ---- compiled functions, cached per process --------------------------------------------------------------------
 struct pcl_cellfn {
     long id = 0;                // never reused: the solvers' loaded modules are keyed by it
-    int kind = 0, meqn = 0, maux = 0, ndim = 0, math = 0, writes_aux = 0;
+    int kind = 0, meqn = 0, maux = 0, ndim = 0, math = 0, writes_aux = 0, reach = 0;
     int refs = 0;
     std::string key;
     std::vector<char> code;     // the code object
@@ -341,9 +414,11 @@ static inline CellfnCache &cellfn_cache() {
 }
 
 static inline std::string cellfn_key(int kind, const char *body, const char *preamble, int meqn, int maux, int ndim, int math,
-                                     int writes_aux) {
-    std::string k = std::to_string(kind) + "," + std::to_string(meqn) + "," + std::to_string(maux) + "," +
-                    std::to_string(ndim) + "," + std::to_string(math) + "," + std::to_string(writes_aux) + ",";
+                                     int writes_aux, int reach) {
+    // (reach = 0 keeps the key it always had: that one starts with a digit)
+    std::string k = reach > 0 ? "reach=" + std::to_string(reach) + ";" : std::string();
+    k += std::to_string(kind) + "," + std::to_string(meqn) + "," + std::to_string(maux) + "," +
+         std::to_string(ndim) + "," + std::to_string(math) + "," + std::to_string(writes_aux) + ",";
     k += std::to_string(strlen(preamble)) + ":";
     k += preamble;
     k += body;
@@ -352,7 +427,7 @@ static inline std::string cellfn_key(int kind, const char *body, const char *pre
 
 // hiprtc compile of head + preamble + body + tail; math: 0 exact, 1 fast, 2 strict.  0 = ok, else err holds the log
 static inline int cellfn_build(int kind, const char *body, const char *preamble, int meqn, int maux, int ndim, int math,
-                               int writes_aux, std::vector<char> &code, std::string &err) {
+                               int writes_aux, int reach, std::vector<char> &code, std::string &err) {
     if (hiprtc_load(err)) return -1;
     HiprtcApi &a = hiprtc_api();
     const char *kname = cellfn_kind_name(kind);
@@ -372,11 +447,13 @@ static inline int cellfn_build(int kind, const char *body, const char *preamble,
     // exact / strict: what pclaw.hip itself is built with (no contraction; / and sqrt are IEEE either way)
     const std::string d_meqn = "-DMEQN=" + std::to_string(meqn), d_maux = "-DMAUX=" + std::to_string(maux),
                       d_ndim = "-DNDIM=" + std::to_string(ndim), d_kind = "-DKIND=" + std::to_string(kind),
-                      d_waux = "-DWRITES_AUX=" + std::to_string(writes_aux ? 1 : 0);
-    const char *opts[] = {"--offload-arch=" PCL_ARCH, "-O3", "-std=c++17",
-                          math == 1 ? "-ffp-contract=fast" : "-ffp-contract=off",
-                          d_meqn.c_str(), d_maux.c_str(), d_ndim.c_str(), d_kind.c_str(), d_waux.c_str()};
-    r = a.hiprtcCompileProgram(prog, (int)(sizeof(opts) / sizeof(opts[0])), opts);
+                      d_waux = "-DWRITES_AUX=" + std::to_string(writes_aux ? 1 : 0),
+                      d_reach = "-DREACH=" + std::to_string(reach);
+    std::vector<const char *> opts = {"--offload-arch=" PCL_ARCH, "-O3", "-std=c++17",
+                                      math == 1 ? "-ffp-contract=fast" : "-ffp-contract=off",
+                                      d_meqn.c_str(), d_maux.c_str(), d_ndim.c_str(), d_kind.c_str(), d_waux.c_str()};
+    if (reach > 0) opts.push_back(d_reach.c_str());       // reach = 0: the options it was always compiled with
+    r = a.hiprtcCompileProgram(prog, (int)opts.size(), opts.data());
     if (r != HIPRTC_SUCCESS) {
         size_t n = 0;
         std::string log;

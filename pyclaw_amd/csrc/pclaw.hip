@@ -1,6 +1,7 @@
 // pclaw.hip -- C ABI of libpyclaw_amd.so (see include/pyclaw_amd.h).
 // gfx950 only.  No CPU fallback: every entry point needs a HIP device.
 #include <hip/hip_runtime.h>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -95,6 +96,7 @@ struct pcl_solver {
     pcl::CellfnModules cellfn;
     double cf_lower[3] = {0.0, 0.0, 0.0};
     int cf_nstart[3] = {0, 0, 0};
+    double *cf_snap = nullptr;     // reach > 0: the copy of the selected register the launch reads, allocated at the first one
     // cfg.rp == PCL_RP_CELL: the user-written Riemann solver's module (cellrp.hpp, pcl_cellrp_attach)
     pcl::CellrpModule cellrp;
     // pcl_put_aux has been called: the aux allocation holds the caller's coefficients and not the zeros of pcl_create.
@@ -881,7 +883,7 @@ void pcl_destroy(pcl_solver *s) {
     if (s->hstream) hipStreamDestroy(s->hstream);
     for (auto &t : s->timed) { hipEventDestroy(t.a); hipEventDestroy(t.b); }
     for (auto &e : s->evpool) hipEventDestroy(e);
-    for (double *p : {s->q, s->t1, s->t2, s->t3, s->bak, s->aux, s->stage})
+    for (double *p : {s->q, s->t1, s->t2, s->t3, s->bak, s->aux, s->stage, s->cf_snap})
         if (p) hipFree(p - s->lead);
     for (int k = 1; k < 5; k++)
         if (s->sreg[k]) hipFree(s->sreg[k] - s->lead);
@@ -1652,6 +1654,12 @@ int pcl_src(pcl_solver *s, int src_id, double dt, const double *params, int npar
 // ---- cell functions (cellfn.hpp) ----------------------------------------------------------------------------------
 int pcl_cellfn_compile(int kind, const char *body, const char *preamble, int meqn, int maux, int ndim, int math,
                        int writes_aux, pcl_cellfn **out, long *code_size) {
+    return pcl_cellfn_compile_reach(kind, body, preamble, meqn, maux, ndim, math, writes_aux, 0, out, code_size);
+}
+
+// reach == 0 is pcl_cellfn_compile: the same compile options, key and handle
+int pcl_cellfn_compile_reach(int kind, const char *body, const char *preamble, int meqn, int maux, int ndim, int math,
+                             int writes_aux, int reach, pcl_cellfn **out, long *code_size) {
     if (!body || !out) return fail(PCL_EINVAL, "null argument");
     *out = nullptr;
     if (!preamble) preamble = "";
@@ -1662,10 +1670,18 @@ int pcl_cellfn_compile(int kind, const char *body, const char *preamble, int meq
     if (writes_aux && kind != PCL_CELLFN_START_STEP)
         return fail(PCL_EINVAL, "pcl_cellfn_compile: only a start_step cell function may write aux");
     if (writes_aux && maux == 0) return fail(PCL_EINVAL, "pcl_cellfn_compile: writes_aux needs an aux array (maux == 0)");
+    if (reach < 0 || reach > PCL_CELLFN_MAX_REACH)
+        return fail(PCL_EINVAL, "pcl_cellfn_compile_reach: reach must be 0.." + std::to_string(PCL_CELLFN_MAX_REACH) +
+                                    " (the largest mbc the library takes), got " + std::to_string(reach));
+    if (reach > 0 && kind == PCL_CELLFN_BC)
+        return fail(PCL_EINVAL, "pcl_cellfn_compile_reach: a boundary-condition cell function takes no reach (it has qin and auxin)");
+    if (reach > 0 && writes_aux)
+        return fail(PCL_EINVAL, "pcl_cellfn_compile_reach: writes_aux with reach > 0 is not built (neighbours would read aux "
+                                "while it is written: a second snapshot)");
     writes_aux = writes_aux ? 1 : 0;
     CellfnCache &c = cellfn_cache();
     std::lock_guard<std::mutex> lock(c.mu);
-    const std::string key = cellfn_key(kind, body, preamble, meqn, maux, ndim, math, writes_aux);
+    const std::string key = cellfn_key(kind, body, preamble, meqn, maux, ndim, math, writes_aux, reach);
     auto it = c.by_key.find(key);
     pcl_cellfn *f = nullptr;
     if (it != c.by_key.end()) {
@@ -1674,10 +1690,11 @@ int pcl_cellfn_compile(int kind, const char *body, const char *preamble, int meq
     } else {
         std::vector<char> code;
         std::string err;
-        if (cellfn_build(kind, body, preamble, meqn, maux, ndim, math, writes_aux, code, err)) return fail(PCL_EINVAL, err);
+        if (cellfn_build(kind, body, preamble, meqn, maux, ndim, math, writes_aux, reach, code, err)) return fail(PCL_EINVAL, err);
         f = new pcl_cellfn();
         f->id = c.next_id++;
         f->kind = kind; f->meqn = meqn; f->maux = maux; f->ndim = ndim; f->math = math; f->writes_aux = writes_aux;
+        f->reach = reach;
         f->key = key;
         f->code.swap(code);
         c.by_key[key] = f;
@@ -1977,7 +1994,7 @@ int pcl_cellfn_apply(pcl_solver *s, pcl_cellfn *f, double t, double dt, const do
     pcl_cell_args a;
     memset(&a, 0, sizeof(a));
     long id = 0;
-    int kind = 0;
+    int kind = 0, reach = 0;
     const void *code = nullptr;
     {
         CellfnCache &c = cellfn_cache();
@@ -1985,10 +2002,15 @@ int pcl_cellfn_apply(pcl_solver *s, pcl_cellfn *f, double t, double dt, const do
         if (int rc = cellfn_check_locked(c, f, s->cfg.meqn, s->cfg.maux, s->cfg.ndim)) return rc;
         id = f->id;
         kind = f->kind;
+        reach = f->reach;
         code = f->code.data();        // stays put while the caller holds its reference
     }
     if (kind == PCL_CELLFN_BC)
         return fail(PCL_EINVAL, "pcl_cellfn_apply: a boundary-condition cell function runs through pcl_cellbc_apply");
+    // qn() clamps its offsets to [-reach, reach]: with reach <= mbc every read stays inside the ghosted block
+    if (reach < 0 || reach > s->cfg.mbc)
+        return fail(PCL_EINVAL, "pcl_cellfn_apply: the cell function reads " + std::to_string(reach) +
+                                    " cells away (reach) and the solver has mbc = " + std::to_string(s->cfg.mbc) + " ghost layers");
     if (kind == PCL_CELLFN_DQ_SRC && s->cfg.kind != PCL_KIND_SHARPCLAW)
         return fail(PCL_EINVAL, "pcl_cellfn_apply: a dq_src cell function needs a SharpClaw solver (the dq register)");
     if (s->cfg.maux > 0 && !s->aux) return fail(PCL_ESTATE, "pcl_cellfn_apply: no aux array on the device");
@@ -2012,7 +2034,21 @@ int pcl_cellfn_apply(pcl_solver *s, pcl_cellfn *f, double t, double dt, const do
     a.dt = dt;
     for (int k = 0; k < nparams; k++) a.p[k] = params[k];
     if (a.n[1] > 65535 || a.n[2] > 65535) return fail(PCL_EINVAL, "pcl_cellfn_apply: more than 65535 rows or planes");
-    size_t size = sizeof(a);
+    if (reach > 0 && kind == PCL_CELLFN_DQ_SRC) {
+        a.snap = cur(s);                  // q is const in a dq_src and the stores go to the dq register
+    } else if (reach > 0) {
+        // the state as it is now, ghost frame and all, for every read of the launch; the kernel stores into cur(s)
+        const size_t qbytes = (size_t)s->total * sizeof(double);
+        if (!s->cf_snap) {
+            double *raw = nullptr;
+            HIP_TRY(hipMalloc((void **)&raw, qbytes + 16 * sizeof(double)));
+            s->cf_snap = raw + s->lead;
+        }
+        HIP_TRY(hipMemcpyAsync(s->cf_snap, cur(s), qbytes, hipMemcpyDeviceToDevice, s->stream));
+        a.snap = s->cf_snap;
+    }
+    // a reach = 0 kernel declares the struct without its last field
+    size_t size = reach > 0 ? sizeof(a) : offsetof(pcl_cell_args, snap);
     void *config[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &a, HIP_LAUNCH_PARAM_BUFFER_SIZE, &size, HIP_LAUNCH_PARAM_END};
     HIP_TRY(hipModuleLaunchKernel(fn, (unsigned)((a.n[0] + 255) / 256), (unsigned)a.n[1], (unsigned)a.n[2], 256, 1, 1,
                                   0, s->stream, nullptr, config));

@@ -93,13 +93,17 @@ class CellDqSource(CellFunction, DeviceDqSource):
     step length.
 
     It is never fused into the last pass of a stage: every stage runs its directional passes, this launch (one read of
-    q, one read and write of deltaq) and the Runge-Kutta combination as separate kernels."""
+    q, one read and write of deltaq) and the Runge-Kutta combination as separate kernels.
+
+    ``reach > 0`` gives the body ``qn`` / ``auxn`` (see ``CellFunction``), e.g. for a 4th-order Laplacian with
+    ``reach=2``.  The stage's register was filled by the ``apply_q_bcs(stage)`` of ``dq_hyperbolic`` just before and q
+    is const here, so the launch needs neither an extra ghost fill nor a snapshot: ``qn`` reads the register itself."""
 
     kind = 2
     src_id = 0
 
-    def __init__(self, body, params=(), preamble=""):
-        CellFunction.__init__(self, body, params, preamble)
+    def __init__(self, body, params=(), preamble="", reach=0):
+        CellFunction.__init__(self, body, params, preamble, reach=reach)
 
     def __call__(self, solver, state, dt):
         raise NotImplementedError("a CellDqSource runs on the device only")
@@ -319,6 +323,7 @@ class SharpClawSolver(Solver):
         if isinstance(rp, riemann.CellRiemann):
             raise NotImplementedError("CellRiemann: the SharpClaw solvers are not served: a user-written Riemann solver is "
                                       "compiled into the classic sweep kernel only (ClawSolver1D / ClawSolver2D)")
+        self._check_cell_functions(state)
         if rp.ndim != self.ndim or rp.mwaves != self.mwaves or rp.meqn != state.meqn:
             raise Exception("Riemann solver %s does not match ndim/mwaves/meqn of the problem" % rp.name)
         params = rp.all_params(state)

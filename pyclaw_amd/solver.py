@@ -78,18 +78,53 @@ class CellFunction(object):
     The body sees ``q[MEQN]``, ``aux[MAUX]`` (const), ``c.t``, ``c.dt``, the GLOBAL 0-based interior indices
     ``c.i[NDIM]``, the cell centre ``c.x[NDIM]`` (``lower + (i + 0.5) * d``, as ``grid.x.center`` computes it), the cell
     sizes ``c.d[NDIM]`` and ``p[]``, up to 16 doubles taken from ``params`` at every launch (reassigning ``params``
-    between steps never recompiles).  ``preamble`` holds helper functions.  Neighbour cells are not available.
+    between steps never recompiles).  ``preamble`` holds helper functions.
     ``solver.math`` is part of the compile: 'exact' and 'strict' evaluate the body without FMA contraction and with IEEE
     division and square root, 'fast' allows contraction.  A body that does not compile raises at ``setup()`` with the
-    compiler's log, whose line numbers are the body's own."""
+    compiler's log, whose line numbers are the body's own.
+
+    Neighbour cells (``CellSource``, ``CellDqSource``, ``CellStartStep``; a ``CellBC`` has ``qin`` / ``auxin`` instead):
+    ``reach``, an integer 0..8, is the largest index offset, in any dimension, at which the body reads other cells.  With
+    ``reach > 0`` the body also sees ``qn(m, di)`` (1-D), ``qn(m, di, dj)`` (2-D), ``qn(m, di, dj, dk)`` (3-D; trailing
+    offsets default to 0): component ``m`` of the cell at that index offset from the lane's own cell, and
+    ``auxn(m, di, dj, dk)``, the same for ``aux`` (when ``MAUX > 0``).
+
+    * Snapshot: every ``qn`` read returns the value the cell had when the launch began, the lane's own cell included
+      (``qn(m, 0, 0)`` is the old ``q[m]``) -- what a numpy callback computes when it forms the right-hand side from the
+      old array and then assigns.  No lane sees a value another lane of the same launch stored.  ``q[m]`` is initialised
+      with the old value and writable as before, and a component is still stored only where its bits changed.
+    * Ghost cells are valid: a read may land in a ghost cell, up to ``reach`` layers.  At the launch they hold what
+      ``apply_q_bcs`` gives for the state being read -- halo exchange, then the boundary conditions per dimension, lower
+      then upper, corners included, ``CellBC`` and Python callbacks too.  The solver runs that fill in front of a
+      ``step_src`` or ``start_step`` launch with ``reach > 0`` (the frame a hyperbolic step leaves behind is stale); a
+      ``dq_src`` reads the stage's register, which the stage's own ``apply_q_bcs`` has just filled.  The aux ghost cells
+      are the resident ones: uploaded with ``auxbc``, refreshed behind a ``start_step`` that writes aux.
+    * No read outside the allocation, whatever the body passes: the accessors clamp every offset to ``[-reach, reach]``
+      (a compile-time constant) and ``m`` to ``[0, MEQN - 1]`` (``MAUX - 1``); for literal arguments both clamps fold
+      away.  ``reach <= solver.mbc`` is required (2 for the classic solvers, ``(weno_order + 1) // 2`` for SharpClaw)
+      and checked at ``setup()``, at the first ``step()`` for a function assigned later, and by the library.
+    * ``writes_aux=True`` with ``reach > 0`` is refused: neighbours reading aux while it is written would need a second
+      snapshot.  ``qn`` in a ``reach=0`` body is a compile error that says so."""
 
     kind = 0
     MAX_PARAMS = 16
+    MAX_REACH = 8               # the largest mbc the library takes
 
-    def __init__(self, body, params=(), preamble="", writes_aux=False):
+    def __init__(self, body, params=(), preamble="", writes_aux=False, reach=0):
         self.body = str(body)
         self.preamble = str(preamble)
         self.writes_aux = bool(writes_aux)
+        if int(reach) != reach:
+            raise ValueError("reach must be an integer, got %r" % (reach,))
+        self.reach = int(reach)
+        if self.reach < 0:
+            raise ValueError("reach must be >= 0 (the largest index offset at which the body reads other cells), got %d"
+                             % self.reach)
+        if self.reach > self.MAX_REACH:
+            raise ValueError("reach must be <= %d, the largest mbc the library takes, got %d" % (self.MAX_REACH, self.reach))
+        if self.reach > 0 and self.writes_aux:
+            raise ValueError("writes_aux=True together with reach=%d is not built: a body that writes aux while neighbours "
+                             "read it would need a second snapshot" % self.reach)
         self.params = params
         self._fn = None            # pcl_cellfn handle and the constants it was compiled for
         self._key = None
@@ -111,16 +146,16 @@ class CellFunction(object):
         import ctypes
         if math not in ('exact', 'fast', 'strict'):
             raise Exception("math must be 'exact', 'fast' or 'strict'")
-        key = (int(meqn), int(maux), int(ndim), math, self.body, self.preamble, self.writes_aux)
+        key = (int(meqn), int(maux), int(ndim), math, self.body, self.preamble, self.writes_aux, self.reach)
         if self._fn is not None and self._key == key:
             return self
         if self.writes_aux and maux == 0:
             raise ValueError("writes_aux needs an aux array: the state has maux == 0")
         L = _lib.lib()
         fn, size = ctypes.c_void_p(), ctypes.c_long(0)
-        rc = L.pcl_cellfn_compile(self.kind, self.body.encode(), self.preamble.encode(), key[0], key[1], key[2],
-                                  {'exact': 0, 'fast': 1, 'strict': 2}[math], int(self.writes_aux), ctypes.byref(fn),
-                                  ctypes.byref(size))
+        rc = L.pcl_cellfn_compile_reach(self.kind, self.body.encode(), self.preamble.encode(), key[0], key[1], key[2],
+                                        {'exact': 0, 'fast': 1, 'strict': 2}[math], int(self.writes_aux), self.reach,
+                                        ctypes.byref(fn), ctypes.byref(size))
         _lib.check(rc)
         self.release()
         self._fn, self._key, self.code_size = fn, key, int(size.value)
@@ -139,10 +174,18 @@ class CellFunction(object):
             pass
 
     def _compile_for(self, solver, state):
+        self._check_reach(solver)
         return self.compile(state.meqn, state.maux, solver.ndim, solver.math)
 
+    def _check_reach(self, solver):
+        """Host only, before any device call: qn() may read ``reach`` ghost layers, the solver has ``mbc``."""
+        if self.reach > solver.mbc:
+            raise ValueError("%s: reach=%d, but the solver has mbc=%d ghost layers: a neighbour read could leave the "
+                             "block (reach <= solver.mbc is required)" % (type(self).__name__, self.reach, solver.mbc))
+
     def launch(self, solver, t, dt):
-        """One pass over the interior cells of the solver's selected register."""
+        """One pass over the interior cells of the solver's selected register.  With ``reach > 0`` the caller has filled
+        the ghost cells of that register (``apply``)."""
         # compiled here when the object was assigned after setup() or its text was changed since (a cache look-up otherwise)
         self._compile_for(solver, solver._state)
         p = self._params
@@ -155,7 +198,8 @@ class CellStartStep(CellFunction):
     """A before-step hook (``solver.start_step``) as a cell function: ``q`` is read/write, ``c.t`` is the time at the
     start of the step.  Accepted by the classic and the SharpClaw solvers in place of a Python
     ``start_step(solver, solution)``, and treated like one everywhere else: the step keeps a copied backup of q, and a
-    rejected step restores it.
+    rejected step restores it.  With ``reach > 0`` the body reads neighbour cells through ``qn`` / ``auxn`` (see
+    ``CellFunction``): the solver fills the ghost cells of the current state (``apply_q_bcs``) in front of the launch.
 
     ``writes_aux=True`` makes ``aux[MAUX]`` writable as well (time-dependent aux, e.g. ``aux[3] = q[0];`` for the
     p-system's strain copy).  After the launch the solver fills the aux ghost cells again on the device -- halo exchange
@@ -167,6 +211,9 @@ class CellStartStep(CellFunction):
     kind = 3
 
     def apply(self, solver, state):
+        if self.reach > 0:
+            self._check_reach(solver)
+            solver.apply_q_bcs(state)          # the frame left behind the last step is stale
         self.launch(solver, state.t, solver.dt)
         if self.writes_aux:
             solver._refresh_aux_ghosts(state)
@@ -349,6 +396,12 @@ class Solver(object):
     def _cell_functions(self):
         fns = [getattr(self, name, None) for name in ('start_step', 'step_src', 'dq_src', 'user_bc_lower', 'user_bc_upper')]
         return [f for f in fns if isinstance(f, CellFunction)]
+
+    def _check_cell_functions(self, state):
+        """What the cell functions among start_step / step_src / dq_src cannot be given, refused before the device
+        handle exists (setup(), next to the check of a user-written Riemann solver)."""
+        for fn in self._cell_functions():
+            fn._check_reach(self)
 
     def _setup_cell_functions(self, state):
         """Called by setup() once the device handle exists: tell the library where this block sits in the global grid
