@@ -220,6 +220,66 @@ wave[1][0] = a2 * zi;   wave[1][1] = a2; s[1] = auxr[1];
 for (int m = 0; m < 2; m++) { amdq[m] = s[0] * wave[0][m]; apdq[m] = s[1] * wave[1][m]; }
 """
 
+# F-wave solvers: pyclaw.CellRiemann(..., fwave=True) with solver.fwave = True.  The array the body assigns is fwave[][],
+# the pieces of the flux difference; between two EQUAL cells over different coefficients they are not zero, and every
+# interface is solved.
+
+# 1-D nonlinear elasticity in a layered medium, q = (eps, rho u), aux = (0, 1, 2) = (rho, K, stress-law flag): the
+# arithmetic of the built-in elasticity_fwave_1d (FwaveElastic<2> of rp.hpp: its precell of either cell, then its solve)
+# in its operation order.  ps_sigma / ps_sigmap are rp.hpp's: flag 1 is sigma = K eps, anything else exp(K eps) - 1.
+ELASTICITY_FWAVE_1D_RP = """
+const double rhol = auxl[0], rhor = auxr[0];
+const double unl = fdiv_ieee(ql[1], rhol), unr = fdiv_ieee(qr[1], rhor);
+const double sigl = ps_sigma(ql[0], auxl[1], auxl[2]), sigr = ps_sigma(qr[0], auxr[1], auxr[2]);
+const double cl = dsqrt(fdiv_ieee(ps_sigmap(ql[0], auxl[1], auxl[2]), rhol));
+const double cr = dsqrt(fdiv_ieee(ps_sigmap(qr[0], auxr[1], auxr[2]), rhor));
+const double zl = cl * rhol, zr = cr * rhor;
+const double du = unr - unl;
+const double dsig = sigr - sigl;
+const double zs = zl + zr;
+const double b1 = fdiv_ieee(-(zr * du + dsig), zs);
+const double b2 = fdiv_ieee(-(zl * du - dsig), zs);
+fwave[0][0] = b1; fwave[0][1] = b1 * zl; s[0] = -cl;
+fwave[1][0] = b2; fwave[1][1] = b2 * (-zr); s[1] = cr;
+for (int m = 0; m < 2; m++) { amdq[m] = fwave[0][m]; apdq[m] = fwave[1][m]; }
+"""
+
+# A solver the library does not have: conservative advection with a variable speed, q_t + (u(x) q)_x = 0, aux = (0,) =
+# u at the cell centre.  One f-wave, the flux difference itself; between equal cells it is (ur - ul) q, not zero.
+VC_ADVECTION_FWAVE_1D_RP = """
+const double ul = auxl[0], ur = auxr[0];
+fwave[0][0] = ur * qr[0] - ul * ql[0];
+s[0] = 0.5 * (ul + ur);
+if (s[0] >= 0.0) apdq[0] = fwave[0][0];
+else amdq[0] = fwave[0][0];
+"""
+
+# A solver the library does not have: 1-D shallow water over bathymetry, q = (h, hu), aux = (0,) = b, p = g.  Roe-type
+# speeds; the flux difference takes the source term g h b_x with it as g * (hl + hr)/2 * (br - bl) and is decomposed on the
+# eigenvectors (1, s0), (1, s1): a lake at rest (hu = 0, h + b constant) has f-waves that are zero, so it stays at rest --
+# the well-balanced solver people write f-wave solvers for.  h > 0.
+SHALLOW_BATHY_FWAVE_1D_RP = """
+const double g = p[0];
+const double hl = ql[0], hr = qr[0];
+const double ul = ql[1] / hl, ur = qr[1] / hr;
+const double hbar = 0.5 * (hl + hr);
+const double rl = dsqrt(hl), rr = dsqrt(hr);
+const double uhat = (rl * ul + rr * ur) / (rl + rr);
+const double chat = dsqrt(g * hbar);
+s[0] = uhat - chat; s[1] = uhat + chat;
+const double d0 = qr[1] - ql[1];
+const double d1 = (qr[1] * ur + 0.5 * g * hr * hr) - (ql[1] * ul + 0.5 * g * hl * hl) + g * hbar * (auxr[0] - auxl[0]);
+const double b1 = (s[1] * d0 - d1) / (s[1] - s[0]);
+const double b2 = (d1 - s[0] * d0) / (s[1] - s[0]);
+fwave[0][0] = b1; fwave[0][1] = b1 * s[0];
+fwave[1][0] = b2; fwave[1][1] = b2 * s[1];
+for (int mw = 0; mw < 2; mw++)
+    for (int m = 0; m < 2; m++) {
+        if (s[mw] < 0.0) amdq[m] += fwave[mw][m];
+        else apdq[m] += fwave[mw][m];
+    }
+"""
+
 # Transverse Riemann solvers as bodies for pyclaw.CellRiemann(..., transverse=...): Clawpack's rpt2 for one interface, for
 # the unsplit step.  ixy is the direction of the NORMAL solve, asdq the fluctuation to split, bmasdq / bpasdq (zero on
 # entry) its down- and up-going parts.  Without aux the body sees ql, qr; with aux q1, aux1 (the cell asdq belongs to)
@@ -517,6 +577,32 @@ def vc_acoustics2D(pyclaw, mx=100, my=100, tfinal=0.12, nout=10, run=True, math=
     for k in range(2):
         solver.aux_bc_lower[k] = solver.aux_bc_upper[k] = pyclaw.BC.outflow
     solver.dt_initial = np.min(old.grid.d) / 2.0 * solver.cfl_desired
+    if run:
+        claw.run()
+    return claw
+
+
+def capa_acoustics2D(pyclaw, mx=100, my=100, tfinal=0.12, nout=10, run=True, math='exact', user_rp=False, dim_split=1):
+    """The pulse of acoustics2D on a grid with a smooth capacity function in aux(1), state.mcapa = 0 (the cell areas of a
+    mapped grid, between 0.6 and 1.4): dimension-split or unsplit (dim_split=0), with rp_acoustics_2d or, user_rp=True,
+    the bodies ACOUSTICS_2D_RP / ACOUSTICS_2D_RPT unchanged in a pyclaw.CellRiemann compiled with capa=True."""
+    claw = acoustics2D(pyclaw, mx=mx, my=my, tfinal=tfinal, nout=nout, run=False, math=math, dim_split=dim_split)
+    old = claw.solution.state
+    state = pyclaw.State(old.grid, 3, 1)
+    state.q[...] = old.q
+    state.aux_global.update(old.aux_global)
+    X, Y = old.grid.c_center
+    state.aux[0] = 1.0 + 0.4 * np.sin(np.pi * X) * np.cos(0.5 * np.pi * Y)
+    state.mcapa = 0
+    claw.solution = pyclaw.Solution(state)
+    solver = claw.solver
+    if user_rp:
+        g = state.aux_global
+        solver.rp = pyclaw.CellRiemann(ACOUSTICS_2D_RP, 3, 2, 2, params=[g['rho'], g['bulk'], g['cc'], g['zz']], capa=True,
+                                       name="acoustics_2d_capa_user", transverse=None if dim_split else ACOUSTICS_2D_RPT)
+    for k in range(2):
+        solver.aux_bc_lower[k] = solver.aux_bc_upper[k] = pyclaw.BC.outflow
+    solver.dt_initial = 0.6 * solver.dt_initial       # the Courant number is dt / (dx capa) c, capa >= 0.6
     if run:
         claw.run()
     return claw

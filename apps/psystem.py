@@ -18,6 +18,41 @@ PERIOD = (1.0, 1.0)
 # before every step of the unsplit classic solver: aux(4) = strain
 STRAIN_COPY = "aux[3] = q[0];"
 
+# The same solver as bodies of a pyclaw.CellRiemann(..., aux=(0, 1, 2, 3), fwave=True): the arithmetic of the built-in
+# psystem_fwave_2d (FwaveElastic<3> of pyclaw_amd/csrc/rp.hpp) in its operation order, so that the 'exact' arithmetic gives
+# the bits of the built-in path.  The normal body reads the first three listed components (rho, K, flag) of the two cells;
+# ps_sigma / ps_sigmap are rp.hpp's.  The momentum across the sweep keeps the zeros it has on entry.
+PSYSTEM_FWAVE_2D_RP = """
+constexpr int mu = ixy;
+const double rhol = auxl[0], rhor = auxr[0];
+const double unl = fdiv_ieee(ql[mu], rhol), unr = fdiv_ieee(qr[mu], rhor);
+const double sigl = ps_sigma(ql[0], auxl[1], auxl[2]), sigr = ps_sigma(qr[0], auxr[1], auxr[2]);
+const double cl = dsqrt(fdiv_ieee(ps_sigmap(ql[0], auxl[1], auxl[2]), rhol));
+const double cr = dsqrt(fdiv_ieee(ps_sigmap(qr[0], auxr[1], auxr[2]), rhor));
+const double zl = cl * rhol, zr = cr * rhor;
+const double du = unr - unl;
+const double dsig = sigr - sigl;
+const double zs = zl + zr;
+const double b1 = fdiv_ieee(-(zr * du + dsig), zs);
+const double b2 = fdiv_ieee(-(zl * du - dsig), zs);
+fwave[0][0] = b1; fwave[0][mu] = b1 * zl; s[0] = -cl;
+fwave[1][0] = b2; fwave[1][mu] = b2 * (-zr); s[1] = cr;
+for (int m = 0; m < 3; m++) { amdq[m] = fwave[0][m]; apdq[m] = fwave[1][m]; }
+"""
+
+# the transverse body: the rows below and above the cell the fluctuation belongs to, with their strain copy in the fourth
+# listed component (transverse_vc of FwaveElastic<3>)
+PSYSTEM_FWAVE_2D_RPT = """
+constexpr int mv = 3 - ixy;
+const double cm = dsqrt(fdiv_ieee(ps_sigmap(aux_below[3], aux_below[1], aux_below[2]), aux_below[0]));
+const double cp = dsqrt(fdiv_ieee(ps_sigmap(aux_above[3], aux_above[1], aux_above[2]), aux_above[0]));
+const double zm = cm * aux_below[0], zp = cp * aux_above[0];
+const double b1 = fdiv_ieee(asdq[mv] + zp * asdq[0], zm + zp);
+const double b3 = fdiv_ieee(zm * asdq[0] - asdq[mv], zm + zp);
+bmasdq[0] = -cm * b1; bmasdq[mv] = -cm * b1 * zm;
+bpasdq[0] = cp * b3;  bpasdq[mv] = cp * b3 * (-zp);
+"""
+
 
 def checkerboard(xc, yc, linearity=2):
     """aux (4, len(xc), len(yc)) of the checkerboard: a cell belongs to material 0 where the half-period tiles it lies
@@ -45,9 +80,11 @@ def stress_pulse(state, amplitude, x0, y0, varx, vary):
 
 def psystem2D(pyclaw, mx=200, my=200, solver_type='classic', lower=(0.25, 0.25), upper=(20.25, 20.25), bc='reference',
               linearity=2, amplitude=10.0, center=(0.25, 0.25), var=(0.5, 0.5), lim_type=2, time_integrator='SSP104',
-              tfinal=20.0, nout=10, math='exact', run=True):
+              tfinal=20.0, nout=10, math='exact', run=True, user_rp=False):
     """bc = 'reference': walls on the lower sides, extrapolation on the upper ones (the pulse sits in the corner, one
     quarter of a symmetric problem); 'periodic': periodic in both directions (the domain should hold whole periods).
+    user_rp=True (the two classic solver types): the same solver as the bodies PSYSTEM_FWAVE_2D_RP / PSYSTEM_FWAVE_2D_RPT of
+    a pyclaw.CellRiemann with fwave=True; its dimension-split step runs as two passes.
     Returns the controller (run or not)."""
     if solver_type == 'classic':
         solver = pyclaw.ClawSolver2D()
@@ -66,7 +103,13 @@ def psystem2D(pyclaw, mx=200, my=200, solver_type='classic', lower=(0.25, 0.25),
         solver.lim_type = lim_type
         solver.time_integrator = time_integrator
     solver.math = math
-    solver.rp = pyclaw.riemann.rp_psystem_fwave_2d
+    if user_rp:
+        if solver_type not in ('classic', 'classic_unsplit'):
+            raise Exception("user_rp=True: a pyclaw.CellRiemann runs under the classic solvers only")
+        solver.rp = pyclaw.CellRiemann(PSYSTEM_FWAVE_2D_RP, 3, 2, 2, aux=(0, 1, 2, 3), fwave=True, name="psystem_fwave_2d_user",
+                                       transverse=PSYSTEM_FWAVE_2D_RPT if solver_type == 'classic_unsplit' else None)
+    else:
+        solver.rp = pyclaw.riemann.rp_psystem_fwave_2d
     solver.fwave = True
     solver.mwaves = 2
     for k in range(2):

@@ -71,8 +71,9 @@ extern "C" {
                                   /* (rpt3/rptt3_vc_acoustics.f) without a capacity function                                   */
 #define PCL_RP_CELL 100 /* a user-written normal Riemann solver compiled at run time (pcl_cellrp_compile / _attach below):  */
                         /* meqn, mwaves <= 8 from the config, rp_params = the body's p[8]; classic 1-D and dimension-split  */
-                        /* 2-D steps in wave form, no capacity function; the body may read listed aux components            */
-                        /* (pcl_cellrp_compile_aux).  Not a built-in solver: pcl_rp_info refuses the id                     */
+                        /* 2-D steps (unsplit with a transverse body); the body may read listed aux components              */
+                        /* (pcl_cellrp_compile_aux); f-waves and a capacity function through pcl_cellrp_compile_form and    */
+                        /* pcl_create_cellrp.  Not a built-in solver: pcl_rp_info refuses the id                            */
 
 /* boundary condition types = pyclaw.BC (src/pyclaw/solver.py:17-23) */
 #define PCL_BC_CUSTOM 0
@@ -413,7 +414,7 @@ int pcl_cellrp_compile(const char *body, const char *preamble, int meqn, int mwa
  * One list serves both sweeps; a body that reads another component per direction branches on ixy.
  * Contract: for bitwise-equal ql and qr the waves and fluctuations must be zero WHATEVER aux holds -- a wavefront without
  * a jump in q takes the speeds alone, each interface with its own auxl / auxr.  A flux-difference form over varying
- * coefficients breaks this; that is an f-wave solver and is not served.
+ * coefficients breaks this; that is an f-wave solver: pcl_cellrp_compile_form with PCL_CELLRP_FORM_FWAVE.
  * The tile holds meqn + naux planes in a workgroup's 64 KB: meqn + naux <= 8 (65536 bytes / (8 bytes * the 1024 cells
  * of the y tile)); more is PCL_EINVAL with the limit in the message, and so are naux < 0 and a negative or repeated
  * index.  The list is part of the cache key (another order is another program); naux == 0 is pcl_cellrp_compile itself:
@@ -438,6 +439,25 @@ int pcl_cellrp_compile_aux(const char *body, const char *preamble, int meqn, int
  * 16 slices per workgroup for meqn <= 6 and 12 above (their static LDS against 160 KB).  Host-only. */
 int pcl_cellrp_compile_t(const char *body, const char *transverse, const char *preamble, int meqn, int mwaves, int ndim, int math,
                          const int *aux_index, int naux, pcl_cellrp **out, long *code_size);
+/* The same with a FORM: the two facts about the step that are template flags of the kernels, so that a handle is compiled
+ * for them and serves them alone.
+ *     PCL_CELLRP_FORM_FWAVE   the body assigns f-waves (cfg.fwave = 1; flux2fw.f / step1fw.f): the array is named
+ *                             fwave[MWAVES][MEQN] in place of wave, everything else of the body's interface is unchanged
+ *                             (the transverse body's too), all of it zero on entry.  The "equal ql and qr: zero waves"
+ *                             contract does NOT apply to an f-wave body: no wavefront takes a jump-free shortcut, every
+ *                             interface is solved, so a flux-difference solver over varying coefficients is served
+ *     PCL_CELLRP_FORM_CAPA    the sweeps run with a capacity function (cfg.method[5] = mcapa >= 1, any component: it is a
+ *                             run-time value); the body does not change.  The sweep tile holds one more plane:
+ *                             meqn + 1 + naux <= 8, else PCL_EINVAL with the sum and the limit in the message
+ * form == 0 is pcl_cellrp_compile_t itself: the same program, key and handle.  Any other form is part of the cache key, a
+ * program of its own; only the kernels of that one form are compiled.  A bit outside the two is PCL_EINVAL.  Every refusal
+ * comes before the compiler.  Host-only. */
+#define PCL_CELLRP_FORM_FWAVE 1
+#define PCL_CELLRP_FORM_CAPA 2
+int pcl_cellrp_compile_form(const char *body, const char *transverse, const char *preamble, int meqn, int mwaves, int ndim,
+                            int math, const int *aux_index, int naux, int form, pcl_cellrp **out, long *code_size);
+/* Host-only: the PCL_CELLRP_FORM_* bits a live handle was compiled with. */
+int pcl_cellrp_form(const pcl_cellrp *r, int *form);
 /* Host-only: *has = 1 if the live handle was compiled with a transverse body, and then *slices (may be null) = the slices
  * per workgroup of its unsplit kernels; else *has = 0, *slices = 0. */
 int pcl_cellrp_transverse(const pcl_cellrp *r, int *has, int *slices);
@@ -446,7 +466,10 @@ int pcl_cellrp_transverse(const pcl_cellrp *r, int *has, int *slices);
  * body, else PCL_EINVAL.  Every other refusal is pcl_create's and pcl_cellrp_attach's.  All argument checks are host-only
  * and come before the device is touched (no device, acceptable arguments: PCL_ENODEVICE).  pcl_create itself goes on
  * refusing method[2] >= 0 for PCL_RP_CELL: it cannot know the handle.  The unsplit step of such a solver runs whole
- * blocks in wave form without a capacity function, the y phase always in its tile form. */
+ * blocks, the y phase always in its tile form.
+ * The form likewise: cfg.fwave != 0 is accepted if and only if the handle has PCL_CELLRP_FORM_FWAVE, cfg.method[5] > 0
+ * (1 <= method[5] <= maux as for any solver) if and only if it has PCL_CELLRP_FORM_CAPA; every other combination is
+ * PCL_EINVAL, in either direction.  pcl_create goes on refusing cfg.fwave and method[5] != 0 for PCL_RP_CELL. */
 int pcl_create_cellrp(const pcl_config *cfg, pcl_cellrp *r, pcl_solver **out);
 /* Host-only: the list a live handle was compiled with; aux_index (may be null) gets *naux <= 8 entries. */
 int pcl_cellrp_aux(const pcl_cellrp *r, int *naux, int *aux_index);
@@ -457,8 +480,9 @@ int pcl_cellrp_check(const pcl_cellrp *r, int meqn, int mwaves, int ndim, int ma
  * pcl_destroy unloads it).  Until then every step of such a solver is refused with PCL_ESTATE.  A handle whose largest
  * listed aux component is >= cfg.maux is refused (PCL_EINVAL, both numbers in the message) before anything is loaded, and
  * the sweeps of a solver that reads aux are refused (PCL_EINVAL) until pcl_put_aux has uploaded the array.  A solver
- * created unsplit (pcl_create_cellrp) refuses a handle without a transverse body (PCL_EINVAL); the module attached before
- * stays attached. */
+ * created unsplit (pcl_create_cellrp) refuses a handle without a transverse body (PCL_EINVAL), and any solver a handle
+ * whose form (pcl_cellrp_form) is not the solver's cfg.fwave and method[5] > 0; the module attached before stays
+ * attached.  The sweeps of a solver with a capacity function are refused until pcl_put_aux has uploaded the array. */
 int pcl_cellrp_attach(pcl_solver *s, pcl_cellrp *r);
 /* The body's p[0..nparams-1] from the next sweep on (nparams <= 8; the rest are zero): they travel by value with every
  * launch, so changing them compiles nothing. */

@@ -280,8 +280,9 @@ class ClawSolver(Solver):
         cfg.math = {'exact': 0, 'fast': 1, 'strict': 2}[self.math]
         import ctypes
         h = ctypes.c_void_p()
-        if user_rp and self.ndim == 2 and not self.dim_split:
-            # the unsplit step: the library checks the configuration against the handle (its transverse body) and attaches
+        if user_rp and ((self.ndim == 2 and not self.dim_split) or rp.fwave or rp.capa):
+            # the unsplit step, f-waves, a capacity function: the library checks the configuration against the handle (its
+            # transverse body, its form) and attaches
             _lib.check(_lib.lib().pcl_create_cellrp(ctypes.byref(cfg), rp._rp, ctypes.byref(h)))
             self._h = h
         else:
@@ -310,12 +311,19 @@ class ClawSolver(Solver):
             raise NotImplementedError("CellRiemann: dim_split = False needs a transverse Riemann solver (rpt2); the body "
                                       "is the normal solver only, so the 2-D step is the dimension-split one "
                                       "(CellRiemann(..., transverse=...) gives it one)")
-        if self.fwave:
-            raise NotImplementedError("CellRiemann: fwave = True is not served: the body returns waves, and the f-wave "
-                                      "form of the sweep has no user-written instantiation")
-        if state.mcapa >= 0:
-            raise NotImplementedError("CellRiemann: state.mcapa (a capacity function) is not served: the user-written "
-                                      "solver is compiled into the sweep without one")
+        # the form is compiled into the kernels (CellRiemann(fwave=..., capa=...)): the solver and the state must say the same
+        if self.fwave and not self.rp.fwave:
+            raise NotImplementedError("CellRiemann: fwave = True is not served by this solver: its body returns waves; an "
+                                      "f-wave body is compiled with CellRiemann(..., fwave=True)")
+        if self.rp.fwave and not self.fwave:
+            raise ValueError("CellRiemann: the solver was written with fwave=True (its body assigns f-waves) and "
+                             "solver.fwave is False: set solver.fwave = True")
+        if state.mcapa >= 0 and not self.rp.capa:
+            raise NotImplementedError("CellRiemann: state.mcapa (a capacity function) is not served by this solver: it is "
+                                      "compiled into the sweep without one (CellRiemann(..., capa=True) compiles it with one)")
+        if self.rp.capa and state.mcapa < 0:
+            raise ValueError("CellRiemann: the solver was written with capa=True (sweeps with a capacity function) and "
+                             "state.mcapa is not set: name the aux component in state.mcapa")
         if state.decomp is not None and parallel.world_size() > 1:
             raise NotImplementedError("CellRiemann: more than one rank is not served: a user-written solver runs on one "
                                       "block (the decomposed step's plans know the built-in solvers only)")

@@ -28,8 +28,8 @@
 // solve() by construction; NAUX = 0, ONEK and SHARP* false.
 // Contract: for bitwise-equal ql and qr the waves and fluctuations are zero -- the jump-free shortcut (classic.hpp,
 // DESIGN.md 4.1) copies such a wavefront through and takes only the speeds, as any consistent solver has it.
-// Limits: meqn, mwaves <= 8 (MAX_WAVES_K; the y tile of meqn = 8 is the 64 KB a workgroup may declare), 8 parameters,
-// wave form only, no capacity function.
+// (This contract is the wave form's.  An f-wave body, below, is not held to it.)
+// Limits: meqn, mwaves <= 8 (MAX_WAVES_K; the y tile of meqn = 8 is the 64 KB a workgroup may declare), 8 parameters.
 //
 // A solver with cell-wise coefficients lists the components of the aux array its body reads (pcl_cellrp_compile_aux,
 // CellRiemann(aux=...)): the program is then the second wrapper below, compiled with -DPCL_CELLRP_NAUX=<n> behind a
@@ -43,7 +43,7 @@
 // Contract with aux: for bitwise-equal ql and qr the waves and fluctuations are zero WHATEVER aux holds -- the jump-free
 // shortcut of the solvers with aux (classic.hpp, lane_core: `!FWAVE && RP::NAUX > 0`) compares cL.q with cR.q alone and
 // takes speeds(cL, cR), each interface with its own auxl / auxr, on such a wavefront.  A flux-difference form over
-// varying coefficients breaks this: that is an f-wave solver, and not served.
+// varying coefficients breaks this: that is an f-wave solver, compiled with the f-wave form below.
 // Limit with aux: the tile holds MEQN + NAUX planes of TileShape<IXY>::PLANE doubles, so meqn + naux <=
 // cellrp_max_planes() = 65536 / (8 * max PLANE) -- 8, set by the 1024-double y tile; refused on the host with that sum
 // and by the static_assert below.  The list is part of the cache key; without one the program text, the key and the
@@ -58,6 +58,28 @@
 // handle records it and the launcher sizes its grids from the handle.  Always the tile form of the y phase: the marching
 // kernel (its static LDS is 29184 * meqn bytes) stays with the built-in solvers.  Without a transverse text the program
 // text, the key, the handle and the symbols are what they were.
+//
+// The FORM of a solver (pcl_cellrp_compile_form, CellRiemann(fwave=..., capa=...)) is the pair of template flags the
+// kernels are instantiated with: sweep_kernel<UserRp, IXY, CAPA, FWAVE, DIM1> and, with a transverse text,
+// unsplit_x_kernel<UserRp, FWAVE, U, CAPA>, unsplit_y_kernel<UserRp, FWAVE, U, CAPA, false>.  A handle serves one form --
+// only that form's instantiations are compiled -- and records it; the solver's cfg.fwave and method[5] must say the same
+// (pcl_create_cellrp, pcl_cellrp_attach, and once more the launchers of kernels.hip).  Form 0 is the program text, key,
+// handle and symbols of before there were forms.
+//   PCL_CELLRP_FORM_FWAVE: the body assigns F-WAVES, and the array is named fwave[MWAVES][MEQN] as in Clawpack's f-wave
+//     solvers (a body that assigns `wave` does not compile: "riemann:<n>: ... undeclared identifier 'wave'"); s, amdq,
+//     apdq, ql, qr, auxl, auxr, p, ixy, the preamble and the helpers are unchanged, everything is zero on entry, and the
+//     transverse body's interface is what it is in wave form.  The "equal q => zero waves" contract does NOT apply: the
+//     f-waves of a flux-difference solver over varying coefficients are non-zero between equal cells, and lane_core takes
+//     neither jump-free shortcut when FWAVE is set (both sit behind `if constexpr (!FWAVE && ...)`): every interface is
+//     solved.  UserRp::IS_FWAVE is true.  The limiter and the second-order correction are flux2fw.f's (dsign(1, s)).
+//   PCL_CELLRP_FORM_CAPA: the sweeps divide dt/dx by aux(mcapa) per cell and accumulate the reference's Courant expression
+//     (cfl_accumulate<true>); the body does not change.  The component is a run-time value, SweepArgs::mcapa, so one handle
+//     serves any mcapa.  The sweep tile holds the capacity function's plane next to q and the listed aux components:
+//     meqn + 1 + naux <= cellrp_max_planes() = 8, refused on the host with the sum and by the static_assert of kCellrpForm.
+//     The unsplit kernels read capa from global memory per lane (classic.hpp: unsplit_x_kernel, unsplit_y_kernel, `if
+//     constexpr (CAPA)`) and declare no LDS for it, so unsplit_user_slices(meqn) stands as it is.
+// Not served in any form: HAS_QCOR (the sphere solver's conservation fix), a transverse body with both cells and aux, the
+// marching y phase, the one-kernel step, SharpClaw, 3-D, more than one block.
 #pragma once
 #include "cellfn.hpp"
 // generated by the Makefile (embed_headers.py): PCL_RTC_FLAGS_EXACT / _FAST / _STRICT, the flags kernels_<mode>.o is built
@@ -80,6 +102,8 @@ struct pcl_cellrp {
     bool trans = false;
     int slices = 0;
     std::string sym_u[2];
+    // PCL_CELLRP_FORM_* bits: what the kernels in the code object were instantiated for (f-waves, a capacity function)
+    int form = 0;
 };
 
 namespace pcl {
@@ -258,6 +282,17 @@ static const char *const kCellrpTransTailAux = R"PCLSRC(
     }
 )PCLSRC";
 
+// A form other than 0 (pcl_cellrp_compile_form): the last members of the struct.  IS_FWAVE is what IsFwave<RP> (classic.hpp)
+// reads off a solver; with a capacity function the sweep tile holds one plane more (sweep_kernel: PAUX = MEQN + 1), and the
+// limit the host refused over is restated.  NAUX is 0 in the wrapper without aux.
+static const char *const kCellrpForm = R"PCLSRC(
+    static constexpr bool IS_FWAVE = (PCL_CELLRP_FORM & 1) != 0;
+    static constexpr bool FORM_CAPA = (PCL_CELLRP_FORM & 2) != 0;
+    static_assert(!FORM_CAPA || (sizeof(double) * (MEQN + 1 + NAUX) * TileShape<2>::PLANE <= 65536 &&
+                                 sizeof(double) * (MEQN + 1 + NAUX) * TileShape<1>::PLANE <= 65536),
+                  "meqn + 1 + naux: the LDS tile of sweep_kernel (classic.hpp) with the capacity function's plane does not fit a workgroup's 64 KB");
+)PCLSRC";
+
 // the slices per workgroup the host named the unsplit kernels with are the rule's, and both kernels' static LDS fits
 static const char *const kCellrpTransCheck = R"PCLSRC(
     static constexpr int USLICES = PCL_CELLRP_USLICES;
@@ -270,13 +305,14 @@ static const char *const kCellrpTransCheck = R"PCLSRC(
 static inline const char *cellrp_ns(int math) { return math == 1 ? "fast" : math == 2 ? "strict" : "exact"; }
 
 // (without a list the key is what it was before there were lists: the same entry as pcl_cellrp_compile's; without a
-// transverse text it is what it was before there were transverse texts)
+// transverse text it is what it was before there were transverse texts; form 0 likewise)
 static inline std::string cellrp_key(const char *body, const char *preamble, int meqn, int mwaves, int ndim, int math,
-                                     const int *aux = nullptr, int naux = 0, const char *trans = nullptr) {
+                                     const int *aux = nullptr, int naux = 0, const char *trans = nullptr, int form = 0) {
     std::string k = std::string(trans ? "rpt," : "rp,") + std::to_string(meqn) + "," + std::to_string(mwaves) + "," +
                     std::to_string(ndim) + "," + std::to_string(math) + ",";
     for (int i = 0; i < naux; i++) k += (i ? "." : "aux") + std::to_string(aux[i]);
     if (naux > 0) k += ",";
+    if (form) k += "form" + std::to_string(form) + ",";     // (form 0: the key of before there were forms)
     if (trans) { k += std::to_string(strlen(trans)) + ":"; k += trans; }
     k += std::to_string(strlen(preamble)) + ":";
     k += preamble;
@@ -285,25 +321,28 @@ static inline std::string cellrp_key(const char *body, const char *preamble, int
 }
 
 // the sweep kernels of a UserRp of this dimension, as hiprtc name expressions; uslices > 0 (a transverse body, 2-D): the
-// x and y phases of the unsplit step behind them, the tile form of either, without a capacity function or fused source
-static inline std::vector<std::string> cellrp_exprs(int ndim, int math, int uslices = 0) {
+// x and y phases of the unsplit step behind them, the tile form of either, without a fused source.  CAPA and FWAVE of every
+// one come from the form: a handle serves one form, so only that form's instantiations are compiled
+static inline std::vector<std::string> cellrp_exprs(int ndim, int math, int uslices = 0, int form = 0) {
     const std::string ns = std::string("pcl::") + cellrp_ns(math) + "::";
+    const char *fw = (form & PCL_CELLRP_FORM_FWAVE) ? "true" : "false", *capa = (form & PCL_CELLRP_FORM_CAPA) ? "true" : "false";
     auto k = [&](int ixy, bool dim1) {
-        return "&" + ns + "sweep_kernel<" + ns + "UserRp, " + std::to_string(ixy) + ", false, false, " + (dim1 ? "true" : "false") + ">";
+        return "&" + ns + "sweep_kernel<" + ns + "UserRp, " + std::to_string(ixy) + ", " + capa + ", " + fw + ", " + (dim1 ? "true" : "false") + ">";
     };
     if (ndim == 1) return {k(1, true)};
     if (uslices <= 0) return {k(1, false), k(2, false)};
     const std::string u = std::to_string(uslices);
-    return {k(1, false), k(2, false), "&" + ns + "unsplit_x_kernel<" + ns + "UserRp, false, " + u + ", false>",
-            "&" + ns + "unsplit_y_kernel<" + ns + "UserRp, false, " + u + ", false, false>"};
+    return {k(1, false), k(2, false), "&" + ns + "unsplit_x_kernel<" + ns + "UserRp, " + fw + ", " + u + ", " + capa + ">",
+            "&" + ns + "unsplit_y_kernel<" + ns + "UserRp, " + fw + ", " + u + ", " + capa + ", false>"};
 }
 
 // hiprtc compile of the sweep kernels around body; math: 0 exact, 1 fast, 2 strict.  0 = ok, else err holds the log
 // aux[0..naux): the aux components the body reads (naux == 0: the wrapper without aux, the program text of before)
 // trans (null: none, the program text of before): the transverse body; uslices: the slices per workgroup of the unsplit
 // kernels it is compiled into; sym[2], sym[3]: their lowered names
+// form (0: the program text of before): PCL_CELLRP_FORM_* bits; with the f-wave bit the array the body assigns is `fwave`
 static inline int cellrp_build(const char *body, const char *trans, const char *preamble, int meqn, int mwaves, int ndim, int math,
-                               const int *aux, int naux, int uslices, std::vector<char> &code, std::string (&sym)[4],
+                               const int *aux, int naux, int uslices, int form, std::vector<char> &code, std::string (&sym)[4],
                                std::string &err) {
     if (hiprtc_load(err)) return -1;
     HiprtcApi &a = hiprtc_api();
@@ -317,7 +356,14 @@ static inline int cellrp_build(const char *body, const char *trans, const char *
         for (int i = 0; i < naux; i++) src += "k == " + std::to_string(i) + " ? " + std::to_string(aux[i]) + " : ";
         src += "0; }\n";
     }
-    src += naux > 0 ? kCellrpOpenAux : kCellrpOpen;
+    {
+        std::string open = naux > 0 ? kCellrpOpenAux : kCellrpOpen;
+        if (form & PCL_CELLRP_FORM_FWAVE) {     // the body's name of the array, as Clawpack's f-wave solvers have it
+            const size_t at = open.find("(&wave)");
+            open.replace(at, 7, "(&fwave)");
+        }
+        src += open;
+    }
     src += "#line 1 \"riemann\"\n";
     src += body;
     src += "\n";
@@ -330,11 +376,12 @@ static inline int cellrp_build(const char *body, const char *trans, const char *
         src += naux > 0 ? kCellrpTransTailAux : kCellrpTransTail;
         src += kCellrpTransCheck;
     }
+    if (form) src += kCellrpForm;
     src += naux > 0 ? kCellrpCloseAux : kCellrpClose;
     hiprtcProgram prog = nullptr;
     hiprtcResult r = a.hiprtcCreateProgram(&prog, src.c_str(), "pcl_cellrp.hip", kCellrpHeaderCount, kCellrpHeaderTexts, kCellrpHeaderNames);
     if (r != HIPRTC_SUCCESS) { err = std::string("hiprtcCreateProgram: ") + a.hiprtcGetErrorString(r); return -1; }
-    const std::vector<std::string> exprs = cellrp_exprs(ndim, math, trans ? uslices : 0);
+    const std::vector<std::string> exprs = cellrp_exprs(ndim, math, trans ? uslices : 0, form);
     for (const std::string &e : exprs) {
         r = a.hiprtcAddNameExpression(prog, e.c_str());
         if (r != HIPRTC_SUCCESS) {
@@ -361,6 +408,7 @@ static inline int cellrp_build(const char *body, const char *trans, const char *
     flags.push_back("-DPCL_CELLRP_NDIM=" + std::to_string(ndim));
     if (naux > 0) flags.push_back("-DPCL_CELLRP_NAUX=" + std::to_string(naux));
     if (trans) flags.push_back("-DPCL_CELLRP_USLICES=" + std::to_string(uslices));
+    if (form) flags.push_back("-DPCL_CELLRP_FORM=" + std::to_string(form));
     std::vector<const char *> opts;
     for (const std::string &f : flags) opts.push_back(f.c_str());
     r = a.hiprtcCompileProgram(prog, (int)opts.size(), opts.data());
@@ -411,9 +459,10 @@ struct CellrpModule {
     // the unsplit phases (by ids - 1) of a solver with a transverse body, and its slices per workgroup; else null, 0
     hipFunction_t fn_u[2] = {nullptr, nullptr};
     int slices = 0;
+    int form = 0;               // PCL_CELLRP_FORM_* bits of the attached solver: what its kernels were instantiated for
     void unload() {
         if (mod) (void)hipModuleUnload(mod);
-        mod = nullptr; fn[0] = fn[1] = fn_u[0] = fn_u[1] = nullptr; id = 0; naux = 0; slices = 0;
+        mod = nullptr; fn[0] = fn[1] = fn_u[0] = fn_u[1] = nullptr; id = 0; naux = 0; slices = 0; form = 0;
     }
 };
 

@@ -71,18 +71,33 @@ template <int IXY, bool DIM1> int sweep_grid(const SweepArgs &a, SweepGrid &g, s
     return PCL_OK;
 }
 
-// A user-written Riemann solver (cellrp.hpp): l.user_fn is sweep_kernel<UserRp, IXY, false, false, DIM1> of a module
-// compiled at run time from the text of classic.hpp, so the kernel's parameters are those of the launches below.
+// What the module of a user-written Riemann solver was compiled for against what this launch asks: the kernel's FWAVE and
+// CAPA are template flags (cellrp.hpp: the handle's form), so a launch that says otherwise would run the wrong kernel.
+static int user_form_check(const SweepLaunch &l, std::string &err) {
+    if ((l.fwave != 0) != l.user_fwave) {
+        err = l.user_fwave ? "user-written Riemann solver: the attached solver was compiled for f-waves and the step is in wave form"
+                           : "user-written Riemann solver: the step asks for f-waves and the attached solver was compiled in wave form";
+        return PCL_EINVAL;
+    }
+    if ((l.a.mcapa > 0) != l.user_capa) {
+        err = l.user_capa ? "user-written Riemann solver: the attached solver was compiled for a capacity function and the step has none"
+                          : "user-written Riemann solver: the step has a capacity function and the attached solver was compiled without one";
+        return PCL_EINVAL;
+    }
+    if ((l.user_naux > 0 || l.user_capa) && !l.a.aux) {
+        err = l.user_naux > 0 ? "user-written Riemann solver: this solver reads aux arrays and there are none (pcl_put_aux)"
+                              : "user-written Riemann solver: the capacity function is a component of the aux arrays and there are none (pcl_put_aux)";
+        return PCL_EINVAL;
+    }
+    return PCL_OK;
+}
+
+// A user-written Riemann solver (cellrp.hpp): l.user_fn is sweep_kernel<UserRp, IXY, user_capa, user_fwave, DIM1> of a
+// module compiled at run time from the text of classic.hpp, so the kernel's parameters are those of the launches below.
 template <int IXY, bool DIM1> int launch_user(const SweepLaunch &l, std::string &err) {
     if (!l.user_fn) { err = "user-written Riemann solver: no compiled solver is attached (pcl_cellrp_attach)"; return PCL_ESTATE; }
-    if (l.fwave || l.a.mcapa > 0 || l.a.src_id != 0) {
-        err = "user-written Riemann solver: wave form only, no capacity function, no fused source";
-        return PCL_EINVAL;
-    }
-    if (l.user_naux > 0 && !l.a.aux) {
-        err = "user-written Riemann solver: this solver reads aux arrays and there are none (pcl_put_aux)";
-        return PCL_EINVAL;
-    }
+    if (l.a.src_id != 0) { err = "user-written Riemann solver: no fused source"; return PCL_EINVAL; }
+    if (int rc = user_form_check(l, err)) return rc;
     SweepGrid g;
     if (int rc = sweep_grid<IXY, DIM1>(l.a, g, err)) return rc;
     if (g.nblocks == 0) return PCL_OK;
@@ -414,23 +429,20 @@ template <class RP> int launch_unsplit_t(const SweepLaunch &l, const double *qx,
         return launch_unsplit_u<RP, 16, 16>(l, qx, err);
     } else return launch_unsplit_u<RP, 16, 16>(l, qx, err);
 }
-// A user-written Riemann solver with a transverse body (cellrp.hpp): l.user_fn is unsplit_x_kernel<UserRp, false, U, false>
-// or unsplit_y_kernel<UserRp, false, U, false, false> of the module compiled at run time, U = l.user_slices as the handle
-// records it; the parameters and grids are those of launch_unsplit_u.  Always the tile form of the y phase: the marching
+// A user-written Riemann solver with a transverse body (cellrp.hpp): l.user_fn is unsplit_x_kernel<UserRp, FWAVE, U, CAPA>
+// or unsplit_y_kernel<UserRp, FWAVE, U, CAPA, false> of the module compiled at run time, FWAVE and CAPA = l.user_fwave and
+// l.user_capa (the handle's form), U = l.user_slices as the handle records it; the parameters and grids are those of launch_unsplit_u.  Always the tile form of the y phase: the marching
 // kernel stays with the built-in solvers.
 int launch_unsplit_user(const SweepLaunch &l, const double *qx, std::string &err) {
     if (!l.user_fn || l.user_slices < 3) {
         err = "user-written Riemann solver: no compiled solver with a transverse body is attached (pcl_cellrp_attach)";
         return PCL_ESTATE;
     }
-    if (l.fwave || l.a.mcapa > 0 || l.a.src_id != 0 || l.a.sub != 0) {
-        err = "user-written Riemann solver, unsplit step: wave form only, no capacity function, no fused source, whole blocks";
+    if (l.a.src_id != 0 || l.a.sub != 0) {
+        err = "user-written Riemann solver, unsplit step: no fused source, whole blocks";
         return PCL_EINVAL;
     }
-    if (l.user_naux > 0 && !l.a.aux) {
-        err = "user-written Riemann solver: this solver reads aux arrays and there are none (pcl_put_aux)";
-        return PCL_EINVAL;
-    }
+    if (int rc = user_form_check(l, err)) return rc;
     SweepArgs a = l.a;
     const int U = l.user_slices;
     hipError_t e;

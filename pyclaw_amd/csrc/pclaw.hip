@@ -383,7 +383,10 @@ SweepLaunch make_launch(const pcl_solver *s, const SweepArgs &a, int ndim, int i
     if (l.rp == PCL_RP_CELL && ndim <= 2) {
         l.user_fn = s->cellrp.fn[ids - 1];     // null: nothing attached, refused by the launcher
         l.user_naux = s->cellrp.naux;
-        if (l.user_naux > 0 && !s->aux_put) l.a.aux = nullptr;     // nothing uploaded yet: refused by the launcher too
+        l.user_fwave = (s->cellrp.form & PCL_CELLRP_FORM_FWAVE) != 0;
+        l.user_capa = (s->cellrp.form & PCL_CELLRP_FORM_CAPA) != 0;
+        // nothing uploaded yet (listed components or the capacity function): refused by the launcher too
+        if ((l.user_naux > 0 || l.user_capa) && !s->aux_put) l.a.aux = nullptr;
     }
     return l;
 }
@@ -695,7 +698,7 @@ int check_device() {
 extern "C" {
 
 const char *pcl_last_error(void) { return g_err.c_str(); }
-int pcl_version(void) { return 108; }
+int pcl_version(void) { return 109; }
 int pcl_device_count(void) {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess) return 0;
@@ -710,9 +713,10 @@ int pcl_rp_info(int rp, int info[10]) {
 }
 
 // pcl_create in two halves, so that pcl_create_cellrp can put what the handle must be able to do between them.
-// create_check: every test of the configuration, host-only.  cell_unsplit: a PCL_RP_CELL solver may be unsplit (the caller
-// knows the handle and checks it itself); pcl_create cannot know it and refuses.
-static int create_check(const pcl_config *cfg, bool cell_unsplit) {
+// create_check: every test of the configuration, host-only.  cell_handle: the caller knows the handle of a PCL_RP_CELL
+// solver and checks against it what only the handle can serve (the unsplit step, f-waves, a capacity function:
+// cellrp_fits_locked); pcl_create cannot know it and refuses all three.
+static int create_check(const pcl_config *cfg, bool cell_handle) {
     if (getenv("PCL_TRACE_ABORT")) {   // diagnostics: C backtrace on abort()
         signal(SIGABRT, [](int) {
             void *bt[64];
@@ -755,13 +759,15 @@ static int create_check(const pcl_config *cfg, bool cell_unsplit) {
     if (!facts) return fail(PCL_EINVAL, "unknown Riemann solver id");
     if (cfg->rp == PCL_RP_CELL) {
         // a user-written normal solver (cellrp.hpp): sizes from the config; it serves the classic 1-D step and the two
-        // passes of the dimension-split 2-D step, in wave form, without a capacity function
+        // passes of the dimension-split 2-D step; in wave form without a capacity function unless a handle says otherwise
         if (cfg->kind != PCL_KIND_CLASSIC)
             return fail(PCL_EINVAL, "PCL_RP_CELL: a user-written Riemann solver runs in the classic sweeps only, not under SharpClaw");
         if (cfg->ndim == 3) return fail(PCL_EINVAL, "PCL_RP_CELL: a user-written Riemann solver is 1-D or 2-D (ndim == 3)");
-        if (cfg->fwave) return fail(PCL_EINVAL, "PCL_RP_CELL: a user-written Riemann solver returns waves, not f-waves (cfg.fwave must be 0)");
-        if (cfg->method[5] != 0) return fail(PCL_EINVAL, "PCL_RP_CELL: no capacity function with a user-written Riemann solver (mcapa must be 0)");
-        if (cfg->ndim == 2 && cfg->method[2] >= 0 && !cell_unsplit)
+        if (cfg->fwave && !cell_handle)
+            return fail(PCL_EINVAL, "PCL_RP_CELL: a user-written Riemann solver returns waves, not f-waves (cfg.fwave must be 0)");
+        if (cfg->method[5] != 0 && !cell_handle)
+            return fail(PCL_EINVAL, "PCL_RP_CELL: no capacity function with a user-written Riemann solver (mcapa must be 0)");
+        if (cfg->ndim == 2 && cfg->method[2] >= 0 && !cell_handle)
             return fail(PCL_EINVAL, "PCL_RP_CELL: the unsplit step needs a transverse solver; a user-written solver has the "
                                     "dimension-split step only (method[2] < 0)");
         if (cfg->meqn < 1 || cfg->meqn > PCL_MAX_WAVES) return fail(PCL_EINVAL, "PCL_RP_CELL: 1 <= meqn <= 8");
@@ -784,7 +790,7 @@ static int create_check(const pcl_config *cfg, bool cell_unsplit) {
         // 1-D elasticity solver has no rp1 in the SharpClaw oracle (nothing to check a kernel against): classic only
         if (cfg->kind == PCL_KIND_SHARPCLAW && cfg->rp == PCL_RP_ELASTICITY_FWAVE_1D)
             return fail(PCL_EINVAL, "elasticity_fwave_1d is wired for the classic solver only");
-    } else if (cfg->fwave) {
+    } else if (cfg->fwave && cfg->rp != PCL_RP_CELL) {      // (PCL_RP_CELL: refused above, or the handle's business)
         return fail(PCL_EINVAL, "cfg.fwave = 1 needs an f-wave Riemann solver (PCL_RP_ELASTICITY_FWAVE_1D, PCL_RP_PSYSTEM_FWAVE_2D)");
     }
     if (cfg->rp == PCL_RP_SHALLOW_SPHERE_2D) {
@@ -1758,6 +1764,14 @@ int pcl_cellrp_compile_aux(const char *body, const char *preamble, int meqn, int
 // object also holds the two unsplit kernels, unsplit_user_slices(meqn) slices per workgroup (sweep_args.hpp)
 int pcl_cellrp_compile_t(const char *body, const char *transverse, const char *preamble, int meqn, int mwaves, int ndim, int math,
                          const int *aux_index, int naux, pcl_cellrp **out, long *code_size) {
+    return pcl_cellrp_compile_form(body, transverse, preamble, meqn, mwaves, ndim, math, aux_index, naux, 0, out, code_size);
+}
+
+// form == 0 is pcl_cellrp_compile_t: the same program text, key and handle.  Any other form (PCL_CELLRP_FORM_* bits) is part
+// of the key, and the code object holds the kernels of that one form: sweep_kernel<UserRp, IXY, CAPA, FWAVE, DIM1> and,
+// with a transverse body, unsplit_x/y_kernel<UserRp, FWAVE, U, CAPA> (cellrp.hpp: cellrp_exprs)
+int pcl_cellrp_compile_form(const char *body, const char *transverse, const char *preamble, int meqn, int mwaves, int ndim,
+                            int math, const int *aux_index, int naux, int form, pcl_cellrp **out, long *code_size) {
     if (!body || !out) return fail(PCL_EINVAL, "null argument");
     *out = nullptr;
     if (!preamble) preamble = "";
@@ -1777,6 +1791,14 @@ int pcl_cellrp_compile_t(const char *body, const char *transverse, const char *p
                                     std::to_string(max_planes) + " planes (q components and listed aux components) in a workgroup's 64 KB");
     static_assert(PCL_CELLRP_MAX_AUX >= PCL_MAX_WAVES, "pcl_cellrp_aux writes up to 8 indices");
     if (naux > PCL_CELLRP_MAX_AUX) return fail(PCL_EINVAL, "pcl_cellrp_compile_aux: at most 8 aux components");
+    if (form & ~(PCL_CELLRP_FORM_FWAVE | PCL_CELLRP_FORM_CAPA))
+        return fail(PCL_EINVAL, "pcl_cellrp_compile_form: form = " + std::to_string(form) + " has a bit that is neither "
+                                "PCL_CELLRP_FORM_FWAVE (1) nor PCL_CELLRP_FORM_CAPA (2)");
+    // the capacity function takes a plane of the sweep tile (classic.hpp: sweep_kernel, PAUX = MEQN + 1)
+    if ((form & PCL_CELLRP_FORM_CAPA) && meqn + 1 + naux > max_planes)
+        return fail(PCL_EINVAL, "pcl_cellrp_compile_form: meqn + 1 + naux = " + std::to_string(meqn + 1 + naux) + ", the sweep's tile holds "
+                                "at most " + std::to_string(max_planes) + " planes (q components, the capacity function and listed aux "
+                                "components) in a workgroup's 64 KB");
     for (int i = 0; i < naux; i++) {
         if (aux_index[i] < 0)
             return fail(PCL_EINVAL, "pcl_cellrp_compile_aux: aux index " + std::to_string(aux_index[i]) + " is negative (0-based components of the aux array)");
@@ -1786,7 +1808,7 @@ int pcl_cellrp_compile_t(const char *body, const char *transverse, const char *p
     }
     CellfnCache &c = cellfn_cache();
     std::lock_guard<std::mutex> lock(c.mu);
-    const std::string key = cellrp_key(body, preamble, meqn, mwaves, ndim, math, aux_index, naux, transverse);
+    const std::string key = cellrp_key(body, preamble, meqn, mwaves, ndim, math, aux_index, naux, transverse, form);
     auto it = c.rp_by_key.find(key);
     pcl_cellrp *r = nullptr;
     if (it != c.rp_by_key.end()) {
@@ -1796,7 +1818,7 @@ int pcl_cellrp_compile_t(const char *body, const char *transverse, const char *p
         std::vector<char> code;
         std::string err, sym[4];
         const int slices = transverse ? pcl::unsplit_user_slices(meqn) : 0;
-        if (cellrp_build(body, transverse, preamble, meqn, mwaves, ndim, math, aux_index, naux, slices, code, sym, err))
+        if (cellrp_build(body, transverse, preamble, meqn, mwaves, ndim, math, aux_index, naux, slices, form, code, sym, err))
             return fail(PCL_EINVAL, err);
         r = new pcl_cellrp();
         r->id = c.next_id++;
@@ -1809,6 +1831,7 @@ int pcl_cellrp_compile_t(const char *body, const char *transverse, const char *p
         r->trans = transverse != nullptr;
         r->slices = slices;
         r->sym_u[0] = sym[2]; r->sym_u[1] = sym[3];
+        r->form = form;
         c.rp_by_key[key] = r;
         c.rp_live[r] = r->id;
         c.compiles++;
@@ -1865,6 +1888,15 @@ int pcl_cellrp_transverse(const pcl_cellrp *r, int *has, int *slices) {
     return PCL_OK;
 }
 
+int pcl_cellrp_form(const pcl_cellrp *r, int *form) {
+    if (!form) return fail(PCL_EINVAL, "null argument");
+    CellfnCache &c = cellfn_cache();
+    std::lock_guard<std::mutex> lock(c.mu);
+    if (!r || !c.rp_live.count(r)) return fail(PCL_EINVAL, "not a live Riemann solver handle (pcl_cellrp_compile)");
+    *form = r->form;
+    return PCL_OK;
+}
+
 // what attaching r to a solver of this configuration asks of the handle; host-only (the cache's lock is held)
 static int cellrp_fits_locked(CellfnCache &c, const pcl_cellrp *r, const pcl_config &cfg, const char *who) {
     if (int rc = cellrp_check_locked(c, r, cfg.meqn, cfg.mwaves, cfg.ndim, cfg.math)) return rc;
@@ -1877,6 +1909,18 @@ static int cellrp_fits_locked(CellfnCache &c, const pcl_cellrp *r, const pcl_con
     if (cfg.ndim == 2 && cfg.method[2] >= 0 && !r->trans)
         return fail(PCL_EINVAL, std::string(who) + ": PCL_RP_CELL: the unsplit step (method[2] >= 0) needs a handle compiled with a "
                                     "transverse body (pcl_cellrp_compile_t)");
+    // the kernels in the handle were instantiated for one form (FWAVE, CAPA): the configuration must say the same
+    const bool hfw = (r->form & PCL_CELLRP_FORM_FWAVE) != 0, hcapa = (r->form & PCL_CELLRP_FORM_CAPA) != 0;
+    if ((cfg.fwave != 0) != hfw)
+        return fail(PCL_EINVAL, std::string(who) + (hfw ? ": PCL_RP_CELL: the handle was compiled for f-waves (PCL_CELLRP_FORM_FWAVE) and "
+                                                          "cfg.fwave is 0"
+                                                        : ": PCL_RP_CELL: cfg.fwave = 1 asks for f-waves and the handle was compiled in "
+                                                          "wave form (pcl_cellrp_compile_form with PCL_CELLRP_FORM_FWAVE)"));
+    if ((cfg.method[5] > 0) != hcapa)
+        return fail(PCL_EINVAL, std::string(who) + (hcapa ? ": PCL_RP_CELL: the handle was compiled for a capacity function "
+                                                            "(PCL_CELLRP_FORM_CAPA) and the solver has none (method[5] is 0)"
+                                                          : ": PCL_RP_CELL: method[5] > 0 asks for a capacity function and the handle "
+                                                            "was compiled without one (pcl_cellrp_compile_form with PCL_CELLRP_FORM_CAPA)"));
     return PCL_OK;
 }
 
@@ -1885,7 +1929,7 @@ int pcl_cellrp_attach(pcl_solver *s, pcl_cellrp *r) {
     if (!s) return fail(PCL_EINVAL, "null argument");
     if (s->cfg.rp != PCL_RP_CELL) return fail(PCL_EINVAL, "pcl_cellrp_attach: the solver was not created with cfg.rp = PCL_RP_CELL");
     long id;
-    int naux, slices;
+    int naux, slices, form;
     const void *code;
     std::string sym[2], sym_u[2];
     {   // (the entry is never freed: code and names stay valid outside the lock)
@@ -1895,6 +1939,7 @@ int pcl_cellrp_attach(pcl_solver *s, pcl_cellrp *r) {
         if (int rc = cellrp_fits_locked(c, r, s->cfg, "pcl_cellrp_attach")) return rc;
         id = r->id; naux = r->naux; code = r->code.data(); sym[0] = r->sym[0]; sym[1] = r->sym[1];
         slices = r->trans ? r->slices : 0; sym_u[0] = r->sym_u[0]; sym_u[1] = r->sym_u[1];
+        form = r->form;
     }
     if (s->cellrp.id == id) return PCL_OK;
     HIP_TRY(hipSetDevice(s->cfg.device));
@@ -1919,12 +1964,14 @@ int pcl_cellrp_attach(pcl_solver *s, pcl_cellrp *r) {
     m.id = id;
     m.naux = naux;
     m.slices = slices;
+    m.form = form;
     s->cellrp = m;
     return PCL_OK;
 }
 
 // a PCL_RP_CELL solver with r attached, in one call: the configuration is checked against what the handle can do (the
-// unsplit step, method[2] >= 0 in 2-D, if and only if it has a transverse body) before the device is touched
+// unsplit step, method[2] >= 0 in 2-D, if and only if it has a transverse body; cfg.fwave and method[5] > 0 if and only
+// if its form has the bit) before the device is touched
 int pcl_create_cellrp(const pcl_config *cfg, pcl_cellrp *r, pcl_solver **out) {
     if (!cfg || !out) return fail(PCL_EINVAL, "null argument");
     *out = nullptr;

@@ -181,11 +181,14 @@ struct SweepLaunch {
     int lim_type;  // SharpClaw reconstruction (2 PyWENO weno5, 3 legacy weno5)
     int char_decomp = 0;   // SharpClaw: 1 = wave-based reconstruction (1-D: tvd2_wave / weno5_wave)
     hipStream_t stream;
-    // rp == PCL_RP_CELL (a user-written Riemann solver, cellrp.hpp): sweep_kernel<UserRp, ids, ...> of the module the
+    // rp == PCL_RP_CELL (a user-written Riemann solver, cellrp.hpp): sweep_kernel<UserRp, ids, user_capa, user_fwave, .> of the module the
     // solver handle has loaded; launch_sweep launches it over the grid it computes for the built-in solvers
     hipFunction_t user_fn = nullptr;
     int user_naux = 0;      // aux components that solver's body reads: with any, a launch without a.aux is refused
-    // launch_unsplit: user_fn is unsplit_x_kernel / unsplit_y_kernel<UserRp, false, user_slices, ...> of that module (null:
+    // the form that module's kernels were instantiated for (FWAVE, CAPA): a launch whose fwave or a.mcapa > 0 says
+    // otherwise is refused, and so is one with user_capa and without a.aux
+    bool user_fwave = false, user_capa = false;
+    // launch_unsplit: user_fn is unsplit_x_kernel / unsplit_y_kernel<UserRp, user_fwave, user_slices, user_capa> of that module (null:
     // nothing attached), user_slices the U its handle was compiled with (unsplit_user_slices)
     int user_slices = 0;
     // one-kernel step only (classic_fused.hpp, quiet tiles): this launch's per-tile words and per-wavefront Courant

@@ -83,7 +83,8 @@ class CellRiemann(RiemannSolver):
     reassigning them between steps compiles nothing), the compile-time constant ``ixy`` (1 = x, always in 1-D; 2 = y)
     and assigns ``wave[MWAVES][MEQN]``, ``s[MWAVES]``, ``amdq[MEQN]``, ``apdq[MEQN]``, all zero on entry.  The helpers
     of the built-in solvers (``dmax``, ``dmin``, ``dsqrt``, ``fdiv``, ``Recip``) are in scope; ``preamble`` holds helper
-    functions.  For bitwise-equal ``ql`` and ``qr`` the waves and fluctuations must be zero.
+    functions.  For bitwise-equal ``ql`` and ``qr`` the waves and fluctuations must be zero (the wave form's contract;
+    an f-wave body, below, is not held to it).
 
     A solver with cell-wise coefficients names the components of ``state.aux`` its body reads: ``aux=(0, 1)``
     (0-based).  The sweep stages those planes next to q in its tile, and the body also sees ``auxl[NAUX]`` and
@@ -92,7 +93,7 @@ class CellRiemann(RiemannSolver):
     that reads another component per direction branches on ``ixy``.  With aux the contract reads: for bitwise-equal
     ``ql`` and ``qr`` the waves and fluctuations are zero *whatever aux holds* -- a wavefront without a jump in q takes
     the speeds alone, each interface with its own ``auxl`` / ``auxr``.  A flux-difference form over varying coefficients
-    breaks this; that is an f-wave solver and is not served.  The tile holds ``meqn + len(aux)`` planes in a
+    breaks this; that is an f-wave solver: ``fwave=True``, below.  The tile holds ``meqn + len(aux)`` planes in a
     workgroup's 64 KB, which comes to at most 8 (``MAX_PLANES``; the library derives it from its tile shapes and
     refuses with its own figure).  ``setup()`` needs ``state.aux`` with ``maux > max(aux)``; aux upload, aux ghost
     cells and aux boundary conditions then run as for a built-in solver with aux, and a ``CellStartStep`` with
@@ -110,14 +111,28 @@ class CellRiemann(RiemannSolver):
     never calls the body.  Its diagnostics read ``transverse:<n>``.  The dimension-split step of a solver that carries
     a transverse body is unchanged.
 
-    Not served: a transverse body that needs both cells and aux, f-waves, a capacity function, SharpClaw, 3-D, more than
-    one block.  The dimension-split 2-D step always runs as two passes, the unsplit y phase always in its tile form
-    (the marching y kernel stays with the built-in solvers)."""
+    ``fwave=True`` is an f-wave solver (``solver.fwave = True``; Clawpack's classic1fw / classic2fw): the array the body
+    assigns is named ``fwave[MWAVES][MEQN]`` in place of ``wave``, as in Clawpack's f-wave solvers, and holds the pieces
+    of the flux difference; ``s``, ``amdq``, ``apdq`` and everything the body reads are unchanged, all results zero on
+    entry, and the transverse body's interface is the same in either form.  The "equal q, zero waves" contract does
+    *not* apply to an f-wave body: every interface is solved, no wavefront is skipped, so the f-waves between two equal
+    cells over different coefficients (well-balanced shallow water over bathymetry, conservative variable-coefficient
+    advection, layered elasticity) are what the body says they are.  ``capa=True`` compiles the sweeps with a capacity
+    function, ``state.mcapa`` (any component; it is a run-time value): the body does not change, the sweeps divide
+    dt/dx by it per cell.  The tile then holds one more plane: ``meqn + 1 + len(aux) <= MAX_PLANES``.  Both are part
+    of the compile key and readable as attributes; the solver and the state must say the same as the ``CellRiemann``
+    (``setup()`` refuses each mismatch with its reason).
+
+    Not served: a transverse body that needs both cells and aux, a conservation fix in the unsplit step (the sphere
+    solver's ``qcor``), SharpClaw, 3-D, more than one block.  The dimension-split 2-D step always runs as two passes,
+    never as the one-kernel step, the unsplit y phase always in its tile form (the marching y kernel stays with the
+    built-in solvers)."""
 
     MAX_PARAMS = 8
     MAX_PLANES = 8
 
-    def __init__(self, body, meqn, mwaves, ndim, params=(), preamble="", name="user", aux=(), transverse=None):
+    def __init__(self, body, meqn, mwaves, ndim, params=(), preamble="", name="user", aux=(), transverse=None, fwave=False,
+                 capa=False):
         RiemannSolver.__init__(self, name, PCL_RP_CELL, int(ndim), int(meqn), int(mwaves), (),
                                has_transverse=transverse is not None)
         if not 1 <= self.meqn <= 8 or not 1 <= self.mwaves <= 8:
@@ -132,6 +147,12 @@ class CellRiemann(RiemannSolver):
         if self.aux and self.meqn + len(self.aux) > self.MAX_PLANES:
             raise ValueError("CellRiemann: meqn + len(aux) = %d, the sweep's tile holds at most %d planes (q components and "
                              "listed aux components)" % (self.meqn + len(self.aux), self.MAX_PLANES))
+        self.fwave = bool(fwave)
+        self.capa = bool(capa)
+        if self.capa and self.meqn + 1 + len(self.aux) > self.MAX_PLANES:
+            raise ValueError("CellRiemann: meqn + 1 + len(aux) = %d with capa=True, the sweep's tile holds at most %d planes "
+                             "(q components, the capacity function and listed aux components)"
+                             % (self.meqn + 1 + len(self.aux), self.MAX_PLANES))
         if transverse is not None and self.ndim != 2:
             raise ValueError("CellRiemann: a transverse body belongs to the unsplit 2-D step, got ndim=%d" % self.ndim)
         self.body = str(body)
@@ -163,12 +184,19 @@ class CellRiemann(RiemannSolver):
         from . import _lib
         if math not in ('exact', 'fast', 'strict'):
             raise Exception("math must be 'exact', 'fast' or 'strict'")
-        key = (self.meqn, self.mwaves, self.ndim, math, self.body, self.preamble, self.aux, self.transverse)
+        form = (1 if self.fwave else 0) | (2 if self.capa else 0)      # PCL_CELLRP_FORM_FWAVE, PCL_CELLRP_FORM_CAPA
+        key = (self.meqn, self.mwaves, self.ndim, math, self.body, self.preamble, self.aux, self.transverse, form)
         if self._rp is not None and self._key == key:
             return self
         rp, size = ctypes.c_void_p(), ctypes.c_long(0)
         mode = {'exact': 0, 'fast': 1, 'strict': 2}[math]
-        if self.transverse is not None:
+        if form:
+            _lib.check(_lib.lib().pcl_cellrp_compile_form(self.body.encode(),
+                                                          None if self.transverse is None else self.transverse.encode(),
+                                                          self.preamble.encode(), self.meqn, self.mwaves, self.ndim, mode,
+                                                          (ctypes.c_int * len(self.aux))(*self.aux) if self.aux else None,
+                                                          len(self.aux), form, ctypes.byref(rp), ctypes.byref(size)))
+        elif self.transverse is not None:
             _lib.check(_lib.lib().pcl_cellrp_compile_t(self.body.encode(), self.transverse.encode(), self.preamble.encode(),
                                                        self.meqn, self.mwaves, self.ndim, mode,
                                                        (ctypes.c_int * len(self.aux))(*self.aux) if self.aux else None,

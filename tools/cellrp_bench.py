@@ -25,7 +25,14 @@ the built-in solver without aux the marching kernel once the grid is large enoug
 2048^2), so at 2048^2 the two runs execute the same templates and at 4096^2 their difference is the price of that limit.
 The children also time the run-time compile of the solver with and without its transverse text.
 
-  python tools/cellrp_bench.py [--aux] [--unsplit] [--n 4096] [--steps 20] [--warmup 3] [--reps 7] [--out FILE]
+--fwave measures the three ways of the first paragraph on the p-system (apps/psystem.py: psystem2D, dimension-split):
+the built-in f-wave solver psystem_fwave_2d held to two passes, the same solver as a CellRiemann compiled with
+fwave=True (PSYSTEM_FWAVE_2D_RP, aux=(0, 1, 2, 3)), and the built-in solver on its default path.
+
+--capa measures acoustics on a grid with a capacity function (problems.capa_acoustics2D) two ways: "two_pass", the
+built-in solver held to two passes, and "user", ACOUSTICS_2D_RP in a CellRiemann compiled with capa=True.
+
+  python tools/cellrp_bench.py [--aux] [--unsplit] [--fwave | --capa] [--n 4096] [--steps 20] [--warmup 3] [--reps 7] [--out FILE]
 """
 import argparse
 import ctypes
@@ -42,6 +49,7 @@ sys.path.insert(0, ROOT)
 
 VARIANTS = ("two_pass", "user", "default")
 VARIANTS_UNSPLIT = ("builtin", "user")
+VARIANTS_CAPA = ("two_pass", "user")
 
 
 def child(args):
@@ -51,7 +59,13 @@ def child(args):
     L = _lib.lib()
     if L.pcl_device_count() < 1:
         raise SystemExit("cellrp_bench: no HIP device (nothing here can be measured without one)")
-    if args.unsplit:
+    if args.fwave:
+        from apps import psystem
+        claw = psystem.psystem2D(pyclaw, mx=args.n, my=args.n, solver_type='classic', run=False, math=args.math,
+                                 user_rp=args.child == "user")
+    elif args.capa:
+        claw = problems.capa_acoustics2D(pyclaw, mx=args.n, my=args.n, run=False, math=args.math, user_rp=args.child == "user")
+    elif args.unsplit:
         make = problems.vc_acoustics2D if args.aux else problems.acoustics2D
         claw = make(pyclaw, mx=args.n, my=args.n, run=False, math=args.math, dim_split=0, user_rp=args.child == "user")
         claw.solver.order_trans = 2
@@ -69,7 +83,7 @@ def child(args):
             t0 = time.perf_counter()
             plain.compile(args.math)
             res["compile_plain_s"] = time.perf_counter() - t0
-        elif not args.aux:
+        elif not args.aux and not args.fwave and not args.capa:
             g = state.aux_global
             solver.rp = pyclaw.CellRiemann(problems.ACOUSTICS_2D_RP, 3, 2, 2, params=[g['rho'], g['bulk'], g['cc'], g['zz']])
         t0 = time.perf_counter()
@@ -77,7 +91,10 @@ def child(args):
         res["compile_s"] = time.perf_counter() - t0
     solver.setup(solution)
     solver.dt_variable = False
-    solver.dt = 0.45 * min(state.grid.d) / (float(state.aux[1].max()) if args.aux else state.aux_global['cc'])
+    if args.fwave or args.capa:
+        solver.dt = solver.dt_initial       # the app's own first step: within its cfl_desired on either state
+    else:
+        solver.dt = 0.45 * min(state.grid.d) / (float(state.aux[1].max()) if args.aux else state.aux_global['cc'])
     q_pulse = state.q.copy('F')
     rng = np.random.default_rng(7)
     q_dense = q_pulse + 0.01 * rng.standard_normal(q_pulse.shape)
@@ -111,12 +128,18 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--aux", action="store_true", help="the variable-coefficient problem: vc_acoustics_2d against CellRiemann(aux=(0, 1))")
     ap.add_argument("--unsplit", action="store_true", help="the unsplit step: the built-in solver against CellRiemann(transverse=...)")
+    ap.add_argument("--fwave", action="store_true", help="the p-system: psystem_fwave_2d against CellRiemann(fwave=True)")
+    ap.add_argument("--capa", action="store_true", help="acoustics with a capacity function: the built-in two passes against CellRiemann(capa=True)")
     ap.add_argument("--child", default=None, choices=VARIANTS + VARIANTS_UNSPLIT)
     args = ap.parse_args()
+    if (args.fwave or args.capa) and (args.aux or args.unsplit or (args.fwave and args.capa)):
+        raise SystemExit("cellrp_bench: --fwave and --capa are measurements of their own (not with --aux, --unsplit or each other)")
     if args.child:
         return child(args)
 
-    variants = VARIANTS_UNSPLIT if args.unsplit else VARIANTS
+    variants = VARIANTS_UNSPLIT if args.unsplit else VARIANTS_CAPA if args.capa else VARIANTS
+    mode = (["--aux"] if args.aux else []) + (["--unsplit"] if args.unsplit else []) + (["--fwave"] if args.fwave else []) + \
+           (["--capa"] if args.capa else [])
     runs = {v: [] for v in variants}
     for _ in range(args.reps):
         for v in variants:
@@ -125,8 +148,7 @@ def main():
             if v == "two_pass":
                 env["PCL_TUNE_FUSED_STEP"] = "0"
             cmd = [sys.executable, os.path.abspath(__file__), "--child", v, "--n", str(args.n), "--steps", str(args.steps),
-                   "--warmup", str(args.warmup), "--math", args.math] + (["--aux"] if args.aux else []) + \
-                  (["--unsplit"] if args.unsplit else [])
+                   "--warmup", str(args.warmup), "--math", args.math] + mode
             out = subprocess.run(cmd, env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=300)
             lines = [l for l in out.stdout.splitlines() if l.startswith("CELLRP_CHILD ")]
             if out.returncode != 0 or not lines:
@@ -137,7 +159,7 @@ def main():
 
     def spread(vals):
         return {"median": float(np.median(vals)), "min": min(vals), "max": max(vals), "all": vals}
-    res = {"tool": "cellrp_bench" + (" --aux" if args.aux else "") + (" --unsplit" if args.unsplit else ""), "n": args.n, "math": args.math, "steps": args.steps, "warmup": args.warmup, "reps": args.reps,
+    res = {"tool": " ".join(["cellrp_bench"] + mode), "n": args.n, "math": args.math, "steps": args.steps, "warmup": args.warmup, "reps": args.reps,
            "compile_s": spread([r["compile_s"] for r in runs["user"]]), "forms": {v: runs[v][-1]["forms"] for v in variants},
            "states": {}}
     if args.unsplit:
@@ -153,10 +175,11 @@ def main():
             st["user_and_builtin_spreads_overlap"] = not (b["min"] > a["max"] or a["min"] > b["max"])
             res["states"][name] = st
             continue
-        a, b, c = (st[v + "_ms"] for v in variants)
+        a, b = st["two_pass_ms"], st["user_ms"]
         st["user_over_two_pass"] = b["median"] / a["median"]
         st["user_and_two_pass_spreads_overlap"] = not (b["min"] > a["max"] or a["min"] > b["max"])
-        st["user_over_default"] = b["median"] / c["median"]
+        if "default" in variants:
+            st["user_over_default"] = b["median"] / st["default_ms"]["median"]
         res["states"][name] = st
     line = json.dumps(res)
     print(line)

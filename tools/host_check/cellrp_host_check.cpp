@@ -5,6 +5,9 @@
 // checks and a PCL_RP_CELL handle stays without a solver: every step is refused, which is the path checked here.
 // The second half does the same for solvers that read aux (pcl_cellrp_compile_aux, pcl_cellrp_aux): the list in the
 // cache key, every refusal of a list, and attach against a solver whose maux does not reach it.
+// The third half is the form (pcl_cellrp_compile_form, pcl_cellrp_form): a compile per form, hit and miss on the form, form 0
+// as pcl_cellrp_compile_t's entry, the refusals with the compile count unmoved, pcl_create_cellrp against every pair of
+// handle and configuration, and attach of a handle of another form.
 // Exit status 0 and no sanitizer report: passed.  tools/host_check/run.sh
 #include <cstdio>
 #include <cstdlib>
@@ -189,6 +192,101 @@ int main() {
     CHECK(pcl_cellrp_release(x31));
     CHECK(pcl_cellrp_release(y31));
     CHECK(pcl_cellrp_release(plain));
+
+    // ---- the form of a solver: pcl_cellrp_compile_form, pcl_cellrp_form ----
+    // (a body that assigns neither wave nor fwave compiles in every form)
+    static const char *kSpeeds = "s[0] = -p[2]; s[1] = p[2];\n";
+    static const char *kNoTrans = "";
+    const int FW = PCL_CELLRP_FORM_FWAVE, CA = PCL_CELLRP_FORM_CAPA;
+    pcl_cellrp *f[4] = {nullptr, nullptr, nullptr, nullptr}, *again = nullptr, *viat = nullptr;
+    CHECK(pcl_cellfn_stats(&n0, &h0));
+    // the refusals, in front of the compiler: an unknown bit, and one plane too many with the capacity function's
+    EXPECT(pcl_cellrp_compile_form(kSpeeds, kNoTrans, "", 3, 2, 2, PCL_MATH_EXACT, nullptr, 0, 4, &bad, nullptr) == PCL_EINVAL && !bad);
+    EXPECT(strstr(pcl_last_error(), "form = 4") != nullptr);
+    EXPECT(pcl_cellrp_compile_form(kSpeeds, kNoTrans, "", 3, 2, 2, PCL_MATH_EXACT, nullptr, 0, -1, &bad, nullptr) == PCL_EINVAL && !bad);
+    EXPECT(pcl_cellrp_compile_form(kSpeeds, nullptr, "", 3, 2, 2, PCL_MATH_EXACT, many, 5, CA, &bad, nullptr) == PCL_EINVAL && !bad);
+    EXPECT(strstr(pcl_last_error(), "meqn + 1 + naux = 9") != nullptr && strstr(pcl_last_error(), "at most 8 planes") != nullptr);
+    CHECK(pcl_cellfn_stats(&n, &h));
+    EXPECT(n == n0 && h == h0);
+    // form 0 is pcl_cellrp_compile_t: one entry, whichever door
+    CHECK(pcl_cellrp_compile_t(kSpeeds, kNoTrans, "", 3, 2, 2, PCL_MATH_EXACT, nullptr, 0, &viat, &size));
+    long size0 = 0;
+    CHECK(pcl_cellrp_compile_form(kSpeeds, kNoTrans, nullptr, 3, 2, 2, PCL_MATH_EXACT, nullptr, 0, 0, &f[0], &size0));
+    EXPECT(f[0] == viat && size0 == size);
+    CHECK(pcl_cellfn_stats(&n, &h));
+    EXPECT(n == n0 + 1 && h == h0 + 1);
+    // every other form is a program of its own; hit and miss on the form; the form comes back
+    for (int form = 1; form < 4; form++) {
+        CHECK(pcl_cellrp_compile_form(kSpeeds, kNoTrans, "", 3, 2, 2, PCL_MATH_EXACT, nullptr, 0, form, &f[form], &size));
+        EXPECT(f[form] && size > 0);
+        for (int k = 0; k < form; k++) EXPECT(f[form] != f[k]);
+    }
+    CHECK(pcl_cellrp_compile_form(kSpeeds, kNoTrans, "", 3, 2, 2, PCL_MATH_EXACT, nullptr, 0, FW | CA, &again, nullptr));
+    EXPECT(again == f[FW | CA]);
+    CHECK(pcl_cellfn_stats(&n, &h));
+    EXPECT(n == n0 + 4 && h == h0 + 2);
+    for (int form = 0; form < 4; form++) {
+        int got = -1;
+        CHECK(pcl_cellrp_form(f[form], &got));
+        EXPECT(got == form);
+    }
+    int got = -1;
+    EXPECT(pcl_cellrp_form(nullptr, &got) == PCL_EINVAL);
+    EXPECT(pcl_cellrp_form(f[0], nullptr) == PCL_EINVAL);
+    // an f-wave body assigns fwave; one that assigns wave does not compile, and its line is named
+    EXPECT(pcl_cellrp_compile_form("s[0] = 1.0;\nwave[0][0] = qr[0] - ql[0];\n", nullptr, "", 1, 1, 1, PCL_MATH_EXACT, nullptr, 0, FW, &bad,
+                                   nullptr) == PCL_EINVAL && !bad);
+    EXPECT(strstr(pcl_last_error(), "riemann:2") != nullptr);
+    pcl_cellrp *fw1 = nullptr;
+    CHECK(pcl_cellrp_compile_form("s[0] = 1.0;\nfwave[0][0] = qr[0] - ql[0];\napdq[0] = fwave[0][0];\n", nullptr, "", 1, 1, 1, PCL_MATH_EXACT,
+                                  nullptr, 0, FW, &fw1, nullptr));
+
+    // pcl_create_cellrp against matching and mismatching handles, dimension-split and unsplit: a match passes every host
+    // check and reaches the shim's module load (PCL_EHIP), every mismatch is PCL_EINVAL in front of the device
+    pcl_config fc;
+    memset(&fc, 0, sizeof fc);
+    fc.ndim = 2; fc.n[0] = 9; fc.n[1] = 7; fc.mbc = 2; fc.meqn = 3; fc.mwaves = 2; fc.maux = 2;
+    fc.method[0] = 1; fc.method[1] = 2; fc.method[6] = 2;
+    fc.mthlim[0] = fc.mthlim[1] = 4; fc.rp = PCL_RP_CELL; fc.d[0] = fc.d[1] = 0.1; fc.math = PCL_MATH_EXACT;
+    for (int unsplit = 0; unsplit < 2; unsplit++)
+        for (int want = 0; want < 4; want++)
+            for (int have = 0; have < 4; have++) {
+                pcl_config k = fc;
+                k.method[2] = unsplit ? 2 : -1;
+                k.fwave = (want & FW) ? 1 : 0;
+                k.method[5] = (want & CA) ? 2 : 0;
+                s = nullptr;
+                const int rc = pcl_create_cellrp(&k, f[have], &s);
+                EXPECT(!s);
+                if (have == want) EXPECT(rc == PCL_EHIP);
+                else {
+                    EXPECT(rc == PCL_EINVAL && strstr(pcl_last_error(), "PCL_RP_CELL") != nullptr);
+                    EXPECT(strstr(pcl_last_error(), ((have ^ want) & FW) ? "f-waves" : "capacity function") != nullptr);
+                }
+                if (want) EXPECT(pcl_create(&k, &s) == PCL_EINVAL && !s);      // pcl_create cannot know a handle
+            }
+    {   // mcapa stays within maux
+        pcl_config k = fc;
+        k.method[2] = -1; k.method[5] = 3;
+        EXPECT(pcl_create_cellrp(&k, f[CA], &s) == PCL_EINVAL && !s);
+    }
+    // attach on a solver made by pcl_create (wave form, no capacity function): a handle of another form is refused in front
+    // of the module load, one of its own form gets as far as the load; the steps stay refused; release, destroy
+    fc.method[2] = -1;
+    s = nullptr;
+    CHECK(pcl_create(&fc, &s));
+    for (int form = 1; form < 4; form++) {
+        EXPECT(pcl_cellrp_attach(s, f[form]) == PCL_EINVAL);
+        EXPECT(strstr(pcl_last_error(), "PCL_RP_CELL") != nullptr);
+    }
+    EXPECT(pcl_cellrp_attach(s, f[0]) == PCL_EHIP);
+    EXPECT(pcl_step_hyperbolic(s, 0.01, &cfl) == PCL_ESTATE);
+    pcl_destroy(s);
+    for (int form = 0; form < 4; form++) CHECK(pcl_cellrp_release(f[form]));
+    CHECK(pcl_cellrp_release(viat));
+    CHECK(pcl_cellrp_release(again));
+    CHECK(pcl_cellrp_release(fw1));
+    EXPECT(pcl_cellrp_release(fw1) == PCL_EINVAL);
     printf("cellrp_host_check: ok\n");
     return 0;
 }
