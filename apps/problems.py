@@ -504,8 +504,9 @@ def ac2d_qinit(state, width=0.2):
 
 def acoustics2D(pyclaw, mx=100, my=100, tfinal=0.12, nout=10, dim_split=1, run=True, math='exact',
                 solver_type='classic', lim_type=2, time_integrator='SSP104', weno_order=5, user_rp=False):
-    """test/acoustics/2d/homogeneous/acoustics.py:19-86 (classic or sharpclaw).  user_rp=True (classic): the same solver
-    as the bodies ACOUSTICS_2D_RP / ACOUSTICS_2D_RPT of a pyclaw.CellRiemann, dimension-split or unsplit."""
+    """test/acoustics/2d/homogeneous/acoustics.py:19-86 (classic or sharpclaw).  user_rp=True: the same solver as the
+    bodies ACOUSTICS_2D_RP / ACOUSTICS_2D_RPT of a pyclaw.CellRiemann, dimension-split or unsplit (classic), or as
+    ACOUSTICS_2D_RP compiled for the SharpClaw stages (sharpclaw=True)."""
     if solver_type == 'classic':
         solver = pyclaw.ClawSolver2D()
     else:
@@ -537,7 +538,10 @@ def acoustics2D(pyclaw, mx=100, my=100, tfinal=0.12, nout=10, dim_split=1, run=T
     state.aux_global['zz'] = zz
     state.aux_global['cc'] = cc
     ac2d_qinit(state)
-    if user_rp:
+    if user_rp and solver_type != 'classic':
+        solver.rp = pyclaw.CellRiemann(ACOUSTICS_2D_RP, 3, 2, 2, params=[rho, bulk, cc, zz], name="acoustics_2d_user",
+                                       sharpclaw=True)
+    elif user_rp:
         # (the transverse body only where the unsplit step asks for it: the split run compiles the two sweeps alone)
         solver.rp = pyclaw.CellRiemann(ACOUSTICS_2D_RP, 3, 2, 2, params=[rho, bulk, cc, zz], name="acoustics_2d_user",
                                        transverse=None if dim_split else ACOUSTICS_2D_RPT)
@@ -609,8 +613,10 @@ def capa_acoustics2D(pyclaw, mx=100, my=100, tfinal=0.12, nout=10, run=True, mat
 
 
 def acoustics1D(pyclaw, mx=100, solver_type='classic', lim_type=2, time_integrator='SSP104', weno_order=5,
-                math='exact', char_decomp=0):
-    """test/acoustics/1d/homogeneous/acoustics.py: returns the one-period L1 error."""
+                math='exact', char_decomp=0, user_rp=False, run=True):
+    """test/acoustics/1d/homogeneous/acoustics.py: returns the one-period L1 error.  user_rp=True: the same solver as the
+    body ACOUSTICS_1D_RP of a pyclaw.CellRiemann, compiled for the classic step or for the SharpClaw stages.  run=False:
+    (None, the controller) before anything ran."""
     if solver_type == 'classic':
         solver = pyclaw.ClawSolver1D()
     else:
@@ -630,6 +636,10 @@ def acoustics1D(pyclaw, mx=100, solver_type='classic', lim_type=2, time_integrat
     state.aux_global['bulk'] = bulk
     state.aux_global['zz'] = np.sqrt(rho * bulk)
     state.aux_global['cc'] = np.sqrt(rho / bulk)
+    if user_rp:
+        g = state.aux_global
+        solver.rp = pyclaw.CellRiemann(ACOUSTICS_1D_RP, 2, 2, 1, params=[g['rho'], g['bulk'], g['cc'], g['zz']],
+                                       name="acoustics_1d_user", sharpclaw=solver_type != 'classic')
     xc = grid.x.center
     beta = 100
     gam = 0
@@ -648,6 +658,8 @@ def acoustics1D(pyclaw, mx=100, solver_type='classic', lim_type=2, time_integrat
     claw.tfinal = 1.0
     claw.solution = init_solution
     claw.solver = solver
+    if not run:
+        return None, claw
     claw.run()
     q0 = claw.frames[0].state.q.reshape([-1])
     qfinal = claw.frames[claw.nout].state.q.reshape([-1])

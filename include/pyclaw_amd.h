@@ -73,7 +73,8 @@ extern "C" {
                         /* meqn, mwaves <= 8 from the config, rp_params = the body's p[8]; classic 1-D and dimension-split  */
                         /* 2-D steps (unsplit with a transverse body); the body may read listed aux components              */
                         /* (pcl_cellrp_compile_aux); f-waves and a capacity function through pcl_cellrp_compile_form and    */
-                        /* pcl_create_cellrp.  Not a built-in solver: pcl_rp_info refuses the id                            */
+                        /* pcl_create_cellrp; the SharpClaw stages through pcl_cellrp_compile_sharp and pcl_create_cellrp.  */
+                        /* Not a built-in solver: pcl_rp_info refuses the id                                                */
 
 /* boundary condition types = pyclaw.BC (src/pyclaw/solver.py:17-23) */
 #define PCL_BC_CUSTOM 0
@@ -458,6 +459,24 @@ int pcl_cellrp_compile_form(const char *body, const char *transverse, const char
                             int math, const int *aux_index, int naux, int form, pcl_cellrp **out, long *code_size);
 /* Host-only: the PCL_CELLRP_FORM_* bits a live handle was compiled with. */
 int pcl_cellrp_form(const pcl_cellrp *r, int *form);
+/* The same body in the SHARPCLAW stages (cfg.kind = PCL_KIND_SHARPCLAW): the library compiles its SharpClaw kernels (the
+ * text of csrc/sharpclaw.hpp) around the body in place of the classic sweeps -- the one reconstruction asked for and no
+ * other: lim_type 1 (tvd2), 2 (WENO) or 3 (legacy WENO5) at weno_order 5, weno_order 7..17 (odd) with lim_type 2, for any
+ * system; char_decomp = 1 (wave-based reconstruction) under pcl_create's conditions: ndim 1, lim_type 1 or 2, weno_order 5,
+ * no PCL_CELLRP_FORM_FWAVE.  Everything else is PCL_EINVAL before the compiler.  The body, the preamble, the aux list and
+ * `form` mean what they mean above (an f-wave body assigns fwave[][]; SharpClaw reads s, amdq and apdq alone).  The "equal
+ * ql and qr: zero waves" contract is not relied on: SharpClaw solves every interface and the problem inside every cell,
+ * both edge states of a cell with the cell's own aux values.
+ * Plane limit: the tile of the SharpClaw kernel is 64 cells x TA strips per plane in the 64 KB a workgroup may declare; TA
+ * is 16, or 8 in the y pass from six listed aux components on.  The x pass (and the 1-D pass) stages q and the capacity
+ * function, meqn + capa <= 8; the y pass the listed aux components too, meqn + capa + naux <= 8 (<= 16 from naux = 6 on);
+ * more is PCL_EINVAL with the sum and the limit.  char_decomp = 1 has no tile.
+ * lim_type, weno_order and char_decomp are part of the cache key.  Such a handle serves pcl_create_cellrp with cfg.kind =
+ * PCL_KIND_SHARPCLAW and nothing else.  Host-only. */
+int pcl_cellrp_compile_sharp(const char *body, const char *preamble, int meqn, int mwaves, int ndim, int math, const int *aux_index,
+                             int naux, int form, int lim_type, int weno_order, int char_decomp, pcl_cellrp **out, long *code_size);
+/* Host-only: what a live handle was compiled for by pcl_cellrp_compile_sharp; three zeros for a classic handle. */
+int pcl_cellrp_sharp(const pcl_cellrp *r, int *lim_type, int *weno_order, int *char_decomp);
 /* Host-only: *has = 1 if the live handle was compiled with a transverse body, and then *slices (may be null) = the slices
  * per workgroup of its unsplit kernels; else *has = 0, *slices = 0. */
 int pcl_cellrp_transverse(const pcl_cellrp *r, int *has, int *slices);
@@ -469,7 +488,13 @@ int pcl_cellrp_transverse(const pcl_cellrp *r, int *has, int *slices);
  * blocks, the y phase always in its tile form.
  * The form likewise: cfg.fwave != 0 is accepted if and only if the handle has PCL_CELLRP_FORM_FWAVE, cfg.method[5] > 0
  * (1 <= method[5] <= maux as for any solver) if and only if it has PCL_CELLRP_FORM_CAPA; every other combination is
- * PCL_EINVAL, in either direction.  pcl_create goes on refusing cfg.fwave and method[5] != 0 for PCL_RP_CELL. */
+ * PCL_EINVAL, in either direction.  pcl_create goes on refusing cfg.fwave and method[5] != 0 for PCL_RP_CELL.
+ * SharpClaw likewise: cfg.kind = PCL_KIND_SHARPCLAW is accepted if and only if the handle was compiled by
+ * pcl_cellrp_compile_sharp and its lim_type, (weno_order + 1) / 2 and char_decomp equal cfg.lim_type, cfg.mbc and
+ * cfg.method[4] (and its form bits cfg.fwave and method[5] > 0, as above); such a handle on cfg.kind = PCL_KIND_CLASSIC, a
+ * classic handle on SharpClaw and every mismatch are PCL_EINVAL with both sides in the message.  pcl_create goes on
+ * refusing PCL_RP_CELL under SharpClaw.  One block (pcl_comm_init* refuses PCL_RP_CELL), no fused dq source
+ * (pcl_sharp_fuse_dq_src refuses it: a source term runs as its own pass). */
 int pcl_create_cellrp(const pcl_config *cfg, pcl_cellrp *r, pcl_solver **out);
 /* Host-only: the list a live handle was compiled with; aux_index (may be null) gets *naux <= 8 entries. */
 int pcl_cellrp_aux(const pcl_cellrp *r, int *naux, int *aux_index);

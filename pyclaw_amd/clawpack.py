@@ -304,6 +304,10 @@ class ClawSolver(Solver):
     def _check_user_rp(self, state):
         """What a user-written Riemann solver (riemann.CellRiemann) does not serve, each refused with its reason."""
         from . import parallel
+        if self.rp.sharpclaw:
+            raise NotImplementedError("CellRiemann: this solver was written with sharpclaw=True: it is compiled into the "
+                                      "SharpClaw kernels and serves SharpClawSolver1D / SharpClawSolver2D alone; a classic "
+                                      "solver takes a CellRiemann without it")
         if self.ndim == 3:
             raise NotImplementedError("CellRiemann: the user-written solver is compiled into the 1-D and 2-D sweep kernels; "
                                       "ClawSolver3D has no sweep for it")

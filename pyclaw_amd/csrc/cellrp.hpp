@@ -78,8 +78,28 @@
 //     meqn + 1 + naux <= cellrp_max_planes() = 8, refused on the host with the sum and by the static_assert of kCellrpForm.
 //     The unsplit kernels read capa from global memory per lane (classic.hpp: unsplit_x_kernel, unsplit_y_kernel, `if
 //     constexpr (CAPA)`) and declare no LDS for it, so unsplit_user_slices(meqn) stands as it is.
+//
+// A SHARPCLAW handle (pcl_cellrp_compile_sharp, CellRiemann(sharpclaw=True)) is the same struct inside another text: the
+// program includes sharpclaw.hpp (embedded with weno_tables.hpp) in place of classic.hpp and asks for the SharpClaw
+// kernels of the one reconstruction the run needs and for no classic kernel --
+//     sharp_kernel<UserRp, 1, CAPA, LIM, K>                                       1-D
+//     sharp_kernel<UserRp, 1, CAPA, LIM, K>, sharp_kernel<UserRp, 2, CAPA, LIM, K>  the x and y passes in 2-D
+//     sharp1w_kernel<UserRp, LIM, CAPA>                                           char_decomp = 1 (1-D, LIM 1 or 2, K 3)
+// LIM = lim_type 1..3, K = mbc = (weno_order + 1) / 2 = 3, or 4..9 with LIM 2: any system gets every order, since only one
+// (LIM, K, CAPA) is instantiated.  The kernels ask of RP what the wrapper has (Cell, precell<IXY> with and without aux,
+// solve<IXY>, MEQN, MWAVES, NAUX, aux_index<IXY>) and have no FWAVE flag -- they read s, amdq, apdq alone -- so the struct
+// gets no member for them and the form's members (kCellrpForm) are left out; an f-wave body still names its array fwave.
+// The "equal q => zero waves" contract is not relied on: every interface and the problem inside every cell are solved.
+// The handle records (lim_type, weno_order, char_decomp), part of its key ("rps<lim>.<order>.<cd>,..."); it serves
+// pcl_create_cellrp with cfg.kind = PCL_KIND_SHARPCLAW whose lim_type, mbc, method[4], fwave and method[5] > 0 say the same,
+// and nothing else; launch_sharp (kernels.hip) checks the same once more and launches over the built-in grids.
+// Limit: sharp_kernel's tile is static LDS of TA * 64 doubles per plane, TA = sharp_tile_across (16; 8 in the y pass from
+// six aux components on); the x pass stages meqn + capa planes, the y pass meqn + capa + naux, each within 64 KB
+// (sharp_tile_max_planes, kernels.hip, next to sweep_tile_max_planes): refused on the host with the sum and by the
+// static_assert of kCellrpCloseSharp.  A classic handle's program text, key and symbols are what they were.
+// Not served under SharpClaw: a fused dq source (a source term runs as its own pass), char_decomp 2 / 3, tfluct.
 // Not served in any form: HAS_QCOR (the sphere solver's conservation fix), a transverse body with both cells and aux, the
-// marching y phase, the one-kernel step, SharpClaw, 3-D, more than one block.
+// marching y phase, the one-kernel step, 3-D, more than one block.
 #pragma once
 #include "cellfn.hpp"
 // generated by the Makefile (embed_headers.py): PCL_RTC_FLAGS_EXACT / _FAST / _STRICT, the flags kernels_<mode>.o is built
@@ -104,12 +124,30 @@ struct pcl_cellrp {
     std::string sym_u[2];
     // PCL_CELLRP_FORM_* bits: what the kernels in the code object were instantiated for (f-waves, a capacity function)
     int form = 0;
+    // a SharpClaw handle (pcl_cellrp_compile_sharp): the code object holds sharp_kernel<UserRp, 1 / 2, CAPA, lim_type, mbc>
+    // (sym[0], sym[1]) or, with char_decomp = 1, sharp1w_kernel<UserRp, lim_type, CAPA> (sym[0]) and no classic kernel
+    bool sharp = false;
+    int lim_type = 0, weno_order = 0, char_decomp = 0;
 };
 
 namespace pcl {
 
+// what a SharpClaw handle is compiled for (lim_type 0: a classic handle)
+struct CellrpSharp {
+    int lim_type = 0, weno_order = 0, char_decomp = 0;
+    bool on() const { return lim_type != 0; }
+    int mbc() const { return (weno_order + 1) / 2; }
+};
+
 static const char *const kCellrpHead = R"PCLSRC(
 #include "classic.hpp"
+namespace pcl {
+namespace PCL_NS {
+)PCLSRC";
+
+// a SharpClaw handle: the same wrapper struct inside the text of the SharpClaw kernels
+static const char *const kCellrpHeadSharp = R"PCLSRC(
+#include "sharpclaw.hpp"
 namespace pcl {
 namespace PCL_NS {
 )PCLSRC";
@@ -293,6 +331,20 @@ static const char *const kCellrpForm = R"PCLSRC(
                   "meqn + 1 + naux: the LDS tile of sweep_kernel (classic.hpp) with the capacity function's plane does not fit a workgroup's 64 KB");
 )PCLSRC";
 
+// The end of a SharpClaw handle's text.  The plane limit the host refused over (kernels.hip: sharp_tile_max_planes, next to
+// sweep_tile_max_planes) restated: sharp_kernel's tile is static LDS of NP * TA * WAVE doubles, NP = meqn + capa in the x
+// pass and meqn + capa + naux in the y pass, TA = sharp_tile_across<UserRp, IXY>().  sharp1w_kernel declares no LDS.
+static const char *const kCellrpCloseSharp = R"PCLSRC(};
+static constexpr int USER_SHARP_CAPA = (PCL_CELLRP_FORM & 2) != 0 ? 1 : 0;
+static_assert(PCL_CELLRP_SHARP_CD == 1 ||
+                  (sizeof(double) * (UserRp::MEQN + USER_SHARP_CAPA) * sharp_tile_across<UserRp, 1>() * WAVE <= 65536 &&
+                   (UserRp::NDIM == 1 ||
+                    sizeof(double) * (UserRp::MEQN + USER_SHARP_CAPA + UserRp::NAUX) * sharp_tile_across<UserRp, 2>() * WAVE <= 65536)),
+              "meqn + capa + naux: the LDS tile of sharp_kernel (sharpclaw.hpp) does not fit the 64 KB a workgroup may declare");
+}  // namespace PCL_NS
+}  // namespace pcl
+)PCLSRC";
+
 // the slices per workgroup the host named the unsplit kernels with are the rule's, and both kernels' static LDS fits
 static const char *const kCellrpTransCheck = R"PCLSRC(
     static constexpr int USLICES = PCL_CELLRP_USLICES;
@@ -307,9 +359,13 @@ static inline const char *cellrp_ns(int math) { return math == 1 ? "fast" : math
 // (without a list the key is what it was before there were lists: the same entry as pcl_cellrp_compile's; without a
 // transverse text it is what it was before there were transverse texts; form 0 likewise)
 static inline std::string cellrp_key(const char *body, const char *preamble, int meqn, int mwaves, int ndim, int math,
-                                     const int *aux = nullptr, int naux = 0, const char *trans = nullptr, int form = 0) {
-    std::string k = std::string(trans ? "rpt," : "rp,") + std::to_string(meqn) + "," + std::to_string(mwaves) + "," +
-                    std::to_string(ndim) + "," + std::to_string(math) + ",";
+                                     const int *aux = nullptr, int naux = 0, const char *trans = nullptr, int form = 0,
+                                     const CellrpSharp &sharp = CellrpSharp()) {
+    // (a SharpClaw handle: its own prefix with lim_type, weno_order and char_decomp; a classic key is what it was)
+    std::string k = sharp.on() ? "rps" + std::to_string(sharp.lim_type) + "." + std::to_string(sharp.weno_order) + "." +
+                                     std::to_string(sharp.char_decomp) + ","
+                               : std::string(trans ? "rpt," : "rp,");
+    k += std::to_string(meqn) + "," + std::to_string(mwaves) + "," + std::to_string(ndim) + "," + std::to_string(math) + ",";
     for (int i = 0; i < naux; i++) k += (i ? "." : "aux") + std::to_string(aux[i]);
     if (naux > 0) k += ",";
     if (form) k += "form" + std::to_string(form) + ",";     // (form 0: the key of before there were forms)
@@ -323,9 +379,23 @@ static inline std::string cellrp_key(const char *body, const char *preamble, int
 // the sweep kernels of a UserRp of this dimension, as hiprtc name expressions; uslices > 0 (a transverse body, 2-D): the
 // x and y phases of the unsplit step behind them, the tile form of either, without a fused source.  CAPA and FWAVE of every
 // one come from the form: a handle serves one form, so only that form's instantiations are compiled
-static inline std::vector<std::string> cellrp_exprs(int ndim, int math, int uslices = 0, int form = 0) {
+// A SharpClaw handle asks for the SharpClaw kernels of its one (LIM, K, CAPA) and for no classic kernel: sharp_kernel<UserRp,
+// 1, CAPA, LIM, K> (1-D), the same and <UserRp, 2, ...> (2-D), or sharp1w_kernel<UserRp, LIM, CAPA> (char_decomp = 1).  The
+// kernels have no FWAVE flag: they read s, amdq and apdq alone
+static inline std::vector<std::string> cellrp_exprs(int ndim, int math, int uslices = 0, int form = 0,
+                                                    const CellrpSharp &sharp = CellrpSharp()) {
     const std::string ns = std::string("pcl::") + cellrp_ns(math) + "::";
     const char *fw = (form & PCL_CELLRP_FORM_FWAVE) ? "true" : "false", *capa = (form & PCL_CELLRP_FORM_CAPA) ? "true" : "false";
+    if (sharp.on()) {
+        const std::string lim = std::to_string(sharp.lim_type);
+        if (sharp.char_decomp == 1) return {"&" + ns + "sharp1w_kernel<" + ns + "UserRp, " + lim + ", " + capa + ">"};
+        auto sk = [&](int ixy) {
+            return "&" + ns + "sharp_kernel<" + ns + "UserRp, " + std::to_string(ixy) + ", " + capa + ", " + lim + ", " +
+                   std::to_string(sharp.mbc()) + ">";
+        };
+        if (ndim == 1) return {sk(1)};
+        return {sk(1), sk(2)};
+    }
     auto k = [&](int ixy, bool dim1) {
         return "&" + ns + "sweep_kernel<" + ns + "UserRp, " + std::to_string(ixy) + ", " + capa + ", " + fw + ", " + (dim1 ? "true" : "false") + ">";
     };
@@ -341,12 +411,14 @@ static inline std::vector<std::string> cellrp_exprs(int ndim, int math, int usli
 // trans (null: none, the program text of before): the transverse body; uslices: the slices per workgroup of the unsplit
 // kernels it is compiled into; sym[2], sym[3]: their lowered names
 // form (0: the program text of before): PCL_CELLRP_FORM_* bits; with the f-wave bit the array the body assigns is `fwave`
+// sharp (off: the program text of before): a SharpClaw handle; the text includes sharpclaw.hpp, the struct gets no form
+// members (the SharpClaw kernels read none) and the name expressions are the SharpClaw kernels alone
 static inline int cellrp_build(const char *body, const char *trans, const char *preamble, int meqn, int mwaves, int ndim, int math,
-                               const int *aux, int naux, int uslices, int form, std::vector<char> &code, std::string (&sym)[4],
-                               std::string &err) {
+                               const int *aux, int naux, int uslices, int form, const CellrpSharp &sharp, std::vector<char> &code,
+                               std::string (&sym)[4], std::string &err) {
     if (hiprtc_load(err)) return -1;
     HiprtcApi &a = hiprtc_api();
-    std::string src = kCellrpHead;
+    std::string src = sharp.on() ? kCellrpHeadSharp : kCellrpHead;
     src += "#line 1 \"preamble\"\n";
     src += preamble;
     src += "\n#line 1 \"pcl_cellrp_wrapper\"\n";
@@ -376,12 +448,12 @@ static inline int cellrp_build(const char *body, const char *trans, const char *
         src += naux > 0 ? kCellrpTransTailAux : kCellrpTransTail;
         src += kCellrpTransCheck;
     }
-    if (form) src += kCellrpForm;
-    src += naux > 0 ? kCellrpCloseAux : kCellrpClose;
+    if (form && !sharp.on()) src += kCellrpForm;
+    src += sharp.on() ? kCellrpCloseSharp : naux > 0 ? kCellrpCloseAux : kCellrpClose;
     hiprtcProgram prog = nullptr;
     hiprtcResult r = a.hiprtcCreateProgram(&prog, src.c_str(), "pcl_cellrp.hip", kCellrpHeaderCount, kCellrpHeaderTexts, kCellrpHeaderNames);
     if (r != HIPRTC_SUCCESS) { err = std::string("hiprtcCreateProgram: ") + a.hiprtcGetErrorString(r); return -1; }
-    const std::vector<std::string> exprs = cellrp_exprs(ndim, math, trans ? uslices : 0, form);
+    const std::vector<std::string> exprs = cellrp_exprs(ndim, math, trans ? uslices : 0, form, sharp);
     for (const std::string &e : exprs) {
         r = a.hiprtcAddNameExpression(prog, e.c_str());
         if (r != HIPRTC_SUCCESS) {
@@ -408,7 +480,8 @@ static inline int cellrp_build(const char *body, const char *trans, const char *
     flags.push_back("-DPCL_CELLRP_NDIM=" + std::to_string(ndim));
     if (naux > 0) flags.push_back("-DPCL_CELLRP_NAUX=" + std::to_string(naux));
     if (trans) flags.push_back("-DPCL_CELLRP_USLICES=" + std::to_string(uslices));
-    if (form) flags.push_back("-DPCL_CELLRP_FORM=" + std::to_string(form));
+    if (form || sharp.on()) flags.push_back("-DPCL_CELLRP_FORM=" + std::to_string(form));
+    if (sharp.on()) flags.push_back("-DPCL_CELLRP_SHARP_CD=" + std::to_string(sharp.char_decomp));
     std::vector<const char *> opts;
     for (const std::string &f : flags) opts.push_back(f.c_str());
     r = a.hiprtcCompileProgram(prog, (int)opts.size(), opts.data());
@@ -460,9 +533,13 @@ struct CellrpModule {
     hipFunction_t fn_u[2] = {nullptr, nullptr};
     int slices = 0;
     int form = 0;               // PCL_CELLRP_FORM_* bits of the attached solver: what its kernels were instantiated for
+    // a SharpClaw handle: fn holds the SharpClaw kernels (by ids - 1; fn[0] alone with char_decomp = 1) of this lim_type,
+    // mbc and char_decomp; sharp_mbc = 0: a classic handle, fn holds the sweeps
+    int sharp_lim = 0, sharp_mbc = 0, sharp_cd = 0;
     void unload() {
         if (mod) (void)hipModuleUnload(mod);
         mod = nullptr; fn[0] = fn[1] = fn_u[0] = fn_u[1] = nullptr; id = 0; naux = 0; slices = 0; form = 0;
+        sharp_lim = sharp_mbc = sharp_cd = 0;
     }
 };
 

@@ -96,6 +96,7 @@ static int user_form_check(const SweepLaunch &l, std::string &err) {
 // module compiled at run time from the text of classic.hpp, so the kernel's parameters are those of the launches below.
 template <int IXY, bool DIM1> int launch_user(const SweepLaunch &l, std::string &err) {
     if (!l.user_fn) { err = "user-written Riemann solver: no compiled solver is attached (pcl_cellrp_attach)"; return PCL_ESTATE; }
+    if (l.user_sharp_k != 0) { err = "user-written Riemann solver: the attached solver was compiled for SharpClaw and holds no classic sweep"; return PCL_EINVAL; }
     if (l.a.src_id != 0) { err = "user-written Riemann solver: no fused source"; return PCL_EINVAL; }
     if (int rc = user_form_check(l, err)) return rc;
     SweepGrid g;
@@ -301,6 +302,10 @@ int sweep_tile_max_planes() {
     constexpr int PLANE = TileShape<1>::PLANE > TileShape<2>::PLANE ? TileShape<1>::PLANE : TileShape<2>::PLANE;
     return 65536 / ((int)sizeof(double) * PLANE);
 }
+// the same for the SharpClaw kernels of a user-written Riemann solver: sharp_kernel's tile is static LDS of TA * 64 doubles
+// per plane, TA = sharp_tile_across (16; 8 in the y pass from six aux components on).  The y pass (ixy 2) stages meqn + capa
+// + naux planes, the x pass (ixy 1; the 1-D pass too) meqn + capa: it reads aux from global memory.
+int sharp_tile_max_planes(int ixy, int naux) { return 65536 / ((int)sizeof(double) * sharp_tile_across_n(ixy, naux) * WAVE); }
 // the same for the one-kernel step (classic_fused.hpp): tile (ty, tx) reads rows mbc-2+F_OWN_R*ty .. +F_ROWS-1 and columns
 // mbc-2+60*tx .. +63; box = [ty_lo, ty_hi) x [tx_lo, tx_hi), ntiles = (nty, ntx)
 bool step2ds_interior_box(const BlockGeom &a, int box[4], int ntiles[2]) {
@@ -476,10 +481,12 @@ int launch_unsplit(const SweepLaunch &l, const double *qx, std::string &err) {
 
 // SharpClaw: dq of one direction (x writes dq, y accumulates)
 namespace {
-template <class RP, int IXY, int K> int launch_sharp_k(const SweepLaunch &l, std::string &err) {
-    SweepArgs a = l.a;
-    constexpr int SH = K, SS = sstrip(K);
-    if (IXY == 1 && a.sub != 0) {
+// The grid of sharp_kernel<., ixy, ., ., K> with ta strips per tile over a, the same for every solver, built in or compiled
+// at run time; the tile subset of a decomposed x pass gets its box here (a.sub is dropped where there is none).
+struct SharpGrid { unsigned nblocks; int ntiles_across, ntiles_along; };
+SharpGrid sharp_grid(SweepArgs &a, int ixy, int K, int ta) {
+    const int SH = K, SS = sstrip(K);
+    if (ixy == 1 && a.sub != 0) {
         // x-pass tiles whose 16 rows x 64 cells lie inside the interior: rows 16*tb .. +15 within [mbc, mbc+my), cells
         // mbc-K+SS*ta .. +63 within [mbc, mbc+mx)
         a.box[0] = (a.mbc + T_ACROSS_S - 1) / T_ACROSS_S;
@@ -487,12 +494,26 @@ template <class RP, int IXY, int K> int launch_sharp_k(const SweepLaunch &l, std
         a.box[2] = 1;
         a.box[3] = a.mx >= WAVE - SH ? (a.mx - (WAVE - SH)) / SS + 1 : 0;
     } else a.sub = 0;
-    const int n_across = IXY == 1 ? a.J : a.I + (LINE - a.mbc);
-    const int m_along = IXY == 1 ? a.mx : a.my;
-    constexpr int TA = sharp_tile_across<RP, IXY>();
-    const int ntiles_across = (n_across + TA - 1) / TA;
-    const int ntiles_along = (m_along + SS - 1) / SS;
-    const dim3 grid((unsigned)ntiles_across * (unsigned)ntiles_along);
+    const int n_across = ixy == 1 ? a.J : a.I + (LINE - a.mbc);
+    const int m_along = ixy == 1 ? a.mx : a.my;
+    SharpGrid g;
+    g.ntiles_across = (n_across + ta - 1) / ta;
+    g.ntiles_along = (m_along + SS - 1) / SS;
+    g.nblocks = (unsigned)g.ntiles_across * (unsigned)g.ntiles_along;
+    return g;
+}
+// sharp1w_kernel: strips of sstrip(3) cells, four to a workgroup
+struct Sharp1wGrid { unsigned nblocks; int nstrips; };
+Sharp1wGrid sharp1w_grid(const SweepArgs &a) {
+    const int nstrips = (a.mx + sstrip(3) - 1) / sstrip(3);
+    return {(unsigned)((nstrips + 3) / 4), nstrips};
+}
+
+template <class RP, int IXY, int K> int launch_sharp_k(const SweepLaunch &l, std::string &err) {
+    SweepArgs a = l.a;
+    const SharpGrid g = sharp_grid(a, IXY, K, sharp_tile_across<RP, IXY>());
+    const int ntiles_across = g.ntiles_across, ntiles_along = g.ntiles_along;
+    const dim3 grid(g.nblocks);
     const bool capa = a.mcapa > 0;
 #define PCL_SHARP_LAUNCH(CAPA_, LIM_)                                                                  \
     hipLaunchKernelGGL((sharp_kernel<RP, IXY, CAPA_, LIM_, K>), grid, dim3(256), 0, l.stream, a, ntiles_across, \
@@ -548,8 +569,9 @@ template <class RP, int IXY, bool HIGH> int launch_sharp_t(const SweepLaunch &l,
 namespace {
 template <class RP> int launch_sharp1w(const SweepLaunch &l, std::string &err) {
     const SweepArgs &a = l.a;
-    const int nstrips = (a.mx + sstrip(3) - 1) / sstrip(3);
-    const dim3 grid((unsigned)((nstrips + 3) / 4));
+    const Sharp1wGrid g = sharp1w_grid(a);
+    const int nstrips = g.nstrips;
+    const dim3 grid(g.nblocks);
     const bool capa = a.mcapa > 0;
 #define PCL_SHARP1W_LAUNCH(LIM_, CAPA_) \
     hipLaunchKernelGGL((sharp1w_kernel<RP, LIM_, CAPA_>), grid, dim3(256), 0, l.stream, a, nstrips)
@@ -561,7 +583,55 @@ template <class RP> int launch_sharp1w(const SweepLaunch &l, std::string &err) {
 }
 }  // namespace
 
+namespace {
+// A user-written Riemann solver under SharpClaw (cellrp.hpp): l.user_fn is sharp_kernel<UserRp, ids, CAPA, LIM, K> or, with
+// char_decomp = 1, sharp1w_kernel<UserRp, LIM, CAPA> of the module compiled at run time -- one (LIM, K, char_decomp), the
+// handle's, with CAPA = l.user_capa -- so this launch must ask for exactly that; the parameters and grids are those of
+// launch_sharp_k / launch_sharp1w.  Whole blocks, no fused dq source.
+int launch_sharp_user(const SweepLaunch &l, std::string &err) {
+    if (!l.user_fn || l.user_sharp_k == 0) {
+        err = "user-written Riemann solver: no solver compiled for SharpClaw is attached (pcl_cellrp_compile_sharp, pcl_create_cellrp)";
+        return PCL_ESTATE;
+    }
+    if (l.a.src_id != 0 || l.a.sub != 0) {
+        err = "user-written Riemann solver under SharpClaw: no fused dq source, whole blocks";
+        return PCL_EINVAL;
+    }
+    if (int rc = user_form_check(l, err)) return rc;
+    if (l.lim_type != l.user_sharp_lim) {
+        err = "user-written Riemann solver: the attached solver was compiled for lim_type " + std::to_string(l.user_sharp_lim) +
+              " and the stage asks for lim_type " + std::to_string(l.lim_type);
+        return PCL_EINVAL;
+    }
+    if (l.a.mbc != l.user_sharp_k) {
+        err = "user-written Riemann solver: the attached solver was compiled for weno_order " + std::to_string(2 * l.user_sharp_k - 1) +
+              " (mbc " + std::to_string(l.user_sharp_k) + ") and the stage runs with mbc " + std::to_string(l.a.mbc);
+        return PCL_EINVAL;
+    }
+    if (l.char_decomp != l.user_sharp_cd) {
+        err = "user-written Riemann solver: the attached solver was compiled for char_decomp " + std::to_string(l.user_sharp_cd) +
+              " and the stage asks for char_decomp " + std::to_string(l.char_decomp);
+        return PCL_EINVAL;
+    }
+    SweepArgs a = l.a;
+    hipError_t e;
+    if (l.char_decomp == 1) {
+        if (l.ndim != 1 || l.a.mbc != 3) { err = "SharpClaw char_decomp = 1: 1-D, mbc 3"; return PCL_EINVAL; }
+        Sharp1wGrid g = sharp1w_grid(a);
+        void *params[] = {&a, &g.nstrips};
+        e = hipModuleLaunchKernel(l.user_fn, g.nblocks, 1, 1, 256, 1, 1, 0, l.stream, params, nullptr);
+    } else {
+        const int ixy = l.ndim == 1 ? 1 : l.ids;
+        SharpGrid g = sharp_grid(a, ixy, l.user_sharp_k, sharp_tile_across_n(ixy, l.user_naux));
+        void *params[] = {&a, &g.ntiles_across, &g.ntiles_along};
+        e = hipModuleLaunchKernel(l.user_fn, g.nblocks, 1, 1, 256, 1, 1, 0, l.stream, params, nullptr);
+    }
+    return e == hipSuccess ? PCL_OK : hip_fail(err, "sharp launch (user-written Riemann solver)", e);
+}
+}  // namespace
+
 int launch_sharp(const SweepLaunch &l, std::string &err) {
+    if (l.rp == PCL_RP_CELL) return launch_sharp_user(l, err);
     const RpFacts *f = Solvers::facts(l.rp);       // the flag follows the solver, among those with SharpClaw kernels
     if ((l.fwave != 0) != (f && f->sharp && f->fwave))
         return not_built(err, "solver.fwave must be True for an f-wave Riemann solver and only for one");

@@ -372,6 +372,20 @@ int frame_launch(pcl_solver *s, hipStream_t stream, double *q, double *dst, cons
     return PCL_OK;
 }
 
+// what a launch of a PCL_RP_CELL solver says about the attached module (cellrp.hpp): the kernel of pass ids -- a classic
+// sweep, or a SharpClaw kernel if the module was compiled for SharpClaw -- and what it was instantiated for
+void user_launch_fields(SweepLaunch &l, const pcl_solver *s, int ids) {
+    l.user_fn = s->cellrp.fn[ids - 1];     // null: nothing attached, refused by the launcher
+    l.user_naux = s->cellrp.naux;
+    l.user_fwave = (s->cellrp.form & PCL_CELLRP_FORM_FWAVE) != 0;
+    l.user_capa = (s->cellrp.form & PCL_CELLRP_FORM_CAPA) != 0;
+    l.user_sharp_lim = s->cellrp.sharp_lim;
+    l.user_sharp_k = s->cellrp.sharp_mbc;
+    l.user_sharp_cd = s->cellrp.sharp_cd;
+    // nothing uploaded yet (listed components or the capacity function): refused by the launcher too
+    if ((l.user_naux > 0 || l.user_capa) && !s->aux_put) l.a.aux = nullptr;
+}
+
 SweepLaunch make_launch(const pcl_solver *s, const SweepArgs &a, int ndim, int ids, hipStream_t stream) {
     SweepLaunch l;
     l.a = a;
@@ -380,14 +394,7 @@ SweepLaunch make_launch(const pcl_solver *s, const SweepArgs &a, int ndim, int i
     l.ids = ids;
     l.fwave = s->cfg.fwave;
     l.stream = stream;
-    if (l.rp == PCL_RP_CELL && ndim <= 2) {
-        l.user_fn = s->cellrp.fn[ids - 1];     // null: nothing attached, refused by the launcher
-        l.user_naux = s->cellrp.naux;
-        l.user_fwave = (s->cellrp.form & PCL_CELLRP_FORM_FWAVE) != 0;
-        l.user_capa = (s->cellrp.form & PCL_CELLRP_FORM_CAPA) != 0;
-        // nothing uploaded yet (listed components or the capacity function): refused by the launcher too
-        if ((l.user_naux > 0 || l.user_capa) && !s->aux_put) l.a.aux = nullptr;
-    }
+    if (l.rp == PCL_RP_CELL && ndim <= 2) user_launch_fields(l, s, ids);
     return l;
 }
 
@@ -698,7 +705,7 @@ int check_device() {
 extern "C" {
 
 const char *pcl_last_error(void) { return g_err.c_str(); }
-int pcl_version(void) { return 109; }
+int pcl_version(void) { return 110; }
 int pcl_device_count(void) {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess) return 0;
@@ -760,7 +767,8 @@ static int create_check(const pcl_config *cfg, bool cell_handle) {
     if (cfg->rp == PCL_RP_CELL) {
         // a user-written normal solver (cellrp.hpp): sizes from the config; it serves the classic 1-D step and the two
         // passes of the dimension-split 2-D step; in wave form without a capacity function unless a handle says otherwise
-        if (cfg->kind != PCL_KIND_CLASSIC)
+        // (SharpClaw: with a handle compiled for it, pcl_cellrp_compile_sharp -- cellrp_fits_locked)
+        if (cfg->kind != PCL_KIND_CLASSIC && !cell_handle)
             return fail(PCL_EINVAL, "PCL_RP_CELL: a user-written Riemann solver runs in the classic sweeps only, not under SharpClaw");
         if (cfg->ndim == 3) return fail(PCL_EINVAL, "PCL_RP_CELL: a user-written Riemann solver is 1-D or 2-D (ndim == 3)");
         if (cfg->fwave && !cell_handle)
@@ -1770,8 +1778,43 @@ int pcl_cellrp_compile_t(const char *body, const char *transverse, const char *p
 // form == 0 is pcl_cellrp_compile_t: the same program text, key and handle.  Any other form (PCL_CELLRP_FORM_* bits) is part
 // of the key, and the code object holds the kernels of that one form: sweep_kernel<UserRp, IXY, CAPA, FWAVE, DIM1> and,
 // with a transverse body, unsplit_x/y_kernel<UserRp, FWAVE, U, CAPA> (cellrp.hpp: cellrp_exprs)
+static int cellrp_compile_impl(const char *body, const char *transverse, const char *preamble, int meqn, int mwaves, int ndim,
+                               int math, const int *aux_index, int naux, int form, const pcl::CellrpSharp &sharp, pcl_cellrp **out,
+                               long *code_size);
 int pcl_cellrp_compile_form(const char *body, const char *transverse, const char *preamble, int meqn, int mwaves, int ndim,
                             int math, const int *aux_index, int naux, int form, pcl_cellrp **out, long *code_size) {
+    return cellrp_compile_impl(body, transverse, preamble, meqn, mwaves, ndim, math, aux_index, naux, form, pcl::CellrpSharp(), out,
+                               code_size);
+}
+
+// The SharpClaw kernels around the body in place of the classic ones: sharp_kernel<UserRp, IXY, CAPA, lim_type, mbc> of the
+// one (lim_type, weno_order) asked for, or sharp1w_kernel<UserRp, lim_type, CAPA> with char_decomp = 1 (cellrp.hpp:
+// cellrp_exprs).  The three are part of the key.  What no SharpClaw kernel exists for is refused here with pcl_create's
+// conditions: lim_type 1..3, weno_order 5..17 odd and above 5 with lim_type 2 only; char_decomp 1 in 1-D with lim_type 1 or
+// 2 at weno_order 5 in wave form.  The tile's plane limit is sharp_tile_max_planes' (kernels.hip).
+int pcl_cellrp_compile_sharp(const char *body, const char *preamble, int meqn, int mwaves, int ndim, int math, const int *aux_index,
+                             int naux, int form, int lim_type, int weno_order, int char_decomp, pcl_cellrp **out, long *code_size) {
+    if (out) *out = nullptr;
+    if (lim_type != 1 && lim_type != 2 && lim_type != 3)
+        return fail(PCL_EINVAL, "pcl_cellrp_compile_sharp: lim_type must be 1 (tvd2), 2 (WENO) or 3 (legacy WENO5), got " + std::to_string(lim_type));
+    if (weno_order < 5 || weno_order > 17 || weno_order % 2 == 0)
+        return fail(PCL_EINVAL, "pcl_cellrp_compile_sharp: weno_order must be odd, 5..17, got " + std::to_string(weno_order));
+    if (weno_order > 5 && lim_type != 2)
+        return fail(PCL_EINVAL, "pcl_cellrp_compile_sharp: weno_order " + std::to_string(weno_order) + " exists for lim_type 2 only, got lim_type " +
+                                    std::to_string(lim_type));
+    if (char_decomp != 0 && char_decomp != 1)
+        return fail(PCL_EINVAL, "pcl_cellrp_compile_sharp: char_decomp must be 0 or 1 (2, 3 need a user evec routine)");
+    if (char_decomp == 1 && (ndim != 1 || lim_type == 3 || weno_order != 5 || (form & PCL_CELLRP_FORM_FWAVE)))
+        return fail(PCL_EINVAL, "pcl_cellrp_compile_sharp: char_decomp = 1 is the wave-based reconstruction: 1-D, lim_type 1 (tvd2_wave) or 2 "
+                                "(weno5_wave), weno_order 5, no f-wave body");
+    pcl::CellrpSharp sharp;
+    sharp.lim_type = lim_type; sharp.weno_order = weno_order; sharp.char_decomp = char_decomp;
+    return cellrp_compile_impl(body, nullptr, preamble, meqn, mwaves, ndim, math, aux_index, naux, form, sharp, out, code_size);
+}
+
+static int cellrp_compile_impl(const char *body, const char *transverse, const char *preamble, int meqn, int mwaves, int ndim,
+                               int math, const int *aux_index, int naux, int form, const pcl::CellrpSharp &sharp, pcl_cellrp **out,
+                               long *code_size) {
     if (!body || !out) return fail(PCL_EINVAL, "null argument");
     *out = nullptr;
     if (!preamble) preamble = "";
@@ -1785,7 +1828,21 @@ int pcl_cellrp_compile_form(const char *body, const char *transverse, const char
     // entry is checked here and the largest against cfg.maux when the handle is attached
     if (naux < 0) return fail(PCL_EINVAL, "pcl_cellrp_compile_aux: naux must be >= 0, got " + std::to_string(naux));
     if (naux > 0 && !aux_index) return fail(PCL_EINVAL, "null argument");
-    const int max_planes = pcl::exact::sweep_tile_max_planes();
+    if (sharp.on() && sharp.char_decomp == 0) {
+        // the tiles of sharp_kernel in place of sweep_kernel's: q and the capacity function in the x pass, the listed aux
+        // components too in the y pass (sharp1w_kernel, char_decomp = 1, has no tile)
+        const int capa = (form & PCL_CELLRP_FORM_CAPA) ? 1 : 0;
+        const int max_x = pcl::exact::sharp_tile_max_planes(1, naux), max_y = pcl::exact::sharp_tile_max_planes(2, naux);
+        if (meqn + capa > max_x)
+            return fail(PCL_EINVAL, "pcl_cellrp_compile_sharp: meqn + capa = " + std::to_string(meqn + capa) + ", the tile of the SharpClaw x pass "
+                                    "holds at most " + std::to_string(max_x) + " planes (q components and the capacity function) in the 64 KB "
+                                    "a workgroup may declare");
+        if (ndim == 2 && meqn + capa + naux > max_y)
+            return fail(PCL_EINVAL, "pcl_cellrp_compile_sharp: meqn + capa + naux = " + std::to_string(meqn + capa + naux) + ", the tile of the "
+                                    "SharpClaw y pass holds at most " + std::to_string(max_y) + " planes (q components, the capacity function and "
+                                    "listed aux components) in the 64 KB a workgroup may declare");
+    }
+    const int max_planes = sharp.on() ? 1 << 30 : pcl::exact::sweep_tile_max_planes();      // (SharpClaw: the rule above)
     if (naux > 0 && meqn + naux > max_planes)
         return fail(PCL_EINVAL, "pcl_cellrp_compile_aux: meqn + naux = " + std::to_string(meqn + naux) + ", the sweep's tile holds at most " +
                                     std::to_string(max_planes) + " planes (q components and listed aux components) in a workgroup's 64 KB");
@@ -1808,7 +1865,7 @@ int pcl_cellrp_compile_form(const char *body, const char *transverse, const char
     }
     CellfnCache &c = cellfn_cache();
     std::lock_guard<std::mutex> lock(c.mu);
-    const std::string key = cellrp_key(body, preamble, meqn, mwaves, ndim, math, aux_index, naux, transverse, form);
+    const std::string key = cellrp_key(body, preamble, meqn, mwaves, ndim, math, aux_index, naux, transverse, form, sharp);
     auto it = c.rp_by_key.find(key);
     pcl_cellrp *r = nullptr;
     if (it != c.rp_by_key.end()) {
@@ -1818,7 +1875,7 @@ int pcl_cellrp_compile_form(const char *body, const char *transverse, const char
         std::vector<char> code;
         std::string err, sym[4];
         const int slices = transverse ? pcl::unsplit_user_slices(meqn) : 0;
-        if (cellrp_build(body, transverse, preamble, meqn, mwaves, ndim, math, aux_index, naux, slices, form, code, sym, err))
+        if (cellrp_build(body, transverse, preamble, meqn, mwaves, ndim, math, aux_index, naux, slices, form, sharp, code, sym, err))
             return fail(PCL_EINVAL, err);
         r = new pcl_cellrp();
         r->id = c.next_id++;
@@ -1832,6 +1889,8 @@ int pcl_cellrp_compile_form(const char *body, const char *transverse, const char
         r->slices = slices;
         r->sym_u[0] = sym[2]; r->sym_u[1] = sym[3];
         r->form = form;
+        r->sharp = sharp.on();
+        r->lim_type = sharp.lim_type; r->weno_order = sharp.weno_order; r->char_decomp = sharp.char_decomp;
         c.rp_by_key[key] = r;
         c.rp_live[r] = r->id;
         c.compiles++;
@@ -1897,6 +1956,15 @@ int pcl_cellrp_form(const pcl_cellrp *r, int *form) {
     return PCL_OK;
 }
 
+int pcl_cellrp_sharp(const pcl_cellrp *r, int *lim_type, int *weno_order, int *char_decomp) {
+    if (!lim_type || !weno_order || !char_decomp) return fail(PCL_EINVAL, "null argument");
+    CellfnCache &c = cellfn_cache();
+    std::lock_guard<std::mutex> lock(c.mu);
+    if (!r || !c.rp_live.count(r)) return fail(PCL_EINVAL, "not a live Riemann solver handle (pcl_cellrp_compile)");
+    *lim_type = r->lim_type; *weno_order = r->weno_order; *char_decomp = r->char_decomp;      // zeros: a classic handle
+    return PCL_OK;
+}
+
 // what attaching r to a solver of this configuration asks of the handle; host-only (the cache's lock is held)
 static int cellrp_fits_locked(CellfnCache &c, const pcl_cellrp *r, const pcl_config &cfg, const char *who) {
     if (int rc = cellrp_check_locked(c, r, cfg.meqn, cfg.mwaves, cfg.ndim, cfg.math)) return rc;
@@ -1906,7 +1974,27 @@ static int cellrp_fits_locked(CellfnCache &c, const pcl_cellrp *r, const pcl_con
     if (top >= cfg.maux)
         return fail(PCL_EINVAL, std::string(who) + ": the Riemann solver reads aux component " + std::to_string(top) +
                                     " (0-based), the solver was created with maux = " + std::to_string(cfg.maux));
-    if (cfg.ndim == 2 && cfg.method[2] >= 0 && !r->trans)
+    // a handle holds the classic kernels or the SharpClaw kernels of one (lim_type, weno_order, char_decomp), never both
+    const bool sharp_cfg = cfg.kind == PCL_KIND_SHARPCLAW;
+    if (sharp_cfg != r->sharp)
+        return fail(PCL_EINVAL, std::string(who) + (r->sharp ? ": PCL_RP_CELL: the handle was compiled for SharpClaw (pcl_cellrp_compile_sharp) "
+                                                               "and the configuration is a classic solver (cfg.kind = 0)"
+                                                             : ": PCL_RP_CELL: a SharpClaw solver (cfg.kind = 1) needs a handle compiled "
+                                                               "for SharpClaw (pcl_cellrp_compile_sharp); this one holds the classic sweeps"));
+    if (sharp_cfg) {
+        const auto s = [](int v) { return std::to_string(v); };
+        if (cfg.lim_type != r->lim_type)
+            return fail(PCL_EINVAL, std::string(who) + ": PCL_RP_CELL: the handle was compiled for lim_type " + s(r->lim_type) +
+                                        " and cfg.lim_type is " + s(cfg.lim_type));
+        if (cfg.mbc != (r->weno_order + 1) / 2)
+            return fail(PCL_EINVAL, std::string(who) + ": PCL_RP_CELL: the handle was compiled for weno_order " + s(r->weno_order) +
+                                        " (mbc " + s((r->weno_order + 1) / 2) + ") and cfg.mbc is " + s(cfg.mbc) +
+                                        " (weno_order " + s(2 * cfg.mbc - 1) + ")");
+        if (cfg.method[4] != r->char_decomp)
+            return fail(PCL_EINVAL, std::string(who) + ": PCL_RP_CELL: the handle was compiled for char_decomp " + s(r->char_decomp) +
+                                        " and cfg.method[4] (char_decomp) is " + s(cfg.method[4]));
+    }
+    if (!sharp_cfg && cfg.ndim == 2 && cfg.method[2] >= 0 && !r->trans)
         return fail(PCL_EINVAL, std::string(who) + ": PCL_RP_CELL: the unsplit step (method[2] >= 0) needs a handle compiled with a "
                                     "transverse body (pcl_cellrp_compile_t)");
     // the kernels in the handle were instantiated for one form (FWAVE, CAPA): the configuration must say the same
@@ -1929,7 +2017,7 @@ int pcl_cellrp_attach(pcl_solver *s, pcl_cellrp *r) {
     if (!s) return fail(PCL_EINVAL, "null argument");
     if (s->cfg.rp != PCL_RP_CELL) return fail(PCL_EINVAL, "pcl_cellrp_attach: the solver was not created with cfg.rp = PCL_RP_CELL");
     long id;
-    int naux, slices, form;
+    int naux, slices, form, sharp[3] = {0, 0, 0};
     const void *code;
     std::string sym[2], sym_u[2];
     {   // (the entry is never freed: code and names stay valid outside the lock)
@@ -1940,6 +2028,7 @@ int pcl_cellrp_attach(pcl_solver *s, pcl_cellrp *r) {
         id = r->id; naux = r->naux; code = r->code.data(); sym[0] = r->sym[0]; sym[1] = r->sym[1];
         slices = r->trans ? r->slices : 0; sym_u[0] = r->sym_u[0]; sym_u[1] = r->sym_u[1];
         form = r->form;
+        if (r->sharp) { sharp[0] = r->lim_type; sharp[1] = (r->weno_order + 1) / 2; sharp[2] = r->char_decomp; }
     }
     if (s->cellrp.id == id) return PCL_OK;
     HIP_TRY(hipSetDevice(s->cfg.device));
@@ -1965,6 +2054,7 @@ int pcl_cellrp_attach(pcl_solver *s, pcl_cellrp *r) {
     m.naux = naux;
     m.slices = slices;
     m.form = form;
+    m.sharp_lim = sharp[0]; m.sharp_mbc = sharp[1]; m.sharp_cd = sharp[2];
     s->cellrp = m;
     return PCL_OK;
 }
@@ -2179,6 +2269,9 @@ int pcl_sharp_fuse_dq_src(pcl_solver *s, int src_id, const double *params, int n
     if (!s) return fail(PCL_EINVAL, "null argument");
     if (s->cfg.kind != PCL_KIND_SHARPCLAW) return fail(PCL_EINVAL, "pcl_sharp_fuse_dq_src: not a SharpClaw solver");
     if (src_id == 0) { s->fused_src = 0; return PCL_OK; }
+    if (s->cfg.rp == PCL_RP_CELL)
+        return fail(PCL_EINVAL, "pcl_sharp_fuse_dq_src: no fused dq source with a user-written Riemann solver (PCL_RP_CELL): the "
+                                "source runs as its own pass");
     if (src_id != PCL_SRC_EULER_RADIAL) return fail(PCL_EINVAL, "pcl_sharp_fuse_dq_src: only the Euler radial source can be fused");
     if (s->cfg.ndim != 2 || s->cfg.rp != PCL_RP_EULER5_2D || s->cfg.maux < 1 || s->cfg.method[5] != 0 ||
         s->cfg.mbc != 3 || s->cfg.lim_type != 2)
@@ -2215,6 +2308,7 @@ static int sharp_pass(pcl_solver *s, int ids, double dt, int rk_op, const double
     l.ndim = s->cfg.ndim; l.rp = s->cfg.rp; l.ids = ids; l.fwave = s->cfg.fwave;
     l.lim_type = s->cfg.lim_type; l.stream = stream;
     l.char_decomp = s->cfg.method[4];          // SharpClaw: clawparams.char_decomp travels in method(5) (unused by it)
+    if (l.rp == PCL_RP_CELL) user_launch_fields(l, s, ids);
     LaunchTimer timer(s, timing_on(s), ids - 1, sub != 2, stream);
     int rc = PCL_BY_MATH(s->cfg.math, launch_sharp(l, err));
     timer.end();

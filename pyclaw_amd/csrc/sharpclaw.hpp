@@ -23,7 +23,9 @@ namespace PCL_NS {
 constexpr int T_ACROSS_S = 16;
 // strips per tile: 16 (a 128-byte row segment per tile row) except in the y pass of solvers that stage many aux planes
 // through the tile (the sphere solver: 4 + 1 + 9 planes): 8 columns = 57 KB instead of 114 KB, two workgroups per CU
-template <class RP, int IXY> constexpr int sharp_tile_across() { return (IXY == 2 && RP::NAUX >= 6) ? 8 : T_ACROSS_S; }
+// (by the number of staged aux components, for the launcher of a solver compiled at run time: kernels.hip)
+constexpr int sharp_tile_across_n(int ixy, int naux) { return (ixy == 2 && naux >= 6) ? 8 : T_ACROSS_S; }
+template <class RP, int IXY> constexpr int sharp_tile_across() { return sharp_tile_across_n(IXY, RP::NAUX); }
 // halo of a strip = mbc = (weno_order+1)/2 (sharpclaw.py:479): 3 for WENO5 / tvd2, up to 9 for WENO17
 constexpr int sstrip(int halo) { return WAVE - 2 * halo; }   // cells updated per strip: 58 ... 46
 

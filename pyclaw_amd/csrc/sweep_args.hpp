@@ -191,6 +191,9 @@ struct SweepLaunch {
     // launch_unsplit: user_fn is unsplit_x_kernel / unsplit_y_kernel<UserRp, user_fwave, user_slices, user_capa> of that module (null:
     // nothing attached), user_slices the U its handle was compiled with (unsplit_user_slices)
     int user_slices = 0;
+    // launch_sharp: user_fn is sharp_kernel<UserRp, ids, user_capa, user_sharp_lim, user_sharp_k> or, with user_sharp_cd = 1,
+    // sharp1w_kernel<UserRp, user_sharp_lim, user_capa> of that module; user_sharp_k = 0: the module holds classic kernels
+    int user_sharp_lim = 0, user_sharp_k = 0, user_sharp_cd = 0;
     // one-kernel step only (classic_fused.hpp, quiet tiles): this launch's per-tile words and per-wavefront Courant
     // maxima (tq_out null: no bookkeeping).  A list launch (tq_list set) computes the tq_next->na + nq tiles a
     // hand-over+list kernel listed behind the previous launch and publishes the Courant number of those it skips.
@@ -247,6 +250,7 @@ struct InteriorBox { bool any = false; int box[4] = {0, 0, 0, 0}, ntiles[2] = {0
 namespace exact {
 const RpFacts *rp_facts(int rp);    // null: no built-in solver has this id (the same in every mode)
 int sweep_tile_max_planes();        // q + aux planes a sweep_kernel tile may hold (TileShape<1/2>::PLANE against 64 KB)
+int sharp_tile_max_planes(int ixy, int naux);   // planes a sharp_kernel tile of pass ixy may hold for a solver with naux aux components
 int launch_sweep(const SweepLaunch &l, std::string &err);
 int launch_step2ds(const SweepLaunch &l, std::string &err);   // whole dim-split 2-D step in one kernel (classic_fused.hpp)
 // x-pass tiles [tb_lo,tb_hi) x [ta_lo,ta_hi) that read no ghost cell; false if there are none

@@ -77,7 +77,8 @@ class CellRiemann(RiemannSolver):
     """A user-written NORMAL Riemann solver (Clawpack's rp1 / rpn2, one interface at a time) as the text of a C++
     function body: ``solver.rp = CellRiemann(body, meqn, mwaves, ndim, params)`` on ``ClawSolver1D`` / ``ClawSolver2D``.
     It is compiled at ``setup()`` into the library's own sweep kernel and runs in the classic 1-D step and in the two
-    passes of the dimension-split 2-D step with the tiles, limiter and Courant reduction of the built-in solvers.
+    passes of the dimension-split 2-D step with the tiles, limiter and Courant reduction of the built-in solvers; with
+    ``sharpclaw=True`` (below) into the SharpClaw kernels instead.
 
     The body sees ``ql[MEQN]``, ``qr[MEQN]`` (the cells left and right of the interface), ``p[8]`` (``params``;
     reassigning them between steps compiles nothing), the compile-time constant ``ixy`` (1 = x, always in 1-D; 2 = y)
@@ -123,33 +124,59 @@ class CellRiemann(RiemannSolver):
     of the compile key and readable as attributes; the solver and the state must say the same as the ``CellRiemann``
     (``setup()`` refuses each mismatch with its reason).
 
+    ``sharpclaw=True`` compiles the solver for ``SharpClawSolver1D`` / ``SharpClawSolver2D`` and for nothing else (a
+    classic solver refuses it; together with ``transverse`` it is a ``ValueError``).  ``setup()`` compiles the library's
+    SharpClaw kernels around the body for the solver's own ``lim_type``, ``weno_order`` and ``char_decomp``, which are
+    part of the compile key: ``lim_type`` 1, 2, 3 at ``weno_order`` 5 and ``weno_order`` 7..17 with ``lim_type`` 2 for
+    any system, the built-in solvers that lack those orders included once they are restated as bodies; ``char_decomp =
+    1`` as for the built-in solvers (1-D, ``lim_type`` 1 or 2, order 5, wave form).  The body, ``preamble``, ``params``,
+    ``aux``, ``fwave`` and ``capa`` mean what they mean above (an f-wave body assigns ``fwave``; SharpClaw reads ``s``,
+    ``amdq`` and ``apdq`` alone).  The "equal q, zero waves" contract is not relied on here: SharpClaw solves every
+    interface and the problem inside every cell, both edge states of a cell with the cell's own aux values.  Euler,
+    SSP33 and SSP104 run with the fused stage calls of the built-in solvers.  The tile holds ``meqn + capa`` planes in
+    the x pass and ``meqn + capa + len(aux)`` in the 2-D y pass, at most ``MAX_PLANES`` each (the y planes are half as
+    large from six aux components on, so the x pass then sets the limit).  A ``dq_src`` -- a ``CellDqSource`` or a
+    Python callable -- runs as its own pass: nothing is fused into the stage.
+
     Not served: a transverse body that needs both cells and aux, a conservation fix in the unsplit step (the sphere
-    solver's ``qcor``), SharpClaw, 3-D, more than one block.  The dimension-split 2-D step always runs as two passes,
-    never as the one-kernel step, the unsplit y phase always in its tile form (the marching y kernel stays with the
-    built-in solvers)."""
+    solver's ``qcor``), 3-D, more than one block; under SharpClaw ``char_decomp`` 2 / 3, ``tfluct_solver`` and a fused
+    dq source.  The dimension-split 2-D step always runs as two passes, never as the one-kernel step, the unsplit y
+    phase always in its tile form (the marching y kernel stays with the built-in solvers)."""
 
     MAX_PARAMS = 8
     MAX_PLANES = 8
 
     def __init__(self, body, meqn, mwaves, ndim, params=(), preamble="", name="user", aux=(), transverse=None, fwave=False,
-                 capa=False):
+                 capa=False, sharpclaw=False):
         RiemannSolver.__init__(self, name, PCL_RP_CELL, int(ndim), int(meqn), int(mwaves), (),
                                has_transverse=transverse is not None)
         if not 1 <= self.meqn <= 8 or not 1 <= self.mwaves <= 8:
             raise ValueError("CellRiemann: 1 <= meqn <= 8 and 1 <= mwaves <= 8, got meqn=%d mwaves=%d" % (self.meqn, self.mwaves))
         if self.ndim not in (1, 2):
             raise ValueError("CellRiemann: ndim must be 1 or 2 (the classic 1-D and dimension-split 2-D sweeps), got %d" % self.ndim)
+        self.sharpclaw = bool(sharpclaw)
+        if self.sharpclaw and transverse is not None:
+            raise ValueError("CellRiemann: sharpclaw=True with a transverse body: SharpClaw has no transverse solve, and a "
+                             "solver compiled for it serves SharpClawSolver1D / SharpClawSolver2D alone")
         self.aux = tuple(int(k) for k in aux)
         if any(k < 0 for k in self.aux):
             raise ValueError("CellRiemann: aux lists 0-based components of state.aux, got a negative index in %r" % (self.aux,))
         if len(set(self.aux)) != len(self.aux):
             raise ValueError("CellRiemann: aux lists a component twice: %r" % (self.aux,))
-        if self.aux and self.meqn + len(self.aux) > self.MAX_PLANES:
-            raise ValueError("CellRiemann: meqn + len(aux) = %d, the sweep's tile holds at most %d planes (q components and "
-                             "listed aux components)" % (self.meqn + len(self.aux), self.MAX_PLANES))
         self.fwave = bool(fwave)
         self.capa = bool(capa)
-        if self.capa and self.meqn + 1 + len(self.aux) > self.MAX_PLANES:
+        if self.sharpclaw:
+            # the SharpClaw tiles (the library has the rule and refuses with its own figures): q and the capacity function in
+            # the x pass, the listed aux components too in the y pass, whose planes are half as large from six components on
+            planes = self.meqn + int(self.capa) + (len(self.aux) if self.ndim == 2 and len(self.aux) < 6 else 0)
+            if planes > self.MAX_PLANES:
+                raise ValueError("CellRiemann: meqn + capa + len(aux) = %d with sharpclaw=True, the SharpClaw tile holds at most "
+                                 "%d planes (q components, the capacity function and, in the 2-D y pass, listed aux components)"
+                                 % (planes, self.MAX_PLANES))
+        elif self.aux and self.meqn + len(self.aux) > self.MAX_PLANES:
+            raise ValueError("CellRiemann: meqn + len(aux) = %d, the sweep's tile holds at most %d planes (q components and "
+                             "listed aux components)" % (self.meqn + len(self.aux), self.MAX_PLANES))
+        if not self.sharpclaw and self.capa and self.meqn + 1 + len(self.aux) > self.MAX_PLANES:
             raise ValueError("CellRiemann: meqn + 1 + len(aux) = %d with capa=True, the sweep's tile holds at most %d planes "
                              "(q components, the capacity function and listed aux components)"
                              % (self.meqn + 1 + len(self.aux), self.MAX_PLANES))
@@ -177,20 +204,32 @@ class CellRiemann(RiemannSolver):
     def all_params(self, state):
         return [float(v) for v in self._params]
 
-    def compile(self, math='exact'):
+    def compile(self, math='exact', sharp=None):
         """Compile (no device needed; cached per process).  Raises with the compiler's log, whose line numbers are the
-        body's ("riemann:<n>"), the transverse body's ("transverse:<n>") or the preamble's ("preamble:<n>")."""
+        body's ("riemann:<n>"), the transverse body's ("transverse:<n>") or the preamble's ("preamble:<n>").
+        ``sharp=(lim_type, weno_order, char_decomp)``, for a solver written with ``sharpclaw=True`` and only for one:
+        the SharpClaw kernels of that one reconstruction; the three are part of the key."""
         import ctypes
         from . import _lib
         if math not in ('exact', 'fast', 'strict'):
             raise Exception("math must be 'exact', 'fast' or 'strict'")
+        if (sharp is not None) != self.sharpclaw:
+            raise ValueError("CellRiemann: compile(sharp=(lim_type, weno_order, char_decomp)) belongs to a solver written with "
+                             "sharpclaw=True, and such a solver is compiled in no other way")
+        sharp = None if sharp is None else tuple(int(v) for v in sharp)
         form = (1 if self.fwave else 0) | (2 if self.capa else 0)      # PCL_CELLRP_FORM_FWAVE, PCL_CELLRP_FORM_CAPA
-        key = (self.meqn, self.mwaves, self.ndim, math, self.body, self.preamble, self.aux, self.transverse, form)
+        key = (self.meqn, self.mwaves, self.ndim, math, self.body, self.preamble, self.aux, self.transverse, form, sharp)
         if self._rp is not None and self._key == key:
             return self
         rp, size = ctypes.c_void_p(), ctypes.c_long(0)
         mode = {'exact': 0, 'fast': 1, 'strict': 2}[math]
-        if form:
+        if sharp is not None:
+            _lib.check(_lib.lib().pcl_cellrp_compile_sharp(self.body.encode(), self.preamble.encode(), self.meqn, self.mwaves,
+                                                           self.ndim, mode,
+                                                           (ctypes.c_int * len(self.aux))(*self.aux) if self.aux else None,
+                                                           len(self.aux), form, sharp[0], sharp[1], sharp[2],
+                                                           ctypes.byref(rp), ctypes.byref(size)))
+        elif form:
             _lib.check(_lib.lib().pcl_cellrp_compile_form(self.body.encode(),
                                                           None if self.transverse is None else self.transverse.encode(),
                                                           self.preamble.encode(), self.meqn, self.mwaves, self.ndim, mode,

@@ -16,6 +16,10 @@ the one the reference's golden ``test/ac_sc_solution`` was produced with) and ``
 ``char_decomp=0``, or ``1`` (wave-based reconstruction) in 1-D with ``lim_type`` 1 or 2; ``tfluct_solver=False``.
 ``solver.fwave`` is ``True`` for ``rp_psystem_fwave_2d`` and only for it (``rp_elasticity_fwave_1d`` is a classic-only
 solver).
+
+``solver.rp`` may be a user-written ``riemann.CellRiemann(..., sharpclaw=True)``: ``setup()`` compiles the SharpClaw kernels
+around its body for this solver's ``lim_type``, ``weno_order`` and ``char_decomp`` (every order 5 .. 17 for any system), on
+one block, with a ``dq_src`` as its own pass.
 """
 import ctypes
 
@@ -146,6 +150,8 @@ class SharpClawSolver(Solver):
         self._default_attr_values['dq_src'] = None
         self._default_attr_values['math'] = 'exact'
         self.rp = None
+        self._user_rp = None         # the riemann.CellRiemann of this setup() and the params the library last got
+        self._user_rp_sent = None
         super(SharpClawSolver, self).__init__(data)
 
     # ------------------------------------------------------------------ RK step
@@ -163,6 +169,8 @@ class SharpClawSolver(Solver):
             self._push(state)
         else:
             self.start_step(self, solution)
+        if self._user_rp is not None:
+            self._send_user_rp_params()
         t, dt = state.t, self.dt
         # st(reg, t, op, D, A, B, ...): deltaq = dq(reg, t) followed by the combination that consumes it.
         # Without a Python dq_src (or with a DeviceDqSource the last pass evaluates) both run as ONE fused device stage
@@ -320,13 +328,17 @@ class SharpClawSolver(Solver):
         if self.rp is None:
             raise Exception("solver.rp is not set: choose a Riemann solver from pyclaw_amd.riemann")
         rp = riemann.get(self.rp)
-        if isinstance(rp, riemann.CellRiemann):
-            raise NotImplementedError("CellRiemann: the SharpClaw solvers are not served: a user-written Riemann solver is "
-                                      "compiled into the classic sweep kernel only (ClawSolver1D / ClawSolver2D)")
+        user_rp = isinstance(rp, riemann.CellRiemann)
+        if user_rp:
+            self._check_user_rp(rp, state)
         self._check_cell_functions(state)
         if rp.ndim != self.ndim or rp.mwaves != self.mwaves or rp.meqn != state.meqn:
             raise Exception("Riemann solver %s does not match ndim/mwaves/meqn of the problem" % rp.name)
         params = rp.all_params(state)
+        if user_rp:
+            # the SharpClaw kernels of this one reconstruction around the body; raises with the compiler's log before any
+            # device work
+            rp.compile(self.math, sharp=(self.lim_type, self.weno_order, self.char_decomp))
 
         self._release()
         cfg = _lib.Config()
@@ -356,8 +368,13 @@ class SharpClawSolver(Solver):
         cfg.kind = 1
         cfg.lim_type = int(self.lim_type)
         h = ctypes.c_void_p()
-        _lib.check(_lib.lib().pcl_create(ctypes.byref(cfg), ctypes.byref(h)))
+        if user_rp:
+            # the library checks the configuration against what the handle was compiled for and attaches it
+            _lib.check(_lib.lib().pcl_create_cellrp(ctypes.byref(cfg), rp._rp, ctypes.byref(h)))
+        else:
+            _lib.check(_lib.lib().pcl_create(ctypes.byref(cfg), ctypes.byref(h)))
         self._h = h
+        self._user_rp, self._user_rp_sent = (rp, np.array(params)) if user_rp else (None, None)
         self._stage = _StageState(state)
         self._dq_src_fused = False
         if isinstance(self.dq_src, DeviceDqSource) and self.dq_src.fusable(self, state):
@@ -368,6 +385,44 @@ class SharpClawSolver(Solver):
         self._setup_halo(state)
         self._upload_aux(state)
         self._setup_cell_functions(state)
+
+    def _check_user_rp(self, rp, state):
+        """What a user-written Riemann solver (riemann.CellRiemann) asks of a SharpClaw solver, each refusal with its reason.
+        (lim_type, weno_order, char_decomp and tfluct_solver were checked above, as for a built-in solver.)"""
+        from . import parallel
+        if not rp.sharpclaw:
+            raise NotImplementedError("CellRiemann: the SharpClaw solvers are served by a solver written with sharpclaw=True "
+                                      "(compiled into the SharpClaw kernels); without it a user-written Riemann solver is "
+                                      "compiled into the classic sweep kernel only (ClawSolver1D / ClawSolver2D)")
+        if self.fwave and not rp.fwave:
+            raise NotImplementedError("CellRiemann: fwave = True is not served by this solver: its body returns waves; an "
+                                      "f-wave body is compiled with CellRiemann(..., fwave=True)")
+        if rp.fwave and not self.fwave:
+            raise ValueError("CellRiemann: the solver was written with fwave=True (its body assigns f-waves) and "
+                             "solver.fwave is False: set solver.fwave = True")
+        if state.mcapa >= 0 and not rp.capa:
+            raise NotImplementedError("CellRiemann: state.mcapa (a capacity function) is not served by this solver: it is "
+                                      "compiled without one (CellRiemann(..., capa=True) compiles it with one)")
+        if rp.capa and state.mcapa < 0:
+            raise ValueError("CellRiemann: the solver was written with capa=True (stages with a capacity function) and "
+                             "state.mcapa is not set: name the aux component in state.mcapa")
+        if state.decomp is not None and parallel.world_size() > 1:
+            raise NotImplementedError("CellRiemann: more than one rank is not served: a user-written solver runs on one "
+                                      "block (the decomposed stage's plans know the built-in solvers only)")
+        if rp.aux:
+            # (an index past maux would be a read outside the aux allocation: the library refuses it again at attach)
+            if state.aux is None:
+                raise ValueError("CellRiemann: the body reads aux components %r and state.aux is None" % (rp.aux,))
+            if max(rp.aux) >= state.maux:
+                raise ValueError("CellRiemann: the body reads aux component %d (0-based) and state.maux = %d"
+                                 % (max(rp.aux), state.maux))
+
+    def _send_user_rp_params(self):
+        """CellRiemann.params reassigned since the last step: they travel by value with the next stages, no compile."""
+        p = self._user_rp.params
+        if len(p) != len(self._user_rp_sent) or not np.array_equal(p, self._user_rp_sent):
+            _lib.check(_lib.lib().pcl_cellrp_params(self._h, _lib.d(p) if len(p) else None, len(p)))
+            self._user_rp_sent = p.copy()
 
     def _custom_bc(self, state, dim, idim, side, fn):
         # Python custom BCs on a stage: same strip protocol as the base class, `state` carries stage time

@@ -32,7 +32,12 @@ fwave=True (PSYSTEM_FWAVE_2D_RP, aux=(0, 1, 2, 3)), and the built-in solver on i
 --capa measures acoustics on a grid with a capacity function (problems.capa_acoustics2D) two ways: "two_pass", the
 built-in solver held to two passes, and "user", ACOUSTICS_2D_RP in a CellRiemann compiled with capa=True.
 
-  python tools/cellrp_bench.py [--aux] [--unsplit] [--fwave | --capa] [--n 4096] [--steps 20] [--warmup 3] [--reps 7] [--out FILE]
+--sharpclaw measures the SharpClaw stages two ways: ms per SSP104 step (ten fused stages, WENO5) of 2-D acoustics with
+"builtin", rp_acoustics_2d, and "user", ACOUSTICS_2D_RP in a CellRiemann compiled with sharpclaw=True.  Both run
+sharp_kernel over the same tiles.  The children also time every distinct run-time compile they make: the user solver's
+SharpClaw kernels ("compile_s") and, for comparison, the same body's classic sweeps ("compile_classic_s").
+
+  python tools/cellrp_bench.py [--aux] [--unsplit] [--fwave | --capa | --sharpclaw] [--n 4096] [--steps 20] [--warmup 3] [--reps 7] [--out FILE]
 """
 import argparse
 import ctypes
@@ -59,7 +64,10 @@ def child(args):
     L = _lib.lib()
     if L.pcl_device_count() < 1:
         raise SystemExit("cellrp_bench: no HIP device (nothing here can be measured without one)")
-    if args.fwave:
+    if args.sharpclaw:
+        claw = problems.acoustics2D(pyclaw, mx=args.n, my=args.n, run=False, math=args.math, solver_type='sharpclaw',
+                                    time_integrator='SSP104', user_rp=args.child == "user")
+    elif args.fwave:
         from apps import psystem
         claw = psystem.psystem2D(pyclaw, mx=args.n, my=args.n, solver_type='classic', run=False, math=args.math,
                                  user_rp=args.child == "user")
@@ -76,7 +84,17 @@ def child(args):
     solver, solution = claw.solver, claw.solution
     state = solution.state
     res = {"variant": args.child}
-    if args.child == "user":
+    if args.child == "user" and args.sharpclaw:
+        rp = solver.rp
+        sharp = (solver.lim_type, solver.weno_order, solver.char_decomp)
+        t0 = time.perf_counter()
+        rp.compile(args.math, sharp=sharp)
+        res["compile_s"] = time.perf_counter() - t0
+        classic = pyclaw.CellRiemann(rp.body, rp.meqn, rp.mwaves, 2)       # the same body's classic sweeps
+        t0 = time.perf_counter()
+        classic.compile(args.math)
+        res["compile_classic_s"] = time.perf_counter() - t0
+    elif args.child == "user":
         if args.unsplit:        # the same normal body without the transverse text, for the compile time alone
             rp = solver.rp
             plain = pyclaw.CellRiemann(rp.body, rp.meqn, rp.mwaves, 2, aux=rp.aux)
@@ -91,7 +109,9 @@ def child(args):
         res["compile_s"] = time.perf_counter() - t0
     solver.setup(solution)
     solver.dt_variable = False
-    if args.fwave or args.capa:
+    # one step: the classic hyperbolic step, or the SSP104 step of its ten stages
+    one_step = solver.step if args.sharpclaw else solver.step_hyperbolic
+    if args.fwave or args.capa or args.sharpclaw:
         solver.dt = solver.dt_initial       # the app's own first step: within its cfl_desired on either state
     else:
         solver.dt = 0.45 * min(state.grid.d) / (float(state.aux[1].max()) if args.aux else state.aux_global['cc'])
@@ -103,11 +123,11 @@ def child(args):
         state.q[...] = q0
         solver.begin_resident(solution)
         for _ in range(args.warmup):
-            solver.step_hyperbolic(solution)
+            one_step(solution)
         _lib.check(L.pcl_sync(solver._h))
         _lib.check(L.pcl_timer_start(solver._h))
         for _ in range(args.steps):
-            solver.step_hyperbolic(solution)
+            one_step(solution)
         _lib.check(L.pcl_timer_stop(solver._h, ctypes.byref(ms)))
         res[name + "_ms"] = ms.value / args.steps
         res[name + "_cfl"] = solver.cfl.get_cached_max()
@@ -130,16 +150,20 @@ def main():
     ap.add_argument("--unsplit", action="store_true", help="the unsplit step: the built-in solver against CellRiemann(transverse=...)")
     ap.add_argument("--fwave", action="store_true", help="the p-system: psystem_fwave_2d against CellRiemann(fwave=True)")
     ap.add_argument("--capa", action="store_true", help="acoustics with a capacity function: the built-in two passes against CellRiemann(capa=True)")
+    ap.add_argument("--sharpclaw", action="store_true", help="the SSP104 step of SharpClaw: rp_acoustics_2d against CellRiemann(sharpclaw=True)")
     ap.add_argument("--child", default=None, choices=VARIANTS + VARIANTS_UNSPLIT)
     args = ap.parse_args()
     if (args.fwave or args.capa) and (args.aux or args.unsplit or (args.fwave and args.capa)):
         raise SystemExit("cellrp_bench: --fwave and --capa are measurements of their own (not with --aux, --unsplit or each other)")
+    if args.sharpclaw and (args.aux or args.unsplit or args.fwave or args.capa):
+        raise SystemExit("cellrp_bench: --sharpclaw is a measurement of its own")
     if args.child:
         return child(args)
 
-    variants = VARIANTS_UNSPLIT if args.unsplit else VARIANTS_CAPA if args.capa else VARIANTS
+    # (--sharpclaw: two variants compared like the unsplit pair)
+    variants = VARIANTS_UNSPLIT if args.unsplit or args.sharpclaw else VARIANTS_CAPA if args.capa else VARIANTS
     mode = (["--aux"] if args.aux else []) + (["--unsplit"] if args.unsplit else []) + (["--fwave"] if args.fwave else []) + \
-           (["--capa"] if args.capa else [])
+           (["--capa"] if args.capa else []) + (["--sharpclaw"] if args.sharpclaw else [])
     runs = {v: [] for v in variants}
     for _ in range(args.reps):
         for v in variants:
@@ -164,12 +188,15 @@ def main():
            "states": {}}
     if args.unsplit:
         res["compile_plain_s"] = spread([r["compile_plain_s"] for r in runs["user"]])
+    if args.sharpclaw:
+        res["compile_classic_s"] = spread([r["compile_classic_s"] for r in runs["user"]])
+        res["what"] = "ms per SSP104 step (ten fused stages, WENO5, lim_type 2)"
     for name in ("pulse", "dense"):
         st = {v + "_ms": spread([r[name + "_ms"] for r in runs[v]]) for v in variants}
         sums = set(r[name + "_sum"] for v in variants for r in runs[v])
         cfls = set(r[name + "_cfl"] for v in variants for r in runs[v])
         st["same_result_in_every_run"] = len(sums) == 1 and len(cfls) == 1
-        if args.unsplit:
+        if args.unsplit or args.sharpclaw:
             a, b = (st[v + "_ms"] for v in variants)
             st["user_over_builtin"] = b["median"] / a["median"]
             st["user_and_builtin_spreads_overlap"] = not (b["min"] > a["max"] or a["min"] > b["max"])
