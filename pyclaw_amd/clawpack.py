@@ -187,7 +187,7 @@ class ClawSolver(Solver):
             cfl = self._cfl_out = ctypes.c_double(0.0)
             self._cfl_ptr = ctypes.cast(ctypes.byref(cfl), _lib.dp)
         if self._user_rp is not None:
-            self._send_user_rp_params()
+            self._user_rp.send_params(self)
         spec = self._device_bc_spec(state)
         if spec is not None:
             # every ghost fill runs on the device: BCs + step in one library call
@@ -302,8 +302,8 @@ class ClawSolver(Solver):
         self._decide_exchange_ahead(state)
 
     def _check_user_rp(self, state):
-        """What a user-written Riemann solver (riemann.CellRiemann) does not serve, each refused with its reason."""
-        from . import parallel
+        """What a user-written Riemann solver (riemann.CellRiemann) does not serve in a classic solver, each refused with its
+        reason; then what it asks of any solver (CellRiemann.check_solver)."""
         if self.rp.sharpclaw:
             raise NotImplementedError("CellRiemann: this solver was written with sharpclaw=True: it is compiled into the "
                                       "SharpClaw kernels and serves SharpClawSolver1D / SharpClawSolver2D alone; a classic "
@@ -315,37 +315,7 @@ class ClawSolver(Solver):
             raise NotImplementedError("CellRiemann: dim_split = False needs a transverse Riemann solver (rpt2); the body "
                                       "is the normal solver only, so the 2-D step is the dimension-split one "
                                       "(CellRiemann(..., transverse=...) gives it one)")
-        # the form is compiled into the kernels (CellRiemann(fwave=..., capa=...)): the solver and the state must say the same
-        if self.fwave and not self.rp.fwave:
-            raise NotImplementedError("CellRiemann: fwave = True is not served by this solver: its body returns waves; an "
-                                      "f-wave body is compiled with CellRiemann(..., fwave=True)")
-        if self.rp.fwave and not self.fwave:
-            raise ValueError("CellRiemann: the solver was written with fwave=True (its body assigns f-waves) and "
-                             "solver.fwave is False: set solver.fwave = True")
-        if state.mcapa >= 0 and not self.rp.capa:
-            raise NotImplementedError("CellRiemann: state.mcapa (a capacity function) is not served by this solver: it is "
-                                      "compiled into the sweep without one (CellRiemann(..., capa=True) compiles it with one)")
-        if self.rp.capa and state.mcapa < 0:
-            raise ValueError("CellRiemann: the solver was written with capa=True (sweeps with a capacity function) and "
-                             "state.mcapa is not set: name the aux component in state.mcapa")
-        if state.decomp is not None and parallel.world_size() > 1:
-            raise NotImplementedError("CellRiemann: more than one rank is not served: a user-written solver runs on one "
-                                      "block (the decomposed step's plans know the built-in solvers only)")
-        rp = self.rp
-        if rp.aux:
-            # (an index past maux would be a read outside the aux allocation: the library refuses it again at attach)
-            if state.aux is None:
-                raise ValueError("CellRiemann: the body reads aux components %r and state.aux is None" % (rp.aux,))
-            if max(rp.aux) >= state.maux:
-                raise ValueError("CellRiemann: the body reads aux component %d (0-based) and state.maux = %d"
-                                 % (max(rp.aux), state.maux))
-
-    def _send_user_rp_params(self):
-        """CellRiemann.params reassigned since the last step: they travel by value with the next sweeps, no compile."""
-        p = self._user_rp.params
-        if len(p) != len(self._user_rp_sent) or not np.array_equal(p, self._user_rp_sent):
-            _lib.check(_lib.lib().pcl_cellrp_params(self._h, _lib.d(p) if len(p) else None, len(p)))
-            self._user_rp_sent = p.copy()
+        self.rp.check_solver(self, state)
 
     def _decide_exchange_ahead(self, state):
         """Decomposed dimension-split 2-D runs: let the library send the new state's halo right behind the y pass

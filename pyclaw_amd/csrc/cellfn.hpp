@@ -425,34 +425,36 @@ static inline std::string cellfn_key(int kind, const char *body, const char *pre
     return k;
 }
 
-// hiprtc compile of head + preamble + body + tail; math: 0 exact, 1 fast, 2 strict.  0 = ok, else err holds the log
-static inline int cellfn_build(int kind, const char *body, const char *preamble, int meqn, int maux, int ndim, int math,
-                               int writes_aux, int reach, std::vector<char> &code, std::string &err) {
+// One hiprtc compile, for the cell functions here and the Riemann solvers of cellrp.hpp: what goes in ...
+struct HiprtcJob {
+    std::string src;
+    const char *name = "";                  // the program's name
+    int nheaders = 0;                       // named headers the text includes (none: a cell function)
+    const char **header_texts = nullptr, **header_names = nullptr;
+    std::vector<std::string> exprs;         // name expressions: template kernels whose lowered names are wanted
+    std::vector<std::string> opts;          // the compiler's options, in order
+    std::string what;                       // "<what> does not compile: ..." in front of the log
+    std::string dump;                       // PCL_CELLFN_DUMP keeps the code object as <dir>/<dump>_<*dump_seq>.co
+    int *dump_seq = nullptr;
+};
+// ... and what comes out: the code object and the lowered name of every expression.  0 = ok, else err holds the log
+static inline int hiprtc_compile(const HiprtcJob &job, std::vector<char> &code, std::vector<std::string> &lowered, std::string &err) {
     if (hiprtc_load(err)) return -1;
     HiprtcApi &a = hiprtc_api();
-    const char *kname = cellfn_kind_name(kind);
-    const bool bc = kind == 4;
-    std::string src = bc ? kCellbcHead : kCellfnHead;
-    src += "#line 1 \"preamble\"\n";
-    src += preamble;
-    src += "\n#line 1 \"pcl_cellfn_wrapper\"\n";
-    src += bc ? kCellbcOpen : kCellfnOpen;
-    src += std::string("#line 1 \"") + kname + "\"\n";
-    src += body;
-    src += "\n";
-    src += bc ? kCellbcTail : kCellfnTail;
     hiprtcProgram prog = nullptr;
-    hiprtcResult r = a.hiprtcCreateProgram(&prog, src.c_str(), "pcl_cellfn.hip", 0, nullptr, nullptr);
+    hiprtcResult r = a.hiprtcCreateProgram(&prog, job.src.c_str(), job.name, job.nheaders, job.header_texts, job.header_names);
     if (r != HIPRTC_SUCCESS) { err = std::string("hiprtcCreateProgram: ") + a.hiprtcGetErrorString(r); return -1; }
-    // exact / strict: what pclaw.hip itself is built with (no contraction; / and sqrt are IEEE either way)
-    const std::string d_meqn = "-DMEQN=" + std::to_string(meqn), d_maux = "-DMAUX=" + std::to_string(maux),
-                      d_ndim = "-DNDIM=" + std::to_string(ndim), d_kind = "-DKIND=" + std::to_string(kind),
-                      d_waux = "-DWRITES_AUX=" + std::to_string(writes_aux ? 1 : 0),
-                      d_reach = "-DREACH=" + std::to_string(reach);
-    std::vector<const char *> opts = {"--offload-arch=" PCL_ARCH, "-O3", "-std=c++17",
-                                      math == 1 ? "-ffp-contract=fast" : "-ffp-contract=off",
-                                      d_meqn.c_str(), d_maux.c_str(), d_ndim.c_str(), d_kind.c_str(), d_waux.c_str()};
-    if (reach > 0) opts.push_back(d_reach.c_str());       // reach = 0: the options it was always compiled with
+    const auto fails = [&](const std::string &msg) {
+        err = msg;
+        a.hiprtcDestroyProgram(&prog);
+        return -1;
+    };
+    for (const std::string &e : job.exprs) {
+        r = a.hiprtcAddNameExpression(prog, e.c_str());
+        if (r != HIPRTC_SUCCESS) return fails(std::string("hiprtcAddNameExpression: ") + a.hiprtcGetErrorString(r));
+    }
+    std::vector<const char *> opts;
+    for (const std::string &o : job.opts) opts.push_back(o.c_str());
     r = a.hiprtcCompileProgram(prog, (int)opts.size(), opts.data());
     if (r != HIPRTC_SUCCESS) {
         size_t n = 0;
@@ -462,9 +464,14 @@ static inline int cellfn_build(int kind, const char *body, const char *preamble,
             a.hiprtcGetProgramLog(prog, &log[0]);
             while (!log.empty() && (log.back() == '\0' || log.back() == '\n')) log.pop_back();
         }
-        err = std::string("cell function (") + kname + ") does not compile: " + a.hiprtcGetErrorString(r) + "\n" + log;
-        a.hiprtcDestroyProgram(&prog);
-        return -1;
+        return fails(job.what + " does not compile: " + a.hiprtcGetErrorString(r) + "\n" + log);
+    }
+    lowered.clear();
+    for (const std::string &e : job.exprs) {
+        const char *low = nullptr;
+        r = a.hiprtcGetLoweredName(prog, e.c_str(), &low);
+        if (r != HIPRTC_SUCCESS || !low) return fails(std::string("hiprtcGetLoweredName: ") + a.hiprtcGetErrorString(r));
+        lowered.push_back(low);
     }
     size_t size = 0;
     r = a.hiprtcGetCodeSize(prog, &size);
@@ -475,11 +482,39 @@ static inline int cellfn_build(int kind, const char *body, const char *preamble,
     a.hiprtcDestroyProgram(&prog);
     if (r != HIPRTC_SUCCESS || size == 0) { err = std::string("hiprtcGetCode: ") + a.hiprtcGetErrorString(r); return -1; }
     if (const char *dir = getenv("PCL_CELLFN_DUMP")) {     // diagnostics: keep the code object for a disassembler
-        static int seq = 0;
-        const std::string path = std::string(dir) + "/" + kname + "_" + std::to_string(seq++) + ".co";
+        const std::string path = std::string(dir) + "/" + job.dump + "_" + std::to_string((*job.dump_seq)++) + ".co";
         if (FILE *fp = fopen(path.c_str(), "wb")) { fwrite(code.data(), 1, code.size(), fp); fclose(fp); }
     }
     return 0;
+}
+
+// hiprtc compile of head + preamble + body + tail; math: 0 exact, 1 fast, 2 strict.  0 = ok, else err holds the log
+static inline int cellfn_build(int kind, const char *body, const char *preamble, int meqn, int maux, int ndim, int math,
+                               int writes_aux, int reach, std::vector<char> &code, std::string &err) {
+    const char *kname = cellfn_kind_name(kind);
+    const bool bc = kind == 4;
+    HiprtcJob job;
+    job.src = bc ? kCellbcHead : kCellfnHead;
+    job.src += "#line 1 \"preamble\"\n";
+    job.src += preamble;
+    job.src += "\n#line 1 \"pcl_cellfn_wrapper\"\n";
+    job.src += bc ? kCellbcOpen : kCellfnOpen;
+    job.src += std::string("#line 1 \"") + kname + "\"\n";
+    job.src += body;
+    job.src += "\n";
+    job.src += bc ? kCellbcTail : kCellfnTail;
+    job.name = "pcl_cellfn.hip";
+    // exact / strict: what pclaw.hip itself is built with (no contraction; / and sqrt are IEEE either way)
+    job.opts = {"--offload-arch=" PCL_ARCH, "-O3", "-std=c++17", math == 1 ? "-ffp-contract=fast" : "-ffp-contract=off",
+                "-DMEQN=" + std::to_string(meqn), "-DMAUX=" + std::to_string(maux), "-DNDIM=" + std::to_string(ndim),
+                "-DKIND=" + std::to_string(kind), "-DWRITES_AUX=" + std::to_string(writes_aux ? 1 : 0)};
+    if (reach > 0) job.opts.push_back("-DREACH=" + std::to_string(reach));      // reach = 0 passes no -DREACH: the text defaults it
+    job.what = std::string("cell function (") + kname + ")";
+    static int seq = 0;
+    job.dump = kname;
+    job.dump_seq = &seq;
+    std::vector<std::string> none;
+    return hiprtc_compile(job, code, none, err);
 }
 
 // the modules one solver handle has loaded, by function id; unloaded by pcl_destroy, never by a static destructor

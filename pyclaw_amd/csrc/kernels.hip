@@ -74,29 +74,30 @@ template <int IXY, bool DIM1> int sweep_grid(const SweepArgs &a, SweepGrid &g, s
 // What the module of a user-written Riemann solver was compiled for against what this launch asks: the kernel's FWAVE and
 // CAPA are template flags (cellrp.hpp: the handle's form), so a launch that says otherwise would run the wrong kernel.
 static int user_form_check(const SweepLaunch &l, std::string &err) {
-    if ((l.fwave != 0) != l.user_fwave) {
-        err = l.user_fwave ? "user-written Riemann solver: the attached solver was compiled for f-waves and the step is in wave form"
-                           : "user-written Riemann solver: the step asks for f-waves and the attached solver was compiled in wave form";
+    const CellrpSpec &u = l.user;
+    if ((l.fwave != 0) != u.fwave()) {
+        err = u.fwave() ? "user-written Riemann solver: the attached solver was compiled for f-waves and the step is in wave form"
+                        : "user-written Riemann solver: the step asks for f-waves and the attached solver was compiled in wave form";
         return PCL_EINVAL;
     }
-    if ((l.a.mcapa > 0) != l.user_capa) {
-        err = l.user_capa ? "user-written Riemann solver: the attached solver was compiled for a capacity function and the step has none"
-                          : "user-written Riemann solver: the step has a capacity function and the attached solver was compiled without one";
+    if ((l.a.mcapa > 0) != u.capa()) {
+        err = u.capa() ? "user-written Riemann solver: the attached solver was compiled for a capacity function and the step has none"
+                       : "user-written Riemann solver: the step has a capacity function and the attached solver was compiled without one";
         return PCL_EINVAL;
     }
-    if ((l.user_naux > 0 || l.user_capa) && !l.a.aux) {
-        err = l.user_naux > 0 ? "user-written Riemann solver: this solver reads aux arrays and there are none (pcl_put_aux)"
-                              : "user-written Riemann solver: the capacity function is a component of the aux arrays and there are none (pcl_put_aux)";
+    if ((u.naux > 0 || u.capa()) && !l.a.aux) {
+        err = u.naux > 0 ? "user-written Riemann solver: this solver reads aux arrays and there are none (pcl_put_aux)"
+                         : "user-written Riemann solver: the capacity function is a component of the aux arrays and there are none (pcl_put_aux)";
         return PCL_EINVAL;
     }
     return PCL_OK;
 }
 
-// A user-written Riemann solver (cellrp.hpp): l.user_fn is sweep_kernel<UserRp, IXY, user_capa, user_fwave, DIM1> of a
-// module compiled at run time from the text of classic.hpp, so the kernel's parameters are those of the launches below.
+// A user-written Riemann solver (cellrp.hpp): l.user_fn is sweep_kernel<UserRp, IXY, CAPA, FWAVE, DIM1> of a module compiled
+// at run time from the text of classic.hpp for the form of l.user, so the kernel's parameters are those of the launches below.
 template <int IXY, bool DIM1> int launch_user(const SweepLaunch &l, std::string &err) {
     if (!l.user_fn) { err = "user-written Riemann solver: no compiled solver is attached (pcl_cellrp_attach)"; return PCL_ESTATE; }
-    if (l.user_sharp_k != 0) { err = "user-written Riemann solver: the attached solver was compiled for SharpClaw and holds no classic sweep"; return PCL_EINVAL; }
+    if (l.user.sharp()) { err = "user-written Riemann solver: the attached solver was compiled for SharpClaw and holds no classic sweep"; return PCL_EINVAL; }
     if (l.a.src_id != 0) { err = "user-written Riemann solver: no fused source"; return PCL_EINVAL; }
     if (int rc = user_form_check(l, err)) return rc;
     SweepGrid g;
@@ -435,11 +436,12 @@ template <class RP> int launch_unsplit_t(const SweepLaunch &l, const double *qx,
     } else return launch_unsplit_u<RP, 16, 16>(l, qx, err);
 }
 // A user-written Riemann solver with a transverse body (cellrp.hpp): l.user_fn is unsplit_x_kernel<UserRp, FWAVE, U, CAPA>
-// or unsplit_y_kernel<UserRp, FWAVE, U, CAPA, false> of the module compiled at run time, FWAVE and CAPA = l.user_fwave and
-// l.user_capa (the handle's form), U = l.user_slices as the handle records it; the parameters and grids are those of launch_unsplit_u.  Always the tile form of the y phase: the marching
-// kernel stays with the built-in solvers.
+// or unsplit_y_kernel<UserRp, FWAVE, U, CAPA, false> of the module compiled at run time, FWAVE and CAPA the form of l.user,
+// U = l.user.slices(); the parameters and grids are those of launch_unsplit_u.  Always the tile form of the y phase: the
+// marching kernel stays with the built-in solvers.
 int launch_unsplit_user(const SweepLaunch &l, const double *qx, std::string &err) {
-    if (!l.user_fn || l.user_slices < 3) {
+    const int U = l.user.slices();
+    if (!l.user_fn || U < 3) {
         err = "user-written Riemann solver: no compiled solver with a transverse body is attached (pcl_cellrp_attach)";
         return PCL_ESTATE;
     }
@@ -449,7 +451,6 @@ int launch_unsplit_user(const SweepLaunch &l, const double *qx, std::string &err
     }
     if (int rc = user_form_check(l, err)) return rc;
     SweepArgs a = l.a;
-    const int U = l.user_slices;
     hipError_t e;
     if (l.ids == 1) {
         int nstrips = (a.mx + STRIP - 1) / STRIP;
@@ -586,10 +587,11 @@ template <class RP> int launch_sharp1w(const SweepLaunch &l, std::string &err) {
 namespace {
 // A user-written Riemann solver under SharpClaw (cellrp.hpp): l.user_fn is sharp_kernel<UserRp, ids, CAPA, LIM, K> or, with
 // char_decomp = 1, sharp1w_kernel<UserRp, LIM, CAPA> of the module compiled at run time -- one (LIM, K, char_decomp), the
-// handle's, with CAPA = l.user_capa -- so this launch must ask for exactly that; the parameters and grids are those of
+// ones of l.user, with CAPA its form's -- so this launch must ask for exactly that; the parameters and grids are those of
 // launch_sharp_k / launch_sharp1w.  Whole blocks, no fused dq source.
 int launch_sharp_user(const SweepLaunch &l, std::string &err) {
-    if (!l.user_fn || l.user_sharp_k == 0) {
+    const CellrpSpec &u = l.user;
+    if (!l.user_fn || !u.sharp()) {
         err = "user-written Riemann solver: no solver compiled for SharpClaw is attached (pcl_cellrp_compile_sharp, pcl_create_cellrp)";
         return PCL_ESTATE;
     }
@@ -598,18 +600,18 @@ int launch_sharp_user(const SweepLaunch &l, std::string &err) {
         return PCL_EINVAL;
     }
     if (int rc = user_form_check(l, err)) return rc;
-    if (l.lim_type != l.user_sharp_lim) {
-        err = "user-written Riemann solver: the attached solver was compiled for lim_type " + std::to_string(l.user_sharp_lim) +
+    if (l.lim_type != u.lim_type) {
+        err = "user-written Riemann solver: the attached solver was compiled for lim_type " + std::to_string(u.lim_type) +
               " and the stage asks for lim_type " + std::to_string(l.lim_type);
         return PCL_EINVAL;
     }
-    if (l.a.mbc != l.user_sharp_k) {
-        err = "user-written Riemann solver: the attached solver was compiled for weno_order " + std::to_string(2 * l.user_sharp_k - 1) +
-              " (mbc " + std::to_string(l.user_sharp_k) + ") and the stage runs with mbc " + std::to_string(l.a.mbc);
+    if (l.a.mbc != u.mbc()) {
+        err = "user-written Riemann solver: the attached solver was compiled for weno_order " + std::to_string(u.weno_order) +
+              " (mbc " + std::to_string(u.mbc()) + ") and the stage runs with mbc " + std::to_string(l.a.mbc);
         return PCL_EINVAL;
     }
-    if (l.char_decomp != l.user_sharp_cd) {
-        err = "user-written Riemann solver: the attached solver was compiled for char_decomp " + std::to_string(l.user_sharp_cd) +
+    if (l.char_decomp != u.char_decomp) {
+        err = "user-written Riemann solver: the attached solver was compiled for char_decomp " + std::to_string(u.char_decomp) +
               " and the stage asks for char_decomp " + std::to_string(l.char_decomp);
         return PCL_EINVAL;
     }
@@ -622,7 +624,7 @@ int launch_sharp_user(const SweepLaunch &l, std::string &err) {
         e = hipModuleLaunchKernel(l.user_fn, g.nblocks, 1, 1, 256, 1, 1, 0, l.stream, params, nullptr);
     } else {
         const int ixy = l.ndim == 1 ? 1 : l.ids;
-        SharpGrid g = sharp_grid(a, ixy, l.user_sharp_k, sharp_tile_across_n(ixy, l.user_naux));
+        SharpGrid g = sharp_grid(a, ixy, u.mbc(), sharp_tile_across_n(ixy, u.naux));
         void *params[] = {&a, &g.ntiles_across, &g.ntiles_along};
         e = hipModuleLaunchKernel(l.user_fn, g.nblocks, 1, 1, 256, 1, 1, 0, l.stream, params, nullptr);
     }

@@ -376,14 +376,9 @@ int frame_launch(pcl_solver *s, hipStream_t stream, double *q, double *dst, cons
 // sweep, or a SharpClaw kernel if the module was compiled for SharpClaw -- and what it was instantiated for
 void user_launch_fields(SweepLaunch &l, const pcl_solver *s, int ids) {
     l.user_fn = s->cellrp.fn[ids - 1];     // null: nothing attached, refused by the launcher
-    l.user_naux = s->cellrp.naux;
-    l.user_fwave = (s->cellrp.form & PCL_CELLRP_FORM_FWAVE) != 0;
-    l.user_capa = (s->cellrp.form & PCL_CELLRP_FORM_CAPA) != 0;
-    l.user_sharp_lim = s->cellrp.sharp_lim;
-    l.user_sharp_k = s->cellrp.sharp_mbc;
-    l.user_sharp_cd = s->cellrp.sharp_cd;
+    l.user = s->cellrp.spec;
     // nothing uploaded yet (listed components or the capacity function): refused by the launcher too
-    if ((l.user_naux > 0 || l.user_capa) && !s->aux_put) l.a.aux = nullptr;
+    if ((l.user.naux > 0 || l.user.capa()) && !s->aux_put) l.a.aux = nullptr;
 }
 
 SweepLaunch make_launch(const pcl_solver *s, const SweepArgs &a, int ndim, int ids, hipStream_t stream) {
@@ -560,10 +555,8 @@ static int unsplit_phase(pcl_solver *s, int ids, double dt, int sub, hipStream_t
     l.a.trans = s->cfg.method[2];
     l.a.dtd_t = dt / s->cfg.d[2 - ids];
     l.a.sub = sub;
-    if (l.rp == PCL_RP_CELL) {      // the unsplit kernels of the attached module (null: nothing attached, refused by the launcher)
-        l.user_fn = s->cellrp.fn_u[ids - 1];
-        l.user_slices = s->cellrp.slices;
-    }
+    // the unsplit kernels of the attached module (null: nothing attached or no transverse body, refused by the launcher)
+    if (l.rp == PCL_RP_CELL) l.user_fn = s->cellrp.fn[2 + ids - 1];
     LaunchTimer timer(s, timing_on(s), ids - 1, sub != 2, stream);
     int rc = PCL_BY_MATH(s->cfg.math, launch_unsplit(l, s->t1, err));
     timer.end();
@@ -722,7 +715,7 @@ int pcl_rp_info(int rp, int info[10]) {
 // pcl_create in two halves, so that pcl_create_cellrp can put what the handle must be able to do between them.
 // create_check: every test of the configuration, host-only.  cell_handle: the caller knows the handle of a PCL_RP_CELL
 // solver and checks against it what only the handle can serve (the unsplit step, f-waves, a capacity function:
-// cellrp_fits_locked); pcl_create cannot know it and refuses all three.
+// cellrp_fits); pcl_create cannot know it and refuses all three.
 static int create_check(const pcl_config *cfg, bool cell_handle) {
     if (getenv("PCL_TRACE_ABORT")) {   // diagnostics: C backtrace on abort()
         signal(SIGABRT, [](int) {
@@ -767,7 +760,7 @@ static int create_check(const pcl_config *cfg, bool cell_handle) {
     if (cfg->rp == PCL_RP_CELL) {
         // a user-written normal solver (cellrp.hpp): sizes from the config; it serves the classic 1-D step and the two
         // passes of the dimension-split 2-D step; in wave form without a capacity function unless a handle says otherwise
-        // (SharpClaw: with a handle compiled for it, pcl_cellrp_compile_sharp -- cellrp_fits_locked)
+        // (SharpClaw: with a handle compiled for it, pcl_cellrp_compile_sharp -- cellrp_fits)
         if (cfg->kind != PCL_KIND_CLASSIC && !cell_handle)
             return fail(PCL_EINVAL, "PCL_RP_CELL: a user-written Riemann solver runs in the classic sweeps only, not under SharpClaw");
         if (cfg->ndim == 3) return fail(PCL_EINVAL, "PCL_RP_CELL: a user-written Riemann solver is 1-D or 2-D (ndim == 3)");
@@ -1757,115 +1750,18 @@ int pcl_cellfn_check(const pcl_cellfn *f, int meqn, int maux, int ndim) {
 }
 
 // ---- user-written Riemann solvers (cellrp.hpp) ---------------------------------------------------------------------
-int pcl_cellrp_compile(const char *body, const char *preamble, int meqn, int mwaves, int ndim, int math, pcl_cellrp **out,
-                       long *code_size) {
-    return pcl_cellrp_compile_aux(body, preamble, meqn, mwaves, ndim, math, nullptr, 0, out, code_size);
-}
-
-// naux == 0 is pcl_cellrp_compile: the same program text, key and handle
-int pcl_cellrp_compile_aux(const char *body, const char *preamble, int meqn, int mwaves, int ndim, int math, const int *aux_index,
-                           int naux, pcl_cellrp **out, long *code_size) {
-    return pcl_cellrp_compile_t(body, nullptr, preamble, meqn, mwaves, ndim, math, aux_index, naux, out, code_size);
-}
-
-// transverse == null is pcl_cellrp_compile_aux: the same program text, key and handle.  With one (2-D only) the code
-// object also holds the two unsplit kernels, unsplit_user_slices(meqn) slices per workgroup (sweep_args.hpp)
-int pcl_cellrp_compile_t(const char *body, const char *transverse, const char *preamble, int meqn, int mwaves, int ndim, int math,
-                         const int *aux_index, int naux, pcl_cellrp **out, long *code_size) {
-    return pcl_cellrp_compile_form(body, transverse, preamble, meqn, mwaves, ndim, math, aux_index, naux, 0, out, code_size);
-}
-
-// form == 0 is pcl_cellrp_compile_t: the same program text, key and handle.  Any other form (PCL_CELLRP_FORM_* bits) is part
-// of the key, and the code object holds the kernels of that one form: sweep_kernel<UserRp, IXY, CAPA, FWAVE, DIM1> and,
-// with a transverse body, unsplit_x/y_kernel<UserRp, FWAVE, U, CAPA> (cellrp.hpp: cellrp_exprs)
-static int cellrp_compile_impl(const char *body, const char *transverse, const char *preamble, int meqn, int mwaves, int ndim,
-                               int math, const int *aux_index, int naux, int form, const pcl::CellrpSharp &sharp, pcl_cellrp **out,
-                               long *code_size);
-int pcl_cellrp_compile_form(const char *body, const char *transverse, const char *preamble, int meqn, int mwaves, int ndim,
-                            int math, const int *aux_index, int naux, int form, pcl_cellrp **out, long *code_size) {
-    return cellrp_compile_impl(body, transverse, preamble, meqn, mwaves, ndim, math, aux_index, naux, form, pcl::CellrpSharp(), out,
-                               code_size);
-}
-
-// The SharpClaw kernels around the body in place of the classic ones: sharp_kernel<UserRp, IXY, CAPA, lim_type, mbc> of the
-// one (lim_type, weno_order) asked for, or sharp1w_kernel<UserRp, lim_type, CAPA> with char_decomp = 1 (cellrp.hpp:
-// cellrp_exprs).  The three are part of the key.  What no SharpClaw kernel exists for is refused here with pcl_create's
-// conditions: lim_type 1..3, weno_order 5..17 odd and above 5 with lim_type 2 only; char_decomp 1 in 1-D with lim_type 1 or
-// 2 at weno_order 5 in wave form.  The tile's plane limit is sharp_tile_max_planes' (kernels.hip).
-int pcl_cellrp_compile_sharp(const char *body, const char *preamble, int meqn, int mwaves, int ndim, int math, const int *aux_index,
-                             int naux, int form, int lim_type, int weno_order, int char_decomp, pcl_cellrp **out, long *code_size) {
+// The one compile: the refusals (cellrp_spec_check), the key, the cache, the build.  The public entry points below fill a
+// CellrpSpec -- the narrower ones fewer of its fields, so equal content is one key and one handle -- and end here.
+static int cellrp_compile(const pcl::CellrpSpec &sp, pcl::CellrpTexts t, pcl::CellrpGiven given, pcl_cellrp **out, long *code_size) {
     if (out) *out = nullptr;
-    if (lim_type != 1 && lim_type != 2 && lim_type != 3)
-        return fail(PCL_EINVAL, "pcl_cellrp_compile_sharp: lim_type must be 1 (tvd2), 2 (WENO) or 3 (legacy WENO5), got " + std::to_string(lim_type));
-    if (weno_order < 5 || weno_order > 17 || weno_order % 2 == 0)
-        return fail(PCL_EINVAL, "pcl_cellrp_compile_sharp: weno_order must be odd, 5..17, got " + std::to_string(weno_order));
-    if (weno_order > 5 && lim_type != 2)
-        return fail(PCL_EINVAL, "pcl_cellrp_compile_sharp: weno_order " + std::to_string(weno_order) + " exists for lim_type 2 only, got lim_type " +
-                                    std::to_string(lim_type));
-    if (char_decomp != 0 && char_decomp != 1)
-        return fail(PCL_EINVAL, "pcl_cellrp_compile_sharp: char_decomp must be 0 or 1 (2, 3 need a user evec routine)");
-    if (char_decomp == 1 && (ndim != 1 || lim_type == 3 || weno_order != 5 || (form & PCL_CELLRP_FORM_FWAVE)))
-        return fail(PCL_EINVAL, "pcl_cellrp_compile_sharp: char_decomp = 1 is the wave-based reconstruction: 1-D, lim_type 1 (tvd2_wave) or 2 "
-                                "(weno5_wave), weno_order 5, no f-wave body");
-    pcl::CellrpSharp sharp;
-    sharp.lim_type = lim_type; sharp.weno_order = weno_order; sharp.char_decomp = char_decomp;
-    return cellrp_compile_impl(body, nullptr, preamble, meqn, mwaves, ndim, math, aux_index, naux, form, sharp, out, code_size);
-}
-
-static int cellrp_compile_impl(const char *body, const char *transverse, const char *preamble, int meqn, int mwaves, int ndim,
-                               int math, const int *aux_index, int naux, int form, const pcl::CellrpSharp &sharp, pcl_cellrp **out,
-                               long *code_size) {
-    if (!body || !out) return fail(PCL_EINVAL, "null argument");
-    *out = nullptr;
-    if (!preamble) preamble = "";
-    if (transverse && ndim != 2)
-        return fail(PCL_EINVAL, "pcl_cellrp_compile_t: a transverse body belongs to the unsplit 2-D step (ndim must be 2)");
-    if (meqn < 1 || meqn > PCL_MAX_WAVES || mwaves < 1 || mwaves > PCL_MAX_WAVES)
-        return fail(PCL_EINVAL, "pcl_cellrp_compile: 1 <= meqn <= 8 and 1 <= mwaves <= 8");
-    if (ndim < 1 || ndim > 2) return fail(PCL_EINVAL, "pcl_cellrp_compile: ndim must be 1 or 2 (the classic 1-D and dimension-split 2-D sweeps)");
-    if (math != PCL_MATH_EXACT && math != PCL_MATH_FAST && math != PCL_MATH_STRICT) return fail(PCL_EINVAL, "unknown math mode");
-    // the list of aux components: an index past the solver's maux would be a read outside the aux allocation, so every
-    // entry is checked here and the largest against cfg.maux when the handle is attached
-    if (naux < 0) return fail(PCL_EINVAL, "pcl_cellrp_compile_aux: naux must be >= 0, got " + std::to_string(naux));
-    if (naux > 0 && !aux_index) return fail(PCL_EINVAL, "null argument");
-    if (sharp.on() && sharp.char_decomp == 0) {
-        // the tiles of sharp_kernel in place of sweep_kernel's: q and the capacity function in the x pass, the listed aux
-        // components too in the y pass (sharp1w_kernel, char_decomp = 1, has no tile)
-        const int capa = (form & PCL_CELLRP_FORM_CAPA) ? 1 : 0;
-        const int max_x = pcl::exact::sharp_tile_max_planes(1, naux), max_y = pcl::exact::sharp_tile_max_planes(2, naux);
-        if (meqn + capa > max_x)
-            return fail(PCL_EINVAL, "pcl_cellrp_compile_sharp: meqn + capa = " + std::to_string(meqn + capa) + ", the tile of the SharpClaw x pass "
-                                    "holds at most " + std::to_string(max_x) + " planes (q components and the capacity function) in the 64 KB "
-                                    "a workgroup may declare");
-        if (ndim == 2 && meqn + capa + naux > max_y)
-            return fail(PCL_EINVAL, "pcl_cellrp_compile_sharp: meqn + capa + naux = " + std::to_string(meqn + capa + naux) + ", the tile of the "
-                                    "SharpClaw y pass holds at most " + std::to_string(max_y) + " planes (q components, the capacity function and "
-                                    "listed aux components) in the 64 KB a workgroup may declare");
-    }
-    const int max_planes = sharp.on() ? 1 << 30 : pcl::exact::sweep_tile_max_planes();      // (SharpClaw: the rule above)
-    if (naux > 0 && meqn + naux > max_planes)
-        return fail(PCL_EINVAL, "pcl_cellrp_compile_aux: meqn + naux = " + std::to_string(meqn + naux) + ", the sweep's tile holds at most " +
-                                    std::to_string(max_planes) + " planes (q components and listed aux components) in a workgroup's 64 KB");
-    static_assert(PCL_CELLRP_MAX_AUX >= PCL_MAX_WAVES, "pcl_cellrp_aux writes up to 8 indices");
-    if (naux > PCL_CELLRP_MAX_AUX) return fail(PCL_EINVAL, "pcl_cellrp_compile_aux: at most 8 aux components");
-    if (form & ~(PCL_CELLRP_FORM_FWAVE | PCL_CELLRP_FORM_CAPA))
-        return fail(PCL_EINVAL, "pcl_cellrp_compile_form: form = " + std::to_string(form) + " has a bit that is neither "
-                                "PCL_CELLRP_FORM_FWAVE (1) nor PCL_CELLRP_FORM_CAPA (2)");
-    // the capacity function takes a plane of the sweep tile (classic.hpp: sweep_kernel, PAUX = MEQN + 1)
-    if ((form & PCL_CELLRP_FORM_CAPA) && meqn + 1 + naux > max_planes)
-        return fail(PCL_EINVAL, "pcl_cellrp_compile_form: meqn + 1 + naux = " + std::to_string(meqn + 1 + naux) + ", the sweep's tile holds "
-                                "at most " + std::to_string(max_planes) + " planes (q components, the capacity function and listed aux "
-                                "components) in a workgroup's 64 KB");
-    for (int i = 0; i < naux; i++) {
-        if (aux_index[i] < 0)
-            return fail(PCL_EINVAL, "pcl_cellrp_compile_aux: aux index " + std::to_string(aux_index[i]) + " is negative (0-based components of the aux array)");
-        for (int j = 0; j < i; j++)
-            if (aux_index[j] == aux_index[i])
-                return fail(PCL_EINVAL, "pcl_cellrp_compile_aux: aux index " + std::to_string(aux_index[i]) + " is listed twice");
-    }
+    given.body_and_out = t.body && out;
+    given.transverse = t.transverse != nullptr;
+    if (!t.preamble) t.preamble = "";
+    std::string err;
+    if (cellrp_spec_check(sp, given, err)) return fail(PCL_EINVAL, err);
     CellfnCache &c = cellfn_cache();
     std::lock_guard<std::mutex> lock(c.mu);
-    const std::string key = cellrp_key(body, preamble, meqn, mwaves, ndim, math, aux_index, naux, transverse, form, sharp);
+    const std::string key = cellrp_key(sp, t);
     auto it = c.rp_by_key.find(key);
     pcl_cellrp *r = nullptr;
     if (it != c.rp_by_key.end()) {
@@ -1873,24 +1769,14 @@ static int cellrp_compile_impl(const char *body, const char *transverse, const c
         c.hits++;
     } else {
         std::vector<char> code;
-        std::string err, sym[4];
-        const int slices = transverse ? pcl::unsplit_user_slices(meqn) : 0;
-        if (cellrp_build(body, transverse, preamble, meqn, mwaves, ndim, math, aux_index, naux, slices, form, sharp, code, sym, err))
-            return fail(PCL_EINVAL, err);
+        std::string sym[4];
+        if (cellrp_build(sp, t, code, sym, err)) return fail(PCL_EINVAL, err);
         r = new pcl_cellrp();
         r->id = c.next_id++;
-        r->meqn = meqn; r->mwaves = mwaves; r->ndim = ndim; r->math = math;
-        r->naux = naux;
-        for (int i = 0; i < naux; i++) r->aux[i] = aux_index[i];
         r->key = key;
         r->code.swap(code);
-        r->sym[0] = sym[0]; r->sym[1] = sym[1];
-        r->trans = transverse != nullptr;
-        r->slices = slices;
-        r->sym_u[0] = sym[2]; r->sym_u[1] = sym[3];
-        r->form = form;
-        r->sharp = sharp.on();
-        r->lim_type = sharp.lim_type; r->weno_order = sharp.weno_order; r->char_decomp = sharp.char_decomp;
+        for (int k = 0; k < 4; k++) r->sym[k] = sym[k];
+        r->spec = sp;
         c.rp_by_key[key] = r;
         c.rp_live[r] = r->id;
         c.compiles++;
@@ -1899,6 +1785,54 @@ static int cellrp_compile_impl(const char *body, const char *transverse, const c
     *out = r;
     if (code_size) *code_size = (long)r->code.size();
     return PCL_OK;
+}
+
+// meqn, mwaves, ndim, math and the aux list of a call (the list as far as it was given and fits: the rest is refused)
+static pcl::CellrpSpec cellrp_spec(int meqn, int mwaves, int ndim, int math, const int *aux_index, int naux) {
+    pcl::CellrpSpec sp;
+    sp.meqn = meqn; sp.mwaves = mwaves; sp.ndim = ndim; sp.math = math;
+    sp.naux = naux;
+    for (int i = 0; aux_index && i < naux && i < PCL_CELLRP_MAX_AUX; i++) sp.aux[i] = aux_index[i];
+    return sp;
+}
+
+// With a transverse body (2-D only) the code object also holds the two unsplit kernels; the form (PCL_CELLRP_FORM_* bits)
+// is the pair of template flags its kernels are instantiated with
+int pcl_cellrp_compile_form(const char *body, const char *transverse, const char *preamble, int meqn, int mwaves, int ndim,
+                            int math, const int *aux_index, int naux, int form, pcl_cellrp **out, long *code_size) {
+    pcl::CellrpSpec sp = cellrp_spec(meqn, mwaves, ndim, math, aux_index, naux);
+    sp.trans = transverse != nullptr;
+    sp.form = form;
+    pcl::CellrpGiven given = {};
+    given.aux_list = aux_index != nullptr;
+    return cellrp_compile(sp, {body, transverse, preamble}, given, out, code_size);
+}
+
+int pcl_cellrp_compile_t(const char *body, const char *transverse, const char *preamble, int meqn, int mwaves, int ndim, int math,
+                         const int *aux_index, int naux, pcl_cellrp **out, long *code_size) {
+    return pcl_cellrp_compile_form(body, transverse, preamble, meqn, mwaves, ndim, math, aux_index, naux, 0, out, code_size);
+}
+
+int pcl_cellrp_compile_aux(const char *body, const char *preamble, int meqn, int mwaves, int ndim, int math, const int *aux_index,
+                           int naux, pcl_cellrp **out, long *code_size) {
+    return pcl_cellrp_compile_form(body, nullptr, preamble, meqn, mwaves, ndim, math, aux_index, naux, 0, out, code_size);
+}
+
+int pcl_cellrp_compile(const char *body, const char *preamble, int meqn, int mwaves, int ndim, int math, pcl_cellrp **out,
+                       long *code_size) {
+    return pcl_cellrp_compile_form(body, nullptr, preamble, meqn, mwaves, ndim, math, nullptr, 0, 0, out, code_size);
+}
+
+// The SharpClaw kernels of the one (lim_type, weno_order, char_decomp) around the body in place of the classic ones
+int pcl_cellrp_compile_sharp(const char *body, const char *preamble, int meqn, int mwaves, int ndim, int math, const int *aux_index,
+                             int naux, int form, int lim_type, int weno_order, int char_decomp, pcl_cellrp **out, long *code_size) {
+    pcl::CellrpSpec sp = cellrp_spec(meqn, mwaves, ndim, math, aux_index, naux);
+    sp.form = form;
+    sp.lim_type = lim_type; sp.weno_order = weno_order; sp.char_decomp = char_decomp;
+    pcl::CellrpGiven given = {};
+    given.aux_list = aux_index != nullptr;
+    given.sharp = true;
+    return cellrp_compile(sp, {body, nullptr, preamble}, given, out, code_size);
 }
 
 int pcl_cellrp_release(pcl_cellrp *r) {
@@ -1911,104 +1845,53 @@ int pcl_cellrp_release(pcl_cellrp *r) {
     return PCL_OK;
 }
 
-static int cellrp_check_locked(CellfnCache &c, const pcl_cellrp *r, int meqn, int mwaves, int ndim, int math) {
+// what a live handle was compiled for, copied out under the cache's lock
+static int cellrp_live_spec(const pcl_cellrp *r, pcl::CellrpSpec &sp) {
+    CellfnCache &c = cellfn_cache();
+    std::lock_guard<std::mutex> lock(c.mu);
     if (!r || !c.rp_live.count(r)) return fail(PCL_EINVAL, "not a live Riemann solver handle (pcl_cellrp_compile)");
-    if (r->meqn != meqn || r->mwaves != mwaves || r->ndim != ndim || r->math != math)
-        return fail(PCL_EINVAL, "Riemann solver was compiled for meqn=" + std::to_string(r->meqn) + " mwaves=" + std::to_string(r->mwaves) +
-                                    " ndim=" + std::to_string(r->ndim) + " math=" + std::to_string(r->math) + ", the solver has meqn=" +
-                                    std::to_string(meqn) + " mwaves=" + std::to_string(mwaves) + " ndim=" + std::to_string(ndim) +
-                                    " math=" + std::to_string(math));
+    sp = r->spec;
     return PCL_OK;
 }
 
 int pcl_cellrp_check(const pcl_cellrp *r, int meqn, int mwaves, int ndim, int math) {
-    CellfnCache &c = cellfn_cache();
-    std::lock_guard<std::mutex> lock(c.mu);
-    return cellrp_check_locked(c, r, meqn, mwaves, ndim, math);
+    pcl::CellrpSpec sp;
+    if (int rc = cellrp_live_spec(r, sp)) return rc;
+    std::string err;
+    return cellrp_sizes_check(sp, meqn, mwaves, ndim, math, err) ? fail(PCL_EINVAL, err) : PCL_OK;
 }
 
 int pcl_cellrp_aux(const pcl_cellrp *r, int *naux, int *aux_index) {
     if (!naux) return fail(PCL_EINVAL, "null argument");
-    CellfnCache &c = cellfn_cache();
-    std::lock_guard<std::mutex> lock(c.mu);
-    if (!r || !c.rp_live.count(r)) return fail(PCL_EINVAL, "not a live Riemann solver handle (pcl_cellrp_compile)");
-    *naux = r->naux;
-    for (int i = 0; aux_index && i < r->naux; i++) aux_index[i] = r->aux[i];
+    pcl::CellrpSpec sp;
+    if (int rc = cellrp_live_spec(r, sp)) return rc;
+    *naux = sp.naux;
+    for (int i = 0; aux_index && i < sp.naux; i++) aux_index[i] = sp.aux[i];
     return PCL_OK;
 }
 
 int pcl_cellrp_transverse(const pcl_cellrp *r, int *has, int *slices) {
     if (!has) return fail(PCL_EINVAL, "null argument");
-    CellfnCache &c = cellfn_cache();
-    std::lock_guard<std::mutex> lock(c.mu);
-    if (!r || !c.rp_live.count(r)) return fail(PCL_EINVAL, "not a live Riemann solver handle (pcl_cellrp_compile)");
-    *has = r->trans ? 1 : 0;
-    if (slices) *slices = r->slices;
+    pcl::CellrpSpec sp;
+    if (int rc = cellrp_live_spec(r, sp)) return rc;
+    *has = sp.trans;
+    if (slices) *slices = sp.slices();
     return PCL_OK;
 }
 
 int pcl_cellrp_form(const pcl_cellrp *r, int *form) {
     if (!form) return fail(PCL_EINVAL, "null argument");
-    CellfnCache &c = cellfn_cache();
-    std::lock_guard<std::mutex> lock(c.mu);
-    if (!r || !c.rp_live.count(r)) return fail(PCL_EINVAL, "not a live Riemann solver handle (pcl_cellrp_compile)");
-    *form = r->form;
+    pcl::CellrpSpec sp;
+    if (int rc = cellrp_live_spec(r, sp)) return rc;
+    *form = sp.form;
     return PCL_OK;
 }
 
 int pcl_cellrp_sharp(const pcl_cellrp *r, int *lim_type, int *weno_order, int *char_decomp) {
     if (!lim_type || !weno_order || !char_decomp) return fail(PCL_EINVAL, "null argument");
-    CellfnCache &c = cellfn_cache();
-    std::lock_guard<std::mutex> lock(c.mu);
-    if (!r || !c.rp_live.count(r)) return fail(PCL_EINVAL, "not a live Riemann solver handle (pcl_cellrp_compile)");
-    *lim_type = r->lim_type; *weno_order = r->weno_order; *char_decomp = r->char_decomp;      // zeros: a classic handle
-    return PCL_OK;
-}
-
-// what attaching r to a solver of this configuration asks of the handle; host-only (the cache's lock is held)
-static int cellrp_fits_locked(CellfnCache &c, const pcl_cellrp *r, const pcl_config &cfg, const char *who) {
-    if (int rc = cellrp_check_locked(c, r, cfg.meqn, cfg.mwaves, cfg.ndim, cfg.math)) return rc;
-    // every aux plane the kernel stages must lie inside the solver's aux allocation of cfg.maux planes
-    int top = -1;
-    for (int i = 0; i < r->naux; i++) top = r->aux[i] > top ? r->aux[i] : top;
-    if (top >= cfg.maux)
-        return fail(PCL_EINVAL, std::string(who) + ": the Riemann solver reads aux component " + std::to_string(top) +
-                                    " (0-based), the solver was created with maux = " + std::to_string(cfg.maux));
-    // a handle holds the classic kernels or the SharpClaw kernels of one (lim_type, weno_order, char_decomp), never both
-    const bool sharp_cfg = cfg.kind == PCL_KIND_SHARPCLAW;
-    if (sharp_cfg != r->sharp)
-        return fail(PCL_EINVAL, std::string(who) + (r->sharp ? ": PCL_RP_CELL: the handle was compiled for SharpClaw (pcl_cellrp_compile_sharp) "
-                                                               "and the configuration is a classic solver (cfg.kind = 0)"
-                                                             : ": PCL_RP_CELL: a SharpClaw solver (cfg.kind = 1) needs a handle compiled "
-                                                               "for SharpClaw (pcl_cellrp_compile_sharp); this one holds the classic sweeps"));
-    if (sharp_cfg) {
-        const auto s = [](int v) { return std::to_string(v); };
-        if (cfg.lim_type != r->lim_type)
-            return fail(PCL_EINVAL, std::string(who) + ": PCL_RP_CELL: the handle was compiled for lim_type " + s(r->lim_type) +
-                                        " and cfg.lim_type is " + s(cfg.lim_type));
-        if (cfg.mbc != (r->weno_order + 1) / 2)
-            return fail(PCL_EINVAL, std::string(who) + ": PCL_RP_CELL: the handle was compiled for weno_order " + s(r->weno_order) +
-                                        " (mbc " + s((r->weno_order + 1) / 2) + ") and cfg.mbc is " + s(cfg.mbc) +
-                                        " (weno_order " + s(2 * cfg.mbc - 1) + ")");
-        if (cfg.method[4] != r->char_decomp)
-            return fail(PCL_EINVAL, std::string(who) + ": PCL_RP_CELL: the handle was compiled for char_decomp " + s(r->char_decomp) +
-                                        " and cfg.method[4] (char_decomp) is " + s(cfg.method[4]));
-    }
-    if (!sharp_cfg && cfg.ndim == 2 && cfg.method[2] >= 0 && !r->trans)
-        return fail(PCL_EINVAL, std::string(who) + ": PCL_RP_CELL: the unsplit step (method[2] >= 0) needs a handle compiled with a "
-                                    "transverse body (pcl_cellrp_compile_t)");
-    // the kernels in the handle were instantiated for one form (FWAVE, CAPA): the configuration must say the same
-    const bool hfw = (r->form & PCL_CELLRP_FORM_FWAVE) != 0, hcapa = (r->form & PCL_CELLRP_FORM_CAPA) != 0;
-    if ((cfg.fwave != 0) != hfw)
-        return fail(PCL_EINVAL, std::string(who) + (hfw ? ": PCL_RP_CELL: the handle was compiled for f-waves (PCL_CELLRP_FORM_FWAVE) and "
-                                                          "cfg.fwave is 0"
-                                                        : ": PCL_RP_CELL: cfg.fwave = 1 asks for f-waves and the handle was compiled in "
-                                                          "wave form (pcl_cellrp_compile_form with PCL_CELLRP_FORM_FWAVE)"));
-    if ((cfg.method[5] > 0) != hcapa)
-        return fail(PCL_EINVAL, std::string(who) + (hcapa ? ": PCL_RP_CELL: the handle was compiled for a capacity function "
-                                                            "(PCL_CELLRP_FORM_CAPA) and the solver has none (method[5] is 0)"
-                                                          : ": PCL_RP_CELL: method[5] > 0 asks for a capacity function and the handle "
-                                                            "was compiled without one (pcl_cellrp_compile_form with PCL_CELLRP_FORM_CAPA)"));
+    pcl::CellrpSpec sp;
+    if (int rc = cellrp_live_spec(r, sp)) return rc;
+    *lim_type = sp.lim_type; *weno_order = sp.weno_order; *char_decomp = sp.char_decomp;      // zeros: a classic handle
     return PCL_OK;
 }
 
@@ -2016,45 +1899,33 @@ int pcl_cellrp_attach(pcl_solver *s, pcl_cellrp *r) {
     if (s) s->qt.invalidate();            // quiet tiles: not a read-only call (quiet_tiles.hpp)
     if (!s) return fail(PCL_EINVAL, "null argument");
     if (s->cfg.rp != PCL_RP_CELL) return fail(PCL_EINVAL, "pcl_cellrp_attach: the solver was not created with cfg.rp = PCL_RP_CELL");
-    long id;
-    int naux, slices, form, sharp[3] = {0, 0, 0};
+    pcl::CellrpModule m;
     const void *code;
-    std::string sym[2], sym_u[2];
-    {   // (the entry is never freed: code and names stay valid outside the lock)
+    std::string sym[4];
+    {   // (the entry is never freed: the code stays valid outside the lock)
         CellfnCache &c = cellfn_cache();
         std::lock_guard<std::mutex> lock(c.mu);
         // (a refusal leaves the module attached before where it is)
-        if (int rc = cellrp_fits_locked(c, r, s->cfg, "pcl_cellrp_attach")) return rc;
-        id = r->id; naux = r->naux; code = r->code.data(); sym[0] = r->sym[0]; sym[1] = r->sym[1];
-        slices = r->trans ? r->slices : 0; sym_u[0] = r->sym_u[0]; sym_u[1] = r->sym_u[1];
-        form = r->form;
-        if (r->sharp) { sharp[0] = r->lim_type; sharp[1] = (r->weno_order + 1) / 2; sharp[2] = r->char_decomp; }
+        if (!r || !c.rp_live.count(r)) return fail(PCL_EINVAL, "not a live Riemann solver handle (pcl_cellrp_compile)");
+        std::string err;
+        if (cellrp_fits(r->spec, s->cfg, "pcl_cellrp_attach", err)) return fail(PCL_EINVAL, err);
+        m.id = r->id;
+        m.spec = r->spec;
+        code = r->code.data();
+        for (int k = 0; k < 4; k++) sym[k] = r->sym[k];
     }
-    if (s->cellrp.id == id) return PCL_OK;
+    if (s->cellrp.id == m.id) return PCL_OK;
     HIP_TRY(hipSetDevice(s->cfg.device));
     HIP_TRY(hipStreamSynchronize(s->stream));       // a sweep of the module attached before may still run
     s->cellrp.unload();
-    pcl::CellrpModule m;
     HIP_TRY(hipModuleLoadData(&m.mod, code));
-    for (int k = 0; k < s->cfg.ndim; k++) {
+    for (int k = 0; k < 4 && !sym[k].empty(); k++) {
         hipError_t e = hipModuleGetFunction(&m.fn[k], m.mod, sym[k].c_str());
         if (e != hipSuccess) {
             (void)hipModuleUnload(m.mod);
             return fail(PCL_EHIP, "hipModuleGetFunction(" + sym[k] + "): " + hipGetErrorString(e));
         }
     }
-    for (int k = 0; k < 2 && slices > 0; k++) {
-        hipError_t e = hipModuleGetFunction(&m.fn_u[k], m.mod, sym_u[k].c_str());
-        if (e != hipSuccess) {
-            (void)hipModuleUnload(m.mod);
-            return fail(PCL_EHIP, "hipModuleGetFunction(" + sym_u[k] + "): " + hipGetErrorString(e));
-        }
-    }
-    m.id = id;
-    m.naux = naux;
-    m.slices = slices;
-    m.form = form;
-    m.sharp_lim = sharp[0]; m.sharp_mbc = sharp[1]; m.sharp_cd = sharp[2];
     s->cellrp = m;
     return PCL_OK;
 }
@@ -2068,9 +1939,10 @@ int pcl_create_cellrp(const pcl_config *cfg, pcl_cellrp *r, pcl_solver **out) {
     if (cfg->rp != PCL_RP_CELL) return fail(PCL_EINVAL, "pcl_create_cellrp: cfg.rp must be PCL_RP_CELL");
     if (int rc = create_check(cfg, true)) return rc;
     {
-        CellfnCache &c = cellfn_cache();
-        std::lock_guard<std::mutex> lock(c.mu);
-        if (int rc = cellrp_fits_locked(c, r, *cfg, "pcl_create_cellrp")) return rc;
+        pcl::CellrpSpec sp;
+        std::string err;
+        if (int rc = cellrp_live_spec(r, sp)) return rc;
+        if (cellrp_fits(sp, *cfg, "pcl_create_cellrp", err)) return fail(PCL_EINVAL, err);
     }
     pcl_solver *s = nullptr;
     if (int rc = create_alloc(cfg, &s)) return rc;

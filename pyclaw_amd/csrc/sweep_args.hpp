@@ -172,6 +172,23 @@ struct TileNext {
 // cells a tile of the one-kernel step owns, for the host's tile counts (kernels.hip ties them to F_OWN_C, F_OWN_R)
 constexpr int TILE_OWN_C = 60, TILE_OWN_R = 12;
 
+// What a user-written Riemann solver (cellrp.hpp) is compiled for: the one record that travels from a pcl_cellrp_compile*
+// call through the cache entry and the loaded module to the launchers.  Every field is part of the cache key and decides
+// which kernels the code object holds.  A default-constructed one is "nothing attached".
+#define PCL_CELLRP_MAX_AUX 8       // what pcl_cellrp_aux writes at most; the tile limits are tighter (cellrp_spec_check)
+struct CellrpSpec {
+    int meqn = 0, mwaves = 0, ndim = 0, math = 0;
+    int naux = 0, aux[PCL_CELLRP_MAX_AUX] = {0};    // the aux components the body reads, in the body's order
+    int trans = 0;                                  // 1: a transverse body, the code object holds the unsplit kernels too
+    int form = 0;                                   // PCL_CELLRP_FORM_* bits
+    int lim_type = 0, weno_order = 0, char_decomp = 0;      // a SharpClaw handle (lim_type 0: a classic one)
+    bool fwave() const { return (form & PCL_CELLRP_FORM_FWAVE) != 0; }
+    bool capa() const { return (form & PCL_CELLRP_FORM_CAPA) != 0; }
+    bool sharp() const { return lim_type != 0; }
+    int mbc() const { return sharp() ? (weno_order + 1) / 2 : 0; }
+    int slices() const { return trans ? unsplit_user_slices(meqn) : 0; }   // per workgroup of the unsplit kernels
+};
+
 struct SweepLaunch {
     SweepArgs a;
     int ndim;   // 1 or 2
@@ -181,19 +198,11 @@ struct SweepLaunch {
     int lim_type;  // SharpClaw reconstruction (2 PyWENO weno5, 3 legacy weno5)
     int char_decomp = 0;   // SharpClaw: 1 = wave-based reconstruction (1-D: tvd2_wave / weno5_wave)
     hipStream_t stream;
-    // rp == PCL_RP_CELL (a user-written Riemann solver, cellrp.hpp): sweep_kernel<UserRp, ids, user_capa, user_fwave, .> of the module the
-    // solver handle has loaded; launch_sweep launches it over the grid it computes for the built-in solvers
+    // rp == PCL_RP_CELL (a user-written Riemann solver, cellrp.hpp): user_fn is the kernel of this pass in the module the solver
+    // handle has loaded (null: nothing attached) and user what that module was compiled for.  launch_sweep, launch_unsplit and
+    // launch_sharp refuse a launch that says otherwise and launch user_fn over the grids of the built-in solvers
     hipFunction_t user_fn = nullptr;
-    int user_naux = 0;      // aux components that solver's body reads: with any, a launch without a.aux is refused
-    // the form that module's kernels were instantiated for (FWAVE, CAPA): a launch whose fwave or a.mcapa > 0 says
-    // otherwise is refused, and so is one with user_capa and without a.aux
-    bool user_fwave = false, user_capa = false;
-    // launch_unsplit: user_fn is unsplit_x_kernel / unsplit_y_kernel<UserRp, user_fwave, user_slices, user_capa> of that module (null:
-    // nothing attached), user_slices the U its handle was compiled with (unsplit_user_slices)
-    int user_slices = 0;
-    // launch_sharp: user_fn is sharp_kernel<UserRp, ids, user_capa, user_sharp_lim, user_sharp_k> or, with user_sharp_cd = 1,
-    // sharp1w_kernel<UserRp, user_sharp_lim, user_capa> of that module; user_sharp_k = 0: the module holds classic kernels
-    int user_sharp_lim = 0, user_sharp_k = 0, user_sharp_cd = 0;
+    CellrpSpec user;
     // one-kernel step only (classic_fused.hpp, quiet tiles): this launch's per-tile words and per-wavefront Courant
     // maxima (tq_out null: no bookkeeping).  A list launch (tq_list set) computes the tq_next->na + nq tiles a
     // hand-over+list kernel listed behind the previous launch and publishes the Courant number of those it skips.

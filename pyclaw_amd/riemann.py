@@ -223,33 +223,55 @@ class CellRiemann(RiemannSolver):
             return self
         rp, size = ctypes.c_void_p(), ctypes.c_long(0)
         mode = {'exact': 0, 'fast': 1, 'strict': 2}[math]
+        aux = (ctypes.c_int * len(self.aux))(*self.aux) if self.aux else None
         if sharp is not None:
             _lib.check(_lib.lib().pcl_cellrp_compile_sharp(self.body.encode(), self.preamble.encode(), self.meqn, self.mwaves,
-                                                           self.ndim, mode,
-                                                           (ctypes.c_int * len(self.aux))(*self.aux) if self.aux else None,
-                                                           len(self.aux), form, sharp[0], sharp[1], sharp[2],
+                                                           self.ndim, mode, aux, len(self.aux), form, sharp[0], sharp[1], sharp[2],
                                                            ctypes.byref(rp), ctypes.byref(size)))
-        elif form:
+        else:
             _lib.check(_lib.lib().pcl_cellrp_compile_form(self.body.encode(),
                                                           None if self.transverse is None else self.transverse.encode(),
                                                           self.preamble.encode(), self.meqn, self.mwaves, self.ndim, mode,
-                                                          (ctypes.c_int * len(self.aux))(*self.aux) if self.aux else None,
-                                                          len(self.aux), form, ctypes.byref(rp), ctypes.byref(size)))
-        elif self.transverse is not None:
-            _lib.check(_lib.lib().pcl_cellrp_compile_t(self.body.encode(), self.transverse.encode(), self.preamble.encode(),
-                                                       self.meqn, self.mwaves, self.ndim, mode,
-                                                       (ctypes.c_int * len(self.aux))(*self.aux) if self.aux else None,
-                                                       len(self.aux), ctypes.byref(rp), ctypes.byref(size)))
-        elif self.aux:
-            _lib.check(_lib.lib().pcl_cellrp_compile_aux(self.body.encode(), self.preamble.encode(), self.meqn, self.mwaves,
-                                                         self.ndim, mode, (ctypes.c_int * len(self.aux))(*self.aux),
-                                                         len(self.aux), ctypes.byref(rp), ctypes.byref(size)))
-        else:
-            _lib.check(_lib.lib().pcl_cellrp_compile(self.body.encode(), self.preamble.encode(), self.meqn, self.mwaves,
-                                                     self.ndim, mode, ctypes.byref(rp), ctypes.byref(size)))
+                                                          aux, len(self.aux), form, ctypes.byref(rp), ctypes.byref(size)))
         self.release()
         self._rp, self._key, self.code_size = rp, key, int(size.value)
         return self
+
+    def check_solver(self, solver, state):
+        """What the classic and the SharpClaw solvers alike refuse of a user-written solver, each with its reason: the
+        form (compiled into the kernels, so the solver and the state must say the same), more than one rank, the aux list."""
+        from . import parallel
+        passes, into, unit = ("stages", "", "stage") if self.sharpclaw else ("sweeps", " into the sweep", "step")
+        if solver.fwave and not self.fwave:
+            raise NotImplementedError("CellRiemann: fwave = True is not served by this solver: its body returns waves; an "
+                                      "f-wave body is compiled with CellRiemann(..., fwave=True)")
+        if self.fwave and not solver.fwave:
+            raise ValueError("CellRiemann: the solver was written with fwave=True (its body assigns f-waves) and "
+                             "solver.fwave is False: set solver.fwave = True")
+        if state.mcapa >= 0 and not self.capa:
+            raise NotImplementedError("CellRiemann: state.mcapa (a capacity function) is not served by this solver: it is "
+                                      "compiled%s without one (CellRiemann(..., capa=True) compiles it with one)" % into)
+        if self.capa and state.mcapa < 0:
+            raise ValueError("CellRiemann: the solver was written with capa=True (%s with a capacity function) and "
+                             "state.mcapa is not set: name the aux component in state.mcapa" % passes)
+        if state.decomp is not None and parallel.world_size() > 1:
+            raise NotImplementedError("CellRiemann: more than one rank is not served: a user-written solver runs on one "
+                                      "block (the decomposed %s's plans know the built-in solvers only)" % unit)
+        if self.aux:
+            # (an index past maux would be a read outside the aux allocation: the library refuses it again at attach)
+            if state.aux is None:
+                raise ValueError("CellRiemann: the body reads aux components %r and state.aux is None" % (self.aux,))
+            if max(self.aux) >= state.maux:
+                raise ValueError("CellRiemann: the body reads aux component %d (0-based) and state.maux = %d"
+                                 % (max(self.aux), state.maux))
+
+    def send_params(self, solver):
+        """params reassigned since the solver's last step: they travel by value with its next kernels, no compile."""
+        from . import _lib
+        p = self._params
+        if len(p) != len(solver._user_rp_sent) or not np.array_equal(p, solver._user_rp_sent):
+            _lib.check(_lib.lib().pcl_cellrp_params(solver._h, _lib.d(p) if len(p) else None, len(p)))
+            solver._user_rp_sent = p.copy()
 
     def release(self):
         if self._rp is not None:

@@ -170,7 +170,7 @@ class SharpClawSolver(Solver):
         else:
             self.start_step(self, solution)
         if self._user_rp is not None:
-            self._send_user_rp_params()
+            self._user_rp.send_params(self)
         t, dt = state.t, self.dt
         # st(reg, t, op, D, A, B, ...): deltaq = dq(reg, t) followed by the combination that consumes it.
         # Without a Python dq_src (or with a DeviceDqSource the last pass evaluates) both run as ONE fused device stage
@@ -389,40 +389,11 @@ class SharpClawSolver(Solver):
     def _check_user_rp(self, rp, state):
         """What a user-written Riemann solver (riemann.CellRiemann) asks of a SharpClaw solver, each refusal with its reason.
         (lim_type, weno_order, char_decomp and tfluct_solver were checked above, as for a built-in solver.)"""
-        from . import parallel
         if not rp.sharpclaw:
             raise NotImplementedError("CellRiemann: the SharpClaw solvers are served by a solver written with sharpclaw=True "
                                       "(compiled into the SharpClaw kernels); without it a user-written Riemann solver is "
                                       "compiled into the classic sweep kernel only (ClawSolver1D / ClawSolver2D)")
-        if self.fwave and not rp.fwave:
-            raise NotImplementedError("CellRiemann: fwave = True is not served by this solver: its body returns waves; an "
-                                      "f-wave body is compiled with CellRiemann(..., fwave=True)")
-        if rp.fwave and not self.fwave:
-            raise ValueError("CellRiemann: the solver was written with fwave=True (its body assigns f-waves) and "
-                             "solver.fwave is False: set solver.fwave = True")
-        if state.mcapa >= 0 and not rp.capa:
-            raise NotImplementedError("CellRiemann: state.mcapa (a capacity function) is not served by this solver: it is "
-                                      "compiled without one (CellRiemann(..., capa=True) compiles it with one)")
-        if rp.capa and state.mcapa < 0:
-            raise ValueError("CellRiemann: the solver was written with capa=True (stages with a capacity function) and "
-                             "state.mcapa is not set: name the aux component in state.mcapa")
-        if state.decomp is not None and parallel.world_size() > 1:
-            raise NotImplementedError("CellRiemann: more than one rank is not served: a user-written solver runs on one "
-                                      "block (the decomposed stage's plans know the built-in solvers only)")
-        if rp.aux:
-            # (an index past maux would be a read outside the aux allocation: the library refuses it again at attach)
-            if state.aux is None:
-                raise ValueError("CellRiemann: the body reads aux components %r and state.aux is None" % (rp.aux,))
-            if max(rp.aux) >= state.maux:
-                raise ValueError("CellRiemann: the body reads aux component %d (0-based) and state.maux = %d"
-                                 % (max(rp.aux), state.maux))
-
-    def _send_user_rp_params(self):
-        """CellRiemann.params reassigned since the last step: they travel by value with the next stages, no compile."""
-        p = self._user_rp.params
-        if len(p) != len(self._user_rp_sent) or not np.array_equal(p, self._user_rp_sent):
-            _lib.check(_lib.lib().pcl_cellrp_params(self._h, _lib.d(p) if len(p) else None, len(p)))
-            self._user_rp_sent = p.copy()
+        rp.check_solver(self, state)
 
     def _custom_bc(self, state, dim, idim, side, fn):
         # Python custom BCs on a stage: same strip protocol as the base class, `state` carries stage time
