@@ -220,6 +220,83 @@ wave[1][0] = a2 * zi;   wave[1][1] = a2; s[1] = auxr[1];
 for (int m = 0; m < 2; m++) { amdq[m] = s[0] * wave[0][m]; apdq[m] = s[1] * wave[1][m]; }
 """
 
+# Bodies for pyclaw.CellRiemann3D, the dimension-split 3-D step: ixy is 1, 2 or 3.
+
+# 3-D acoustics q = (p, u, v, w) with impedance and sound speed per cell, aux = (0, 1) = (Z, c): the built-in
+# vc_acoustics_3d (VcAcoustics3D of pyclaw_amd/csrc/rp.hpp) expression by expression
+VC_ACOUSTICS_3D_RP = """
+constexpr int mu = ixy;
+const double d1 = qr[0] - ql[0];
+const double d2 = qr[mu] - ql[mu];
+const double zi = auxr[0], zim = auxl[0];
+const Recip by_zz(zim + zi);
+const double a1 = by_zz.div(-d1 + zi * d2);
+const double a2 = by_zz.div(d1 + zim * d2);
+wave[0][0] = -a1 * zim; wave[0][mu] = a1; s[0] = -auxl[1];
+wave[1][0] = a2 * zi;   wave[1][mu] = a2; s[1] = auxr[1];
+amdq[0] = s[0] * wave[0][0]; amdq[mu] = s[0] * wave[0][mu];
+apdq[0] = s[1] * wave[1][0]; apdq[mu] = s[1] * wave[1][mu];
+"""
+
+# A solver the library does not have: 3-D acoustics in a homogeneous medium, no aux arrays; p = Z, c.  The formulas of the
+# body above with both cells' coefficients taken from p[]: where the aux arrays of vc_acoustics_3d are constant, its bits
+ACOUSTICS_3D_RP = """
+constexpr int mu = ixy;
+const double d1 = qr[0] - ql[0];
+const double d2 = qr[mu] - ql[mu];
+const double zz = p[0], cc = p[1];
+const Recip by_zz(zz + zz);
+const double a1 = by_zz.div(-d1 + zz * d2);
+const double a2 = by_zz.div(d1 + zz * d2);
+wave[0][0] = -a1 * zz; wave[0][mu] = a1; s[0] = -cc;
+wave[1][0] = a2 * zz;  wave[1][mu] = a2; s[1] = cc;
+amdq[0] = s[0] * wave[0][0]; amdq[mu] = s[0] * wave[0][mu];
+apdq[0] = s[1] * wave[1][0]; apdq[mu] = s[1] * wave[1][mu];
+"""
+
+# p = u, v, w: the text of the 2-D body, the sweep direction picks the velocity
+ADVECTION_3D_RP = ADVECTION_2D_RP
+
+# scalar 3-D Burgers, q_t + (q^2/2)_x + (q^2/2)_y + (q^2/2)_z = 0 -- the 1-D body in every direction
+BURGERS_3D_RP = BURGERS_1D_RP
+
+# 3-D Euler equations, q = (rho, rho u, rho v, rho w, E), p = gamma: Roe solver with three waves (u - c, u, u + c; the
+# middle one carries the entropy wave and both shear waves), no entropy fix.  Written in the sweep's own frame -- mu the
+# normal momentum, mv and mw the other two in cyclic order -- so that a cyclic permutation of the axes and of the
+# momentum components permutes the result bit for bit.
+EULER_3D_RP = """
+constexpr int mu = ixy, mv = ixy % 3 + 1, mw = (ixy + 1) % 3 + 1;
+const double gamma1 = p[0] - 1.0;
+const double rsl = dsqrt(ql[0]), rsr = dsqrt(qr[0]), rsq2 = rsl + rsr;
+const double pl = gamma1 * (ql[4] - 0.5 * (ql[mu] * ql[mu] + ql[mv] * ql[mv] + ql[mw] * ql[mw]) / ql[0]);
+const double pr = gamma1 * (qr[4] - 0.5 * (qr[mu] * qr[mu] + qr[mv] * qr[mv] + qr[mw] * qr[mw]) / qr[0]);
+const double u = (ql[mu] / rsl + qr[mu] / rsr) / rsq2;
+const double v = (ql[mv] / rsl + qr[mv] / rsr) / rsq2;
+const double w = (ql[mw] / rsl + qr[mw] / rsr) / rsq2;
+const double enth = ((ql[4] + pl) / rsl + (qr[4] + pr) / rsr) / rsq2;
+const double uvw2 = u * u + v * v + w * w;
+const double a2 = gamma1 * (enth - 0.5 * uvw2);
+const double a = dsqrt(a2);
+const double g1a2 = gamma1 / a2, euv = enth - uvw2;
+const double d1 = qr[0] - ql[0], d2 = qr[mu] - ql[mu], d3 = qr[mv] - ql[mv], d4 = qr[mw] - ql[mw], d5 = qr[4] - ql[4];
+const double b4 = g1a2 * (euv * d1 + u * d2 + v * d3 + w * d4 - d5);
+const double b2 = d3 - v * d1;
+const double b3 = d4 - w * d1;
+const double b5 = (d2 + (a - u) * d1 - a * b4) / (2.0 * a);
+const double b1 = d1 - b4 - b5;
+wave[0][0] = b1; wave[0][mu] = b1 * (u - a); wave[0][mv] = b1 * v; wave[0][mw] = b1 * w; wave[0][4] = b1 * (enth - u * a);
+s[0] = u - a;
+wave[1][0] = b4; wave[1][mu] = b4 * u; wave[1][mv] = b4 * v + b2; wave[1][mw] = b4 * w + b3;
+wave[1][4] = b4 * 0.5 * uvw2 + b2 * v + b3 * w;
+s[1] = u;
+wave[2][0] = b5; wave[2][mu] = b5 * (u + a); wave[2][mv] = b5 * v; wave[2][mw] = b5 * w; wave[2][4] = b5 * (enth + u * a);
+s[2] = u + a;
+for (int m = 0; m < 5; m++) {
+    amdq[m] = dmin(s[0], 0.0) * wave[0][m] + dmin(s[1], 0.0) * wave[1][m] + dmin(s[2], 0.0) * wave[2][m];
+    apdq[m] = dmax(s[0], 0.0) * wave[0][m] + dmax(s[1], 0.0) * wave[1][m] + dmax(s[2], 0.0) * wave[2][m];
+}
+"""
+
 # F-wave solvers: pyclaw.CellRiemann(..., fwave=True) with solver.fwave = True.  The array the body assigns is fwave[][],
 # the pieces of the flux difference; between two EQUAL cells over different coefficients they are not zero, and every
 # interface is solved.
@@ -693,12 +770,14 @@ def advection1D(pyclaw, mx=1000, tfinal=1.0, nout=10):
     return claw
 
 
-def acoustics3D(pyclaw, test='hom', mx=None, my=None, mz=None, run=True, math='exact', tfinal=2.0, nout=10):
+def acoustics3D(pyclaw, test='hom', mx=None, my=None, mz=None, run=True, math='exact', tfinal=2.0, nout=10, user_rp=False):
     """test/acoustics/3d/acoustics.py:6-96.  'hom': dim-split 256x4x4, all periodic (the reference gates
-    final_difference = 0.00286 +- 1e-4, test/test_examples.py:481-488); 'het' needs the unsplit step3."""
+    final_difference = 0.00286 +- 1e-4, test/test_examples.py:481-488); 'het' needs the unsplit step3.  user_rp=True
+    ('hom' only: the dimension-split step): the same solver as the body VC_ACOUSTICS_3D_RP of a pyclaw.CellRiemann3D."""
     solver = pyclaw.ClawSolver3D()
     solver.math = math
-    solver.rp = pyclaw.riemann.rp_vc_acoustics_3d
+    solver.rp = (pyclaw.CellRiemann3D(VC_ACOUSTICS_3D_RP, 4, 2, aux=(0, 1), name="vc_acoustics_3d_user") if user_rp
+                 else pyclaw.riemann.rp_vc_acoustics_3d)
     for k in range(3):
         solver.bc_lower[k] = solver.bc_upper[k] = pyclaw.BC.periodic
         solver.aux_bc_lower[k] = solver.aux_bc_upper[k] = pyclaw.BC.periodic
@@ -741,6 +820,44 @@ def acoustics3D(pyclaw, test='hom', mx=None, my=None, mz=None, run=True, math='e
     claw.solver = solver
     claw.tfinal = tfinal
     claw.nout = nout
+    if not run:
+        return claw
+    claw.run()
+    return claw
+
+
+def euler3D(pyclaw, axis=0, n=64, across=(4, 4), tfinal=0.1, nout=1, run=True, math='exact', order=2):
+    """A system the library has no 3-D solver for: the Euler equations through EULER_3D_RP in a pyclaw.CellRiemann3D.
+    Sod's jump across the plane through the middle of the box normal to `axis` (0, 1, 2), n cells along that axis and
+    `across` cells along the other two (in cyclic order), extrapolation on every side, dimension-split step."""
+    solver = pyclaw.ClawSolver3D()
+    solver.math = math
+    solver.rp = pyclaw.CellRiemann3D(EULER_3D_RP, 5, 3, params=[gamma], name="euler_3d_user")
+    solver.dim_split = True
+    solver.order = order
+    solver.mwaves = 3
+    solver.limiters = [4, 4, 4]
+    for k in range(3):
+        solver.bc_lower[k] = solver.bc_upper[k] = pyclaw.BC.outflow
+    cells = [0, 0, 0]
+    cells[axis], cells[(axis + 1) % 3], cells[(axis + 2) % 3] = n, across[0], across[1]
+    # (unit cells in all three directions: a permutation of the axes is a permutation of the problem)
+    d = 1.0 / n
+    dims = [pyclaw.Dimension(name, 0.0, cells[k] * d, cells[k]) for k, name in enumerate('xyz')]
+    grid = pyclaw.Grid(dims)
+    state = pyclaw.State(grid, 5)
+    grid.compute_c_center()
+    along = grid._c_center[axis]
+    left = along < 0.5
+    state.q[0] = np.where(left, 1.0, 0.125)
+    state.q[1:4] = 0.0
+    state.q[4] = np.where(left, 1.0, 0.1) / gamma1
+    claw = pyclaw.Controller()
+    claw.keep_copy = True
+    claw.solution = pyclaw.Solution(state)
+    claw.solver = solver
+    claw.tfinal, claw.nout = tfinal, nout
+    solver.dt_initial = 0.2 * d
     if not run:
         return claw
     claw.run()

@@ -73,7 +73,8 @@ extern "C" {
                         /* meqn, mwaves <= 8 from the config, rp_params = the body's p[8]; classic 1-D and dimension-split  */
                         /* 2-D steps (unsplit with a transverse body); the body may read listed aux components              */
                         /* (pcl_cellrp_compile_aux); f-waves and a capacity function through pcl_cellrp_compile_form and    */
-                        /* pcl_create_cellrp; the SharpClaw stages through pcl_cellrp_compile_sharp and pcl_create_cellrp.  */
+                        /* pcl_create_cellrp; the SharpClaw stages through pcl_cellrp_compile_sharp and pcl_create_cellrp;  */
+                        /* the dimension-split 3-D step through pcl_cellrp_compile3 and pcl_create_cellrp.                  */
                         /* Not a built-in solver: pcl_rp_info refuses the id                                                */
 
 /* boundary condition types = pyclaw.BC (src/pyclaw/solver.py:17-23) */
@@ -477,6 +478,18 @@ int pcl_cellrp_compile_sharp(const char *body, const char *preamble, int meqn, i
                              int naux, int form, int lim_type, int weno_order, int char_decomp, pcl_cellrp **out, long *code_size);
 /* Host-only: what a live handle was compiled for by pcl_cellrp_compile_sharp; three zeros for a classic handle. */
 int pcl_cellrp_sharp(const pcl_cellrp *r, int *lim_type, int *weno_order, int *char_decomp);
+/* The same body in the dimension-split 3-D step (cfg.ndim = 3, method[2] < 0, mbc = 2; step3ds): the library compiles the
+ * x, y and z passes of its 3-D sweep kernel (csrc/classic.hpp: sweep3_kernel, DIR 1..3) around the body and nothing else.
+ * ixy is 1, 2 or 3; the body, the preamble and the aux list mean what they mean above (maux may be 0: no list).  form may
+ * carry PCL_CELLRP_FORM_CAPA only: PCL_CELLRP_FORM_FWAVE is PCL_EINVAL (the 3-D kernel has no f-wave form).
+ * Plane limit: all three passes stage q, the listed aux components and the capacity function in one tile of the 64 KB a
+ * workgroup may declare, 64 cells x (16 + 1) columns per plane in the y and z passes: meqn + naux + capa <= 7; more is
+ * PCL_EINVAL with the sum and the limit.  Such a handle serves pcl_create_cellrp with cfg.ndim = 3 and nothing else, and a
+ * 3-D configuration is served by such a handle alone: the calls above go on refusing ndim == 3, pcl_create goes on
+ * refusing PCL_RP_CELL with ndim == 3, and pcl_create_cellrp refuses the unsplit 3-D step (method[2] >= 0: it needs rpt3 and
+ * rptt3 bodies), cfg.fwave and every cfg.kind but PCL_KIND_CLASSIC for it.  One block.  Host-only. */
+int pcl_cellrp_compile3(const char *body, const char *preamble, int meqn, int mwaves, int math, const int *aux_index, int naux,
+                        int form, pcl_cellrp **out, long *code_size);
 /* Host-only: *has = 1 if the live handle was compiled with a transverse body, and then *slices (may be null) = the slices
  * per workgroup of its unsplit kernels; else *has = 0, *slices = 0. */
 int pcl_cellrp_transverse(const pcl_cellrp *r, int *has, int *slices);

@@ -11,7 +11,7 @@ from .cfl import CFL
 from .clawpack import (CellSource, ClawSolver1D, ClawSolver2D, ClawSolver3D, DeviceSource, EulerRadialSource,
                        SphereCoriolisSource)
 from .controller import Controller
-from .riemann import CellRiemann
+from .riemann import CellRiemann, CellRiemann3D
 from .grid import Dimension, Grid
 from .sharpclaw import CellDqSource, SharpClawSolver1D, SharpClawSolver2D, DeviceDqSource, EulerRadialDqSource
 from .solution import Solution
@@ -20,4 +20,4 @@ from .state import State
 
 __all__ = ['limiters', 'riemann', 'CFL', 'ClawSolver1D', 'ClawSolver2D', 'ClawSolver3D', 'DeviceSource', 'EulerRadialSource', 'SphereCoriolisSource', 'SphereMirrorBC',
            'Controller', 'SharpClawSolver1D', 'SharpClawSolver2D', 'DeviceDqSource', 'EulerRadialDqSource', 'Dimension', 'Grid', 'Solution', 'BC', 'ConstantStateBC', 'DeviceBC', 'State',
-           'CellFunction', 'CellSource', 'CellDqSource', 'CellStartStep', 'CellBC', 'CellRiemann']
+           'CellFunction', 'CellSource', 'CellDqSource', 'CellStartStep', 'CellBC', 'CellRiemann', 'CellRiemann3D']

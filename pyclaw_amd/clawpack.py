@@ -280,9 +280,9 @@ class ClawSolver(Solver):
         cfg.math = {'exact': 0, 'fast': 1, 'strict': 2}[self.math]
         import ctypes
         h = ctypes.c_void_p()
-        if user_rp and ((self.ndim == 2 and not self.dim_split) or rp.fwave or rp.capa):
-            # the unsplit step, f-waves, a capacity function: the library checks the configuration against the handle (its
-            # transverse body, its form) and attaches
+        if user_rp and ((self.ndim == 2 and not self.dim_split) or rp.fwave or rp.capa or self.ndim == 3):
+            # the unsplit step, f-waves, a capacity function, 3-D: the library checks the configuration against the handle
+            # (its transverse body, its form, the sweeps it holds) and attaches
             _lib.check(_lib.lib().pcl_create_cellrp(ctypes.byref(cfg), rp._rp, ctypes.byref(h)))
             self._h = h
         else:
@@ -308,9 +308,17 @@ class ClawSolver(Solver):
             raise NotImplementedError("CellRiemann: this solver was written with sharpclaw=True: it is compiled into the "
                                       "SharpClaw kernels and serves SharpClawSolver1D / SharpClawSolver2D alone; a classic "
                                       "solver takes a CellRiemann without it")
-        if self.ndim == 3:
-            raise NotImplementedError("CellRiemann: the user-written solver is compiled into the 1-D and 2-D sweep kernels; "
-                                      "ClawSolver3D has no sweep for it")
+        if self.rp.ndim == 3 and self.ndim != 3:
+            raise NotImplementedError("CellRiemann3D: this solver is compiled into the three passes of the 3-D sweep kernel "
+                                      "and serves ClawSolver3D alone; %s takes a CellRiemann with ndim=%d"
+                                      % (type(self).__name__, self.ndim))
+        if self.ndim == 3 and self.rp.ndim != 3:
+            raise NotImplementedError("CellRiemann: this user-written solver is compiled into the 1-D and 2-D sweep kernels; "
+                                      "ClawSolver3D takes a CellRiemann3D, compiled into its three sweeps")
+        if self.ndim == 3 and not self.dim_split:
+            raise NotImplementedError("CellRiemann3D: dim_split = False (the unsplit 3-D step) needs transverse solvers, rpt3 "
+                                      "and rptt3; the body is the normal solver only, so the 3-D step is the dimension-split "
+                                      "one (dim_split = True)")
         if self.ndim == 2 and not self.dim_split and not self.rp.has_transverse:
             raise NotImplementedError("CellRiemann: dim_split = False needs a transverse Riemann solver (rpt2); the body "
                                       "is the normal solver only, so the 2-D step is the dimension-split one "
@@ -430,7 +438,8 @@ class ClawSolver2D(ClawSolver):
 
 class ClawSolver3D(ClawSolver):
     r"""3D classic solver (clawpack.py:563-702): ``dim_split=True`` (Godunov splitting, ``step3ds``) or the unsplit
-    algorithm with the ``rpt3``/``rptt3`` transverse solves (``step3``; ``order_trans`` 0, 10, 11, 20, 21, 22)."""
+    algorithm with the ``rpt3``/``rptt3`` transverse solves (``step3``; ``order_trans`` 0, 10, 11, 20, 21, 22).
+    ``solver.rp`` may be a user-written ``riemann.CellRiemann3D``: the dimension-split step only."""
 
     no_trans = 0
     trans_inc = 11

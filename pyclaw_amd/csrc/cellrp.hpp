@@ -18,7 +18,7 @@
 //     const double ql[MEQN], qr[MEQN]      the cells left and right of the interface
 //     const double p[8]                    the solver's parameters (RpParams::v; by value in SweepArgs, so changing them
 //                                          compiles nothing)
-//     ixy                                  compile-time constant, 1 = x sweep (always in 1-D), 2 = y sweep
+//     ixy                                  compile-time constant, 1 = x sweep (always in 1-D), 2 = y sweep, 3 = z sweep
 //     double wave[MWAVES][MEQN], s[MWAVES], amdq[MEQN], apdq[MEQN]
 //                                          the results, zero on entry: what the body never assigns is a compile-time zero
 //     dmax, dmin, dsqrt, fdiv, Recip ...   the helpers rp.hpp gives the built-in solvers (a built-in solver restated as a
@@ -37,6 +37,12 @@
 //     -DPCL_CELLRP_MEQN / _MWAVES / _NDIM and the namespace and flags of the mode.  1 <= meqn, mwaves <= 8 (MAX_WAVES_K),
 //     ndim 1 or 2, 8 parameters.  Kernels: sweep_kernel<UserRp, 1, CAPA, FWAVE, true> (the 1-D step), or <UserRp, 1, ..,
 //     false> and <UserRp, 2, .., false> (the x and y passes of step2ds).
+//     ndim 3 (pcl_cellrp_compile3 alone; every other call refuses it): sweep3_kernel<UserRp, 1, CAPA>, <UserRp, 2, CAPA>,
+//     <UserRp, 3, CAPA>, the x, y and z passes of the dimension-split step3ds, and nothing else -- no transverse body, no
+//     SharpClaw kernels, no f-wave form (sweep3_kernel has none).  ixy is 1, 2 or 3.  The aux list and CAPA mean what they
+//     mean below; all three passes stage q, the listed components and the capacity function in one static tile, so
+//     meqn + naux + capa <= sweep3_tile_max_planes() (7, set by the 64 x 17 doubles of the y / z tile: Tile3Shape,
+//     classic.hpp).  Such a handle serves cfg.ndim = 3 with method[2] < 0 and mbc = 2 (pcl_create_cellrp), nothing else.
 //   naux, aux[]   (pcl_cellrp_compile_aux, CellRiemann(aux=...))
 //     The components of the aux array the body reads.  -DPCL_CELLRP_NAUX=<n> behind a generated constexpr table of the
 //     list: NAUX = NAUX_T = n, aux_index<IXY>(k) = auxt_index<IXY>(k) = the k-th listed component (0-based; one list for
@@ -90,7 +96,8 @@
 //
 // NOT SERVED under SharpClaw: a fused dq source (a source term runs as its own pass), char_decomp 2 / 3, tfluct, a
 // transverse body.  Not served in any form: HAS_QCOR (the sphere solver's conservation fix), a transverse body with both
-// cells and aux, the marching y phase, the one-kernel step, 3-D, more than one block.
+// cells and aux, the marching y phase, the one-kernel step, the unsplit 3-D step (rpt3 / rptt3 bodies, march3p_kernel),
+// f-waves in 3-D, more than one block (decomposed runs).
 #pragma once
 #include "cellfn.hpp"
 // generated by the Makefile (embed_headers.py): PCL_RTC_FLAGS_EXACT / _FAST / _STRICT, the flags kernels_<mode>.o is built
@@ -257,7 +264,8 @@ static const char *const kCellrpTransSolve = R"PCLSRC(
 // The end of the text: the plane limits the host refused over (cellrp_spec_check), restated.  The classic sweep tile holds
 // q, the listed aux components and, with one, the capacity function's plane (sweep_kernel: PAUX = MEQN + 1); sharp_kernel's
 // tile is static LDS of NP * TA * WAVE doubles, NP = meqn + capa in the x pass and meqn + capa + naux in the y pass, TA =
-// sharp_tile_across<UserRp, IXY>().
+// sharp_tile_across<UserRp, IXY>(); sweep3_kernel's (NDIM == 3) is static LDS of (meqn + naux + capa) * Tile3Shape<DIR>::PLANE
+// doubles, the rule sweep3_tile_planes() (classic.hpp).
 static const char *const kCellrpClose = R"PCLSRC(};
 static constexpr int USER_CAPA = (PCL_CELLRP_FORM & 2) != 0 ? 1 : 0;
 #if PCL_CELLRP_SHARP
@@ -266,6 +274,13 @@ static_assert(PCL_CELLRP_SHARP_CD == 1 ||
                    (UserRp::NDIM == 1 ||
                     sizeof(double) * (UserRp::MEQN + USER_CAPA + UserRp::NAUX) * sharp_tile_across<UserRp, 2>() * WAVE <= 65536)),
               "meqn + capa + naux: the LDS tile of sharp_kernel (sharpclaw.hpp) does not fit the 64 KB a workgroup may declare");
+#elif PCL_CELLRP_NDIM == 3
+static_assert(sizeof(double) * (UserRp::MEQN + USER_CAPA + UserRp::NAUX) * Tile3Shape<1>::PLANE <= 65536 &&
+                  sizeof(double) * (UserRp::MEQN + USER_CAPA + UserRp::NAUX) * Tile3Shape<2>::PLANE <= 65536 &&
+                  sizeof(double) * (UserRp::MEQN + USER_CAPA + UserRp::NAUX) * Tile3Shape<3>::PLANE <= 65536 &&
+                  UserRp::MEQN + USER_CAPA + UserRp::NAUX <= sweep3_tile_planes(),
+              "meqn + naux + capa: the LDS tile of sweep3_kernel (classic.hpp) does not fit the 64 KB a workgroup may declare");
+static_assert((PCL_CELLRP_FORM & 1) == 0, "no f-wave form of sweep3_kernel");
 #else
 static_assert(sizeof(double) * (UserRp::MEQN + USER_CAPA + UserRp::NAUX) * TileShape<2>::PLANE <= 65536 &&
                   sizeof(double) * (UserRp::MEQN + USER_CAPA + UserRp::NAUX) * TileShape<1>::PLANE <= 65536,
@@ -280,8 +295,9 @@ static inline const char *cellrp_ns(int math) { return math == 1 ? "fast" : math
 // ---- the rules, as functions of the spec alone: 0, or the reason in err ---------------------------------------------
 // What no program is compiled for.  given: which pointers of the call were there (body and the handle's place; the
 // transverse text; the list of naux > 0 components -- sp.aux holds it only as far as it was given and fits), and whether
-// the call asked for a SharpClaw handle (behind its first refusal that is sp.sharp()).
-struct CellrpGiven { bool body_and_out, transverse, aux_list, sharp; };
+// the call asked for a SharpClaw handle (behind its first refusal that is sp.sharp()) or for the 3-D sweeps
+// (pcl_cellrp_compile3; every other call goes on refusing ndim == 3).
+struct CellrpGiven { bool body_and_out, transverse, aux_list, sharp, dim3; };
 static inline int cellrp_spec_check(const CellrpSpec &sp, const CellrpGiven &given, std::string &err) {
     const auto no = [&err](const std::string &why) { err = why; return -1; };
     const auto n = [](int v) { return std::to_string(v); };
@@ -304,13 +320,30 @@ static inline int cellrp_spec_check(const CellrpSpec &sp, const CellrpGiven &giv
         return no("pcl_cellrp_compile_t: a transverse body belongs to the unsplit 2-D step (ndim must be 2)");
     if (sp.meqn < 1 || sp.meqn > PCL_MAX_WAVES || sp.mwaves < 1 || sp.mwaves > PCL_MAX_WAVES)
         return no("pcl_cellrp_compile: 1 <= meqn <= 8 and 1 <= mwaves <= 8");
-    if (sp.ndim < 1 || sp.ndim > 2) return no("pcl_cellrp_compile: ndim must be 1 or 2 (the classic 1-D and dimension-split 2-D sweeps)");
+    if (given.dim3 ? sp.ndim != 3 : (sp.ndim < 1 || sp.ndim > 2))
+        return no("pcl_cellrp_compile: ndim must be 1 or 2 (the classic 1-D and dimension-split 2-D sweeps; the dimension-split "
+                  "3-D sweeps are pcl_cellrp_compile3)");
     if (sp.math != PCL_MATH_EXACT && sp.math != PCL_MATH_FAST && sp.math != PCL_MATH_STRICT) return no("unknown math mode");
     // the list of aux components: an index past the solver's maux would be a read outside the aux allocation, so every
     // entry is checked here and the largest against cfg.maux when the handle is attached (cellrp_fits)
     if (sp.naux < 0) return no("pcl_cellrp_compile_aux: naux must be >= 0, got " + n(sp.naux));
     if (sp.naux > 0 && !given.aux_list) return no("null argument");
     const int capa = sp.capa() ? 1 : 0;
+    if (sp.ndim == 3) {
+        // the three passes of sweep3_kernel and nothing else: wave form, one tile of meqn + naux + capa planes
+        if (sp.form & ~(PCL_CELLRP_FORM_FWAVE | PCL_CELLRP_FORM_CAPA))
+            return no("pcl_cellrp_compile3: form = " + n(sp.form) + " has a bit that is neither "
+                      "PCL_CELLRP_FORM_FWAVE (1) nor PCL_CELLRP_FORM_CAPA (2)");
+        if (sp.fwave())
+            return no("pcl_cellrp_compile3: PCL_CELLRP_FORM_FWAVE: no f-wave body in 3-D -- sweep3_kernel has no f-wave "
+                      "instantiation, the 3-D launcher refuses an f-wave step, and there is no frozen 3-D f-wave step to check "
+                      "one against; form may carry PCL_CELLRP_FORM_CAPA only");
+        const int max3 = exact::sweep3_tile_max_planes();
+        if (sp.meqn + sp.naux + capa > max3)
+            return no("pcl_cellrp_compile3: meqn + naux + capa = " + n(sp.meqn + sp.naux + capa) + ", the tile of the 3-D sweeps "
+                      "holds at most " + n(max3) + " planes (q components, listed aux components and the capacity function) in "
+                      "the 64 KB a workgroup may declare");
+    }
     if (sp.sharp() && sp.char_decomp == 0) {
         // the tiles of sharp_kernel: q and the capacity function in the x pass, the listed aux components too in the y
         // pass (sharp1w_kernel, char_decomp = 1, has no tile)
@@ -326,7 +359,7 @@ static inline int cellrp_spec_check(const CellrpSpec &sp, const CellrpGiven &giv
     }
     // the tile of sweep_kernel: q, the listed aux components and the capacity function's plane (PAUX = MEQN + 1)
     const int max_planes = exact::sweep_tile_max_planes();
-    if (!sp.sharp() && sp.naux > 0 && sp.meqn + sp.naux > max_planes)
+    if (!sp.sharp() && sp.ndim != 3 && sp.naux > 0 && sp.meqn + sp.naux > max_planes)
         return no("pcl_cellrp_compile_aux: meqn + naux = " + n(sp.meqn + sp.naux) + ", the sweep's tile holds at most " +
                   n(max_planes) + " planes (q components and listed aux components) in a workgroup's 64 KB");
     static_assert(PCL_CELLRP_MAX_AUX >= PCL_MAX_WAVES, "pcl_cellrp_aux writes up to 8 indices");
@@ -334,7 +367,7 @@ static inline int cellrp_spec_check(const CellrpSpec &sp, const CellrpGiven &giv
     if (sp.form & ~(PCL_CELLRP_FORM_FWAVE | PCL_CELLRP_FORM_CAPA))
         return no("pcl_cellrp_compile_form: form = " + n(sp.form) + " has a bit that is neither "
                   "PCL_CELLRP_FORM_FWAVE (1) nor PCL_CELLRP_FORM_CAPA (2)");
-    if (!sp.sharp() && capa && sp.meqn + 1 + sp.naux > max_planes)
+    if (!sp.sharp() && sp.ndim != 3 && capa && sp.meqn + 1 + sp.naux > max_planes)
         return no("pcl_cellrp_compile_form: meqn + 1 + naux = " + n(sp.meqn + 1 + sp.naux) + ", the sweep's tile holds "
                   "at most " + n(max_planes) + " planes (q components, the capacity function and listed aux "
                   "components) in a workgroup's 64 KB");
@@ -383,6 +416,7 @@ static inline int cellrp_fits(const CellrpSpec &sp, const pcl_config &cfg, const
             return no(": PCL_RP_CELL: the handle was compiled for char_decomp " + n(sp.char_decomp) +
                       " and cfg.method[4] (char_decomp) is " + n(cfg.method[4]));
     }
+    // (3-D: the unsplit step, f-waves and mbc != 2 are refused for any handle where the configuration is checked, pcl_create_cellrp)
     if (!sharp_cfg && cfg.ndim == 2 && cfg.method[2] >= 0 && !sp.trans)
         return no(": PCL_RP_CELL: the unsplit step (method[2] >= 0) needs a handle compiled with a transverse body (pcl_cellrp_compile_t)");
     // the kernels in the handle were instantiated for one form (FWAVE, CAPA): the configuration must say the same
@@ -424,6 +458,10 @@ static inline std::vector<std::string> cellrp_exprs(const CellrpSpec &sp) {
         auto sk = [&](int ixy) { return "&" + ns + "sharp_kernel<" + rp + n(ixy) + ", " + capa + ", " + n(sp.lim_type) + ", " + n(sp.mbc()) + ">"; };
         if (sp.ndim == 1) return {sk(1)};
         return {sk(1), sk(2)};
+    }
+    if (sp.ndim == 3) {     // x, y, z
+        auto k3 = [&](int dir) { return "&" + ns + "sweep3_kernel<" + rp + n(dir) + ", " + capa + ">"; };
+        return {k3(1), k3(2), k3(3)};
     }
     auto k = [&](int ixy, bool dim1) { return "&" + ns + "sweep_kernel<" + rp + n(ixy) + ", " + capa + ", " + fw + ", " + (dim1 ? "true" : "false") + ">"; };
     if (sp.ndim == 1) return {k(1, true)};
@@ -491,7 +529,8 @@ struct CellrpModule {
     long id = 0;                // 0: nothing attached
     hipModule_t mod = nullptr;
     // the kernels of cellrp_exprs(spec), in its order: [0], [1] the sweeps or the SharpClaw kernels by ids - 1 (1-D and
-    // char_decomp = 1: [0] alone), [2], [3] the unsplit phases by ids - 1 of a solver with a transverse body; the rest null
+    // char_decomp = 1: [0] alone), [2], [3] the unsplit phases by ids - 1 of a solver with a transverse body; a 3-D handle:
+    // [0], [1], [2] the x, y, z sweeps by ids - 1; the rest null
     hipFunction_t fn[4] = {nullptr, nullptr, nullptr, nullptr};
     CellrpSpec spec;            // what they were compiled for
     void unload() {

@@ -1273,16 +1273,29 @@ __global__ __launch_bounds__(NWV *WAVE) void unsplit_ym_kernel(SweepArgs a, int 
 // every other cell is copied through, so the output array is complete.
 // CAPA: capacity function aux(mcapa) (step3ds.f:138-141,196-200: dtdx1d = dtdx / capa per cell, the correction-flux
 // difference of the update divided by the cell's capa); it rides in the tile as one more plane.
+// The tile's shape, for the kernel, its launchers (kernels.hip) and the plane limit of a user-written solver (cellrp.hpp).
+// DIR 1 (along i): 4 rows x 244 cells, each wavefront walks the 4 strips of its row: 240 updated cells =
+// 15 whole lines per row, like the 2-D x pass.  DIR 2, 3: 64 cells along x 16 columns, one strip per column.
+template <int DIR> struct Tile3Shape {
+    static constexpr int NSTRIP = DIR == 1 ? 4 : 1;                 // strips along the sweep per tile
+    static constexpr int ADV = NSTRIP * STRIP, ALONG = ADV + 2 * HALO;
+    static constexpr int AC = DIR == 1 ? 4 : 16;                    // slices across
+    static constexpr int PLANE = DIR == 1 ? AC * ALONG : ALONG * (AC + 1);   // doubles per component
+    static constexpr int UNITS = NSTRIP * AC / 4;                   // strips per wavefront
+};
+// planes (q components, staged aux components, the capacity function) the static LDS tile of sweep3_kernel holds in the
+// 64 KB a workgroup may declare, for all three directions: the DIR 2 / 3 tile with its pitch of AC + 1 decides
+constexpr int sweep3_tile_planes() {
+    constexpr int PLANE = Tile3Shape<1>::PLANE > Tile3Shape<2>::PLANE ? Tile3Shape<1>::PLANE : Tile3Shape<2>::PLANE;
+    static_assert(Tile3Shape<3>::PLANE == Tile3Shape<2>::PLANE, "the y and z sweeps share a tile shape");
+    return 65536 / ((int)sizeof(double) * PLANE);
+}
 template <class RP, int DIR, bool CAPA = false>
 __global__ __launch_bounds__(256) void sweep3_kernel(SweepArgs a, int ntiles_ac, int ntiles_al) {
     constexpr int MEQN = RP::MEQN, NAUX = RP::NAUX, NP = MEQN + NAUX + (CAPA ? 1 : 0);
-    // DIR 1 (along i): 4 rows x 244 cells, each wavefront walks the 4 strips of its row: 240 updated cells =
-    // 15 whole lines per row, like the 2-D x pass.  DIR 2, 3: 64 cells along x 16 columns, one strip per column.
-    constexpr int NSTRIP = DIR == 1 ? 4 : 1;
-    constexpr int ADV = NSTRIP * STRIP, ALONG = ADV + 2 * HALO;
-    constexpr int AC = DIR == 1 ? 4 : 16;
-    constexpr int PLANE = DIR == 1 ? AC * ALONG : ALONG * (AC + 1);
-    constexpr int UNITS = NSTRIP * AC / 4;
+    using T = Tile3Shape<DIR>;
+    constexpr int ADV = T::ADV, ALONG = T::ALONG, AC = T::AC, PLANE = T::PLANE, UNITS = T::UNITS;
+    static_assert(NP <= sweep3_tile_planes(), "meqn + naux + capa: the tile does not fit the 64 KB a workgroup may declare");
     __shared__ double tile[NP * PLANE];
     auto at = [](int m, int al, int ac) { return m * PLANE + (DIR == 1 ? ac * ALONG + al : al * (AC + 1) + ac); };
 

@@ -220,14 +220,45 @@ int launch_step2ds(const SweepLaunch &l, std::string &err) {
     return rc != RP_NONE ? rc : not_built(err, "step2ds kernel: no instantiation for this Riemann solver");
 }
 
+// The grid of sweep3_kernel<., DIR, .> over l.a, DIR = l.ids: the same for the built-in solver and one compiled at run time
+namespace {
+struct Sweep3Grid { int ntiles_ac, ntiles_al; };
+Sweep3Grid sweep3_grid(const SweepLaunch &l) {
+    const SweepArgs &a = l.a;
+    const int n_ac = l.ids == 1 ? a.n_ac : a.n_ac + (LINE - a.mbc);  // y, z: columns counted from the line boundary
+    const int ac = l.ids == 1 ? Tile3Shape<1>::AC : Tile3Shape<2>::AC, adv = l.ids == 1 ? Tile3Shape<1>::ADV : Tile3Shape<2>::ADV;
+    static_assert(Tile3Shape<3>::AC == Tile3Shape<2>::AC && Tile3Shape<3>::ADV == Tile3Shape<2>::ADV, "y and z: one tile shape");
+    return {(n_ac + ac - 1) / ac, (a.m_al + adv - 1) / adv};
+}
+
+// A user-written Riemann solver (cellrp.hpp) in 3-D: l.user_fn is sweep3_kernel<UserRp, l.ids, CAPA> of a module compiled at
+// run time from the text of classic.hpp, so the kernel's parameters and grid are those of the built-in launch below.
+int launch_sweep3_user(const SweepLaunch &l, std::string &err) {
+    if (!l.user_fn) { err = "user-written Riemann solver: no compiled solver is attached (pcl_cellrp_attach)"; return PCL_ESTATE; }
+    if (l.user.sharp()) { err = "user-written Riemann solver: the attached solver was compiled for SharpClaw and holds no classic sweep"; return PCL_EINVAL; }
+    if (l.user.ndim != 3) { err = "user-written Riemann solver: the attached solver was not compiled for the 3-D sweeps (pcl_cellrp_compile3)"; return PCL_EINVAL; }
+    if (l.ids < 1 || l.ids > 3) { err = "3-D sweep: direction must be 1, 2 or 3"; return PCL_EINVAL; }
+    if (l.a.src_id != 0) { err = "user-written Riemann solver: no fused source"; return PCL_EINVAL; }
+    if (l.a.mbc != HALO) { err = "3-D sweep: mbc = 2"; return PCL_EINVAL; }
+    if (int rc = user_form_check(l, err)) return rc;
+    const Sweep3Grid g = sweep3_grid(l);
+    SweepArgs a = l.a;
+    int ntiles_ac = g.ntiles_ac, ntiles_al = g.ntiles_al;
+    void *params[] = {&a, &ntiles_ac, &ntiles_al};
+    hipError_t e = hipModuleLaunchKernel(l.user_fn, (unsigned)ntiles_ac * (unsigned)ntiles_al, (unsigned)a.n_b, 1, 256, 1, 1, 0,
+                                         l.stream, params, nullptr);
+    return e == hipSuccess ? PCL_OK : hip_fail(err, "sweep3 launch (user-written Riemann solver)", e);
+}
+}  // namespace
+
 // 3-D dimension-split sweep along direction l.ids (classic.hpp: sweep3_kernel)
 int launch_sweep3(const SweepLaunch &l, std::string &err) {
     const SweepArgs &a = l.a;
+    if (l.rp == PCL_RP_CELL) return launch_sweep3_user(l, err);
     if (l.fwave) { err = "fwave: no 3-D f-wave Riemann solver is built in"; return PCL_EINVAL; }
     if (l.rp != VcAcoustics3D::ID) { err = "Riemann solver id is not a 3-D solver"; return PCL_EINVAL; }
-    const int n_ac = l.ids == 1 ? a.n_ac : a.n_ac + (LINE - a.mbc);  // y, z: columns counted from the line boundary
-    const int ac = l.ids == 1 ? 4 : 16, adv = l.ids == 1 ? 4 * STRIP : STRIP;   // tile shape, classic.hpp
-    const int ntiles_ac = (n_ac + ac - 1) / ac, ntiles_al = (a.m_al + adv - 1) / adv;
+    const Sweep3Grid g = sweep3_grid(l);
+    const int ntiles_ac = g.ntiles_ac, ntiles_al = g.ntiles_al;
     const dim3 grid((unsigned)ntiles_ac * (unsigned)ntiles_al, (unsigned)a.n_b);
     if (a.mcapa > 0) {      // capacity function (step3ds.f:138-141,196-200)
         if (l.ids == 1) hipLaunchKernelGGL((sweep3_kernel<VcAcoustics3D, 1, true>), grid, dim3(256), 0, l.stream, a, ntiles_ac, ntiles_al);
@@ -303,6 +334,8 @@ int sweep_tile_max_planes() {
     constexpr int PLANE = TileShape<1>::PLANE > TileShape<2>::PLANE ? TileShape<1>::PLANE : TileShape<2>::PLANE;
     return 65536 / ((int)sizeof(double) * PLANE);
 }
+// the same for the 3-D sweeps (sweep3_kernel: Tile3Shape<1..3>::PLANE against 64 KB, classic.hpp): meqn + naux + capa
+int sweep3_tile_max_planes() { return sweep3_tile_planes(); }
 // the same for the SharpClaw kernels of a user-written Riemann solver: sharp_kernel's tile is static LDS of TA * 64 doubles
 // per plane, TA = sharp_tile_across (16; 8 in the y pass from six aux components on).  The y pass (ixy 2) stages meqn + capa
 // + naux planes, the x pass (ixy 1; the 1-D pass too) meqn + capa: it reads aux from global memory.

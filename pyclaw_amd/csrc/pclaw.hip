@@ -389,7 +389,7 @@ SweepLaunch make_launch(const pcl_solver *s, const SweepArgs &a, int ndim, int i
     l.ids = ids;
     l.fwave = s->cfg.fwave;
     l.stream = stream;
-    if (l.rp == PCL_RP_CELL && ndim <= 2) user_launch_fields(l, s, ids);
+    if (l.rp == PCL_RP_CELL) user_launch_fields(l, s, ids);      // (3-D: ids 1..3, the three sweeps of a 3-D handle)
     return l;
 }
 
@@ -517,6 +517,9 @@ int do_sweep3(pcl_solver *s, const double *qin, double *qout, int dir, double dt
 // unsplit 3-D step (step3.f): for x, y, z in turn, every slice's pieces applied in the reference's order to t1
 // (march3p_kernel, classic3.hpp).  All three directions read the same qold = q.
 int do_unsplit3(pcl_solver *s, double dt) {
+    if (s->cfg.rp == PCL_RP_CELL)
+        return fail(PCL_EINVAL, "the unsplit 3-D step needs rpt3 and rptt3 solvers: a user-written Riemann solver (PCL_RP_CELL) has "
+                                "the dimension-split 3-D step only");
     const int m3 = s->cfg.method[2] / 10, m4 = s->cfg.method[2] - 10 * m3;
     if (m3 < 0 || m3 > 2 || m4 < 0 || m4 > 2 || (m4 > 0 && m3 == 0))
         return fail(PCL_EINVAL, "3-D order_trans must be 0, 10, 11, 20, 21 or 22 (flux3.f:46-73)");
@@ -698,7 +701,7 @@ int check_device() {
 extern "C" {
 
 const char *pcl_last_error(void) { return g_err.c_str(); }
-int pcl_version(void) { return 110; }
+int pcl_version(void) { return 111; }
 int pcl_device_count(void) {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess) return 0;
@@ -715,8 +718,9 @@ int pcl_rp_info(int rp, int info[10]) {
 // pcl_create in two halves, so that pcl_create_cellrp can put what the handle must be able to do between them.
 // create_check: every test of the configuration, host-only.  cell_handle: the caller knows the handle of a PCL_RP_CELL
 // solver and checks against it what only the handle can serve (the unsplit step, f-waves, a capacity function:
-// cellrp_fits); pcl_create cannot know it and refuses all three.
-static int create_check(const pcl_config *cfg, bool cell_handle) {
+// cellrp_fits); pcl_create cannot know it and refuses all three.  handle_ndim: what that handle was compiled for -- a 3-D
+// configuration needs a 3-D handle (pcl_cellrp_compile3), which pcl_create cannot know either.
+static int create_check(const pcl_config *cfg, bool cell_handle, int handle_ndim = 0) {
     if (getenv("PCL_TRACE_ABORT")) {   // diagnostics: C backtrace on abort()
         signal(SIGABRT, [](int) {
             void *bt[64];
@@ -763,7 +767,18 @@ static int create_check(const pcl_config *cfg, bool cell_handle) {
         // (SharpClaw: with a handle compiled for it, pcl_cellrp_compile_sharp -- cellrp_fits)
         if (cfg->kind != PCL_KIND_CLASSIC && !cell_handle)
             return fail(PCL_EINVAL, "PCL_RP_CELL: a user-written Riemann solver runs in the classic sweeps only, not under SharpClaw");
-        if (cfg->ndim == 3) return fail(PCL_EINVAL, "PCL_RP_CELL: a user-written Riemann solver is 1-D or 2-D (ndim == 3)");
+        if (cfg->ndim == 3 && !cell_handle)
+            return fail(PCL_EINVAL, "PCL_RP_CELL: a user-written Riemann solver is 1-D or 2-D (ndim == 3) unless it was compiled for "
+                                    "the 3-D sweeps (pcl_cellrp_compile3) and is given with the configuration (pcl_create_cellrp)");
+        if (cfg->ndim == 3 && handle_ndim != 3)
+            return fail(PCL_EINVAL, "PCL_RP_CELL: the handle holds the 1-D or 2-D kernels; a 3-D configuration (ndim == 3) needs one "
+                                    "compiled for the 3-D sweeps (pcl_cellrp_compile3)");
+        if (cfg->ndim == 3 && cfg->method[2] >= 0)
+            return fail(PCL_EINVAL, "PCL_RP_CELL: the unsplit 3-D step (method[2] >= 0, step3) needs rpt3 and rptt3 bodies, and "
+                                    "march3p_kernel is not compiled around a user-written solver: in 3-D it serves the "
+                                    "dimension-split step only (method[2] < 0)");
+        if (cfg->ndim == 3 && cfg->fwave)
+            return fail(PCL_EINVAL, "PCL_RP_CELL: cfg.fwave = 1: no f-waves in 3-D (sweep3_kernel has no f-wave form)");
         if (cfg->fwave && !cell_handle)
             return fail(PCL_EINVAL, "PCL_RP_CELL: a user-written Riemann solver returns waves, not f-waves (cfg.fwave must be 0)");
         if (cfg->method[5] != 0 && !cell_handle)
@@ -803,7 +818,8 @@ static int create_check(const pcl_config *cfg, bool cell_handle) {
     }
     if (cfg->ndim == 3) {
         if (cfg->kind != PCL_KIND_CLASSIC) return fail(PCL_EINVAL, "3-D: classic solver only (the reference has no 3-D SharpClaw)");
-        if (cfg->maux < 2) return fail(PCL_EINVAL, "rpn3_vc_acoustics needs aux(1)=impedance, aux(2)=sound speed");
+        // (the built-in solver's; a user-written one lists what it reads, checked against maux by cellrp_fits)
+        if (cfg->rp != PCL_RP_CELL && cfg->maux < 2) return fail(PCL_EINVAL, "rpn3_vc_acoustics needs aux(1)=impedance, aux(2)=sound speed");
         if (cfg->method[5] != 0 && cfg->method[2] >= 0)
             return fail(PCL_EINVAL, "3-D: the capacity function is built for the dimension-split step (step3ds); the unsplit step3 "
                                     "with mcapa is not");
@@ -1835,6 +1851,17 @@ int pcl_cellrp_compile_sharp(const char *body, const char *preamble, int meqn, i
     return cellrp_compile(sp, {body, nullptr, preamble}, given, out, code_size);
 }
 
+// The three passes of the dimension-split 3-D step (sweep3_kernel, DIR 1..3) around the body, and nothing else
+int pcl_cellrp_compile3(const char *body, const char *preamble, int meqn, int mwaves, int math, const int *aux_index, int naux,
+                        int form, pcl_cellrp **out, long *code_size) {
+    pcl::CellrpSpec sp = cellrp_spec(meqn, mwaves, 3, math, aux_index, naux);
+    sp.form = form;
+    pcl::CellrpGiven given = {};
+    given.aux_list = aux_index != nullptr;
+    given.dim3 = true;
+    return cellrp_compile(sp, {body, nullptr, preamble}, given, out, code_size);
+}
+
 int pcl_cellrp_release(pcl_cellrp *r) {
     if (!r) return PCL_OK;
     CellfnCache &c = cellfn_cache();
@@ -1937,7 +1964,13 @@ int pcl_create_cellrp(const pcl_config *cfg, pcl_cellrp *r, pcl_solver **out) {
     if (!cfg || !out) return fail(PCL_EINVAL, "null argument");
     *out = nullptr;
     if (cfg->rp != PCL_RP_CELL) return fail(PCL_EINVAL, "pcl_create_cellrp: cfg.rp must be PCL_RP_CELL");
-    if (int rc = create_check(cfg, true)) return rc;
+    int handle_ndim = cfg->ndim;        // (not a live handle: refused as such below, behind the configuration's own refusals)
+    {
+        CellfnCache &c = cellfn_cache();
+        std::lock_guard<std::mutex> lock(c.mu);
+        if (r && c.rp_live.count(r)) handle_ndim = r->spec.ndim;
+    }
+    if (int rc = create_check(cfg, true, handle_ndim)) return rc;
     {
         pcl::CellrpSpec sp;
         std::string err;

@@ -177,7 +177,7 @@ constexpr int TILE_OWN_C = 60, TILE_OWN_R = 12;
 // which kernels the code object holds.  A default-constructed one is "nothing attached".
 #define PCL_CELLRP_MAX_AUX 8       // what pcl_cellrp_aux writes at most; the tile limits are tighter (cellrp_spec_check)
 struct CellrpSpec {
-    int meqn = 0, mwaves = 0, ndim = 0, math = 0;
+    int meqn = 0, mwaves = 0, ndim = 0, math = 0;   // ndim 3: the three sweep3_kernel passes and nothing else (pcl_cellrp_compile3)
     int naux = 0, aux[PCL_CELLRP_MAX_AUX] = {0};    // the aux components the body reads, in the body's order
     int trans = 0;                                  // 1: a transverse body, the code object holds the unsplit kernels too
     int form = 0;                                   // PCL_CELLRP_FORM_* bits
@@ -191,16 +191,16 @@ struct CellrpSpec {
 
 struct SweepLaunch {
     SweepArgs a;
-    int ndim;   // 1 or 2
+    int ndim;   // 1, 2 or 3
     int rp;     // PCL_RP_*
-    int ids;    // 1 = x pass (or the 1-D step), 2 = y pass
+    int ids;    // 1 = x pass (or the 1-D step), 2 = y pass, 3 = z pass (launch_sweep3)
     int fwave;
     int lim_type;  // SharpClaw reconstruction (2 PyWENO weno5, 3 legacy weno5)
     int char_decomp = 0;   // SharpClaw: 1 = wave-based reconstruction (1-D: tvd2_wave / weno5_wave)
     hipStream_t stream;
     // rp == PCL_RP_CELL (a user-written Riemann solver, cellrp.hpp): user_fn is the kernel of this pass in the module the solver
-    // handle has loaded (null: nothing attached) and user what that module was compiled for.  launch_sweep, launch_unsplit and
-    // launch_sharp refuse a launch that says otherwise and launch user_fn over the grids of the built-in solvers
+    // handle has loaded (null: nothing attached) and user what that module was compiled for.  launch_sweep, launch_sweep3,
+    // launch_unsplit and launch_sharp refuse a launch that says otherwise and launch user_fn over the grids of the built-in solvers
     hipFunction_t user_fn = nullptr;
     CellrpSpec user;
     // one-kernel step only (classic_fused.hpp, quiet tiles): this launch's per-tile words and per-wavefront Courant
@@ -259,6 +259,7 @@ struct InteriorBox { bool any = false; int box[4] = {0, 0, 0, 0}, ntiles[2] = {0
 namespace exact {
 const RpFacts *rp_facts(int rp);    // null: no built-in solver has this id (the same in every mode)
 int sweep_tile_max_planes();        // q + aux planes a sweep_kernel tile may hold (TileShape<1/2>::PLANE against 64 KB)
+int sweep3_tile_max_planes();       // q + aux + capa planes a sweep3_kernel tile may hold (Tile3Shape<1..3>::PLANE against 64 KB)
 int sharp_tile_max_planes(int ixy, int naux);   // planes a sharp_kernel tile of pass ixy may hold for a solver with naux aux components
 int launch_sweep(const SweepLaunch &l, std::string &err);
 int launch_step2ds(const SweepLaunch &l, std::string &err);   // whole dim-split 2-D step in one kernel (classic_fused.hpp)

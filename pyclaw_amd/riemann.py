@@ -6,7 +6,8 @@ The reference picks the Riemann solver when the app's f2py module is linked
 ``cparam`` common block filled from ``state.aux_global`` (src/pyclaw/state.py:142-162).
 Here a solver is named on the Solver object (``solver.rp = riemann.rp_euler_5wave_2d`` or
 the string ``'euler_5wave_2d'``); ``cparam`` lists the aux_global keys in common-block order.
-A solver of the user's own is a ``CellRiemann``: C++ text compiled at ``setup()``, outside the table of built-in solvers.
+A solver of the user's own is a ``CellRiemann`` (1-D, 2-D) or a ``CellRiemann3D``: C++ text compiled at ``setup()``,
+outside the table of built-in solvers.
 """
 import numpy as np
 
@@ -138,13 +139,16 @@ class CellRiemann(RiemannSolver):
     large from six aux components on, so the x pass then sets the limit).  A ``dq_src`` -- a ``CellDqSource`` or a
     Python callable -- runs as its own pass: nothing is fused into the stage.
 
+    The dimension-split 3-D step takes a ``CellRiemann3D`` (below); ``CellRiemann(..., ndim=3)`` is a ``ValueError``.
+
     Not served: a transverse body that needs both cells and aux, a conservation fix in the unsplit step (the sphere
-    solver's ``qcor``), 3-D, more than one block; under SharpClaw ``char_decomp`` 2 / 3, ``tfluct_solver`` and a fused
-    dq source.  The dimension-split 2-D step always runs as two passes, never as the one-kernel step, the unsplit y
+    solver's ``qcor``), the unsplit 3-D step (``rpt3`` / ``rptt3`` bodies), f-waves in 3-D, more than one block
+    (decomposed runs); under SharpClaw ``char_decomp`` 2 / 3, ``tfluct_solver`` and a fused dq source.  The dimension-split 2-D step always runs as two passes, never as the one-kernel step, the unsplit y
     phase always in its tile form (the marching y kernel stays with the built-in solvers)."""
 
     MAX_PARAMS = 8
     MAX_PLANES = 8
+    _NDIMS = (1, 2)
 
     def __init__(self, body, meqn, mwaves, ndim, params=(), preamble="", name="user", aux=(), transverse=None, fwave=False,
                  capa=False, sharpclaw=False):
@@ -152,8 +156,9 @@ class CellRiemann(RiemannSolver):
                                has_transverse=transverse is not None)
         if not 1 <= self.meqn <= 8 or not 1 <= self.mwaves <= 8:
             raise ValueError("CellRiemann: 1 <= meqn <= 8 and 1 <= mwaves <= 8, got meqn=%d mwaves=%d" % (self.meqn, self.mwaves))
-        if self.ndim not in (1, 2):
-            raise ValueError("CellRiemann: ndim must be 1 or 2 (the classic 1-D and dimension-split 2-D sweeps), got %d" % self.ndim)
+        if self.ndim not in self._NDIMS:
+            raise ValueError("CellRiemann: ndim must be 1 or 2 (the classic 1-D and dimension-split 2-D sweeps), got %d; the "
+                             "dimension-split 3-D sweeps take a CellRiemann3D" % self.ndim)
         self.sharpclaw = bool(sharpclaw)
         if self.sharpclaw and transverse is not None:
             raise ValueError("CellRiemann: sharpclaw=True with a transverse body: SharpClaw has no transverse solve, and a "
@@ -224,7 +229,10 @@ class CellRiemann(RiemannSolver):
         rp, size = ctypes.c_void_p(), ctypes.c_long(0)
         mode = {'exact': 0, 'fast': 1, 'strict': 2}[math]
         aux = (ctypes.c_int * len(self.aux))(*self.aux) if self.aux else None
-        if sharp is not None:
+        if self.ndim == 3:
+            _lib.check(_lib.lib().pcl_cellrp_compile3(self.body.encode(), self.preamble.encode(), self.meqn, self.mwaves, mode,
+                                                      aux, len(self.aux), form, ctypes.byref(rp), ctypes.byref(size)))
+        elif sharp is not None:
             _lib.check(_lib.lib().pcl_cellrp_compile_sharp(self.body.encode(), self.preamble.encode(), self.meqn, self.mwaves,
                                                            self.ndim, mode, aux, len(self.aux), form, sharp[0], sharp[1], sharp[2],
                                                            ctypes.byref(rp), ctypes.byref(size)))
@@ -285,6 +293,34 @@ class CellRiemann(RiemannSolver):
             self.release()
         except Exception:
             pass
+
+
+class CellRiemann3D(CellRiemann):
+    """A user-written normal Riemann solver (Clawpack's rpn3, one interface at a time) for the dimension-split 3-D step:
+    ``solver.rp = CellRiemann3D(body, meqn, mwaves, params)`` on ``ClawSolver3D(dim_split=True)``.  ``setup()`` compiles the
+    x, y and z passes of the library's 3-D sweep kernel around the body, which is written as for a ``CellRiemann``: it sees
+    ``ql``, ``qr``, ``p[8]``, with ``aux=(...)`` also ``auxl`` / ``auxr``, and the compile-time constant ``ixy``, here 1, 2
+    or 3; it assigns ``wave``, ``s``, ``amdq``, ``apdq``, zero on entry, and for bitwise-equal ``ql`` and ``qr`` the waves
+    and fluctuations must be zero whatever aux holds.  ``capa=True`` compiles the passes with a capacity function
+    (``state.mcapa``).  ``params`` can be reassigned between steps without a compile.
+
+    All three passes stage q, the listed aux components and the capacity function in one tile:
+    ``meqn + len(aux) + capa <= MAX_PLANES`` (7; the library derives it from its tile shapes and refuses with its own
+    figure).
+
+    Not served in 3-D, so there is no keyword for them: a transverse body (the unsplit step, ``dim_split=False``, needs
+    ``rpt3`` and ``rptt3`` solvers), f-waves and SharpClaw.  One block; ``mbc`` 2."""
+
+    MAX_PLANES = 7
+    _NDIMS = (3,)
+
+    def __init__(self, body, meqn, mwaves, params=(), preamble="", name="user", aux=(), capa=False):
+        aux = tuple(aux)
+        planes = int(meqn) + len(aux) + int(bool(capa))
+        if planes > self.MAX_PLANES:
+            raise ValueError("CellRiemann3D: meqn + len(aux) + capa = %d, the tile of the 3-D sweeps holds at most %d planes "
+                             "(q components, listed aux components and the capacity function)" % (planes, self.MAX_PLANES))
+        CellRiemann.__init__(self, body, meqn, mwaves, 3, params=params, preamble=preamble, name=name, aux=aux, capa=capa)
 
 
 def get(rp):

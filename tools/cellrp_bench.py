@@ -37,7 +37,13 @@ built-in solver held to two passes, and "user", ACOUSTICS_2D_RP in a CellRiemann
 sharp_kernel over the same tiles.  The children also time every distinct run-time compile they make: the user solver's
 SharpClaw kernels ("compile_s") and, for comparison, the same body's classic sweeps ("compile_classic_s").
 
-  python tools/cellrp_bench.py [--aux] [--unsplit] [--fwave | --capa | --sharpclaw] [--n 4096] [--steps 20] [--warmup 3] [--reps 7] [--out FILE]
+--ndim 3 measures the dimension-split 3-D step two ways on the workload of `bench.py --ndim 3` (its build3d: 3-D acoustics
+in two materials, n^3 cells, n = 512 unless --n says otherwise): "builtin", rp_vc_acoustics_3d, and "user", the same solver
+as a CellRiemann3D (problems.VC_ACOUSTICS_3D_RP, aux=(0, 1)).  Both run sweep3_kernel over the same tiles, and nothing
+here is read once per process, so the two solvers live side by side in this process and are timed in alternating
+segments of `--steps` steps, `--reps` of each per state.
+
+  python tools/cellrp_bench.py [--aux] [--unsplit] [--fwave | --capa | --sharpclaw | --ndim 3] [--n 4096] [--steps 20] [--warmup 3] [--reps 7] [--out FILE]
 """
 import argparse
 import ctypes
@@ -138,6 +144,79 @@ def child(args):
     print("CELLRP_CHILD " + json.dumps(res))
 
 
+def run3(args):
+    """--ndim 3: both solvers in this process, timed in alternating segments"""
+    import pyclaw_amd as pyclaw
+    from pyclaw_amd import _lib
+    from apps import problems
+    import bench
+    L = _lib.lib()
+    if L.pcl_device_count() < 1:
+        raise SystemExit("cellrp_bench: no HIP device (nothing here can be measured without one)")
+    n = 512 if args.n == 4096 else args.n
+    variants = VARIANTS_UNSPLIT
+    claws, compile_s = {}, None
+    for v in variants:
+        claw = bench.build3d(n, args.math)
+        if v == "user":
+            claw.solver.rp = pyclaw.CellRiemann3D(problems.VC_ACOUSTICS_3D_RP, 4, 2, aux=(0, 1), name="vc_acoustics_3d_user")
+            t0 = time.perf_counter()
+            claw.solver.rp.compile(args.math)
+            compile_s = time.perf_counter() - t0
+        claw.solver.setup(claw.solution)
+        claw.solver.dt_variable = False
+        claw.solver.dt = claw.solver.dt_initial         # bench.py's: a Courant number of 0.4 in the faster material
+        claws[v] = claw
+    q_pulse = claws["builtin"].solution.state.q.copy('F')
+    rng = np.random.default_rng(7)
+    noise = 0.01 * rng.standard_normal(q_pulse.shape[1:])     # one plane's worth, on every component
+    ms = ctypes.c_float()
+    res = {"tool": "cellrp_bench --ndim 3", "n": n, "grid": [n, n, n], "math": args.math, "steps": args.steps, "warmup": args.warmup,
+           "reps": args.reps, "what": "ms per dimension-split 3-D step (x, y, z sweeps), segments of the two solvers alternating in one process",
+           "compile_s": compile_s, "states": {}}
+
+    def spread(vals):
+        return {"median": float(np.median(vals)), "min": min(vals), "max": max(vals), "all": vals}
+    for name in ("pulse", "dense"):
+        for v in variants:
+            st = claws[v].solution.state
+            st.q[...] = q_pulse
+            if name == "dense":
+                st.q[...] += noise
+            claws[v].solver.begin_resident(claws[v].solution)
+            for _ in range(args.warmup):
+                claws[v].solver.step_hyperbolic(claws[v].solution)
+        seg = {v: [] for v in variants}
+        for r in range(args.reps):
+            for v in variants:
+                solver, solution = claws[v].solver, claws[v].solution
+                _lib.check(L.pcl_sync(solver._h))
+                _lib.check(L.pcl_timer_start(solver._h))
+                for _ in range(args.steps):
+                    solver.step_hyperbolic(solution)
+                _lib.check(L.pcl_timer_stop(solver._h, ctypes.byref(ms)))
+                seg[v].append(ms.value / args.steps)
+            print("round %d %s: builtin %.4f ms, user %.4f ms" % (r + 1, name, seg["builtin"][-1], seg["user"][-1]),
+                  file=sys.stderr, flush=True)
+        sums, cfls = set(), set()
+        for v in variants:
+            claws[v].solver.end_resident(claws[v].solution)
+            sums.add(float(np.abs(claws[v].solution.state.q).sum()))       # the two compute the same thing
+            cfls.add(claws[v].solver.cfl.get_cached_max())
+        a, b = spread(seg["builtin"]), spread(seg["user"])
+        res["states"][name] = {"builtin_ms": a, "user_ms": b, "same_result_in_every_run": len(sums) == 1 and len(cfls) == 1,
+                               "user_over_builtin": b["median"] / a["median"],
+                               "user_and_builtin_spreads_overlap": not (b["min"] > a["max"] or a["min"] > b["max"])}
+    for v in variants:
+        claws[v].solver.teardown()
+    line = json.dumps(res)
+    print(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=4096)
@@ -151,8 +230,14 @@ def main():
     ap.add_argument("--fwave", action="store_true", help="the p-system: psystem_fwave_2d against CellRiemann(fwave=True)")
     ap.add_argument("--capa", action="store_true", help="acoustics with a capacity function: the built-in two passes against CellRiemann(capa=True)")
     ap.add_argument("--sharpclaw", action="store_true", help="the SSP104 step of SharpClaw: rp_acoustics_2d against CellRiemann(sharpclaw=True)")
+    ap.add_argument("--ndim", type=int, default=2, choices=[2, 3],
+                    help="3: the dimension-split 3-D step on bench.py's 3-D grid, rp_vc_acoustics_3d against CellRiemann3D")
     ap.add_argument("--child", default=None, choices=VARIANTS + VARIANTS_UNSPLIT)
     args = ap.parse_args()
+    if args.ndim == 3:
+        if args.aux or args.unsplit or args.fwave or args.capa or args.sharpclaw:
+            raise SystemExit("cellrp_bench: --ndim 3 is a measurement of its own")
+        return run3(args)
     if (args.fwave or args.capa) and (args.aux or args.unsplit or (args.fwave and args.capa)):
         raise SystemExit("cellrp_bench: --fwave and --capa are measurements of their own (not with --aux, --unsplit or each other)")
     if args.sharpclaw and (args.aux or args.unsplit or args.fwave or args.capa):
