@@ -75,6 +75,8 @@ extern "C" {
                         /* (pcl_cellrp_compile_aux); f-waves and a capacity function through pcl_cellrp_compile_form and    */
                         /* pcl_create_cellrp; the SharpClaw stages through pcl_cellrp_compile_sharp and pcl_create_cellrp;  */
                         /* the dimension-split 3-D step through pcl_cellrp_compile3 and pcl_create_cellrp.                  */
+                        /* The dimension-split 2-D step runs as two passes unless the handle also carries the one-kernel    */
+                        /* step (pcl_cellrp_compile_onek): then in either form, chosen as for a built-in solver.            */
                         /* Not a built-in solver: pcl_rp_info refuses the id                                                */
 
 /* boundary condition types = pyclaw.BC (src/pyclaw/solver.py:17-23) */
@@ -460,6 +462,21 @@ int pcl_cellrp_compile_form(const char *body, const char *transverse, const char
                             int math, const int *aux_index, int naux, int form, pcl_cellrp **out, long *code_size);
 /* Host-only: the PCL_CELLRP_FORM_* bits a live handle was compiled with. */
 int pcl_cellrp_form(const pcl_cellrp *r, int *form);
+/* pcl_cellrp_compile_form for ndim = 2 with the ONE-KERNEL form of the dimension-split 2-D step next to the sweeps: the
+ * code object also holds step2ds_kernel (csrc/classic_fused.hpp: both sweeps on a 16 x 64 tile in LDS, q through HBM once
+ * per step) around the body, in the handle's form.  A dimension-split solver with such a handle attached chooses between
+ * the two forms of the step exactly as for a built-in solver that has the kernel: a wave-form body without an aux list
+ * and without a capacity function gets quiet tiles, tile lists, row reuse, the column shortcut, the form trials and step
+ * ahead -- all of which rest on the contract "bitwise-equal ql and qr: zero waves" alone; a body with an aux list or a
+ * capacity function the kernel over the whole block without that bookkeeping; an f-wave body the f-wave instantiation, in
+ * which no wavefront takes the shortcut.  The unsplit step of a handle with a transverse body is unchanged.
+ * Another cache entry than the same call without it (key piece "onek"), a larger code object.  PCL_EINVAL before the
+ * compiler, with the reason: meqn > 5 (the one-kernel tile holds up to 5 equations, the rule for every solver), and
+ * everything pcl_cellrp_compile_form refuses.  There is no 1-D, 3-D or SharpClaw form of this call.  Host-only. */
+int pcl_cellrp_compile_onek(const char *body, const char *transverse, const char *preamble, int meqn, int mwaves, int math,
+                            const int *aux_index, int naux, int form, pcl_cellrp **out, long *code_size);
+/* Host-only: has = 1 if a live handle carries the one-kernel step (pcl_cellrp_compile_onek), 0 for every other handle. */
+int pcl_cellrp_onek(const pcl_cellrp *r, int *has);
 /* The same body in the SHARPCLAW stages (cfg.kind = PCL_KIND_SHARPCLAW): the library compiles its SharpClaw kernels (the
  * text of csrc/sharpclaw.hpp) around the body in place of the classic sweeps -- the one reconstruction asked for and no
  * other: lim_type 1 (tvd2), 2 (WENO) or 3 (legacy WENO5) at weno_order 5, weno_order 7..17 (odd) with lim_type 2, for any

@@ -111,6 +111,9 @@ PROTOTYPES = {
     "pcl_cellrp_compile_form": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, ip, C.c_int,
                                           C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_long)]),
     "pcl_cellrp_form": (C.c_int, [C.c_void_p, ip]),
+    "pcl_cellrp_compile_onek": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_int, ip, C.c_int,
+                                          C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_long)]),
+    "pcl_cellrp_onek": (C.c_int, [C.c_void_p, ip]),
     "pcl_cellrp_compile_sharp": (C.c_int, [C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, ip, C.c_int, C.c_int,
                                            C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_long)]),
     "pcl_cellrp_sharp": (C.c_int, [C.c_void_p, ip, ip, ip]),

@@ -413,7 +413,9 @@ class ClawSolver1D(ClawSolver):
 
 class ClawSolver2D(ClawSolver):
     r"""2D classic solver (clawpack.py:412-558): dimensional splitting or unsplit with
-    transverse Riemann solves (``dim_split``, ``order_trans``)."""
+    transverse Riemann solves (``dim_split``, ``order_trans``).  The dimension-split step has two forms with the same
+    results, one kernel or two passes (``status["step_forms"]`` counts them); a user-written ``riemann.CellRiemann`` takes
+    part in that choice if it was written with ``one_kernel=True`` and runs the two passes otherwise."""
 
     no_trans = 0
     trans_inc = 1

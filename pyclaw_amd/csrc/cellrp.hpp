@@ -3,7 +3,7 @@
 // cfg.rp = PCL_RP_CELL).
 //
 // Nothing of a kernel is restated here.  The Makefile embeds the headers the kernels are written in -- sweep_args.hpp,
-// ghost_rule.hpp, rp.hpp, classic.hpp, sharpclaw.hpp, weno_tables.hpp and include/pyclaw_amd.h -- as text
+// ghost_rule.hpp, rp.hpp, classic.hpp, classic_fused.hpp, sharpclaw.hpp, weno_tables.hpp and include/pyclaw_amd.h -- as text
 // (cellrp_headers.inc), hiprtc gets them as named headers, and the program below wraps the user's body in a solver struct
 // UserRp of the shape rp.hpp documents and asks for the kernels of that struct by name expression, compiled with the flags
 // of the library's own arithmetic mode (PCL_RTC_FLAGS_*, from the Makefile).  A user solver thereby runs with the LDS
@@ -92,11 +92,24 @@
 //     sharp_kernel's tile is static LDS of TA * 64 doubles per plane, TA = sharp_tile_across (16; 8 in the y pass from six
 //     aux components on); the x pass stages meqn + capa planes, the y pass meqn + capa + naux, each within 64 KB
 //     (sharp_tile_max_planes, kernels.hip).  sharp1w_kernel declares no LDS.
+//   onek   (pcl_cellrp_compile_onek, CellRiemann(one_kernel=True); 2-D classic handles only)
+//     The dimension-split 2-D step as ONE kernel around the body, next to everything the same call without it compiles:
+//     -DPCL_CELLRP_ONEK=1 makes the text include classic_fused.hpp (which includes classic.hpp) and adds one name
+//     expression, step2ds_kernel<UserRp, FWAVE, false, CAPA>, behind the others (CellrpModule::onek).  The host then
+//     treats the solver like a built-in one with such an instantiation (pclaw.hip: solver_facts): quiet tiles, tile lists,
+//     row reuse, the y-column shortcut, the form trials and step ahead for a wave-form body without aux and capa -- all of
+//     which rest on the contract above and on nothing else --, the whole block without bookkeeping with an aux list or a
+//     capacity function, the FWAVE instantiation (no shortcut, so no quiet tile) for an f-wave body.  launch_step2ds
+//     launches it over the grid and with the parameters of the built-in instantiations.  The hand-over and tile-list kernel
+//     is not compiled into the module (classic_fused.hpp keeps it behind __HIPCC_RTC__): the library's own serves every
+//     solver.  Key: "onek,".  Limits: ndim 2, no SharpClaw handle, meqn <= ONEK_MAX_MEQN (5, the rule of fused_step_ok);
+//     the two-pass tile's meqn + capa + naux <= 8 lies inside the one-kernel tile's ONEK_MAX_PLANES (10).  A body heavy
+//     enough to spill registers in this kernel is still correct; the form trials then keep the two passes.
 // Every plane limit is refused on the host with the sum and restated by a static_assert at the end of the text.
 //
 // NOT SERVED under SharpClaw: a fused dq source (a source term runs as its own pass), char_decomp 2 / 3, tfluct, a
 // transverse body.  Not served in any form: HAS_QCOR (the sphere solver's conservation fix), a transverse body with both
-// cells and aux, the marching y phase, the one-kernel step, the unsplit 3-D step (rpt3 / rptt3 bodies, march3p_kernel),
+// cells and aux, the marching y phase, the unsplit 3-D step (rpt3 / rptt3 bodies, march3p_kernel),
 // f-waves in 3-D, more than one block (decomposed runs).
 #pragma once
 #include "cellfn.hpp"
@@ -105,13 +118,14 @@
 #include "cellrp_headers.inc"
 
 #define PCL_CELLRP_MAX_PARAMS 8
+#define PCL_CELLRP_MAX_KERNELS 5    // what cellrp_exprs names at most: two sweeps, two unsplit phases, the one-kernel step
 
 struct pcl_cellrp {
     long id = 0;                // never reused, from the counter of the cell functions
     int refs = 0;
     std::string key;
     std::vector<char> code;     // the code object
-    std::string sym[4];         // lowered names of cellrp_exprs(spec), in its order; the rest empty
+    std::string sym[PCL_CELLRP_MAX_KERNELS];    // lowered names of cellrp_exprs(spec), in its order; the rest empty
     pcl::CellrpSpec spec;
 };
 
@@ -126,6 +140,8 @@ struct CellrpTexts {
 static const char *const kCellrpHead = R"PCLSRC(
 #if PCL_CELLRP_SHARP
 #include "sharpclaw.hpp"
+#elif PCL_CELLRP_ONEK
+#include "classic_fused.hpp"
 #else
 #include "classic.hpp"
 #endif
@@ -285,6 +301,11 @@ static_assert((PCL_CELLRP_FORM & 1) == 0, "no f-wave form of sweep3_kernel");
 static_assert(sizeof(double) * (UserRp::MEQN + USER_CAPA + UserRp::NAUX) * TileShape<2>::PLANE <= 65536 &&
                   sizeof(double) * (UserRp::MEQN + USER_CAPA + UserRp::NAUX) * TileShape<1>::PLANE <= 65536,
               "meqn + capa + naux: the LDS tile of sweep_kernel (classic.hpp) does not fit a workgroup's 64 KB");
+#if PCL_CELLRP_ONEK
+static_assert(UserRp::NDIM == 2 && UserRp::MEQN <= ONEK_MAX_MEQN && UserRp::MEQN + USER_CAPA + UserRp::NAUX <= ONEK_MAX_PLANES &&
+                  sizeof(double) * (UserRp::MEQN + USER_CAPA + UserRp::NAUX) * F_ROWS * F_COLS <= 80 * 1024,
+              "meqn, meqn + capa + naux: the LDS tile of step2ds_kernel (classic_fused.hpp) holds up to 5 equations and 10 planes");
+#endif
 #endif
 }  // namespace PCL_NS
 }  // namespace pcl
@@ -298,6 +319,18 @@ static inline const char *cellrp_ns(int math) { return math == 1 ? "fast" : math
 // the call asked for a SharpClaw handle (behind its first refusal that is sp.sharp()) or for the 3-D sweeps
 // (pcl_cellrp_compile3; every other call goes on refusing ndim == 3).
 struct CellrpGiven { bool body_and_out, transverse, aux_list, sharp, dim3; };
+// the reason a handle with the one-kernel step (spec.onek) cannot be compiled for this spec, or null.  Today's only caller
+// that sets spec.onek, pcl_cellrp_compile_onek, fills ndim = 2 and no SharpClaw field, so of these only meqn > 5 can be
+// reached through the C interface; the other three state the rule for the spec and guard a later entry point that fills
+// it otherwise.  The plane limit needs no refusal: the sweep tile's limit, which every 2-D handle meets, lies inside the
+// one-kernel tile's ONEK_MAX_PLANES (a static_assert next to sweep_tile_max_planes, kernels.hip).
+static inline const char *cellrp_onek_refusal(const CellrpSpec &sp, bool dim3) {
+    if (sp.sharp()) return "a SharpClaw handle holds the SharpClaw kernels alone: the one-kernel step is a classic step";
+    if (dim3 || sp.ndim == 3) return "a 3-D handle holds the three sweeps alone: the one-kernel step is the dimension-split 2-D step";
+    if (sp.ndim != 2) return "the one-kernel step is the dimension-split 2-D step (ndim must be 2)";
+    if (sp.meqn > ONEK_MAX_MEQN) return "meqn > 5: the tile of the one-kernel step holds up to 5 equations";
+    return nullptr;
+}
 static inline int cellrp_spec_check(const CellrpSpec &sp, const CellrpGiven &given, std::string &err) {
     const auto no = [&err](const std::string &why) { err = why; return -1; };
     const auto n = [](int v) { return std::to_string(v); };
@@ -316,6 +349,8 @@ static inline int cellrp_spec_check(const CellrpSpec &sp, const CellrpGiven &giv
                       "(weno5_wave), weno_order 5, no f-wave body");
     }
     if (!given.body_and_out) return no("null argument");
+    if (sp.onek)
+        if (const char *why = cellrp_onek_refusal(sp, given.dim3)) return no(std::string("pcl_cellrp_compile_onek: ") + why);
     if (given.transverse && sp.ndim != 2)
         return no("pcl_cellrp_compile_t: a transverse body belongs to the unsplit 2-D step (ndim must be 2)");
     if (sp.meqn < 1 || sp.meqn > PCL_MAX_WAVES || sp.mwaves < 1 || sp.mwaves > PCL_MAX_WAVES)
@@ -441,6 +476,7 @@ static inline std::string cellrp_key(const CellrpSpec &sp, const CellrpTexts &t)
     for (int i = 0; i < sp.naux; i++) k += (i ? "." : "aux") + n(sp.aux[i]);
     if (sp.naux > 0) k += ",";
     if (sp.form) k += "form" + n(sp.form) + ",";
+    if (sp.onek) k += "onek,";
     if (sp.trans) { k += n((int)strlen(t.transverse)) + ":"; k += t.transverse; }
     k += n((int)strlen(t.preamble)) + ":";
     k += t.preamble;
@@ -448,7 +484,8 @@ static inline std::string cellrp_key(const CellrpSpec &sp, const CellrpTexts &t)
     return k;
 }
 
-// the kernels of a UserRp compiled for sp, as hiprtc name expressions (at most 4)
+// the kernels of a UserRp compiled for sp, as hiprtc name expressions (at most PCL_CELLRP_MAX_KERNELS); with sp.onek the
+// one-kernel step comes last, behind the expressions of the same spec without it
 static inline std::vector<std::string> cellrp_exprs(const CellrpSpec &sp) {
     const auto n = [](int v) { return std::to_string(v); };
     const std::string ns = std::string("pcl::") + cellrp_ns(sp.math) + "::", rp = ns + "UserRp, ";
@@ -465,14 +502,19 @@ static inline std::vector<std::string> cellrp_exprs(const CellrpSpec &sp) {
     }
     auto k = [&](int ixy, bool dim1) { return "&" + ns + "sweep_kernel<" + rp + n(ixy) + ", " + capa + ", " + fw + ", " + (dim1 ? "true" : "false") + ">"; };
     if (sp.ndim == 1) return {k(1, true)};
-    if (!sp.trans) return {k(1, false), k(2, false)};
-    const std::string u = n(sp.slices());
-    return {k(1, false), k(2, false), "&" + ns + "unsplit_x_kernel<" + rp + fw + ", " + u + ", " + capa + ">",
-            "&" + ns + "unsplit_y_kernel<" + rp + fw + ", " + u + ", " + capa + ", false>"};
+    std::vector<std::string> e = {k(1, false), k(2, false)};
+    if (sp.trans) {
+        const std::string u = n(sp.slices());
+        e.push_back("&" + ns + "unsplit_x_kernel<" + rp + fw + ", " + u + ", " + capa + ">");
+        e.push_back("&" + ns + "unsplit_y_kernel<" + rp + fw + ", " + u + ", " + capa + ", false>");
+    }
+    if (sp.onek) e.push_back("&" + ns + "step2ds_kernel<" + rp + fw + ", false, " + capa + ">");
+    return e;
 }
 
 // hiprtc compile of the kernels of sp around the texts.  0 = ok, else err holds the log
-static inline int cellrp_build(const CellrpSpec &sp, const CellrpTexts &t, std::vector<char> &code, std::string (&sym)[4], std::string &err) {
+static inline int cellrp_build(const CellrpSpec &sp, const CellrpTexts &t, std::vector<char> &code,
+                               std::string (&sym)[PCL_CELLRP_MAX_KERNELS], std::string &err) {
     const auto n = [](int v) { return std::to_string(v); };
     HiprtcJob job;
     std::string &src = job.src;
@@ -512,7 +554,8 @@ static inline int cellrp_build(const CellrpSpec &sp, const CellrpTexts &t, std::
     job.opts.push_back("--offload-arch=" PCL_ARCH);
     const std::pair<const char *, int> defs[] = {{"MEQN", sp.meqn},        {"MWAVES", sp.mwaves}, {"NDIM", sp.ndim},
                                                  {"NAUX", sp.naux},        {"USLICES", sp.slices()}, {"FORM", sp.form},
-                                                 {"SHARP", sp.sharp()},    {"SHARP_CD", sp.char_decomp}};
+                                                 {"SHARP", sp.sharp()},    {"SHARP_CD", sp.char_decomp},
+                                                 {"ONEK", sp.onek}};
     for (const auto &d : defs) job.opts.push_back(std::string("-DPCL_CELLRP_") + d.first + "=" + n(d.second));
     job.what = "Riemann solver body";
     static int seq = 0;
@@ -532,6 +575,8 @@ struct CellrpModule {
     // char_decomp = 1: [0] alone), [2], [3] the unsplit phases by ids - 1 of a solver with a transverse body; a 3-D handle:
     // [0], [1], [2] the x, y, z sweeps by ids - 1; the rest null
     hipFunction_t fn[4] = {nullptr, nullptr, nullptr, nullptr};
+    // step2ds_kernel<UserRp, FWAVE, false, CAPA> of a handle compiled with spec.onek (the last of cellrp_exprs); else null
+    hipFunction_t onek = nullptr;
     CellrpSpec spec;            // what they were compiled for
     void unload() {
         if (mod) (void)hipModuleUnload(mod);

@@ -86,6 +86,9 @@ static_assert(F_WAVES == 4, "one quiet byte per wavefront in a 32-bit word");
 // 1024 tiles and issues at most four: the maxima of its 16 wavefronts meet in LDS behind the barrier the prefix needs
 // anyway, one thread issues the max of each word, and none when it is 0 (the same word: an integer max of the same set
 // of patterns, in any grouping).
+// Not part of the run-time program of a user-written Riemann solver (cellrp.hpp: spec.onek): the library's own copy serves
+// every solver, so the module of such a solver holds step2ds_kernel alone.
+#ifndef __HIPCC_RTC__
 constexpr int TL_THREADS = 1024, TL_WAVES = TL_THREADS / WAVE;
 __global__ __launch_bounds__(TL_THREADS) void handover_list_kernel(unsigned long long *cfl, unsigned long long *host,
                                                                    unsigned long long seq, int ntx, int nty, int mbc,
@@ -181,6 +184,7 @@ __global__ __launch_bounds__(TL_THREADS) void handover_list_kernel(unsigned long
         list[c ? ntx * nty - 1 - i : i] = t;
     }
 }
+#endif  // !__HIPCC_RTC__
 
 // The ring check of a class-Q tile: its owned interior cells all compare equal to one state S (the
 // launch before found the whole window uniform and left them as they were), so the window is uniform again exactly

@@ -165,29 +165,27 @@ int launch_sweep(const SweepLaunch &l, std::string &err) {
 // a.src_id of the step.  The host (pclaw.hip: fused_step_ok) only sends what the kernel covers.
 namespace {
 static_assert(F_OWN_C == TILE_OWN_C && F_OWN_R == TILE_OWN_R, "the host counts tiles with TILE_OWN_* (sweep_args.hpp)");
-template <class RP> int launch_step2ds_t(const SweepLaunch &l, std::string &err) {
+// What a one-kernel launch asks of l whatever the solver, built in or compiled at run time (naux: the aux components its
+// normal solver reads), and the grid: ntx x nty tiles, nblocks workgroups (0: the tile subset is empty, nothing to launch).
+struct Step2dsGrid { int ntx, nty; unsigned nblocks; };
+int step2ds_grid(const SweepLaunch &l, int naux, Step2dsGrid &g, std::string &err) {
     const SweepArgs &a = l.a;
-    constexpr bool FW = IsFwave<RP>::value;
-    if ((l.fwave != 0) != FW) { err = "solver.fwave does not match the Riemann solver"; return PCL_EINVAL; }
     if (a.mbc != HALO) { err = "step2ds kernel: mbc = 2"; return PCL_EINVAL; }
     const bool capa = a.mcapa > 0;
-    if ((capa || RP::NAUX > 0) && !a.aux) { err = "step2ds kernel: this solver reads aux arrays and there are none"; return PCL_EINVAL; }
+    if ((capa || naux > 0) && !a.aux) { err = "step2ds kernel: this solver reads aux arrays and there are none"; return PCL_EINVAL; }
     // quiet tiles: the bookkeeping of the aux-free instantiations without a capacity function only (classic_fused.hpp)
-    if ((capa || RP::NAUX > 0) && (l.tq_out || l.tq_list)) { err = "step2ds kernel: no quiet-tile bookkeeping with aux arrays"; return PCL_EINVAL; }
-    const int ntx = (a.mx + F_OWN_C - 1) / F_OWN_C, nty = (a.my + F_OWN_R - 1) / F_OWN_R;
-    unsigned nblocks = (unsigned)ntx * (unsigned)nty;
+    if ((capa || naux > 0) && (l.tq_out || l.tq_list)) { err = "step2ds kernel: no quiet-tile bookkeeping with aux arrays"; return PCL_EINVAL; }
+    g.ntx = (a.mx + F_OWN_C - 1) / F_OWN_C;
+    g.nty = (a.my + F_OWN_R - 1) / F_OWN_R;
+    g.nblocks = (unsigned)g.ntx * (unsigned)g.nty;
     if (a.sub != 0) {
-        if (a.box[0] < 0 || a.box[1] > nty || a.box[2] < 0 || a.box[3] > ntx || a.box[0] >= a.box[1] || a.box[2] >= a.box[3]) {
+        if (a.box[0] < 0 || a.box[1] > g.nty || a.box[2] < 0 || a.box[3] > g.ntx || a.box[0] >= a.box[1] || a.box[2] >= a.box[3]) {
             err = "step2ds tile subset: bad box";
             return PCL_EINVAL;
         }
         const unsigned inside = (unsigned)(a.box[1] - a.box[0]) * (unsigned)(a.box[3] - a.box[2]);
-        nblocks = a.sub == 1 ? inside : nblocks - inside;
-        if (nblocks == 0) return PCL_OK;
-    }
-    if (a.src_id != 0 && !(std::is_same<RP, Euler5>::value && a.src_id == 1 && !capa)) {
-        err = "fused source: only the Euler solver's radial source, no capacity function";
-        return PCL_EINVAL;
+        g.nblocks = a.sub == 1 ? inside : g.nblocks - inside;
+        if (g.nblocks == 0) return PCL_OK;
     }
     // a list launch: the tiles the hand-over+list kernel behind the previous launch listed (classic_fused.hpp); one
     // workgroup per tile of the grid, those past the list's end return at once
@@ -196,7 +194,49 @@ template <class RP> int launch_step2ds_t(const SweepLaunch &l, std::string &err)
         err = "step2ds tile list: the whole block, with its bookkeeping";
         return PCL_EINVAL;
     }
-    const dim3 grid(nblocks);
+    return PCL_OK;
+}
+
+// A user-written Riemann solver compiled with the one-kernel step (cellrp.hpp: spec.onek): l.user_fn is
+// step2ds_kernel<UserRp, FWAVE, false, CAPA> of the module compiled at run time from the text of classic_fused.hpp, FWAVE
+// and CAPA the form of l.user, so the grid, the block and the thirteen parameters are those of launch_step2ds_t below.
+int launch_step2ds_user(const SweepLaunch &l, std::string &err) {
+    if (!l.user_fn || !l.user.onek) {
+        err = "user-written Riemann solver: no solver compiled with the one-kernel step is attached (pcl_cellrp_compile_onek, pcl_cellrp_attach)";
+        return PCL_ESTATE;
+    }
+    if (l.user.sharp()) { err = "user-written Riemann solver: the attached solver was compiled for SharpClaw and holds no classic step"; return PCL_EINVAL; }
+    if (l.a.src_id != 0) { err = "user-written Riemann solver: no fused source"; return PCL_EINVAL; }
+    if (int rc = user_form_check(l, err)) return rc;
+    Step2dsGrid g;
+    if (int rc = step2ds_grid(l, l.user.naux, g, err)) return rc;
+    if (g.nblocks == 0) return PCL_OK;
+    SweepArgs a = l.a;
+    unsigned *tq_out = l.tq_out, *tq_ring = l.tq_ring, *tq_reuse = l.tq_reuse, *tq_ycol = l.tq_ycol;
+    double2 *tq_cfl = l.tq_cfl;
+    const int *tq_list = l.tq_list;
+    const TileNext *tq_next = l.tq_next;
+    unsigned ring_seq = l.ring_seq;
+    int rowreuse = l.rowreuse, ycol = l.ycol;
+    void *params[] = {&a, &g.ntx, &g.nty, &tq_out, &tq_cfl, &tq_list, &tq_next, &tq_ring, &ring_seq, &tq_reuse, &rowreuse, &tq_ycol, &ycol};
+    hipError_t e = hipModuleLaunchKernel(l.user_fn, g.nblocks, 1, 1, F_THREADS, 1, 1, 0, l.stream, params, nullptr);
+    return e == hipSuccess ? PCL_OK : hip_fail(err, "step2ds launch (user-written Riemann solver)", e);
+}
+
+template <class RP> int launch_step2ds_t(const SweepLaunch &l, std::string &err) {
+    const SweepArgs &a = l.a;
+    constexpr bool FW = IsFwave<RP>::value;
+    if ((l.fwave != 0) != FW) { err = "solver.fwave does not match the Riemann solver"; return PCL_EINVAL; }
+    Step2dsGrid g;
+    if (int rc = step2ds_grid(l, RP::NAUX, g, err)) return rc;
+    if (g.nblocks == 0) return PCL_OK;
+    const int ntx = g.ntx, nty = g.nty;
+    const bool capa = a.mcapa > 0;
+    if (a.src_id != 0 && !(std::is_same<RP, Euler5>::value && a.src_id == 1 && !capa)) {
+        err = "fused source: only the Euler solver's radial source, no capacity function";
+        return PCL_EINVAL;
+    }
+    const dim3 grid(g.nblocks);
     if (a.src_id != 0) {
         if constexpr (std::is_same<RP, Euler5>::value)
             hipLaunchKernelGGL((step2ds_kernel<RP, FW, true>), grid, dim3(F_THREADS), 0, l.stream, a, ntx, nty, l.tq_out,
@@ -212,6 +252,7 @@ template <class RP> int launch_step2ds_t(const SweepLaunch &l, std::string &err)
 }
 }  // namespace
 int launch_step2ds(const SweepLaunch &l, std::string &err) {
+    if (l.rp == PCL_RP_CELL) return launch_step2ds_user(l, err);
     const int rc = Solvers::with(l.rp, [&](auto tag) {
         using RP = typename decltype(tag)::type;
         if constexpr (RP::ONEK) return launch_step2ds_t<RP>(l, err);
@@ -332,6 +373,8 @@ const RpFacts *rp_facts(int rp) { return Solvers::facts(rp); }
 // tile shapes: what a user-written Riemann solver's meqn + naux may come to (cellrp.hpp)
 int sweep_tile_max_planes() {
     constexpr int PLANE = TileShape<1>::PLANE > TileShape<2>::PLANE ? TileShape<1>::PLANE : TileShape<2>::PLANE;
+    // (a user-written solver compiled with the one-kernel step meets this limit first: it must lie inside that tile's)
+    static_assert(65536 / ((int)sizeof(double) * PLANE) <= ONEK_MAX_PLANES, "the sweep tile's plane limit lies inside the one-kernel tile's");
     return 65536 / ((int)sizeof(double) * PLANE);
 }
 // the same for the 3-D sweeps (sweep3_kernel: Tile3Shape<1..3>::PLANE against 64 KB, classic.hpp): meqn + naux + capa

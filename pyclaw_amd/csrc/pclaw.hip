@@ -433,19 +433,30 @@ int fused_step_mode() {
     return on;
 }
 // What the host layer knows about each built-in Riemann solver (sweep_args.hpp: RpFacts), read off the solver's struct
-// where the kernels are compiled; null for an id no solver has.
-// A user-written solver (PCL_RP_CELL, cellrp.hpp) has the two sweeps and nothing else: a record with everything off, so
-// that the one-kernel step, quiet tiles, step ahead and the overlap plans never choose it.  Its sizes are the config's.
-const pcl::RpFacts *solver_facts(int rp) {
+// where the kernels are compiled; null for an id no solver has.  By id alone -- for a configuration no handle exists for
+// yet (pcl_create, the stateless calls) -- a user-written solver (PCL_RP_CELL, cellrp.hpp) is a record with everything off.
+const pcl::RpFacts *rp_id_facts(int rp) {
     static const pcl::RpFacts cell = {PCL_RP_CELL, 0, 0, 0, 0, false, false, false, false, false, false};
     return rp == PCL_RP_CELL ? &cell : pcl::exact::rp_facts(rp);
 }
+// The same of the solver of a handle: the one function the step's decisions read (fused_step_ok, fused_aux_family,
+// block_facts, do_step2ds, ahead_enqueue, the form trials).  A user-written solver has the sizes of the configuration and
+// the two sweeps; with a module that carries the one-kernel step (cellrp.hpp: spec.onek) also onek, or onek_aux where its
+// body reads aux components -- and with that quiet tiles, tile lists, the form trials and step ahead exactly as a built-in
+// solver of that record.  Everything else stays off: more than one block is refused for it at pcl_comm_init.
+pcl::RpFacts solver_facts(const pcl_solver *s) {
+    if (s->cfg.rp != PCL_RP_CELL) return *rp_id_facts(s->cfg.rp);
+    const pcl::CellrpSpec &u = s->cellrp.spec;
+    const bool onek = s->cellrp.onek != nullptr;
+    return {PCL_RP_CELL, s->cfg.ndim, s->cfg.meqn, s->cfg.mwaves, u.naux, u.fwave(), onek && u.naux == 0, onek && u.naux > 0,
+            false, false, false};
+}
 // the one-kernel step stages aux planes next to q: a solver with cell-wise coefficients, or any solver with a capacity function
-bool fused_aux_family(const pcl_solver *s) { return s->cfg.method[5] > 0 || solver_facts(s->cfg.rp)->onek_aux; }
+bool fused_aux_family(const pcl_solver *s) { return s->cfg.method[5] > 0 || solver_facts(s).onek_aux; }
 bool fused_step_ok(const pcl_solver *s) {
     const int on = fused_step_mode();
-    const pcl::RpFacts *f = solver_facts(s->cfg.rp);
-    if (!(on && s->cfg.ndim == 2 && s->cfg.method[2] < 0 && s->cfg.mbc == 2 && s->cfg.meqn <= 5 && (f->onek || f->onek_aux))) return false;
+    const pcl::RpFacts f = solver_facts(s);
+    if (!(on && s->cfg.ndim == 2 && s->cfg.method[2] < 0 && s->cfg.mbc == 2 && s->cfg.meqn <= pcl::ONEK_MAX_MEQN && (f.onek || f.onek_aux))) return false;
     // whole blocks only, and not under the fused source (Euler without a capacity function: pcl_fuse_source)
     return !fused_aux_family(s) || (!s->halo.active && s->aux && s->fused_src == 0);
 }
@@ -460,7 +471,7 @@ OverlapPlan::Facts block_facts(const pcl_solver *s) {
     if (!f.split2) return f;
     f.sel0 = s->sel == 0;
     f.onek_ok = fused_step_ok(s);
-    f.onek_family = s->cfg.method[5] <= 0 && solver_facts(s->cfg.rp)->onek;
+    f.onek_family = s->cfg.method[5] <= 0 && solver_facts(s).onek;
     f.onek_box = s->box_onek.any;
     f.x_box = s->box_x.any;
     return f;
@@ -476,10 +487,13 @@ int do_step2ds(pcl_solver *s, const double *qin, double *qout, double dt, bool c
     if (sub) for (int k = 0; k < 4; k++) a.box[k] = box[k];
     LaunchTimer timer(s, timing_on(s) && !on, 2, sub != 2, stream);
     SweepLaunch l = make_launch(s, a, 2, 1, stream);
+    // (a user-written solver: the one-kernel step of its module, null where the handle was compiled without it)
+    if (l.rp == PCL_RP_CELL) l.user_fn = s->cellrp.onek;
     // quiet tiles (quiet_tiles.hpp): the whole block only (a decomposed block's ghost frame and tile subsets are left out),
     // and not where aux planes are staged (the key of the remembered state does not cover pcl_put_aux, and with a
     // capacity function a tile's cached Courant maxima are not dt-free)
-    const QuietTiles::Key key(s->cfg.rp, s->cfg.fwave, s->cfg.math, a);
+    // (two bodies share rp = PCL_RP_CELL: the attached module's id tells them apart, 0 for a built-in solver)
+    const QuietTiles::Key key(s->cfg.rp, s->cellrp.id, s->cfg.fwave, s->cfg.math, a);
     const bool book = s->qt.plan(l, qin, qout, key, dt, sub == 0 && !s->halo.active && !fused_aux_family(s), carry);
     std::string err;
     int rc = PCL_BY_MATH(s->cfg.math, launch_step2ds(l, err));
@@ -701,14 +715,14 @@ int check_device() {
 extern "C" {
 
 const char *pcl_last_error(void) { return g_err.c_str(); }
-int pcl_version(void) { return 111; }
+int pcl_version(void) { return 112; }
 int pcl_device_count(void) {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess) return 0;
     return n;
 }
 int pcl_rp_info(int rp, int info[10]) {
-    const pcl::RpFacts *f = rp == PCL_RP_CELL ? nullptr : solver_facts(rp);    // built-in solvers only
+    const pcl::RpFacts *f = rp == PCL_RP_CELL ? nullptr : rp_id_facts(rp);     // built-in solvers only
     if (!f || !info) return fail(PCL_EINVAL, !info ? "null argument" : "unknown Riemann solver id");
     const int v[10] = {f->ndim, f->meqn, f->mwaves, f->naux, f->fwave, f->onek, f->onek_aux, f->sharp, f->sharp_high, f->sharp_wave};
     std::copy(v, v + 10, info);
@@ -759,7 +773,7 @@ static int create_check(const pcl_config *cfg, bool cell_handle, int handle_ndim
     if (cfg->mwaves < 1 || cfg->mwaves > PCL_MAX_WAVES) return fail(PCL_EINVAL, "bad mwaves");
     if (cfg->math != PCL_MATH_EXACT && cfg->math != PCL_MATH_FAST && cfg->math != PCL_MATH_STRICT)
         return fail(PCL_EINVAL, "unknown math mode");
-    const pcl::RpFacts *facts = solver_facts(cfg->rp);
+    const pcl::RpFacts *facts = rp_id_facts(cfg->rp);
     if (!facts) return fail(PCL_EINVAL, "unknown Riemann solver id");
     if (cfg->rp == PCL_RP_CELL) {
         // a user-written normal solver (cellrp.hpp): sizes from the config; it serves the classic 1-D step and the two
@@ -1785,13 +1799,13 @@ static int cellrp_compile(const pcl::CellrpSpec &sp, pcl::CellrpTexts t, pcl::Ce
         c.hits++;
     } else {
         std::vector<char> code;
-        std::string sym[4];
+        std::string sym[PCL_CELLRP_MAX_KERNELS];
         if (cellrp_build(sp, t, code, sym, err)) return fail(PCL_EINVAL, err);
         r = new pcl_cellrp();
         r->id = c.next_id++;
         r->key = key;
         r->code.swap(code);
-        for (int k = 0; k < 4; k++) r->sym[k] = sym[k];
+        for (int k = 0; k < PCL_CELLRP_MAX_KERNELS; k++) r->sym[k] = sym[k];
         r->spec = sp;
         c.rp_by_key[key] = r;
         c.rp_live[r] = r->id;
@@ -1819,6 +1833,18 @@ int pcl_cellrp_compile_form(const char *body, const char *transverse, const char
     pcl::CellrpSpec sp = cellrp_spec(meqn, mwaves, ndim, math, aux_index, naux);
     sp.trans = transverse != nullptr;
     sp.form = form;
+    pcl::CellrpGiven given = {};
+    given.aux_list = aux_index != nullptr;
+    return cellrp_compile(sp, {body, transverse, preamble}, given, out, code_size);
+}
+
+// The same with the dimension-split 2-D step as one kernel next to the sweeps (classic_fused.hpp: step2ds_kernel): 2-D only
+int pcl_cellrp_compile_onek(const char *body, const char *transverse, const char *preamble, int meqn, int mwaves, int math,
+                            const int *aux_index, int naux, int form, pcl_cellrp **out, long *code_size) {
+    pcl::CellrpSpec sp = cellrp_spec(meqn, mwaves, 2, math, aux_index, naux);
+    sp.trans = transverse != nullptr;
+    sp.form = form;
+    sp.onek = 1;
     pcl::CellrpGiven given = {};
     given.aux_list = aux_index != nullptr;
     return cellrp_compile(sp, {body, transverse, preamble}, given, out, code_size);
@@ -1914,6 +1940,14 @@ int pcl_cellrp_form(const pcl_cellrp *r, int *form) {
     return PCL_OK;
 }
 
+int pcl_cellrp_onek(const pcl_cellrp *r, int *has) {
+    if (!has) return fail(PCL_EINVAL, "null argument");
+    pcl::CellrpSpec sp;
+    if (int rc = cellrp_live_spec(r, sp)) return rc;
+    *has = sp.onek;
+    return PCL_OK;
+}
+
 int pcl_cellrp_sharp(const pcl_cellrp *r, int *lim_type, int *weno_order, int *char_decomp) {
     if (!lim_type || !weno_order || !char_decomp) return fail(PCL_EINVAL, "null argument");
     pcl::CellrpSpec sp;
@@ -1928,7 +1962,7 @@ int pcl_cellrp_attach(pcl_solver *s, pcl_cellrp *r) {
     if (s->cfg.rp != PCL_RP_CELL) return fail(PCL_EINVAL, "pcl_cellrp_attach: the solver was not created with cfg.rp = PCL_RP_CELL");
     pcl::CellrpModule m;
     const void *code;
-    std::string sym[4];
+    std::string sym[PCL_CELLRP_MAX_KERNELS];
     {   // (the entry is never freed: the code stays valid outside the lock)
         CellfnCache &c = cellfn_cache();
         std::lock_guard<std::mutex> lock(c.mu);
@@ -1939,15 +1973,20 @@ int pcl_cellrp_attach(pcl_solver *s, pcl_cellrp *r) {
         m.id = r->id;
         m.spec = r->spec;
         code = r->code.data();
-        for (int k = 0; k < 4; k++) sym[k] = r->sym[k];
+        for (int k = 0; k < PCL_CELLRP_MAX_KERNELS; k++) sym[k] = r->sym[k];
     }
     if (s->cellrp.id == m.id) return PCL_OK;
     HIP_TRY(hipSetDevice(s->cfg.device));
     HIP_TRY(hipStreamSynchronize(s->stream));       // a sweep of the module attached before may still run
     s->cellrp.unload();
     HIP_TRY(hipModuleLoadData(&m.mod, code));
-    for (int k = 0; k < 4 && !sym[k].empty(); k++) {
-        hipError_t e = hipModuleGetFunction(&m.fn[k], m.mod, sym[k].c_str());
+    // (with spec.onek the last name is the one-kernel step's: cellrp_exprs)
+    int nsym = 0;
+    while (nsym < PCL_CELLRP_MAX_KERNELS && !sym[nsym].empty()) nsym++;
+    for (int k = 0; k < nsym; k++) {
+        const bool last_onek = m.spec.onek && k == nsym - 1;
+        hipError_t e = !last_onek && k >= 4 ? hipErrorInvalidValue      // (cellrp_exprs names at most four others)
+                                            : hipModuleGetFunction(last_onek ? &m.onek : &m.fn[k], m.mod, sym[k].c_str());
         if (e != hipSuccess) {
             (void)hipModuleUnload(m.mod);
             return fail(PCL_EHIP, "hipModuleGetFunction(" + sym[k] + "): " + hipGetErrorString(e));
@@ -2762,7 +2801,7 @@ static int host_sharp(int ndim, int rp, const double *rp_params, int lim_type, i
     c.method[1] = 2; c.method[5] = mcapa; c.method[6] = maux;
     c.kind = PCL_KIND_SHARPCLAW; c.lim_type = lim_type;
     // clawparams.fwave follows the Riemann solver (sharpclaw.py:269): flux1 / flux2 carry no argument for it
-    const pcl::RpFacts *facts = solver_facts(rp);      // (PCL_RP_CELL: everything off; pcl_create refuses it for SharpClaw)
+    const pcl::RpFacts *facts = rp_id_facts(rp);       // (PCL_RP_CELL: everything off; pcl_create refuses it for SharpClaw)
     c.fwave = facts && facts->fwave;
     return layer1_run(c, q, aux, dq, L1_SHARP_DQ, 0, dt, cfl);
 }

@@ -55,11 +55,13 @@ public:
     // the settings two launches must share for the words of one to decide the other (compared bytewise)
     struct Key {
         int rp, fwave, math, src;
+        long module;        // the id of the attached module of a user-written solver (cellrp.hpp), 0 for a built-in one:
+                            // two bodies share rp = PCL_RP_CELL, and a skipped tile's cached Courant maxima are the body's speeds
         double src_p[2];
         RpParams par;
-        Key(int rp_, int fwave_, int math_, const SweepArgs &a) {
+        Key(int rp_, long module_, int fwave_, int math_, const SweepArgs &a) {
             memset(this, 0, sizeof(Key));
-            rp = rp_; fwave = fwave_; math = math_; src = a.src_id;
+            rp = rp_; module = module_; fwave = fwave_; math = math_; src = a.src_id;
             src_p[0] = a.src_p[0]; src_p[1] = a.src_p[1];
             par = a.par;
         }

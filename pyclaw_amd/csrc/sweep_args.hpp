@@ -138,6 +138,23 @@ struct SweepArgs {
     double src_p[2];
 };
 
+// The tile list's small state (classic_fused.hpp): the number of listed tiles of class A (they computed something in the
+// launch before; from the list's front) and of class Q (quiet there; from its back), and the largest cached Courant
+// maxima (bit patterns of doubles >= +0, before dt/d) of the x and y sweeps over the tiles it skips.  Three of them, rotating:
+// a hand-over+list launch fills one and zeroes the one the hand-over after it fills; the third keeps the list the last
+// launch ran over (pcl_tile_skip_stats).
+struct TileNext {
+    int na, nq;
+    unsigned long long cx, cy;
+};
+// cells a tile of the one-kernel step owns, for the host's tile counts (kernels.hip ties them to F_OWN_C, F_OWN_R)
+constexpr int TILE_OWN_C = 60, TILE_OWN_R = 12;
+// The one-kernel step (classic_fused.hpp) holds q of up to ONEK_MAX_MEQN equations and up to ONEK_MAX_PLANES planes in all
+// (q, the capacity function, staged aux components: two 80 KB workgroups per CU at least).  The one rule for every solver,
+// built in or compiled at run time: read by fused_step_ok (pclaw.hip) and by cellrp_spec_check (cellrp.hpp), restated by
+// the kernel's own static_assert.
+constexpr int ONEK_MAX_MEQN = 5, ONEK_MAX_PLANES = 10;
+
 #ifndef __HIPCC_RTC__       // from here on: host-side launch descriptors and the launchers' declarations
 // unsplit 3-D (classic3.hpp): one direction's slices, applied in the reference's order by the marching kernel
 struct Unsplit3Launch {
@@ -160,18 +177,6 @@ struct RkLaunch {
     int op;
 };
 
-// The tile list's small state (classic_fused.hpp): the number of listed tiles of class A (they computed something in the
-// launch before; from the list's front) and of class Q (quiet there; from its back), and the largest cached Courant
-// maxima (bit patterns of doubles >= +0, before dt/d) of the x and y sweeps over the tiles it skips.  Three of them, rotating:
-// a hand-over+list launch fills one and zeroes the one the hand-over after it fills; the third keeps the list the last
-// launch ran over (pcl_tile_skip_stats).
-struct TileNext {
-    int na, nq;
-    unsigned long long cx, cy;
-};
-// cells a tile of the one-kernel step owns, for the host's tile counts (kernels.hip ties them to F_OWN_C, F_OWN_R)
-constexpr int TILE_OWN_C = 60, TILE_OWN_R = 12;
-
 // What a user-written Riemann solver (cellrp.hpp) is compiled for: the one record that travels from a pcl_cellrp_compile*
 // call through the cache entry and the loaded module to the launchers.  Every field is part of the cache key and decides
 // which kernels the code object holds.  A default-constructed one is "nothing attached".
@@ -182,6 +187,7 @@ struct CellrpSpec {
     int trans = 0;                                  // 1: a transverse body, the code object holds the unsplit kernels too
     int form = 0;                                   // PCL_CELLRP_FORM_* bits
     int lim_type = 0, weno_order = 0, char_decomp = 0;      // a SharpClaw handle (lim_type 0: a classic one)
+    int onek = 0;                                   // 1: the code object holds the one-kernel dimension-split 2-D step too
     bool fwave() const { return (form & PCL_CELLRP_FORM_FWAVE) != 0; }
     bool capa() const { return (form & PCL_CELLRP_FORM_CAPA) != 0; }
     bool sharp() const { return lim_type != 0; }

@@ -139,19 +139,33 @@ class CellRiemann(RiemannSolver):
     large from six aux components on, so the x pass then sets the limit).  A ``dq_src`` -- a ``CellDqSource`` or a
     Python callable -- runs as its own pass: nothing is fused into the stage.
 
+    ``one_kernel=True`` (2-D, classic) also compiles the library's one-kernel form of the dimension-split 2-D step
+    around the body: both sweeps on one tile in LDS, q through memory once per step.  ``ClawSolver2D(dim_split=True)``
+    then chooses between that step and the two passes exactly as it does for a built-in solver, and
+    ``solver.status["step_forms"]`` reports what ran.  A wave-form body without ``aux`` and ``capa`` gets everything the
+    built-in solvers get there -- tiles whose update is the identity are skipped, only the tiles that compute are
+    launched, timed trials pick the faster form, and resident mode enqueues the next step ahead -- all of which rest on
+    the contract above ("bitwise-equal ``ql`` and ``qr`` give zero waves") and on nothing else.  A body with ``aux`` or
+    ``capa=True`` runs the one-kernel step over the whole block; an f-wave body its f-wave form, in which every interface
+    is solved.  It is a ``ValueError`` with ``ndim != 2``, with ``sharpclaw=True`` and with ``meqn > 5`` (the tile of the
+    one-kernel step holds up to five equations, for every solver).  It is part of the compile key and readable as an
+    attribute; the default is ``False``, which compiles what it always did.  A solver that carries a transverse body and
+    runs ``dim_split=False`` keeps its unsplit kernels and never uses the extra one.
+
     The dimension-split 3-D step takes a ``CellRiemann3D`` (below); ``CellRiemann(..., ndim=3)`` is a ``ValueError``.
 
     Not served: a transverse body that needs both cells and aux, a conservation fix in the unsplit step (the sphere
     solver's ``qcor``), the unsplit 3-D step (``rpt3`` / ``rptt3`` bodies), f-waves in 3-D, more than one block
-    (decomposed runs); under SharpClaw ``char_decomp`` 2 / 3, ``tfluct_solver`` and a fused dq source.  The dimension-split 2-D step always runs as two passes, never as the one-kernel step, the unsplit y
-    phase always in its tile form (the marching y kernel stays with the built-in solvers)."""
+    (decomposed runs); under SharpClaw ``char_decomp`` 2 / 3, ``tfluct_solver`` and a fused dq source.  The unsplit y
+    phase always runs in its tile form (the marching y kernel stays with the built-in solvers)."""
 
     MAX_PARAMS = 8
     MAX_PLANES = 8
+    ONE_KERNEL_MAX_MEQN = 5
     _NDIMS = (1, 2)
 
     def __init__(self, body, meqn, mwaves, ndim, params=(), preamble="", name="user", aux=(), transverse=None, fwave=False,
-                 capa=False, sharpclaw=False):
+                 capa=False, sharpclaw=False, one_kernel=False):
         RiemannSolver.__init__(self, name, PCL_RP_CELL, int(ndim), int(meqn), int(mwaves), (),
                                has_transverse=transverse is not None)
         if not 1 <= self.meqn <= 8 or not 1 <= self.mwaves <= 8:
@@ -163,6 +177,8 @@ class CellRiemann(RiemannSolver):
         if self.sharpclaw and transverse is not None:
             raise ValueError("CellRiemann: sharpclaw=True with a transverse body: SharpClaw has no transverse solve, and a "
                              "solver compiled for it serves SharpClawSolver1D / SharpClawSolver2D alone")
+        self.one_kernel = bool(one_kernel)
+        self._check_one_kernel()
         self.aux = tuple(int(k) for k in aux)
         if any(k < 0 for k in self.aux):
             raise ValueError("CellRiemann: aux lists 0-based components of state.aux, got a negative index in %r" % (self.aux,))
@@ -195,6 +211,21 @@ class CellRiemann(RiemannSolver):
         self._key = None
         self.code_size = 0
 
+    def _check_one_kernel(self):
+        """What one_kernel=True cannot go with, each with its reason: at construction, and again in compile(), since the
+        attribute can be assigned afterwards."""
+        if not self.one_kernel:
+            return
+        if self.ndim != 2:
+            raise ValueError("CellRiemann: one_kernel=True with ndim=%d: the one-kernel step is the dimension-split 2-D "
+                             "step (ndim must be 2)" % self.ndim)
+        if self.sharpclaw:
+            raise ValueError("CellRiemann: one_kernel=True with sharpclaw=True: the one-kernel step is a classic step, "
+                             "and a solver compiled for SharpClaw holds the SharpClaw kernels alone")
+        if self.meqn > self.ONE_KERNEL_MAX_MEQN:
+            raise ValueError("CellRiemann: one_kernel=True with meqn=%d: the tile of the one-kernel step holds up to %d "
+                             "equations (meqn > %d)" % (self.meqn, self.ONE_KERNEL_MAX_MEQN, self.ONE_KERNEL_MAX_MEQN))
+
     @property
     def params(self):
         return self._params
@@ -221,9 +252,11 @@ class CellRiemann(RiemannSolver):
         if (sharp is not None) != self.sharpclaw:
             raise ValueError("CellRiemann: compile(sharp=(lim_type, weno_order, char_decomp)) belongs to a solver written with "
                              "sharpclaw=True, and such a solver is compiled in no other way")
+        self._check_one_kernel()
         sharp = None if sharp is None else tuple(int(v) for v in sharp)
         form = (1 if self.fwave else 0) | (2 if self.capa else 0)      # PCL_CELLRP_FORM_FWAVE, PCL_CELLRP_FORM_CAPA
-        key = (self.meqn, self.mwaves, self.ndim, math, self.body, self.preamble, self.aux, self.transverse, form, sharp)
+        key = (self.meqn, self.mwaves, self.ndim, math, self.body, self.preamble, self.aux, self.transverse, form, sharp,
+               bool(self.one_kernel))
         if self._rp is not None and self._key == key:
             return self
         rp, size = ctypes.c_void_p(), ctypes.c_long(0)
@@ -236,6 +269,11 @@ class CellRiemann(RiemannSolver):
             _lib.check(_lib.lib().pcl_cellrp_compile_sharp(self.body.encode(), self.preamble.encode(), self.meqn, self.mwaves,
                                                            self.ndim, mode, aux, len(self.aux), form, sharp[0], sharp[1], sharp[2],
                                                            ctypes.byref(rp), ctypes.byref(size)))
+        elif self.one_kernel:           # (2-D, classic, meqn <= 5: _check_one_kernel)
+            _lib.check(_lib.lib().pcl_cellrp_compile_onek(self.body.encode(),
+                                                          None if self.transverse is None else self.transverse.encode(),
+                                                          self.preamble.encode(), self.meqn, self.mwaves, mode,
+                                                          aux, len(self.aux), form, ctypes.byref(rp), ctypes.byref(size)))
         else:
             _lib.check(_lib.lib().pcl_cellrp_compile_form(self.body.encode(),
                                                           None if self.transverse is None else self.transverse.encode(),

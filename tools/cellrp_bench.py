@@ -37,13 +37,20 @@ built-in solver held to two passes, and "user", ACOUSTICS_2D_RP in a CellRiemann
 sharp_kernel over the same tiles.  The children also time every distinct run-time compile they make: the user solver's
 SharpClaw kernels ("compile_s") and, for comparison, the same body's classic sweeps ("compile_classic_s").
 
+--one-kernel measures what CellRiemann(..., one_kernel=True) buys, three ways: "default", the built-in solver on its
+default path (the one-kernel step with its quiet tiles: the yardstick), "user_onek", the same solver as a CellRiemann
+compiled with one_kernel=True (the same one-kernel step around the body, chosen as for the built-in solver), and "user",
+the CellRiemann without it (always two passes).  With --aux the same on vc_acoustics_2d against CellRiemann(aux=(0, 1)).
+"compile_s" is the cold run-time compile with the one-kernel step, "compile_plain_s" the one without, each as its
+children saw it.
+
 --ndim 3 measures the dimension-split 3-D step two ways on the workload of `bench.py --ndim 3` (its build3d: 3-D acoustics
 in two materials, n^3 cells, n = 512 unless --n says otherwise): "builtin", rp_vc_acoustics_3d, and "user", the same solver
 as a CellRiemann3D (problems.VC_ACOUSTICS_3D_RP, aux=(0, 1)).  Both run sweep3_kernel over the same tiles, and nothing
 here is read once per process, so the two solvers live side by side in this process and are timed in alternating
 segments of `--steps` steps, `--reps` of each per state.
 
-  python tools/cellrp_bench.py [--aux] [--unsplit] [--fwave | --capa | --sharpclaw | --ndim 3] [--n 4096] [--steps 20] [--warmup 3] [--reps 7] [--out FILE]
+  python tools/cellrp_bench.py [--aux] [--unsplit | --one-kernel] [--fwave | --capa | --sharpclaw | --ndim 3] [--n 4096] [--steps 20] [--warmup 3] [--reps 7] [--out FILE]
 """
 import argparse
 import ctypes
@@ -61,6 +68,7 @@ sys.path.insert(0, ROOT)
 VARIANTS = ("two_pass", "user", "default")
 VARIANTS_UNSPLIT = ("builtin", "user")
 VARIANTS_CAPA = ("two_pass", "user")
+VARIANTS_ONEK = ("default", "user_onek", "user")
 
 
 def child(args):
@@ -70,21 +78,22 @@ def child(args):
     L = _lib.lib()
     if L.pcl_device_count() < 1:
         raise SystemExit("cellrp_bench: no HIP device (nothing here can be measured without one)")
+    user = args.child in ("user", "user_onek")
     if args.sharpclaw:
         claw = problems.acoustics2D(pyclaw, mx=args.n, my=args.n, run=False, math=args.math, solver_type='sharpclaw',
-                                    time_integrator='SSP104', user_rp=args.child == "user")
+                                    time_integrator='SSP104', user_rp=user)
     elif args.fwave:
         from apps import psystem
         claw = psystem.psystem2D(pyclaw, mx=args.n, my=args.n, solver_type='classic', run=False, math=args.math,
-                                 user_rp=args.child == "user")
+                                 user_rp=user)
     elif args.capa:
-        claw = problems.capa_acoustics2D(pyclaw, mx=args.n, my=args.n, run=False, math=args.math, user_rp=args.child == "user")
+        claw = problems.capa_acoustics2D(pyclaw, mx=args.n, my=args.n, run=False, math=args.math, user_rp=user)
     elif args.unsplit:
         make = problems.vc_acoustics2D if args.aux else problems.acoustics2D
-        claw = make(pyclaw, mx=args.n, my=args.n, run=False, math=args.math, dim_split=0, user_rp=args.child == "user")
+        claw = make(pyclaw, mx=args.n, my=args.n, run=False, math=args.math, dim_split=0, user_rp=user)
         claw.solver.order_trans = 2
     elif args.aux:
-        claw = problems.vc_acoustics2D(pyclaw, mx=args.n, my=args.n, run=False, math=args.math, user_rp=args.child == "user")
+        claw = problems.vc_acoustics2D(pyclaw, mx=args.n, my=args.n, run=False, math=args.math, user_rp=user)
     else:
         claw = problems.acoustics2D(pyclaw, mx=args.n, my=args.n, run=False, math=args.math)
     solver, solution = claw.solver, claw.solution
@@ -100,7 +109,7 @@ def child(args):
         t0 = time.perf_counter()
         classic.compile(args.math)
         res["compile_classic_s"] = time.perf_counter() - t0
-    elif args.child == "user":
+    elif user:
         if args.unsplit:        # the same normal body without the transverse text, for the compile time alone
             rp = solver.rp
             plain = pyclaw.CellRiemann(rp.body, rp.meqn, rp.mwaves, 2, aux=rp.aux)
@@ -110,6 +119,7 @@ def child(args):
         elif not args.aux and not args.fwave and not args.capa:
             g = state.aux_global
             solver.rp = pyclaw.CellRiemann(problems.ACOUSTICS_2D_RP, 3, 2, 2, params=[g['rho'], g['bulk'], g['cc'], g['zz']])
+        solver.rp.one_kernel = args.child == "user_onek"
         t0 = time.perf_counter()
         solver.rp.compile(args.math)
         res["compile_s"] = time.perf_counter() - t0
@@ -232,23 +242,30 @@ def main():
     ap.add_argument("--sharpclaw", action="store_true", help="the SSP104 step of SharpClaw: rp_acoustics_2d against CellRiemann(sharpclaw=True)")
     ap.add_argument("--ndim", type=int, default=2, choices=[2, 3],
                     help="3: the dimension-split 3-D step on bench.py's 3-D grid, rp_vc_acoustics_3d against CellRiemann3D")
-    ap.add_argument("--child", default=None, choices=VARIANTS + VARIANTS_UNSPLIT)
+    ap.add_argument("--one-kernel", dest="one_kernel", action="store_true",
+                    help="CellRiemann(one_kernel=True) against the built-in one-kernel step and against the user solver's two passes")
+    ap.add_argument("--child", default=None, choices=VARIANTS + VARIANTS_UNSPLIT + VARIANTS_ONEK[1:2])
     args = ap.parse_args()
     if args.ndim == 3:
-        if args.aux or args.unsplit or args.fwave or args.capa or args.sharpclaw:
+        if args.aux or args.unsplit or args.fwave or args.capa or args.sharpclaw or args.one_kernel:
             raise SystemExit("cellrp_bench: --ndim 3 is a measurement of its own")
         return run3(args)
     if (args.fwave or args.capa) and (args.aux or args.unsplit or (args.fwave and args.capa)):
         raise SystemExit("cellrp_bench: --fwave and --capa are measurements of their own (not with --aux, --unsplit or each other)")
     if args.sharpclaw and (args.aux or args.unsplit or args.fwave or args.capa):
         raise SystemExit("cellrp_bench: --sharpclaw is a measurement of its own")
+    if args.one_kernel and (args.unsplit or args.fwave or args.capa or args.sharpclaw):
+        raise SystemExit("cellrp_bench: --one-kernel goes with --aux or alone")
     if args.child:
         return child(args)
 
     # (--sharpclaw: two variants compared like the unsplit pair)
-    variants = VARIANTS_UNSPLIT if args.unsplit or args.sharpclaw else VARIANTS_CAPA if args.capa else VARIANTS
+    variants = (VARIANTS_ONEK if args.one_kernel else VARIANTS_UNSPLIT if args.unsplit or args.sharpclaw
+                else VARIANTS_CAPA if args.capa else VARIANTS)
     mode = (["--aux"] if args.aux else []) + (["--unsplit"] if args.unsplit else []) + (["--fwave"] if args.fwave else []) + \
            (["--capa"] if args.capa else []) + (["--sharpclaw"] if args.sharpclaw else [])
+    # (the children of --one-kernel differ in their variant alone: nothing of the mode reaches them but --aux)
+    label = mode + (["--one-kernel"] if args.one_kernel else [])
     runs = {v: [] for v in variants}
     for _ in range(args.reps):
         for v in variants:
@@ -268,9 +285,12 @@ def main():
 
     def spread(vals):
         return {"median": float(np.median(vals)), "min": min(vals), "max": max(vals), "all": vals}
-    res = {"tool": " ".join(["cellrp_bench"] + mode), "n": args.n, "math": args.math, "steps": args.steps, "warmup": args.warmup, "reps": args.reps,
-           "compile_s": spread([r["compile_s"] for r in runs["user"]]), "forms": {v: runs[v][-1]["forms"] for v in variants},
+    res = {"tool": " ".join(["cellrp_bench"] + label), "n": args.n, "math": args.math, "steps": args.steps, "warmup": args.warmup, "reps": args.reps,
+           "compile_s": spread([r["compile_s"] for r in runs["user_onek" if args.one_kernel else "user"]]), "forms": {v: runs[v][-1]["forms"] for v in variants},
            "states": {}}
+    if args.one_kernel:
+        res["compile_plain_s"] = spread([r["compile_s"] for r in runs["user"]])
+        res["what"] = "ms per dimension-split step; default = the built-in solver's one-kernel path, user_onek = CellRiemann(one_kernel=True), user = its two passes"
     if args.unsplit:
         res["compile_plain_s"] = spread([r["compile_plain_s"] for r in runs["user"]])
     if args.sharpclaw:
@@ -281,6 +301,14 @@ def main():
         sums = set(r[name + "_sum"] for v in variants for r in runs[v])
         cfls = set(r[name + "_cfl"] for v in variants for r in runs[v])
         st["same_result_in_every_run"] = len(sums) == 1 and len(cfls) == 1
+        if args.one_kernel:
+            a, b, c = (st[v + "_ms"] for v in variants)
+            st["user_onek_over_default"] = b["median"] / a["median"]
+            st["user_onek_and_default_spreads_overlap"] = not (b["min"] > a["max"] or a["min"] > b["max"])
+            st["user_over_user_onek"] = c["median"] / b["median"]
+            st["user_onek_and_user_spreads_overlap"] = not (b["min"] > c["max"] or c["min"] > b["max"])
+            res["states"][name] = st
+            continue
         if args.unsplit or args.sharpclaw:
             a, b = (st[v + "_ms"] for v in variants)
             st["user_over_builtin"] = b["median"] / a["median"]

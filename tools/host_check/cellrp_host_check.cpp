@@ -8,6 +8,8 @@
 // The third half is the form (pcl_cellrp_compile_form, pcl_cellrp_form): a compile per form, hit and miss on the form, form 0
 // as pcl_cellrp_compile_t's entry, the refusals with the compile count unmoved, pcl_create_cellrp against every pair of
 // handle and configuration, and attach of a handle of another form.
+// The last part is the one-kernel step (pcl_cellrp_compile_onek, pcl_cellrp_onek): its refusals, its own cache entry, five
+// kernels in one program, and attach as far as the module load.
 // Exit status 0 and no sanitizer report: passed.  tools/host_check/run.sh
 #include <cstdio>
 #include <cstdlib>
@@ -287,6 +289,50 @@ int main() {
     CHECK(pcl_cellrp_release(again));
     CHECK(pcl_cellrp_release(fw1));
     EXPECT(pcl_cellrp_release(fw1) == PCL_EINVAL);
+
+    // ---- the one-kernel step: pcl_cellrp_compile_onek, pcl_cellrp_onek ----
+    {
+        pcl_cellrp *plain = nullptr, *one = nullptr, *one2 = nullptr, *five = nullptr;
+        long psize = 0, osize = 0;
+        int has = -1;
+        CHECK(pcl_cellfn_stats(&n0, &h0));
+        // refused in front of the compiler: more than five equations, a form bit, a null body
+        EXPECT(pcl_cellrp_compile_onek(kBurgers, nullptr, "", 6, 1, PCL_MATH_EXACT, nullptr, 0, 0, &bad, nullptr) == PCL_EINVAL && !bad);
+        EXPECT(strstr(pcl_last_error(), "meqn > 5") != nullptr);
+        EXPECT(pcl_cellrp_compile_onek(kBurgers, nullptr, "", 1, 1, PCL_MATH_EXACT, nullptr, 0, 4, &bad, nullptr) == PCL_EINVAL);
+        EXPECT(pcl_cellrp_compile_onek(nullptr, nullptr, "", 1, 1, PCL_MATH_EXACT, nullptr, 0, 0, &bad, nullptr) == PCL_EINVAL);
+        CHECK(pcl_cellfn_stats(&n, &h));
+        EXPECT(n == n0 && h == h0);
+        // another entry than the same text without the kernel, a larger code object; again: a hit
+        CHECK(pcl_cellrp_compile(kBurgers, "// onek\n", 1, 1, 2, PCL_MATH_EXACT, &plain, &psize));
+        CHECK(pcl_cellrp_compile_onek(kBurgers, nullptr, "// onek\n", 1, 1, PCL_MATH_EXACT, nullptr, 0, 0, &one, &osize));
+        EXPECT(one && one != plain && osize > psize);
+        CHECK(pcl_cellrp_compile_onek(kBurgers, nullptr, "// onek\n", 1, 1, PCL_MATH_EXACT, nullptr, 0, 0, &one2, nullptr));
+        EXPECT(one2 == one);
+        CHECK(pcl_cellfn_stats(&n, &h));
+        EXPECT(n == n0 + 2 && h == h0 + 1);
+        CHECK(pcl_cellrp_onek(one, &has));
+        EXPECT(has == 1);
+        CHECK(pcl_cellrp_onek(plain, &has));
+        EXPECT(has == 0);
+        EXPECT(pcl_cellrp_onek(nullptr, &has) == PCL_EINVAL && pcl_cellrp_onek(one, nullptr) == PCL_EINVAL);
+        // five kernels: the sweeps, the unsplit phases and the one-kernel step, in the f-wave form with a capacity function
+        CHECK(pcl_cellrp_compile_onek("s[0] = p[0];\n", "", "", 5, 2, PCL_MATH_STRICT, nullptr, 0, 3, &five, nullptr));
+        CHECK(pcl_cellrp_onek(five, &has));
+        EXPECT(has == 1);
+        // attach: the host checks pass, the shim loads no module; the step stays refused
+        pcl_config k = cfg;
+        k.mbc = 2;
+        s = nullptr;
+        CHECK(pcl_create(&k, &s));
+        EXPECT(pcl_cellrp_attach(s, one) == PCL_EHIP);
+        EXPECT(pcl_step_hyperbolic(s, 0.01, &cfl) == PCL_ESTATE);
+        pcl_destroy(s);
+        CHECK(pcl_cellrp_release(plain));
+        CHECK(pcl_cellrp_release(one));
+        CHECK(pcl_cellrp_release(one2));
+        CHECK(pcl_cellrp_release(five));
+    }
     printf("cellrp_host_check: ok\n");
     return 0;
 }
