@@ -8,11 +8,13 @@
 // UserRp of the shape rp.hpp documents and asks for the kernels of that struct by name expression, compiled with the flags
 // of the library's own arithmetic mode (PCL_RTC_FLAGS_*, from the Makefile).  A user solver thereby runs with the LDS
 // tiles, DPP shifts, limiter, jump-free shortcut and Courant reduction of the built-in solvers, bit for bit; kernels.hip
-// launches the module's functions over the grids it computes for its own.
+// fires the launch plan of each kernel family -- grid, block and typed arguments, stated once -- at its own kernel or at the
+// module's function in the family's slot (sweep_args.hpp: CellrpSlot).
 //
 // What a solver is compiled for is one value, CellrpSpec (sweep_args.hpp).  It travels from the pcl_cellrp_compile* call
-// through the cache entry (pcl_cellrp) and the loaded module (CellrpModule) to the launchers (SweepLaunch::user); the
-// rules over it are stated once, in cellrp_spec_check (a compile) and cellrp_fits (an attach).
+// through the cache entry (pcl_cellrp) and the loaded module (CellrpModule) to the launchers (SweepLaunch::user, next to the
+// module's kernels by slot, SweepLaunch::user_fns); the rules over it are stated once, in cellrp_spec_check (a compile) and
+// cellrp_fits (an attach).
 //
 // THE BODY is the inside of solve():
 //     const double ql[MEQN], qr[MEQN]      the cells left and right of the interface
@@ -95,7 +97,7 @@
 //   onek   (pcl_cellrp_compile_onek, CellRiemann(one_kernel=True); 2-D classic handles only)
 //     The dimension-split 2-D step as ONE kernel around the body, next to everything the same call without it compiles:
 //     -DPCL_CELLRP_ONEK=1 makes the text include classic_fused.hpp (which includes classic.hpp) and adds one name
-//     expression, step2ds_kernel<UserRp, FWAVE, false, CAPA>, behind the others (CellrpModule::onek).  The host then
+//     expression, step2ds_kernel<UserRp, FWAVE, false, CAPA>, behind the others (SLOT_ONEK).  The host then
 //     treats the solver like a built-in one with such an instantiation (pclaw.hip: solver_facts): quiet tiles, tile lists,
 //     row reuse, the y-column shortcut, the form trials and step ahead for a wave-form body without aux and capa -- all of
 //     which rest on the contract above and on nothing else --, the whole block without bookkeeping with an aux list or a
@@ -118,14 +120,13 @@
 #include "cellrp_headers.inc"
 
 #define PCL_CELLRP_MAX_PARAMS 8
-#define PCL_CELLRP_MAX_KERNELS 5    // what cellrp_exprs names at most: two sweeps, two unsplit phases, the one-kernel step
 
 struct pcl_cellrp {
     long id = 0;                // never reused, from the counter of the cell functions
     int refs = 0;
     std::string key;
     std::vector<char> code;     // the code object
-    std::string sym[PCL_CELLRP_MAX_KERNELS];    // lowered names of cellrp_exprs(spec), in its order; the rest empty
+    std::string sym[pcl::CELLRP_NSLOTS];        // lowered names of cellrp_exprs(spec), by slot; the rest empty
     pcl::CellrpSpec spec;
 };
 
@@ -484,37 +485,38 @@ static inline std::string cellrp_key(const CellrpSpec &sp, const CellrpTexts &t)
     return k;
 }
 
-// the kernels of a UserRp compiled for sp, as hiprtc name expressions (at most PCL_CELLRP_MAX_KERNELS); with sp.onek the
-// one-kernel step comes last, behind the expressions of the same spec without it
-static inline std::vector<std::string> cellrp_exprs(const CellrpSpec &sp) {
+// the kernels of a UserRp compiled for sp: the slot of each (sweep_args.hpp: CellrpSlot) and its hiprtc name expression, in
+// the order hiprtc gets them (slot order; the one-kernel step behind the expressions of the same spec without it)
+using CellrpExprs = std::vector<std::pair<CellrpSlot, std::string>>;
+static inline CellrpExprs cellrp_exprs(const CellrpSpec &sp) {
     const auto n = [](int v) { return std::to_string(v); };
     const std::string ns = std::string("pcl::") + cellrp_ns(sp.math) + "::", rp = ns + "UserRp, ";
     const char *fw = sp.fwave() ? "true" : "false", *capa = sp.capa() ? "true" : "false";
     if (sp.sharp()) {
-        if (sp.char_decomp == 1) return {"&" + ns + "sharp1w_kernel<" + rp + n(sp.lim_type) + ", " + capa + ">"};
+        if (sp.char_decomp == 1) return {{SLOT_SWEEP_X, "&" + ns + "sharp1w_kernel<" + rp + n(sp.lim_type) + ", " + capa + ">"}};
         auto sk = [&](int ixy) { return "&" + ns + "sharp_kernel<" + rp + n(ixy) + ", " + capa + ", " + n(sp.lim_type) + ", " + n(sp.mbc()) + ">"; };
-        if (sp.ndim == 1) return {sk(1)};
-        return {sk(1), sk(2)};
+        if (sp.ndim == 1) return {{SLOT_SWEEP_X, sk(1)}};
+        return {{SLOT_SWEEP_X, sk(1)}, {SLOT_SWEEP_Y, sk(2)}};
     }
     if (sp.ndim == 3) {     // x, y, z
         auto k3 = [&](int dir) { return "&" + ns + "sweep3_kernel<" + rp + n(dir) + ", " + capa + ">"; };
-        return {k3(1), k3(2), k3(3)};
+        return {{SLOT_SWEEP_X, k3(1)}, {SLOT_SWEEP_Y, k3(2)}, {SLOT_SWEEP_Z, k3(3)}};
     }
     auto k = [&](int ixy, bool dim1) { return "&" + ns + "sweep_kernel<" + rp + n(ixy) + ", " + capa + ", " + fw + ", " + (dim1 ? "true" : "false") + ">"; };
-    if (sp.ndim == 1) return {k(1, true)};
-    std::vector<std::string> e = {k(1, false), k(2, false)};
+    if (sp.ndim == 1) return {{SLOT_SWEEP_X, k(1, true)}};
+    CellrpExprs e = {{SLOT_SWEEP_X, k(1, false)}, {SLOT_SWEEP_Y, k(2, false)}};
     if (sp.trans) {
         const std::string u = n(sp.slices());
-        e.push_back("&" + ns + "unsplit_x_kernel<" + rp + fw + ", " + u + ", " + capa + ">");
-        e.push_back("&" + ns + "unsplit_y_kernel<" + rp + fw + ", " + u + ", " + capa + ", false>");
+        e.push_back({SLOT_UNSPLIT_X, "&" + ns + "unsplit_x_kernel<" + rp + fw + ", " + u + ", " + capa + ">"});
+        e.push_back({SLOT_UNSPLIT_Y, "&" + ns + "unsplit_y_kernel<" + rp + fw + ", " + u + ", " + capa + ", false>"});
     }
-    if (sp.onek) e.push_back("&" + ns + "step2ds_kernel<" + rp + fw + ", false, " + capa + ">");
+    if (sp.onek) e.push_back({SLOT_ONEK, "&" + ns + "step2ds_kernel<" + rp + fw + ", false, " + capa + ">"});
     return e;
 }
 
 // hiprtc compile of the kernels of sp around the texts.  0 = ok, else err holds the log
 static inline int cellrp_build(const CellrpSpec &sp, const CellrpTexts &t, std::vector<char> &code,
-                               std::string (&sym)[PCL_CELLRP_MAX_KERNELS], std::string &err) {
+                               std::string (&sym)[CELLRP_NSLOTS], std::string &err) {
     const auto n = [](int v) { return std::to_string(v); };
     HiprtcJob job;
     std::string &src = job.src;
@@ -542,7 +544,8 @@ static inline int cellrp_build(const CellrpSpec &sp, const CellrpTexts &t, std::
     job.nheaders = kCellrpHeaderCount;
     job.header_texts = kCellrpHeaderTexts;
     job.header_names = kCellrpHeaderNames;
-    job.exprs = cellrp_exprs(sp);
+    const CellrpExprs exprs = cellrp_exprs(sp);
+    for (const auto &e : exprs) job.exprs.push_back(e.second);
     // the flags kernels_<mode>.o is built with (Makefile), then this solver's constants
     const std::string all = sp.math == 1 ? PCL_RTC_FLAGS_FAST : sp.math == 2 ? PCL_RTC_FLAGS_STRICT : PCL_RTC_FLAGS_EXACT;
     for (size_t i = 0; i < all.size();) {
@@ -563,7 +566,7 @@ static inline int cellrp_build(const CellrpSpec &sp, const CellrpTexts &t, std::
     job.dump_seq = &seq;
     std::vector<std::string> lowered;
     if (hiprtc_compile(job, code, lowered, err)) return -1;
-    for (size_t k = 0; k < lowered.size(); k++) sym[k] = lowered[k];
+    for (size_t k = 0; k < lowered.size(); k++) sym[exprs[k].first] = lowered[k];
     return 0;
 }
 
@@ -571,12 +574,7 @@ static inline int cellrp_build(const CellrpSpec &sp, const CellrpTexts &t, std::
 struct CellrpModule {
     long id = 0;                // 0: nothing attached
     hipModule_t mod = nullptr;
-    // the kernels of cellrp_exprs(spec), in its order: [0], [1] the sweeps or the SharpClaw kernels by ids - 1 (1-D and
-    // char_decomp = 1: [0] alone), [2], [3] the unsplit phases by ids - 1 of a solver with a transverse body; a 3-D handle:
-    // [0], [1], [2] the x, y, z sweeps by ids - 1; the rest null
-    hipFunction_t fn[4] = {nullptr, nullptr, nullptr, nullptr};
-    // step2ds_kernel<UserRp, FWAVE, false, CAPA> of a handle compiled with spec.onek (the last of cellrp_exprs); else null
-    hipFunction_t onek = nullptr;
+    hipFunction_t fn[CELLRP_NSLOTS] = {};       // the kernels of cellrp_exprs(spec), by slot; the rest null
     CellrpSpec spec;            // what they were compiled for
     void unload() {
         if (mod) (void)hipModuleUnload(mod);

@@ -8,6 +8,8 @@
 #include <algorithm>
 #include <cstdlib>
 #include <string>
+#include <tuple>
+#include <type_traits>
 
 #include "../../include/pyclaw_amd.h"
 #include "classic.hpp"
@@ -49,73 +51,105 @@ using Solvers = RpList<Advection1D, Acoustics1D, Burgers1D, Euler1D, Shallow1D, 
                        Euler5, Advection2D, Shallow2D, VcAcoustics2D, VcAdvection2D, ShallowSphere, PSystem2D, VcAcoustics3D>;
 int not_built(std::string &err, const char *why) { err = why; return PCL_EINVAL; }
 
-// The grid of sweep_kernel<., IXY, ., ., DIM1> over l.a: the same for every solver, built in or compiled at run time
-// (nblocks == 0: the tile subset is empty, nothing to launch).
-struct SweepGrid { unsigned nblocks; int ntiles_across, ntiles_along; };
-template <int IXY, bool DIM1> int sweep_grid(const SweepArgs &a, SweepGrid &g, std::string &err) {
+// One launch, stated once: the grid, the block, the stream and the kernel's arguments as a tuple of the kernel's own parameter
+// types.  fire() sends it to a kernel of this file -- A... is deduced from the kernel's function type, so a plan that does
+// not match the kernel's signature does not compile -- or to a function of the module of a user-written Riemann solver
+// (cellrp.hpp): an instantiation of the same kernel template, so its parameters are the ones the built-in launch was checked
+// against.  Each kernel family has one function that fills its plan, for the built-in and the user launcher alike.
+// grid.x == 0: nothing to launch.
+template <class... A> struct Plan { dim3 grid, block; hipStream_t stream; std::tuple<A...> args; };
+template <class... A> hipError_t fire(void (*kern)(A...), Plan<A...> &p) {
+    std::apply([&](A &...a) { hipLaunchKernelGGL(kern, p.grid, p.block, 0, p.stream, a...); }, p.args);
+    return hipGetLastError();
+}
+template <class... A> hipError_t fire(hipFunction_t f, Plan<A...> &p) {
+    return std::apply([&](A &...a) {
+        void *params[] = {(void *)&a...};
+        return hipModuleLaunchKernel(f, p.grid.x, p.grid.y, p.grid.z, p.block.x, p.block.y, p.block.z, 0, p.stream, params, nullptr);
+    }, p.args);
+}
+int launched(hipError_t e, const char *what, std::string &err) { return e == hipSuccess ? PCL_OK : hip_fail(err, what, e); }
+// a run-time flag as a template argument: f(std::true_type{}) or f(std::false_type{})
+template <class F> auto with_flag(bool on, F &&f) { return on ? f(std::true_type{}) : f(std::false_type{}); }
+
+using SweepPlan = Plan<SweepArgs, int, int>;    // sweep_kernel, sweep3_kernel, sharp_kernel: (a, tiles across, tiles along)
+using StripPlan = Plan<SweepArgs, int>;         // unsplit_x_kernel, sharp1w_kernel: (a, strips)
+
+// sweep_kernel<., IXY, ., ., DIM1> over l.a
+template <int IXY, bool DIM1> int sweep_plan(const SweepLaunch &l, SweepPlan &p, std::string &err) {
     using T = TileShape<IXY>;
+    const SweepArgs &a = l.a;
     const int n_across = IXY == 1 ? a.J : a.I + (LINE - a.mbc);  // y: columns counted from the line boundary
     const int m_along = IXY == 1 ? a.mx : a.my;
-    g.ntiles_across = (n_across + T::ACROSS - 1) / T::ACROSS;
-    g.ntiles_along = (m_along + T::NSTRIP * STRIP - 1) / (T::NSTRIP * STRIP);
-    g.nblocks = (unsigned)g.ntiles_across * (unsigned)g.ntiles_along;
+    const int ntiles_across = (n_across + T::ACROSS - 1) / T::ACROSS;
+    const int ntiles_along = (m_along + T::NSTRIP * STRIP - 1) / (T::NSTRIP * STRIP);
+    unsigned nblocks = (unsigned)ntiles_across * (unsigned)ntiles_along;
     if (a.sub != 0) {
-        if (IXY != 1 || DIM1 || a.box[0] < 0 || a.box[1] > g.ntiles_across || a.box[2] < 0 ||
-            a.box[3] > g.ntiles_along || a.box[0] >= a.box[1] || a.box[2] >= a.box[3]) {
+        if (IXY != 1 || DIM1 || a.box[0] < 0 || a.box[1] > ntiles_across || a.box[2] < 0 ||
+            a.box[3] > ntiles_along || a.box[0] >= a.box[1] || a.box[2] >= a.box[3]) {
             err = "tile subset: bad box";
             return PCL_EINVAL;
         }
         const unsigned inside = (unsigned)(a.box[1] - a.box[0]) * (unsigned)(a.box[3] - a.box[2]);
-        g.nblocks = a.sub == 1 ? inside : g.nblocks - inside;
+        nblocks = a.sub == 1 ? inside : nblocks - inside;
     }
+    p = {dim3(nblocks), dim3(256), l.stream, {a, ntiles_across, ntiles_along}};
     return PCL_OK;
 }
 
-// What the module of a user-written Riemann solver was compiled for against what this launch asks: the kernel's FWAVE and
-// CAPA are template flags (cellrp.hpp: the handle's form), so a launch that says otherwise would run the wrong kernel.
-static int user_form_check(const SweepLaunch &l, std::string &err) {
+// ---- what every launch of a user-written Riemann solver (rp == PCL_RP_CELL, cellrp.hpp) checks -------------------------
+// the kernel in `slot` of the attached module (sweep_args.hpp: CellrpSlot); null: nothing attached, or no such kernel in it
+hipFunction_t user_kernel(const SweepLaunch &l, int slot) {
+    return l.user_fns && slot >= 0 && slot < CELLRP_NSLOTS ? l.user_fns[slot] : nullptr;
+}
+int sweep_slot(int ids) { return ids >= 1 && ids <= 3 ? SLOT_SWEEP_X + ids - 1 : -1; }
+const char *const USER_NONE = "user-written Riemann solver: no compiled solver is attached (pcl_cellrp_attach)";
+const char *const USER_NO_SRC = "user-written Riemann solver: no fused source";
+// What a family asks beyond the form: the refusal where no kernel of the family is attached (PCL_ESTATE); the noun by which a
+// classic family refuses a SharpClaw handle (null: the family's `have` test covers it); the refusal of a fused source -- and,
+// for a family of whole blocks, of a tile subset.
+struct UserFamily { const char *none, *classic, *src; bool whole; };
+// have: a kernel in the family's slot, of a handle compiled for the family.  handle, step: a refusal of the family's own
+// about the handle / the step's geometry, found by the caller (null: none), in its place in the order.  Then the form: the
+// kernel's FWAVE and CAPA are template flags (cellrp.hpp: the handle's form), so a launch that says otherwise would run the
+// wrong kernel.
+int user_check(const SweepLaunch &l, bool have, const UserFamily &fam, std::string &err, const char *handle = nullptr,
+               const char *step = nullptr) {
     const CellrpSpec &u = l.user;
-    if ((l.fwave != 0) != u.fwave()) {
-        err = u.fwave() ? "user-written Riemann solver: the attached solver was compiled for f-waves and the step is in wave form"
-                        : "user-written Riemann solver: the step asks for f-waves and the attached solver was compiled in wave form";
-        return PCL_EINVAL;
-    }
-    if ((l.a.mcapa > 0) != u.capa()) {
-        err = u.capa() ? "user-written Riemann solver: the attached solver was compiled for a capacity function and the step has none"
-                       : "user-written Riemann solver: the step has a capacity function and the attached solver was compiled without one";
-        return PCL_EINVAL;
-    }
-    if ((u.naux > 0 || u.capa()) && !l.a.aux) {
-        err = u.naux > 0 ? "user-written Riemann solver: this solver reads aux arrays and there are none (pcl_put_aux)"
-                         : "user-written Riemann solver: the capacity function is a component of the aux arrays and there are none (pcl_put_aux)";
-        return PCL_EINVAL;
-    }
+    const auto no = [&err](const std::string &why) { err = why; return PCL_EINVAL; };
+    if (!have) { err = fam.none; return PCL_ESTATE; }
+    if (fam.classic && u.sharp())
+        return no(std::string("user-written Riemann solver: the attached solver was compiled for SharpClaw and holds no classic ") + fam.classic);
+    if (handle) return no(handle);
+    if (l.a.src_id != 0 || (fam.whole && l.a.sub != 0)) return no(fam.src);
+    if (step) return no(step);
+    if ((l.fwave != 0) != u.fwave())
+        return no(u.fwave() ? "user-written Riemann solver: the attached solver was compiled for f-waves and the step is in wave form"
+                            : "user-written Riemann solver: the step asks for f-waves and the attached solver was compiled in wave form");
+    if ((l.a.mcapa > 0) != u.capa())
+        return no(u.capa() ? "user-written Riemann solver: the attached solver was compiled for a capacity function and the step has none"
+                           : "user-written Riemann solver: the step has a capacity function and the attached solver was compiled without one");
+    if ((u.naux > 0 || u.capa()) && !l.a.aux)
+        return no(u.naux > 0 ? "user-written Riemann solver: this solver reads aux arrays and there are none (pcl_put_aux)"
+                             : "user-written Riemann solver: the capacity function is a component of the aux arrays and there are none (pcl_put_aux)");
     return PCL_OK;
 }
 
-// A user-written Riemann solver (cellrp.hpp): l.user_fn is sweep_kernel<UserRp, IXY, CAPA, FWAVE, DIM1> of a module compiled
-// at run time from the text of classic.hpp for the form of l.user, so the kernel's parameters are those of the launches below.
+// sweep_kernel<UserRp, IXY, CAPA, FWAVE, DIM1> of the attached module
 template <int IXY, bool DIM1> int launch_user(const SweepLaunch &l, std::string &err) {
-    if (!l.user_fn) { err = "user-written Riemann solver: no compiled solver is attached (pcl_cellrp_attach)"; return PCL_ESTATE; }
-    if (l.user.sharp()) { err = "user-written Riemann solver: the attached solver was compiled for SharpClaw and holds no classic sweep"; return PCL_EINVAL; }
-    if (l.a.src_id != 0) { err = "user-written Riemann solver: no fused source"; return PCL_EINVAL; }
-    if (int rc = user_form_check(l, err)) return rc;
-    SweepGrid g;
-    if (int rc = sweep_grid<IXY, DIM1>(l.a, g, err)) return rc;
-    if (g.nblocks == 0) return PCL_OK;
-    SweepArgs a = l.a;
-    void *params[] = {&a, &g.ntiles_across, &g.ntiles_along};
-    hipError_t e = hipModuleLaunchKernel(l.user_fn, g.nblocks, 1, 1, 256, 1, 1, 0, l.stream, params, nullptr);
-    return e == hipSuccess ? PCL_OK : hip_fail(err, "sweep launch (user-written Riemann solver)", e);
+    const hipFunction_t f = user_kernel(l, IXY == 1 ? SLOT_SWEEP_X : SLOT_SWEEP_Y);
+    if (int rc = user_check(l, f != nullptr, {USER_NONE, "sweep", USER_NO_SRC, false}, err)) return rc;
+    SweepPlan p;
+    if (int rc = sweep_plan<IXY, DIM1>(l, p, err)) return rc;
+    if (p.grid.x == 0) return PCL_OK;
+    return launched(fire(f, p), "sweep launch (user-written Riemann solver)", err);
 }
 
 template <class RP, int IXY, bool DIM1> int launch(const SweepLaunch &l, std::string &err) {
     const SweepArgs &a = l.a;
-    SweepGrid g;
-    if (int rc = sweep_grid<IXY, DIM1>(a, g, err)) return rc;
-    if (g.nblocks == 0) return PCL_OK;
-    const int ntiles_across = g.ntiles_across, ntiles_along = g.ntiles_along;
-    const dim3 grid(g.nblocks);
+    SweepPlan p;
+    if (int rc = sweep_plan<IXY, DIM1>(l, p, err)) return rc;
+    if (p.grid.x == 0) return PCL_OK;
     constexpr bool FW = IsFwave<RP>::value;       // f-wave solvers run the flux2fw.f / step1fw.f form of the kernel
     if ((l.fwave != 0) != FW) {
         err = FW ? "this Riemann solver returns f-waves: set solver.fwave = True (classic1fw / classic2fw)"
@@ -125,23 +159,14 @@ template <class RP, int IXY, bool DIM1> int launch(const SweepLaunch &l, std::st
     if (a.src_id != 0) {      // fused source term: its own instantiation (classic.hpp), Euler y pass without capa
         if constexpr (IXY == 2 && !DIM1 && std::is_same<RP, Euler5>::value) {
             if (a.src_id != 1 || a.mcapa > 0) { err = "fused source: Euler radial source, no capacity function"; return PCL_EINVAL; }
-            hipLaunchKernelGGL((sweep_kernel<RP, IXY, false, FW, DIM1, true>), grid, dim3(256), 0, l.stream, a,
-                               ntiles_across, ntiles_along);
-            hipError_t e = hipGetLastError();
-            return e == hipSuccess ? PCL_OK : hip_fail(err, "sweep launch", e);
+            return launched(fire(sweep_kernel<RP, IXY, false, FW, DIM1, true>, p), "sweep launch", err);
         } else {
             err = "fused source: only the y pass of the Euler solver has it";
             return PCL_EINVAL;
         }
     }
-    if (a.mcapa > 0)
-        hipLaunchKernelGGL((sweep_kernel<RP, IXY, true, FW, DIM1>), grid, dim3(256), 0, l.stream, a,
-                           ntiles_across, ntiles_along);
-    else
-        hipLaunchKernelGGL((sweep_kernel<RP, IXY, false, FW, DIM1>), grid, dim3(256), 0, l.stream, a,
-                           ntiles_across, ntiles_along);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? PCL_OK : hip_fail(err, "sweep launch", e);
+    return launched(with_flag(a.mcapa > 0, [&](auto C) { return fire(sweep_kernel<RP, IXY, decltype(C)::value, FW, DIM1>, p); }),
+                    "sweep launch", err);
 }
 
 }  // namespace
@@ -165,28 +190,30 @@ int launch_sweep(const SweepLaunch &l, std::string &err) {
 // a.src_id of the step.  The host (pclaw.hip: fused_step_ok) only sends what the kernel covers.
 namespace {
 static_assert(F_OWN_C == TILE_OWN_C && F_OWN_R == TILE_OWN_R, "the host counts tiles with TILE_OWN_* (sweep_args.hpp)");
-// What a one-kernel launch asks of l whatever the solver, built in or compiled at run time (naux: the aux components its
-// normal solver reads), and the grid: ntx x nty tiles, nblocks workgroups (0: the tile subset is empty, nothing to launch).
-struct Step2dsGrid { int ntx, nty; unsigned nblocks; };
-int step2ds_grid(const SweepLaunch &l, int naux, Step2dsGrid &g, std::string &err) {
+// step2ds_kernel<., ., ., .> over l: what a one-kernel launch asks of l whatever the solver, built in or compiled at run time
+// (naux: the aux components its normal solver reads), the grid of ntx x nty tiles and the kernel's thirteen arguments.
+using Step2dsPlan = Plan<SweepArgs, int, int, unsigned *, double2 *, const int *, const TileNext *, unsigned *, unsigned,
+                         unsigned *, int, unsigned *, int>;
+int step2ds_plan(const SweepLaunch &l, int naux, Step2dsPlan &p, std::string &err) {
     const SweepArgs &a = l.a;
     if (a.mbc != HALO) { err = "step2ds kernel: mbc = 2"; return PCL_EINVAL; }
     const bool capa = a.mcapa > 0;
     if ((capa || naux > 0) && !a.aux) { err = "step2ds kernel: this solver reads aux arrays and there are none"; return PCL_EINVAL; }
     // quiet tiles: the bookkeeping of the aux-free instantiations without a capacity function only (classic_fused.hpp)
     if ((capa || naux > 0) && (l.tq_out || l.tq_list)) { err = "step2ds kernel: no quiet-tile bookkeeping with aux arrays"; return PCL_EINVAL; }
-    g.ntx = (a.mx + F_OWN_C - 1) / F_OWN_C;
-    g.nty = (a.my + F_OWN_R - 1) / F_OWN_R;
-    g.nblocks = (unsigned)g.ntx * (unsigned)g.nty;
+    const int ntx = (a.mx + F_OWN_C - 1) / F_OWN_C, nty = (a.my + F_OWN_R - 1) / F_OWN_R;
+    unsigned nblocks = (unsigned)ntx * (unsigned)nty;
     if (a.sub != 0) {
-        if (a.box[0] < 0 || a.box[1] > g.nty || a.box[2] < 0 || a.box[3] > g.ntx || a.box[0] >= a.box[1] || a.box[2] >= a.box[3]) {
+        if (a.box[0] < 0 || a.box[1] > nty || a.box[2] < 0 || a.box[3] > ntx || a.box[0] >= a.box[1] || a.box[2] >= a.box[3]) {
             err = "step2ds tile subset: bad box";
             return PCL_EINVAL;
         }
         const unsigned inside = (unsigned)(a.box[1] - a.box[0]) * (unsigned)(a.box[3] - a.box[2]);
-        g.nblocks = a.sub == 1 ? inside : g.nblocks - inside;
-        if (g.nblocks == 0) return PCL_OK;
+        nblocks = a.sub == 1 ? inside : nblocks - inside;
     }
+    p = {dim3(nblocks), dim3(F_THREADS), l.stream,
+         {a, ntx, nty, l.tq_out, l.tq_cfl, l.tq_list, l.tq_next, l.tq_ring, l.ring_seq, l.tq_reuse, l.rowreuse, l.tq_ycol, l.ycol}};
+    if (a.sub != 0 && nblocks == 0) return PCL_OK;       // the tile subset is empty
     // a list launch: the tiles the hand-over+list kernel behind the previous launch listed (classic_fused.hpp); one
     // workgroup per tile of the grid, those past the list's end return at once
     const bool list = l.tq_list != nullptr;
@@ -197,58 +224,36 @@ int step2ds_grid(const SweepLaunch &l, int naux, Step2dsGrid &g, std::string &er
     return PCL_OK;
 }
 
-// A user-written Riemann solver compiled with the one-kernel step (cellrp.hpp: spec.onek): l.user_fn is
-// step2ds_kernel<UserRp, FWAVE, false, CAPA> of the module compiled at run time from the text of classic_fused.hpp, FWAVE
-// and CAPA the form of l.user, so the grid, the block and the thirteen parameters are those of launch_step2ds_t below.
+// step2ds_kernel<UserRp, FWAVE, false, CAPA> of a module compiled with the one-kernel step (cellrp.hpp: spec.onek)
 int launch_step2ds_user(const SweepLaunch &l, std::string &err) {
-    if (!l.user_fn || !l.user.onek) {
-        err = "user-written Riemann solver: no solver compiled with the one-kernel step is attached (pcl_cellrp_compile_onek, pcl_cellrp_attach)";
-        return PCL_ESTATE;
-    }
-    if (l.user.sharp()) { err = "user-written Riemann solver: the attached solver was compiled for SharpClaw and holds no classic step"; return PCL_EINVAL; }
-    if (l.a.src_id != 0) { err = "user-written Riemann solver: no fused source"; return PCL_EINVAL; }
-    if (int rc = user_form_check(l, err)) return rc;
-    Step2dsGrid g;
-    if (int rc = step2ds_grid(l, l.user.naux, g, err)) return rc;
-    if (g.nblocks == 0) return PCL_OK;
-    SweepArgs a = l.a;
-    unsigned *tq_out = l.tq_out, *tq_ring = l.tq_ring, *tq_reuse = l.tq_reuse, *tq_ycol = l.tq_ycol;
-    double2 *tq_cfl = l.tq_cfl;
-    const int *tq_list = l.tq_list;
-    const TileNext *tq_next = l.tq_next;
-    unsigned ring_seq = l.ring_seq;
-    int rowreuse = l.rowreuse, ycol = l.ycol;
-    void *params[] = {&a, &g.ntx, &g.nty, &tq_out, &tq_cfl, &tq_list, &tq_next, &tq_ring, &ring_seq, &tq_reuse, &rowreuse, &tq_ycol, &ycol};
-    hipError_t e = hipModuleLaunchKernel(l.user_fn, g.nblocks, 1, 1, F_THREADS, 1, 1, 0, l.stream, params, nullptr);
-    return e == hipSuccess ? PCL_OK : hip_fail(err, "step2ds launch (user-written Riemann solver)", e);
+    const hipFunction_t f = user_kernel(l, SLOT_ONEK);
+    const UserFamily fam = {"user-written Riemann solver: no solver compiled with the one-kernel step is attached (pcl_cellrp_compile_onek, pcl_cellrp_attach)",
+                            "step", USER_NO_SRC, false};
+    if (int rc = user_check(l, f && l.user.onek, fam, err)) return rc;
+    Step2dsPlan p;
+    if (int rc = step2ds_plan(l, l.user.naux, p, err)) return rc;
+    if (p.grid.x == 0) return PCL_OK;
+    return launched(fire(f, p), "step2ds launch (user-written Riemann solver)", err);
 }
 
 template <class RP> int launch_step2ds_t(const SweepLaunch &l, std::string &err) {
     const SweepArgs &a = l.a;
     constexpr bool FW = IsFwave<RP>::value;
     if ((l.fwave != 0) != FW) { err = "solver.fwave does not match the Riemann solver"; return PCL_EINVAL; }
-    Step2dsGrid g;
-    if (int rc = step2ds_grid(l, RP::NAUX, g, err)) return rc;
-    if (g.nblocks == 0) return PCL_OK;
-    const int ntx = g.ntx, nty = g.nty;
+    Step2dsPlan p;
+    if (int rc = step2ds_plan(l, RP::NAUX, p, err)) return rc;
+    if (p.grid.x == 0) return PCL_OK;
     const bool capa = a.mcapa > 0;
     if (a.src_id != 0 && !(std::is_same<RP, Euler5>::value && a.src_id == 1 && !capa)) {
         err = "fused source: only the Euler solver's radial source, no capacity function";
         return PCL_EINVAL;
     }
-    const dim3 grid(g.nblocks);
+    hipError_t e = hipSuccess;
     if (a.src_id != 0) {
-        if constexpr (std::is_same<RP, Euler5>::value)
-            hipLaunchKernelGGL((step2ds_kernel<RP, FW, true>), grid, dim3(F_THREADS), 0, l.stream, a, ntx, nty, l.tq_out,
-                               l.tq_cfl, l.tq_list, l.tq_next, l.tq_ring, l.ring_seq, l.tq_reuse, l.rowreuse, l.tq_ycol, l.ycol);
-    } else if (capa)
-        hipLaunchKernelGGL((step2ds_kernel<RP, FW, false, true>), grid, dim3(F_THREADS), 0, l.stream, a, ntx, nty, l.tq_out,
-                           l.tq_cfl, l.tq_list, l.tq_next, l.tq_ring, l.ring_seq, l.tq_reuse, l.rowreuse, l.tq_ycol, l.ycol);
-    else
-        hipLaunchKernelGGL((step2ds_kernel<RP, FW, false>), grid, dim3(F_THREADS), 0, l.stream, a, ntx, nty, l.tq_out,
-                           l.tq_cfl, l.tq_list, l.tq_next, l.tq_ring, l.ring_seq, l.tq_reuse, l.rowreuse, l.tq_ycol, l.ycol);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? PCL_OK : hip_fail(err, "step2ds launch", e);
+        if constexpr (std::is_same<RP, Euler5>::value) e = fire(step2ds_kernel<RP, FW, true>, p);
+    } else
+        e = with_flag(capa, [&](auto C) { return fire(step2ds_kernel<RP, FW, false, decltype(C)::value>, p); });
+    return launched(e, "step2ds launch", err);
 }
 }  // namespace
 int launch_step2ds(const SweepLaunch &l, std::string &err) {
@@ -261,55 +266,42 @@ int launch_step2ds(const SweepLaunch &l, std::string &err) {
     return rc != RP_NONE ? rc : not_built(err, "step2ds kernel: no instantiation for this Riemann solver");
 }
 
-// The grid of sweep3_kernel<., DIR, .> over l.a, DIR = l.ids: the same for the built-in solver and one compiled at run time
+// sweep3_kernel<., DIR, .> over l.a, DIR = l.ids
 namespace {
-struct Sweep3Grid { int ntiles_ac, ntiles_al; };
-Sweep3Grid sweep3_grid(const SweepLaunch &l) {
+SweepPlan sweep3_plan(const SweepLaunch &l) {
     const SweepArgs &a = l.a;
     const int n_ac = l.ids == 1 ? a.n_ac : a.n_ac + (LINE - a.mbc);  // y, z: columns counted from the line boundary
     const int ac = l.ids == 1 ? Tile3Shape<1>::AC : Tile3Shape<2>::AC, adv = l.ids == 1 ? Tile3Shape<1>::ADV : Tile3Shape<2>::ADV;
     static_assert(Tile3Shape<3>::AC == Tile3Shape<2>::AC && Tile3Shape<3>::ADV == Tile3Shape<2>::ADV, "y and z: one tile shape");
-    return {(n_ac + ac - 1) / ac, (a.m_al + adv - 1) / adv};
+    const int ntiles_ac = (n_ac + ac - 1) / ac, ntiles_al = (a.m_al + adv - 1) / adv;
+    return {dim3((unsigned)ntiles_ac * (unsigned)ntiles_al, (unsigned)a.n_b), dim3(256), l.stream, {a, ntiles_ac, ntiles_al}};
 }
 
-// A user-written Riemann solver (cellrp.hpp) in 3-D: l.user_fn is sweep3_kernel<UserRp, l.ids, CAPA> of a module compiled at
-// run time from the text of classic.hpp, so the kernel's parameters and grid are those of the built-in launch below.
+// sweep3_kernel<UserRp, l.ids, CAPA> of a module compiled for the 3-D sweeps
 int launch_sweep3_user(const SweepLaunch &l, std::string &err) {
-    if (!l.user_fn) { err = "user-written Riemann solver: no compiled solver is attached (pcl_cellrp_attach)"; return PCL_ESTATE; }
-    if (l.user.sharp()) { err = "user-written Riemann solver: the attached solver was compiled for SharpClaw and holds no classic sweep"; return PCL_EINVAL; }
-    if (l.user.ndim != 3) { err = "user-written Riemann solver: the attached solver was not compiled for the 3-D sweeps (pcl_cellrp_compile3)"; return PCL_EINVAL; }
-    if (l.ids < 1 || l.ids > 3) { err = "3-D sweep: direction must be 1, 2 or 3"; return PCL_EINVAL; }
-    if (l.a.src_id != 0) { err = "user-written Riemann solver: no fused source"; return PCL_EINVAL; }
-    if (l.a.mbc != HALO) { err = "3-D sweep: mbc = 2"; return PCL_EINVAL; }
-    if (int rc = user_form_check(l, err)) return rc;
-    const Sweep3Grid g = sweep3_grid(l);
-    SweepArgs a = l.a;
-    int ntiles_ac = g.ntiles_ac, ntiles_al = g.ntiles_al;
-    void *params[] = {&a, &ntiles_ac, &ntiles_al};
-    hipError_t e = hipModuleLaunchKernel(l.user_fn, (unsigned)ntiles_ac * (unsigned)ntiles_al, (unsigned)a.n_b, 1, 256, 1, 1, 0,
-                                         l.stream, params, nullptr);
-    return e == hipSuccess ? PCL_OK : hip_fail(err, "sweep3 launch (user-written Riemann solver)", e);
+    const hipFunction_t f = user_kernel(l, sweep_slot(l.ids));
+    const char *handle = l.user.ndim != 3 ? "user-written Riemann solver: the attached solver was not compiled for the 3-D sweeps (pcl_cellrp_compile3)"
+                         : (l.ids < 1 || l.ids > 3) ? "3-D sweep: direction must be 1, 2 or 3" : nullptr;
+    if (int rc = user_check(l, f != nullptr, {USER_NONE, "sweep", USER_NO_SRC, false}, err, handle,
+                            l.a.mbc != HALO ? "3-D sweep: mbc = 2" : nullptr))
+        return rc;
+    SweepPlan p = sweep3_plan(l);
+    return launched(fire(f, p), "sweep3 launch (user-written Riemann solver)", err);
 }
 }  // namespace
 
 // 3-D dimension-split sweep along direction l.ids (classic.hpp: sweep3_kernel)
 int launch_sweep3(const SweepLaunch &l, std::string &err) {
-    const SweepArgs &a = l.a;
     if (l.rp == PCL_RP_CELL) return launch_sweep3_user(l, err);
     if (l.fwave) { err = "fwave: no 3-D f-wave Riemann solver is built in"; return PCL_EINVAL; }
     if (l.rp != VcAcoustics3D::ID) { err = "Riemann solver id is not a 3-D solver"; return PCL_EINVAL; }
-    const Sweep3Grid g = sweep3_grid(l);
-    const int ntiles_ac = g.ntiles_ac, ntiles_al = g.ntiles_al;
-    const dim3 grid((unsigned)ntiles_ac * (unsigned)ntiles_al, (unsigned)a.n_b);
-    if (a.mcapa > 0) {      // capacity function (step3ds.f:138-141,196-200)
-        if (l.ids == 1) hipLaunchKernelGGL((sweep3_kernel<VcAcoustics3D, 1, true>), grid, dim3(256), 0, l.stream, a, ntiles_ac, ntiles_al);
-        else if (l.ids == 2) hipLaunchKernelGGL((sweep3_kernel<VcAcoustics3D, 2, true>), grid, dim3(256), 0, l.stream, a, ntiles_ac, ntiles_al);
-        else hipLaunchKernelGGL((sweep3_kernel<VcAcoustics3D, 3, true>), grid, dim3(256), 0, l.stream, a, ntiles_ac, ntiles_al);
-    } else if (l.ids == 1) hipLaunchKernelGGL((sweep3_kernel<VcAcoustics3D, 1>), grid, dim3(256), 0, l.stream, a, ntiles_ac, ntiles_al);
-    else if (l.ids == 2) hipLaunchKernelGGL((sweep3_kernel<VcAcoustics3D, 2>), grid, dim3(256), 0, l.stream, a, ntiles_ac, ntiles_al);
-    else hipLaunchKernelGGL((sweep3_kernel<VcAcoustics3D, 3>), grid, dim3(256), 0, l.stream, a, ntiles_ac, ntiles_al);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? PCL_OK : hip_fail(err, "sweep3 launch", e);
+    SweepPlan p = sweep3_plan(l);
+    using RP = VcAcoustics3D;
+    const hipError_t e = with_flag(l.a.mcapa > 0, [&](auto C) {      // capacity function (step3ds.f:138-141,196-200)
+        constexpr bool CAPA = decltype(C)::value;
+        return l.ids == 1 ? fire(sweep3_kernel<RP, 1, CAPA>, p) : l.ids == 2 ? fire(sweep3_kernel<RP, 2, CAPA>, p) : fire(sweep3_kernel<RP, 3, CAPA>, p);
+    });
+    return launched(e, "sweep3 launch", err);
 }
 
 // unsplit 3-D step, one direction: march3p_kernel (classic3.hpp), one launch per direction
@@ -431,11 +423,22 @@ bool x_interior_box(const BlockGeom &a, int box[4], int ntiles[2]) {
 
 // unsplit step (step2.f / step2qcor.f): both phases without scratch planes (classic.hpp: unsplit_x/y_kernel)
 namespace {
+// The tile form of the two phases, U slices per workgroup: unsplit_x_kernel<., ., U, .> and unsplit_y_kernel<., ., U, ., .>
+StripPlan unsplit_x_plan(const SweepArgs &a, int U, hipStream_t stream) {
+    const int nstrips = (a.mx + STRIP - 1) / STRIP, ntr = (a.my + (U - 2) - 1) / (U - 2);
+    return {dim3((unsigned)nstrips * ntr), dim3((unsigned)U * WAVE), stream, {a, nstrips}};
+}
+using UnsplitYPlan = Plan<SweepArgs, int, const double *>;      // (a, tiles along x, the x phase's result)
+UnsplitYPlan unsplit_y_plan(const SweepArgs &a, int U, const double *qx, hipStream_t stream) {
+    const int nti = (a.mx + (U - 2) - 1) / (U - 2), ntj = (a.my + STRIP - 1) / STRIP;
+    return {dim3((unsigned)nti * ntj), dim3((unsigned)U * WAVE), stream, {a, nti, qx}};
+}
+
 template <class RP, int UX, int UY> int launch_unsplit_u(const SweepLaunch &l, const double *qx, std::string &err) {
     SweepArgs a = l.a;
+    constexpr bool FW = IsFwave<RP>::value;
+    hipError_t e;
     if (l.ids == 1) {
-        const int nstrips = (a.mx + STRIP - 1) / STRIP;
-        const int ntr = (a.my + (UX - 2) - 1) / (UX - 2);
         if (a.sub != 0) {
             // tiles whose 64 cells x UX rows lie inside the interior: cells mbc-2+60*ta .. +63 within [mbc, mbc+mx),
             // rows mbc-1+(UX-2)*tr .. +UX-1 within [mbc, mbc+my)
@@ -444,19 +447,13 @@ template <class RP, int UX, int UY> int launch_unsplit_u(const SweepLaunch &l, c
             a.box[2] = 1;
             a.box[3] = a.mx >= 62 ? (a.mx - 62) / STRIP + 1 : 0;
         }
-        if (a.mcapa > 0)
-            hipLaunchKernelGGL((unsplit_x_kernel<RP, IsFwave<RP>::value, UX, true>), dim3((unsigned)nstrips * ntr),
-                               dim3(UX * WAVE), 0, l.stream, a, nstrips);
-        else
-            hipLaunchKernelGGL((unsplit_x_kernel<RP, IsFwave<RP>::value, UX>), dim3((unsigned)nstrips * ntr),
-                               dim3(UX * WAVE), 0, l.stream, a, nstrips);
+        StripPlan p = unsplit_x_plan(a, UX, l.stream);
+        e = with_flag(a.mcapa > 0, [&](auto C) { return fire(unsplit_x_kernel<RP, FW, UX, decltype(C)::value>, p); });
     } else {
-        const int nti = (a.mx + (UY - 2) - 1) / (UY - 2);
-        const int ntj = (a.my + STRIP - 1) / STRIP;
         if constexpr (RP::NAUX == 0 && UY == 16) {
             // marching y phase (classic.hpp: unsplit_ym_kernel): segments of `seg` lines of 16 columns; enough
             // workgroups for ~4 rounds over the 256 CUs, warm-up step of a segment <= 1/8 of its work
-            const int nlines = (a.mx + 15) / 16;
+            const int nlines = (a.mx + 15) / 16, ntj = (a.my + STRIP - 1) / STRIP;
             int nseg = (1024 + ntj - 1) / ntj;
             if (nseg > (nlines + 7) / 8) nseg = (nlines + 7) / 8;
             if (nseg < 1) nseg = 1;
@@ -476,29 +473,22 @@ template <class RP, int UX, int UY> int launch_unsplit_u(const SweepLaunch &l, c
                 } else
                     hipLaunchKernelGGL((unsplit_ym_kernel<RP, IsFwave<RP>::value, false, NWY>), dim3((unsigned)ntj * nseg),
                                        dim3(NWY * WAVE), 0, l.stream, a, ntj, seg, qx);
-                hipError_t e = hipGetLastError();
-                if (e != hipSuccess) return hip_fail(err, "unsplit y (marching) launch", e);
-                return PCL_OK;
+                return launched(hipGetLastError(), "unsplit y (marching) launch", err);
             }
         }
+        UnsplitYPlan p = unsplit_y_plan(a, UY, qx, l.stream);
         if (a.src_id != 0) {       // fused source term: Euler solver without a capacity function
             if constexpr (std::is_same<RP, Euler5>::value) {
                 if (a.src_id != 1 || a.mcapa > 0) { err = "fused source: Euler radial source, no capacity function"; return PCL_EINVAL; }
-                hipLaunchKernelGGL((unsplit_y_kernel<RP, false, UY, false, true>), dim3((unsigned)nti * ntj),
-                                   dim3(UY * WAVE), 0, l.stream, a, nti, qx);
+                e = fire(unsplit_y_kernel<RP, false, UY, false, true>, p);
             } else {
                 err = "fused source: only the Euler solver has it";
                 return PCL_EINVAL;
             }
-        } else if (a.mcapa > 0)
-            hipLaunchKernelGGL((unsplit_y_kernel<RP, IsFwave<RP>::value, UY, true>), dim3((unsigned)nti * ntj),
-                               dim3(UY * WAVE), 0, l.stream, a, nti, qx);
-        else
-            hipLaunchKernelGGL((unsplit_y_kernel<RP, IsFwave<RP>::value, UY>), dim3((unsigned)nti * ntj),
-                               dim3(UY * WAVE), 0, l.stream, a, nti, qx);
+        } else
+            e = with_flag(a.mcapa > 0, [&](auto C) { return fire(unsplit_y_kernel<RP, FW, UY, decltype(C)::value>, p); });
     }
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? PCL_OK : hip_fail(err, "unsplit launch", e);
+    return launched(e, "unsplit launch", err);
 }
 template <class RP> int launch_unsplit_t(const SweepLaunch &l, const double *qx, std::string &err) {
     // slices per workgroup in the x / y phase.  16 wavefronts per workgroup leave 128 VGPRs per lane.  The Euler kernels
@@ -511,35 +501,24 @@ template <class RP> int launch_unsplit_t(const SweepLaunch &l, const double *qx,
         return launch_unsplit_u<RP, 16, 16>(l, qx, err);
     } else return launch_unsplit_u<RP, 16, 16>(l, qx, err);
 }
-// A user-written Riemann solver with a transverse body (cellrp.hpp): l.user_fn is unsplit_x_kernel<UserRp, FWAVE, U, CAPA>
-// or unsplit_y_kernel<UserRp, FWAVE, U, CAPA, false> of the module compiled at run time, FWAVE and CAPA the form of l.user,
-// U = l.user.slices(); the parameters and grids are those of launch_unsplit_u.  Always the tile form of the y phase: the
-// marching kernel stays with the built-in solvers.
+// unsplit_x_kernel<UserRp, FWAVE, U, CAPA> or unsplit_y_kernel<UserRp, FWAVE, U, CAPA, false> of a module compiled with a
+// transverse body, U = l.user.slices().  Always the tile form of the y phase: the marching kernel stays with the built-in
+// solvers.
 int launch_unsplit_user(const SweepLaunch &l, const double *qx, std::string &err) {
     const int U = l.user.slices();
-    if (!l.user_fn || U < 3) {
-        err = "user-written Riemann solver: no compiled solver with a transverse body is attached (pcl_cellrp_attach)";
-        return PCL_ESTATE;
-    }
-    if (l.a.src_id != 0 || l.a.sub != 0) {
-        err = "user-written Riemann solver, unsplit step: no fused source, whole blocks";
-        return PCL_EINVAL;
-    }
-    if (int rc = user_form_check(l, err)) return rc;
-    SweepArgs a = l.a;
+    const hipFunction_t f = user_kernel(l, l.ids == 1 ? SLOT_UNSPLIT_X : SLOT_UNSPLIT_Y);
+    const UserFamily fam = {"user-written Riemann solver: no compiled solver with a transverse body is attached (pcl_cellrp_attach)", nullptr,
+                            "user-written Riemann solver, unsplit step: no fused source, whole blocks", true};
+    if (int rc = user_check(l, f && U >= 3, fam, err)) return rc;
     hipError_t e;
     if (l.ids == 1) {
-        int nstrips = (a.mx + STRIP - 1) / STRIP;
-        const int ntr = (a.my + (U - 2) - 1) / (U - 2);
-        void *params[] = {&a, &nstrips};
-        e = hipModuleLaunchKernel(l.user_fn, (unsigned)nstrips * ntr, 1, 1, (unsigned)U * WAVE, 1, 1, 0, l.stream, params, nullptr);
+        StripPlan p = unsplit_x_plan(l.a, U, l.stream);
+        e = fire(f, p);
     } else {
-        int nti = (a.mx + (U - 2) - 1) / (U - 2);
-        const int ntj = (a.my + STRIP - 1) / STRIP;
-        void *params[] = {&a, &nti, &qx};
-        e = hipModuleLaunchKernel(l.user_fn, (unsigned)nti * ntj, 1, 1, (unsigned)U * WAVE, 1, 1, 0, l.stream, params, nullptr);
+        UnsplitYPlan p = unsplit_y_plan(l.a, U, qx, l.stream);
+        e = fire(f, p);
     }
-    return e == hipSuccess ? PCL_OK : hip_fail(err, "unsplit launch (user-written Riemann solver)", e);
+    return launched(e, "unsplit launch (user-written Riemann solver)", err);
 }
 }  // namespace
 
@@ -558,10 +537,10 @@ int launch_unsplit(const SweepLaunch &l, const double *qx, std::string &err) {
 
 // SharpClaw: dq of one direction (x writes dq, y accumulates)
 namespace {
-// The grid of sharp_kernel<., ixy, ., ., K> with ta strips per tile over a, the same for every solver, built in or compiled
-// at run time; the tile subset of a decomposed x pass gets its box here (a.sub is dropped where there is none).
-struct SharpGrid { unsigned nblocks; int ntiles_across, ntiles_along; };
-SharpGrid sharp_grid(SweepArgs &a, int ixy, int K, int ta) {
+// sharp_kernel<., ixy, ., ., K> with ta strips per tile over l.a; the tile subset of a decomposed x pass gets its box here
+// (a.sub is dropped where there is none).
+SweepPlan sharp_plan(const SweepLaunch &l, int ixy, int K, int ta) {
+    SweepArgs a = l.a;
     const int SH = K, SS = sstrip(K);
     if (ixy == 1 && a.sub != 0) {
         // x-pass tiles whose 16 rows x 64 cells lie inside the interior: rows 16*tb .. +15 within [mbc, mbc+my), cells
@@ -573,53 +552,43 @@ SharpGrid sharp_grid(SweepArgs &a, int ixy, int K, int ta) {
     } else a.sub = 0;
     const int n_across = ixy == 1 ? a.J : a.I + (LINE - a.mbc);
     const int m_along = ixy == 1 ? a.mx : a.my;
-    SharpGrid g;
-    g.ntiles_across = (n_across + ta - 1) / ta;
-    g.ntiles_along = (m_along + SS - 1) / SS;
-    g.nblocks = (unsigned)g.ntiles_across * (unsigned)g.ntiles_along;
-    return g;
+    const int ntiles_across = (n_across + ta - 1) / ta, ntiles_along = (m_along + SS - 1) / SS;
+    return {dim3((unsigned)ntiles_across * (unsigned)ntiles_along), dim3(256), l.stream, {a, ntiles_across, ntiles_along}};
 }
 // sharp1w_kernel: strips of sstrip(3) cells, four to a workgroup
-struct Sharp1wGrid { unsigned nblocks; int nstrips; };
-Sharp1wGrid sharp1w_grid(const SweepArgs &a) {
-    const int nstrips = (a.mx + sstrip(3) - 1) / sstrip(3);
-    return {(unsigned)((nstrips + 3) / 4), nstrips};
+StripPlan sharp1w_plan(const SweepLaunch &l) {
+    const int nstrips = (l.a.mx + sstrip(3) - 1) / sstrip(3);
+    return {dim3((unsigned)((nstrips + 3) / 4)), dim3(256), l.stream, {l.a, nstrips}};
 }
 
 template <class RP, int IXY, int K> int launch_sharp_k(const SweepLaunch &l, std::string &err) {
-    SweepArgs a = l.a;
-    const SharpGrid g = sharp_grid(a, IXY, K, sharp_tile_across<RP, IXY>());
-    const int ntiles_across = g.ntiles_across, ntiles_along = g.ntiles_along;
-    const dim3 grid(g.nblocks);
+    const SweepArgs &a = l.a;
+    SweepPlan p = sharp_plan(l, IXY, K, sharp_tile_across<RP, IXY>());
     const bool capa = a.mcapa > 0;
-#define PCL_SHARP_LAUNCH(CAPA_, LIM_)                                                                  \
-    hipLaunchKernelGGL((sharp_kernel<RP, IXY, CAPA_, LIM_, K>), grid, dim3(256), 0, l.stream, a, ntiles_across, \
-                       ntiles_along)
+    const auto go = [&](auto LIM) {
+        return with_flag(capa, [&](auto C) { return fire(sharp_kernel<RP, IXY, decltype(C)::value, decltype(LIM)::value, K>, p); });
+    };
+    using std::integral_constant;
+    hipError_t e;
     if (a.src_id != 0) {
         // deltaq += dq_src inside the last pass: built for the shock-bubble configuration only
         if constexpr (std::is_same<RP, Euler5>::value && IXY == 2 && K == 3) {
             if (a.src_id != 1 || capa || l.lim_type != 2) { err = "SharpClaw: the fused dq source needs euler_5wave_2d, WENO5 (lim_type 2), no capacity function"; return PCL_EINVAL; }
-            hipLaunchKernelGGL((sharp_kernel<RP, IXY, false, 2, K, true>), grid, dim3(256), 0, l.stream, a, ntiles_across,
-                               ntiles_along);
-            hipError_t e = hipGetLastError();
-            return e == hipSuccess ? PCL_OK : hip_fail(err, "sharp launch", e);
+            e = fire(sharp_kernel<RP, IXY, false, 2, K, true>, p);
         } else {
             err = "SharpClaw: the fused dq source needs euler_5wave_2d, WENO5 (lim_type 2), no capacity function";
             return PCL_EINVAL;
         }
-    }
-    if constexpr (K > 3) {
+    } else if constexpr (K > 3) {
         if (l.lim_type != 2) { err = "SharpClaw: weno_order > 5 needs lim_type 2"; return PCL_EINVAL; }
-        if (capa) PCL_SHARP_LAUNCH(true, 2); else PCL_SHARP_LAUNCH(false, 2);
+        e = go(integral_constant<int, 2>{});
     } else {
-        if (l.lim_type == 1) { if (capa) PCL_SHARP_LAUNCH(true, 1); else PCL_SHARP_LAUNCH(false, 1); }
-        else if (l.lim_type == 2) { if (capa) PCL_SHARP_LAUNCH(true, 2); else PCL_SHARP_LAUNCH(false, 2); }
-        else if (l.lim_type == 3) { if (capa) PCL_SHARP_LAUNCH(true, 3); else PCL_SHARP_LAUNCH(false, 3); }
+        if (l.lim_type == 1) e = go(integral_constant<int, 1>{});
+        else if (l.lim_type == 2) e = go(integral_constant<int, 2>{});
+        else if (l.lim_type == 3) e = go(integral_constant<int, 3>{});
         else { err = "SharpClaw: lim_type must be 1 (tvd2), 2 (WENO5) or 3 (legacy WENO5)"; return PCL_EINVAL; }
     }
-#undef PCL_SHARP_LAUNCH
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? PCL_OK : hip_fail(err, "sharp launch", e);
+    return launched(e, "sharp launch", err);
 }
 // mbc = (weno_order+1)/2 (sharpclaw.py:479).  HIGH = this solver also has the kernels of weno_order 7..17 (mbc 4..9):
 // the 1-D solvers, 2-D advection, acoustics and Euler; the others are built for mbc = 3 only.
@@ -645,37 +614,23 @@ template <class RP, int IXY, bool HIGH> int launch_sharp_t(const SweepLaunch &l,
 
 namespace {
 template <class RP> int launch_sharp1w(const SweepLaunch &l, std::string &err) {
-    const SweepArgs &a = l.a;
-    const Sharp1wGrid g = sharp1w_grid(a);
-    const int nstrips = g.nstrips;
-    const dim3 grid(g.nblocks);
-    const bool capa = a.mcapa > 0;
-#define PCL_SHARP1W_LAUNCH(LIM_, CAPA_) \
-    hipLaunchKernelGGL((sharp1w_kernel<RP, LIM_, CAPA_>), grid, dim3(256), 0, l.stream, a, nstrips)
-    if (l.lim_type == 1) { if (capa) PCL_SHARP1W_LAUNCH(1, true); else PCL_SHARP1W_LAUNCH(1, false); }
-    else { if (capa) PCL_SHARP1W_LAUNCH(2, true); else PCL_SHARP1W_LAUNCH(2, false); }
-#undef PCL_SHARP1W_LAUNCH
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? PCL_OK : hip_fail(err, "sharp (wave-based) launch", e);
+    StripPlan p = sharp1w_plan(l);
+    const auto go = [&](auto LIM) {
+        return with_flag(l.a.mcapa > 0, [&](auto C) { return fire(sharp1w_kernel<RP, decltype(LIM)::value, decltype(C)::value>, p); });
+    };
+    const hipError_t e = l.lim_type == 1 ? go(std::integral_constant<int, 1>{}) : go(std::integral_constant<int, 2>{});
+    return launched(e, "sharp (wave-based) launch", err);
 }
-}  // namespace
 
-namespace {
-// A user-written Riemann solver under SharpClaw (cellrp.hpp): l.user_fn is sharp_kernel<UserRp, ids, CAPA, LIM, K> or, with
-// char_decomp = 1, sharp1w_kernel<UserRp, LIM, CAPA> of the module compiled at run time -- one (LIM, K, char_decomp), the
-// ones of l.user, with CAPA its form's -- so this launch must ask for exactly that; the parameters and grids are those of
-// launch_sharp_k / launch_sharp1w.  Whole blocks, no fused dq source.
+// sharp_kernel<UserRp, ids, CAPA, LIM, K> or, with char_decomp = 1, sharp1w_kernel<UserRp, LIM, CAPA> of a module compiled for
+// SharpClaw -- one (LIM, K, char_decomp), the ones of l.user, with CAPA its form's -- so this launch must ask for exactly
+// that.  Whole blocks, no fused dq source.
 int launch_sharp_user(const SweepLaunch &l, std::string &err) {
     const CellrpSpec &u = l.user;
-    if (!l.user_fn || !u.sharp()) {
-        err = "user-written Riemann solver: no solver compiled for SharpClaw is attached (pcl_cellrp_compile_sharp, pcl_create_cellrp)";
-        return PCL_ESTATE;
-    }
-    if (l.a.src_id != 0 || l.a.sub != 0) {
-        err = "user-written Riemann solver under SharpClaw: no fused dq source, whole blocks";
-        return PCL_EINVAL;
-    }
-    if (int rc = user_form_check(l, err)) return rc;
+    const hipFunction_t f = user_kernel(l, sweep_slot(l.ids));
+    const UserFamily fam = {"user-written Riemann solver: no solver compiled for SharpClaw is attached (pcl_cellrp_compile_sharp, pcl_create_cellrp)", nullptr,
+                            "user-written Riemann solver under SharpClaw: no fused dq source, whole blocks", true};
+    if (int rc = user_check(l, f && u.sharp(), fam, err)) return rc;
     if (l.lim_type != u.lim_type) {
         err = "user-written Riemann solver: the attached solver was compiled for lim_type " + std::to_string(u.lim_type) +
               " and the stage asks for lim_type " + std::to_string(l.lim_type);
@@ -691,20 +646,17 @@ int launch_sharp_user(const SweepLaunch &l, std::string &err) {
               " and the stage asks for char_decomp " + std::to_string(l.char_decomp);
         return PCL_EINVAL;
     }
-    SweepArgs a = l.a;
     hipError_t e;
     if (l.char_decomp == 1) {
         if (l.ndim != 1 || l.a.mbc != 3) { err = "SharpClaw char_decomp = 1: 1-D, mbc 3"; return PCL_EINVAL; }
-        Sharp1wGrid g = sharp1w_grid(a);
-        void *params[] = {&a, &g.nstrips};
-        e = hipModuleLaunchKernel(l.user_fn, g.nblocks, 1, 1, 256, 1, 1, 0, l.stream, params, nullptr);
+        StripPlan p = sharp1w_plan(l);
+        e = fire(f, p);
     } else {
         const int ixy = l.ndim == 1 ? 1 : l.ids;
-        SharpGrid g = sharp_grid(a, ixy, u.mbc(), sharp_tile_across_n(ixy, u.naux));
-        void *params[] = {&a, &g.ntiles_across, &g.ntiles_along};
-        e = hipModuleLaunchKernel(l.user_fn, g.nblocks, 1, 1, 256, 1, 1, 0, l.stream, params, nullptr);
+        SweepPlan p = sharp_plan(l, ixy, u.mbc(), sharp_tile_across_n(ixy, u.naux));
+        e = fire(f, p);
     }
-    return e == hipSuccess ? PCL_OK : hip_fail(err, "sharp launch (user-written Riemann solver)", e);
+    return launched(e, "sharp launch (user-written Riemann solver)", err);
 }
 }  // namespace
 

@@ -372,10 +372,10 @@ int frame_launch(pcl_solver *s, hipStream_t stream, double *q, double *dst, cons
     return PCL_OK;
 }
 
-// what a launch of a PCL_RP_CELL solver says about the attached module (cellrp.hpp): the kernel of pass ids -- a classic
-// sweep, or a SharpClaw kernel if the module was compiled for SharpClaw -- and what it was instantiated for
-void user_launch_fields(SweepLaunch &l, const pcl_solver *s, int ids) {
-    l.user_fn = s->cellrp.fn[ids - 1];     // null: nothing attached, refused by the launcher
+// what a launch of a PCL_RP_CELL solver says about the attached module (cellrp.hpp): its kernels by slot -- each launcher
+// takes its own -- and what they were instantiated for
+void user_launch_fields(SweepLaunch &l, const pcl_solver *s) {
+    l.user_fns = s->cellrp.mod ? s->cellrp.fn : nullptr;    // null: nothing attached, refused by the launcher
     l.user = s->cellrp.spec;
     // nothing uploaded yet (listed components or the capacity function): refused by the launcher too
     if ((l.user.naux > 0 || l.user.capa()) && !s->aux_put) l.a.aux = nullptr;
@@ -389,7 +389,7 @@ SweepLaunch make_launch(const pcl_solver *s, const SweepArgs &a, int ndim, int i
     l.ids = ids;
     l.fwave = s->cfg.fwave;
     l.stream = stream;
-    if (l.rp == PCL_RP_CELL) user_launch_fields(l, s, ids);      // (3-D: ids 1..3, the three sweeps of a 3-D handle)
+    if (l.rp == PCL_RP_CELL) user_launch_fields(l, s);
     return l;
 }
 
@@ -447,7 +447,7 @@ const pcl::RpFacts *rp_id_facts(int rp) {
 pcl::RpFacts solver_facts(const pcl_solver *s) {
     if (s->cfg.rp != PCL_RP_CELL) return *rp_id_facts(s->cfg.rp);
     const pcl::CellrpSpec &u = s->cellrp.spec;
-    const bool onek = s->cellrp.onek != nullptr;
+    const bool onek = s->cellrp.fn[pcl::SLOT_ONEK] != nullptr;
     return {PCL_RP_CELL, s->cfg.ndim, s->cfg.meqn, s->cfg.mwaves, u.naux, u.fwave(), onek && u.naux == 0, onek && u.naux > 0,
             false, false, false};
 }
@@ -487,8 +487,6 @@ int do_step2ds(pcl_solver *s, const double *qin, double *qout, double dt, bool c
     if (sub) for (int k = 0; k < 4; k++) a.box[k] = box[k];
     LaunchTimer timer(s, timing_on(s) && !on, 2, sub != 2, stream);
     SweepLaunch l = make_launch(s, a, 2, 1, stream);
-    // (a user-written solver: the one-kernel step of its module, null where the handle was compiled without it)
-    if (l.rp == PCL_RP_CELL) l.user_fn = s->cellrp.onek;
     // quiet tiles (quiet_tiles.hpp): the whole block only (a decomposed block's ghost frame and tile subsets are left out),
     // and not where aux planes are staged (the key of the remembered state does not cover pcl_put_aux, and with a
     // capacity function a tile's cached Courant maxima are not dt-free)
@@ -572,8 +570,6 @@ static int unsplit_phase(pcl_solver *s, int ids, double dt, int sub, hipStream_t
     l.a.trans = s->cfg.method[2];
     l.a.dtd_t = dt / s->cfg.d[2 - ids];
     l.a.sub = sub;
-    // the unsplit kernels of the attached module (null: nothing attached or no transverse body, refused by the launcher)
-    if (l.rp == PCL_RP_CELL) l.user_fn = s->cellrp.fn[2 + ids - 1];
     LaunchTimer timer(s, timing_on(s), ids - 1, sub != 2, stream);
     int rc = PCL_BY_MATH(s->cfg.math, launch_unsplit(l, s->t1, err));
     timer.end();
@@ -1799,13 +1795,13 @@ static int cellrp_compile(const pcl::CellrpSpec &sp, pcl::CellrpTexts t, pcl::Ce
         c.hits++;
     } else {
         std::vector<char> code;
-        std::string sym[PCL_CELLRP_MAX_KERNELS];
+        std::string sym[pcl::CELLRP_NSLOTS];
         if (cellrp_build(sp, t, code, sym, err)) return fail(PCL_EINVAL, err);
         r = new pcl_cellrp();
         r->id = c.next_id++;
         r->key = key;
         r->code.swap(code);
-        for (int k = 0; k < PCL_CELLRP_MAX_KERNELS; k++) r->sym[k] = sym[k];
+        for (int k = 0; k < pcl::CELLRP_NSLOTS; k++) r->sym[k] = sym[k];
         r->spec = sp;
         c.rp_by_key[key] = r;
         c.rp_live[r] = r->id;
@@ -1962,7 +1958,7 @@ int pcl_cellrp_attach(pcl_solver *s, pcl_cellrp *r) {
     if (s->cfg.rp != PCL_RP_CELL) return fail(PCL_EINVAL, "pcl_cellrp_attach: the solver was not created with cfg.rp = PCL_RP_CELL");
     pcl::CellrpModule m;
     const void *code;
-    std::string sym[PCL_CELLRP_MAX_KERNELS];
+    std::string sym[pcl::CELLRP_NSLOTS];
     {   // (the entry is never freed: the code stays valid outside the lock)
         CellfnCache &c = cellfn_cache();
         std::lock_guard<std::mutex> lock(c.mu);
@@ -1973,20 +1969,16 @@ int pcl_cellrp_attach(pcl_solver *s, pcl_cellrp *r) {
         m.id = r->id;
         m.spec = r->spec;
         code = r->code.data();
-        for (int k = 0; k < PCL_CELLRP_MAX_KERNELS; k++) sym[k] = r->sym[k];
+        for (int k = 0; k < pcl::CELLRP_NSLOTS; k++) sym[k] = r->sym[k];
     }
     if (s->cellrp.id == m.id) return PCL_OK;
     HIP_TRY(hipSetDevice(s->cfg.device));
     HIP_TRY(hipStreamSynchronize(s->stream));       // a sweep of the module attached before may still run
     s->cellrp.unload();
     HIP_TRY(hipModuleLoadData(&m.mod, code));
-    // (with spec.onek the last name is the one-kernel step's: cellrp_exprs)
-    int nsym = 0;
-    while (nsym < PCL_CELLRP_MAX_KERNELS && !sym[nsym].empty()) nsym++;
-    for (int k = 0; k < nsym; k++) {
-        const bool last_onek = m.spec.onek && k == nsym - 1;
-        hipError_t e = !last_onek && k >= 4 ? hipErrorInvalidValue      // (cellrp_exprs names at most four others)
-                                            : hipModuleGetFunction(last_onek ? &m.onek : &m.fn[k], m.mod, sym[k].c_str());
+    for (int k = 0; k < pcl::CELLRP_NSLOTS; k++) {       // every slot the handle has a kernel for
+        if (sym[k].empty()) continue;
+        hipError_t e = hipModuleGetFunction(&m.fn[k], m.mod, sym[k].c_str());
         if (e != hipSuccess) {
             (void)hipModuleUnload(m.mod);
             return fail(PCL_EHIP, "hipModuleGetFunction(" + sym[k] + "): " + hipGetErrorString(e));
@@ -2252,7 +2244,7 @@ static int sharp_pass(pcl_solver *s, int ids, double dt, int rk_op, const double
     l.ndim = s->cfg.ndim; l.rp = s->cfg.rp; l.ids = ids; l.fwave = s->cfg.fwave;
     l.lim_type = s->cfg.lim_type; l.stream = stream;
     l.char_decomp = s->cfg.method[4];          // SharpClaw: clawparams.char_decomp travels in method(5) (unused by it)
-    if (l.rp == PCL_RP_CELL) user_launch_fields(l, s, ids);
+    if (l.rp == PCL_RP_CELL) user_launch_fields(l, s);
     LaunchTimer timer(s, timing_on(s), ids - 1, sub != 2, stream);
     int rc = PCL_BY_MATH(s->cfg.math, launch_sharp(l, err));
     timer.end();

@@ -195,6 +195,12 @@ struct CellrpSpec {
     int slices() const { return trans ? unsplit_user_slices(meqn) : 0; }   // per workgroup of the unsplit kernels
 };
 
+// The kernels a module of a user-written Riemann solver can hold, by what launches them.  A classic handle fills the sweeps of
+// its dimension (1-D: SWEEP_X alone; 3-D: the three sweep3_kernel passes), with a transverse body the unsplit phases, with
+// spec.onek the one-kernel step; a SharpClaw handle holds its kernels in the sweep slots (char_decomp = 1: SWEEP_X alone).
+// The order is that of cellrp_exprs.
+enum CellrpSlot { SLOT_SWEEP_X, SLOT_SWEEP_Y, SLOT_SWEEP_Z, SLOT_UNSPLIT_X, SLOT_UNSPLIT_Y, SLOT_ONEK, CELLRP_NSLOTS };
+
 struct SweepLaunch {
     SweepArgs a;
     int ndim;   // 1, 2 or 3
@@ -204,10 +210,11 @@ struct SweepLaunch {
     int lim_type;  // SharpClaw reconstruction (2 PyWENO weno5, 3 legacy weno5)
     int char_decomp = 0;   // SharpClaw: 1 = wave-based reconstruction (1-D: tvd2_wave / weno5_wave)
     hipStream_t stream;
-    // rp == PCL_RP_CELL (a user-written Riemann solver, cellrp.hpp): user_fn is the kernel of this pass in the module the solver
-    // handle has loaded (null: nothing attached) and user what that module was compiled for.  launch_sweep, launch_sweep3,
-    // launch_unsplit and launch_sharp refuse a launch that says otherwise and launch user_fn over the grids of the built-in solvers
-    hipFunction_t user_fn = nullptr;
+    // rp == PCL_RP_CELL (a user-written Riemann solver, cellrp.hpp): user_fns is the kernel table of the module the solver handle
+    // has loaded, indexed by CellrpSlot (null: nothing attached), and user what that module was compiled for.  Each launcher
+    // takes the slot of its own family and direction, refuses a launch the module was not compiled for and fires the plan of
+    // the built-in solvers at that kernel (kernels.hip: Plan)
+    const hipFunction_t *user_fns = nullptr;
     CellrpSpec user;
     // one-kernel step only (classic_fused.hpp, quiet tiles): this launch's per-tile words and per-wavefront Courant
     // maxima (tq_out null: no bookkeeping).  A list launch (tq_list set) computes the tq_next->na + nq tiles a
@@ -261,44 +268,38 @@ struct BlockGeom { int mx, my, mbc, I, J; };
 // ntiles = the counts of either; any: the box is not empty.
 struct InteriorBox { bool any = false; int box[4] = {0, 0, 0, 0}, ntiles[2] = {0, 0}; };
 
-// defined in kernels.hip, once per arithmetic mode; returns 0 or a PCL_E* code + message
+// defined in kernels.hip, once per arithmetic mode; returns 0 or a PCL_E* code + message:
+//   launch_sweep     one directional sweep, l.ids 1 = x (or the 1-D step), 2 = y
+//   launch_step2ds   whole dim-split 2-D step in one kernel (classic_fused.hpp)
+//   launch_sweep3    3-D dim-split sweep, l.ids = direction 1..3
+//   launch_unsplit3  unsplit 3-D: slices + combine of one direction
+//   launch_unsplit   scratch-free unsplit phase
+//   launch_sharp     SharpClaw dq of one direction
+#define PCL_LAUNCHERS                                                              \
+    int launch_sweep(const SweepLaunch &l, std::string &err);                      \
+    int launch_step2ds(const SweepLaunch &l, std::string &err);                    \
+    int launch_sweep3(const SweepLaunch &l, std::string &err);                     \
+    int launch_unsplit3(const Unsplit3Launch &l, std::string &err);                \
+    int launch_unsplit(const SweepLaunch &l, const double *qx, std::string &err);  \
+    int launch_sharp(const SweepLaunch &l, std::string &err);                      \
+    int launch_rk(const RkLaunch &r, hipStream_t stream, std::string &err);
 namespace exact {
-const RpFacts *rp_facts(int rp);    // null: no built-in solver has this id (the same in every mode)
+PCL_LAUNCHERS
+// what does not depend on the arithmetic mode: exact alone has it
+const RpFacts *rp_facts(int rp);    // null: no built-in solver has this id
 int sweep_tile_max_planes();        // q + aux planes a sweep_kernel tile may hold (TileShape<1/2>::PLANE against 64 KB)
 int sweep3_tile_max_planes();       // q + aux + capa planes a sweep3_kernel tile may hold (Tile3Shape<1..3>::PLANE against 64 KB)
 int sharp_tile_max_planes(int ixy, int naux);   // planes a sharp_kernel tile of pass ixy may hold for a solver with naux aux components
-int launch_sweep(const SweepLaunch &l, std::string &err);
-int launch_step2ds(const SweepLaunch &l, std::string &err);   // whole dim-split 2-D step in one kernel (classic_fused.hpp)
 // x-pass tiles [tb_lo,tb_hi) x [ta_lo,ta_hi) that read no ghost cell; false if there are none
 // ntiles[0], ntiles[1] = row tiles / tiles along a row of the x pass
 bool x_interior_box(const BlockGeom &a, int box[4], int ntiles[2]);
 bool step2ds_interior_box(const BlockGeom &a, int box[4], int ntiles[2]);   // the same for the one-kernel step: (nty, ntx)
 int launch_tile_handover(const TileHandover &h, std::string &err);   // Courant hand-over + next tile list (bit-only)
-int launch_sweep3(const SweepLaunch &l, std::string &err);   // 3-D dim-split sweep, l.ids = direction 1..3
-int launch_unsplit3(const Unsplit3Launch &l, std::string &err);   // unsplit 3-D: slices + combine of one direction
-int launch_unsplit(const SweepLaunch &l, const double *qx, std::string &err);  // scratch-free unsplit phase
-int launch_sharp(const SweepLaunch &l, std::string &err);     // SharpClaw dq of one direction
-int launch_rk(const RkLaunch &r, hipStream_t stream, std::string &err);
 }
-namespace fast {
-int launch_sweep(const SweepLaunch &l, std::string &err);
-int launch_step2ds(const SweepLaunch &l, std::string &err);   // whole dim-split 2-D step in one kernel (classic_fused.hpp)
-int launch_sweep3(const SweepLaunch &l, std::string &err);
-int launch_unsplit3(const Unsplit3Launch &l, std::string &err);
-int launch_unsplit(const SweepLaunch &l, const double *qx, std::string &err);  // scratch-free unsplit phase
-int launch_sharp(const SweepLaunch &l, std::string &err);
-int launch_rk(const RkLaunch &r, hipStream_t stream, std::string &err);
-}
+namespace fast { PCL_LAUNCHERS }
 // exact + IEEE quotients for underflow-range numerators as well (rp.hpp PCL_DENORM_GUARD), PCL_MATH_STRICT
-namespace strict {
-int launch_sweep(const SweepLaunch &l, std::string &err);
-int launch_step2ds(const SweepLaunch &l, std::string &err);   // whole dim-split 2-D step in one kernel (classic_fused.hpp)
-int launch_sweep3(const SweepLaunch &l, std::string &err);
-int launch_unsplit3(const Unsplit3Launch &l, std::string &err);
-int launch_unsplit(const SweepLaunch &l, const double *qx, std::string &err);
-int launch_sharp(const SweepLaunch &l, std::string &err);
-int launch_rk(const RkLaunch &r, hipStream_t stream, std::string &err);
-}
+namespace strict { PCL_LAUNCHERS }
+#undef PCL_LAUNCHERS
 #endif  // !__HIPCC_RTC__
 
 }  // namespace pcl
