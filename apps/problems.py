@@ -297,6 +297,98 @@ for (int m = 0; m < 5; m++) {
 }
 """
 
+# Transverse bodies for pyclaw.CellRiemann3D(..., rpt3=..., rptt3=...), the unsplit 3-D step: ixyz is the direction of the
+# normal solve, icoor 2 / 3 the y-like / z-like direction the split is made in, so the split direction (1-based, cyclic) is
+_SPLIT_DIR_3D = "constexpr int iuvw = (ixyz + icoor - 2) % 3 + 1;"
+
+# The built-in vc_acoustics_3d's transverse solvers (rpt3_vc_acoustics / rptt3_vc_acoustics of oracle/classic_oracle.c)
+# expression by expression, in general form: the velocity component of the split direction takes part in a1 and a2 even
+# where the library's own kernel knows it to be zero.  aux = (0, 1) = (Z, c); auxb[a][b][k] is the neighbour at y-like
+# offset a-1, z-like offset b-1.  The part going down enters the neighbouring row with ITS impedance and sound speed.
+VC_ACOUSTICS_3D_RPT = _SPLIT_DIR_3D + """
+const double zm = icoor == 2 ? auxb[0][1][0] : auxb[1][0][0], zz = auxb[1][1][0], zp = icoor == 2 ? auxb[2][1][0] : auxb[1][2][0];
+const double cm = icoor == 2 ? auxb[0][1][1] : auxb[1][0][1], cp = icoor == 2 ? auxb[2][1][1] : auxb[1][2][1];
+const double a1 = fdiv(-asdq[0] + asdq[iuvw] * zz, zm + zz);
+const double a2 = fdiv(asdq[0] + asdq[iuvw] * zz, zz + zp);
+bmasdq[0] = cm * a1 * zm; bmasdq[iuvw] = -cm * a1;
+bpasdq[0] = cp * a2 * zp; bpasdq[iuvw] = cp * a2;
+"""
+# the new split lies inside the row the input went to: the z-like row impt names (icoor 2) or the y-like one (icoor 3)
+VC_ACOUSTICS_3D_RPTT = _SPLIT_DIR_3D + """
+const int r = impt == 1 ? 0 : 2;
+const double zm = icoor == 2 ? auxb[0][r][0] : auxb[r][0][0], zz = icoor == 2 ? auxb[1][r][0] : auxb[r][1][0];
+const double zp = icoor == 2 ? auxb[2][r][0] : auxb[r][2][0];
+const double cm = icoor == 2 ? auxb[0][r][1] : auxb[r][0][1], cp = icoor == 2 ? auxb[2][r][1] : auxb[r][2][1];
+const double a1 = fdiv(-bsasdq[0] + bsasdq[iuvw] * zz, zm + zz);
+const double a2 = fdiv(bsasdq[0] + bsasdq[iuvw] * zz, zz + zp);
+cmbsasdq[0] = cm * a1 * zm; cmbsasdq[iuvw] = -cm * a1;
+cpbsasdq[0] = cp * a2 * zp; cpbsasdq[iuvw] = cp * a2;
+"""
+
+# homogeneous 3-D acoustics, no aux arrays; p = Z, c: the two bodies above with every coefficient taken from p[]
+ACOUSTICS_3D_RPT = _SPLIT_DIR_3D + """
+const double zz = p[0], cc = p[1];
+const double a1 = fdiv(-asdq[0] + asdq[iuvw] * zz, zz + zz);
+const double a2 = fdiv(asdq[0] + asdq[iuvw] * zz, zz + zz);
+bmasdq[0] = cc * a1 * zz; bmasdq[iuvw] = -cc * a1;
+bpasdq[0] = cc * a2 * zz; bpasdq[iuvw] = cc * a2;
+"""
+ACOUSTICS_3D_RPTT = _SPLIT_DIR_3D + """
+const double zz = p[0], cc = p[1];
+const double a1 = fdiv(-bsasdq[0] + bsasdq[iuvw] * zz, zz + zz);
+const double a2 = fdiv(bsasdq[0] + bsasdq[iuvw] * zz, zz + zz);
+cmbsasdq[0] = cc * a1 * zz; cmbsasdq[iuvw] = -cc * a1;
+cpbsasdq[0] = cc * a2 * zz; cpbsasdq[iuvw] = cc * a2;
+"""
+
+# p = u, v, w: the part of the input moving down / up with the velocity of the split direction
+ADVECTION_3D_RPT = _SPLIT_DIR_3D + """
+const double vel = p[iuvw - 1];
+bmasdq[0] = dmin(vel, 0.0) * asdq[0];
+bpasdq[0] = dmax(vel, 0.0) * asdq[0];
+"""
+ADVECTION_3D_RPTT = _SPLIT_DIR_3D + """
+const double vel = p[iuvw - 1];
+cmbsasdq[0] = dmin(vel, 0.0) * bsasdq[0];
+cpbsasdq[0] = dmax(vel, 0.0) * bsasdq[0];
+"""
+
+# 3-D Euler: the three-wave Roe decomposition of EULER_3D_RP in the frame of the split direction -- mu its momentum, mv
+# and mw the other two in cyclic order -- with the Roe averages of ql and qr, applied to the input in place of qr - ql;
+# the parts with negative speeds go down, those with positive speeds up.  IN_, OM_, OP_ stand for the three arrays.
+_EULER_3D_SPLIT = _SPLIT_DIR_3D + """
+constexpr int mu = iuvw, mv = iuvw % 3 + 1, mw = (iuvw + 1) % 3 + 1;
+const double gamma1 = p[0] - 1.0;
+const double rsl = dsqrt(ql[0]), rsr = dsqrt(qr[0]), rsq2 = rsl + rsr;
+const double pl = gamma1 * (ql[4] - 0.5 * (ql[mu] * ql[mu] + ql[mv] * ql[mv] + ql[mw] * ql[mw]) / ql[0]);
+const double pr = gamma1 * (qr[4] - 0.5 * (qr[mu] * qr[mu] + qr[mv] * qr[mv] + qr[mw] * qr[mw]) / qr[0]);
+const double u = (ql[mu] / rsl + qr[mu] / rsr) / rsq2;
+const double v = (ql[mv] / rsl + qr[mv] / rsr) / rsq2;
+const double w = (ql[mw] / rsl + qr[mw] / rsr) / rsq2;
+const double enth = ((ql[4] + pl) / rsl + (qr[4] + pr) / rsr) / rsq2;
+const double uvw2 = u * u + v * v + w * w;
+const double a2 = gamma1 * (enth - 0.5 * uvw2);
+const double a = dsqrt(a2);
+const double g1a2 = gamma1 / a2, euv = enth - uvw2;
+const double d1 = IN_[0], d2 = IN_[mu], d3 = IN_[mv], d4 = IN_[mw], d5 = IN_[4];
+const double b4 = g1a2 * (euv * d1 + u * d2 + v * d3 + w * d4 - d5);
+const double b2 = d3 - v * d1;
+const double b3 = d4 - w * d1;
+const double b5 = (d2 + (a - u) * d1 - a * b4) / (2.0 * a);
+const double b1 = d1 - b4 - b5;
+double w0[5], w1[5], w2[5];
+w0[0] = b1; w0[mu] = b1 * (u - a); w0[mv] = b1 * v; w0[mw] = b1 * w; w0[4] = b1 * (enth - u * a);
+w1[0] = b4; w1[mu] = b4 * u; w1[mv] = b4 * v + b2; w1[mw] = b4 * w + b3; w1[4] = b4 * 0.5 * uvw2 + b2 * v + b3 * w;
+w2[0] = b5; w2[mu] = b5 * (u + a); w2[mv] = b5 * v; w2[mw] = b5 * w; w2[4] = b5 * (enth + u * a);
+const double s0 = u - a, s1 = u, s2 = u + a;
+for (int m = 0; m < 5; m++) {
+    OM_[m] = dmin(s0, 0.0) * w0[m] + dmin(s1, 0.0) * w1[m] + dmin(s2, 0.0) * w2[m];
+    OP_[m] = dmax(s0, 0.0) * w0[m] + dmax(s1, 0.0) * w1[m] + dmax(s2, 0.0) * w2[m];
+}
+"""
+EULER_3D_RPT = _EULER_3D_SPLIT.replace("IN_", "asdq").replace("OM_", "bmasdq").replace("OP_", "bpasdq")
+EULER_3D_RPTT = _EULER_3D_SPLIT.replace("IN_", "bsasdq").replace("OM_", "cmbsasdq").replace("OP_", "cpbsasdq")
+
 # F-wave solvers: pyclaw.CellRiemann(..., fwave=True) with solver.fwave = True.  The array the body assigns is fwave[][],
 # the pieces of the flux difference; between two EQUAL cells over different coefficients they are not zero, and every
 # interface is solved.
@@ -772,11 +864,13 @@ def advection1D(pyclaw, mx=1000, tfinal=1.0, nout=10):
 
 def acoustics3D(pyclaw, test='hom', mx=None, my=None, mz=None, run=True, math='exact', tfinal=2.0, nout=10, user_rp=False):
     """test/acoustics/3d/acoustics.py:6-96.  'hom': dim-split 256x4x4, all periodic (the reference gates
-    final_difference = 0.00286 +- 1e-4, test/test_examples.py:481-488); 'het' needs the unsplit step3.  user_rp=True
-    ('hom' only: the dimension-split step): the same solver as the body VC_ACOUSTICS_3D_RP of a pyclaw.CellRiemann3D."""
+    final_difference = 0.00286 +- 1e-4, test/test_examples.py:481-488); 'het' needs the unsplit step3.  user_rp=True:
+    the same solver as the body VC_ACOUSTICS_3D_RP of a pyclaw.CellRiemann3D, for 'het' with the transverse bodies
+    VC_ACOUSTICS_3D_RPT / VC_ACOUSTICS_3D_RPTT."""
     solver = pyclaw.ClawSolver3D()
     solver.math = math
-    solver.rp = (pyclaw.CellRiemann3D(VC_ACOUSTICS_3D_RP, 4, 2, aux=(0, 1), name="vc_acoustics_3d_user") if user_rp
+    trans = {} if test == 'hom' else dict(rpt3=VC_ACOUSTICS_3D_RPT, rptt3=VC_ACOUSTICS_3D_RPTT)
+    solver.rp = (pyclaw.CellRiemann3D(VC_ACOUSTICS_3D_RP, 4, 2, aux=(0, 1), name="vc_acoustics_3d_user", **trans) if user_rp
                  else pyclaw.riemann.rp_vc_acoustics_3d)
     for k in range(3):
         solver.bc_lower[k] = solver.bc_upper[k] = pyclaw.BC.periodic
@@ -826,14 +920,19 @@ def acoustics3D(pyclaw, test='hom', mx=None, my=None, mz=None, run=True, math='e
     return claw
 
 
-def euler3D(pyclaw, axis=0, n=64, across=(4, 4), tfinal=0.1, nout=1, run=True, math='exact', order=2):
+def euler3D(pyclaw, axis=0, n=64, across=(4, 4), tfinal=0.1, nout=1, run=True, math='exact', order=2, dim_split=True,
+            order_trans=22):
     """A system the library has no 3-D solver for: the Euler equations through EULER_3D_RP in a pyclaw.CellRiemann3D.
     Sod's jump across the plane through the middle of the box normal to `axis` (0, 1, 2), n cells along that axis and
-    `across` cells along the other two (in cyclic order), extrapolation on every side, dimension-split step."""
+    `across` cells along the other two (in cyclic order), extrapolation on every side; the dimension-split step or,
+    dim_split=False, the unsplit one with the transverse bodies EULER_3D_RPT / EULER_3D_RPTT and `order_trans`."""
     solver = pyclaw.ClawSolver3D()
     solver.math = math
-    solver.rp = pyclaw.CellRiemann3D(EULER_3D_RP, 5, 3, params=[gamma], name="euler_3d_user")
-    solver.dim_split = True
+    trans = {} if dim_split else dict(rpt3=EULER_3D_RPT, rptt3=EULER_3D_RPTT)
+    solver.rp = pyclaw.CellRiemann3D(EULER_3D_RP, 5, 3, params=[gamma], name="euler_3d_user", **trans)
+    solver.dim_split = bool(dim_split)
+    if not dim_split:
+        solver.order_trans = order_trans
     solver.order = order
     solver.mwaves = 3
     solver.limiters = [4, 4, 4]

@@ -507,6 +507,33 @@ int pcl_cellrp_sharp(const pcl_cellrp *r, int *lim_type, int *weno_order, int *c
  * rptt3 bodies), cfg.fwave and every cfg.kind but PCL_KIND_CLASSIC for it.  One block.  Host-only. */
 int pcl_cellrp_compile3(const char *body, const char *preamble, int meqn, int mwaves, int math, const int *aux_index, int naux,
                         int form, pcl_cellrp **out, long *code_size);
+/* pcl_cellrp_compile3 with the transverse solvers of the UNSPLIT 3-D step (cfg.method[2] >= 0; step3.f + flux3.f): rpt3 is
+ * the inside of Clawpack's rpt3 for one interface, rptt3 (may be null) the inside of rptt3.  The code object also holds
+ * the pieces kernels of the general unsplit step (csrc/classic3.hpp: pieces3_kernel, DIR 1..3); the library's own gather
+ * kernel applies what they leave in scratch planes in the order of step3.f's loop nest.
+ * Both texts see the compile-time constants ixyz (alias ixy: the direction of the normal solve, 1..3) and icoor (2: the
+ * split is in the y-like direction ixyz+1, 3: in the z-like direction ixyz+2, cyclic) and p[8].  Without an aux list they
+ * see ql[MEQN], qr[MEQN], the cells left and right of the interface (one pair for A-dq, A+dq and the correction wave; no
+ * imp); with one, imp (1, 2), q1[MEQN] (the cell i-2+imp the fluctuation belongs to) and auxb[3][3][NAUX], auxb[a][b][k]
+ * the k-th listed component of that cell's neighbour at y-like offset a-1 and z-like offset b-1.
+ *     rpt3:   asdq[MEQN] in; assigns bmasdq[MEQN], bpasdq[MEQN] (zero on entry)
+ *     rptt3:  impt (1: the input came out of a split that went down in the other transverse direction, 2: up) and
+ *             bsasdq[MEQN] in; assigns cmbsasdq[MEQN], cpbsasdq[MEQN] (zero on entry)
+ * For an all-zero input the results must be zero.  Diagnostics carry "rpt3:<n>" / "rptt3:<n>".
+ * Refused (PCL_EINVAL, before the compiler): rptt3 without rpt3; PCL_CELLRP_FORM_FWAVE; PCL_CELLRP_FORM_CAPA together with
+ * rpt3 (step3 with mcapa is not built for any solver).  Both texts null: pcl_cellrp_compile3 itself.
+ * A handle with rpt3 alone serves method[2] = 0, 10 and 20, one with both 0, 10, 11, 20, 21 and 22 (pcl_create_cellrp
+ * refuses the rest); either still serves the dimension-split step where meqn + naux <= 7, and the unsplit step alone above
+ * that.  Attaching such a handle to an unsplit configuration allocates pcl_unsplit3_scratch_bytes of device memory, freed
+ * by pcl_destroy; a failed allocation is refused with the bytes.  mbc = 2, one block.  Host-only. */
+int pcl_cellrp_compile3t(const char *body, const char *rpt3, const char *rptt3, const char *preamble, int meqn, int mwaves,
+                         int math, const int *aux_index, int naux, int form, pcl_cellrp **out, long *code_size);
+/* Host-only: *trans3 = 0 (no 3-D transverse body), 1 (rpt3) or 2 (rpt3 and rptt3) of a live handle. */
+int pcl_cellrp_transverse3(const pcl_cellrp *r, int *trans3);
+/* The scratch of the general unsplit 3-D step: 14 * meqn doubles per cell, ghost cells included (the one rule,
+ * csrc/sweep_args.hpp), and the bytes of it that live solvers of this process hold. */
+long long pcl_unsplit3_scratch_bytes(int meqn, int nx, int ny, int nz, int mbc);
+long long pcl_unsplit3_scratch_live(void);
 /* Host-only: *has = 1 if the live handle was compiled with a transverse body, and then *slices (may be null) = the slices
  * per workgroup of its unsplit kernels; else *has = 0, *slices = 0. */
 int pcl_cellrp_transverse(const pcl_cellrp *r, int *has, int *slices);

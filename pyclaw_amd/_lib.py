@@ -119,6 +119,11 @@ PROTOTYPES = {
     "pcl_cellrp_sharp": (C.c_int, [C.c_void_p, ip, ip, ip]),
     "pcl_cellrp_compile3": (C.c_int, [C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_int, ip, C.c_int, C.c_int,
                                       C.POINTER(C.c_void_p), C.POINTER(C.c_long)]),
+    "pcl_cellrp_compile3t": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_int, ip, C.c_int,
+                                       C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_long)]),
+    "pcl_cellrp_transverse3": (C.c_int, [C.c_void_p, ip]),
+    "pcl_unsplit3_scratch_bytes": (C.c_longlong, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "pcl_unsplit3_scratch_live": (C.c_longlong, []),
     "pcl_cellrp_transverse": (C.c_int, [C.c_void_p, ip, ip]),
     "pcl_create_cellrp": (C.c_int, [C.POINTER(Config), C.c_void_p, C.POINTER(C.c_void_p)]),
     "pcl_cellrp_aux": (C.c_int, [C.c_void_p, ip, ip]),

@@ -316,9 +316,19 @@ class ClawSolver(Solver):
             raise NotImplementedError("CellRiemann: this user-written solver is compiled into the 1-D and 2-D sweep kernels; "
                                       "ClawSolver3D takes a CellRiemann3D, compiled into its three sweeps")
         if self.ndim == 3 and not self.dim_split:
-            raise NotImplementedError("CellRiemann3D: dim_split = False (the unsplit 3-D step) needs transverse solvers, rpt3 "
-                                      "and rptt3; the body is the normal solver only, so the 3-D step is the dimension-split "
-                                      "one (dim_split = True)")
+            if self.rp.rpt3 is None:
+                raise NotImplementedError("CellRiemann3D: dim_split = False (the unsplit 3-D step) needs transverse solvers, "
+                                          "rpt3 and rptt3; the body is the normal solver only, so the 3-D step is the "
+                                          "dimension-split one (CellRiemann3D(..., rpt3=..., rptt3=...) gives it both)")
+            if self.order_trans not in (0, 10, 11, 20, 21, 22):
+                raise ValueError("ClawSolver3D: order_trans must be 0, 10, 11, 20, 21 or 22, got %r" % (self.order_trans,))
+            if self.order_trans % 10 > 0 and self.rp.rptt3 is None:
+                raise NotImplementedError("CellRiemann3D: order_trans = %d has double-transverse terms and the solver was "
+                                          "written without an rptt3 body: it serves order_trans 0, 10 and 20"
+                                          % self.order_trans)
+        if self.ndim == 3 and self.dim_split and self.rp.meqn + len(self.rp.aux) + int(self.rp.capa) > 7:
+            raise NotImplementedError("CellRiemann3D: meqn + len(aux) + capa > 7: the tile of the dimension-split 3-D sweeps "
+                                      "does not hold this solver, it serves dim_split = False alone")
         if self.ndim == 2 and not self.dim_split and not self.rp.has_transverse:
             raise NotImplementedError("CellRiemann: dim_split = False needs a transverse Riemann solver (rpt2); the body "
                                       "is the normal solver only, so the 2-D step is the dimension-split one "
@@ -441,7 +451,8 @@ class ClawSolver2D(ClawSolver):
 class ClawSolver3D(ClawSolver):
     r"""3D classic solver (clawpack.py:563-702): ``dim_split=True`` (Godunov splitting, ``step3ds``) or the unsplit
     algorithm with the ``rpt3``/``rptt3`` transverse solves (``step3``; ``order_trans`` 0, 10, 11, 20, 21, 22).
-    ``solver.rp`` may be a user-written ``riemann.CellRiemann3D``: the dimension-split step only."""
+    ``solver.rp`` may be a user-written ``riemann.CellRiemann3D``: the dimension-split step, and with ``rpt3`` / ``rptt3``
+    bodies the unsplit one."""
 
     no_trans = 0
     trans_inc = 11

@@ -3,7 +3,7 @@
 // cfg.rp = PCL_RP_CELL).
 //
 // Nothing of a kernel is restated here.  The Makefile embeds the headers the kernels are written in -- sweep_args.hpp,
-// ghost_rule.hpp, rp.hpp, classic.hpp, classic_fused.hpp, sharpclaw.hpp, weno_tables.hpp and include/pyclaw_amd.h -- as text
+// ghost_rule.hpp, rp.hpp, classic.hpp, classic3.hpp, classic_fused.hpp, sharpclaw.hpp, weno_tables.hpp and include/pyclaw_amd.h -- as text
 // (cellrp_headers.inc), hiprtc gets them as named headers, and the program below wraps the user's body in a solver struct
 // UserRp of the shape rp.hpp documents and asks for the kernels of that struct by name expression, compiled with the flags
 // of the library's own arithmetic mode (PCL_RTC_FLAGS_*, from the Makefile).  A user solver thereby runs with the LDS
@@ -40,11 +40,23 @@
 //     ndim 1 or 2, 8 parameters.  Kernels: sweep_kernel<UserRp, 1, CAPA, FWAVE, true> (the 1-D step), or <UserRp, 1, ..,
 //     false> and <UserRp, 2, .., false> (the x and y passes of step2ds).
 //     ndim 3 (pcl_cellrp_compile3 alone; every other call refuses it): sweep3_kernel<UserRp, 1, CAPA>, <UserRp, 2, CAPA>,
-//     <UserRp, 3, CAPA>, the x, y and z passes of the dimension-split step3ds, and nothing else -- no transverse body, no
-//     SharpClaw kernels, no f-wave form (sweep3_kernel has none).  ixy is 1, 2 or 3.  The aux list and CAPA mean what they
-//     mean below; all three passes stage q, the listed components and the capacity function in one static tile, so
+//     <UserRp, 3, CAPA>, the x, y and z passes of the dimension-split step3ds -- no 2-D transverse body, no SharpClaw
+//     kernels, no f-wave form (sweep3_kernel has none); with trans3 (below) the unsplit step's kernels too.  ixy is 1, 2 or
+//     3.  The aux list and CAPA mean what they mean below; all three passes stage q, the listed components and the capacity function in one static tile, so
 //     meqn + naux + capa <= sweep3_tile_max_planes() (7, set by the 64 x 17 doubles of the y / z tile: Tile3Shape,
 //     classic.hpp).  Such a handle serves cfg.ndim = 3 with method[2] < 0 and mbc = 2 (pcl_create_cellrp), nothing else.
+//   trans3   (pcl_cellrp_compile3t, CellRiemann3D(rpt3=..., rptt3=...); 3-D only: 1 an rpt3 text, 2 rpt3 and rptt3)
+//     Two more texts, the TRANSVERSE and DOUBLE-TRANSVERSE solvers of the unsplit 3-D step (Clawpack's rpt3 / rptt3): members
+//     transverse3<IXYZ, ICOOR> and dtransverse3<IXYZ, ICOOR> of the struct (kCellrpTrans3, where the texts' interface and
+//     contract are written down), -DPCL_CELLRP_TRANS3=<n>, the text includes classic3.hpp, and three more name expressions,
+//     pieces3_kernel<UserRp, 1>, <UserRp, 2>, <UserRp, 3> (SLOT_PIECES3_X / _Y / _Z): the pieces of every slice of the general
+//     unsplit step, which the library's own gather3_kernel applies from scratch planes (launch_unsplit3; the scratch, 14 *
+//     meqn doubles per cell with ghost cells -- sweep_args.hpp: unsplit3_scratch_bytes --, is allocated at the attach to an
+//     unsplit configuration and freed with the solver).  With rpt3 alone the kernel never names dtransverse3 (UserRp::TRANS3);
+//     such a handle serves method[2] = 0, 10, 20, one with both 0, 10, 11, 20, 21, 22 (cellrp_fits).  Wave form without a
+//     capacity function only (step3 with mcapa is built for no solver).  pieces3_kernel has no tile: a handle whose
+//     meqn + naux exceeds the sweep3 tile is compiled without the three sweeps and serves the unsplit step alone
+//     (cellrp_has_sweep3).  Key: prefixes "rpt3," / "rptt3," and the texts.
 //   naux, aux[]   (pcl_cellrp_compile_aux, CellRiemann(aux=...))
 //     The components of the aux array the body reads.  -DPCL_CELLRP_NAUX=<n> behind a generated constexpr table of the
 //     list: NAUX = NAUX_T = n, aux_index<IXY>(k) = auxt_index<IXY>(k) = the k-th listed component (0-based; one list for
@@ -111,8 +123,8 @@
 //
 // NOT SERVED under SharpClaw: a fused dq source (a source term runs as its own pass), char_decomp 2 / 3, tfluct, a
 // transverse body.  Not served in any form: HAS_QCOR (the sphere solver's conservation fix), a transverse body with both
-// cells and aux, the marching y phase, the unsplit 3-D step (rpt3 / rptt3 bodies, march3p_kernel),
-// f-waves in 3-D, more than one block (decomposed runs).
+// cells and aux (2-D or 3-D), the marching y phase, f-waves in 3-D, the unsplit 3-D step with a capacity function
+// (step3 with mcapa), mbc > 2 in 3-D, more than one block (decomposed runs).
 #pragma once
 #include "cellfn.hpp"
 // generated by the Makefile (embed_headers.py): PCL_RTC_FLAGS_EXACT / _FAST / _STRICT, the flags kernels_<mode>.o is built
@@ -135,6 +147,7 @@ namespace pcl {
 // the texts of one compile, as the caller gave them (transverse null: none)
 struct CellrpTexts {
     const char *body = nullptr, *transverse = nullptr, *preamble = nullptr;
+    const char *rpt3 = nullptr, *rptt3 = nullptr;       // 3-D: the transverse and double-transverse bodies (null: none)
 };
 
 // ---- the program text: each piece once; the spec's -D constants choose inside it ------------------------------------
@@ -143,6 +156,8 @@ static const char *const kCellrpHead = R"PCLSRC(
 #include "sharpclaw.hpp"
 #elif PCL_CELLRP_ONEK
 #include "classic_fused.hpp"
+#elif PCL_CELLRP_TRANS3
+#include "classic3.hpp"
 #else
 #include "classic.hpp"
 #endif
@@ -278,6 +293,91 @@ static const char *const kCellrpTransSolve = R"PCLSRC(
                   "the static LDS of unsplit_x_kernel / unsplit_y_kernel (classic.hpp) does not fit a workgroup's 160 KB");
 )PCLSRC";
 
+// The 3-D transverse bodies (spec.trans3): the insides of Clawpack's rpt3 and rptt3 for one interface, members
+// transverse3<IXYZ, ICOOR> and dtransverse3<IXYZ, ICOOR> of the struct, which pieces3_kernel (classic3.hpp) calls.  Both see
+//     ixyz (alias ixy), icoor             compile-time constants: the direction of the normal solve, 1..3; 2 = the split is in
+//                                         the y-like direction ixyz + 1, 3 = in the z-like direction ixyz + 2 (cyclic)
+//     const double p[8]
+// and, without an aux list,
+//     const double ql[MEQN], qr[MEQN]     the cells left and right of the interface -- the same pair for A-dq, A+dq and the
+//                                         correction wave of one interface: there is no imp
+// or, with one,
+//     imp                                 1 or 2
+//     const double q1[MEQN]               the cell i-2+imp the fluctuation belongs to
+//     const double auxb[3][3][NAUX]       auxb[a][b][k]: listed component k of that cell's neighbour at y-like offset a-1 and
+//                                         z-like offset b-1 (Clawpack's aux1 / aux2 / aux3(:, i1, 1..3))
+// rpt3:   const double asdq[MEQN] in, double bmasdq[MEQN], bpasdq[MEQN] out (zero on entry).
+// rptt3:  impt (1: the input came out of a split that went DOWN in the other transverse direction, 2: up), const double
+//         bsasdq[MEQN] in, double cmbsasdq[MEQN], cpbsasdq[MEQN] out (zero on entry); the new split lies inside the
+//         neighbouring row the input went to (oracle/classic_oracle.c: rptt3_vc_acoustics).
+// Contract: for an all-zero input the results are zero.  Diagnostics: "rpt3:<n>", "rptt3:<n>".
+#define PCL_CELLRP_T3_ARGS R"PCLSRC(
+#if PCL_CELLRP_NAUX > 0
+        const int imp, const double (&q1)[MEQN], const double (&auxb)[3][3][NAUX],
+#else
+        const double (&ql)[MEQN], const double (&qr)[MEQN],
+#endif
+        const double (&p)[8],)PCLSRC"
+static const char *const kCellrpTrans3 = R"PCLSRC(
+    template <int ixyz, int icoor>
+    __device__ static __forceinline__ void t3body()PCLSRC" PCL_CELLRP_T3_ARGS R"PCLSRC(
+        const double (&asdq)[MEQN], double (&bmasdq)[MEQN], double (&bpasdq)[MEQN]) {
+        constexpr int ixy = ixyz; (void)ixy;
+#line 1 "rpt3"
+)PCLSRC";
+static const char *const kCellrpTrans3Solve = R"PCLSRC(
+    }
+#line 1 "pcl_cellrp_wrapper_t3"
+    template <int IXYZ, int ICOOR>
+    __device__ static __forceinline__ void transverse3(
+#if PCL_CELLRP_NAUX > 0
+        const int imp, const double (&q1)[MEQN], const double (&auxb)[3][3][NAUX],
+#else
+        const double (&ql)[MEQN], const double (&qr)[MEQN],
+#endif
+        const RpParams &p, const double (&asdq)[MEQN], double (&bm)[MEQN], double (&bp)[MEQN]) {
+#pragma unroll
+        for (int m = 0; m < MEQN; m++) { bm[m] = 0.0; bp[m] = 0.0; }
+#if PCL_CELLRP_NAUX > 0
+        t3body<IXYZ, ICOOR>(imp, q1, auxb, p.v, asdq, bm, bp);
+#else
+        t3body<IXYZ, ICOOR>(ql, qr, p.v, asdq, bm, bp);
+#endif
+    }
+)PCLSRC";
+static const char *const kCellrpDtrans3 = R"PCLSRC(
+    template <int ixyz, int icoor>
+    __device__ static __forceinline__ void tt3body()PCLSRC" PCL_CELLRP_T3_ARGS R"PCLSRC(
+        const int impt, const double (&bsasdq)[MEQN], double (&cmbsasdq)[MEQN], double (&cpbsasdq)[MEQN]) {
+        constexpr int ixy = ixyz; (void)ixy;
+#line 1 "rptt3"
+)PCLSRC";
+static const char *const kCellrpDtrans3Solve = R"PCLSRC(
+    }
+#line 1 "pcl_cellrp_wrapper_tt3"
+    template <int IXYZ, int ICOOR>
+    __device__ static __forceinline__ void dtransverse3(
+#if PCL_CELLRP_NAUX > 0
+        const int imp, const int impt, const double (&q1)[MEQN], const double (&auxb)[3][3][NAUX],
+#else
+        const int impt, const double (&ql)[MEQN], const double (&qr)[MEQN],
+#endif
+        const RpParams &p, const double (&bsasdq)[MEQN], double (&cm)[MEQN], double (&cp)[MEQN]) {
+#pragma unroll
+        for (int m = 0; m < MEQN; m++) { cm[m] = 0.0; cp[m] = 0.0; }
+#if PCL_CELLRP_NAUX > 0
+        tt3body<IXYZ, ICOOR>(imp, q1, auxb, p.v, impt, bsasdq, cm, cp);
+#else
+        tt3body<IXYZ, ICOOR>(ql, qr, p.v, impt, bsasdq, cm, cp);
+#endif
+    }
+)PCLSRC";
+// behind the 3-D transverse bodies: what pieces3_kernel reads off the struct
+static const char *const kCellrpTrans3Close = R"PCLSRC(
+    static constexpr int TRANS3 = PCL_CELLRP_TRANS3;
+    static_assert(NDIM == 3 && (PCL_CELLRP_FORM & 3) == 0, "rpt3 / rptt3 bodies belong to a 3-D solver in wave form without a capacity function");
+)PCLSRC";
+
 // The end of the text: the plane limits the host refused over (cellrp_spec_check), restated.  The classic sweep tile holds
 // q, the listed aux components and, with one, the capacity function's plane (sweep_kernel: PAUX = MEQN + 1); sharp_kernel's
 // tile is static LDS of NP * TA * WAVE doubles, NP = meqn + capa in the x pass and meqn + capa + naux in the y pass, TA =
@@ -291,6 +391,8 @@ static_assert(PCL_CELLRP_SHARP_CD == 1 ||
                    (UserRp::NDIM == 1 ||
                     sizeof(double) * (UserRp::MEQN + USER_CAPA + UserRp::NAUX) * sharp_tile_across<UserRp, 2>() * WAVE <= 65536)),
               "meqn + capa + naux: the LDS tile of sharp_kernel (sharpclaw.hpp) does not fit the 64 KB a workgroup may declare");
+#elif PCL_CELLRP_NDIM == 3 && !PCL_CELLRP_SWEEP3
+static_assert(PCL_CELLRP_TRANS3 > 0, "a 3-D handle without the three sweeps holds the unsplit step's kernels");
 #elif PCL_CELLRP_NDIM == 3
 static_assert(sizeof(double) * (UserRp::MEQN + USER_CAPA + UserRp::NAUX) * Tile3Shape<1>::PLANE <= 65536 &&
                   sizeof(double) * (UserRp::MEQN + USER_CAPA + UserRp::NAUX) * Tile3Shape<2>::PLANE <= 65536 &&
@@ -319,7 +421,7 @@ static inline const char *cellrp_ns(int math) { return math == 1 ? "fast" : math
 // transverse text; the list of naux > 0 components -- sp.aux holds it only as far as it was given and fits), and whether
 // the call asked for a SharpClaw handle (behind its first refusal that is sp.sharp()) or for the 3-D sweeps
 // (pcl_cellrp_compile3; every other call goes on refusing ndim == 3).
-struct CellrpGiven { bool body_and_out, transverse, aux_list, sharp, dim3; };
+struct CellrpGiven { bool body_and_out, transverse, aux_list, sharp, dim3, rpt3, rptt3; };
 // the reason a handle with the one-kernel step (spec.onek) cannot be compiled for this spec, or null.  Today's only caller
 // that sets spec.onek, pcl_cellrp_compile_onek, fills ndim = 2 and no SharpClaw field, so of these only meqn > 5 can be
 // reached through the C interface; the other three state the rule for the spec and guard a later entry point that fills
@@ -331,6 +433,11 @@ static inline const char *cellrp_onek_refusal(const CellrpSpec &sp, bool dim3) {
     if (sp.ndim != 2) return "the one-kernel step is the dimension-split 2-D step (ndim must be 2)";
     if (sp.meqn > ONEK_MAX_MEQN) return "meqn > 5: the tile of the one-kernel step holds up to 5 equations";
     return nullptr;
+}
+// a 3-D handle holds the three dimension-split sweeps where their tile takes the solver's planes; one with rpt3 / rptt3 bodies
+// and more planes than that is compiled without them and serves the unsplit step alone (pieces3_kernel has no tile)
+static inline bool cellrp_has_sweep3(const CellrpSpec &sp) {
+    return sp.ndim == 3 && sp.meqn + sp.naux + (sp.capa() ? 1 : 0) <= exact::sweep3_tile_max_planes();
 }
 static inline int cellrp_spec_check(const CellrpSpec &sp, const CellrpGiven &given, std::string &err) {
     const auto no = [&err](const std::string &why) { err = why; return -1; };
@@ -365,6 +472,17 @@ static inline int cellrp_spec_check(const CellrpSpec &sp, const CellrpGiven &giv
     if (sp.naux < 0) return no("pcl_cellrp_compile_aux: naux must be >= 0, got " + n(sp.naux));
     if (sp.naux > 0 && !given.aux_list) return no("null argument");
     const int capa = sp.capa() ? 1 : 0;
+    // the 3-D transverse bodies (pcl_cellrp_compile3t): rptt3 splits what an rpt3 returned; 3-D, wave form, no capacity function
+    if (given.rptt3 && !given.rpt3)
+        return no("pcl_cellrp_compile3t: an rptt3 body without an rpt3 body: the double-transverse solver splits what the "
+                  "transverse solver returned");
+    if (sp.trans3 != (given.rptt3 ? 2 : given.rpt3 ? 1 : 0) || (sp.trans3 && sp.ndim != 3))
+        return no("pcl_cellrp_compile3t: rpt3 / rptt3 bodies belong to the unsplit 3-D step (ndim must be 3)");
+    if (sp.trans3 && sp.fwave())
+        return no("pcl_cellrp_compile3t: PCL_CELLRP_FORM_FWAVE: no f-wave body in 3-D, with or without rpt3 / rptt3 bodies");
+    if (sp.trans3 && sp.capa())
+        return no("pcl_cellrp_compile3t: PCL_CELLRP_FORM_CAPA with rpt3 / rptt3 bodies: the unsplit 3-D step (step3) with a "
+                  "capacity function (mcapa) is not built for any solver");
     if (sp.ndim == 3) {
         // the three passes of sweep3_kernel and nothing else: wave form, one tile of meqn + naux + capa planes
         if (sp.form & ~(PCL_CELLRP_FORM_FWAVE | PCL_CELLRP_FORM_CAPA))
@@ -375,7 +493,7 @@ static inline int cellrp_spec_check(const CellrpSpec &sp, const CellrpGiven &giv
                       "instantiation, the 3-D launcher refuses an f-wave step, and there is no frozen 3-D f-wave step to check "
                       "one against; form may carry PCL_CELLRP_FORM_CAPA only");
         const int max3 = exact::sweep3_tile_max_planes();
-        if (sp.meqn + sp.naux + capa > max3)
+        if (!sp.trans3 && sp.meqn + sp.naux + capa > max3)
             return no("pcl_cellrp_compile3: meqn + naux + capa = " + n(sp.meqn + sp.naux + capa) + ", the tile of the 3-D sweeps "
                       "holds at most " + n(max3) + " planes (q components, listed aux components and the capacity function) in "
                       "the 64 KB a workgroup may declare");
@@ -452,7 +570,23 @@ static inline int cellrp_fits(const CellrpSpec &sp, const pcl_config &cfg, const
             return no(": PCL_RP_CELL: the handle was compiled for char_decomp " + n(sp.char_decomp) +
                       " and cfg.method[4] (char_decomp) is " + n(cfg.method[4]));
     }
-    // (3-D: the unsplit step, f-waves and mbc != 2 are refused for any handle where the configuration is checked, pcl_create_cellrp)
+    // 3-D (f-waves are refused for any handle where the configuration is checked, pcl_create_cellrp)
+    if (!sharp_cfg && cfg.ndim == 3 && cfg.method[2] < 0 && sp.ndim == 3 && !cellrp_has_sweep3(sp))
+        return no(": PCL_RP_CELL: meqn + naux + capa = " + n(sp.meqn + sp.naux + (sp.capa() ? 1 : 0)) + " is more than the tile of "
+                  "the dimension-split 3-D sweeps holds (" + n(exact::sweep3_tile_max_planes()) + " planes): this handle serves the "
+                  "unsplit step alone (method[2] >= 0)");
+    if (!sharp_cfg && cfg.ndim == 3 && cfg.method[2] >= 0) {
+        const int ot = cfg.method[2], m3 = ot / 10, m4 = ot - 10 * m3;
+        if (!sp.trans3)
+            return no(": PCL_RP_CELL: the unsplit 3-D step (method[2] >= 0, step3) needs a handle compiled with rpt3 and rptt3 "
+                      "bodies (pcl_cellrp_compile3t); this one holds the three dimension-split sweeps only");
+        if (m3 > 2 || m4 > m3)      // (m4 = 2 splits the corrected increments: it needs the correction waves of m3 = 2)
+            return no(": PCL_RP_CELL: method[2] = " + n(ot) + ": the 3-D order_trans must be 0, 10, 11, 20, 21 or 22 (flux3.f:46-73)");
+        if (m4 > 0 && sp.trans3 < 2)
+            return no(": PCL_RP_CELL: method[2] = " + n(ot) + " asks for double-transverse terms and the handle was compiled "
+                      "without an rptt3 body: it serves method[2] = 0, 10 and 20");
+        if (cfg.mbc != 2) return no(": PCL_RP_CELL: the unsplit 3-D step needs mbc == 2, got " + n(cfg.mbc));
+    }
     if (!sharp_cfg && cfg.ndim == 2 && cfg.method[2] >= 0 && !sp.trans)
         return no(": PCL_RP_CELL: the unsplit step (method[2] >= 0) needs a handle compiled with a transverse body (pcl_cellrp_compile_t)");
     // the kernels in the handle were instantiated for one form (FWAVE, CAPA): the configuration must say the same
@@ -479,6 +613,8 @@ static inline std::string cellrp_key(const CellrpSpec &sp, const CellrpTexts &t)
     if (sp.form) k += "form" + n(sp.form) + ",";
     if (sp.onek) k += "onek,";
     if (sp.trans) { k += n((int)strlen(t.transverse)) + ":"; k += t.transverse; }
+    if (sp.trans3) { k = "rpt3," + k + n((int)strlen(t.rpt3)) + ":" + t.rpt3; }
+    if (sp.trans3 > 1) { k = "rptt3," + k + n((int)strlen(t.rptt3)) + ":" + t.rptt3; }
     k += n((int)strlen(t.preamble)) + ":";
     k += t.preamble;
     k += t.body;
@@ -500,7 +636,12 @@ static inline CellrpExprs cellrp_exprs(const CellrpSpec &sp) {
     }
     if (sp.ndim == 3) {     // x, y, z
         auto k3 = [&](int dir) { return "&" + ns + "sweep3_kernel<" + rp + n(dir) + ", " + capa + ">"; };
-        return {{SLOT_SWEEP_X, k3(1)}, {SLOT_SWEEP_Y, k3(2)}, {SLOT_SWEEP_Z, k3(3)}};
+        CellrpExprs e3;
+        if (cellrp_has_sweep3(sp)) e3 = {{SLOT_SWEEP_X, k3(1)}, {SLOT_SWEEP_Y, k3(2)}, {SLOT_SWEEP_Z, k3(3)}};
+        if (sp.trans3)      // the pieces of the unsplit step's slices, x, y, z (classic3.hpp; the gather kernel is the library's)
+            for (int dir = 1; dir <= 3; dir++)
+                e3.push_back({(CellrpSlot)(SLOT_PIECES3_X + dir - 1), "&" + ns + "pieces3_kernel<" + rp + n(dir) + ">"});
+        return e3;
     }
     auto k = [&](int ixy, bool dim1) { return "&" + ns + "sweep_kernel<" + rp + n(ixy) + ", " + capa + ", " + fw + ", " + (dim1 ? "true" : "false") + ">"; };
     if (sp.ndim == 1) return {{SLOT_SWEEP_X, k(1, true)}};
@@ -539,6 +680,19 @@ static inline int cellrp_build(const CellrpSpec &sp, const CellrpTexts &t, std::
         src += "\n";
         src += kCellrpTransSolve;
     }
+    if (sp.trans3) {
+        src += kCellrpTrans3;
+        src += t.rpt3;
+        src += "\n";
+        src += kCellrpTrans3Solve;
+        if (sp.trans3 > 1) {
+            src += kCellrpDtrans3;
+            src += t.rptt3;
+            src += "\n";
+            src += kCellrpDtrans3Solve;
+        }
+        src += kCellrpTrans3Close;
+    }
     src += kCellrpClose;
     job.name = "pcl_cellrp.hip";
     job.nheaders = kCellrpHeaderCount;
@@ -558,7 +712,8 @@ static inline int cellrp_build(const CellrpSpec &sp, const CellrpTexts &t, std::
     const std::pair<const char *, int> defs[] = {{"MEQN", sp.meqn},        {"MWAVES", sp.mwaves}, {"NDIM", sp.ndim},
                                                  {"NAUX", sp.naux},        {"USLICES", sp.slices()}, {"FORM", sp.form},
                                                  {"SHARP", sp.sharp()},    {"SHARP_CD", sp.char_decomp},
-                                                 {"ONEK", sp.onek}};
+                                                 {"ONEK", sp.onek},         {"TRANS3", sp.trans3},
+                                                 {"SWEEP3", cellrp_has_sweep3(sp)}};
     for (const auto &d : defs) job.opts.push_back(std::string("-DPCL_CELLRP_") + d.first + "=" + n(d.second));
     job.what = "Riemann solver body";
     static int seq = 0;

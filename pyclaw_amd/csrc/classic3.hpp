@@ -561,6 +561,409 @@ __global__ __launch_bounds__(NW *WAVE) void march3p_kernel(SweepArgs a, Slices3A
     cfl_publish(a.cfl, cfl_value<false>(cflmax, a.dtd));
 }
 
+// ---- the general form: any meqn, every component of every split, rpt3 / rptt3 given by the solver --------------------
+// For a solver RP with transverse3<DIR, ICOOR>(...) and, where RP::TRANS3 == 2, dtransverse3<DIR, ICOOR>(...) (a user-written
+// solver with rpt3 / rptt3 bodies, cellrp.hpp).  Two kernels per direction instead of the march: with 16 user solves per
+// interface the pieces of a slice do not stay in registers across a march for general meqn.
+//   pieces3_kernel   one wavefront per strip of one slice (e, f), one lane per cell of the sweep line, neighbours by the
+//                    lane shifts slice3_pieces_p uses (60 owned cells per wavefront).  Every statement of flux3.f in its
+//                    order and association (oracle/classic_oracle.c, flux3_full); as in slice3_pieces_p the splits of
+//                    A-dq and of the correction flux of interface l+1 are made in lane l, whose cell they belong to
+//                    (imp = 1), after fetching the input from the right-hand lane.  The 14 * meqn values of a cell --
+//                    qadd, fadd(i+1) - fadd(i), gadd(1:2, -1:1), hadd(1:2, -1:1) -- go to scratch planes as each is final.
+//   gather3_kernel   one thread per interior cell: the nine slices around it in the order of step3.f's loop nest, each
+//                    as q = (q + A) + B with pair3p's formulas (26 * meqn reads), the centre's qadd and -dtd * dfadd in front.
+// The scratch is dense (no row pitch): cell (i, j, k) with ghost cells at i + n0 * (j + n1 * k), value v of component m
+// in plane v * meqn + m (sweep_args.hpp: unsplit3_scratch_bytes).
+constexpr int P3_QADD = 0, P3_DF = 1, P3_G = 2, P3_H = 8;      // value index: G / H + 3 * (k - 1) + (j + 1)
+static_assert(P3_H + 6 == UNSPLIT3_VALUES, "14 values per cell and component");
+struct Pieces3Args {
+    double *scr;
+    long s_al, s_e, s_f;   // scratch strides (doubles) of the sweep, y-like and z-like directions
+    long cells;            // doubles per scratch plane
+    int g0, g1, g2;        // the grid of workgroups (g0 fastest); the launch is g0 * g1 * g2 blocks in one dimension
+};
+
+// one rpt3: the fluctuation `in` of the interface whose side imp says (1: it belongs to the cell left of the interface,
+// 2: right of it); this lane's cell q0 is that cell either way, qm / qp are its left / right neighbours
+template <class RP, int DIR, int ICOOR>
+__device__ __forceinline__ void rpt3_lane(int imp, const double (&qm)[RP::MEQN], const double (&q0)[RP::MEQN],
+                                          const double (&qp)[RP::MEQN], const double (&blk)[3][3][RP::NAUX > 0 ? RP::NAUX : 1],
+                                          const RpParams &par, const double (&in)[RP::MEQN], double (&om)[RP::MEQN],
+                                          double (&op)[RP::MEQN]) {
+    if constexpr (RP::NAUX > 0) RP::template transverse3<DIR, ICOOR>(imp, q0, blk, par, in, om, op);
+    else RP::template transverse3<DIR, ICOOR>(imp == 1 ? q0 : qm, imp == 1 ? qp : q0, par, in, om, op);
+}
+template <class RP, int DIR, int ICOOR>
+__device__ __forceinline__ void rptt3_lane(int imp, int impt, const double (&qm)[RP::MEQN], const double (&q0)[RP::MEQN],
+                                           const double (&qp)[RP::MEQN], const double (&blk)[3][3][RP::NAUX > 0 ? RP::NAUX : 1],
+                                           const RpParams &par, const double (&in)[RP::MEQN], double (&om)[RP::MEQN],
+                                           double (&op)[RP::MEQN]) {
+    if constexpr (RP::NAUX > 0) RP::template dtransverse3<DIR, ICOOR>(imp, impt, q0, blk, par, in, om, op);
+    else RP::template dtransverse3<DIR, ICOOR>(impt, imp == 1 ? q0 : qm, imp == 1 ? qp : q0, par, in, om, op);
+}
+
+// A workgroup is P3_NW wavefronts on neighbouring slices of one transverse direction: the one whose index is i, the
+// contiguous one, where there is one (y sweep: z-like, z sweep: y-like), so that the wavefronts of a workgroup touch
+// neighbouring doubles of every line a lane reads or writes, as march3p_kernel's do; in the x sweep the y-like one.
+constexpr int P3_NW = 8;
+template <int DIR> constexpr bool p3_waves_on_f() { return DIR == 2; }
+template <class RP, int DIR>
+__global__ __launch_bounds__(WAVE *P3_NW) void pieces3_kernel(SweepArgs a, Slices3Args t, Pieces3Args g) {
+    constexpr int MEQN = RP::MEQN, MWAVES = RP::MWAVES, NAUX = RP::NAUX, NB = NAUX > 0 ? NAUX : 1;
+    using Cell = typename RP::Cell;
+    const int lane = threadIdx.x & (WAVE - 1), w = threadIdx.x / WAVE;
+    // block indices of the strip along the sweep and of the y-like / z-like slices.  The fastest one, b0, runs along i in
+    // every direction, and workgroups that are neighbours along i run on the same XCD close in time (xcd_logical_block):
+    // the 60-cell strips and the P3_NW-column tiles are not line-aligned, so neighbours share lines of q and aux and write
+    // the two parts of scratch lines, which merge in that XCD's L2 before they go to HBM
+    const int bid = xcd_logical_block();
+    const int b0 = bid % g.g0, b1 = (bid / g.g0) % g.g1, b2 = bid / (g.g0 * g.g1);
+    const int bs = DIR == 1 ? b0 : b2;
+    const int be = DIR == 3 ? b0 : b1;
+    const int bf = DIR == 1 ? b2 : DIR == 2 ? b0 : b1;
+    const int ca = a.mbc - HALO + bs * STRIP + lane;
+    const int cc = ca < a.n_al ? ca : a.n_al - 1;
+    // y and z sweeps: the lanes of a wavefront are a row / a plane of the array apart, 64 lines per load / store
+    // instruction.  Their wave axis is i: the workgroup moves q in and the 14 * meqn results out as 64-row x P3_NW-column
+    // tiles, 64 B per row segment, transposed through LDS (STAGED; as march3p_kernel's tiles).  A wavefront past the last
+    // swept slice then stays for the barriers: it computes that last slice again and stores nothing.
+    constexpr bool STAGED = DIR != 1;
+    constexpr int SV = 8;       // values the stage holds at once: MEQN <= 8 components of q, or a group of results
+    static_assert(MEQN <= SV && SV >= 6, "the stage holds q of one cell and the six G or H values of one component");
+    __shared__ double stg[STAGED ? SV : 1][STAGED ? WAVE : 1][STAGED ? P3_NW + 1 : 1];
+    const int we = t.lo_e + (p3_waves_on_f<DIR>() ? be : be * P3_NW + w);
+    const int wf = t.lo_f + (p3_waves_on_f<DIR>() ? bf * P3_NW + w : bf);
+    if (!STAGED && (we > t.hi_e || wf > t.hi_f)) return;     // (wave-uniform, and no barrier on this path)
+    const int ce = we > t.hi_e ? t.hi_e : we, cf = wf > t.hi_f ? t.hi_f : wf;
+    const bool owned = (ca >= a.mbc) && (ca < a.mbc + a.m_al) && lane >= HALO && lane < WAVE - HALO;
+    const bool cfl_ok = (ca >= a.mbc) && (ca <= a.mbc + a.m_al) && lane >= 1;
+    const long gq = (long)cc * a.s_al + (long)ce * t.s_e + (long)cf * t.s_f;
+    // this thread's cell of the cooperative tiles: row tr along the sweep, column tc along the wave axis
+    const int tc = threadIdx.x % P3_NW, tr = threadIdx.x / P3_NW;
+    const int ta = a.mbc - HALO + bs * STRIP + tr;
+    const int te_w = t.lo_e + (p3_waves_on_f<DIR>() ? be : be * P3_NW + tc);
+    const int tf_w = t.lo_f + (p3_waves_on_f<DIR>() ? bf * P3_NW + tc : bf);
+    const bool t_owned = (ta >= a.mbc) && (ta < a.mbc + a.m_al) && tr >= HALO && tr < WAVE - HALO && te_w <= t.hi_e && tf_w <= t.hi_f;
+    const int te = te_w > t.hi_e ? t.hi_e : te_w, tf = tf_w > t.hi_f ? t.hi_f : tf_w;
+    const long tgs = (long)ta * g.s_al + (long)te * g.s_e + (long)tf * g.s_f;      // (used where t_owned: inside the scratch)
+    double q[MEQN], blk[3][3][NB];
+    // the aux block's offsets are clamped like load_blk's: every USED block lies inside the array (slices 0..m+1, mbc = 2)
+    if constexpr (STAGED) {
+        const long tgq = (long)(ta < a.n_al ? ta : a.n_al - 1) * a.s_al + (long)te * t.s_e + (long)tf * t.s_f;
+#pragma unroll
+        for (int m = 0; m < MEQN; m++) stg[m][tr][tc] = a.qin[m * a.plane + tgq];
+        __syncthreads();
+#pragma unroll
+        for (int m = 0; m < MEQN; m++) q[m] = stg[m][lane][w];
+        __syncthreads();
+        // the 9 * NAUX values of the block, SV tiles at a time: value x = ((oe + 1) * 3 + (of + 1)) * NAUX + k
+        constexpr int NX = NAUX > 0 ? 9 * NAUX : 0;
+#pragma unroll
+        for (int x0 = 0; x0 < NX; x0 += SV) {
+#pragma unroll
+            for (int j = 0; j < SV; j++) {
+                const int x = x0 + j;
+                if (x < NX) {
+                    const int oe = x / (3 * NB) - 1, of = (x / NB) % 3 - 1, k = x % NB;
+                    const int de = (te + oe < 0) ? 0 : (te + oe >= t.n_e ? 0 : oe);
+                    const int df_ = (tf + of < 0) ? 0 : (tf + of >= t.n_f ? 0 : of);
+                    stg[j][tr][tc] = a.aux[aux_idx<RP, DIR>(k) * a.plane + tgq + de * t.s_e + df_ * t.s_f];
+                }
+            }
+            __syncthreads();
+#pragma unroll
+            for (int j = 0; j < SV; j++) {
+                const int x = x0 + j;
+                if (x < NX) blk[x / (3 * NB)][(x / NB) % 3][x % NB] = stg[j][lane][w];
+            }
+            __syncthreads();
+        }
+        if constexpr (NAUX == 0) {
+#pragma unroll
+            for (int x = 0; x < 9; x++) blk[x / 3][x % 3][0] = 0.0;
+        }
+    } else {
+#pragma unroll
+        for (int m = 0; m < MEQN; m++) q[m] = a.qin[m * a.plane + gq];
+#pragma unroll
+        for (int oe = -1; oe <= 1; oe++)
+#pragma unroll
+            for (int of = -1; of <= 1; of++) {
+                const int de = (ce + oe < 0) ? 0 : (ce + oe >= t.n_e ? 0 : oe);
+                const int df_ = (cf + of < 0) ? 0 : (cf + of >= t.n_f ? 0 : of);
+#pragma unroll
+                for (int k = 0; k < NB; k++)
+                    blk[oe + 1][of + 1][k] = NAUX > 0 ? a.aux[aux_idx<RP, DIR>(k) * a.plane + gq + de * t.s_e + df_ * t.s_f] : 0.0;
+            }
+    }
+    const double d = a.dtd;
+    Cell cR;
+    if constexpr (NAUX > 0) {
+        double auxv[NB];
+#pragma unroll
+        for (int k = 0; k < NB; k++) auxv[k] = blk[1][1][k];
+        cR = RP::template precell<DIR>(q, a.par, auxv);
+    } else cR = RP::template precell<DIR>(q, a.par);
+    const Cell cL = struct_from_left(cR);
+    double wave[MWAVES][MEQN], s[MWAVES], amdq[MEQN], apdq[MEQN];
+    RP::template solve<DIR>(cL, cR, a.par, wave, s, amdq, apdq);
+    double cflmax = 0.0;
+    cfl_accumulate<false, MWAVES>(s, d, d, cfl_ok, cflmax);
+    cfl_publish(a.cfl, cfl_value<false>(cflmax, a.dtd));
+    double cq[MEQN];
+#pragma unroll
+    for (int m = 0; m < MEQN; m++) cq[m] = 0.0;
+    if (a.order != 1) {
+#pragma unroll
+        for (int mw = 0; mw < MWAVES; mw++) {
+            const int lim = a.mthlim[mw];
+            if (lim == 0) continue;
+            double wn = 0.0, dl = 0.0;
+#pragma unroll
+            for (int m = 0; m < MEQN; m++) {
+                const double w = wave[mw][m], wl = from_left(w);
+                wn = m == 0 ? w * w : wn + w * w;
+                dl = m == 0 ? wl * w : dl + wl * w;
+            }
+            const double dr = from_right(dl);
+            if (wn != 0.0) {
+                const double phi = philim(wn, s[mw] > 0.0 ? dl : dr, lim);
+#pragma unroll
+                for (int m = 0; m < MEQN; m++) wave[mw][m] = phi * wave[mw][m];
+            }
+        }
+        const double dtdxave = 0.5 * (d + d);
+#pragma unroll
+        for (int m = 0; m < MEQN; m++) {
+            double c = 0.0;
+#pragma unroll
+            for (int mw = 0; mw < MWAVES; mw++) {
+                const double sa = fabs(s[mw]);
+                const double term = 0.5 * sa * (1.0 - sa * dtdxave) * wave[mw][m];
+                c = mw == 0 ? term : c + term;
+            }
+            cq[m] = c;
+        }
+    }
+    const long gs = (long)cc * g.s_al + (long)ce * g.s_e + (long)cf * g.s_f;
+    // STAGED: put(slot, ...) leaves a value in the stage and flush(n, plane of slot k) moves the first n slots out; else put
+    // stores at once and flush does nothing
+    auto put = [&](int slot, int v, int m, double x) {
+        if constexpr (STAGED) stg[slot][lane][w] = x;
+        else if (owned) g.scr[(long)(v * MEQN + m) * g.cells + gs] = x;
+    };
+    auto flush = [&](int n, auto plane_of) {
+        if constexpr (STAGED) {
+            __syncthreads();
+#pragma unroll
+            for (int k = 0; k < SV; k++)
+                if (k < n && t_owned) g.scr[(long)plane_of(k) * g.cells + tgs] = stg[k][tr][tc];
+            __syncthreads();
+        }
+    };
+    // the fluctuations and correction fluxes of this cell: A+dq and cqxx of interface l (imp = 2), A-dq and cqxx of
+    // interface l+1 (imp = 1)
+    double aP[MEQN], aM[MEQN], kP[MEQN], kM[MEQN], qm[MEQN], qp[MEQN];
+#pragma unroll
+    for (int m = 0; m < MEQN; m++) {
+        aP[m] = apdq[m]; aM[m] = from_right(amdq[m]);
+        kP[m] = cq[m]; kM[m] = from_right(cq[m]);
+        qm[m] = NAUX > 0 ? 0.0 : from_left(q[m]);
+        qp[m] = NAUX > 0 ? 0.0 : from_right(q[m]);
+    }
+#pragma unroll
+    for (int m = 0; m < MEQN; m++) {
+        put(0, P3_QADD, m, -(d * aP[m]) - d * aM[m]);
+        put(1, P3_DF, m, kM[m] - kP[m]);
+        flush(2, [&](int k) { return k * MEQN + m; });
+    }
+    const int m3 = t.m3, m4 = t.m4;
+    if (m3 <= 0) {      // flux3.f:260: no transverse propagation (the same for every wavefront)
+#pragma unroll
+        for (int m = 0; m < MEQN; m++) {
+#pragma unroll
+            for (int k = 0; k < 6; k++) put(k, P3_G + k, m, 0.0);
+            flush(6, [&](int k) { return (P3_G + k) * MEQN + m; });
+#pragma unroll
+            for (int k = 0; k < 6; k++) put(k, P3_H + k, m, 0.0);
+            flush(6, [&](int k) { return (P3_H + k) * MEQN + m; });
+        }
+        return;
+    }
+#define PCL_T3(ICOOR, imp, in, om, op) rpt3_lane<RP, DIR, ICOOR>(imp, qm, q, qp, blk, a.par, in, om, op)
+#define PCL_TT3(ICOOR, imp, impt, in, om, op) rptt3_lane<RP, DIR, ICOOR>(imp, impt, qm, q, qp, blk, a.par, in, om, op)
+    // names as in flux3.f; the ...amdq / ...cqxxm ones are those of interface l+1
+    double bmamdq[MEQN], bpamdq[MEQN], bmapdq[MEQN], bpapdq[MEQN], cmamdq[MEQN], cpamdq[MEQN], cmapdq[MEQN], cpapdq[MEQN];
+    PCL_T3(2, 1, aM, bmamdq, bpamdq);
+    PCL_T3(2, 2, aP, bmapdq, bpapdq);
+    PCL_T3(3, 1, aM, cmamdq, cpamdq);
+    PCL_T3(3, 2, aP, cmapdq, cpapdq);
+    double bmcqxxm[MEQN], bpcqxxm[MEQN], bmcqxxp[MEQN], bpcqxxp[MEQN], cmcqxxm[MEQN], cpcqxxm[MEQN], cmcqxxp[MEQN], cpcqxxp[MEQN];
+#pragma unroll
+    for (int m = 0; m < MEQN; m++) {
+        bmcqxxm[m] = 0.0; bpcqxxm[m] = 0.0; bmcqxxp[m] = 0.0; bpcqxxp[m] = 0.0;
+        cmcqxxm[m] = 0.0; cpcqxxm[m] = 0.0; cmcqxxp[m] = 0.0; cpcqxxp[m] = 0.0;
+    }
+    if (m3 == 2) {      // flux3.f:299-337: with aux one split per side; without, the same values from the side's own pair
+        PCL_T3(2, 1, kM, bmcqxxm, bpcqxxm);
+        PCL_T3(2, 2, kP, bmcqxxp, bpcqxxp);
+        PCL_T3(3, 1, kM, cmcqxxm, cpcqxxm);
+        PCL_T3(3, 2, kP, cmcqxxp, cpcqxxp);
+    }
+    // one component of the six G (or H) values of this cell: flux3.f's statements in their order (slice3_pieces_p: six)
+    auto six = [&](int vbase, int m, double k6, double bmap, double bpap, double bmam, double bpam, double xmcpap, double xpcpap,
+                   double xmcmap, double xpcmap, double xmcpam, double xpcpam, double xmcmam, double xpcmam, double qmp, double qpp,
+                   double qmm, double qpm) {
+        double g10 = 0.0, g20 = 0.0, g21 = 0.0, g11 = 0.0, g2m = 0.0, g1m = 0.0;
+        g10 = g10 - 0.5 * d * bmap;
+        g20 = g20 - 0.5 * d * bpap;
+        if (m4 > 0) {
+            g20 = g20 + k6 * (xpcpap - xpcmap);
+            g10 = g10 + k6 * (xmcpap - xmcmap);
+            g21 = g21 - k6 * xpcpap;
+            g11 = g11 - k6 * xmcpap;
+            g2m = g2m + k6 * xpcmap;
+            g1m = g1m + k6 * xmcmap;
+        }
+        if (m3 >= 2) {
+            g20 = g20 + d * qpp;
+            g10 = g10 + d * qmp;
+        }
+        g10 = g10 - 0.5 * d * bmam;                 // interface l+1
+        g20 = g20 - 0.5 * d * bpam;
+        if (m4 > 0) {
+            g20 = g20 + k6 * (xpcpam - xpcmam);
+            g10 = g10 + k6 * (xmcpam - xmcmam);
+            g21 = g21 - k6 * xpcpam;
+            g11 = g11 - k6 * xmcpam;
+            g2m = g2m + k6 * xpcmam;
+            g1m = g1m + k6 * xmcmam;
+        }
+        if (m3 >= 2) {
+            g20 = g20 - d * qpm;
+            g10 = g10 - d * qmm;
+        }
+        // value index vbase + 3 * (k - 1) + (j + 1)
+        put(0, vbase + 0, m, g1m); put(1, vbase + 1, m, g10); put(2, vbase + 2, m, g11);
+        put(3, vbase + 3, m, g2m); put(4, vbase + 4, m, g20); put(5, vbase + 5, m, g21);
+        flush(6, [&](int k) { return (vbase + k) * MEQN + m; });
+    };
+    const double k6z = (1.0 / 6.0) * d * t.dtz, k6y = (1.0 / 6.0) * d * t.dty;
+    double xmcpap[MEQN], xpcpap[MEQN], xmcpam[MEQN], xpcpam[MEQN], xmcmap[MEQN], xpcmap[MEQN], xmcmam[MEQN], xpcmam[MEQN];
+    auto zero8 = [&]() {
+#pragma unroll
+        for (int m = 0; m < MEQN; m++) {
+            xmcpap[m] = 0.0; xpcpap[m] = 0.0; xmcpam[m] = 0.0; xpcpam[m] = 0.0;
+            xmcmap[m] = 0.0; xpcmap[m] = 0.0; xmcmam[m] = 0.0; xpcmam[m] = 0.0;
+        }
+    };
+    {   // ---- G fluxes (y-like), flux3.f:347-452: the z-like splits (corrected by the correction waves' for m4 = 2)
+        // split again in the y-like direction, inside the z-like row they went to
+        zero8();
+        if constexpr (RP::TRANS3 >= 2) {
+            if (m4 > 0) {
+                double pp[MEQN], pm[MEQN], mp[MEQN], mm[MEQN];
+#pragma unroll
+                for (int m = 0; m < MEQN; m++) {
+                    pp[m] = m4 == 2 ? cpapdq[m] - 3.0 * cpcqxxp[m] : cpapdq[m];
+                    pm[m] = m4 == 2 ? cpamdq[m] + 3.0 * cpcqxxm[m] : cpamdq[m];
+                    mp[m] = m4 == 2 ? cmapdq[m] - 3.0 * cmcqxxp[m] : cmapdq[m];
+                    mm[m] = m4 == 2 ? cmamdq[m] + 3.0 * cmcqxxm[m] : cmamdq[m];
+                }
+                PCL_TT3(2, 2, 2, pp, xmcpap, xpcpap);
+                PCL_TT3(2, 1, 2, pm, xmcpam, xpcpam);
+                PCL_TT3(2, 2, 1, mp, xmcmap, xpcmap);
+                PCL_TT3(2, 1, 1, mm, xmcmam, xpcmam);
+            }
+        }
+#pragma unroll
+        for (int m = 0; m < MEQN; m++)
+            six(P3_G, m, k6z, bmapdq[m], bpapdq[m], bmamdq[m], bpamdq[m], xmcpap[m], xpcpap[m], xmcmap[m], xpcmap[m], xmcpam[m],
+                xpcpam[m], xmcmam[m], xpcmam[m], bmcqxxp[m], bpcqxxp[m], bmcqxxm[m], bpcqxxm[m]);
+    }
+    {   // ---- H fluxes (z-like), flux3.f:462-590: the y-like splits (corrected for m4 = 2) split again in the z-like direction
+        zero8();
+        if constexpr (RP::TRANS3 >= 2) {
+            if (m4 > 0) {
+                double pp[MEQN], pm[MEQN], mp[MEQN], mm[MEQN];
+#pragma unroll
+                for (int m = 0; m < MEQN; m++) {
+                    pp[m] = m4 == 2 ? bpapdq[m] - 3.0 * bpcqxxp[m] : bpapdq[m];
+                    pm[m] = m4 == 2 ? bpamdq[m] + 3.0 * bpcqxxm[m] : bpamdq[m];
+                    mp[m] = m4 == 2 ? bmapdq[m] - 3.0 * bmcqxxp[m] : bmapdq[m];
+                    mm[m] = m4 == 2 ? bmamdq[m] + 3.0 * bmcqxxm[m] : bmamdq[m];
+                }
+                PCL_TT3(3, 2, 2, pp, xmcpap, xpcpap);
+                PCL_TT3(3, 1, 2, pm, xmcpam, xpcpam);
+                PCL_TT3(3, 2, 1, mp, xmcmap, xpcmap);
+                PCL_TT3(3, 1, 1, mm, xmcmam, xpcmam);
+            }
+        }
+#pragma unroll
+        for (int m = 0; m < MEQN; m++)
+            six(P3_H, m, k6y, cmapdq[m], cpapdq[m], cmamdq[m], cpamdq[m], xmcpap[m], xpcpap[m], xmcmap[m], xpcmap[m], xmcpam[m],
+                xpcpam[m], xmcmam[m], xpcmam[m], cmcqxxp[m], cpcqxxp[m], cmcqxxm[m], cpcqxxm[m]);
+    }
+#undef PCL_T3
+#undef PCL_TT3
+}
+
+// what a gather launch needs: the scratch, where a cell's accumulator starts from (qold in the x direction, the state
+// accumulated so far in y and z) and the result; threads run over (i, j, k) with i, the contiguous index, fastest in
+// every direction, and the direction only names the strides of the y-like and z-like neighbours
+struct Gather3Args {
+    const double *scr, *qsrc;
+    double *qacc;
+    long plane;                 // doubles between components of q
+    long s[3];                  // strides of q (doubles) along x, y, z
+    long c[3], cells;           // the same of the scratch, and doubles per scratch plane
+    long c_e, c_f;              // scratch strides of the y-like / z-like direction
+    int mbc, m[3], meqn;
+    double dtd, dty, dtz;
+};
+
+// E_OUTER: the y-like index is the outer one of step3.f's loop nest (the y sweep), else the z-like one
+template <bool E_OUTER>
+__global__ __launch_bounds__(256) void gather3_kernel(Gather3Args g) {
+    const int i0 = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i0 >= g.m[0] || (int)blockIdx.y >= g.m[1] || (int)blockIdx.z >= g.m[2]) return;
+    const int c0 = g.mbc + i0, c1 = g.mbc + (int)blockIdx.y, c2 = g.mbc + (int)blockIdx.z;
+    const long gq = (long)c0 * g.s[0] + (long)c1 * g.s[1] + (long)c2 * g.s[2];
+    const long gs = (long)c0 * g.c[0] + (long)c1 * g.c[1] + (long)c2 * g.c[2];
+    const double dty = g.dty, dtz = g.dtz;
+    for (int m = 0; m < g.meqn; m++) {
+        double v = g.qsrc[m * g.plane + gq];
+#pragma unroll
+        for (int so = -1; so <= 1; so++)
+#pragma unroll
+            for (int si = -1; si <= 1; si++) {
+                // the source slice at (se, sf) from here; this cell lies at (oe, of) = (-se, -sf) from it
+                const int se = E_OUTER ? so : si, sf = E_OUTER ? si : so;
+                const int oe = -se, of = -sf;
+                const long src = gs + se * g.c_e + sf * g.c_f;
+                auto val = [&](int vi) { return g.scr[(long)(vi * g.meqn + m) * g.cells + src]; };
+                auto G_ = [&](int k, int j) { return val(P3_G + 3 * (k - 1) + (j + 1)); };
+                auto H_ = [&](int k, int j) { return val(P3_H + 3 * (k - 1) + (j + 1)); };
+                double A, B;      // step3.f's update formulas, as pair3p
+                if (oe == 0 && of == 0) {
+                    v = v + val(P3_QADD);
+                    v = v - g.dtd * val(P3_DF);
+                    A = -(dty * (G_(2, 0) - G_(1, 0))); B = -(dtz * (H_(2, 0) - H_(1, 0)));
+                } else if (oe == -1 && of == 0) { A = -(dty * G_(1, 0)); B = -(dtz * (H_(2, -1) - H_(1, -1))); }
+                else if (oe == -1 && of == -1) { A = -(dty * G_(1, -1)); B = -(dtz * H_(1, -1)); }
+                else if (oe == 0 && of == -1) { A = -(dty * (G_(2, -1) - G_(1, -1))); B = -(dtz * H_(1, 0)); }
+                else if (oe == 1 && of == -1) { A = dty * G_(2, -1); B = -(dtz * H_(1, 1)); }
+                else if (oe == 1 && of == 0) { A = dty * G_(2, 0); B = -(dtz * (H_(2, 1) - H_(1, 1))); }
+                else if (oe == 1 && of == 1) { A = dty * G_(2, 1); B = dtz * H_(2, 1); }
+                else if (oe == 0 && of == 1) { A = -(dty * (G_(2, 1) - G_(1, 1))); B = dtz * H_(2, 0); }
+                else { A = -(dty * G_(1, 1)); B = dtz * H_(2, -1); }
+                v = (v + A) + B;
+            }
+        g.qacc[m * g.plane + gq] = v;
+    }
+}
+
 // ghost frame of the accumulated state := the old state's (the first direction writes interior cells only)
 __global__ __launch_bounds__(256) void ghost3_copy_kernel(const double *src, double *dst, int meqn, long plane, int I, int J, int K,
                                                            long pitch, int mbc) {

@@ -350,7 +350,81 @@ template <class RP, int DIR> int launch_unsplit3_t(const Unsplit3Launch &l, std:
 }
 }  // namespace
 
+// The general unsplit 3-D step of one direction around a user-written solver with rpt3 / rptt3 bodies (classic3.hpp):
+// pieces3_kernel<UserRp, DIR> of the attached module, then the library's gather3_kernel.  One plan per kernel, stated once.
+namespace {
+using Pieces3Plan = Plan<SweepArgs, Slices3Args, Pieces3Args>;
+using Gather3Plan = Plan<Gather3Args>;
+int unsplit3_general_plans(const Unsplit3Launch &l, Pieces3Plan &pp, Gather3Plan &gp, std::string &err) {
+    const SweepArgs &a = l.a;
+    const auto no = [&err](const char *why) { err = why; return PCL_EINVAL; };
+    if (l.dir < 1 || l.dir > 3) return no("unsplit 3-D step: direction must be 1, 2 or 3");
+    if (a.mbc != HALO) return no("unsplit 3-D step: mbc = 2");
+    if (!l.scratch) return no("unsplit 3-D step (user-written Riemann solver): no scratch planes were allocated");
+    const int d = l.dir - 1, e = (d + 1) % 3, f = (d + 2) % 3;
+    if (l.n3[d] != a.n_al || l.n3[e] != l.n_e || l.n3[f] != l.n_f) return no("unsplit 3-D step: the scratch extents are not the block's");
+    if (((long)a.m_al / STRIP + 1) * (l.m_e + 2) * (l.m_f + 2) > 0x7fffffffL || l.m_e > 65535 || l.m_f > 65535)
+        return no("unsplit 3-D step: the block is too large for one launch");
+    const long sc[3] = {1, (long)l.n3[0], (long)l.n3[0] * l.n3[1]};
+    const long cells = sc[2] * l.n3[2];
+    Slices3Args t;
+    t.s_e = l.s_e; t.s_f = l.s_f; t.n_e = l.n_e; t.n_f = l.n_f;
+    t.lo_e = a.mbc - 1; t.hi_e = a.mbc + l.m_e; t.lo_f = a.mbc - 1; t.hi_f = a.mbc + l.m_f;
+    t.m3 = l.m3; t.m4 = l.m4; t.dty = l.dty; t.dtz = l.dtz;
+    Pieces3Args p;
+    p.scr = l.scratch; p.s_al = sc[d]; p.s_e = sc[e]; p.s_f = sc[f]; p.cells = cells;
+    const int nstrips = (a.m_al + STRIP - 1) / STRIP;
+    const bool on_f = l.dir == 2;       // p3_waves_on_f: which transverse direction a workgroup's wavefronts lie along
+    const int ge = on_f ? l.m_e + 2 : (l.m_e + 2 + P3_NW - 1) / P3_NW, gf = on_f ? (l.m_f + 2 + P3_NW - 1) / P3_NW : l.m_f + 2;
+    static_assert(!p3_waves_on_f<1>() && p3_waves_on_f<2>() && !p3_waves_on_f<3>(), "the grid follows the kernel's wave axis");
+    // (the fastest index runs along i in every direction: pieces3_kernel's b0, b1, b2)
+    p.g0 = l.dir == 1 ? nstrips : l.dir == 2 ? gf : ge;
+    p.g1 = l.dir == 3 ? gf : ge;
+    p.g2 = l.dir == 1 ? gf : nstrips;
+    pp = {dim3((unsigned)p.g0 * (unsigned)p.g1 * (unsigned)p.g2), dim3(WAVE * P3_NW), l.stream, {a, t, p}};
+    Gather3Args g;
+    g.scr = l.scratch; g.qsrc = l.dir == 1 ? a.qin : l.qacc; g.qacc = l.qacc;
+    g.plane = a.plane;
+    const long sq[3] = {a.s_al, l.s_e, l.s_f};      // (sweep, y-like, z-like) -> (x, y, z)
+    const int mq[3] = {a.m_al, l.m_e, l.m_f};
+    const int axis[3] = {d, e, f};
+    for (int k = 0; k < 3; k++) { g.s[axis[k]] = sq[k]; g.m[axis[k]] = mq[k]; g.c[k] = sc[k]; }
+    g.cells = cells; g.c_e = sc[e]; g.c_f = sc[f];
+    g.mbc = a.mbc; g.meqn = l.user->meqn;
+    g.dtd = a.dtd; g.dty = l.dty; g.dtz = l.dtz;
+    gp = {dim3((unsigned)((g.m[0] + 255) / 256), (unsigned)g.m[1], (unsigned)g.m[2]), dim3(256), l.stream, {g}};
+    return PCL_OK;
+}
+
+int launch_unsplit3_user(const Unsplit3Launch &l, std::string &err) {
+    const auto no = [&err](const char *why) { err = why; return PCL_EINVAL; };
+    const int slot = l.dir >= 1 && l.dir <= 3 ? SLOT_PIECES3_X + l.dir - 1 : -1;
+    const hipFunction_t f = l.user_fns && l.user && slot >= 0 ? l.user_fns[slot] : nullptr;
+    if (!f || !l.user->trans3) {
+        err = "user-written Riemann solver: no solver compiled with rpt3 / rptt3 bodies is attached (pcl_cellrp_compile3t, pcl_cellrp_attach)";
+        return PCL_ESTATE;
+    }
+    const CellrpSpec &u = *l.user;
+    if (l.m4 > 0 && u.trans3 < 2) return no("user-written Riemann solver: the attached solver has no rptt3 body and method[2] asks for double-transverse terms");
+    if (l.fwave || u.fwave()) return no("user-written Riemann solver: no f-waves in 3-D");
+    if (l.a.mcapa > 0 || u.capa()) return no("3-D: capacity function not implemented in the unsplit step");
+    if (l.a.src_id != 0) return no(USER_NO_SRC);
+    if (u.naux > 0 && !l.a.aux) return no("user-written Riemann solver: this solver reads aux arrays and there are none (pcl_put_aux)");
+    Pieces3Plan pp;
+    Gather3Plan gp;
+    if (int rc = unsplit3_general_plans(l, pp, gp, err)) return rc;
+    if (l.dir == 1) {     // the first direction writes interior cells only: the ghost frame of the result := qold's
+        const int I = l.a.n_al, J = l.n_e, K = l.n_f;
+        hipLaunchKernelGGL(ghost3_copy_kernel, dim3((unsigned)((I + 255) / 256), (unsigned)J, (unsigned)K), dim3(256), 0,
+                           l.stream, l.a.qin, l.qacc, u.meqn, l.a.plane, I, J, K, l.s_e, l.a.mbc);
+    }
+    if (int rc = launched(fire(f, pp), "pieces3 launch (user-written Riemann solver)", err)) return rc;
+    return launched(l.dir == 2 ? fire(gather3_kernel<true>, gp) : fire(gather3_kernel<false>, gp), "gather3 launch", err);
+}
+}  // namespace
+
 int launch_unsplit3(const Unsplit3Launch &l, std::string &err) {
+    if (l.rp == PCL_RP_CELL) return launch_unsplit3_user(l, err);
     if (l.rp != VcAcoustics3D::ID) { err = "Riemann solver id is not a 3-D solver with transverse solvers"; return PCL_EINVAL; }
     if (l.a.mcapa > 0) { err = "3-D: capacity function not implemented"; return PCL_EINVAL; }
     if (l.dir == 1) return launch_unsplit3_t<VcAcoustics3D, 1>(l, err);

@@ -1,6 +1,7 @@
 // pclaw.hip -- C ABI of libpyclaw_amd.so (see include/pyclaw_amd.h).
 // gfx950 only.  No CPU fallback: every entry point needs a HIP device.
 #include <hip/hip_runtime.h>
+#include <atomic>
 #include <cstddef>
 #include <cstdio>
 #include <cstdlib>
@@ -99,6 +100,10 @@ struct pcl_solver {
     double *cf_snap = nullptr;     // reach > 0: the copy of the selected register the launch reads, allocated at the first one
     // cfg.rp == PCL_RP_CELL: the user-written Riemann solver's module (cellrp.hpp, pcl_cellrp_attach)
     pcl::CellrpModule cellrp;
+    // the scratch planes of the general unsplit 3-D step (classic3.hpp; sweep_args.hpp: unsplit3_scratch_bytes): allocated when
+    // a handle with rpt3 / rptt3 bodies is attached to an unsplit 3-D configuration, freed by pcl_destroy
+    double *scr3 = nullptr;
+    long long scr3_bytes = 0;
     // pcl_put_aux has been called: the aux allocation holds the caller's coefficients and not the zeros of pcl_create.
     // A user-written solver whose body reads aux is not launched before (make_launch)
     bool aux_put = false;
@@ -501,6 +506,16 @@ int do_step2ds(pcl_solver *s, const double *qin, double *qout, double dt, bool c
     return rc;
 }
 
+// bytes of scratch planes of the general unsplit 3-D step that live solvers hold (pcl_unsplit3_scratch_live)
+static std::atomic<long long> g_scr3_live{0};
+static void scr3_release(pcl_solver *s) {
+    if (!s->scr3) return;
+    (void)hipFree(s->scr3);
+    g_scr3_live -= s->scr3_bytes;
+    s->scr3 = nullptr;
+    s->scr3_bytes = 0;
+}
+
 // 3-D dimension-split sweep along dir (1..3), qin -> qout (step3ds.f; kernel in classic.hpp)
 int do_sweep3(pcl_solver *s, const double *qin, double *qout, int dir, double dt) {
     SweepArgs a = make_args(s, qin, qout, 1, dt);
@@ -529,9 +544,10 @@ int do_sweep3(pcl_solver *s, const double *qin, double *qout, int dir, double dt
 // unsplit 3-D step (step3.f): for x, y, z in turn, every slice's pieces applied in the reference's order to t1
 // (march3p_kernel, classic3.hpp).  All three directions read the same qold = q.
 int do_unsplit3(pcl_solver *s, double dt) {
-    if (s->cfg.rp == PCL_RP_CELL)
-        return fail(PCL_EINVAL, "the unsplit 3-D step needs rpt3 and rptt3 solvers: a user-written Riemann solver (PCL_RP_CELL) has "
-                                "the dimension-split 3-D step only");
+    const bool user = s->cfg.rp == PCL_RP_CELL;
+    if (user && !(s->cellrp.mod && s->cellrp.spec.trans3))
+        return fail(PCL_EINVAL, "the unsplit 3-D step needs rpt3 and rptt3 solvers: a user-written Riemann solver (PCL_RP_CELL) "
+                                "compiled without those bodies has the dimension-split 3-D step only (pcl_cellrp_compile3t)");
     const int m3 = s->cfg.method[2] / 10, m4 = s->cfg.method[2] - 10 * m3;
     if (m3 < 0 || m3 > 2 || m4 < 0 || m4 > 2 || (m4 > 0 && m3 == 0))
         return fail(PCL_EINVAL, "3-D order_trans must be 0, 10, 11, 20, 21 or 22 (flux3.f:46-73)");
@@ -551,6 +567,15 @@ int do_unsplit3(pcl_solver *s, double dt) {
         l.m3 = m3; l.m4 = m4;
         l.dty = dt / s->cfg.d[e]; l.dtz = dt / s->cfg.d[f];
         l.dir = dir; l.rp = s->cfg.rp; l.stream = s->stream;
+        if (user) {      // the module's pieces kernels, what it was compiled for, the scratch planes
+            l.user_fns = s->cellrp.fn;
+            l.user = &s->cellrp.spec;
+            l.scratch = s->scr3;
+            l.fwave = s->cfg.fwave;
+            for (int k = 0; k < 3; k++) l.n3[k] = s->cfg.n[k] + 2 * s->cfg.mbc;
+            // nothing uploaded yet: refused by the launcher, as for the sweeps (user_launch_fields)
+            if (l.user->naux > 0 && !s->aux_put) l.a.aux = nullptr;
+        }
         LaunchTimer timer(s, timing_on(s), dir == 1 ? 0 : 1, true, s->stream);
         int rc = PCL_BY_MATH(s->cfg.math, launch_unsplit3(l, err));
         timer.end();
@@ -711,7 +736,7 @@ int check_device() {
 extern "C" {
 
 const char *pcl_last_error(void) { return g_err.c_str(); }
-int pcl_version(void) { return 112; }
+int pcl_version(void) { return 113; }
 int pcl_device_count(void) {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess) return 0;
@@ -730,7 +755,7 @@ int pcl_rp_info(int rp, int info[10]) {
 // solver and checks against it what only the handle can serve (the unsplit step, f-waves, a capacity function:
 // cellrp_fits); pcl_create cannot know it and refuses all three.  handle_ndim: what that handle was compiled for -- a 3-D
 // configuration needs a 3-D handle (pcl_cellrp_compile3), which pcl_create cannot know either.
-static int create_check(const pcl_config *cfg, bool cell_handle, int handle_ndim = 0) {
+static int create_check(const pcl_config *cfg, bool cell_handle, int handle_ndim = 0, int handle_trans3 = 0) {
     if (getenv("PCL_TRACE_ABORT")) {   // diagnostics: C backtrace on abort()
         signal(SIGABRT, [](int) {
             void *bt[64];
@@ -783,10 +808,10 @@ static int create_check(const pcl_config *cfg, bool cell_handle, int handle_ndim
         if (cfg->ndim == 3 && handle_ndim != 3)
             return fail(PCL_EINVAL, "PCL_RP_CELL: the handle holds the 1-D or 2-D kernels; a 3-D configuration (ndim == 3) needs one "
                                     "compiled for the 3-D sweeps (pcl_cellrp_compile3)");
-        if (cfg->ndim == 3 && cfg->method[2] >= 0)
-            return fail(PCL_EINVAL, "PCL_RP_CELL: the unsplit 3-D step (method[2] >= 0, step3) needs rpt3 and rptt3 bodies, and "
-                                    "march3p_kernel is not compiled around a user-written solver: in 3-D it serves the "
-                                    "dimension-split step only (method[2] < 0)");
+        if (cfg->ndim == 3 && cfg->method[2] >= 0 && !handle_trans3)
+            return fail(PCL_EINVAL, "PCL_RP_CELL: the unsplit 3-D step (method[2] >= 0, step3) needs rpt3 and rptt3 bodies "
+                                    "(pcl_cellrp_compile3t); a handle compiled without them serves the dimension-split 3-D step "
+                                    "only (method[2] < 0)");
         if (cfg->ndim == 3 && cfg->fwave)
             return fail(PCL_EINVAL, "PCL_RP_CELL: cfg.fwave = 1: no f-waves in 3-D (sweep3_kernel has no f-wave form)");
         if (cfg->fwave && !cell_handle)
@@ -910,6 +935,7 @@ void pcl_destroy(pcl_solver *s) {
     s->halo.destroy();
     s->cellfn.unload_all();     // here, never from a static destructor: the HIP runtime is still alive
     s->cellrp.unload();
+    scr3_release(s);
     if (s->ev_h0) hipEventDestroy(s->ev_h0);
     if (s->ev_h1) hipEventDestroy(s->ev_h1);
     if (s->ev_y) hipEventDestroy(s->ev_y);
@@ -1884,6 +1910,23 @@ int pcl_cellrp_compile3(const char *body, const char *preamble, int meqn, int mw
     return cellrp_compile(sp, {body, nullptr, preamble}, given, out, code_size);
 }
 
+// The same with the inside of rpt3 and, where rptt3 is not null, of rptt3 (cellrp.hpp: kCellrpTrans3): the code object also
+// holds the pieces kernels of the general unsplit 3-D step (classic3.hpp), one per direction
+int pcl_cellrp_compile3t(const char *body, const char *rpt3, const char *rptt3, const char *preamble, int meqn, int mwaves, int math,
+                         const int *aux_index, int naux, int form, pcl_cellrp **out, long *code_size) {
+    pcl::CellrpSpec sp = cellrp_spec(meqn, mwaves, 3, math, aux_index, naux);
+    sp.form = form;
+    sp.trans3 = rptt3 ? 2 : rpt3 ? 1 : 0;
+    pcl::CellrpGiven given = {};
+    given.aux_list = aux_index != nullptr;
+    given.dim3 = true;
+    given.rpt3 = rpt3 != nullptr;
+    given.rptt3 = rptt3 != nullptr;
+    pcl::CellrpTexts t = {body, nullptr, preamble};
+    t.rpt3 = rpt3; t.rptt3 = rptt3;
+    return cellrp_compile(sp, t, given, out, code_size);
+}
+
 int pcl_cellrp_release(pcl_cellrp *r) {
     if (!r) return PCL_OK;
     CellfnCache &c = cellfn_cache();
@@ -1927,6 +1970,19 @@ int pcl_cellrp_transverse(const pcl_cellrp *r, int *has, int *slices) {
     if (slices) *slices = sp.slices();
     return PCL_OK;
 }
+
+int pcl_cellrp_transverse3(const pcl_cellrp *r, int *trans3) {
+    if (!trans3) return fail(PCL_EINVAL, "null argument");
+    pcl::CellrpSpec sp;
+    if (int rc = cellrp_live_spec(r, sp)) return rc;
+    *trans3 = sp.trans3;
+    return PCL_OK;
+}
+
+long long pcl_unsplit3_scratch_bytes(int meqn, int nx, int ny, int nz, int mbc) {
+    return pcl::unsplit3_scratch_bytes(meqn, nx, ny, nz, mbc);
+}
+long long pcl_unsplit3_scratch_live(void) { return g_scr3_live.load(); }
 
 int pcl_cellrp_form(const pcl_cellrp *r, int *form) {
     if (!form) return fail(PCL_EINVAL, "null argument");
@@ -1985,6 +2041,18 @@ int pcl_cellrp_attach(pcl_solver *s, pcl_cellrp *r) {
         }
     }
     s->cellrp = m;
+    // the general unsplit 3-D step passes its pieces through scratch planes: the one size rule, a refusal with the bytes
+    if (s->cfg.ndim == 3 && s->cfg.method[2] >= 0 && m.spec.trans3 && !s->scr3) {
+        const long long bytes = pcl::unsplit3_scratch_bytes(s->cfg.meqn, s->cfg.n[0], s->cfg.n[1], s->cfg.n[2], s->cfg.mbc);
+        if (hipMalloc((void **)&s->scr3, (size_t)bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            s->scr3 = nullptr;
+            return fail(PCL_EHIP, "pcl_cellrp_attach: the unsplit 3-D step of a user-written solver needs " + std::to_string(bytes) +
+                                      " bytes of scratch (14 * meqn doubles per cell with ghost cells) and the allocation failed");
+        }
+        s->scr3_bytes = bytes;
+        g_scr3_live += bytes;
+    }
     return PCL_OK;
 }
 
@@ -1995,13 +2063,14 @@ int pcl_create_cellrp(const pcl_config *cfg, pcl_cellrp *r, pcl_solver **out) {
     if (!cfg || !out) return fail(PCL_EINVAL, "null argument");
     *out = nullptr;
     if (cfg->rp != PCL_RP_CELL) return fail(PCL_EINVAL, "pcl_create_cellrp: cfg.rp must be PCL_RP_CELL");
+    int handle_trans3 = 0;
     int handle_ndim = cfg->ndim;        // (not a live handle: refused as such below, behind the configuration's own refusals)
     {
         CellfnCache &c = cellfn_cache();
         std::lock_guard<std::mutex> lock(c.mu);
-        if (r && c.rp_live.count(r)) handle_ndim = r->spec.ndim;
+        if (r && c.rp_live.count(r)) { handle_ndim = r->spec.ndim; handle_trans3 = r->spec.trans3; }
     }
-    if (int rc = create_check(cfg, true, handle_ndim)) return rc;
+    if (int rc = create_check(cfg, true, handle_ndim, handle_trans3)) return rc;
     {
         pcl::CellrpSpec sp;
         std::string err;

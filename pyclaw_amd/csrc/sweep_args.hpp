@@ -30,6 +30,14 @@ constexpr bool unsplit_user_slices_fit() {
 }
 static_assert(unsplit_user_slices_fit(), "unsplit_user_slices: the static LDS of unsplit_x/y_kernel must fit 160 KB for every meqn");
 
+// The general unsplit 3-D step (classic3.hpp: pieces3_kernel, gather3_kernel) passes the pieces of every slice through
+// scratch planes: per cell with ghost cells and per component qadd, fadd(i+1) - fadd(i), gadd(1:2, -1:1) and hadd(1:2, -1:1).
+// The one size rule, read by the host when it allocates (pclaw.hip) and by pcl_unsplit3_scratch_bytes.
+constexpr int UNSPLIT3_VALUES = 14;
+constexpr long long unsplit3_scratch_bytes(int meqn, int nx, int ny, int nz, int mbc) {
+    return 8LL * UNSPLIT3_VALUES * meqn * (nx + 2 * mbc) * (long long)(ny + 2 * mbc) * (nz + 2 * mbc);
+}
+
 struct RpParams {
     double v[8];
 };
@@ -167,6 +175,14 @@ struct Unsplit3Launch {
     int dir;              // 1..3
     int rp;
     hipStream_t stream;
+    // rp == PCL_RP_CELL (a user-written solver with rpt3 / rptt3 bodies, cellrp.hpp): the kernel table of the attached
+    // module by CellrpSlot, what it was compiled for (as SweepLaunch::user_fns / user), and the solver's scratch planes
+    // (unsplit3_scratch_bytes) with the extents, ghost cells included, they are laid out over
+    const hipFunction_t *user_fns = nullptr;
+    const struct CellrpSpec *user = nullptr;
+    double *scratch = nullptr;
+    int fwave = 0;
+    int n3[3] = {0, 0, 0};
 };
 
 struct RkLaunch {
@@ -185,6 +201,7 @@ struct CellrpSpec {
     int meqn = 0, mwaves = 0, ndim = 0, math = 0;   // ndim 3: the three sweep3_kernel passes and nothing else (pcl_cellrp_compile3)
     int naux = 0, aux[PCL_CELLRP_MAX_AUX] = {0};    // the aux components the body reads, in the body's order
     int trans = 0;                                  // 1: a transverse body, the code object holds the unsplit kernels too
+    int trans3 = 0;                                 // 3-D: 1 an rpt3 body, 2 rpt3 and rptt3; the code object holds pieces3_kernel too
     int form = 0;                                   // PCL_CELLRP_FORM_* bits
     int lim_type = 0, weno_order = 0, char_decomp = 0;      // a SharpClaw handle (lim_type 0: a classic one)
     int onek = 0;                                   // 1: the code object holds the one-kernel dimension-split 2-D step too
@@ -197,9 +214,10 @@ struct CellrpSpec {
 
 // The kernels a module of a user-written Riemann solver can hold, by what launches them.  A classic handle fills the sweeps of
 // its dimension (1-D: SWEEP_X alone; 3-D: the three sweep3_kernel passes), with a transverse body the unsplit phases, with
-// spec.onek the one-kernel step; a SharpClaw handle holds its kernels in the sweep slots (char_decomp = 1: SWEEP_X alone).
-// The order is that of cellrp_exprs.
-enum CellrpSlot { SLOT_SWEEP_X, SLOT_SWEEP_Y, SLOT_SWEEP_Z, SLOT_UNSPLIT_X, SLOT_UNSPLIT_Y, SLOT_ONEK, CELLRP_NSLOTS };
+// spec.onek the one-kernel step, with spec.trans3 the pieces kernels of the three directions of the unsplit 3-D step; a
+// SharpClaw handle holds its kernels in the sweep slots (char_decomp = 1: SWEEP_X alone).  The order is that of cellrp_exprs.
+enum CellrpSlot { SLOT_SWEEP_X, SLOT_SWEEP_Y, SLOT_SWEEP_Z, SLOT_UNSPLIT_X, SLOT_UNSPLIT_Y, SLOT_ONEK,
+                  SLOT_PIECES3_X, SLOT_PIECES3_Y, SLOT_PIECES3_Z, CELLRP_NSLOTS };
 
 struct SweepLaunch {
     SweepArgs a;

@@ -155,14 +155,16 @@ class CellRiemann(RiemannSolver):
     The dimension-split 3-D step takes a ``CellRiemann3D`` (below); ``CellRiemann(..., ndim=3)`` is a ``ValueError``.
 
     Not served: a transverse body that needs both cells and aux, a conservation fix in the unsplit step (the sphere
-    solver's ``qcor``), the unsplit 3-D step (``rpt3`` / ``rptt3`` bodies), f-waves in 3-D, more than one block
-    (decomposed runs); under SharpClaw ``char_decomp`` 2 / 3, ``tfluct_solver`` and a fused dq source.  The unsplit y
+    solver's ``qcor``), f-waves in 3-D, the unsplit 3-D step with a capacity function, ``mbc > 2`` in 3-D, more than one
+    block (decomposed runs); under SharpClaw ``char_decomp`` 2 / 3, ``tfluct_solver`` and a fused dq source.  The unsplit y
     phase always runs in its tile form (the marching y kernel stays with the built-in solvers)."""
 
     MAX_PARAMS = 8
     MAX_PLANES = 8
     ONE_KERNEL_MAX_MEQN = 5
     _NDIMS = (1, 2)
+    rpt3 = None             # the 3-D transverse bodies: a CellRiemann3D's alone
+    rptt3 = None
 
     def __init__(self, body, meqn, mwaves, ndim, params=(), preamble="", name="user", aux=(), transverse=None, fwave=False,
                  capa=False, sharpclaw=False, one_kernel=False):
@@ -256,13 +258,18 @@ class CellRiemann(RiemannSolver):
         sharp = None if sharp is None else tuple(int(v) for v in sharp)
         form = (1 if self.fwave else 0) | (2 if self.capa else 0)      # PCL_CELLRP_FORM_FWAVE, PCL_CELLRP_FORM_CAPA
         key = (self.meqn, self.mwaves, self.ndim, math, self.body, self.preamble, self.aux, self.transverse, form, sharp,
-               bool(self.one_kernel))
+               bool(self.one_kernel), self.rpt3, self.rptt3)
         if self._rp is not None and self._key == key:
             return self
         rp, size = ctypes.c_void_p(), ctypes.c_long(0)
         mode = {'exact': 0, 'fast': 1, 'strict': 2}[math]
         aux = (ctypes.c_int * len(self.aux))(*self.aux) if self.aux else None
-        if self.ndim == 3:
+        if self.ndim == 3 and self.rpt3 is not None:
+            _lib.check(_lib.lib().pcl_cellrp_compile3t(self.body.encode(), self.rpt3.encode(),
+                                                       None if self.rptt3 is None else self.rptt3.encode(),
+                                                       self.preamble.encode(), self.meqn, self.mwaves, mode,
+                                                       aux, len(self.aux), form, ctypes.byref(rp), ctypes.byref(size)))
+        elif self.ndim == 3:
             _lib.check(_lib.lib().pcl_cellrp_compile3(self.body.encode(), self.preamble.encode(), self.meqn, self.mwaves, mode,
                                                       aux, len(self.aux), form, ctypes.byref(rp), ctypes.byref(size)))
         elif sharp is not None:
@@ -334,31 +341,59 @@ class CellRiemann(RiemannSolver):
 
 
 class CellRiemann3D(CellRiemann):
-    """A user-written normal Riemann solver (Clawpack's rpn3, one interface at a time) for the dimension-split 3-D step:
-    ``solver.rp = CellRiemann3D(body, meqn, mwaves, params)`` on ``ClawSolver3D(dim_split=True)``.  ``setup()`` compiles the
-    x, y and z passes of the library's 3-D sweep kernel around the body, which is written as for a ``CellRiemann``: it sees
-    ``ql``, ``qr``, ``p[8]``, with ``aux=(...)`` also ``auxl`` / ``auxr``, and the compile-time constant ``ixy``, here 1, 2
-    or 3; it assigns ``wave``, ``s``, ``amdq``, ``apdq``, zero on entry, and for bitwise-equal ``ql`` and ``qr`` the waves
-    and fluctuations must be zero whatever aux holds.  ``capa=True`` compiles the passes with a capacity function
-    (``state.mcapa``).  ``params`` can be reassigned between steps without a compile.
+    """A user-written Riemann solver for ``ClawSolver3D``: ``solver.rp = CellRiemann3D(body, meqn, mwaves, params)``.  The body
+    is Clawpack's rpn3 for one interface, written as for a ``CellRiemann``: it sees ``ql``, ``qr``, ``p[8]``, with
+    ``aux=(...)`` also ``auxl`` / ``auxr``, and the compile-time constant ``ixy``, here 1, 2 or 3; it assigns ``wave``,
+    ``s``, ``amdq``, ``apdq``, zero on entry, and for bitwise-equal ``ql`` and ``qr`` the waves and fluctuations must be
+    zero whatever aux holds.  ``setup()`` compiles the x, y and z passes of the library's 3-D sweep kernel around it
+    (``dim_split=True``).  ``capa=True`` compiles the passes with a capacity function (``state.mcapa``).  ``params`` can be
+    reassigned between steps without a compile.
 
-    All three passes stage q, the listed aux components and the capacity function in one tile:
+    ``rpt3=text`` and ``rptt3=text`` are the insides of Clawpack's ``rpt3`` and ``rptt3`` for one interface and give the
+    solver the unsplit step, ``ClawSolver3D(dim_split=False)``: the library compiles the pieces kernel of its general
+    unsplit 3-D step around the three texts, for every ``order_trans`` of the reference (0, 10, 11, 20, 21, 22); with
+    ``rpt3`` alone for 0, 10 and 20, and ``setup()`` refuses the others with the reason.  Both texts see the compile-time
+    constants ``ixyz`` (alias ``ixy``: the direction of the normal solve, 1..3) and ``icoor`` (2: the split is in the y-like
+    direction ``ixyz+1``, 3: in the z-like direction ``ixyz+2``, cyclic), and ``p[8]``.  Without an aux list they see
+    ``ql[MEQN]``, ``qr[MEQN]``, the cells left and right of the interface (the same pair for A-dq, A+dq and the
+    correction wave: there is no ``imp``); with one they see ``imp`` (1, 2), ``q1[MEQN]``, the cell ``i-2+imp`` the
+    fluctuation belongs to, and ``auxb[3][3][NAUX]``, ``auxb[a][b][k]`` being the k-th listed component of that cell's
+    neighbour at y-like offset ``a-1`` and z-like offset ``b-1``.  ``rpt3`` reads ``asdq[MEQN]`` and assigns
+    ``bmasdq[MEQN]``, ``bpasdq[MEQN]``; ``rptt3`` also sees ``impt`` (1: its input came out of a split that went down
+    in the other transverse direction, 2: up), reads ``bsasdq[MEQN]`` and assigns ``cmbsasdq[MEQN]``,
+    ``cpbsasdq[MEQN]`` -- the new split lies inside the neighbouring row the input went to.  Outputs are zero on entry,
+    and for an all-zero input they must stay zero.  Diagnostics carry ``rpt3:<n>`` and ``rptt3:<n>``.  ``rptt3``
+    without ``rpt3`` and ``capa=True`` with ``rpt3`` are a ``ValueError``.  The unsplit step holds 14 * meqn doubles of
+    scratch per cell (ghost cells included) on the device, released by ``teardown()``.
+
+    The three dimension-split passes stage q, the listed aux components and the capacity function in one tile:
     ``meqn + len(aux) + capa <= MAX_PLANES`` (7; the library derives it from its tile shapes and refuses with its own
-    figure).
+    figure).  A solver with ``rpt3`` may exceed it and then serves ``dim_split=False`` alone.
 
-    Not served in 3-D, so there is no keyword for them: a transverse body (the unsplit step, ``dim_split=False``, needs
-    ``rpt3`` and ``rptt3`` solvers), f-waves and SharpClaw.  One block; ``mbc`` 2."""
+    Not served in 3-D, so there is no keyword for them: f-waves and SharpClaw.  Nor: the unsplit step with a capacity
+    function, a transverse body with both cells and aux, ``mbc`` other than 2, more than one block."""
 
     MAX_PLANES = 7
     _NDIMS = (3,)
 
-    def __init__(self, body, meqn, mwaves, params=(), preamble="", name="user", aux=(), capa=False):
+    def __init__(self, body, meqn, mwaves, params=(), preamble="", name="user", aux=(), capa=False, rpt3=None, rptt3=None):
         aux = tuple(aux)
+        if rptt3 is not None and rpt3 is None:
+            raise ValueError("CellRiemann3D: rptt3 without rpt3: the double-transverse solver splits what the transverse "
+                             "solver returned")
+        if rpt3 is not None and capa:
+            raise ValueError("CellRiemann3D: capa=True with rpt3: the unsplit 3-D step (step3) with a capacity function is "
+                             "not built for any solver")
         planes = int(meqn) + len(aux) + int(bool(capa))
         if planes > self.MAX_PLANES:
-            raise ValueError("CellRiemann3D: meqn + len(aux) + capa = %d, the tile of the 3-D sweeps holds at most %d planes "
-                             "(q components, listed aux components and the capacity function)" % (planes, self.MAX_PLANES))
+            if rpt3 is None:
+                raise ValueError("CellRiemann3D: meqn + len(aux) + capa = %d, the tile of the 3-D sweeps holds at most %d planes "
+                                 "(q components, listed aux components and the capacity function)" % (planes, self.MAX_PLANES))
+            self.MAX_PLANES = 16        # the unsplit step alone: its kernels have no tile
         CellRiemann.__init__(self, body, meqn, mwaves, 3, params=params, preamble=preamble, name=name, aux=aux, capa=capa)
+        self.rpt3 = None if rpt3 is None else str(rpt3)
+        self.rptt3 = None if rptt3 is None else str(rptt3)
+        self.has_transverse = self.rpt3 is not None
 
 
 def get(rp):

@@ -50,7 +50,15 @@ as a CellRiemann3D (problems.VC_ACOUSTICS_3D_RP, aux=(0, 1)).  Both run sweep3_k
 here is read once per process, so the two solvers live side by side in this process and are timed in alternating
 segments of `--steps` steps, `--reps` of each per state.
 
-  python tools/cellrp_bench.py [--aux] [--unsplit | --one-kernel] [--fwave | --capa | --sharpclaw | --ndim 3] [--n 4096] [--steps 20] [--warmup 3] [--reps 7] [--out FILE]
+--ndim 3 --unsplit measures the unsplit 3-D step (step3, order_trans 22) on the grid of `bench.py --ndim 3 --unsplit` (its
+build3d(unsplit=True), n = 256 unless --n says otherwise): "builtin", rp_vc_acoustics_3d in march3p_kernel, against "user",
+the same solver as the three texts VC_ACOUSTICS_3D_RP / _RPT / _RPTT of a CellRiemann3D in the general form (pieces3_kernel
++ gather3_kernel through scratch planes), alternating as above; then, unless --euler-n 0, the Euler equations through
+EULER_3D_RP / _RPT / _RPTT unsplit ("user") against the same bodies dimension-split ("builtin" in the output's terms:
+the yardstick) on an --euler-n cube.  The output also holds the scratch bytes and the cold compile times of the
+three-text handles.
+
+  python tools/cellrp_bench.py [--aux] [--unsplit | --one-kernel] [--fwave | --capa | --sharpclaw | --ndim 3 [--unsplit]] [--n 4096] [--steps 20] [--warmup 3] [--reps 7] [--out FILE]
 """
 import argparse
 import ctypes
@@ -163,27 +171,98 @@ def run3(args):
     L = _lib.lib()
     if L.pcl_device_count() < 1:
         raise SystemExit("cellrp_bench: no HIP device (nothing here can be measured without one)")
-    n = 512 if args.n == 4096 else args.n
+    n = (256 if args.unsplit else 512) if args.n == 4096 else args.n
     variants = VARIANTS_UNSPLIT
-    claws, compile_s = {}, None
-    for v in variants:
-        claw = bench.build3d(n, args.math)
-        if v == "user":
-            claw.solver.rp = pyclaw.CellRiemann3D(problems.VC_ACOUSTICS_3D_RP, 4, 2, aux=(0, 1), name="vc_acoustics_3d_user")
-            t0 = time.perf_counter()
-            claw.solver.rp.compile(args.math)
-            compile_s = time.perf_counter() - t0
-        claw.solver.setup(claw.solution)
-        claw.solver.dt_variable = False
-        claw.solver.dt = claw.solver.dt_initial         # bench.py's: a Courant number of 0.4 in the faster material
-        claws[v] = claw
+
+    def cold_compile(rp):
+        """the run-time compile of rp's texts with nothing cached: a comment that no earlier run can have made"""
+        twin = pyclaw.CellRiemann3D(rp.body + "// cold compile %r\n" % time.time(), rp.meqn, rp.mwaves, aux=rp.aux, rpt3=rp.rpt3,
+                                    rptt3=rp.rptt3)
+        t0 = time.perf_counter()
+        twin.compile(args.math)
+        return time.perf_counter() - t0
+
+    def vc_pair():
+        claws, compile_s = {}, None
+        for v in variants:
+            claw = bench.build3d(n, args.math, args.unsplit)
+            if v == "user":
+                trans = dict(rpt3=problems.VC_ACOUSTICS_3D_RPT, rptt3=problems.VC_ACOUSTICS_3D_RPTT) if args.unsplit else {}
+                claw.solver.rp = pyclaw.CellRiemann3D(problems.VC_ACOUSTICS_3D_RP, 4, 2, aux=(0, 1), name="vc_acoustics_3d_user", **trans)
+                t0 = time.perf_counter()
+                claw.solver.rp.compile(args.math)
+                compile_s = time.perf_counter() - t0
+            claw.solver.setup(claw.solution)
+            claw.solver.dt_variable = False
+            claw.solver.dt = claw.solver.dt_initial         # bench.py's: a Courant number of 0.4 in the faster material
+            claws[v] = claw
+        return claws, compile_s
+
+    def euler_pair(m):
+        """the Euler bodies dimension-split ("builtin": the yardstick) and unsplit ("user") on an m^3 box of smooth data"""
+        claws, compile_s = {}, None
+        for v in variants:
+            claw = problems.euler3D(pyclaw, n=m, across=(m, m), run=False, math=args.math, dim_split=v == "builtin")
+            st = claw.solution.state
+            X, Y, Z = st.grid.c_center
+            rho = 1.0 + 0.2 * np.sin(2 * np.pi * X) * np.cos(2 * np.pi * Y) * np.cos(2 * np.pi * Z)
+            vel = (0.3, -0.2, 0.25)
+            st.q[0] = rho
+            for k in range(3):
+                st.q[1 + k] = rho * vel[k]
+            st.q[4] = 1.0 / 0.4 + 0.5 * rho * sum(c * c for c in vel)
+            if v == "user":
+                t0 = time.perf_counter()
+                claw.solver.rp.compile(args.math)
+                compile_s = time.perf_counter() - t0
+            claw.solver.setup(claw.solution)
+            claw.solver.dt_variable = False
+            claw.solver.dt = 0.4 * (1.0 / m) / 2.0          # sound speed about 1.2, |velocity| below 0.5
+            claws[v] = claw
+        return claws, compile_s
+    if args.unsplit:
+        res = {"tool": "cellrp_bench --ndim 3 --unsplit", "math": args.math, "steps": args.steps, "warmup": args.warmup, "reps": args.reps,
+               "what": "ms per unsplit 3-D step (order_trans 22), segments of the two variants alternating in one process"}
+        claws, compile_s = vc_pair()
+        cold_vc = cold_compile(claws["user"].solver.rp)
+        res["vc_acoustics"] = dict(alternate3(args, claws, variants), n=n, grid=[n, n, n], compile_s=compile_s,
+                                   builtin="rp_vc_acoustics_3d, march3p_kernel", user="VC_ACOUSTICS_3D_RP / _RPT / _RPTT, pieces3_kernel + gather3_kernel",
+                                   scratch_bytes=int(L.pcl_unsplit3_scratch_bytes(4, n, n, n, 2)), cold_compile_s=cold_vc)
+        if args.euler_n > 0:
+            m = args.euler_n
+            claws, compile_s = euler_pair(m)
+            cold_eu = cold_compile(claws["user"].solver.rp)
+            res["euler"] = dict(alternate3(args, claws, variants, same=False), n=m, grid=[m, m, m], compile_s=compile_s,
+                                builtin="EULER_3D_RP dimension-split (sweep3_kernel x 3)", user="EULER_3D_RP / _RPT / _RPTT unsplit",
+                                scratch_bytes=int(L.pcl_unsplit3_scratch_bytes(5, m, m, m, 2)), cold_compile_s=cold_eu)
+        return emit(args, res)
+    claws, compile_s = vc_pair()
+    res = {"tool": "cellrp_bench --ndim 3", "n": n, "grid": [n, n, n], "math": args.math, "steps": args.steps, "warmup": args.warmup,
+           "reps": args.reps, "what": "ms per dimension-split 3-D step (x, y, z sweeps), segments of the two solvers alternating in one process",
+           "compile_s": compile_s}
+    res.update(alternate3(args, claws, variants))
+    emit(args, res)
+
+
+def emit(args, res):
+    line = json.dumps(res)
+    print(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+
+
+def alternate3(args, claws, variants, same=True):
+    """warm both set-up solvers up on each state and time them in alternating segments; tears them down.  same: the two
+    compute the same thing (then the output says whether they did)"""
+    from pyclaw_amd import _lib
+    L = _lib.lib()
     q_pulse = claws["builtin"].solution.state.q.copy('F')
     rng = np.random.default_rng(7)
     noise = 0.01 * rng.standard_normal(q_pulse.shape[1:])     # one plane's worth, on every component
     ms = ctypes.c_float()
-    res = {"tool": "cellrp_bench --ndim 3", "n": n, "grid": [n, n, n], "math": args.math, "steps": args.steps, "warmup": args.warmup,
-           "reps": args.reps, "what": "ms per dimension-split 3-D step (x, y, z sweeps), segments of the two solvers alternating in one process",
-           "compile_s": compile_s, "states": {}}
+    res = {"states": {}}
 
     def spread(vals):
         return {"median": float(np.median(vals)), "min": min(vals), "max": max(vals), "all": vals}
@@ -214,17 +293,13 @@ def run3(args):
             sums.add(float(np.abs(claws[v].solution.state.q).sum()))       # the two compute the same thing
             cfls.add(claws[v].solver.cfl.get_cached_max())
         a, b = spread(seg["builtin"]), spread(seg["user"])
-        res["states"][name] = {"builtin_ms": a, "user_ms": b, "same_result_in_every_run": len(sums) == 1 and len(cfls) == 1,
+        res["states"][name] = {"builtin_ms": a, "user_ms": b,
+                               "same_result_in_every_run": (len(sums) == 1 and len(cfls) == 1) if same else None,
                                "user_over_builtin": b["median"] / a["median"],
                                "user_and_builtin_spreads_overlap": not (b["min"] > a["max"] or a["min"] > b["max"])}
     for v in variants:
         claws[v].solver.teardown()
-    line = json.dumps(res)
-    print(line)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(line + "\n")
+    return res
 
 
 def main():
@@ -244,10 +319,12 @@ def main():
                     help="3: the dimension-split 3-D step on bench.py's 3-D grid, rp_vc_acoustics_3d against CellRiemann3D")
     ap.add_argument("--one-kernel", dest="one_kernel", action="store_true",
                     help="CellRiemann(one_kernel=True) against the built-in one-kernel step and against the user solver's two passes")
+    ap.add_argument("--euler-n", dest="euler_n", type=int, default=256,
+                    help="--ndim 3 --unsplit: the cube of the Euler measurement (0: leave it out)")
     ap.add_argument("--child", default=None, choices=VARIANTS + VARIANTS_UNSPLIT + VARIANTS_ONEK[1:2])
     args = ap.parse_args()
     if args.ndim == 3:
-        if args.aux or args.unsplit or args.fwave or args.capa or args.sharpclaw or args.one_kernel:
+        if args.aux or args.fwave or args.capa or args.sharpclaw or args.one_kernel:
             raise SystemExit("cellrp_bench: --ndim 3 is a measurement of its own")
         return run3(args)
     if (args.fwave or args.capa) and (args.aux or args.unsplit or (args.fwave and args.capa)):
