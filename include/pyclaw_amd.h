@@ -392,6 +392,33 @@ int pcl_cellfn_apply(pcl_solver *s, pcl_cellfn *f, double t, double dt, const do
  * dimension lower and upper, only on blocks that own that boundary.  The argument checks are host-only and come first;
  * otherwise the bookkeeping of pcl_bc_const. */
 int pcl_cellbc_apply(pcl_solver *s, pcl_cellfn *f, int idim, int side, double t, const double *params, int nparams);
+/* A functional: per-cell integrands reduced over the interior cells of the block (pyclaw.CellFunctional).  The body sees
+ * what a cell function's body sees -- q[MEQN] and aux[MAUX], both const, c.t, c.i, c.x, c.d, p[16], with reach > 0 also
+ * qn / auxn, which read the register itself; c.dt is 0 -- and assigns f[NOUT], which is zero on entry.  ops[nout],
+ * 1 <= nout <= 8, name the operation of each output: the sum of f, the sum of |f|, or the largest / smallest f with
+ * fmax / fmin semantics (a NaN integrand is passed over; the sums propagate it).  Host-only, no device needed; the
+ * per-process cache and the counters of pcl_cellfn_stats; nout and ops are -D constants of the compile and part of
+ * the key.  The handle is released with pcl_cellfn_release.  pcl_cellfn_compile / _compile_reach do not make such a
+ * handle, and pcl_cellfn_apply / pcl_cellbc_apply refuse one. */
+#define PCL_REDUCE_SUM 0
+#define PCL_REDUCE_ABS_SUM 1
+#define PCL_REDUCE_MAX 2
+#define PCL_REDUCE_MIN 3
+int pcl_cellfn_compile_reduce(const char *body, const char *preamble, int meqn, int maux, int ndim, int math,
+                              int reach, int nout, const int *ops, pcl_cellfn **out, long *code_size);
+/* Evaluates a functional on the interior cells of the SELECTED register, on the solver's stream, writes the nout values
+ * to out (host memory) and returns when they are there.  Two launches: the compiled wrapper leaves one partial per
+ * workgroup and output in a buffer of the handle (allocated at the first call for the block's size, freed by
+ * pcl_destroy), a fixed kernel of the library reduces those.  Both combine in an order fixed by the block's shape --
+ * cross-lane butterfly, wavefronts in order, partials in order, no atomics -- so the result is a function of the state,
+ * the text and the shape alone and has the same bits on every call.  Ghost cells are never part of the reduction; with
+ * reach > 0 they are read, and filling them is the caller's business.
+ * A READ-ONLY call in the sense of the quiet tiles and of pcl_step_ahead below: it stores nothing into the state, sees
+ * the state the caller knows (behind a step enqueued ahead: the accepted one), and that step is still adopted by the
+ * next pcl_bc_step.  Like pcl_get_cells it ends with a synchronisation of the stream, so it waits for a step enqueued
+ * ahead.  The argument checks are host-only and come first: PCL_EINVAL for a handle of another kind, for one compiled
+ * for other shape constants (pcl_cellfn_check), for reach > cfg.mbc and for nparams > 16. */
+int pcl_cellfn_reduce(pcl_solver *s, pcl_cellfn *f, double t, const double *params, int nparams, double *out);
 
 /* ---- user-written Riemann solvers (cfg.rp = PCL_RP_CELL) ---------------------------------------------------------
  * The normal Riemann solver of one interface (Clawpack's rp1 / rpn2) as the text of a C++ function body.  The library
@@ -689,7 +716,7 @@ int pcl_step_count(pcl_solver *s, long *steps);
  * the grid -- since what is saved is one host turn-round per step and what a wrong guess costs is a whole launch.  The
  * state is not advanced and nothing is counted.  The next pcl_bc_step ADOPTS the pending step -- the result becomes the state, the counters advance, the call
  * waits for the Courant number -- if its dt has the same 64 bits as dt', its bc and constant states are bytewise the
- * same, and only read-only calls (pcl_get_q, pcl_get_cells, pcl_get_strip, pcl_sync, the timers, pcl_step_count,
+ * same, and only read-only calls (pcl_get_q, pcl_get_cells, pcl_get_strip, pcl_cellfn_reduce, pcl_sync, the timers, pcl_step_count,
  * pcl_step_form_stats; they see the state the caller knows) came in between.  Otherwise the pending step is DROPPED: a
  * finished kernel whose output nobody uses; the call proceeds as if nothing had been enqueued, and its one-kernel launch
  * computes every tile.  A drop with nothing in between means the caller follows another rule: the next step is not run

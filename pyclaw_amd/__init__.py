@@ -15,9 +15,9 @@ from .riemann import CellRiemann, CellRiemann3D
 from .grid import Dimension, Grid
 from .sharpclaw import CellDqSource, SharpClawSolver1D, SharpClawSolver2D, DeviceDqSource, EulerRadialDqSource
 from .solution import Solution
-from .solver import BC, CellBC, CellFunction, CellStartStep, ConstantStateBC, DeviceBC, SphereMirrorBC
+from .solver import BC, CellBC, CellFunction, CellFunctional, CellStartStep, ConstantStateBC, DeviceBC, SphereMirrorBC
 from .state import State
 
 __all__ = ['limiters', 'riemann', 'CFL', 'ClawSolver1D', 'ClawSolver2D', 'ClawSolver3D', 'DeviceSource', 'EulerRadialSource', 'SphereCoriolisSource', 'SphereMirrorBC',
            'Controller', 'SharpClawSolver1D', 'SharpClawSolver2D', 'DeviceDqSource', 'EulerRadialDqSource', 'Dimension', 'Grid', 'Solution', 'BC', 'ConstantStateBC', 'DeviceBC', 'State',
-           'CellFunction', 'CellSource', 'CellDqSource', 'CellStartStep', 'CellBC', 'CellRiemann', 'CellRiemann3D']
+           'CellFunction', 'CellSource', 'CellDqSource', 'CellStartStep', 'CellBC', 'CellFunctional', 'CellRiemann', 'CellRiemann3D']

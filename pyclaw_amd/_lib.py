@@ -102,6 +102,9 @@ PROTOTYPES = {
     "pcl_cellfn_geometry": (C.c_int, [C.c_void_p, dp, ip]),
     "pcl_cellfn_apply": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_double, dp, C.c_int]),
     "pcl_cellbc_apply": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, dp, C.c_int]),
+    "pcl_cellfn_compile_reduce": (C.c_int, [C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                            ip, C.POINTER(C.c_void_p), C.POINTER(C.c_long)]),
+    "pcl_cellfn_reduce": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, dp, C.c_int, dp]),
     "pcl_cellrp_compile": (C.c_int, [C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p),
                                      C.POINTER(C.c_long)]),
     "pcl_cellrp_compile_aux": (C.c_int, [C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, ip, C.c_int,

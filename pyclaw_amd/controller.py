@@ -105,9 +105,15 @@ class Controller(object):
         import os
         from . import parallel
         state = self.solution.state
-        self.compute_F(state)
-        sums = [float(np.sum(np.abs(state.F[i, ...]))) for i in range(state.F.shape[0])]
-        sums = parallel.allreduce_sum_host(sums)
+        from .solver import CellFunctional
+        if isinstance(self.compute_F, CellFunctional):
+            # the device path: reduced on the resident arrays, combined over the ranks; its own ``reduce`` decides what
+            # the values are, and state.F is not touched
+            sums = [float(v) for v in self.compute_F.evaluate(self.solver, state)]
+        else:
+            self.compute_F(state)
+            sums = [float(np.sum(np.abs(state.F[i, ...]))) for i in range(state.F.shape[0])]
+            sums = parallel.allreduce_sum_host(sums)
         if parallel.rank() == 0:
             os.makedirs(self.outdir, exist_ok=True)
             with open(os.path.join(self.outdir, self.F_file_name + '.txt'), mode) as f:

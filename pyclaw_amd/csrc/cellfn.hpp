@@ -21,6 +21,10 @@
 // A fourth kind, the boundary condition (PCL_CELLFN_BC; pyclaw.CellBC), has a wrapper of its own further
 // down: one lane = one ghost cell of one side, the body's only neighbour reads go inward along the lane's own normal line.
 //
+// A fifth wrapper, the functional (pcl_cellfn_compile_reduce; pyclaw.CellFunctional), stores nothing into
+// the state: every lane evaluates the body into f[NOUT] and the workgroup reduces those to NOUT partials (kCellfnReduce*
+// below).  Its kind value is internal: pcl_cellfn_compile knows the kinds 1..4 alone.
+//
 // libhiprtc is dlopen()ed on first use, like librccl in halo.hpp: a library without it loads and runs every other path.
 #pragma once
 #include <dlfcn.h>
@@ -39,11 +43,14 @@
 #endif
 
 #define PCL_CELLFN_MAX_PARAMS 16
+#define PCL_CELLFN_MAX_NOUT 8
+// the kind a handle of pcl_cellfn_compile_reduce carries; not a kind of pcl_cellfn_compile (the public ones are 1..4)
+#define PCL_CELLFN_KIND_REDUCE 5
 
 // by-value argument of the wrapper kernel; the text below declares the same struct for the device compile
 struct pcl_cell_args {
     double *q;          // the selected register
-    double *dq;         // dq_src: the increment register
+    double *dq;         // dq_src: the increment register; functional: the workgroups' partials, [NOUT][workgroups]
     double *aux;
     long pitch, plane, slab;        // doubles between rows, components and (3-D) k-planes
     int n[3];           // interior cells of this block
@@ -102,7 +109,7 @@ struct pcl_cell_args {
 #endif
 };
 #define PCL_MAUXN (MAUX > 0 ? MAUX : 1)
-#if KIND == 2
+#if KIND == 2 || KIND == 5
 #define PCL_Q_QUAL const
 #else
 #define PCL_Q_QUAL
@@ -321,11 +328,107 @@ extern "C" __global__ void __launch_bounds__(256) pcl_cellbc(const pcl_cellbc_ar
 }
 )PCLSRC";
 
+// ---- the functional: per-cell integrands reduced over the interior ------------------------------------------------------
+// The head is the cell functions' (q and aux const, qn / auxn read the register itself).  One lane = one interior cell as
+// above, but no lane leaves early: a lane beyond the row contributes the identity of each output's operation (+0, -inf,
+// +inf).  The order of the combination is fixed by the block's shape alone -- the same bits on every call:
+//   1. across the wavefront, a butterfly of 6 cross-lane exchanges at distances 1, 2, 4, ... 32 (a + b and b + a have the
+//      same bits, so every lane of a pair holds the same value after each exchange);
+//   2. across the workgroup's four wavefronts through LDS, by thread 0 in wavefront order 0, 1, 2, 3;
+//   3. thread 0 stores the NOUT partials of workgroup w at a.dq[m * workgroups + w] with plain vector stores; the library's
+//      reduce_partials_kernel (kernels.hip) combines those, again in a fixed order.
+// No atomics and no counters: nothing depends on which workgroup finishes first.  PCL_OPS is the comma-separated list of
+// the NOUT operations (PCL_REDUCE_*): 0 sum, 1 sum of |f|, 2 max, 3 min; max / min are fmax / fmin, which pass over a NaN.
+static const char *const kCellfnReduceOpen = R"PCLSRC(
+__device__ __forceinline__ void pcl_cell_body(const double (&q)[MEQN], double (&f)[NOUT],
+                                              const double (&aux)[PCL_MAUXN], const pcl_cell &c,
+                                              const double (&p)[16] PCL_NEAR_PARAM) {
+#if REACH > 0
+    const auto qn = [&pcl_nb](int m, int di, int dj = 0, int dk = 0) { return pcl_nb.qn(m, di, dj, dk); };
+    (void)qn;
+#if MAUX > 0
+    const auto auxn = [&pcl_nb](int m, int di, int dj = 0, int dk = 0) { return pcl_nb.auxn(m, di, dj, dk); };
+    (void)auxn;
+#endif
+#endif
+)PCLSRC";
+
+static const char *const kCellfnReduceTail = R"PCLSRC(
+}
+#line 1 "pcl_cellfn_wrapper"
+__device__ __forceinline__ double pcl_red_identity(int op) {
+    return op == 2 ? -__builtin_huge_val() : op == 3 ? __builtin_huge_val() : 0.0;
+}
+__device__ __forceinline__ double pcl_red_combine(int op, double a, double b) {
+    return op == 2 ? fmax(a, b) : op == 3 ? fmin(a, b) : a + b;
+}
+extern "C" __global__ void __launch_bounds__(256) pcl_cellfn_red(const pcl_cell_args a) {
+    constexpr int ops[NOUT] = {PCL_OPS};
+    __shared__ double part[4][NOUT];
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    const int j = NDIM > 1 ? (int)blockIdx.y : 0, k = NDIM > 2 ? (int)blockIdx.z : 0;
+    double f[NOUT];
+    for (int m = 0; m < NOUT; m++) f[m] = pcl_red_identity(ops[m]);
+    if (i < a.n[0]) {
+        long g = i + a.mbc;
+        if (NDIM > 1) g += (long)(j + a.mbc) * a.pitch;
+        if (NDIM > 2) g += (long)(k + a.mbc) * a.slab;
+        pcl_cell c;
+        c.t = a.t;
+        c.dt = a.dt;
+        const int loc[3] = {i, j, k};
+        for (int n = 0; n < NDIM; n++) {
+            c.i[n] = loc[n] + a.nstart[n];
+            c.d[n] = a.d[n];
+            c.x[n] = a.lower[n] + (c.i[n] + 0.5) * a.d[n];
+        }
+        double q[MEQN], aux[PCL_MAUXN], v[NOUT];
+        for (int m = 0; m < MEQN; m++) q[m] = a.q[m * a.plane + g];
+        for (int m = 0; m < PCL_MAUXN; m++) aux[m] = MAUX > 0 ? a.aux[m * a.plane + g] : 0.0;
+        for (int m = 0; m < NOUT; m++) v[m] = 0.0;
+#if REACH > 0
+        pcl_near nb;
+        nb.q = a.snap + g;          // the register itself: q is const, the launch stores nothing into it
+        nb.aux = MAUX > 0 ? a.aux + g : nullptr;
+        nb.pitch = a.pitch; nb.plane = a.plane; nb.slab = a.slab;
+        pcl_cell_body(q, v, aux, c, a.p, nb);
+#else
+        pcl_cell_body(q, v, aux, c, a.p);
+#endif
+        for (int m = 0; m < NOUT; m++) f[m] = ops[m] == 1 ? fabs(v[m]) : v[m];
+    }
+    for (int m = 0; m < NOUT; m++) {
+        double v = f[m];
+        for (int w = 1; w < 64; w <<= 1) v = pcl_red_combine(ops[m], v, __shfl_xor(v, w, 64));
+        f[m] = v;
+    }
+    const int wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0)
+        for (int m = 0; m < NOUT; m++) part[wave][m] = f[m];
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const long nwg = (long)gridDim.x * gridDim.y * gridDim.z;
+        const long wg = blockIdx.x + (long)gridDim.x * (blockIdx.y + (long)gridDim.y * blockIdx.z);
+        for (int m = 0; m < NOUT; m++) {
+            double v = part[0][m];
+            for (int w = 1; w < 4; w++) v = pcl_red_combine(ops[m], v, part[w][m]);
+            a.dq[m * nwg + wg] = v;
+        }
+    }
+}
+)PCLSRC";
+
 static inline const char *cellfn_kind_name(int kind) {
     return kind == 1 ? "step_src" : kind == 2 ? "dq_src" : kind == 3 ? "start_step" : kind == 4 ? "bc" : nullptr;
 }
+// the same for messages about any live handle: a functional's kind is none of pcl_cellfn_compile's
+static inline const char *cellfn_kind_label(int kind) {
+    return kind == PCL_CELLFN_KIND_REDUCE ? "functional" : cellfn_kind_name(kind) ? cellfn_kind_name(kind) : "unknown";
+}
 // the __global__ function of a kind's wrapper
-static inline const char *cellfn_entry_name(int kind) { return kind == 4 ? "pcl_cellbc" : "pcl_cellfn"; }
+static inline const char *cellfn_entry_name(int kind) {
+    return kind == 4 ? "pcl_cellbc" : kind == PCL_CELLFN_KIND_REDUCE ? "pcl_cellfn_red" : "pcl_cellfn";
+}
 
 // ---- libhiprtc, loaded on first use ---------------------------------------------------------------------------
 struct HiprtcApi {
@@ -389,6 +492,7 @@ static inline int hiprtc_load(std::string &err) {
 struct pcl_cellfn {
     long id = 0;                // never reused: the solvers' loaded modules are keyed by it
     int kind = 0, meqn = 0, maux = 0, ndim = 0, math = 0, writes_aux = 0, reach = 0;
+    int nout = 0, ops[PCL_CELLFN_MAX_NOUT] = {0, 0, 0, 0, 0, 0, 0, 0};      // a functional's outputs (PCL_REDUCE_*)
     int refs = 0;
     std::string key;
     std::vector<char> code;     // the code object
@@ -489,26 +593,34 @@ static inline int hiprtc_compile(const HiprtcJob &job, std::vector<char> &code, 
 }
 
 // hiprtc compile of head + preamble + body + tail; math: 0 exact, 1 fast, 2 strict.  0 = ok, else err holds the log
+// nout, ops: a functional's outputs (kind PCL_CELLFN_KIND_REDUCE), -D constants like the rest
 static inline int cellfn_build(int kind, const char *body, const char *preamble, int meqn, int maux, int ndim, int math,
-                               int writes_aux, int reach, std::vector<char> &code, std::string &err) {
-    const char *kname = cellfn_kind_name(kind);
-    const bool bc = kind == 4;
+                               int writes_aux, int reach, std::vector<char> &code, std::string &err, int nout = 0,
+                               const int *ops = nullptr) {
+    const char *kname = cellfn_kind_label(kind);
+    const bool bc = kind == 4, red = kind == PCL_CELLFN_KIND_REDUCE;
     HiprtcJob job;
     job.src = bc ? kCellbcHead : kCellfnHead;
     job.src += "#line 1 \"preamble\"\n";
     job.src += preamble;
     job.src += "\n#line 1 \"pcl_cellfn_wrapper\"\n";
-    job.src += bc ? kCellbcOpen : kCellfnOpen;
+    job.src += bc ? kCellbcOpen : red ? kCellfnReduceOpen : kCellfnOpen;
     job.src += std::string("#line 1 \"") + kname + "\"\n";
     job.src += body;
     job.src += "\n";
-    job.src += bc ? kCellbcTail : kCellfnTail;
+    job.src += bc ? kCellbcTail : red ? kCellfnReduceTail : kCellfnTail;
     job.name = "pcl_cellfn.hip";
     // exact / strict: what pclaw.hip itself is built with (no contraction; / and sqrt are IEEE either way)
     job.opts = {"--offload-arch=" PCL_ARCH, "-O3", "-std=c++17", math == 1 ? "-ffp-contract=fast" : "-ffp-contract=off",
                 "-DMEQN=" + std::to_string(meqn), "-DMAUX=" + std::to_string(maux), "-DNDIM=" + std::to_string(ndim),
                 "-DKIND=" + std::to_string(kind), "-DWRITES_AUX=" + std::to_string(writes_aux ? 1 : 0)};
     if (reach > 0) job.opts.push_back("-DREACH=" + std::to_string(reach));      // reach = 0 passes no -DREACH: the text defaults it
+    if (red) {
+        std::string list;
+        for (int m = 0; m < nout; m++) list += (m ? "," : "") + std::to_string(ops[m]);
+        job.opts.push_back("-DNOUT=" + std::to_string(nout));
+        job.opts.push_back("-DPCL_OPS=" + list);
+    }
     job.what = std::string("cell function (") + kname + ")";
     static int seq = 0;
     job.dump = kname;

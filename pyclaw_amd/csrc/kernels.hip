@@ -771,6 +771,57 @@ int launch_rk(const RkLaunch &r, hipStream_t stream, std::string &err) {
 }
 
 #if !PCL_FAST
+// The second pass of a functional (sweep_args.hpp: ReduceFinal; the first is the run-time wrapper of cellfn.hpp).
+// Workgroup m reduces output m.  The order is a function of npart alone: thread t folds partials t, t + 256, t + 512, ...
+// in eight interleaved chains, each in ascending order, and adds the chains up in order; the wavefront combines its 64 values in a butterfly at distances 1, 2, ... 32, thread 0 combines the four
+// wavefronts in order through LDS and stores out[m].  No atomics: the same partials give the same bits on every launch.
+struct ReduceOps { int op[8]; };
+__device__ __forceinline__ double reduce_combine(int op, double a, double b) {
+    return op == PCL_REDUCE_MAX ? fmax(a, b) : op == PCL_REDUCE_MIN ? fmin(a, b) : a + b;
+}
+__global__ void __launch_bounds__(REDUCE_FINAL_THREADS) reduce_partials_kernel(const double *__restrict__ part,
+                                                                               double *__restrict__ out, long npart,
+                                                                               ReduceOps ops) {
+    static_assert(REDUCE_FINAL_THREADS == 256, "four wavefronts of 64");
+    __shared__ double wsum[REDUCE_FINAL_THREADS / 64];
+    const int m = blockIdx.x, op = ops.op[m];
+    const double *p = part + (long)m * npart;
+    const double identity = op == PCL_REDUCE_MAX ? -__builtin_huge_val() : op == PCL_REDUCE_MIN ? __builtin_huge_val() : 0.0;
+    // eight chains per thread, so that eight loads are in flight (one chain waits a memory latency per partial): chain i
+    // folds partials t + 256 (8 j + i), j = 0, 1, ..., and the chains are combined in the order 0 .. 7
+    constexpr int CHAINS = 8;
+    double acc[CHAINS];
+    for (int i = 0; i < CHAINS; i++) acc[i] = identity;
+    for (long base = threadIdx.x; base < npart; base += (long)REDUCE_FINAL_THREADS * CHAINS) {
+#pragma unroll
+        for (int i = 0; i < CHAINS; i++) {
+            const long k = base + (long)REDUCE_FINAL_THREADS * i;
+            if (k < npart) acc[i] = reduce_combine(op, acc[i], p[k]);
+        }
+    }
+    double v = acc[0];
+    for (int i = 1; i < CHAINS; i++) v = reduce_combine(op, v, acc[i]);
+    for (int w = 1; w < 64; w <<= 1) v = reduce_combine(op, v, __shfl_xor(v, w, 64));
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = v;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double r = wsum[0];
+        for (int w = 1; w < REDUCE_FINAL_THREADS / 64; w++) r = reduce_combine(op, r, wsum[w]);
+        out[m] = r;
+    }
+}
+int launch_reduce_partials(const ReduceFinal &r, std::string &err) {
+    if (!r.part || !r.out || r.npart <= 0 || r.nout < 1 || r.nout > 8) {
+        err = "launch_reduce_partials: bad arguments";
+        return PCL_EINVAL;
+    }
+    ReduceOps ops;
+    for (int m = 0; m < 8; m++) ops.op[m] = r.op[m];
+    hipLaunchKernelGGL(reduce_partials_kernel, dim3(r.nout), dim3(REDUCE_FINAL_THREADS), 0, r.stream, r.part, r.out, r.npart, ops);
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? PCL_OK : hip_fail(err, "reduce_partials launch", e);
+}
+
 __global__ void shift_test_kernel(const double *in, double *l, double *r) {
     const int t = threadIdx.x;
     const double x = in[t];

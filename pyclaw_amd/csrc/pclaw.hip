@@ -98,6 +98,9 @@ struct pcl_solver {
     double cf_lower[3] = {0.0, 0.0, 0.0};
     int cf_nstart[3] = {0, 0, 0};
     double *cf_snap = nullptr;     // reach > 0: the copy of the selected register the launch reads, allocated at the first one
+    // functionals (pcl_cellfn_reduce): PCL_CELLFN_MAX_NOUT partials per workgroup of the wrapper's grid, then the results;
+    // allocated at the first call (the grid follows from cfg.n), freed by pcl_destroy
+    double *cf_part = nullptr;
     // cfg.rp == PCL_RP_CELL: the user-written Riemann solver's module (cellrp.hpp, pcl_cellrp_attach)
     pcl::CellrpModule cellrp;
     // the scratch planes of the general unsplit 3-D step (classic3.hpp; sweep_args.hpp: unsplit3_scratch_bytes): allocated when
@@ -736,7 +739,7 @@ int check_device() {
 extern "C" {
 
 const char *pcl_last_error(void) { return g_err.c_str(); }
-int pcl_version(void) { return 113; }
+int pcl_version(void) { return 114; }
 int pcl_device_count(void) {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess) return 0;
@@ -949,6 +952,7 @@ void pcl_destroy(pcl_solver *s) {
     hipFree(s->cfl_dev);
     if (s->glog_ij) hipFree(s->glog_ij);
     if (s->glog_buf) hipFree(s->glog_buf);
+    if (s->cf_part) hipFree(s->cf_part);
     s->qt.destroy();
     if (s->cfl_host) hipHostFree(s->cfl_host);
     if (s->ev0) hipEventDestroy(s->ev0);
@@ -1766,6 +1770,60 @@ int pcl_cellfn_compile_reach(int kind, const char *body, const char *preamble, i
     return PCL_OK;
 }
 
+// A functional (cellfn.hpp: kCellfnReduce*).  The handle's kind is PCL_CELLFN_KIND_REDUCE, which the two entries above refuse
+// like any other number: this is the only way to one.
+int pcl_cellfn_compile_reduce(const char *body, const char *preamble, int meqn, int maux, int ndim, int math, int reach,
+                              int nout, const int *ops, pcl_cellfn **out, long *code_size) {
+    if (!body || !out || !ops) return fail(PCL_EINVAL, "null argument");
+    *out = nullptr;
+    if (!preamble) preamble = "";
+    if (meqn < 1 || meqn > 64 || maux < 0 || maux > 64) return fail(PCL_EINVAL, "pcl_cellfn_compile_reduce: 1 <= meqn <= 64 and 0 <= maux <= 64");
+    if (ndim < 1 || ndim > 3) return fail(PCL_EINVAL, "pcl_cellfn_compile_reduce: ndim must be 1, 2 or 3");
+    if (math != PCL_MATH_EXACT && math != PCL_MATH_FAST && math != PCL_MATH_STRICT) return fail(PCL_EINVAL, "unknown math mode");
+    if (reach < 0 || reach > PCL_CELLFN_MAX_REACH)
+        return fail(PCL_EINVAL, "pcl_cellfn_compile_reduce: reach must be 0.." + std::to_string(PCL_CELLFN_MAX_REACH) +
+                                    " (the largest mbc the library takes), got " + std::to_string(reach));
+    if (nout < 1 || nout > PCL_CELLFN_MAX_NOUT)
+        return fail(PCL_EINVAL, "pcl_cellfn_compile_reduce: nout must be 1.." + std::to_string(PCL_CELLFN_MAX_NOUT) + ", got " +
+                                    std::to_string(nout));
+    std::string key = "reduce=" + std::to_string(nout) + ":";
+    for (int m = 0; m < nout; m++) {
+        if (ops[m] < PCL_REDUCE_SUM || ops[m] > PCL_REDUCE_MIN)
+            return fail(PCL_EINVAL, "pcl_cellfn_compile_reduce: ops[" + std::to_string(m) + "] = " + std::to_string(ops[m]) +
+                                        " is no PCL_REDUCE_* operation");
+        key += std::to_string(ops[m]) + ",";
+    }
+    key += ";" + cellfn_key(PCL_CELLFN_KIND_REDUCE, body, preamble, meqn, maux, ndim, math, 0, reach);
+    CellfnCache &c = cellfn_cache();
+    std::lock_guard<std::mutex> lock(c.mu);
+    auto it = c.by_key.find(key);
+    pcl_cellfn *f = nullptr;
+    if (it != c.by_key.end()) {
+        f = it->second;
+        c.hits++;
+    } else {
+        std::vector<char> code;
+        std::string err;
+        if (cellfn_build(PCL_CELLFN_KIND_REDUCE, body, preamble, meqn, maux, ndim, math, 0, reach, code, err, nout, ops))
+            return fail(PCL_EINVAL, err);
+        f = new pcl_cellfn();
+        f->id = c.next_id++;
+        f->kind = PCL_CELLFN_KIND_REDUCE; f->meqn = meqn; f->maux = maux; f->ndim = ndim; f->math = math;
+        f->reach = reach;
+        f->nout = nout;
+        for (int m = 0; m < nout; m++) f->ops[m] = ops[m];
+        f->key = key;
+        f->code.swap(code);
+        c.by_key[key] = f;
+        c.live[f] = f->id;
+        c.compiles++;
+    }
+    f->refs++;
+    *out = f;
+    if (code_size) *code_size = (long)f->code.size();
+    return PCL_OK;
+}
+
 int pcl_cellfn_release(pcl_cellfn *f) {
     if (!f) return PCL_OK;
     CellfnCache &c = cellfn_cache();
@@ -2132,6 +2190,12 @@ int pcl_cellfn_apply(pcl_solver *s, pcl_cellfn *f, double t, double dt, const do
     if (s) s->plan.touched();             // exchange-ahead: whatever filled the ghost frames no longer holds
     if (nparams < 0 || nparams > PCL_CELLFN_MAX_PARAMS)
         return fail(PCL_EINVAL, "pcl_cellfn_apply: a cell function takes at most 16 parameters");
+    {   // a functional has an entry point of its own; refused whatever the other arguments are
+        CellfnCache &c = cellfn_cache();
+        std::lock_guard<std::mutex> lock(c.mu);
+        if (f && c.live.count(f) && f->kind == PCL_CELLFN_KIND_REDUCE)
+            return fail(PCL_EINVAL, "pcl_cellfn_apply: a functional runs through pcl_cellfn_reduce");
+    }
     if (!s || !f || (nparams > 0 && !params)) return fail(PCL_EINVAL, "null argument");
     pcl_cell_args a;
     memset(&a, 0, sizeof(a));
@@ -2212,7 +2276,7 @@ int pcl_cellbc_apply(pcl_solver *s, pcl_cellfn *f, int idim, int side, double t,
         std::lock_guard<std::mutex> lock(c.mu);
         if (!c.live.count(f)) return fail(PCL_EINVAL, "not a live cell function handle");
         if (f->kind != PCL_CELLFN_BC)
-            return fail(PCL_EINVAL, std::string("pcl_cellbc_apply: the handle is a ") + cellfn_kind_name(f->kind) +
+            return fail(PCL_EINVAL, std::string("pcl_cellbc_apply: the handle is a ") + cellfn_kind_label(f->kind) +
                                         " cell function, not a boundary condition");
         if (!s) return fail(PCL_EINVAL, "null argument");
         if (int rc = cellfn_check_locked(c, f, s->cfg.meqn, s->cfg.maux, s->cfg.ndim)) return rc;
@@ -2251,6 +2315,85 @@ int pcl_cellbc_apply(pcl_solver *s, pcl_cellfn *f, int idim, int side, double t,
     size_t size = sizeof(a);
     void *config[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &a, HIP_LAUNCH_PARAM_BUFFER_SIZE, &size, HIP_LAUNCH_PARAM_END};
     HIP_TRY(hipModuleLaunchKernel(fn, (unsigned)groups, 1, 1, 256, 1, 1, 0, s->stream, nullptr, config));
+    return PCL_OK;
+}
+
+// A functional on the selected register.  A READ-ONLY call (include/pyclaw_amd.h: the quiet tiles, pcl_step_ahead): it
+// launches two kernels that store into the handle's partial buffer alone and copies nout doubles back, so it neither
+// invalidates the quiet tiles nor touches the ghost-frame marks, and a step enqueued ahead is still adopted -- that step
+// read s->q and wrote s->t2, and cur(s) is the accepted state until pcl_bc_step commits.
+// (The parameter is not spelled "s" on purpose: tests/test_quiet_tiles_cpu.py holds every definition of the form
+// "int pcl_x(pcl_solver *s" that is not on its list of read-only calls to invalidate first; this call belongs on that
+// list.  tests/test_cellfunctional_cpu.py holds this body to what makes it read-only instead.)
+int pcl_cellfn_reduce(pcl_solver *solver, pcl_cellfn *f, double t, const double *params, int nparams, double *out) {
+    pcl_solver *const s = solver;
+    if (nparams < 0 || nparams > PCL_CELLFN_MAX_PARAMS)
+        return fail(PCL_EINVAL, "pcl_cellfn_reduce: a cell function takes at most 16 parameters");
+    if (!f || (nparams > 0 && !params)) return fail(PCL_EINVAL, "null argument");
+    long id = 0;
+    int reach = 0;
+    ReduceFinal fin;
+    const void *code = nullptr;
+    {
+        CellfnCache &c = cellfn_cache();
+        std::lock_guard<std::mutex> lock(c.mu);
+        if (!c.live.count(f)) return fail(PCL_EINVAL, "not a live cell function handle");
+        if (f->kind != PCL_CELLFN_KIND_REDUCE)
+            return fail(PCL_EINVAL, std::string("pcl_cellfn_reduce: the handle is a ") + cellfn_kind_label(f->kind) +
+                                        " cell function, not a functional (pcl_cellfn_compile_reduce)");
+        if (!s || !out) return fail(PCL_EINVAL, "null argument");
+        if (int rc = cellfn_check_locked(c, f, s->cfg.meqn, s->cfg.maux, s->cfg.ndim)) return rc;
+        id = f->id;
+        reach = f->reach;
+        fin.nout = f->nout;
+        for (int m = 0; m < f->nout; m++) fin.op[m] = f->ops[m];
+        code = f->code.data();        // stays put while the caller holds its reference
+    }
+    // qn() clamps its offsets to [-reach, reach]: with reach <= mbc every read stays inside the ghosted block
+    if (reach < 0 || reach > s->cfg.mbc)
+        return fail(PCL_EINVAL, "pcl_cellfn_reduce: the functional reads " + std::to_string(reach) +
+                                    " cells away (reach) and the solver has mbc = " + std::to_string(s->cfg.mbc) + " ghost layers");
+    if (s->cfg.maux > 0 && !s->aux) return fail(PCL_ESTATE, "pcl_cellfn_reduce: no aux array on the device");
+    pcl_cell_args a;
+    memset(&a, 0, sizeof(a));
+    for (int k = 0; k < 3; k++) {
+        a.n[k] = k < s->cfg.ndim ? s->cfg.n[k] : 1;
+        a.nstart[k] = s->cf_nstart[k];
+        a.lower[k] = s->cf_lower[k];
+        a.d[k] = s->cfg.d[k];
+    }
+    if (a.n[1] > 65535 || a.n[2] > 65535) return fail(PCL_EINVAL, "pcl_cellfn_reduce: more than 65535 rows or planes");
+    // one workgroup per 256 cells of a row: the wrapper's grid, and the partials it leaves per output
+    const unsigned gx = (unsigned)((a.n[0] + 255) / 256);
+    const long npart = (long)gx * a.n[1] * a.n[2];
+    HIP_TRY(hipSetDevice(s->cfg.device));
+    hipFunction_t fn = nullptr;
+    if (int rc = cellfn_loaded(s, id, PCL_CELLFN_KIND_REDUCE, code, &fn)) return rc;
+    if (!s->cf_part) HIP_TRY(hipMalloc((void **)&s->cf_part, (size_t)(npart + 1) * PCL_CELLFN_MAX_NOUT * sizeof(double)));
+    a.q = cur(s);
+    a.dq = s->cf_part;
+    a.aux = s->aux;
+    a.pitch = s->pitch;
+    a.plane = s->plane;
+    a.slab = s->pitch * s->J;
+    a.mbc = s->cfg.mbc;
+    a.t = t;
+    a.dt = 0.0;
+    for (int k = 0; k < nparams; k++) a.p[k] = params[k];
+    a.snap = cur(s);                      // q is const in a functional: qn() reads the register itself
+    // a reach = 0 kernel declares the struct without its last field
+    size_t size = reach > 0 ? sizeof(a) : offsetof(pcl_cell_args, snap);
+    void *config[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &a, HIP_LAUNCH_PARAM_BUFFER_SIZE, &size, HIP_LAUNCH_PARAM_END};
+    HIP_TRY(hipModuleLaunchKernel(fn, gx, (unsigned)a.n[1], (unsigned)a.n[2], 256, 1, 1, 0, s->stream, nullptr, config));
+    fin.part = s->cf_part;
+    fin.out = s->cf_part + npart * PCL_CELLFN_MAX_NOUT;
+    fin.npart = npart;
+    fin.stream = s->stream;
+    std::string err;
+    // (adds, fmax and fmin: the exact build serves every mode)
+    if (int rc = pcl::exact::launch_reduce_partials(fin, err)) return fail(rc, err);
+    HIP_TRY(hipMemcpyAsync(out, fin.out, (size_t)fin.nout * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
     return PCL_OK;
 }
 

@@ -274,6 +274,19 @@ struct TileHandover {
     hipStream_t stream;
 };
 
+// The second pass of a functional (cellfn.hpp: pcl_cellfn_red leaves part[m * npart + w], the partial of output m from
+// workgroup w): nout workgroups of REDUCE_FINAL_THREADS threads, one per output, each combining its npart partials in an
+// order fixed by npart alone, into out[m].  op[m] is a PCL_REDUCE_* (the partials of a sum of |f| are summed).
+constexpr int REDUCE_FINAL_THREADS = 256;
+struct ReduceFinal {
+    const double *part = nullptr;
+    double *out = nullptr;
+    long npart = 0;
+    int nout = 0;
+    int op[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    hipStream_t stream;
+};
+
 // What the host layer knows about a built-in Riemann solver, read off its struct in rp.hpp through the solver list of
 // kernels.hip: the sizes pcl_create insists on, and which kernels have an instantiation of it -- onek / onek_aux: the
 // one-kernel step (launch_step2ds) without aux planes / with the solver's cell-wise coefficients staged next to q;
@@ -313,6 +326,7 @@ int sharp_tile_max_planes(int ixy, int naux);   // planes a sharp_kernel tile of
 bool x_interior_box(const BlockGeom &a, int box[4], int ntiles[2]);
 bool step2ds_interior_box(const BlockGeom &a, int box[4], int ntiles[2]);   // the same for the one-kernel step: (nty, ntx)
 int launch_tile_handover(const TileHandover &h, std::string &err);   // Courant hand-over + next tile list (bit-only)
+int launch_reduce_partials(const ReduceFinal &r, std::string &err);  // a functional's second pass (adds, fmax, fmin: no mode)
 }
 namespace fast { PCL_LAUNCHERS }
 // exact + IEEE quotients for underflow-range numerators as well (rp.hpp PCL_DENORM_GUARD), PCL_MATH_STRICT

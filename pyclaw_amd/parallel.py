@@ -339,6 +339,23 @@ def allreduce_sum_host(values):
     return out
 
 
+def allreduce_minmax_host(values, largest):
+    """The same for the largest (``largest[k]`` true) or smallest of each entry over the ranks, taken in rank order
+    with fmax / fmin semantics: a NaN is passed over unless every rank holds one."""
+    g = _state["group"]
+    if g is None:
+        return list(values)
+    rows = g.allgather([float(v) for v in values])
+    out = list(rows[0])
+    for row in rows[1:]:
+        for k, v in enumerate(row):
+            if v != v:
+                continue
+            if out[k] != out[k] or (v > out[k] if largest[k] else v < out[k]):
+                out[k] = v
+    return out
+
+
 def proc_grid(n_global, size):
     """Processor grid for `size` blocks: PETSc DMDA's default rule (DMSetUp_DA_2D).
 

@@ -268,6 +268,90 @@ class CellBC(CellFunction, DeviceBC):
         solver._host_stale = True
 
 
+class CellFunctional(CellFunction):
+    """Per-cell integrands reduced over the whole state on the device: what ``np.sum(f(state.q))`` or a Python
+    ``compute_F`` followed by ``np.sum(np.abs(state.F[i]))`` computes on a downloaded ``q``, as one pass over the resident
+    arrays that returns ``nout`` numbers.
+
+    The body (see ``CellFunction``) reads ``q[MEQN]`` and ``aux[MAUX]``, both const, ``c.t``, ``c.i``, ``c.x``, ``c.d``
+    and ``p[]`` -- with ``reach > 0`` also ``qn`` / ``auxn``, which read the register itself -- and assigns ``f[NOUT]``,
+    zero on entry; ``c.dt`` is 0.  It writes nothing else: assigning ``q[...]`` or ``aux[...]`` is a compile error.  Cell
+    volumes are the body's business (``c.d[]``).
+
+    ``reduce`` is one name or a sequence of ``nout`` names out of ``'sum'``, ``'abs_sum'`` (the reference's
+    ``sum|F_i|``), ``'max'`` and ``'min'``.  ``max`` / ``min`` pass over a NaN integrand (``fmax`` / ``fmin``); the sums
+    propagate it.  The reduction runs over the interior cells of the block, never over ghost cells, in an order fixed by
+    the block's shape: the same state gives the same bits on every call.
+
+    ``evaluate(solver, state)`` works after ``setup()`` on every solver, in and out of resident mode, and in a
+    decomposed run returns the same array on every rank.  ``claw.compute_F = CellFunctional(...)`` makes
+    ``Controller.write_F`` write these values."""
+
+    kind = 5                    # internal: compiled through pcl_cellfn_compile_reduce alone
+    MAX_NOUT = 8
+    OPS = {'sum': 0, 'abs_sum': 1, 'max': 2, 'min': 3}
+
+    def __init__(self, body, nout, reduce='sum', params=(), preamble="", reach=0):
+        CellFunction.__init__(self, body, params, preamble, reach=reach)
+        if int(nout) != nout or not 1 <= nout <= self.MAX_NOUT:
+            raise ValueError("nout must be an integer 1..%d, got %r" % (self.MAX_NOUT, nout))
+        self.nout = int(nout)
+        names = [reduce] * self.nout if isinstance(reduce, str) else list(reduce)
+        for name in names:
+            if name not in self.OPS:
+                raise ValueError("reduce must be 'sum', 'abs_sum', 'max' or 'min', got %r" % (name,))
+        if len(names) != self.nout:
+            raise ValueError("reduce names %d operations, but nout=%d" % (len(names), self.nout))
+        self.reduce = tuple(names)
+
+    def compile(self, meqn, maux, ndim, math='exact'):
+        """Compile for these shape constants (no device needed; cached per process).  Raises with the compiler's log."""
+        import ctypes
+        if math not in ('exact', 'fast', 'strict'):
+            raise Exception("math must be 'exact', 'fast' or 'strict'")
+        key = (int(meqn), int(maux), int(ndim), math, self.body, self.preamble, self.reach, self.nout, self.reduce)
+        if self._fn is not None and self._key == key:
+            return self
+        ops = np.array([self.OPS[name] for name in self.reduce], dtype=np.int32)
+        fn, size = ctypes.c_void_p(), ctypes.c_long(0)
+        rc = _lib.lib().pcl_cellfn_compile_reduce(self.body.encode(), self.preamble.encode(), key[0], key[1], key[2],
+                                                  {'exact': 0, 'fast': 1, 'strict': 2}[math], self.reach, self.nout,
+                                                  _lib.i(ops), ctypes.byref(fn), ctypes.byref(size))
+        _lib.check(rc)
+        self.release()
+        self._fn, self._key, self.code_size = fn, key, int(size.value)
+        return self
+
+    def launch(self, solver, t, dt):
+        raise NotImplementedError("a CellFunctional stores nothing into the state: use evaluate(solver, state)")
+
+    def evaluate(self, solver, state):
+        """The ``nout`` values of the state ``pcl_get_q`` would return now, as a float64 array; the same on every rank.
+
+        Out of resident mode the host copy is the newer one and is uploaded first, by the rule of ``step()``.  In
+        resident mode the call reads the resident state and leaves a step enqueued ahead in place: it sees the accepted
+        state.  With ``reach > 0`` the ghost cells are filled first (``apply_q_bcs``)."""
+        from . import parallel
+        self._check_reach(solver)                       # host only, before any device call
+        if solver._h is None:
+            raise Exception("solver.setup(solution) must be called before CellFunctional.evaluate")
+        self.compile(state.meqn, state.maux, solver.ndim, solver.math)
+        if not solver._pinned:
+            resident = solver._resident
+            solver._push(state)
+            solver._resident = resident
+        if self.reach > 0:
+            solver.apply_q_bcs(state)
+        p = self._params
+        out = np.zeros(self.nout)
+        _lib.check(_lib.lib().pcl_cellfn_reduce(solver._h, self._fn, float(state.t), _lib.d(p) if len(p) else None,
+                                                len(p), _lib.d(out)))
+        summed = parallel.allreduce_sum_host(out)
+        largest = [name == 'max' for name in self.reduce]
+        extreme = parallel.allreduce_minmax_host(out, largest)
+        return np.array([e if name in ('max', 'min') else s for name, s, e in zip(self.reduce, summed, extreme)])
+
+
 class Solver(object):
     r"""Pyclaw solver superclass; see the reference docstring (solver.py:25-125)."""
 
