@@ -112,6 +112,10 @@ extern "C" {
 #define PCL_REG_S2 2
 #define PCL_REG_DQ 3
 #define PCL_REG_TMP 4
+/* Stage derivatives K_0 .. K_{s-1} of a Runge-Kutta scheme given by its Butcher tableau (pcl_rk_stages): s <= 16.  They are
+ * named by their index; PCL_REG_K0 + j is K_j where a register id is asked for (only to be refused: pcl_rk_lincomb). */
+#define PCL_RK_MAX_STAGES 16
+#define PCL_REG_K0 16
 
 typedef struct pcl_solver pcl_solver;
 
@@ -637,6 +641,29 @@ int pcl_sharp_bc_stage(pcl_solver *s, const int *bc, const double *cstate, doubl
  *          6: C = A/ca + cb*B, then D = cc*C - 5*B with D == B (ops 3 and 4 of SSP104's mid-step, sharpclaw.py:186-187,
  *             in one pass over the registers).  D, A, B, C are PCL_REG_* ids. */
 int pcl_rk_op(pcl_solver *s, int op, int D, int A, int B, int Cc, double ca, double cb, double cc);
+
+/* ---- explicit Runge-Kutta schemes from a Butcher tableau (time_integrator = 'RK' and the named tableaus) -------------
+ * y_i = q + sum_j a_ij K_j,  K_i = dt L(y_i),  q <- q + sum_j b_j K_j, with K_j kept in stage registers of their own.
+ * All three calls check their arguments on the host before any device call and leave the handle as it was when they
+ * refuse: PCL_ESTATE on a classic solver, and (take, lincomb) before any stage register exists; PCL_EINVAL otherwise.
+ *
+ * pcl_rk_stages: hold exactly `nstages` stage registers (0 .. PCL_RK_MAX_STAGES), each the size of q and zero-filled;
+ * 0 frees them, pcl_destroy does too.  A count that is already held is kept as it is, any other frees the registers held
+ * (after a synchronisation of the stream) and allocates anew.  nstages < 0 changes nothing.  *held (may be null) gets the
+ * number held after the call.  If the memory is not there nothing is held, and PCL_EHIP's message names the stages and the
+ * bytes asked for.  A solver that never calls this allocates nothing for them. */
+int pcl_rk_stages(pcl_solver *s, int nstages, int *held);
+/* What pcl_sharp_dq / pcl_sharp_bc_dq (and a dq_src after them) left in PCL_REG_DQ becomes K_stage, without a copy: the
+ * two buffers swap their names, so PCL_REG_DQ then holds what K_stage held, for the next dq to write over.  The stage's
+ * Courant number was returned by the dq call. */
+int pcl_rk_take(pcl_solver *s, int stage);
+/* D = A + coef[0]*K_{stages[0]} + ... + coef[n-1]*K_{stages[n-1]} over the whole allocation, ghost cells included, n <=
+ * PCL_RK_MAX_STAGES, one kernel.  Per element r = A, then r = r + coef[k]*K for ascending k: in the exact and strict
+ * modes every product is rounded before its sum (no FMA), `fast` may contract.  A term whose coefficient is exactly 0.0
+ * is dropped on the host and its register is not read; every other coefficient is multiplied, 1.0 included.  D, A in
+ * {PCL_REG_Q, PCL_REG_S1, PCL_REG_S2}; D == A is served in place; D = PCL_REG_K0 + j with j among `stages` is refused as
+ * aliasing an input.  D's ghost cells are left unset, as by pcl_rk_op. */
+int pcl_rk_lincomb(pcl_solver *s, int D, int A, int n, const int *stages, const double *coef);
 
 int pcl_sync(pcl_solver *s);
 

@@ -16,6 +16,7 @@ MAX_WAVES = 8
 MAX_RP_PARAMS = 8
 
 OK, EINVAL, ENODEVICE, EHIP, ECOMM, ESTATE = 0, -1, -2, -3, -4, -5
+RK_MAX_STAGES, REG_K0 = 16, 16       # PCL_RK_MAX_STAGES, PCL_REG_K0
 
 dp = C.POINTER(C.c_double)
 ip = C.POINTER(C.c_int)
@@ -144,6 +145,9 @@ PROTOTYPES = {
                                      C.c_double, C.c_double, C.c_double, dp]),
     "pcl_rk_op": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double,
                             C.c_double]),
+    "pcl_rk_stages": (C.c_int, [C.c_void_p, C.c_int, ip]),
+    "pcl_rk_take": (C.c_int, [C.c_void_p, C.c_int]),
+    "pcl_rk_lincomb": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, ip, dp]),
     "pcl_sync": (C.c_int, [C.c_void_p]),
     "pcl_timer_start": (C.c_int, [C.c_void_p]),
     "pcl_timer_stop": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),

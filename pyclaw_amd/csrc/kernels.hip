@@ -6,10 +6,12 @@
 // Distinct namespaces keep the two sets of template instantiations apart at link time.
 #include <hip/hip_runtime.h>
 #include <algorithm>
+#include <cstdint>
 #include <cstdlib>
 #include <string>
 #include <tuple>
 #include <type_traits>
+#include <utility>
 
 #include "../../include/pyclaw_amd.h"
 #include "classic.hpp"
@@ -768,6 +770,40 @@ int launch_rk(const RkLaunch &r, hipStream_t stream, std::string &err) {
     hipLaunchKernelGGL(rk_kernel, dim3(2048), dim3(256), 0, stream, o);
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? PCL_OK : hip_fail(err, "rk launch", e);
+}
+
+// one instantiation per number of terms, so that the loads of an element are independent and unrolled
+template <int... N>
+static auto rk_lincomb_kernels(std::integer_sequence<int, N...>) {
+    static void (*const table[])(RkLincomb) = {rk_lincomb_kernel<N>...};
+    return table;
+}
+int launch_rk_lincomb(const RkLincombLaunch &r, hipStream_t stream, std::string &err) {
+    if (!r.d || !r.a || r.n <= 0 || r.nterms < 0 || r.nterms > RK_LINCOMB_MAX) {
+        err = "launch_rk_lincomb: bad arguments";
+        return PCL_EINVAL;
+    }
+    RkLincomb o;
+    o.d = r.d; o.a = r.a; o.n = r.n;
+    const uintptr_t align = (uintptr_t)r.d & 15;
+    bool same = ((uintptr_t)r.a & 15) == align && (align == 0 || align == 8);
+    for (int t = 0; t < RK_LINCOMB_MAX; t++) {
+        o.k[t] = t < r.nterms ? r.k[t] : r.a;
+        o.c[t] = t < r.nterms ? r.c[t] : 0.0;
+        if (t < r.nterms && (!r.k[t] || r.k[t] == r.d)) {
+            err = "launch_rk_lincomb: a term is null or the destination";
+            return PCL_EINVAL;
+        }
+        same = same && ((uintptr_t)o.k[t] & 15) == align;
+    }
+    o.head = !same ? -1 : align ? 1 : 0;
+    // 16 bytes per thread and trip; at most 2048 workgroups (eight per CU), the rest by the grid stride
+    const long pairs = (r.n + 1) / 2;
+    const int blocks = (int)std::min<long>(2048, (pairs + 255) / 256);
+    const auto table = rk_lincomb_kernels(std::make_integer_sequence<int, RK_LINCOMB_MAX + 1>());
+    hipLaunchKernelGGL(table[r.nterms], dim3(blocks), dim3(256), 0, stream, o);
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? PCL_OK : hip_fail(err, "rk_lincomb launch", e);
 }
 
 #if !PCL_FAST

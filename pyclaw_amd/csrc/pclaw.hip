@@ -54,6 +54,10 @@ struct pcl_solver {
     double *q = nullptr, *t1 = nullptr, *t2 = nullptr, *t3 = nullptr, *bak = nullptr;
     double *aux = nullptr;
     double *sreg[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // SharpClaw registers (0 aliases q)
+    // stage derivatives K_0 .. K_{nkreg-1} of a Runge-Kutta scheme given by its tableau (pcl_rk_stages): each the size of
+    // q, none before that call, freed by it and by pcl_destroy
+    double *kreg[PCL_RK_MAX_STAGES] = {};
+    int nkreg = 0;
     int sel = 0;          // register the put/get/bc/strip/halo calls act on
     double *stage = nullptr;  // AoS staging for host transfers (qbc-sized)
     size_t stage_bytes = 0;
@@ -930,6 +934,14 @@ int pcl_create(const pcl_config *cfg, pcl_solver **out) {
     return create_alloc(cfg, out);
 }
 
+static void rk_stages_release(pcl_solver *s) {
+    for (int k = 0; k < PCL_RK_MAX_STAGES; k++) {
+        if (s->kreg[k]) hipFree(s->kreg[k] - s->lead);
+        s->kreg[k] = nullptr;
+    }
+    s->nkreg = 0;
+}
+
 void pcl_destroy(pcl_solver *s) {
     if (!s) return;
     hipSetDevice(s->cfg.device);
@@ -949,6 +961,7 @@ void pcl_destroy(pcl_solver *s) {
         if (p) hipFree(p - s->lead);
     for (int k = 1; k < 5; k++)
         if (s->sreg[k]) hipFree(s->sreg[k] - s->lead);
+    rk_stages_release(s);
     hipFree(s->cfl_dev);
     if (s->glog_ij) hipFree(s->glog_ij);
     if (s->glog_buf) hipFree(s->glog_buf);
@@ -2582,6 +2595,90 @@ int pcl_rk_op(pcl_solver *s, int op, int D, int A, int B, int Cc, double ca, dou
     std::string err;
     int rc = PCL_BY_MATH(s->cfg.math, launch_rk(r, s->stream, err));
     if (rc) return fail(rc, err);
+    return PCL_OK;
+}
+
+int pcl_rk_stages(pcl_solver *s, int nstages, int *held) {
+    if (s) s->qt.invalidate();            // quiet tiles: not a read-only call (quiet_tiles.hpp)
+    if (!s) return fail(PCL_EINVAL, "null argument");
+    if (held) *held = s->nkreg;
+    if (nstages < 0) return PCL_OK;       // the count alone
+    if (s->cfg.kind != PCL_KIND_SHARPCLAW) return fail(PCL_ESTATE, "SharpClaw call on a classic solver");
+    if (nstages > PCL_RK_MAX_STAGES)
+        return fail(PCL_EINVAL, "pcl_rk_stages: " + std::to_string(nstages) + " stages asked for, at most " +
+                                    std::to_string(PCL_RK_MAX_STAGES) + " are served");
+    if (nstages == s->nkreg) return PCL_OK;
+    HIP_TRY(hipSetDevice(s->cfg.device));
+    HIP_TRY(hipStreamSynchronize(s->stream));       // a combination that reads them may still be running
+    rk_stages_release(s);
+    if (held) *held = 0;
+    // like every other register: 16 doubles of slack for the shifted base, zero-filled on the solver's stream
+    const size_t bytes = ((size_t)s->total + 16) * sizeof(double);
+    for (int k = 0; k < nstages; k++) {
+        double *raw = nullptr;
+        hipError_t e = hipMalloc((void **)&raw, bytes);
+        if (e == hipSuccess) {
+            s->kreg[k] = raw + s->lead;
+            e = hipMemsetAsync(raw, 0, bytes, s->stream);
+        }
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            rk_stages_release(s);
+            return fail(PCL_EHIP, "pcl_rk_stages: no memory for " + std::to_string(nstages) + " stage registers of " +
+                                      std::to_string(bytes) + " bytes each (" + std::to_string(bytes * (size_t)nstages) +
+                                      " bytes asked for, register " + std::to_string(k) + " failed): " + hipGetErrorString(e));
+        }
+    }
+    s->nkreg = nstages;
+    if (held) *held = nstages;
+    return PCL_OK;
+}
+
+int pcl_rk_take(pcl_solver *s, int stage) {
+    if (s) s->qt.invalidate();            // quiet tiles: not a read-only call (quiet_tiles.hpp)
+    if (!s) return fail(PCL_EINVAL, "null argument");
+    if (s->cfg.kind != PCL_KIND_SHARPCLAW) return fail(PCL_ESTATE, "SharpClaw call on a classic solver");
+    if (s->nkreg == 0) return fail(PCL_ESTATE, "pcl_rk_take: no stage registers (pcl_rk_stages)");
+    if (stage < 0 || stage >= s->nkreg)
+        return fail(PCL_EINVAL, "pcl_rk_take: stage " + std::to_string(stage) + " of " + std::to_string(s->nkreg));
+    if (!s->sreg[PCL_REG_DQ] || !s->kreg[stage]) return fail(PCL_ESTATE, "SharpClaw registers not allocated");
+    // work on the stream is ordered, so the buffers change names without a copy: what the dq passes (and a dq_src) left
+    // in the dq register is K_stage, and the next dq writes over what K_stage held
+    std::swap(s->sreg[PCL_REG_DQ], s->kreg[stage]);
+    s->undo_slot = nullptr;
+    return PCL_OK;
+}
+
+int pcl_rk_lincomb(pcl_solver *s, int D, int A, int n, const int *stages, const double *coef) {
+    if (s) s->qt.invalidate();            // quiet tiles: not a read-only call (quiet_tiles.hpp)
+    if (!s) return fail(PCL_EINVAL, "null argument");
+    if (s->cfg.kind != PCL_KIND_SHARPCLAW) return fail(PCL_ESTATE, "SharpClaw call on a classic solver");
+    if (n < 0 || n > PCL_RK_MAX_STAGES)
+        return fail(PCL_EINVAL, "pcl_rk_lincomb: " + std::to_string(n) + " terms, at most " + std::to_string(PCL_RK_MAX_STAGES));
+    if (n > 0 && (!stages || !coef)) return fail(PCL_EINVAL, "null argument");
+    // D named as a stage register (PCL_REG_K0 + j): in place over an input is the one aliasing the kernel cannot take
+    for (int t = 0; t < n; t++)
+        if (D == PCL_REG_K0 + stages[t]) return fail(PCL_EINVAL, "pcl_rk_lincomb: D is one of the inputs");
+    if (D < 0 || D > 2 || A < 0 || A > 2) return fail(PCL_EINVAL, "pcl_rk_lincomb: D and A must be q, s1 or s2");
+    if (s->nkreg == 0) return fail(PCL_ESTATE, "pcl_rk_lincomb: no stage registers (pcl_rk_stages)");
+    auto reg = [&](int r) -> double * { return r == 0 ? s->q : s->sreg[r]; };
+    RkLincombLaunch r;
+    r.d = reg(D); r.a = reg(A); r.n = s->total;
+    if (!r.d || !r.a) return fail(PCL_ESTATE, "SharpClaw registers not allocated");
+    for (int t = 0; t < n; t++) {
+        if (stages[t] < 0 || stages[t] >= s->nkreg)
+            return fail(PCL_EINVAL, "pcl_rk_lincomb: stage " + std::to_string(stages[t]) + " of " + std::to_string(s->nkreg));
+        if (!(coef[t] == coef[t]) || coef[t] - coef[t] != 0.0) return fail(PCL_EINVAL, "pcl_rk_lincomb: coefficient not finite");
+        if (coef[t] == 0.0) continue;     // that register is not read
+        r.k[r.nterms] = s->kreg[stages[t]];
+        r.c[r.nterms] = coef[t];
+        r.nterms++;
+    }
+    HIP_TRY(hipSetDevice(s->cfg.device));
+    std::string err;
+    int rc = PCL_BY_MATH(s->cfg.math, launch_rk_lincomb(r, s->stream, err));
+    if (rc) return fail(rc, err);
+    if (D == PCL_REG_Q) s->undo_slot = nullptr;
     return PCL_OK;
 }
 

@@ -637,5 +637,51 @@ __global__ __launch_bounds__(256) void rk_kernel(RkOp o) {
     }
 }
 
+// ---- Runge-Kutta schemes from a Butcher tableau: D = A + c_0*K_0 + c_1*K_1 + ... + c_{N-1}*K_{N-1} over whole arrays ------
+// The order of evaluation is part of the contract (the CPU restatement of the scheme forms the same sums): r = A[i], then
+// r = r + c_t * K_t[i] for ascending t, every product rounded before its sum in the exact and strict builds
+// (-ffp-contract=off) and every coefficient multiplied, 1.0 included.  Pointers and coefficients travel by value.  D may be A
+// (each element is read before it is written, by the thread that writes it); D is never one of the K (the host refuses).
+// A pure stream of N + 1 arrays in and one out: the body moves 16 bytes per access, all N + 1 loads of an element pair issued
+// before the first sum.  The registers share one alignment (base = allocation + lead doubles), so `head` (0 or 1) scalar
+// elements in front make the body 16-byte aligned in all of them; head < 0: they do not agree, every element goes alone.
+constexpr int RK_LINCOMB_MAX = 16;
+struct RkLincomb {
+    double *d;
+    const double *a;
+    const double *k[RK_LINCOMB_MAX];
+    double c[RK_LINCOMB_MAX];
+    long n;
+    int head;
+};
+template <int N>
+__global__ __launch_bounds__(256) void rk_lincomb_kernel(RkLincomb o) {
+    const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x, nthr = (long)gridDim.x * blockDim.x;
+    const long body = o.head > 0 ? o.head : 0;
+    const long nvec = o.head < 0 ? 0 : (o.n - body) / 2;
+    for (long v = tid; v < nvec; v += nthr) {
+        const long i = body + 2 * v;
+        double2 r = *reinterpret_cast<const double2 *>(o.a + i);
+        double2 k[N > 0 ? N : 1];
+#pragma unroll
+        for (int t = 0; t < N; t++) k[t] = *reinterpret_cast<const double2 *>(o.k[t] + i);
+#pragma unroll
+        for (int t = 0; t < N; t++) {
+            r.x = r.x + o.c[t] * k[t].x;
+            r.y = r.y + o.c[t] * k[t].y;
+        }
+        *reinterpret_cast<double2 *>(o.d + i) = r;
+    }
+    // what the body leaves: elements [0, body) and [body + 2 nvec, n)
+    const long done = body + 2 * nvec, nrest = o.n - 2 * nvec;
+    for (long e = tid; e < nrest; e += nthr) {
+        const long i = e < body ? e : done + (e - body);
+        double r = o.a[i];
+#pragma unroll
+        for (int t = 0; t < N; t++) r = r + o.c[t] * o.k[t][i];
+        o.d[i] = r;
+    }
+}
+
 }  // namespace PCL_NS
 }  // namespace pcl

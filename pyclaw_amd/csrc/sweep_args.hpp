@@ -193,6 +193,17 @@ struct RkLaunch {
     int op;
 };
 
+// D = A + c[0]*K[0] + ... + c[nterms-1]*K[nterms-1] over n doubles (sharpclaw.hpp: rk_lincomb_kernel), nterms <= 16; the
+// caller has dropped the terms whose coefficient is zero and has checked that d is none of the k
+struct RkLincombLaunch {
+    double *d = nullptr;
+    const double *a = nullptr;
+    const double *k[16] = {};
+    double c[16] = {};
+    int nterms = 0;
+    long n = 0;
+};
+
 // What a user-written Riemann solver (cellrp.hpp) is compiled for: the one record that travels from a pcl_cellrp_compile*
 // call through the cache entry and the loaded module to the launchers.  Every field is part of the cache key and decides
 // which kernels the code object holds.  A default-constructed one is "nothing attached".
@@ -306,6 +317,7 @@ struct InteriorBox { bool any = false; int box[4] = {0, 0, 0, 0}, ntiles[2] = {0
 //   launch_unsplit3  unsplit 3-D: slices + combine of one direction
 //   launch_unsplit   scratch-free unsplit phase
 //   launch_sharp     SharpClaw dq of one direction
+//   launch_rk / launch_rk_lincomb   register arithmetic of the Runge-Kutta schemes
 #define PCL_LAUNCHERS                                                              \
     int launch_sweep(const SweepLaunch &l, std::string &err);                      \
     int launch_step2ds(const SweepLaunch &l, std::string &err);                    \
@@ -313,7 +325,8 @@ struct InteriorBox { bool any = false; int box[4] = {0, 0, 0, 0}, ntiles[2] = {0
     int launch_unsplit3(const Unsplit3Launch &l, std::string &err);                \
     int launch_unsplit(const SweepLaunch &l, const double *qx, std::string &err);  \
     int launch_sharp(const SweepLaunch &l, std::string &err);                      \
-    int launch_rk(const RkLaunch &r, hipStream_t stream, std::string &err);
+    int launch_rk(const RkLaunch &r, hipStream_t stream, std::string &err);       \
+    int launch_rk_lincomb(const RkLincombLaunch &r, hipStream_t stream, std::string &err);
 namespace exact {
 PCL_LAUNCHERS
 // what does not depend on the arithmetic mode: exact alone has it

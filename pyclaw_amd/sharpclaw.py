@@ -9,6 +9,15 @@ kernel of csrc/sharpclaw.hpp; the stage registers and the register arithmetic of
 schemes live on the device too (``pcl_rk_op`` evaluates each formula in the order the
 reference's numpy expressions do).
 
+``time_integrator`` may also name an explicit Runge-Kutta scheme by its Butcher tableau: ``'RK'`` with ``solver.a`` (s x s,
+strictly lower triangular), ``solver.b`` and ``solver.c`` (s each, ``c[0] == 0``; ``c`` is taken as given), 1 <= s <= 16, as
+upstream PyClaw spells it, or one of the named entries of ``rk_tableaus.TABLEAUS`` -- ``'SSP22'`` (Heun), ``'RK44'`` (the
+classical method), ``'DP5'`` (the six stages of Dormand and Prince's fifth-order solution, no step-size control).  Each stage
+derivative has a register of its own on the device (``pcl_rk_stages``; the size of q each, none for the three schemes above),
+a stage's increment becomes ``K_i`` by a pointer swap (``pcl_rk_take``) and one kernel forms the combinations in a fixed order
+(``pcl_rk_lincomb``).  ``cfl_max`` and ``cfl_desired`` keep the SharpClaw defaults 2.5 / 2.45 whatever the scheme: those are
+SSP104's and too large for most tableaus, so a user of ``'RK'`` / ``'RK44'`` / ... sets them; nothing is changed silently.
+
 Implemented reconstruction: ``lim_type=2`` with ``weno_order`` 5 .. 17 (the PyWENO-generated ``weno5`` ...
 ``weno17``, float32-rounded literals included; orders above 5 for the 1-D solvers and advection_2d, acoustics_2d,
 euler_5wave_2d) and ``lim_type=3`` (the legacy ``weno5`` of reconstruct.f90,
@@ -25,7 +34,7 @@ import ctypes
 
 import numpy as np
 
-from . import _lib, riemann
+from . import _lib, riemann, rk_tableaus
 from .solver import CellFunction, CellStartStep, Solver
 
 Q, S1, S2, DQ, TMP = 0, 1, 2, 3, 4
@@ -152,6 +161,7 @@ class SharpClawSolver(Solver):
         self.rp = None
         self._user_rp = None         # the riemann.CellRiemann of this setup() and the params the library last got
         self._user_rp_sent = None
+        self._rk = None              # (a, b, c) of a scheme given by its tableau: set by setup()
         super(SharpClawSolver, self).__init__(data)
 
     # ------------------------------------------------------------------ RK step
@@ -195,11 +205,36 @@ class SharpClawSolver(Solver):
                     st(S1, s1t, 1, S1, S1, Q, ca=6.)
                     s1t = s1t + dt / 6.
                 st(S1, s1t, 5, Q, S2, S1, cb=0.6, cc=0.1)             # q = s2 + 0.6*s1 + 0.1*deltaq
+            elif self._rk is not None:
+                self._step_tableau(t, dt)
             else:
                 raise Exception('Unrecognized time integrator')
             self._host_stale = True
         except CFLError:
             return False
+
+    def _lincomb(self, D, A, coef):
+        """D = A + sum_j coef[j]*K_j on the device, terms in ascending j; a coefficient of exactly 0.0 is no term."""
+        js = [j for j in range(len(coef)) if coef[j] != 0.0]
+        stages = np.array(js, dtype=np.int32)
+        cs = np.array([coef[j] for j in js], dtype=np.float64)
+        _lib.check(_lib.lib().pcl_rk_lincomb(self._h, D, A, len(js), _lib.i(stages), _lib.d(cs)))
+
+    def _step_tableau(self, t, dt):
+        """One step of the explicit Runge-Kutta scheme of ``self._rk = (a, b, c)`` (rk_tableaus.py):
+        y_i = q + sum_j a_ij K_j in S1 (stage 0 reads q itself), K_i = dq(y_i, t + c_i dt) taken from the dq register
+        by a pointer swap, q = q + sum_j b_j K_j.  q is written by the last combination only, so a CFLError of any
+        stage leaves it as it was."""
+        a, b, c = self._rk
+        L = _lib.lib()
+        for i in range(len(b)):
+            reg = Q
+            if i > 0:
+                self._lincomb(S1, Q, a[i, :i])
+                reg = S1
+            self.dq(reg, t + c[i] * dt)
+            _lib.check(L.pcl_rk_take(self._h, i))
+        self._lincomb(Q, Q, b)
 
     def _stage_split(self, reg, t, op, D, A, B, ca=0.0, cb=0.0, cc=0.0):
         self.dq(reg, t)
@@ -319,7 +354,13 @@ class SharpClawSolver(Solver):
             # 1d/sharpclaw/flux1.f90:80-107; the 2-D flux1.f90 calls rpn2 with a wrong argument list on this path
             raise NotImplementedError("char_decomp=1 (wave-based reconstruction): 1-D solvers, lim_type 1 (tvd2_wave) or "
                                       "2 (weno5_wave), weno_order 5, no f-wave solver")
-        if self.time_integrator not in ('Euler', 'SSP33', 'SSP104'):
+        self._rk = None
+        if self.time_integrator == 'RK':
+            self._rk = rk_tableaus.validate(getattr(self, 'a', None), getattr(self, 'b', None), getattr(self, 'c', None))
+        elif self.time_integrator in rk_tableaus.TABLEAUS:
+            tab = rk_tableaus.TABLEAUS[self.time_integrator]
+            self._rk = rk_tableaus.validate(tab['a'], tab['b'], tab['c'])
+        elif self.time_integrator not in ('Euler', 'SSP33', 'SSP104'):
             raise Exception('Unrecognized time integrator')
         self.mbc = (self.weno_order + 1) // 2
         state = solution.states[0]
@@ -376,6 +417,9 @@ class SharpClawSolver(Solver):
         self._h = h
         self._user_rp, self._user_rp_sent = (rp, np.array(params)) if user_rp else (None, None)
         self._stage = _StageState(state)
+        if self._rk is not None:
+            # the stage derivatives K_0 .. K_{s-1}, each the size of q; the three hand-written schemes hold none
+            _lib.check(_lib.lib().pcl_rk_stages(self._h, len(self._rk[1]), None))
         self._dq_src_fused = False
         if isinstance(self.dq_src, DeviceDqSource) and self.dq_src.fusable(self, state):
             _lib.check(_lib.lib().pcl_sharp_fuse_dq_src(self._h, self.dq_src.src_id, _lib.d(self.dq_src.params),

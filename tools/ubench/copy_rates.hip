@@ -56,7 +56,21 @@ template <class F> static double time_ms(F launch, int reps) {
     return ms / reps;
 }
 
-int main() {
+int main(int argc, char **argv) {
+    if (argc > 1) {
+        // ./copy_rates DOUBLES [LAUNCHES]: the grid-stride double x2 kernel alone, 2048 workgroups, over that many doubles
+        // (tools/rk_bench.py: the yardstick of the Runge-Kutta combination kernel, which has this launch shape)
+        const long m = atol(argv[1]);
+        const int launches = argc > 2 ? atoi(argv[2]) : 20;
+        if (m < 2 || launches < 1) { printf("usage: copy_rates [DOUBLES >= 2 [LAUNCHES >= 1]]\n"); return 2; }
+        double *a, *b;
+        CHECK(hipMalloc(&a, m * sizeof(double))); CHECK(hipMalloc(&b, m * sizeof(double)));
+        CHECK(hipMemset(a, 0, m * sizeof(double))); CHECK(hipMemset(b, 0, m * sizeof(double)));
+        const double ms = time_ms([&] { hipLaunchKernelGGL((copy_k<2, false>), dim3(2048), dim3(256), 0, 0, a, b, m); }, launches);
+        printf("COPY %ld doubles %10.4f ms  %7.0f GB/s\n", m, ms, 2.0 * m * sizeof(double) / ms / 1e6);
+        CHECK(hipFree(a)); CHECK(hipFree(b));
+        return 0;
+    }
     const int nx = 4096, ny = 4096;
     const long plane = (long)nx * ny, n = 5 * plane;
     double *a, *b;
