@@ -862,25 +862,34 @@ def advection1D(pyclaw, mx=1000, tfinal=1.0, nout=10):
     return claw
 
 
-def acoustics3D(pyclaw, test='hom', mx=None, my=None, mz=None, run=True, math='exact', tfinal=2.0, nout=10, user_rp=False):
+def acoustics3D(pyclaw, test='hom', mx=None, my=None, mz=None, run=True, math='exact', tfinal=2.0, nout=10, user_rp=False,
+                solver_type='classic', lim_type=2, weno_order=5, time_integrator='SSP104'):
     """test/acoustics/3d/acoustics.py:6-96.  'hom': dim-split 256x4x4, all periodic (the reference gates
     final_difference = 0.00286 +- 1e-4, test/test_examples.py:481-488); 'het' needs the unsplit step3.  user_rp=True:
     the same solver as the body VC_ACOUSTICS_3D_RP of a pyclaw.CellRiemann3D, for 'het' with the transverse bodies
-    VC_ACOUSTICS_3D_RPT / VC_ACOUSTICS_3D_RPTT."""
-    solver = pyclaw.ClawSolver3D()
+    VC_ACOUSTICS_3D_RPT / VC_ACOUSTICS_3D_RPTT.  solver_type='sharpclaw': SharpClawSolver3D with the same body in a
+    pyclaw.SharpCellRiemann3D (SharpClaw in 3-D runs solvers compiled at run time only), either test's set-up."""
+    sharp = solver_type == 'sharpclaw'
+    solver = pyclaw.SharpClawSolver3D() if sharp else pyclaw.ClawSolver3D()
     solver.math = math
     trans = {} if test == 'hom' else dict(rpt3=VC_ACOUSTICS_3D_RPT, rptt3=VC_ACOUSTICS_3D_RPTT)
-    solver.rp = (pyclaw.CellRiemann3D(VC_ACOUSTICS_3D_RP, 4, 2, aux=(0, 1), name="vc_acoustics_3d_user", **trans) if user_rp
-                 else pyclaw.riemann.rp_vc_acoustics_3d)
+    if sharp:
+        solver.rp = pyclaw.SharpCellRiemann3D(VC_ACOUSTICS_3D_RP, 4, 2, aux=(0, 1), name="vc_acoustics_3d_sharp")
+        solver.lim_type, solver.weno_order, solver.time_integrator = lim_type, weno_order, time_integrator
+    else:
+        solver.rp = (pyclaw.CellRiemann3D(VC_ACOUSTICS_3D_RP, 4, 2, aux=(0, 1), name="vc_acoustics_3d_user", **trans) if user_rp
+                     else pyclaw.riemann.rp_vc_acoustics_3d)
     for k in range(3):
         solver.bc_lower[k] = solver.bc_upper[k] = pyclaw.BC.periodic
         solver.aux_bc_lower[k] = solver.aux_bc_upper[k] = pyclaw.BC.periodic
     if test == 'hom':
-        solver.dim_split = True
+        if not sharp:
+            solver.dim_split = True
         mx, my, mz = mx or 256, my or 4, mz or 4
         zr = cr = 1.0
     else:
-        solver.dim_split = False
+        if not sharp:
+            solver.dim_split = False
         for k in range(3):
             solver.bc_lower[k] = pyclaw.BC.reflecting
             solver.aux_bc_lower[k] = pyclaw.BC.reflecting
@@ -921,21 +930,27 @@ def acoustics3D(pyclaw, test='hom', mx=None, my=None, mz=None, run=True, math='e
 
 
 def euler3D(pyclaw, axis=0, n=64, across=(4, 4), tfinal=0.1, nout=1, run=True, math='exact', order=2, dim_split=True,
-            order_trans=22):
+            order_trans=22, solver_type='classic', lim_type=2, weno_order=5, time_integrator='SSP104'):
     """A system the library has no 3-D solver for: the Euler equations through EULER_3D_RP in a pyclaw.CellRiemann3D.
     Sod's jump across the plane through the middle of the box normal to `axis` (0, 1, 2), n cells along that axis and
     `across` cells along the other two (in cyclic order), extrapolation on every side; the dimension-split step or,
-    dim_split=False, the unsplit one with the transverse bodies EULER_3D_RPT / EULER_3D_RPTT and `order_trans`."""
-    solver = pyclaw.ClawSolver3D()
+    dim_split=False, the unsplit one with the transverse bodies EULER_3D_RPT / EULER_3D_RPTT and `order_trans`.
+    solver_type='sharpclaw': SharpClawSolver3D with the body in a pyclaw.SharpCellRiemann3D."""
+    sharp = solver_type == 'sharpclaw'
+    solver = pyclaw.SharpClawSolver3D() if sharp else pyclaw.ClawSolver3D()
     solver.math = math
-    trans = {} if dim_split else dict(rpt3=EULER_3D_RPT, rptt3=EULER_3D_RPTT)
-    solver.rp = pyclaw.CellRiemann3D(EULER_3D_RP, 5, 3, params=[gamma], name="euler_3d_user", **trans)
-    solver.dim_split = bool(dim_split)
-    if not dim_split:
-        solver.order_trans = order_trans
-    solver.order = order
+    if sharp:
+        solver.rp = pyclaw.SharpCellRiemann3D(EULER_3D_RP, 5, 3, params=[gamma], name="euler_3d_sharp")
+        solver.lim_type, solver.weno_order, solver.time_integrator = lim_type, weno_order, time_integrator
+    else:
+        trans = {} if dim_split else dict(rpt3=EULER_3D_RPT, rptt3=EULER_3D_RPTT)
+        solver.rp = pyclaw.CellRiemann3D(EULER_3D_RP, 5, 3, params=[gamma], name="euler_3d_user", **trans)
+        solver.dim_split = bool(dim_split)
+        if not dim_split:
+            solver.order_trans = order_trans
+        solver.order = order
+        solver.limiters = [4, 4, 4]
     solver.mwaves = 3
-    solver.limiters = [4, 4, 4]
     for k in range(3):
         solver.bc_lower[k] = solver.bc_upper[k] = pyclaw.BC.outflow
     cells = [0, 0, 0]

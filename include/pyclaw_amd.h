@@ -538,6 +538,23 @@ int pcl_cellrp_sharp(const pcl_cellrp *r, int *lim_type, int *weno_order, int *c
  * rptt3 bodies), cfg.fwave and every cfg.kind but PCL_KIND_CLASSIC for it.  One block.  Host-only. */
 int pcl_cellrp_compile3(const char *body, const char *preamble, int meqn, int mwaves, int math, const int *aux_index, int naux,
                         int form, pcl_cellrp **out, long *code_size);
+/* The same body in the SHARPCLAW stages of a 3-D solver (cfg.ndim = 3, cfg.kind = PCL_KIND_SHARPCLAW): the library compiles the
+ * x, y and z passes of its 3-D SharpClaw kernel (csrc/sharpclaw.hpp: sharp3_kernel, DIR 1..3) of the one (lim_type,
+ * weno_order) around the body and nothing else.  This is the only way SharpClaw runs in 3-D: no SharpClaw kernel of a
+ * built-in 3-D solver is instantiated (the library's own vc_acoustics_3d runs as its body), pcl_create goes on refusing a
+ * built-in id with ndim == 3 under SharpClaw, and pcl_cellrp_compile_sharp goes on refusing ndim == 3.  ixy is 1, 2 or 3;
+ * the body, the preamble and the aux list mean what they mean above; char_decomp is 0.  A line is swept where both of its
+ * transverse indices lie in 0 .. m+1 (the rule of the reference's 2-D flux2.f90, which has no 3-D counterpart).
+ * Refused before the compiler (PCL_EINVAL, each with its reason): PCL_CELLRP_FORM_FWAVE (form may carry
+ * PCL_CELLRP_FORM_CAPA only); lim_type outside 1..3; weno_order not odd in 5..17, or above 5 with lim_type != 2; meqn or
+ * mwaves outside 1..8; meqn + capa + naux > 8 (the tile of each pass holds q, the capacity function and, in the y and z
+ * passes, the listed aux components in the 64 KB a workgroup may declare).  lim_type and weno_order are part of the cache
+ * key.  Such a handle serves pcl_create_cellrp with cfg.ndim = 3, cfg.kind = PCL_KIND_SHARPCLAW, the same lim_type,
+ * cfg.mbc = (weno_order + 1) / 2, cfg.method[4] = 0 and method[5] > 0 if and only if it has PCL_CELLRP_FORM_CAPA; a classic
+ * 3-D handle on such a configuration and such a handle on a classic configuration are PCL_EINVAL.  One block, no fused dq
+ * source.  Host-only. */
+int pcl_cellrp_compile3_sharp(const char *body, const char *preamble, int meqn, int mwaves, int math, const int *aux_index, int naux,
+                              int form, int lim_type, int weno_order, pcl_cellrp **out);
 /* pcl_cellrp_compile3 with the transverse solvers of the UNSPLIT 3-D step (cfg.method[2] >= 0; step3.f + flux3.f): rpt3 is
  * the inside of Clawpack's rpt3 for one interface, rptt3 (may be null) the inside of rptt3.  The code object also holds
  * the pieces kernels of the general unsplit step (csrc/classic3.hpp: pieces3_kernel, DIR 1..3); the library's own gather

@@ -123,6 +123,8 @@ PROTOTYPES = {
     "pcl_cellrp_sharp": (C.c_int, [C.c_void_p, ip, ip, ip]),
     "pcl_cellrp_compile3": (C.c_int, [C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_int, ip, C.c_int, C.c_int,
                                       C.POINTER(C.c_void_p), C.POINTER(C.c_long)]),
+    "pcl_cellrp_compile3_sharp": (C.c_int, [C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_int, ip, C.c_int, C.c_int, C.c_int,
+                                            C.c_int, C.POINTER(C.c_void_p)]),
     "pcl_cellrp_compile3t": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_int, ip, C.c_int,
                                        C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_long)]),
     "pcl_cellrp_transverse3": (C.c_int, [C.c_void_p, ip]),

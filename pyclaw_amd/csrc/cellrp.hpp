@@ -106,6 +106,12 @@
 //     sharp_kernel's tile is static LDS of TA * 64 doubles per plane, TA = sharp_tile_across (16; 8 in the y pass from six
 //     aux components on); the x pass stages meqn + capa planes, the y pass meqn + capa + naux, each within 64 KB
 //     (sharp_tile_max_planes, kernels.hip).  sharp1w_kernel declares no LDS.
+//     ndim 3 (pcl_cellrp_compile3_sharp alone, SharpCellRiemann3D; pcl_cellrp_compile_sharp goes on refusing ndim 3):
+//         sharp3_kernel<UserRp, 1, CAPA, LIM, K>, <UserRp, 2, ..>, <UserRp, 3, ..>     the x, y and z passes of a stage
+//     and nothing else -- no classic sweep, no char_decomp, no f-wave form (form may carry PCL_CELLRP_FORM_CAPA only).  One
+//     rule for the three tiles: meqn + capa + naux <= SHARP3_MAX_PLANES (8; sharpclaw.hpp).  Such a handle serves cfg.ndim =
+//     3 with cfg.kind = PCL_KIND_SHARPCLAW whose lim_type, mbc and method[5] > 0 say the same and method[4] = 0; it is the
+//     only way SharpClaw runs in 3-D (no SharpClaw kernel of a built-in 3-D solver is instantiated).
 //   onek   (pcl_cellrp_compile_onek, CellRiemann(one_kernel=True); 2-D classic handles only)
 //     The dimension-split 2-D step as ONE kernel around the body, next to everything the same call without it compiles:
 //     -DPCL_CELLRP_ONEK=1 makes the text include classic_fused.hpp (which includes classic.hpp) and adds one name
@@ -386,11 +392,14 @@ static const char *const kCellrpTrans3Close = R"PCLSRC(
 static const char *const kCellrpClose = R"PCLSRC(};
 static constexpr int USER_CAPA = (PCL_CELLRP_FORM & 2) != 0 ? 1 : 0;
 #if PCL_CELLRP_SHARP
-static_assert(PCL_CELLRP_SHARP_CD == 1 ||
+static_assert(UserRp::NDIM == 3 || PCL_CELLRP_SHARP_CD == 1 ||
                   (sizeof(double) * (UserRp::MEQN + USER_CAPA) * sharp_tile_across<UserRp, 1>() * WAVE <= 65536 &&
                    (UserRp::NDIM == 1 ||
                     sizeof(double) * (UserRp::MEQN + USER_CAPA + UserRp::NAUX) * sharp_tile_across<UserRp, 2>() * WAVE <= 65536)),
               "meqn + capa + naux: the LDS tile of sharp_kernel (sharpclaw.hpp) does not fit the 64 KB a workgroup may declare");
+static_assert(UserRp::NDIM != 3 || (PCL_CELLRP_SHARP_CD == 0 && (PCL_CELLRP_FORM & 1) == 0 &&
+                                    UserRp::MEQN + USER_CAPA + UserRp::NAUX <= SHARP3_MAX_PLANES),
+              "a 3-D SharpClaw solver: wave form, char_decomp 0, meqn + capa + naux <= 8 (sharp3_kernel, sharpclaw.hpp)");
 #elif PCL_CELLRP_NDIM == 3 && !PCL_CELLRP_SWEEP3
 static_assert(PCL_CELLRP_TRANS3 > 0, "a 3-D handle without the three sweeps holds the unsplit step's kernels");
 #elif PCL_CELLRP_NDIM == 3
@@ -437,12 +446,33 @@ static inline const char *cellrp_onek_refusal(const CellrpSpec &sp, bool dim3) {
 // a 3-D handle holds the three dimension-split sweeps where their tile takes the solver's planes; one with rpt3 / rptt3 bodies
 // and more planes than that is compiled without them and serves the unsplit step alone (pieces3_kernel has no tile)
 static inline bool cellrp_has_sweep3(const CellrpSpec &sp) {
-    return sp.ndim == 3 && sp.meqn + sp.naux + (sp.capa() ? 1 : 0) <= exact::sweep3_tile_max_planes();
+    return sp.ndim == 3 && !sp.sharp() && sp.meqn + sp.naux + (sp.capa() ? 1 : 0) <= exact::sweep3_tile_max_planes();
 }
 static inline int cellrp_spec_check(const CellrpSpec &sp, const CellrpGiven &given, std::string &err) {
     const auto no = [&err](const std::string &why) { err = why; return -1; };
     const auto n = [](int v) { return std::to_string(v); };
-    if (given.sharp) {
+    if (given.sharp && given.dim3) {
+        // pcl_cellrp_compile3_sharp: the three passes of sharp3_kernel and nothing else, each refusal before the compiler
+        const std::string who = "pcl_cellrp_compile3_sharp: ";
+        if (sp.form & ~(PCL_CELLRP_FORM_FWAVE | PCL_CELLRP_FORM_CAPA))
+            return no(who + "form = " + n(sp.form) + " has a bit that is neither PCL_CELLRP_FORM_FWAVE (1) nor PCL_CELLRP_FORM_CAPA (2)");
+        if (sp.fwave())
+            return no(who + "PCL_CELLRP_FORM_FWAVE: no f-wave form of the 3-D SharpClaw kernel (sharp3_kernel); form may carry "
+                            "PCL_CELLRP_FORM_CAPA only");
+        if (sp.lim_type != 1 && sp.lim_type != 2 && sp.lim_type != 3)
+            return no(who + "lim_type must be 1 (tvd2), 2 (WENO) or 3 (legacy WENO5), got " + n(sp.lim_type));
+        if (sp.weno_order < 5 || sp.weno_order > 17 || sp.weno_order % 2 == 0)
+            return no(who + "weno_order must be odd, 5..17, got " + n(sp.weno_order));
+        if (sp.weno_order > 5 && sp.lim_type != 2)
+            return no(who + "weno_order " + n(sp.weno_order) + " exists for lim_type 2 only, got lim_type " + n(sp.lim_type));
+        if (sp.char_decomp != 0) return no(who + "char_decomp must be 0 in 3-D");
+        if (sp.meqn < 1 || sp.meqn > PCL_MAX_WAVES || sp.mwaves < 1 || sp.mwaves > PCL_MAX_WAVES)
+            return no(who + "1 <= meqn <= 8 and 1 <= mwaves <= 8");
+        if (sp.naux >= 0 && sp.meqn + (sp.capa() ? 1 : 0) + sp.naux > exact::sharp3_tile_max_planes())
+            return no(who + "meqn + capa + naux = " + n(sp.meqn + (sp.capa() ? 1 : 0) + sp.naux) + ", the tile of the 3-D "
+                            "SharpClaw passes holds at most " + n(exact::sharp3_tile_max_planes()) + " planes (q components, the "
+                            "capacity function and listed aux components) in the 64 KB a workgroup may declare");
+    } else if (given.sharp) {
         // what no SharpClaw kernel exists for, with pcl_create's conditions
         if (sp.lim_type != 1 && sp.lim_type != 2 && sp.lim_type != 3)
             return no("pcl_cellrp_compile_sharp: lim_type must be 1 (tvd2), 2 (WENO) or 3 (legacy WENO5), got " + n(sp.lim_type));
@@ -483,7 +513,7 @@ static inline int cellrp_spec_check(const CellrpSpec &sp, const CellrpGiven &giv
     if (sp.trans3 && sp.capa())
         return no("pcl_cellrp_compile3t: PCL_CELLRP_FORM_CAPA with rpt3 / rptt3 bodies: the unsplit 3-D step (step3) with a "
                   "capacity function (mcapa) is not built for any solver");
-    if (sp.ndim == 3) {
+    if (sp.ndim == 3 && !sp.sharp()) {
         // the three passes of sweep3_kernel and nothing else: wave form, one tile of meqn + naux + capa planes
         if (sp.form & ~(PCL_CELLRP_FORM_FWAVE | PCL_CELLRP_FORM_CAPA))
             return no("pcl_cellrp_compile3: form = " + n(sp.form) + " has a bit that is neither "
@@ -498,7 +528,7 @@ static inline int cellrp_spec_check(const CellrpSpec &sp, const CellrpGiven &giv
                       "holds at most " + n(max3) + " planes (q components, listed aux components and the capacity function) in "
                       "the 64 KB a workgroup may declare");
     }
-    if (sp.sharp() && sp.char_decomp == 0) {
+    if (sp.sharp() && sp.char_decomp == 0 && sp.ndim != 3) {
         // the tiles of sharp_kernel: q and the capacity function in the x pass, the listed aux components too in the y
         // pass (sharp1w_kernel, char_decomp = 1, has no tile)
         const int max_x = exact::sharp_tile_max_planes(1, sp.naux), max_y = exact::sharp_tile_max_planes(2, sp.naux);
@@ -632,6 +662,10 @@ static inline CellrpExprs cellrp_exprs(const CellrpSpec &sp) {
         if (sp.char_decomp == 1) return {{SLOT_SWEEP_X, "&" + ns + "sharp1w_kernel<" + rp + n(sp.lim_type) + ", " + capa + ">"}};
         auto sk = [&](int ixy) { return "&" + ns + "sharp_kernel<" + rp + n(ixy) + ", " + capa + ", " + n(sp.lim_type) + ", " + n(sp.mbc()) + ">"; };
         if (sp.ndim == 1) return {{SLOT_SWEEP_X, sk(1)}};
+        if (sp.ndim == 3) {     // x, y, z
+            auto s3 = [&](int dir) { return "&" + ns + "sharp3_kernel<" + rp + n(dir) + ", " + capa + ", " + n(sp.lim_type) + ", " + n(sp.mbc()) + ">"; };
+            return {{SLOT_SWEEP_X, s3(1)}, {SLOT_SWEEP_Y, s3(2)}, {SLOT_SWEEP_Z, s3(3)}};
+        }
         return {{SLOT_SWEEP_X, sk(1)}, {SLOT_SWEEP_Y, sk(2)}};
     }
     if (sp.ndim == 3) {     // x, y, z

@@ -451,6 +451,12 @@ int sweep3_tile_max_planes() { return sweep3_tile_planes(); }
 // per plane, TA = sharp_tile_across (16; 8 in the y pass from six aux components on).  The y pass (ixy 2) stages meqn + capa
 // + naux planes, the x pass (ixy 1; the 1-D pass too) meqn + capa: it reads aux from global memory.
 int sharp_tile_max_planes(int ixy, int naux) { return 65536 / ((int)sizeof(double) * sharp_tile_across_n(ixy, naux) * WAVE); }
+// the same for the three passes of a 3-D SharpClaw stage (sharp3_kernel): one rule, meqn + capa + naux, set by the 16-strip tile
+int sharp3_tile_max_planes() {
+    static_assert(sizeof(double) * SHARP3_MAX_PLANES * sharp3_tile_across_n(1, 0) * WAVE <= 65536 &&
+                  sizeof(double) * SHARP3_MAX_PLANES * sharp3_tile_across_n(2, 5) * WAVE <= 65536, "the 3-D SharpClaw tile fits 64 KB");
+    return SHARP3_MAX_PLANES;
+}
 // the same for the one-kernel step (classic_fused.hpp): tile (ty, tx) reads rows mbc-2+F_OWN_R*ty .. +F_ROWS-1 and columns
 // mbc-2+60*tx .. +63; box = [ty_lo, ty_hi) x [tx_lo, tx_hi), ntiles = (nty, ntx)
 bool step2ds_interior_box(const BlockGeom &a, int box[4], int ntiles[2]) {
@@ -631,6 +637,14 @@ SweepPlan sharp_plan(const SweepLaunch &l, int ixy, int K, int ta) {
     const int ntiles_across = (n_across + ta - 1) / ta, ntiles_along = (m_along + SS - 1) / SS;
     return {dim3((unsigned)ntiles_across * (unsigned)ntiles_along), dim3(256), l.stream, {a, ntiles_across, ntiles_along}};
 }
+// sharp3_kernel<., l.ids, ., ., K> with ta strips per tile over l.a: (tiles, batch), the batch index every k (x, y passes) or j
+// (z pass) of the array -- the kernel leaves at once where that index is not swept
+SweepPlan sharp3_plan(const SweepLaunch &l, int K, int ta) {
+    const SweepArgs &a = l.a;
+    const int n_across = l.ids == 1 ? a.n_ac : a.n_ac + (LINE - a.mbc);     // y, z: columns counted from the line boundary
+    const int ntiles_across = (n_across + ta - 1) / ta, ntiles_along = (a.m_al + sstrip(K) - 1) / sstrip(K);
+    return {dim3((unsigned)ntiles_across * (unsigned)ntiles_along, (unsigned)a.n_b), dim3(256), l.stream, {a, ntiles_across, ntiles_along}};
+}
 // sharp1w_kernel: strips of sstrip(3) cells, four to a workgroup
 StripPlan sharp1w_plan(const SweepLaunch &l) {
     const int nstrips = (l.a.mx + sstrip(3) - 1) / sstrip(3);
@@ -722,8 +736,21 @@ int launch_sharp_user(const SweepLaunch &l, std::string &err) {
               " and the stage asks for char_decomp " + std::to_string(l.char_decomp);
         return PCL_EINVAL;
     }
+    if ((l.ndim == 3) != (u.ndim == 3)) {
+        err = u.ndim == 3 ? "user-written Riemann solver: the attached solver holds the 3-D SharpClaw kernels (pcl_cellrp_compile3_sharp) and the stage is not 3-D"
+                          : "user-written Riemann solver: a 3-D SharpClaw stage needs a solver compiled by pcl_cellrp_compile3_sharp";
+        return PCL_EINVAL;
+    }
     hipError_t e;
-    if (l.char_decomp == 1) {
+    if (l.ndim == 3) {
+        // sharp3_kernel<UserRp, ids, CAPA, LIM, K>: the fused Runge-Kutta store phase exists in the z pass alone
+        if (l.ids < 1 || l.ids > 3 || l.char_decomp != 0 || (l.a.rk_op != 0 && l.ids != 3) || l.a.n_b < 1 || l.a.n_b > 65535) {
+            err = "SharpClaw 3-D pass: direction 1..3, char_decomp 0, the Runge-Kutta combination in the z pass only, at most 65535 batch indices";
+            return PCL_EINVAL;
+        }
+        SweepPlan p = sharp3_plan(l, u.mbc(), sharp3_tile_across_n(l.ids, u.naux));
+        e = fire(f, p);
+    } else if (l.char_decomp == 1) {
         if (l.ndim != 1 || l.a.mbc != 3) { err = "SharpClaw char_decomp = 1: 1-D, mbc 3"; return PCL_EINVAL; }
         StripPlan p = sharp1w_plan(l);
         e = fire(f, p);
@@ -738,6 +765,9 @@ int launch_sharp_user(const SweepLaunch &l, std::string &err) {
 
 int launch_sharp(const SweepLaunch &l, std::string &err) {
     if (l.rp == PCL_RP_CELL) return launch_sharp_user(l, err);
+    if (l.ndim == 3)
+        return not_built(err, "SharpClaw in 3-D: no kernel of a built-in Riemann solver is instantiated; it runs a solver compiled at "
+                              "run time (pcl_cellrp_compile3_sharp, pcl_create_cellrp)");
     const RpFacts *f = Solvers::facts(l.rp);       // the flag follows the solver, among those with SharpClaw kernels
     if ((l.fwave != 0) != (f && f->sharp && f->fwave))
         return not_built(err, "solver.fwave must be True for an f-wave Riemann solver and only for one");

@@ -78,7 +78,7 @@ struct pcl_solver {
     struct Timed { hipEvent_t a, b; int which; bool count; };
     std::vector<Timed> timed;
     std::vector<hipEvent_t> evpool;
-    double kt_ms[3] = {0, 0, 0};      // x pass / y pass (or phases) / the one-kernel dim-split step
+    double kt_ms[3] = {0, 0, 0};      // x pass / y pass (or phases) / the one-kernel dim-split step (3-D SharpClaw: its z pass)
     long kt_n[3] = {0, 0, 0};
     pcl::StepForm form;   // which form of the dimension-split 2-D step runs: state and rule in step_form.hpp
     pcl::Halo halo;
@@ -743,7 +743,7 @@ int check_device() {
 extern "C" {
 
 const char *pcl_last_error(void) { return g_err.c_str(); }
-int pcl_version(void) { return 114; }
+int pcl_version(void) { return 115; }
 int pcl_device_count(void) {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess) return 0;
@@ -762,7 +762,8 @@ int pcl_rp_info(int rp, int info[10]) {
 // solver and checks against it what only the handle can serve (the unsplit step, f-waves, a capacity function:
 // cellrp_fits); pcl_create cannot know it and refuses all three.  handle_ndim: what that handle was compiled for -- a 3-D
 // configuration needs a 3-D handle (pcl_cellrp_compile3), which pcl_create cannot know either.
-static int create_check(const pcl_config *cfg, bool cell_handle, int handle_ndim = 0, int handle_trans3 = 0) {
+// handle_sharp: the handle holds SharpClaw kernels -- in 3-D the only way SharpClaw runs (pcl_cellrp_compile3_sharp).
+static int create_check(const pcl_config *cfg, bool cell_handle, int handle_ndim = 0, int handle_trans3 = 0, bool handle_sharp = false) {
     if (getenv("PCL_TRACE_ABORT")) {   // diagnostics: C backtrace on abort()
         signal(SIGABRT, [](int) {
             void *bt[64];
@@ -815,7 +816,7 @@ static int create_check(const pcl_config *cfg, bool cell_handle, int handle_ndim
         if (cfg->ndim == 3 && handle_ndim != 3)
             return fail(PCL_EINVAL, "PCL_RP_CELL: the handle holds the 1-D or 2-D kernels; a 3-D configuration (ndim == 3) needs one "
                                     "compiled for the 3-D sweeps (pcl_cellrp_compile3)");
-        if (cfg->ndim == 3 && cfg->method[2] >= 0 && !handle_trans3)
+        if (cfg->ndim == 3 && cfg->kind == PCL_KIND_CLASSIC && !handle_sharp && cfg->method[2] >= 0 && !handle_trans3)
             return fail(PCL_EINVAL, "PCL_RP_CELL: the unsplit 3-D step (method[2] >= 0, step3) needs rpt3 and rptt3 bodies "
                                     "(pcl_cellrp_compile3t); a handle compiled without them serves the dimension-split 3-D step "
                                     "only (method[2] < 0)");
@@ -858,8 +859,20 @@ static int create_check(const pcl_config *cfg, bool cell_handle, int handle_ndim
         if (cfg->kind == PCL_KIND_CLASSIC && cfg->method[2] >= 0 && cfg->method[5] == 0)
             return fail(PCL_EINVAL, "shallow water on the sphere, unsplit: the capacity function (mcapa) must be set (step2qcor.f)");
     }
-    if (cfg->ndim == 3) {
-        if (cfg->kind != PCL_KIND_CLASSIC) return fail(PCL_EINVAL, "3-D: classic solver only (the reference has no 3-D SharpClaw)");
+    if (cfg->ndim == 3 && cfg->kind != PCL_KIND_CLASSIC) {
+        // SharpClaw in 3-D: through a handle compiled for it and through nothing else (cellrp_fits holds the two together)
+        if (cfg->rp != PCL_RP_CELL || !cell_handle)
+            return fail(PCL_EINVAL, "3-D: classic solver only for a built-in Riemann solver (no SharpClaw kernel of one is instantiated); "
+                                    "SharpClaw in 3-D runs a solver compiled at run time: pcl_cellrp_compile3_sharp, given with the "
+                                    "configuration (pcl_create_cellrp)");
+        if (!handle_sharp)
+            return fail(PCL_EINVAL, "3-D: this handle holds the kernels of the classic solver only; a SharpClaw configuration "
+                                    "(cfg.kind = 1) needs one compiled by pcl_cellrp_compile3_sharp");
+        if (cfg->method[4] != 0) return fail(PCL_EINVAL, "3-D SharpClaw: char_decomp (cfg.method[4]) must be 0");
+    } else if (cfg->ndim == 3) {
+        if (handle_sharp)
+            return fail(PCL_EINVAL, "3-D: this handle holds the SharpClaw kernels (pcl_cellrp_compile3_sharp) and the configuration "
+                                    "is the classic solver only (cfg.kind = 0), which needs one compiled by pcl_cellrp_compile3");
         // (the built-in solver's; a user-written one lists what it reads, checked against maux by cellrp_fits)
         if (cfg->rp != PCL_RP_CELL && cfg->maux < 2) return fail(PCL_EINVAL, "rpn3_vc_acoustics needs aux(1)=impedance, aux(2)=sound speed");
         if (cfg->method[5] != 0 && cfg->method[2] >= 0)
@@ -1981,6 +1994,20 @@ int pcl_cellrp_compile3(const char *body, const char *preamble, int meqn, int mw
     return cellrp_compile(sp, {body, nullptr, preamble}, given, out, code_size);
 }
 
+// The three passes of a 3-D SharpClaw stage (sharpclaw.hpp: sharp3_kernel, DIR 1..3) of the one (lim_type, weno_order) around the
+// body, and nothing else: the only way SharpClaw runs in 3-D
+int pcl_cellrp_compile3_sharp(const char *body, const char *preamble, int meqn, int mwaves, int math, const int *aux_index, int naux,
+                              int form, int lim_type, int weno_order, pcl_cellrp **out) {
+    pcl::CellrpSpec sp = cellrp_spec(meqn, mwaves, 3, math, aux_index, naux);
+    sp.form = form;
+    sp.lim_type = lim_type; sp.weno_order = weno_order;
+    pcl::CellrpGiven given = {};
+    given.aux_list = aux_index != nullptr;
+    given.sharp = true;
+    given.dim3 = true;
+    return cellrp_compile(sp, {body, nullptr, preamble}, given, out, nullptr);
+}
+
 // The same with the inside of rpt3 and, where rptt3 is not null, of rptt3 (cellrp.hpp: kCellrpTrans3): the code object also
 // holds the pieces kernels of the general unsplit 3-D step (classic3.hpp), one per direction
 int pcl_cellrp_compile3t(const char *body, const char *rpt3, const char *rptt3, const char *preamble, int meqn, int mwaves, int math,
@@ -2135,13 +2162,14 @@ int pcl_create_cellrp(const pcl_config *cfg, pcl_cellrp *r, pcl_solver **out) {
     *out = nullptr;
     if (cfg->rp != PCL_RP_CELL) return fail(PCL_EINVAL, "pcl_create_cellrp: cfg.rp must be PCL_RP_CELL");
     int handle_trans3 = 0;
+    bool handle_sharp = false;
     int handle_ndim = cfg->ndim;        // (not a live handle: refused as such below, behind the configuration's own refusals)
     {
         CellfnCache &c = cellfn_cache();
         std::lock_guard<std::mutex> lock(c.mu);
-        if (r && c.rp_live.count(r)) { handle_ndim = r->spec.ndim; handle_trans3 = r->spec.trans3; }
+        if (r && c.rp_live.count(r)) { handle_ndim = r->spec.ndim; handle_trans3 = r->spec.trans3; handle_sharp = r->spec.sharp(); }
     }
-    if (int rc = create_check(cfg, true, handle_ndim, handle_trans3)) return rc;
+    if (int rc = create_check(cfg, true, handle_ndim, handle_trans3, handle_sharp)) return rc;
     {
         pcl::CellrpSpec sp;
         std::string err;
@@ -2462,6 +2490,20 @@ static int sharp_pass(pcl_solver *s, int ids, double dt, int rk_op, const double
     SweepLaunch l;
     l.a = make_args(s, cur(s), s->sreg[PCL_REG_DQ], ids, dt);
     l.a.sub = sub;
+    if (s->cfg.ndim == 3) {
+        // the pass by strides, as do_sweep3 describes a classic one: (along, across, batch) = x: (i, j, k), y: (j, i, k), z: (k, i, j);
+        // lines whose two transverse indices lie in 0..m+1 are swept (one ghost layer)
+        const int mbc = s->cfg.mbc;
+        const long st[3] = {1, s->pitch, s->pitch * s->J};
+        const int n[3] = {s->I, s->J, s->K};
+        const int al = ids - 1, ac = ids == 1 ? 1 : 0, bt = ids == 3 ? 1 : 2;
+        l.a.s_al = st[al]; l.a.s_ac = st[ac]; l.a.s_b = st[bt];
+        l.a.n_al = n[al]; l.a.n_ac = n[ac]; l.a.n_b = n[bt];
+        l.a.m_al = s->cfg.n[al];
+        l.a.lo_ac = mbc - 1; l.a.hi_ac = mbc + s->cfg.n[ac];
+        l.a.lo_b = mbc - 1; l.a.hi_b = mbc + s->cfg.n[bt];
+        l.a.vbc_on = 0;
+    }
     if (rk_op && ids == s->cfg.ndim) {
         l.a.rk_op = rk_op; l.a.rk_a = ra; l.a.rk_b = rb; l.a.rk_d = rd;
         l.a.rk_ca = ca; l.a.rk_cb = cb; l.a.rk_cc = cc;
@@ -2470,7 +2512,7 @@ static int sharp_pass(pcl_solver *s, int ids, double dt, int rk_op, const double
     l.lim_type = s->cfg.lim_type; l.stream = stream;
     l.char_decomp = s->cfg.method[4];          // SharpClaw: clawparams.char_decomp travels in method(5) (unused by it)
     if (l.rp == PCL_RP_CELL) user_launch_fields(l, s);
-    LaunchTimer timer(s, timing_on(s), ids - 1, sub != 2, stream);
+    LaunchTimer timer(s, timing_on(s), ids - 1, sub != 2, stream);      // (3-D: the z pass in the third slot, pcl_step_form_stats)
     int rc = PCL_BY_MATH(s->cfg.math, launch_sharp(l, err));
     timer.end();
     if (rc) return fail(rc, err);

@@ -411,6 +411,195 @@ __global__ __launch_bounds__(256, CAPA ? 3 : 4) void sharp_kernel(SweepArgs a, i
     cfl_publish(a.cfl, cflmax);
 }
 
+// ---- 3-D: dq of one direction, DIR = 1 (along i), 2 (along j), 3 (along k) ---------------------------------------------
+// The reference has no flux3.f90; this is flux2.f90's slice driver with one more transverse index: a line is swept if and
+// only if BOTH of its transverse indices lie in 0 .. m+1 (one ghost layer, flux2.f90:38,70), the Courant maximum is taken
+// over exactly those lines, and only interior cells are stored.  dq = ((dq_x) + dq_y) + dq_z: DIR 1 stores, DIR 2 and 3 add
+// to what is there, DIR 3 -- the last pass of a stage -- carries the fused Runge-Kutta store phase of sharp_kernel.
+// Addressing is sweep3_kernel's (classic.hpp): the array is q[m][k][j][i] and a launch describes the pass by strides,
+// s_al along the sweep, s_ac across the tile, s_b per batch (blockIdx.y); lo_ac..hi_ac and lo_b..hi_b = mbc-1 .. mbc+m
+// are the swept transverse indices, so lo < index < hi is "interior".  DIR 1 runs along i; DIR 2 and 3 run ACROSS i,
+// every 16-double row segment of a tile one 128-byte line (the array base is shifted so that cell mbc starts a line).
+// Per cell the work is sharp_kernel's, in its order: tile of 64 along x TA across (stile_at<1> for DIR 1, the swizzled
+// stile_at<2> for DIR 2 / 3), halo K = mbc, DIR 1 reads aux per lane from global memory, DIR 2 / 3 stage it in the tile.
+// Instantiated for solvers compiled at run time only (cellrp.hpp); no SRC, no f-wave form, no char_decomp.
+constexpr int sharp3_tile_across_n(int dir, int naux) { return (dir != 1 && naux >= 6) ? 8 : T_ACROSS_S; }
+// planes (q components, the capacity function, staged aux components) a tile may hold: the one rule of every pass
+constexpr int SHARP3_MAX_PLANES = 8;
+
+template <class RP, int DIR, bool CAPA, int LIM, int K = 3>
+__global__ __launch_bounds__(256, CAPA ? 3 : 4) void sharp3_kernel(SweepArgs a, int ntiles_across, int ntiles_along) {
+    constexpr int MEQN = RP::MEQN, MWAVES = RP::MWAVES;
+    constexpr int SHALO = K, SSTRIP = sstrip(K);      // a.mbc == K (checked by the launcher)
+    static_assert(DIR >= 1 && DIR <= 3, "x, y or z");
+    static_assert(K == 3 || LIM == 2, "orders above 5 exist for the PyWENO form only");
+    constexpr int NAUX = RP::NAUX, PAUX = MEQN + (CAPA ? 1 : 0);
+    constexpr int NAUX_LDS = DIR == 1 ? 0 : NAUX;
+    constexpr int NP = PAUX + NAUX_LDS;
+    constexpr int L = DIR == 1 ? 1 : 2;                    // the tile's layout (stile_at)
+    constexpr int TA = sharp3_tile_across_n(DIR, NAUX);
+    constexpr int NLD = TA * WAVE / 256;
+    constexpr int PLANE = TA * WAVE;
+    static_assert(PAUX + NAUX <= SHARP3_MAX_PLANES, "meqn + capa + naux <= 8");
+    static_assert(sizeof(double) * NP * PLANE <= 65536, "the tile does not fit the 64 KB a workgroup may declare");
+    using Cell = typename RP::Cell;
+    __shared__ double tile[NP * PLANE];
+
+    // a batch index outside the swept range: nothing to solve, nothing to store (uniform over the workgroup, before any barrier)
+    const int bt = blockIdx.y;
+    if (bt < a.lo_b || bt > a.hi_b) return;
+    const bool inner_b = bt > a.lo_b && bt < a.hi_b;
+    const int tb = DIR == 1 ? blockIdx.x / ntiles_along : blockIdx.x % ntiles_across;
+    const int ta = DIR == 1 ? blockIdx.x % ntiles_along : blockIdx.x / ntiles_across;
+    const int b0 = DIR == 1 ? tb * TA : tb * TA - (LINE - a.mbc);
+    const int a0 = a.mbc - SHALO + ta * SSTRIP;
+    const long base = (long)bt * a.s_b;
+
+    // cooperative load (memory-contiguous index fastest)
+    const int l_al = DIR == 1 ? threadIdx.x % WAVE : threadIdx.x / TA;
+    const int l_ac = DIR == 1 ? threadIdx.x / WAVE : threadIdx.x % TA;
+    constexpr int STEP_AL = DIR == 1 ? 0 : 256 / TA;
+    constexpr int STEP_AC = DIR == 1 ? 256 / WAVE : 0;
+#pragma unroll
+    for (int k = 0; k < NLD; k++) {
+        const int al = l_al + k * STEP_AL, ac = l_ac + k * STEP_AC;
+        int ga = a0 + al, gb = b0 + ac;
+        ga = ga < a.n_al ? ga : a.n_al - 1;
+        gb = gb < 0 ? 0 : (gb < a.n_ac ? gb : a.n_ac - 1);
+        const long g = base + (long)ga * a.s_al + (long)gb * a.s_ac;
+#pragma unroll
+        for (int m = 0; m < MEQN; m++) tile[stile_at<L, TA>(m, al, ac)] = a.qin[m * a.plane + g];
+        if constexpr (CAPA) tile[stile_at<L, TA>(MEQN, al, ac)] = a.aux[(long)(a.mcapa - 1) * a.plane + g];
+#pragma unroll
+        for (int m = 0; m < NAUX_LDS; m++) tile[stile_at<L, TA>(PAUX + m, al, ac)] = a.aux[aux_idx<RP, DIR>(m) * a.plane + g];
+    }
+    __syncthreads();
+
+    const int lane = threadIdx.x & (WAVE - 1);
+    const int wv = threadIdx.x / WAVE;
+    const int ca = a0 + lane;
+    const bool owned = (ca >= a.mbc) && (ca < a.mbc + a.m_al) && lane >= SHALO && lane < WAVE - SHALO;
+    const bool cfl_ok = (ca >= a.mbc) && (ca <= a.mbc + a.m_al) && lane >= SHALO && lane <= WAVE - SHALO;
+    // stencil positions clamped inside the strip (end lanes never feed a stored value)
+    const int lm2 = lane >= 2 ? lane - 2 : 0, lm1 = lane >= 1 ? lane - 1 : 0;
+    const int lp1 = lane <= WAVE - 2 ? lane + 1 : WAVE - 1, lp2 = lane <= WAVE - 3 ? lane + 2 : WAVE - 1;
+    double cflmax = 0.0;
+    for (int ac = wv; ac < TA; ac += 256 / WAVE) {
+        const int gb = b0 + ac;
+        if (gb >= a.n_ac) break;  // wave-uniform
+        if (gb < a.lo_ac || gb > a.hi_ac) continue;     // lines 0..m+1 only (one ghost layer)
+        double ql[MEQN], qr[MEQN];
+#pragma unroll
+        for (int m = 0; m < MEQN; m++) {
+            const double qm2 = tile[stile_at<L, TA>(m, lm2, ac)], qm1 = tile[stile_at<L, TA>(m, lm1, ac)];
+            const double q0 = tile[stile_at<L, TA>(m, lane, ac)];
+            const double qp1 = tile[stile_at<L, TA>(m, lp1, ac)], qp2 = tile[stile_at<L, TA>(m, lp2, ac)];
+            if constexpr (K > 3) {
+                double qs[2 * K - 1];
+#pragma unroll
+                for (int j = 0; j < 2 * K - 1; j++) {
+                    int l = lane - (K - 1) + j;
+                    l = l < 0 ? 0 : (l > WAVE - 1 ? WAVE - 1 : l);
+                    qs[j] = tile[stile_at<L, TA>(m, l, ac)];
+                }
+                weno_pyweno_k<K>(qs, ql[m], qr[m]);
+            } else if (LIM == 1) tvd2_cell(qm1, q0, qp1, a.mthlim[m < MAX_WAVES_K ? m : MAX_WAVES_K - 1], ql[m], qr[m]);
+            else if (LIM == 2) weno5_pyweno(qm2, qm1, q0, qp1, qp2, ql[m], qr[m]);
+            else weno5_legacy(qm2, qm1, q0, qp1, qp2, ql[m], qr[m]);
+        }
+        double dtdx_c = a.dtd;
+        if constexpr (CAPA) dtdx_c = a.dt / (a.dx * tile[stile_at<L, TA>(MEQN, lane, ac)]);  // flux1.f90:60
+        const double dtdx_l = CAPA ? from_left(dtdx_c) : dtdx_c;
+
+        // both edge states carry the cell's own aux values (flux1.f90:125 passes aux,aux)
+        double auxv[NAUX > 0 ? NAUX : 1];
+        if constexpr (DIR == 1 && NAUX > 0) {
+            const int cc = ca < a.n_al ? ca : a.n_al - 1;
+            const long g = base + (long)gb * a.s_ac + (long)cc * a.s_al;
+#pragma unroll
+            for (int m = 0; m < NAUX; m++) auxv[m] = a.aux[aux_idx<RP, 1>(m) * a.plane + g];
+        } else {
+#pragma unroll
+            for (int m = 0; m < NAUX; m++) auxv[m] = tile[stile_at<L, TA>(PAUX + m, lane, ac)];
+        }
+        Cell cl, cr;
+        if constexpr (NAUX > 0) {
+            cl = RP::template precell<DIR>(ql, a.par, auxv);
+            cr = RP::template precell<DIR>(qr, a.par, auxv);
+        } else {
+            cl = RP::template precell<DIR>(ql, a.par);   // left-edge state of this cell
+            cr = RP::template precell<DIR>(qr, a.par);   // right-edge state of this cell
+        }
+        const Cell crl = struct_from_left(cr);                  // right-edge state of cell i-1
+        double wave[MWAVES][MEQN], s[MWAVES], amdq[MEQN], apdq[MEQN], amdq2[MEQN], apdq2[MEQN];
+        RP::template solve<DIR>(crl, cl, a.par, wave, s, amdq, apdq);       // interface i   (flux1.f90:125)
+        if (cfl_ok) {
+#pragma unroll
+            for (int mw = 0; mw < MWAVES; mw++)
+                cflmax = dmax(dmax(cflmax, dtdx_c * s[mw]), -dtdx_l * s[mw]);
+        }
+        RP::template solve<DIR>(cl, cr, a.par, wave, s, amdq2, apdq2);      // inside cell i (flux1.f90:182)
+        double dq1[MEQN];
+#pragma unroll
+        for (int m = 0; m < MEQN; m++) {  // the shift must run with every lane active
+            const double amdq_r = from_right(amdq[m]);
+            dq1[m] = -(dtdx_c * (amdq_r + apdq[m] + amdq2[m] + apdq2[m]));
+        }
+        if (owned) {
+#pragma unroll
+            for (int m = 0; m < MEQN; m++) tile[stile_at<L, TA>(m, lane, ac)] = dq1[m];
+        }
+    }
+    __syncthreads();
+
+    // cooperative store of dq for the owned interior cells (interior in all three indices)
+    // dq/6 of the SSP33 / Euler-substage combination (op 1): one shared reciprocal, as in sharp_kernel
+    const Recip by_ca(DIR == 3 && a.rk_op == 1 ? a.rk_ca : 1.0);
+#pragma unroll
+    for (int k = 0; k < NLD; k++) {
+        const int al = l_al + k * STEP_AL, ac = l_ac + k * STEP_AC;
+        const int ga = a0 + al, gb = b0 + ac;
+        const bool inner_al = (ga >= a.mbc) && (ga < a.mbc + a.m_al) && al >= SHALO && al < WAVE - SHALO;
+        const bool inner_ac = gb > a.lo_ac && gb < a.hi_ac;     // (inside 0 .. n_ac - 1 by that)
+        if (inner_al && inner_ac && inner_b) {
+            const long g = base + (long)ga * a.s_al + (long)gb * a.s_ac;
+#pragma unroll
+            for (int m = 0; m < MEQN; m++) {
+                const long at = m * a.plane + g;
+                const double v = tile[stile_at<L, TA>(m, al, ac)];
+                const double dq = DIR == 1 ? v : a.qout[at] + v;  // dq = ((0 + dq1d_x) + dq1d_y) + dq1d_z
+                if constexpr (DIR == 3) {
+                    // last pass of a stage: the RK combination of sharpclaw.py:168-206 (same expressions as rk_kernel).
+                    // Branch-free on purpose: with a scalar branch per op the ROCm 7.2 backend left the store base
+                    // of the op-5 path undefined in the 1-D instantiation of sharp_kernel (memory fault at address 0).
+                    double r = dq;
+                    if (a.rk_op != 0) {
+                        const double av = a.rk_a[at], bv = a.rk_b[at];
+                        double quo = by_ca.div(dq);
+#if !PCL_FAST
+                        // an increment deep in the underflow range: the shortcut's residual is no longer exact there, take
+                        // the IEEE quotient (rare, divergent branch; the empty volatile asm keeps it a branch)
+                        if (a.rk_op == 1 && __builtin_fabs(dq) < 0x1p-900 && dq != 0.0) {
+                            asm volatile("");
+                            quo = dq / a.rk_ca;
+                        }
+#endif
+                        const double r1 = av + quo;
+                        const double r2 = a.rk_ca * av + a.rk_cb * (bv + dq);
+                        const double r5 = av + a.rk_cb * bv + a.rk_cc * dq;
+                        r = a.rk_op == 1 ? r1 : (a.rk_op == 2 ? r2 : r5);
+                    }
+                    double *dst = a.rk_op != 0 ? a.rk_d : a.qout;
+                    dst[at] = r;
+                } else {
+                    a.qout[at] = dq;
+                }
+            }
+        }
+    }
+    cfl_publish(a.cfl, cflmax);
+}
+
 // ---- char_decomp = 1 in 1-D: wave-based reconstruction (1d/sharpclaw/flux1.f90:80-107) -------------------------------
 // flux1 first solves the Riemann problems between the cell averages (rp1 on q1d, q1d) and hands the waves to tvd2_wave
 // (lim_type 1, reconstruct.f90:728-806) or weno5_wave (lim_type 2, :393-478), which build the two states of every

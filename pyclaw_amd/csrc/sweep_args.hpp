@@ -214,7 +214,8 @@ struct CellrpSpec {
     int trans = 0;                                  // 1: a transverse body, the code object holds the unsplit kernels too
     int trans3 = 0;                                 // 3-D: 1 an rpt3 body, 2 rpt3 and rptt3; the code object holds pieces3_kernel too
     int form = 0;                                   // PCL_CELLRP_FORM_* bits
-    int lim_type = 0, weno_order = 0, char_decomp = 0;      // a SharpClaw handle (lim_type 0: a classic one)
+    int lim_type = 0, weno_order = 0, char_decomp = 0;      // a SharpClaw handle (lim_type 0: a classic one); with ndim 3 the
+                                                            // three sharp3_kernel passes and nothing else (pcl_cellrp_compile3_sharp)
     int onek = 0;                                   // 1: the code object holds the one-kernel dimension-split 2-D step too
     bool fwave() const { return (form & PCL_CELLRP_FORM_FWAVE) != 0; }
     bool capa() const { return (form & PCL_CELLRP_FORM_CAPA) != 0; }
@@ -333,6 +334,7 @@ PCL_LAUNCHERS
 const RpFacts *rp_facts(int rp);    // null: no built-in solver has this id
 int sweep_tile_max_planes();        // q + aux planes a sweep_kernel tile may hold (TileShape<1/2>::PLANE against 64 KB)
 int sweep3_tile_max_planes();       // q + aux + capa planes a sweep3_kernel tile may hold (Tile3Shape<1..3>::PLANE against 64 KB)
+int sharp3_tile_max_planes();        // q + capa + aux planes a sharp3_kernel tile may hold, one rule for the three passes
 int sharp_tile_max_planes(int ixy, int naux);   // planes a sharp_kernel tile of pass ixy may hold for a solver with naux aux components
 // x-pass tiles [tb_lo,tb_hi) x [ta_lo,ta_hi) that read no ghost cell; false if there are none
 // ntiles[0], ntiles[1] = row tiles / tiles along a row of the x pass

@@ -264,7 +264,10 @@ class CellRiemann(RiemannSolver):
         rp, size = ctypes.c_void_p(), ctypes.c_long(0)
         mode = {'exact': 0, 'fast': 1, 'strict': 2}[math]
         aux = (ctypes.c_int * len(self.aux))(*self.aux) if self.aux else None
-        if self.ndim == 3 and self.rpt3 is not None:
+        if self.ndim == 3 and sharp is not None:        # a SharpCellRiemann3D: (lim_type, weno_order), char_decomp 0
+            _lib.check(_lib.lib().pcl_cellrp_compile3_sharp(self.body.encode(), self.preamble.encode(), self.meqn, self.mwaves,
+                                                            mode, aux, len(self.aux), form, sharp[0], sharp[1], ctypes.byref(rp)))
+        elif self.ndim == 3 and self.rpt3 is not None:
             _lib.check(_lib.lib().pcl_cellrp_compile3t(self.body.encode(), self.rpt3.encode(),
                                                        None if self.rptt3 is None else self.rptt3.encode(),
                                                        self.preamble.encode(), self.meqn, self.mwaves, mode,
@@ -370,7 +373,8 @@ class CellRiemann3D(CellRiemann):
     ``meqn + len(aux) + capa <= MAX_PLANES`` (7; the library derives it from its tile shapes and refuses with its own
     figure).  A solver with ``rpt3`` may exceed it and then serves ``dim_split=False`` alone.
 
-    Not served in 3-D, so there is no keyword for them: f-waves and SharpClaw.  Nor: the unsplit step with a capacity
+    Not served in 3-D, so there is no keyword for them: f-waves and SharpClaw (``SharpClawSolver3D`` takes a
+    ``SharpCellRiemann3D``, a class of its own, below).  Nor: the unsplit step with a capacity
     function, a transverse body with both cells and aux, ``mbc`` other than 2, more than one block."""
 
     MAX_PLANES = 7
@@ -394,6 +398,53 @@ class CellRiemann3D(CellRiemann):
         self.rpt3 = None if rpt3 is None else str(rpt3)
         self.rptt3 = None if rptt3 is None else str(rptt3)
         self.has_transverse = self.rpt3 is not None
+
+
+class SharpCellRiemann3D(CellRiemann):
+    """A user-written Riemann solver for ``SharpClawSolver3D``:
+    ``solver.rp = SharpCellRiemann3D(body, meqn, mwaves, params=(), aux=(), capa=False, preamble="", name=None)``.  The body is
+    Clawpack's rpn3 for one interface under the contract of a ``CellRiemann3D``: it sees ``ql``, ``qr``, ``p[8]``, with
+    ``aux=(...)`` also ``auxl`` / ``auxr``, and the compile-time constant ``ixy``, 1, 2 or 3, and assigns ``wave``, ``s``,
+    ``amdq``, ``apdq``, zero on entry (SharpClaw reads ``s``, ``amdq`` and ``apdq`` alone, solves every interface and the
+    problem inside every cell, both edge states of a cell with the cell's own aux values).  ``setup()`` compiles the x, y and
+    z passes of the library's 3-D SharpClaw kernel around it for the solver's own ``lim_type`` and ``weno_order``
+    (``compile(math, sharp=(lim_type, weno_order))``; both are part of the key): ``lim_type`` 1, 2, 3 at order 5 and orders
+    7..17 with ``lim_type`` 2, for any system.  It is the only way SharpClaw runs in 3-D -- the library's own 3-D solver runs
+    as ``apps.problems.VC_ACOUSTICS_3D_RP`` with ``aux=(0, 1)``.  ``capa=True`` compiles the passes with a capacity function
+    (``state.mcapa``).  The tile of a pass holds ``meqn + capa + len(aux) <= MAX_PLANES`` (8) planes.  ``params`` can be
+    reassigned between steps without a compile.  ``code_size`` is not reported for this class.
+
+    Not served, so there is no keyword for them: f-waves, ``char_decomp``, transverse bodies.  Nor: ``tfluct_solver``, a fused
+    dq source (a ``dq_src`` runs as its own pass), more than one block.  It serves ``SharpClawSolver3D`` and nothing else."""
+
+    MAX_PLANES = 8
+    _NDIMS = (3,)
+
+    def __init__(self, body, meqn, mwaves, params=(), aux=(), capa=False, preamble="", name=None):
+        aux = tuple(aux)
+        planes = int(meqn) + int(bool(capa)) + len(aux)
+        if planes > self.MAX_PLANES:
+            raise ValueError("SharpCellRiemann3D: meqn + capa + len(aux) = %d, the tile of the 3-D SharpClaw passes holds at most "
+                             "%d planes (q components, the capacity function and listed aux components)"
+                             % (planes, self.MAX_PLANES))
+        CellRiemann.__init__(self, body, meqn, mwaves, 3, params=params, preamble=preamble,
+                             name="user" if name is None else name, aux=(), capa=capa, sharpclaw=True)
+        # (the list goes in behind the 1-D / 2-D plane rule of the base class: this class has its own, above)
+        self.aux = tuple(int(k) for k in aux)
+        if any(k < 0 for k in self.aux):
+            raise ValueError("SharpCellRiemann3D: aux lists 0-based components of state.aux, got a negative index in %r" % (self.aux,))
+        if len(set(self.aux)) != len(self.aux):
+            raise ValueError("SharpCellRiemann3D: aux lists a component twice: %r" % (self.aux,))
+
+    def compile(self, math='exact', sharp=None):
+        """``sharp=(lim_type, weno_order)``; a third entry, ``char_decomp``, must be 0."""
+        if sharp is not None:
+            sharp = tuple(int(v) for v in sharp)
+            if len(sharp) not in (2, 3) or (len(sharp) == 3 and sharp[2] != 0):
+                raise NotImplementedError("SharpCellRiemann3D: compile(sharp=(lim_type, weno_order)): char_decomp must be 0 in 3-D, "
+                                          "got %r" % (sharp,))
+            sharp = sharp[:2]
+        return CellRiemann.compile(self, math, sharp=sharp)
 
 
 def get(rp):

@@ -1,7 +1,7 @@
 r"""
 SharpClaw (method-of-lines) solvers on MI355X (reference: src/pyclaw/sharpclaw.py).
 
-``SharpClawSolver1D`` / ``SharpClawSolver2D`` keep the reference's attributes, Runge-Kutta
+``SharpClawSolver1D`` / ``SharpClawSolver2D`` / ``SharpClawSolver3D`` keep the reference's attributes, Runge-Kutta
 schemes (Euler, SSP33, SSP104: sharpclaw.py:152-210) and CFL handling (``CFLError`` inside
 ``dq`` => ``step`` returns False and ``evolve_to_time`` retakes the step).  ``dq_hyperbolic``
 (sharpclaw.py:343-447, 515-563: ``sharpclaw1.flux1`` / ``sharpclaw2.flux2``) runs in the HIP
@@ -29,6 +29,11 @@ solver).
 ``solver.rp`` may be a user-written ``riemann.CellRiemann(..., sharpclaw=True)``: ``setup()`` compiles the SharpClaw kernels
 around its body for this solver's ``lim_type``, ``weno_order`` and ``char_decomp`` (every order 5 .. 17 for any system), on
 one block, with a ``dq_src`` as its own pass.
+
+``SharpClawSolver3D`` runs through such solvers alone: ``solver.rp`` is a ``riemann.SharpCellRiemann3D`` (the library's own
+3-D solver as ``apps.problems.VC_ACOUSTICS_3D_RP``), compiled into the x, y and z passes of ``sharp3_kernel``.  The
+reference has no ``flux3.f90``; a line is swept where both of its transverse indices lie in ``0 .. m+1``, the rule of
+``flux2.f90`` with one more index.  Not served in 3-D: built-in solvers, ``char_decomp``, ``fwave``, decomposed runs.
 """
 import ctypes
 
@@ -339,6 +344,8 @@ class SharpClawSolver(Solver):
         """Allocate RK registers and the device solver (sharpclaw.py:302-323, 474-495)."""
         if self.kernel_language not in ('HIP', 'Fortran'):
             raise Exception("Unrecognized value of solver.kernel_language.")
+        if self.ndim == 3:
+            self._check_3d(solution.states[0])
         if self.weno_order not in (5, 7, 9, 11, 13, 15, 17):
             # reconstruct.f90:112
             raise Exception("ERROR: weno_order must be an odd number between 5 and 17 (inclusive).")
@@ -379,7 +386,8 @@ class SharpClawSolver(Solver):
         if user_rp:
             # the SharpClaw kernels of this one reconstruction around the body; raises with the compiler's log before any
             # device work
-            rp.compile(self.math, sharp=(self.lim_type, self.weno_order, self.char_decomp))
+            rp.compile(self.math, sharp=(self.lim_type, self.weno_order) if self.ndim == 3 else
+                       (self.lim_type, self.weno_order, self.char_decomp))
 
         self._release()
         cfg = _lib.Config()
@@ -433,11 +441,37 @@ class SharpClawSolver(Solver):
     def _check_user_rp(self, rp, state):
         """What a user-written Riemann solver (riemann.CellRiemann) asks of a SharpClaw solver, each refusal with its reason.
         (lim_type, weno_order, char_decomp and tfluct_solver were checked above, as for a built-in solver.)"""
+        if isinstance(rp, riemann.SharpCellRiemann3D) and self.ndim != 3:
+            raise NotImplementedError("SharpCellRiemann3D: this solver is compiled into the three passes of the 3-D SharpClaw "
+                                      "kernel and serves SharpClawSolver3D alone; %s takes a CellRiemann(..., ndim=%d, "
+                                      "sharpclaw=True)" % (type(self).__name__, self.ndim))
+        if self.ndim == 3 and not isinstance(rp, riemann.SharpCellRiemann3D):
+            raise NotImplementedError("SharpClawSolver3D takes a SharpCellRiemann3D, compiled into the three passes of the 3-D "
+                                      "SharpClaw kernel; a %s is compiled into %s" % (type(rp).__name__,
+                                      "the classic 3-D sweeps and serves ClawSolver3D" if rp.ndim == 3 else "the 1-D and 2-D kernels"))
         if not rp.sharpclaw:
             raise NotImplementedError("CellRiemann: the SharpClaw solvers are served by a solver written with sharpclaw=True "
                                       "(compiled into the SharpClaw kernels); without it a user-written Riemann solver is "
                                       "compiled into the classic sweep kernel only (ClawSolver1D / ClawSolver2D)")
         rp.check_solver(self, state)
+
+    def _check_3d(self, state):
+        """What SharpClaw in 3-D does not serve, each refusal with its reason, before anything is compiled."""
+        from . import parallel
+        if self.char_decomp != 0:
+            raise NotImplementedError("SharpClawSolver3D: char_decomp = %r is not served in 3-D (char_decomp must be 0: the "
+                                      "wave-based reconstruction is 1-D, and 2 / 3 need a user evec routine)" % (self.char_decomp,))
+        if self.tfluct_solver:
+            raise NotImplementedError("SharpClawSolver3D: tfluct_solver is not served (the reference's tfluct.f90 is a stub)")
+        if self.fwave:
+            raise NotImplementedError("SharpClawSolver3D: fwave = True is not served: the 3-D SharpClaw kernel has no f-wave form")
+        if self.rp is not None and not isinstance(riemann.get(self.rp), riemann.CellRiemann):
+            raise NotImplementedError("SharpClawSolver3D: no SharpClaw kernel of a built-in 3-D solver is instantiated; SharpClaw "
+                                      "in 3-D runs solvers compiled at run time -- the library's own as "
+                                      "SharpCellRiemann3D(problems.VC_ACOUSTICS_3D_RP, 4, 2, aux=(0, 1))")
+        if state.decomp is not None and parallel.world_size() > 1:
+            raise NotImplementedError("SharpClawSolver3D: a decomposed run (more than one rank) is not served: a user-written "
+                                      "solver runs on one block")
 
     def _custom_bc(self, state, dim, idim, side, fn):
         # Python custom BCs on a stage: same strip protocol as the base class, `state` carries stage time
@@ -458,3 +492,13 @@ class SharpClawSolver2D(SharpClawSolver):
     def __init__(self, data=None):
         self.ndim = 2
         super(SharpClawSolver2D, self).__init__(data)
+
+
+class SharpClawSolver3D(SharpClawSolver):
+    """SharpClaw evolution routine in 3D (upstream PyClaw's ``SharpClawSolver3D``; the reference has none).  Same attributes
+    and defaults as the 2-D class; ``solver.rp`` is a ``riemann.SharpCellRiemann3D`` (see the module text).  ``cfl_max`` and
+    ``cfl_desired`` keep the SharpClaw defaults 2.5 / 2.45 in 3-D too: nothing is changed silently."""
+
+    def __init__(self, data=None):
+        self.ndim = 3
+        super(SharpClawSolver3D, self).__init__(data)
